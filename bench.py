@@ -79,6 +79,36 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_nbest(out_dir, nbest, rows, w2i, topN=10):
+    """--dump-outputs: the n-best lists a caller of the timed path received for the timed region's last step, as arrays:
+      nbest_scores.npy  float64 [sentences, topN]             path scores; NaN past the end of a sentence's list
+      nbest_words.npy   float64 [sentences, topN, max words]  each path's words as lexicon indices (Decoder.w2i); -1 past the path's
+                                                              end, -2 for a word outside the lexicon
+      nbest_rows.npy    float64 [sentences]                   the sentence of each row (index into the step's input)
+    Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the sentences is written."""
+    import numpy as np
+    n = len(nbest)
+    max_words = max([len(w) for r in nbest for _s, w in r] + [1])
+    per_row = 8 * (1 + topN + topN * max_words)
+    budget = DUMP_LIMIT_BYTES - 1024               # (the three .npy headers)
+    keep = np.arange(n)
+    if n * per_row > budget:
+        keep = np.sort(np.random.RandomState(0).choice(n, budget // per_row, replace=False))
+    scores = np.full((keep.size, topN), np.nan)
+    words = np.full((keep.size, topN, max_words), -1.0)
+    for i, j in enumerate(keep):
+        for k, (s, w) in enumerate(nbest[j][:topN]):
+            scores[i, k] = s
+            words[i, k, :len(w)] = [w2i.get(x, -2) for x in w]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "nbest_scores.npy"), scores)
+    np.save(os.path.join(out_dir, "nbest_words.npy"), words)
+    np.save(os.path.join(out_dir, "nbest_rows.npy"), np.asarray(rows, dtype=np.float64)[keep])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -99,6 +129,8 @@ def main():
     # debugging the N > 1 control flow on a one-GPU box: every rank on device 0, control-plane collectives over gloo
     ap.add_argument("--debug-shared-gpu", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-legs", action="store_true", help="config 2 only: skip the short configs[2] / configs[3] legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the n-best lists of the last timed step as DIR/*.npy (rank 0; see dump_nbest)")
     args = ap.parse_args()
     if args.fixture is None:
         args.fixture = "mid-vtable" if args.config == 2 else "mid-tied"
@@ -109,7 +141,7 @@ def main():
 
     import numpy as np
     import torch
-    import jlm_amd          # before the HIP runtime initialises: it defaults GPU_MAX_HW_QUEUES (jlm_amd/__init__.py)
+    import jlm_amd
     import __graft_entry__ as ge
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -170,7 +202,8 @@ def main():
 
     # ------------------------------------------------------------------------------------------ config 5 leg
     def run_config5(dec5, alphabet5, passes):
-        """BASELINE configs[4]: 8 192 sentences dealt over the ranks, strong scaling.  -> (seconds, chars, n_mine)"""
+        """BASELINE configs[4]: 8 192 sentences dealt over the ranks, strong scaling.  -> (seconds, chars, n_mine, (this rank's sentence
+        indices, their n-best lists) of the last pass)"""
         sents5 = synth.make_sentences(CONFIG5_SENTENCES, args.length, seed=5555, alphabet=alphabet5)   # the same set on every rank
         dec5.max_batch = 1024
         idx, _res = shard.decode_sharded(dec5, sents5, rank, world, beam_width=args.beam)             # untimed pass (plans, streams)
@@ -184,7 +217,7 @@ def main():
         assert len(res) == len(idx) and all(len(r) > 0 for r in res)
         n_all = int(round(sum_over_ranks(float(len(idx)))))
         assert n_all == CONFIG5_SENTENCES, "the shards must cover the whole set exactly once"
-        return dt, sum(len(s) for s in sents5), len(idx)
+        return dt, sum(len(s) for s in sents5), len(idx), (idx, res)
 
     def kernel_stats(durs, rows, name, flops_per_row):
         d = np.asarray(durs.get(name, []), dtype=np.float64)
@@ -368,7 +401,10 @@ def main():
         for _ in range(max(0, args.warmup - 1)):
             shard.decode_sharded(dec, synth.make_sentences(1024 * world, args.length, seed=77, alphabet=alphabet), rank, world,
                                  beam_width=args.beam)
-        dt, chars, n_mine = run_config5(dec, alphabet, args.steps)
+        dt, chars, n_mine, (idx5, res5) = run_config5(dec, alphabet, args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_nbest(args.dump_outputs, res5, idx5, dec.w2i)
+        del res5
         value = chars * args.steps / dt
         sents = synth.make_sentences(1024, args.length, seed=5555 + rank, alphabet=alphabet)
         lat = BatchLattice(dec._builder, sents, args.beam)
@@ -454,25 +490,18 @@ def main():
                                             "12 - warmup, 4) = %d steps each, repeated until two successive calls agree within 3 %% "
                                             "(first-touch of the heap, the page-locked blocks and the plans a call of that size needs)"
                                             % (n_settle, settle))
-        # The timed region: EXACTLY K steps between barrier + synchronize on both sides, MAX over ranks -- taken three times in a
-        # row, the MEDIAN reported (`ms_per_step_repeats` lists all three): a 20-step region is 40 ms, and single regions on one
-        # box spread by 8 %, more than most changes the line is meant to show.
-        dts, cpus = [], []
-        for _rep in range(3):
-            barrier()
-            c0 = time.process_time()
-            t0 = time.perf_counter()
-            out = dec.decode_batch(sents * args.steps, beam_width=args.beam, **dkw)      # K steps = K pipelined 256-sentence batches
-            barrier()
-            dts.append(max_over_ranks(time.perf_counter() - t0))
-            cpus.append(time.process_time() - c0)
-            assert len(out) == len(sents) * args.steps and all(len(r) > 0 for r in out)
-            if _rep < 2:
-                del out
-        _mid = sorted(range(3), key=lambda i_: dts[i_])[1]
-        dt, cpu_s = dts[_mid], cpus[_mid]
-        line_extra["ms_per_step_repeats"] = [round(x / args.steps * 1e3, 3) for x in dts]
-        line_extra["ms_per_step_note"] = "three consecutive timed regions of `steps` steps each; `value` / `ms_per_step` are the median one"
+        # The timed region: EXACTLY K steps between barrier + synchronize on both sides, MAX over ranks.  Single 20-step regions
+        # (40 ms) on one box spread by 8 %: a steadier figure takes a larger --steps, not repeats.
+        barrier()
+        c0 = time.process_time()
+        t0 = time.perf_counter()
+        out = dec.decode_batch(sents * args.steps, beam_width=args.beam, **dkw)      # K steps = K pipelined 256-sentence batches
+        barrier()
+        dt = max_over_ranks(time.perf_counter() - t0)
+        cpu_s = time.process_time() - c0
+        assert len(out) == len(sents) * args.steps and all(len(r) > 0 for r in out)
+        if args.dump_outputs and rank == 0:
+            dump_nbest(args.dump_outputs, out[-len(sents):], range(len(sents)), dec.w2i)
         line_extra["host_cpu_ms_per_step"] = round(cpu_s / args.steps * 1e3, 3)
         line_extra["host_cpu_note"] = ("process CPU time (all threads of this rank: calling thread, lattice workers, HIP runtime) per "
                                        "step of the timed region; %.2f CPUs busy on average, %d usable" % (cpu_s / dt, jlm_amd.usable_cpus()))
@@ -590,7 +619,7 @@ def main():
         # ------------------------------------------------------------------ extra leg: BASELINE configs[4] at this N
         if not args.no_config5 and args.decoder == "static":
             _r5, _c5, alphabet5, dec5 = make_decoder("mid-tied", "static")
-            dt5, chars5, n5 = run_config5(dec5, alphabet5, args.config5_passes)
+            dt5, chars5, n5 = run_config5(dec5, alphabet5, args.config5_passes)[:3]
             line_extra["config5"] = {
                 "workload": "BASELINE configs[4]: tied softmax V=50k, beam=10, ONE set of %d sentences x %d kana sharded over %d GPU(s) "
                             "(jlm_amd.shard.decode_sharded), %d on this rank in chunks of 1 024; strings in -> n-best strings out" % (
@@ -672,7 +701,7 @@ def main():
                 d4 = json.loads(pr.stdout.strip().splitlines()[-1])
                 line_extra["config4"] = {
                     "workload": what4, "value": d4["value"], "unit": "chars/s", "n_gpus": 1, "steps": d4["steps"],
-                    "untimed_steps": d4.get("untimed_steps"), "ms_per_step": d4["ms_per_step"], "ms_per_step_repeats": d4.get("ms_per_step_repeats"),
+                    "untimed_steps": d4.get("untimed_steps"), "ms_per_step": d4["ms_per_step"],
                     "device_resident_ms_per_step": d4.get("device_resident_ms_per_step"),
                     "timed": "strings -> strings; `python bench.py --fixture mid-tied --decoder dynamic --steps 40 --warmup 3 --no-legs` in a process of its own",
                     "dominant_kernel": {k: (d4.get("roofline") or {}).get(k) for k in ("kernel", "avg_launch_ms", "note")},

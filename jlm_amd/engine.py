@@ -200,7 +200,7 @@ class DecodeEngine:
         # tools/probes/skip_kernel.sh) and the chains of three batches fill each other's gaps better than those of two; side
         # streams on top (six streams, fork / join events across them) cost more than the overlap buys: 3.3 ms.
         # four streams need more than ROCm's default of four hardware queues (one is the null stream's): there they run 2.31 ms per
-        # step against 2.06 with three (jlm_amd/__init__.py sets GPU_MAX_HW_QUEUES=8 when it still can)
+        # step against 2.06 with three (GPU_MAX_HW_QUEUES >= 8, set by the host process: jlm_amd/__init__.py)
         from . import hw_queues_ok as _hwq
         self.n_streams = max(1, int(os.environ.get("JLM_STREAMS", "4" if _hwq() else "3")))
         # CU share of the vocabulary kernel beside other batches in flight: none since round 4 (the step is flat in it with four batches

@@ -152,23 +152,3 @@ def test_eval_harness_on_a_character_model(batch, fx, fake, golden_char, monkeyp
     gold = golden_char[name]
     assert [ln for ln in buf.getvalue().splitlines() if ln.startswith("best_hit")] == gold["stdout_hits"]
     assert _eval_body(os.path.join("eval", gold["log_name"])) == gold["log_body"]
-
-
-@pytest.mark.skipif(not __import__("os").path.exists("/root/reference/decoder/eval.py"), reason="the reference is only present in the build container")
-def test_reference_eval_py_runs_unchanged_on_a_character_model(fx, fake, golden_char, monkeypatch, tmp_path):
-    """the reference's eval.py, unchanged, over compat/ (``from decoder import Decoder, CharRNNDecoder``, ``from train.data import Vocab,
-    CharVocab``): the class it gets is jlm_amd's"""
-    import contextlib, io, os
-    name, fixture, argv = gc.CHAR_EVAL_CASE
-    f = fx(fixture)
-    synth.write_test_corpus(f["root"], f["lexicon"], f["cfg"]["vocab_size"], **gc.EVAL_CORPUS)
-    jconfig.set_root(f["root"])
-    monkeypatch.chdir(tmp_path)
-    os.makedirs("eval")
-    from tools import run_reference_eval
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf), contextlib.redirect_stderr(io.StringIO()):
-        run_reference_eval.run("/root/reference/decoder/eval.py", argv)
-    gold = golden_char[name]
-    assert [ln for ln in buf.getvalue().splitlines() if ln.startswith("best_hit")] == gold["stdout_hits"]
-    assert _eval_body(os.path.join("eval", gold["log_name"])) == gold["log_body"]

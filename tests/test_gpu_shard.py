@@ -32,7 +32,7 @@ def _worker(rank, world, port, root, sents, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     os.environ["LOCAL_WORLD_SIZE"] = str(world)
-    import jlm_amd  # noqa: F401  (defaults GPU_MAX_HW_QUEUES before the HIP runtime starts)
+    import jlm_amd  # noqa: F401
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
