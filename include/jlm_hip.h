@@ -517,6 +517,43 @@ int jlm_decode_frames(const jlm_decode_model *model_host, const jlm_decode_plan 
 int jlm_lse_probe(const jlm_decode_model *model_host, const int *rowlist, const int *prev, const int *word, int steps, int rows,
                   void *h, float *c, float *T, void *Tm, int ld_tm, int form, float *part, int max_parts, void *stream);
 
+
+/* ------------------------------------------------------------------------
+ * Teacher-forced scoring (LSTM_Model.score / score_streams, jlm_amd/score.py): the per-word -log p of many word sequences at
+ * once -- what the reference's LSTM_Model.evaluate (decoder/model.py:200-206) computes one predict() at a time, and what its
+ * training script reports as test perplexity (train/model.py:262-297 over train/utils.py:17-31 corpus_iterator).
+ * Row r < n_rows is one sequence (or one stream).  Step t consumes word[t][r] and is scored on target[t][r]:
+ *   nll = lse(T_r) - (T_r[t_off:t_off+k] . B_seg[w - v_start] + b2[w]),  w = target[t][r]   (self_norm models: nll = -y)
+ * The rows live at step t are the prefix r < n_live[t] (the caller sorts sequences by length, longest first).
+ * State: two row sets h[2] / c[2] ([n_rows, H] each; split rows on a split-row model, plain f32 otherwise, as jlm_decode_plan.h /
+ * .c), used ping-pong -- step t reads set t % 2 and writes set (t + 1) % 2 (never in place: several workgroups of the step read a
+ * row another one writes).  Step 0 continues row prev0[r] of set 0 (-1: the zero state); the state after the last step is in set
+ * n_steps % 2. */
+typedef struct {
+    int n_rows, n_steps;
+    void *h[2]; float *c[2];        /* [n_rows, H] state row sets */
+    float *T;                       /* [n_rows, ldt] f32 (untied split-row model: the state's f32 copy; untied f32 model: unused) */
+    void *Tm; int ld_tm;            /* packed rows for a normaliser on mixed rows (as jlm_decode_plan.Tm), or NULL */
+    float *part; int max_parts;     /* [max_parts][n_rows][2] normaliser slices (as jlm_decode_plan.part) */
+    const int *rows;                /* [n_rows] device: 0, 1, ..., n_rows - 1 (the compact row list; also the prev of steps t >= 1) */
+    const int *prev0;               /* [n_rows] device: the row of set 0 that step 0 continues, -1 = zero state */
+    const int *word, *target;       /* [n_steps][n_rows] device */
+    const int *n_live;              /* [n_steps] device */
+    const int *n_live_host;         /* [n_steps] host copy (bounds the launches' grids), or NULL: n_rows */
+    double *nll_seq;                /* [n_rows] device: += the row's nll of every step (the caller zeroes it) */
+    double *nll_tok;                /* [n_steps][n_rows] device, or NULL: the nll of each (step, live row) */
+    int *flags;                     /* one device int or NULL: |= 1 when a log-normaliser is not finite (as jlm_beam_state.flags) */
+} jlm_score_plan;
+
+/* Enqueues n_steps x [LSTM step (jlm_lstm_step_xg | jlm_lstm_step), T projection (not on untied models), the full-vocabulary
+ * normaliser exactly as jlm_decode_frames launches it for kind 0 (none on self_norm models), score_fold_kernel (the slices folded
+ * in the beam step's order and arithmetic, the target's logit in jlm_edge_logits' f32 arithmetic, nll in f64)].  No host
+ * synchronisation.  events (may be NULL): JLM_SCORE_EVENTS_PER_STEP * n_steps hipEvent_t (timing enabled), recorded on `stream`
+ *   [0] before the LSTM step  [1] after it  [2] after the T projection  [3] after the normaliser  [4] after the fold.
+ * Returns 0, -2 for a model outside the frame loop's shapes, -1 / a hipError_t as the launchers do. */
+#define JLM_SCORE_EVENTS_PER_STEP 5
+int jlm_score_frames(const jlm_decode_model *model_host, const jlm_score_plan *plan_host, void *stream, void *const *events);
+
 #ifdef __cplusplus
 }
 #endif

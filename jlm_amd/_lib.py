@@ -62,6 +62,16 @@ class DecodePlan(Structure):
                 ("di_wwords", c_void_p), ("sg_wword", c_void_p), ("Tm", c_void_p), ("ld_tm", c_int)]
 
 
+
+class ScorePlan(Structure):
+    """jlm_score_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("T", c_void_p),
+                ("Tm", c_void_p), ("ld_tm", c_int), ("part", c_void_p), ("max_parts", c_int),
+                ("rows", c_void_p), ("prev0", c_void_p), ("word", c_void_p), ("target", c_void_p),
+                ("n_live", c_void_p), ("n_live_host", POINTER(c_int)),
+                ("nll_seq", c_void_p), ("nll_tok", c_void_p), ("flags", c_void_p)]
+
+
 P = c_void_p
 _SIGS = {
     "jlm_abi_version": ([], c_int),
@@ -105,6 +115,7 @@ _SIGS = {
     "jlm_softmax_rows": ([P, P, c_int, c_int, c_int, c_int, P], c_int),
     "jlm_decode_frames": ([POINTER(DecodeModel), POINTER(DecodePlan), POINTER(Lattice), POINTER(BeamState), P, P, P], c_int),
     "jlm_lse_probe": ([POINTER(DecodeModel), P, P, P, c_int, c_int, P, P, P, P, c_int, c_int, P, c_int, P], c_int),
+    "jlm_score_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), P, P], c_int),
 }
 EXPORTS = sorted(_SIGS)
 

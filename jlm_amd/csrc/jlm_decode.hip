@@ -49,6 +49,106 @@ static inline bool jlm_model_mx6(const jlm_decode_model *m) {
 }
 #define JLM_PACK_T_MIXED(m) (jlm_model_mx6(m) ? jlm_pack_t_mixed6 : jlm_pack_t_mixed)
 
+// ---- the full-vocabulary normaliser (kind 0) of one step's rows, shared by the frame loop and the scoring loop (jlm_score_frames).
+// Two halves: full_lse_pack right behind the T projection (the packed rows of the mixed segments, if the model has them), and
+// full_lse_run after it (the decode enqueues its edge logits in between), which leaves the (max, sum exp) slices in `part`.
+// a segment with k > 256 (untied models: k = H) is outside the rows-stationary normalisers: one tile GEMM per segment
+// with a per-tile log-sum-exp epilogue (jlm_vocab_lse_partials), its slices folded by the consumer of the slices
+static bool full_lse_tile_form(const jlm_decode_model *m) {
+    if (m->self_norm) return false;
+    for (int i = 0; i < m->n_segs; ++i)
+        if (m->segs[i].k > 256) return true;
+    return false;
+}
+
+struct FullLse {
+    bool tile_form = false, hybrid = false, all_mixed = false;
+};
+
+// segments of the full-vocabulary normaliser on mixed rows: the step's live rows are packed once, here, behind T
+// (round 5: an untied model at H = 512 -- T is the state's f32 copy, one segment of k = 512 -- runs jlm_vocab_lse_mixed's wide
+//  one-row-set form instead of the tile GEMM below when its vocabulary matrix exists as mixed rows)
+static int full_lse_pack(const jlm_decode_model *m, const float *T, const int *rows, int bound, const int *ndev, void *Tm, int ld_tm,
+                         bool skip_pack, FullLse &fl, void *stream) {
+    fl = FullLse();
+    fl.tile_form = full_lse_tile_form(m);
+    if (m->self_norm) return 0;
+    const bool untied_mixed = fl.tile_form && m->untied && m->n_segs == 1 && m->mixed_segs && m->mixed_segs[0].B && Tm;
+    if ((!fl.tile_form && m->mixed_segs && m->split_segs && Tm) || untied_mixed) {
+        jlm_segment only[JLM_MAX_SEGMENTS];
+        float only_ts[JLM_MAX_SEGMENTS];
+        int n_only = 0;
+        for (int i = 0; i < m->n_segs; ++i)
+            if (m->mixed_segs[i].B) { only[n_only] = m->mixed_segs[i]; only_ts[n_only++] = m->mixed_t_scale[i]; }
+        if (n_only) {
+            if (jlm_mixed_t_stride(only, n_only) != ld_tm) return -1;
+            if (!skip_pack) JLM_TRY(JLM_PACK_T_MIXED(m)(only, only_ts, n_only, T, m->ldt, rows, bound, ndev, Tm, ld_tm, stream));
+            fl.hybrid = true;
+            fl.all_mixed = n_only == m->n_segs;
+            // (ABI 10) a segment whose head stays on split rows: the launch over both formats
+            if (fl.all_mixed && m->mixed_head_split && m->split_segs)
+                for (int i = 0; i < m->n_segs; ++i)
+                    if (m->mixed_head_split[i] > 0) fl.all_mixed = false;
+        }
+    }
+    return 0;
+}
+
+// -> *n_parts slices [n][ld_part] (indexed by compact row).  bound: static bound of the live rows (the column count follows it);
+// tile_rows: the row bound of the tile form's launches; h: the state rows the step wrote (untied split-row models read them).
+static int full_lse_run(const jlm_decode_model *m, const FullLse &fl, const float *T, const void *h, const void *Tm, int ld_tm,
+                        const int *rows, int ld_part, int bound, int tile_rows, const int *ndev, float *part, int max_parts,
+                        int lse_cu_share_pct, int *n_parts_out, void *stream) {
+    *n_parts_out = 0;
+    if (fl.tile_form && !fl.all_mixed) {
+        int n_parts = 0;
+        for (int i = 0; i < m->n_segs; ++i) {
+            const jlm_segment &sg = m->segs[i];
+            // capacity is checked BEFORE the launch that would write the slices (one per 128-word tile)
+            if (n_parts + (sg.v_end - sg.v_start + 127) / 128 > max_parts) return -1;
+            int r = (m->untied && m->untied_split && m->split_lstm)
+                        ? jlm_vocab_lse_partials_split(m->untied_split, m->H, sg.v_end - sg.v_start, m->H, h, m->H, rows,
+                                                       m->b2 + sg.v_start, m->untied_descale, part, ld_part, n_parts,
+                                                       tile_rows, ndev, stream)
+                        : jlm_vocab_lse_partials(sg.B, sg.ldb, sg.v_end - sg.v_start, sg.k, T + sg.t_off, m->ldt, rows,
+                                                 m->b2 + sg.v_start, part, ld_part, n_parts, tile_rows, ndev, stream);
+            if (r < 0) return r;
+            n_parts += r;
+        }
+        if (n_parts > max_parts) return -1;
+        *n_parts_out = n_parts;
+        return 0;
+    }
+    // the share of the chip this batch's normaliser takes: its range count is capped so that ranges x row tiles
+    // (one 8-wave workgroup per CU each) fill that share; the launcher rounds down to a multiple of 8 ranges
+    int cap = max_parts;
+    if (lse_cu_share_pct > 0 && lse_cu_share_pct < 100) {
+        const int n_ptiles = (bound + 255) / 256;
+        int c = 256 * lse_cu_share_pct / 100 / n_ptiles;
+        if (c < 1) c = 1;
+        c += m->n_segs - 1;            // slices = columns + the segment boundaries columns straddle
+        if (c < cap) cap = c;
+    }
+    int r = -2;
+    if (fl.all_mixed)      // every segment on mixed rows (lse_fixed_ref: without a running maximum where the kernel has such a form)
+        r = (m->lse_fixed_ref ? jlm_vocab_lse_mixed_fr : jlm_vocab_lse_mixed)(m->mixed_segs, m->mixed_descale, m->mixed_s8, m->mixed_bias2,
+                                                                             m->n_segs, Tm, ld_tm, part, ld_part, cap, bound, ndev, stream);
+    else if (fl.hybrid)    // -2: a shape the hybrid kernel does not host -- the split rows of every segment exist
+        r = jlm_vocab_lse_hybrid(m->split_segs, m->split_t_scale, m->split_descale, m->split_bias_col, m->mixed_segs,
+                                 m->mixed_descale, m->mixed_s8, m->mixed_head_split, m->n_segs, m->b2, T, m->ldt, Tm,
+                                 ld_tm, rows, part, ld_part, cap, bound, ndev, stream);
+    if (r == -2)
+        r = m->split_segs
+                ? jlm_vocab_lse_split(m->split_segs, m->split_t_scale, m->split_descale, m->split_bias_col,
+                                      m->n_segs, m->b2, T, m->ldt, rows, part, ld_part, cap, bound,
+                                      ndev, stream)
+                : jlm_vocab_lse_stationary(m->segs, m->n_segs, m->b2, T, m->ldt, rows, part, ld_part,
+                                           max_parts, bound, ndev, stream);
+    if (r < 0) return r;
+    *n_parts_out = r;
+    return 0;
+}
+
 extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_plan *p, const jlm_lattice *lat,
                                  const jlm_beam_state *st_in, void *stream, void *side_stream, void *const *events) {
     const int B = lat->n_sent, beam = lat->beam, F = lat->n_frames;
@@ -56,12 +156,6 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
     const bool dynamic = p->kind == 2, select = p->kind == 1, full = p->kind == 0;
     const int mode = m->self_norm ? 1 : (dynamic ? 2 : 0);
     const bool wl_split = m->split_segs != nullptr && m->n_segs == 1 && beam <= 64;
-    // a segment with k > 256 (untied models: k = H) is outside the rows-stationary normalisers: one tile GEMM per segment
-    // with a per-tile log-sum-exp epilogue (jlm_vocab_lse_partials), its slices folded by the next frame's beam step
-    bool tile_form = false;
-    if (full && !m->self_norm)
-        for (int i = 0; i < m->n_segs; ++i)
-            if (m->segs[i].k > 256) tile_form = true;
     jlm_beam_state st = *st_in;
     hipStream_t main_s = (hipStream_t)stream, side_s = events ? nullptr : (hipStream_t)side_stream;
     // events != NULL: JLM_EVENTS_PER_FRAME timing events per frame, recorded on `stream` (no side stream then, so that
@@ -144,28 +238,10 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                 JLM_TRY(jlm_gemm_nt((const float *)p->h, m->H, rows, m->pmt, m->H, nullptr, p->T, m->ldt, rows, nullptr, rmax,
                                     m->n_t, m->H, ndev, stream));
         }
-        // segments of the full-vocabulary normaliser on mixed rows: this frame's live rows are packed once, here, behind T
-        // (round 5: an untied model at H = 512 -- T is the state's f32 copy, one segment of k = 512 -- runs jlm_vocab_lse_mixed's wide
-        //  one-row-set form instead of the tile GEMM below when its vocabulary matrix exists as mixed rows)
-        bool hybrid = false, all_mixed = false;
-        const bool untied_mixed = tile_form && m->untied && m->n_segs == 1 && m->mixed_segs && m->mixed_segs[0].B && p->Tm;
-        if (full && !m->self_norm && ((!tile_form && m->mixed_segs && m->split_segs && p->Tm) || untied_mixed)) {
-            jlm_segment only[JLM_MAX_SEGMENTS];
-            float only_ts[JLM_MAX_SEGMENTS];
-            int n_only = 0;
-            for (int i = 0; i < m->n_segs; ++i)
-                if (m->mixed_segs[i].B) { only[n_only] = m->mixed_segs[i]; only_ts[n_only++] = m->mixed_t_scale[i]; }
-            if (n_only) {
-                if (jlm_mixed_t_stride(only, n_only) != p->ld_tm) return -1;
-                if (!JLM_SKIPPED(32)) JLM_TRY(JLM_PACK_T_MIXED(m)(only, only_ts, n_only, p->T, m->ldt, rows, f == 0 ? B : rmax, ndev, p->Tm, p->ld_tm, stream));
-                hybrid = true;
-                all_mixed = n_only == m->n_segs;
-                // (ABI 10) a segment whose head stays on split rows: the launch over both formats
-                if (all_mixed && m->mixed_head_split && m->split_segs)
-                    for (int i = 0; i < m->n_segs; ++i)
-                        if (m->mixed_head_split[i] > 0) all_mixed = false;
-            }
-        }
+        // the packed rows of the normaliser's mixed segments, behind T (the normaliser itself runs after the edge logits: full_lse_run);
+        // slices of a tile-form normaliser (k > 256) are folded by the next frame's beam step like the others
+        FullLse fl;
+        if (full) JLM_TRY(full_lse_pack(m, p->T, rows, f == 0 ? B : rmax, ndev, p->Tm, p->ld_tm, JLM_SKIPPED(32), fl, stream));
         const int cell = f * B;
         void *est = stream;
         if (side_s) {          // the edge logits need only T: they run beside the normaliser
@@ -191,54 +267,9 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                 JLM_TRY(wl_lse(p->g0 + cell, p->cidx + cell, p->di_words, p->di_off, p->di_idx, 2 * cell, 0, B, p->di_max));
             else if (select)
                 JLM_TRY(wl_lse(p->g0 + cell, p->cidx + cell, p->vs_words, p->vs_off, p->sidx, 0, 0, B, p->vs_max));
-            else if (tile_form && !all_mixed) {
-                int n_parts = 0;
-                for (int i = 0; i < m->n_segs; ++i) {
-                    const jlm_segment &sg = m->segs[i];
-                    // capacity is checked BEFORE the launch that would write the slices (one per 128-word tile)
-                    if (n_parts + (sg.v_end - sg.v_start + 127) / 128 > p->max_parts) return -1;
-                    int r = (m->untied && m->untied_split && m->split_lstm)
-                                ? jlm_vocab_lse_partials_split(m->untied_split, m->H, sg.v_end - sg.v_start, m->H, p->h, m->H, rows,
-                                                               m->b2 + sg.v_start, m->untied_descale, p->part, rmax, n_parts,
-                                                               rmax, ndev, stream)
-                                : jlm_vocab_lse_partials(sg.B, sg.ldb, sg.v_end - sg.v_start, sg.k, p->T + sg.t_off, m->ldt, rows,
-                                                         m->b2 + sg.v_start, p->part, rmax, n_parts, rmax, ndev, stream);
-                    if (r < 0) return r;
-                    n_parts += r;
-                }
-                if (n_parts > p->max_parts) return -1;
-                pending_parts = n_parts;
-            } else {
-                // frame 0 has one row per sentence: the bound lets the kernel cut the vocabulary into more ranges
-                const int bound = f == 0 ? B : rmax;
-                // the share of the chip this batch's normaliser takes: its range count is capped so that ranges x row tiles
-                // (one 8-wave workgroup per CU each) fill that share; the launcher rounds down to a multiple of 8 ranges
-                int cap = p->max_parts;
-                if (p->lse_cu_share_pct > 0 && p->lse_cu_share_pct < 100) {
-                    const int n_ptiles = (bound + 255) / 256;
-                    int c = 256 * p->lse_cu_share_pct / 100 / n_ptiles;
-                    if (c < 1) c = 1;
-                    c += m->n_segs - 1;            // slices = columns + the segment boundaries columns straddle
-                    if (c < cap) cap = c;
-                }
-                int r = -2;
-                if (all_mixed)      // every segment on mixed rows (lse_fixed_ref: without a running maximum where the kernel has such a form)
-                    r = (m->lse_fixed_ref ? jlm_vocab_lse_mixed_fr : jlm_vocab_lse_mixed)(m->mixed_segs, m->mixed_descale, m->mixed_s8, m->mixed_bias2,
-                                                                                         m->n_segs, p->Tm, p->ld_tm, p->part, rmax, cap, bound, ndev, stream);
-                else if (hybrid)    // -2: a shape the hybrid kernel does not host -- the split rows of every segment exist
-                    r = jlm_vocab_lse_hybrid(m->split_segs, m->split_t_scale, m->split_descale, m->split_bias_col, m->mixed_segs,
-                                             m->mixed_descale, m->mixed_s8, m->mixed_head_split, m->n_segs, m->b2, p->T, m->ldt, p->Tm,
-                                             p->ld_tm, rows, p->part, rmax, cap, bound, ndev, stream);
-                if (r == -2)
-                    r = m->split_segs
-                            ? jlm_vocab_lse_split(m->split_segs, m->split_t_scale, m->split_descale, m->split_bias_col,
-                                                  m->n_segs, m->b2, p->T, m->ldt, rows, p->part, rmax, cap, bound,
-                                                  ndev, stream)
-                            : jlm_vocab_lse_stationary(m->segs, m->n_segs, m->b2, p->T, m->ldt, rows, p->part, rmax,
-                                                       p->max_parts, bound, ndev, stream);
-                if (r < 0) return r;
-                pending_parts = r;
-            }
+            else      // frame 0 has one row per sentence: the bound lets the kernel cut the vocabulary into more ranges
+                JLM_TRY(full_lse_run(m, fl, p->T, p->h, p->Tm, p->ld_tm, rows, rmax, f == 0 ? B : rmax, rmax, ndev, p->part, p->max_parts,
+                                     p->lse_cu_share_pct, &pending_parts, stream));
         }
         JLM_TRY(stamp(f, 5));
     }
@@ -302,4 +333,71 @@ extern "C" int jlm_lse_probe(const jlm_decode_model *m, const int *rowlist, cons
     return jlm_vocab_lse_hybrid(m->split_segs, m->split_t_scale, m->split_descale, m->split_bias_col, m->mixed_segs, m->mixed_descale,
                                 m->mixed_s8, m->mixed_head_split, m->n_segs, m->b2, T, m->ldt, Tm, ld_tm, rl, part, rows, max_parts, rows,
                                 nullptr, stream);
+}
+
+// jlm_score.hip: the fold of a scoring step (score_fold_kernel)
+int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, const float *T, int ldt, const float *part, int ld_part,
+                   int n_parts, int self_norm, const int *target, const int *n_dev, int n_rows_max, double *nll_seq, double *nll_tok,
+                   int *flags, void *stream);
+
+// Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),
+// T, the full-vocabulary normaliser as the frame loop launches it for kind 0, and the fold into -log p of the target word.
+extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
+    const int R = p->n_rows, S = p->n_steps;
+    if (R < 0 || S < 0 || !p->rows || !p->prev0 || !p->word || !p->target || !p->n_live || !p->nll_seq) return -1;
+    if (R == 0 || S == 0) return 0;
+    if (m->split_lstm && !m->wt8) return -2;        // (a split-row model always carries wt8 / xgate8: DeviceModel builds them together)
+    if (!m->self_norm && (!p->part || p->max_parts < 1)) return -1;
+    // an untied f32 model's T is the state row set the step wrote; every other model has its own T rows (untied split-row models:
+    // the f32 copy the step writes beside the split rows)
+    const bool t_is_h = m->untied && !m->split_lstm;
+    if (!t_is_h && !p->T) return -1;
+    hipStream_t main_s = (hipStream_t)stream;
+    auto stamp = [&](int t, int i) -> int {
+        if (!events) return 0;
+        return (int)hipEventRecord((hipEvent_t)events[(size_t)t * JLM_SCORE_EVENTS_PER_STEP + i], main_s);
+    };
+    for (int t = 0; t < S; ++t) {
+        const int bound = p->n_live_host ? p->n_live_host[t] : R;
+        if (bound < 0 || bound > R) return -1;
+        const int *ndev = p->n_live + t;
+        const int *word = p->word + (size_t)t * R, *target = p->target + (size_t)t * R;
+        // ping-pong: step t reads set t % 2 and writes the other (word[] and prev[] are indexed by the row: g = rows[r] = r)
+        void *h_in = p->h[t & 1], *h_out = p->h[(t + 1) & 1];
+        float *c_in = p->c[t & 1], *c_out = p->c[(t + 1) & 1];
+        const int *prev = t == 0 ? p->prev0 : p->rows;
+        float *T = t_is_h ? (float *)h_out : p->T;
+        JLM_TRY(stamp(t, 0));
+        if (bound > 0) {
+            if (m->split_lstm)
+                JLM_TRY(jlm_lstm_step_xg(h_in, c_in, m->H, h_out, c_out, p->rows, prev, word, m->wt8, m->xgate8, m->H, m->gate_descale,
+                                         m->h_scale, m->untied ? p->T : nullptr, bound, ndev, stream));
+            else
+                JLM_TRY(jlm_lstm_step((const float *)h_in, c_in, m->H, (float *)h_out, c_out, p->rows, prev, word, m->emb, m->ld_emb,
+                                      m->wt, m->gate_bias, m->kpad, m->H, m->E, bound, ndev, stream));
+        }
+        JLM_TRY(stamp(t, 1));
+        if (bound > 0 && !m->untied) {
+            if (m->split_lstm)
+                JLM_TRY(jlm_gemm_nt_split(h_out, m->H, p->rows, m->pmt_split, m->H, nullptr, T, m->ldt, p->rows, nullptr, m->t_descale,
+                                          bound, m->n_t, m->H, ndev, stream));
+            else
+                JLM_TRY(jlm_gemm_nt((const float *)h_out, m->H, p->rows, m->pmt, m->H, nullptr, T, m->ldt, p->rows, nullptr, bound,
+                                    m->n_t, m->H, ndev, stream));
+        }
+        JLM_TRY(stamp(t, 2));
+        int n_parts = 0;
+        if (bound > 0 && !m->self_norm) {
+            FullLse fl;
+            JLM_TRY(full_lse_pack(m, T, p->rows, bound, ndev, p->Tm, p->ld_tm, false, fl, stream));
+            JLM_TRY(full_lse_run(m, fl, T, h_out, p->Tm, p->ld_tm, p->rows, R, bound, bound, ndev, p->part, p->max_parts, 0, &n_parts,
+                                 stream));
+        }
+        JLM_TRY(stamp(t, 3));
+        if (bound > 0)
+            JLM_TRY(jlm_score_fold(m->segs, m->n_segs, m->b2, T, m->ldt, p->part, R, n_parts, m->self_norm, target, ndev, bound,
+                                   p->nll_seq, p->nll_tok ? p->nll_tok + (size_t)t * R : nullptr, p->flags, stream));
+        JLM_TRY(stamp(t, 4));
+    }
+    return 0;
 }

@@ -14,6 +14,8 @@
 //   torch.ops.jlm.decode_batch(Model, Plan, staging block, lattice block, read-back buffers, ...)
 //                             round 5: upload + frame loop + read-back of one batch, ONE op (what DecodeEngine submits)
 //   torch.ops.jlm.frame_times(Plan) -> Tensor [n_frames, 5] milliseconds of the last timed decode (after it finished)
+//   torch.ops.jlm.score_frames(Model, state row sets, ..., word, target, n_live, nll outputs, ...)
+//                             teacher-forced scoring of many sequences: ONE op (jlm_score_frames; LSTM_Model.score)
 //   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
@@ -452,6 +454,76 @@ int64_t lse_probe(const c10::intrusive_ptr<JlmModel> &model, const Tensor &rowli
     return rc;
 }
 
+// teacher-forced scoring of n_rows sequences / streams over n_steps steps (jlm_score_frames, include/jlm_hip.h): state row sets h0/c0
+// (read by step 0) and h1/c1, ping-pong; T / Tm / part as the model's normaliser needs them; word / target [n_steps][n_rows] int32;
+// n_live [n_steps] int32 on the device and its host copy; nll_seq [n_rows] f64 (accumulated), nll_tok [n_steps][n_rows] f64 (optional),
+// flags one int32 (optional).  Every id must lie in [0, V): the caller checks (jlm_amd/score.py) -- the kernels index with them.
+// -> timed: [n_steps, 4] milliseconds per step (LSTM step, T projection, normaliser, fold) after waiting for the last step; else an
+// empty tensor and nothing waits.
+Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                    const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
+                    const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host,
+                    const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(R >= 0 && S >= 0 && (int64_t)n_live_host.size() == S, "jlm.score_frames: n_live_host holds one count per step");
+    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= R, "jlm.score_frames: a live-row count outside [0, n_rows]");
+    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
+                    is(c0, at::kFloat, R * m.H) && is(c1, at::kFloat, R * m.H),
+                "jlm.score_frames: state row sets [n_rows, H] of 4-byte values");
+    TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
+                    is(n_live, at::kInt, S),
+                "jlm.score_frames: int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
+    TORCH_CHECK(is(nll_seq, at::kDouble, R) && (!has(nll_tok) || is(*nll_tok, at::kDouble, S * R)) && (!has(flags) || is(*flags, at::kInt, 1)),
+                "jlm.score_frames: float64 nll_seq [n_rows] / nll_tok [n_steps][n_rows], int32 flags");
+    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.score_frames: T [n_rows, ldt] float32");
+    TORCH_CHECK(!has(part) || (is(*part, at::kFloat, max_parts * R * 2) && max_parts >= 1), "jlm.score_frames: part [max_parts][n_rows][2]");
+    TORCH_CHECK(!has(Tm) || (ld_tm > 0 && Tm->numel() >= ((R + 31) / 32 * 32) * ld_tm), "jlm.score_frames: Tm (whole 32-row blocks of ld_tm)");
+    jlm_score_plan p{};
+    p.n_rows = (int)R; p.n_steps = (int)S;
+    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+    p.T = optr<float>(T, "T");
+    p.Tm = optr<void>(Tm, "Tm"); p.ld_tm = p.Tm ? (int)ld_tm : 0;
+    p.part = optr<float>(part, "part"); p.max_parts = p.part ? (int)max_parts : 0;
+    p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
+    p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
+    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
+    p.n_live_host = live_host.data();
+    p.nll_seq = ptr<double>(nll_seq, "nll_seq"); p.nll_tok = optr<double>(nll_tok, "nll_tok"); p.flags = optr<int>(flags, "flags");
+    const int dev = h0.device().index();
+    const c10::hip::HIPGuard device_guard(dev);
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
+    std::vector<hipEvent_t> ev;
+    struct Destroy {
+        std::vector<hipEvent_t> &ev;
+        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } destroy{ev};
+    if (timed)
+        for (int64_t i = 0; i < S * JLM_SCORE_EVENTS_PER_STEP; ++i) {
+            hipEvent_t e;
+            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
+            ev.push_back(e);
+        }
+    {
+        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
+        jlm_check(jlm_score_frames(&m, &p, st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), "jlm_score_frames");
+    }
+    if (!timed || S == 0) return at::empty({0}, at::kDouble);
+    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
+    Tensor out = at::zeros({S, JLM_SCORE_EVENTS_PER_STEP - 1}, at::kDouble);
+    auto a = out.accessor<double, 2>();
+    for (int64_t t = 0; t < S; ++t)
+        for (int i = 0; i + 1 < JLM_SCORE_EVENTS_PER_STEP; ++i) {
+            float ms = 0.0f;
+            jlm_check((int)hipEventElapsedTime(&ms, ev[t * JLM_SCORE_EVENTS_PER_STEP + i], ev[t * JLM_SCORE_EVENTS_PER_STEP + i + 1]),
+                      "hipEventElapsedTime");
+            a[t][i] = ms;
+        }
+    return out;
+}
+
 int64_t abi_version() { return jlm_abi_version(); }
 int64_t beam_step_max_cands(int64_t beam, int64_t n_frames, int64_t mode) { return jlm_beam_step_max_cands((int)beam, (int)n_frames, (int)mode); }
 
@@ -482,6 +554,10 @@ TORCH_LIBRARY(jlm, m) {
     m.def("dequant_u8(Tensor code, int rows, int k, int ld_code, Tensor codebook, Tensor(a!) dst, int ld_dst) -> ()", dequant_u8);
     m.def("lse_probe(__torch__.torch.classes.jlm.Model model, Tensor rowlist, Tensor prev, Tensor word, int steps, int rows, Tensor(a!) h, "
           "Tensor(b!) c, Tensor(c!) T, Tensor? Tm, int ld_tm, int form, Tensor(d!) part, int max_parts) -> int", lse_probe);
+    m.def("score_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
+          "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed) -> Tensor",
+          score_frames);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

@@ -7,6 +7,9 @@ Counterpart of ``LSTM_Model`` (reference decoder/model.py:36-198):
     .project(hidden, vocab=None)             -> y
     .predict_with_context(index, hidden, cell, vocab=None)
                                              -> ((pred, y, t1, t2), hidden, cell)
+    .evaluate(start, inputs)                 -> per-word -log p (one predict() per word)
+    .score(sequences, start)                 -> per-word -log p of many sequences in one device call (jlm_amd/score.py)
+    .score_streams(inputs, targets, h, c)    -> (per-token -log p [B, n], h, c): state-carrying streams
     attrs .hidden .cell .hidden_size .embed_size .config .weights
 
 Arrays at this boundary are numpy (float64, like the reference's); on the
@@ -994,6 +997,40 @@ class LSTM_Model():
             probs.append(pred[0, inp])
             pred = self.predict([inp])[0]
         return [-np.log(p) for p in probs]
+
+    def _scorer(self):
+        s = getattr(self, "_score", None)
+        if s is None:
+            from .score import Scorer
+            s = self._score = Scorer(self.dev)
+        return s
+
+    def score(self, sequences, start, per_token=True, max_rows=None):
+        """evaluate() for many sequences at once, on the device (jlm_amd/score.py).  ``sequences``: word-id lists of any length
+        (0 included).  Sequence s is scored as ``evaluate(start, s)`` scores it: step 0 consumes ``start`` from the zero state and is
+        scored on s[0], step t consumes s[t-1] and is scored on s[t].  -> one float64 array of per-word -log p per sequence, in input
+        order (per_token=False: one float64 array of the per-sequence sums).  Sequences are sorted by length and cut into calls of
+        at most ``max_rows`` rows (default: Scorer.max_rows, from the buffers' size).  ValueError for an id outside [0, V) before
+        anything runs; JlmHipError when the device flags a log-normaliser that is not finite."""
+        from .score import score_sequences
+        return score_sequences(self._scorer(), sequences, start, per_token, max_rows)
+
+    def score_streams(self, inputs, targets, h=None, c=None):
+        """The stream form (the reference's training-time evaluation, train/model.py:262-297): ``inputs`` / ``targets`` [B, n] word
+        ids, row b consuming inputs[b, t] and scored on targets[b, t] at step t, the LSTM state carried from (h, c) -- device tensors
+        [B, H] returned by an earlier call, None = zero state.  -> (nll [B, n] float64, h, c): the per-token -log p and the state after
+        the last step (device tensors, in the state-row format of the model; pass them back as they are)."""
+        x = np.asarray(inputs)
+        y = np.asarray(targets)
+        if x.ndim != 2 or x.shape != y.shape:
+            raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
+        B, n = x.shape
+        if (h is None) != (c is None):
+            raise ValueError("carry both h and c, or neither")
+        if B == 0 or n == 0:
+            return np.zeros((B, n), dtype=np.float64), h, c
+        _seq, tok, h2, c2 = self._scorer().run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
+        return np.ascontiguousarray(tok.T), h2, c2
 
 
 def show_prob(model, w2i, inputs):

@@ -1,0 +1,175 @@
+"""Teacher-forced scoring on the device: the per-word -log p of many word sequences at once.
+
+The reference measures a model by its test perplexity (train/train.py:101-102 over train/model.py:262-297) and scores a sentence
+with ``LSTM_Model.evaluate`` (decoder/model.py:200-206), one ``predict()`` -- one materialised softmax -- per word.  Here a call is
+ONE op (``torch.ops.jlm.score_frames``, csrc/jlm_decode.hip ``jlm_score_frames``): per step the LSTM step of the live rows, the T
+projection, the full-vocabulary normaliser the decoders use, and ``score_fold_kernel`` (csrc/jlm_score.hip), which folds the
+normaliser's slices and takes the target word's logit.  Nothing comes back to the host between steps.
+
+Host logic of this module (row plan, stream layout, id checks) is plain numpy; :class:`Scorer` owns the device buffers of a call.
+``LSTM_Model.score`` / ``score_streams`` (jlm_amd/model.py) are the public entry points, ``python -m jlm_amd.perplexity`` the
+command-line front end.
+"""
+import numpy as np
+
+from . import _lib
+from . import ops as _ops
+
+# rows per call: the gate GEMM is most efficient at large row counts (37-40 % of the MFMA peak at 20 480 rows, 28 % at 2 560:
+# BENCH_r06); a call's buffers are bounded by SCORE_BUDGET_BYTES besides
+MAX_ROWS = 20480
+SCORE_BUDGET_BYTES = 2 << 30
+
+
+def check_ids(arr, V, what):
+    """ValueError unless every id of ``arr`` lies in [0, V) -- before anything is launched (the kernels index with them)."""
+    a = np.asarray(arr)
+    if a.size and (a.min() < 0 or a.max() >= V):
+        bad = a[(a < 0) | (a >= V)].ravel()[0]
+        raise ValueError("%s: word id %d outside the model's vocabulary [0, %d)" % (what, int(bad), V))
+
+
+def plan_rows(lengths, max_rows):
+    """The row plan of a sentence-mode call.  Sequences are sorted by length, longest first (stable), so that the rows live at step t
+    -- those with a word left to score -- are a prefix; empty sequences take no row.  -> list of chunks of at most ``max_rows`` rows:
+    dict(idx = the sequence of each row, lens = their lengths, n_steps = the longest, n_live [n_steps] = live rows per step)."""
+    if max_rows < 1:
+        raise ValueError("max_rows must be >= 1")
+    lens = np.asarray(lengths, dtype=np.int64)
+    order = np.argsort(-lens, kind="stable")
+    order = order[lens[order] > 0]
+    chunks = []
+    for i in range(0, len(order), max_rows):
+        idx = order[i:i + max_rows]
+        L = lens[idx]
+        n_steps = int(L[0])
+        n_live = (L[None, :] > np.arange(n_steps)[:, None]).sum(axis=1).astype(np.int32)
+        chunks.append(dict(idx=idx, lens=L, n_steps=n_steps, n_live=n_live))
+    return chunks
+
+
+def sentence_arrays(seqs, start, n_steps):
+    """word / target [n_steps, R] int32 of the rows ``seqs`` (longest first): step 0 consumes ``start``, step t consumes s[t - 1] and is
+    scored on s[t]; positions past a row's end hold 0 (never read: the row is not live there)."""
+    R = len(seqs)
+    word = np.zeros((n_steps, R), dtype=np.int32)
+    target = np.zeros((n_steps, R), dtype=np.int32)
+    word[0, :] = start
+    for r, s in enumerate(seqs):
+        L = len(s)
+        target[:L, r] = s
+        word[1:L, r] = s[:L - 1]
+    return word, target
+
+
+def stream_layout(data, batch_size, num_steps):
+    """The reference's corpus_iterator (train/utils.py:17-31) as two arrays: the id stream cut into ``batch_size`` rows of
+    batch_len = len // batch_size ids (the tail dropped), of which the first epoch_size * num_steps steps are read,
+    epoch_size = (batch_len - 1) // num_steps.  -> (inputs, targets) [batch_size, epoch_size * num_steps] int32, targets shifted
+    by one; chunk i of the iterator is columns [i * num_steps, (i + 1) * num_steps)."""
+    raw = np.asarray(data, dtype=np.int32)
+    batch_len = len(raw) // batch_size
+    rows = raw[:batch_size * batch_len].reshape(batch_size, batch_len)
+    epoch_size = (batch_len - 1) // num_steps
+    if epoch_size <= 0:
+        raise ValueError("epoch_size == 0, decrease batch_size or num_steps")
+    n = epoch_size * num_steps
+    return np.ascontiguousarray(rows[:, :n]), np.ascontiguousarray(rows[:, 1:n + 1])
+
+
+class Scorer:
+    """The device side of a scoring call over a :class:`jlm_amd.model.DeviceModel`."""
+
+    def __init__(self, dev_model):
+        self.m = dev_model
+        self.torch = dev_model.torch
+        self.last_step_ms = None          # [n_steps, 4] of the last timed call: LSTM step, T projection, normaliser, fold
+
+    def row_bytes(self, n_steps, per_token=True):
+        m = self.m
+        n_parts = 0 if m.self_norm else max(m.n_vocab_tiles, 1)
+        return (4 * m.H + m.ldt + (m.ld_tm or 0)) * 4 + n_parts * 8 + 16 + n_steps * (8 + (8 if per_token else 0))
+
+    def max_rows(self, n_steps, per_token=True):
+        """the default row budget of a call: MAX_ROWS, fewer when the call's buffers would exceed SCORE_BUDGET_BYTES, and within the
+        LSTM-step kernels' addressing (rows x H / 4 < 2^31)"""
+        k = SCORE_BUDGET_BYTES // self.row_bytes(n_steps, per_token)
+        return int(max(1, min(MAX_ROWS, k, (0x7ffffff0 // max(self.m.H // 4, 1)) - 1)))
+
+    def run(self, word, target, n_live, h=None, c=None, per_token=True, timed=False):
+        """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
+        the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
+        -> (nll_seq [R] f64, nll_tok [n_steps, R] f64 or None, h, c) -- numpy results, the state after the last step on the device."""
+        torch, m = self.torch, self.m
+        word = np.ascontiguousarray(word, dtype=np.int32)
+        target = np.ascontiguousarray(target, dtype=np.int32)
+        S, R = target.shape
+        check_ids(word, m.V, "score")
+        check_ids(target, m.V, "score")
+        n_live = [int(x) for x in n_live]
+        dev, f32, i32, f64 = m.device, torch.float32, torch.int32, torch.float64
+        with m._ctx():
+            e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
+            hs = [e((R, m.H), f32), e((R, m.H), f32)]
+            cs = [e((R, m.H), f32), e((R, m.H), f32)]
+            rows = torch.arange(R, device=dev, dtype=i32)
+            if h is None:
+                prev0 = torch.full((R,), -1, device=dev, dtype=i32)
+            else:
+                if tuple(h.shape) != (R, m.H) or tuple(c.shape) != (R, m.H):
+                    raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (R, m.H, tuple(h.shape), tuple(c.shape)))
+                hs[0].copy_(h)
+                cs[0].copy_(c)
+                prev0 = rows
+            untied_f32 = m.mode == "untied" and not m.split_lstm
+            T = None if untied_f32 else e((R, m.ldt), f32)
+            part, n_parts = None, 0
+            if not m.self_norm:
+                n_parts = max(m.n_vocab_tiles, 1)
+                part = e((n_parts, R, 2), f32)
+            Tm = None
+            if part is not None and getattr(m, "ld_tm", 0):
+                Tm = torch.zeros(((R + 31) // 32 * 32, m.ld_tm), device=dev, dtype=f32)     # whole 32-row blocks (jlm_hip.h)
+            wd = torch.from_numpy(word).to(dev)
+            tg = torch.from_numpy(target).to(dev)
+            nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
+            nll_seq = torch.zeros(R, device=dev, dtype=f64)
+            nll_tok = torch.zeros((S, R), device=dev, dtype=f64) if per_token else None
+            flags = torch.zeros(1, device=dev, dtype=i32)
+            ms = _ops.backend().score_frames(m.decode_model(), hs[0], cs[0], hs[1], cs[1], T, Tm, int(m.ld_tm or 0), part, n_parts, rows,
+                                             prev0, wd, tg, nl, n_live, nll_seq, nll_tok, flags, R, S, bool(timed))
+            if timed:
+                self.last_step_ms = ms.numpy()
+            fl = int(flags.cpu()[0])
+            seq = nll_seq.cpu().numpy()
+            tok = nll_tok.cpu().numpy() if per_token else None
+        if fl & 1:
+            raise _lib.JlmHipError("a log-normaliser is not finite: this model's logits left the range the fixed-reference normaliser covers "
+                                   "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
+        if fl:
+            raise _lib.JlmHipError("score_fold_kernel flagged a target outside the model's segments (flags %d)" % fl)
+        return seq, tok, hs[S % 2], cs[S % 2]
+
+
+def score_sequences(scorer, sequences, start, per_token=True, max_rows=None):
+    """LSTM_Model.score: see there."""
+    V = scorer.m.V
+    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
+    for s in seqs:
+        check_ids(s, V, "score")
+    check_ids([start], V, "score (start)")
+    lens = [len(s) for s in seqs]
+    longest = max(lens) if lens else 0
+    if max_rows is None:
+        max_rows = scorer.max_rows(longest, per_token)
+    out = [np.zeros(L, dtype=np.float64) for L in lens] if per_token else np.zeros(len(seqs), dtype=np.float64)
+    for ch in plan_rows(lens, max_rows):
+        idx = ch["idx"]
+        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
+        seq, tok, _h, _c = scorer.run(word, target, ch["n_live"], per_token=per_token)
+        for r, i in enumerate(idx):
+            if per_token:
+                out[i] = tok[:ch["lens"][r], r].copy()
+            else:
+                out[i] = seq[r]
+    return out
