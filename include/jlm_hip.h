@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 /* Library / device probe.  Returns the ABI version (JLM_ABI_VERSION). */
-#define JLM_ABI_VERSION 11
+#define JLM_ABI_VERSION 12
 #define JLM_MAX_BEAM 1024           /* ABI 6: jlm_beam_step takes beams above one wave (64): a lane owns several ranks */
 int jlm_abi_version(void);
 /* Writes gfx arch name (e.g. "gfx950:sramecc+:xnack-") of device `dev`. */
@@ -159,6 +159,14 @@ int jlm_lstm_step_xg(const void *h_in, const float *c_in, int ld_state, void *h_
                      const int *rows, const int *prev, const int *word,
                      const void *wt8, const float *xgate8, int H, float descale, float h_scale, float *h_f32_out,
                      int n_rows_max, const int *n_dev, void *stream);
+
+/* ABI 12: which kernel form jlm_lstm_step_xg launches for these arguments (pure host, no HIP call): 0 the loop for every H
+ * (gate_xg_kernel), and at H = 512: 1 one 160 x 128 tile per workgroup (gate_xg_u16_kernel), 3 the same tile persistent (gate_pu_kernel),
+ * 2 W-stationary persistent (gate_ws_kernel), 4 128 x 256 tiles persistent (gate_p2_kernel); -1 for an H the step refuses.
+ * has_rows / has_h_f32: whether rows / h_f32_out are non-NULL.  Default by n_rows_max: 1 below 4 096, 3 up to 16 383, 2 from 16 384;
+ * JLM_GATE_V = 1 .. 4 (read once per process) forces a form where it can serve the launch -- 2 and 3 need a row list, 4 a row list and
+ * no f32 copy -- and the default is taken where it cannot. */
+int jlm_lstm_step_form(int H, int has_rows, int has_h_f32, int n_rows_max);
 
 /* jlm_vocab_lse_partials on split rows (the tile form for k > 256: untied models, k = H; model.py:189-191):
  *   logit[v, r] = descale * sum_k Bsplit[v, k] * Tsplit[rows[r], k] + bias[v]

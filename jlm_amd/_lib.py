@@ -83,6 +83,7 @@ _SIGS = {
     "jlm_vocab_lse_stationary": ([POINTER(Segment), c_int, P, P, c_int, P, P, c_int, c_int, c_int, P, P], c_int),
     "jlm_pack_split_f16": ([P, c_int, c_int, c_int, c_float, P, c_int, P], c_int),
     "jlm_lstm_step_xg": ([P, P, c_int, P, P, P, P, P, P, P, c_int, c_float, c_float, P, c_int, P, P], c_int),
+    "jlm_lstm_step_form": ([c_int, c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_partials_split": ([P, c_int, c_int, c_int, P, c_int, P, P, c_float, P, c_int, c_int, c_int, P, P], c_int),
     "jlm_gemm_nt_split": ([P, c_int, P, P, c_int, P, P, c_int, P, P, c_float, c_int, c_int, c_int, P, P], c_int),
     "jlm_dequant_u8": ([P, c_int, c_int, c_int, P, c_int, P, c_int, P], c_int),
@@ -143,7 +144,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res
-        if l.jlm_abi_version() != 11:
+        if l.jlm_abi_version() != 12:
             raise JlmHipError("libjlm_hip.so ABI version mismatch")
         _lib = l
     return _lib

@@ -1081,6 +1081,24 @@ static const void *gate_u16_selected() {
     return reinterpret_cast<const void *>(gate_xg_u16_kernel<0>);
 }
 
+// JLM_GATE_V: 3 the persistent form of the one-tile kernel (gate_pu_kernel above); 2 the W-stationary persistent kernel
+// (csrc/jlm_gate_ws.hip); 4 128 x 256 tiles, persistent (csrc/jlm_gate_p2.hip) -- all three for H = 512 and a row list (16 gate-column
+// tiles, divisible over the 8 XCDs), 4 only without the f32 copy of h'; 1 one tile per workgroup, refill-in-place pipeline (round 3);
+// 0 the round-2 loop (every H).  Default by the launch's row bound (tools/gpu_gate_pu.sh, tools/gpu_gate_ws.sh; us per launch for
+// 1 / 3 / 2 on one box: 2 560 rows 23.2 / 24.1 / 26.4, 5 120: 42.1 / 40.5 / 43.1, 10 240: 82.7 / 75.0 / 80.2, 20 480: 174 / 160 / 156):
+// one tile per CU -> 1; two to a few tiles per CU -> 3; more -> 2.  JLM_GATE_V = 1 .. 4 forces a form for A/B; a forced form that
+// cannot serve the launch takes the default (the round-2 loop serves the other H only -- forcing it at H = 512, JLM_GATE_V=0, left
+// with ABI 9).  The one place the launcher's choice is made: jlm_lstm_step_xg and the tests ask here.
+extern "C" int jlm_lstm_step_form(int H, int has_rows, int has_h_f32, int n_rows_max) {
+    if (H <= 0 || H % 32 != 0) return -1;
+    if (H != 512) return 0;
+    auto serves = [&](int v) { return v == 1 || ((v == 2 || v == 3) && has_rows) || (v == 4 && has_rows && !has_h_f32); };
+    static const int variant_env = getenv("JLM_GATE_V") ? atoi(getenv("JLM_GATE_V")) : -1;
+    if (serves(variant_env)) return variant_env;
+    const int dflt = n_rows_max >= 16384 ? 2 : n_rows_max >= 4096 ? 3 : 1;
+    return serves(dflt) ? dflt : 1;
+}
+
 extern "C" int jlm_lstm_step_xg(const void *h_in, const float *c_in, int ld_state, void *h_out, float *c_out, const int *rows,
                                 const int *prev, const int *word, const void *wt8, const float *xgate8, int H, float descale,
                                 float h_scale, float *h_f32_out, int n_rows_max, const int *n_dev, void *stream) {
@@ -1102,20 +1120,12 @@ extern "C" int jlm_lstm_step_xg(const void *h_in, const float *c_in, int ld_stat
     a.tiles_m = (n_rows_max + GT_BM - 1) / GT_BM;
     a.tiles_n = 4 * H / GT_BN;
     a.cx = 0;
-    // JLM_GATE_V: 3 the persistent form of the one-tile kernel (gate_pu_kernel above); 2 the W-stationary persistent kernel
-    // (csrc/jlm_gate_ws.hip) -- both for H = 512, a row list, gate-column tiles divisible over the 8 XCDs; 1 one tile per workgroup,
-    // refill-in-place pipeline (round 3); 0 the round-2 loop (every H).  Default by the launch's row bound (tools/gpu_gate_pu.sh,
-    // tools/gpu_gate_ws.sh; us per launch for 1 / 3 / 2 on one box: 2 560 rows 23.2 / 24.1 / 26.4, 5 120: 42.1 / 40.5 / 43.1,
-    // 10 240: 82.7 / 75.0 / 80.2, 20 480: 174 / 160 / 156): one tile per CU -> 1; two to a few tiles per CU -> 3; more -> 2
-    // (JLM_GATE_V = 1 / 2 / 3 forces one of the three H = 512 forms for A/B; the round-2 loop serves the other H only -- forcing it
-    //  at H = 512, JLM_GATE_V=0, left with ABI 9)
-    static const int variant_env = getenv("JLM_GATE_V") ? atoi(getenv("JLM_GATE_V")) : -1;
-    const int variant = variant_env >= 1 ? variant_env : (n_rows_max >= 16384 ? 2 : n_rows_max >= 4096 ? 3 : 1);
+    const int variant = jlm_lstm_step_form(H, rows != nullptr, h_f32_out != nullptr, n_rows_max);
     static const int ws_l = getenv("JLM_GATE_WS_L") ? atoi(getenv("JLM_GATE_WS_L")) : 3;
-    if (variant == 4 && H == 512 && rows && !h_f32_out) {
+    if (variant == 4) {
         // round 6: 128 x 256 tiles, a 2 x 2 register block per wave, persistent (csrc/jlm_gate_p2.hip)
         if (int rc = jlm_gate::p2_launch(a, (hipStream_t)stream)) return rc;
-    } else if (variant == 3 && H == 512 && rows && (a.tiles_n & 7) == 0) {
+    } else if (variant == 3) {
         // the persistent form of the one-tile kernel (gate_pu_kernel): tiles_n column tiles x Q row-tile sequences
         const int per_col = 256 / a.tiles_n;
         const int Q = a.tiles_m < per_col ? a.tiles_m : per_col;
@@ -1126,7 +1136,7 @@ extern "C" int jlm_lstm_step_xg(const void *h_in, const float *c_in, int ld_stat
         void *params[] = {&a};
         hipError_t e = hipLaunchKernel(fn, dim3(a.tiles_n * Q), dim3(512), params, GT_LDS_BYTES, (hipStream_t)stream);
         if (e != hipSuccess) return (int)e;
-    } else if (variant == 2 && H == 512 && rows && (a.tiles_n & 7) == 0) {
+    } else if (variant == 2) {
         const int per_col = 256 / a.tiles_n;                       // row-tile sequences per gate-column tile: one resident workgroup per CU
         const int Q = a.tiles_m < per_col ? a.tiles_m : per_col;
         // gate-column tiles per XCD: fabric bytes ~ (16 / cx) x rows x 2 KB of state + (cx / 16) x 8 XCDs x 4 MB of gate matrix
@@ -1134,7 +1144,7 @@ extern "C" int jlm_lstm_step_xg(const void *h_in, const float *c_in, int ld_stat
         a.cx = ws_cx ? ws_cx : 4;                                  // (measured 2 / 4 / 8 / 16 at 10 240 and 20 480 rows: 4 by 2-4 %)
         if (a.cx > a.tiles_n || a.tiles_n % a.cx || 32 % a.cx) a.cx = 2;
         if (int rc = jlm_gate::ws_launch(a, ws_l == 3 ? 3 : 7, Q, (hipStream_t)stream)) return rc;
-    } else if (variant >= 1 && H == 512) {
+    } else if (variant == 1) {
         void *params[] = {&a};
         hipError_t e = hipLaunchKernel(gate_u16_selected(), dim3(a.tiles_m * a.tiles_n), dim3(512), params, GT_LDS_BYTES, (hipStream_t)stream);
         if (e != hipSuccess) return (int)e;

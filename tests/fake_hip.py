@@ -9,6 +9,8 @@ product never falls back to it; the GPU tests run the real library.
 Each function restates the CONTRACT written in the header, not the HIP code.
 """
 import ctypes
+import os
+import re
 
 import numpy as np
 
@@ -41,9 +43,33 @@ def _rows(rows, n):
     return view(rows, n, np.int32).astype(np.int64) if _p(rows) else np.arange(n, dtype=np.int64)
 
 
+def gate_v_env():
+    """JLM_GATE_V as atoi reads it; -1 when unset"""
+    v = os.environ.get("JLM_GATE_V")
+    if v is None:
+        return -1
+    m = re.match(r"\s*[+-]?\d+", v)
+    return int(m.group()) if m else 0
+
+
+def lstm_step_form(H, has_rows, has_h_f32, n_rows_max, forced):
+    """include/jlm_hip.h jlm_lstm_step_form with JLM_GATE_V = forced: 0 the loop for every H, at H = 512 1 one 160 x 128 tile per
+    workgroup, 3 the same tile persistent, 2 W-stationary, 4 128 x 256 tiles; a forced form that cannot serve the launch (2 / 3 without a
+    row list, 4 without a row list or with the f32 copy of h') takes the row-bound default"""
+    if H <= 0 or H % 32:
+        return -1
+    if H != 512:
+        return 0
+    serves = lambda v: v == 1 or (v in (2, 3) and bool(has_rows)) or (v == 4 and bool(has_rows) and not has_h_f32)
+    if serves(forced):
+        return forced
+    dflt = 2 if n_rows_max >= 16384 else 3 if n_rows_max >= 4096 else 1
+    return dflt if serves(dflt) else 1
+
+
 class FakeLib:
     def jlm_abi_version(self):
-        return 11
+        return 12
 
     @staticmethod
     def _mx6_model(m):
@@ -306,6 +332,11 @@ class FakeLib:
         nb = x.shape[1] // 8
         out[row_ids, :nb, 0, :] = hi.reshape(len(row_ids), nb, 8)
         out[row_ids, :nb, 1, :] = lo.reshape(len(row_ids), nb, 8)
+
+    @staticmethod
+    def jlm_lstm_step_form(H, has_rows, has_h_f32, n_rows_max):
+        """ABI 12: the kernel form jlm_lstm_step_xg launches; JLM_GATE_V as the library reads it (once per process)"""
+        return lstm_step_form(H, has_rows, has_h_f32, n_rows_max, gate_v_env())
 
     def jlm_lstm_step_xg(self, h_in, c_in, ld, h_out, c_out, rows, prev, word, wt8, xgate8, H, descale, h_scale, h_f32_out,
                          n_rows_max, n_dev, stream):

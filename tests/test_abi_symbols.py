@@ -15,14 +15,14 @@ def _declared(header):
     return sorted(set(re.findall(r"\b(jlm_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_hip_library_exports_header():
+def test_hip_library_version_and_exports():
     names = _declared("jlm_hip.h")
     assert len(names) >= 12
     lib = ctypes.CDLL(_lib.LIB_PATH)             # loads on a GPU-less box: no HIP call at load time
     for n in names:
         assert hasattr(lib, n), n
     assert sorted(_lib.EXPORTS) == names
-    assert lib.jlm_abi_version() == 11
+    assert lib.jlm_abi_version() == 12
 
 
 def test_host_library_exports_header():

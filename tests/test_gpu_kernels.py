@@ -126,6 +126,22 @@ def _pack(L, src_g, k, scale, ld_dst=None, dst=None, col0=0, src_col0=0):
     return dst
 
 
+def lstm_xg_f64(h_np, c_np, W, xg, prev, word):
+    """f64 restatement of the table-form LSTM step on the original f32 operands: rows with state prev (-1: zero state) and input
+    word; W [4H, H] and the table xg [V, 4H] in the gate-interleave-8 order -> (h', c') [len(prev), H]"""
+    H = W.shape[1]
+    p = np.asarray(prev).astype(np.int64)
+    hin = np.where((p >= 0)[:, None], h_np[np.maximum(p, 0)], 0.0).astype(np.float64)
+    cin = np.where((p >= 0)[:, None], c_np[np.maximum(p, 0)], 0.0).astype(np.float64)
+    z = hin @ W.astype(np.float64).T + xg[word].astype(np.float64)
+    u = np.arange(H)
+    zi, zf, zo, zg = (z[:, (u // 8) * 32 + k * 8 + (u % 8)] for k in range(4))
+    sig = lambda t: 1.0 / (np.exp(-t) + 1.0)
+    cn = cin * sig(zf) + np.tanh(zg) * sig(zi)
+    hn = np.tanh(cn) * sig(zo)
+    return hn, cn
+
+
 @pytest.mark.parametrize("chunk", ["48", "256"])
 def test_beam_step_chunked_on_ordinary_cells(chunk):
     """JLM_BEAM_CHUNK: every beam step through the chunked kernel (csrc/jlm_beam.hip beam_step_chunked_kernel) with chunks of 48 / 256
@@ -143,18 +159,19 @@ def test_beam_step_chunked_on_ordinary_cells(chunk):
     assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]
 
 
-@pytest.mark.parametrize("variant", ["2", "3", "4"])
-def test_lstm_step_xg_forced_forms(variant):
-    """Every H = 512 form of the LSTM step on every row count of test_lstm_step_xg, whatever the launcher would pick by the row bound:
-    JLM_GATE_V = 2 (W-stationary), 3 (persistent 160 x 128), 4 (persistent 128 x 256, a 2 x 2 register block per wave: csrc/jlm_gate_p2.hip;
-    its tiles: first / middle / last of a sequence at 5 200 and 20 480 rows, a ragged last tile, a single row).  The variable is read once
-    per process, hence the child."""
-    import os, subprocess, sys
-    env = dict(os.environ, JLM_GATE_V=variant)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", "test_lstm_step_xg and not forced"],
-                       env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]
+@pytest.mark.parametrize("variant", ["1", "2", "3", "4", "2-ws_l7", "2-ws_cx2", "2-ws_cx8", "2-ws_cx16"])
+def test_lstm_step_xg_forced_forms(variant, tmp_path_factory):
+    """Every H = 512 form of the LSTM step, whatever the launcher would pick by the row bound: JLM_GATE_V = 1 (one tile per workgroup),
+    2 (W-stationary; also with eight ring stages, gate_ws_kernel<7, *>, and tile maps of 2, 8 and 16 gate-column tiles per XCD),
+    3 (persistent 160 x 128), 4 (persistent 128 x 256, csrc/jlm_gate_p2.hip: only launches without the f32 copy of h').  A child per
+    setting -- the variable is read once per process -- runs every case of test_gpu_gate_forms.py (row bounds 700 .. 20 480, device
+    counts from 0 past the bound, in place and ping-pong, with and without the f32 copy, saturated gates) and test_lstm_step_xg; each
+    case the form serves must have run and launched the forced form (jlm_lstm_step_form)."""
+    import os
+    if os.environ.get("JLM_GATE_FORMS_OUT"):
+        pytest.skip("inside a child")
+    from tests.test_gpu_gate_forms import check_forced_child
+    check_forced_child(variant, tmp_path_factory)
 
 
 @pytest.mark.parametrize("H,R,use_rows", [(64, 10, False), (64, 200, True), (512, 700, True), (512, 2560, True), (128, 161, True),
@@ -184,16 +201,7 @@ def test_lstm_step_xg(L, H, R, use_rows):
         prev_np = np.where(np.arange(G) < R, np.where(np.arange(G) % 3 == 0, -1, R + np.arange(G) % (G - R)), 0).astype(np.int32)
         n_live = R
     sel = rows_np[:n_live] if use_rows else np.arange(R)
-    # f64 restatement
-    p = prev_np[sel].astype(np.int64)
-    hin = np.where((p >= 0)[:, None], h_np[np.maximum(p, 0)], 0.0).astype(np.float64)
-    cin = np.where((p >= 0)[:, None], c_np[np.maximum(p, 0)], 0.0).astype(np.float64)
-    z = hin @ W.astype(np.float64).T + xg[word_np[sel]].astype(np.float64)
-    u = np.arange(H)
-    zi, zf, zo, zg = (z[:, (u // 8) * 32 + k * 8 + (u % 8)] for k in range(4))
-    sig = lambda t: 1.0 / (np.exp(-t) + 1.0)
-    cn = cin * sig(zf) + np.tanh(zg) * sig(zi)
-    hn = np.tanh(cn) * sig(zo)
+    hn, cn = lstm_xg_f64(h_np, c_np, W, xg, prev_np[sel], word_np[sel])
     # device operands
     hg, cg = torch.as_tensor(h_np).cuda(), torch.as_tensor(c_np.copy()).cuda()
     hs = _pack(L, hg, H, 2.0 ** 14)
