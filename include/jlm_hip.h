@@ -562,6 +562,58 @@ typedef struct {
 #define JLM_SCORE_EVENTS_PER_STEP 5
 int jlm_score_frames(const jlm_decode_model *model_host, const jlm_score_plan *plan_host, void *stream, void *const *events);
 
+/* ------------------------------------------------------------------------
+ * Ancestral sampling (LSTM_Model.generate, jlm_amd/generate.py): what the reference's sample(pred, temperature) and its sampling
+ * loop do one predict() at a time on the host (decoder/model.py:28-33, 213-245; train/test.py).
+ *
+ * jlm_sample_rows: one draw per row r < min(n_rows_max, *n_dev) (n_dev may be NULL) of f32 logits y[r * ld_y + 0 .. n_cols) in word-id
+ * order (ld_y % 4 == 0, ld_y >= n_cols rounded up to 4, y 16-byte aligned).  With m = max y, tau = temperature, inv = (float)(1 / tau):
+ *   S = sum_j expf((y_j - m) * inv)  (f32 exp, f64 sums; the order is a fixed function of n_cols and the launch)
+ *   u = uniform(seed, step, row_id[r] (NULL: r)):  z = seed + 0x9E3779B97F4A7C15 * ((step << 32) | (row + 1)) (uint64, wrapping),
+ *       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) * 0x94D049BB133111EB, z ^= z >> 31, u = ((z >> 11) + 0.5) 2^-53
+ *   draw = the smallest i with sum_{j <= i} expf((y_j - m) * inv) > u S; if rounding leaves no crossing, the last word with mass.
+ *   temperature 0: the argmax, the lowest id winning a tie.
+ * Per row: ids[r] = word[r] = the draw, nll[r] = -log p at tau = 1 in f64 (lse - y; self_norm: -y).  forced (or NULL): forced[r] >= 0
+ * passes through (word[r] = forced[r], ids[r] = -1, nll[r] = 0).  done (or NULL): a row with done[r] != 0 is masked (ids -1, nll 0,
+ * word unchanged); a draw equal to stop_id sets done[r] = 1.  A non-finite max or sum: *flags |= 1, ids -1, nll NaN, word 0.
+ * Returns 0, -1 for arguments the kernel cannot handle (temperature < 0 or not finite included), or a hipError_t. */
+int jlm_sample_rows(const float *y, int ld_y, int n_cols, int n_rows_max, const int *n_dev, double temperature, uint64_t seed, int step,
+                    const int *row_id, const int *forced, int *done, int stop_id, int self_norm, int *word, int *ids, double *nll,
+                    int *flags, void *stream);
+
+/* The sampling loop.  Row r < n_rows is one prompt; prompts are RIGHT-aligned on n_prompt frames (the caller sorts rows by prompt
+ * length, longest first, so the rows live at prompt frame f are the prefix r < n_live[f]; every row is live at frame n_prompt - 1).
+ * Frame f < n_prompt consumes prompt[f][r] and continues row prev[f][r] (-1: the zero state, at a row's first frame); frame
+ * f >= n_prompt consumes word[r] (what the previous frame drew) and continues row r.  Frames n_prompt - 1 .. n_prompt + n_words - 2
+ * draw: draw k = frame - (n_prompt - 1) goes to ids[k][r], nll[k][r] (sample_rows_kernel with step = k, row_id).  State: h[2] / c[2]
+ * ping-pong as jlm_score_plan's. */
+typedef struct {
+    int n_rows, n_prompt, n_words;
+    void *h[2]; float *c[2];        /* [n_rows, H] state row sets (both zeroed or not: rows start from prev = -1) */
+    float *T;                       /* [n_rows, ldt] f32 (as jlm_score_plan.T) */
+    float *logits; int ld_logits;   /* [n_rows, ld_logits] f32, ld_logits >= V rounded up to 4 */
+    const int *rows;                /* [n_rows] device: 0, 1, ..., n_rows - 1 */
+    const int *prev, *prompt;       /* [n_prompt][n_rows] device */
+    const int *n_live;              /* [n_prompt] device */
+    const int *n_live_host;         /* [n_prompt] host */
+    const int *row_id;              /* [n_rows] device: the row's index in the caller's list (the random numbers' row), or NULL: r */
+    int *word;                      /* [n_rows] device: the word the next frame consumes */
+    int *done;                      /* [n_rows] device, zeroed, or NULL (no stop word) */
+    int stop_id;
+    double temperature;             /* >= 0; 0 = greedy */
+    uint64_t seed;
+    int *ids; double *nll;          /* [n_words][n_rows] device */
+    int *flags;                     /* one device int or NULL */
+} jlm_generate_plan;
+
+/* Enqueues n_prompt + n_words - 1 frames of [LSTM step (the launches jlm_score_frames makes), and on drawing frames the T projection,
+ * jlm_gemm_nt per segment into plan.logits (+ b2), sample_rows_kernel].  No host synchronisation.  events (may be NULL):
+ * JLM_GENERATE_EVENTS_PER_FRAME * frames hipEvent_t, recorded on `stream` [0] before the LSTM step [1] after it [2] after the T
+ * projection [3] after the logit GEMMs [4] after the draw (prompt frames: empty brackets after [1]).  Returns 0, -2 for a model
+ * outside the loop's shapes, -1 / a hipError_t as the launchers do. */
+#define JLM_GENERATE_EVENTS_PER_FRAME 5
+int jlm_generate_frames(const jlm_decode_model *model_host, const jlm_generate_plan *plan_host, void *stream, void *const *events);
+
 #ifdef __cplusplus
 }
 #endif

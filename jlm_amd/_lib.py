@@ -6,7 +6,7 @@ has not been built (``python -c 'import __graft_entry__ as g; g.build()'``) and
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # JLM_HIP_LIB: developer override used by tools/ab_lib.sh to A/B two builds of the same ABI
@@ -72,6 +72,15 @@ class ScorePlan(Structure):
                 ("nll_seq", c_void_p), ("nll_tok", c_void_p), ("flags", c_void_p)]
 
 
+class GeneratePlan(Structure):
+    """jlm_generate_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_rows", c_int), ("n_prompt", c_int), ("n_words", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("T", c_void_p),
+                ("logits", c_void_p), ("ld_logits", c_int), ("rows", c_void_p), ("prev", c_void_p), ("prompt", c_void_p),
+                ("n_live", c_void_p), ("n_live_host", POINTER(c_int)), ("row_id", c_void_p), ("word", c_void_p), ("done", c_void_p),
+                ("stop_id", c_int), ("temperature", c_double), ("seed", c_uint64), ("ids", c_void_p), ("nll", c_void_p),
+                ("flags", c_void_p)]
+
+
 P = c_void_p
 _SIGS = {
     "jlm_abi_version": ([], c_int),
@@ -117,6 +126,8 @@ _SIGS = {
     "jlm_decode_frames": ([POINTER(DecodeModel), POINTER(DecodePlan), POINTER(Lattice), POINTER(BeamState), P, P, P], c_int),
     "jlm_lse_probe": ([POINTER(DecodeModel), P, P, P, c_int, c_int, P, P, P, P, c_int, c_int, P, c_int, P], c_int),
     "jlm_score_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), P, P], c_int),
+    "jlm_sample_rows": ([P, c_int, c_int, c_int, P, c_double, c_uint64, c_int, P, P, P, c_int, c_int, P, P, P, P, P], c_int),
+    "jlm_generate_frames": ([POINTER(DecodeModel), POINTER(GeneratePlan), P, P], c_int),
 }
 EXPORTS = sorted(_SIGS)
 

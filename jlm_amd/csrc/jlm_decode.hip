@@ -340,6 +340,28 @@ int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, co
                    int n_parts, int self_norm, const int *target, const int *n_dev, int n_rows_max, double *nll_seq, double *nll_tok,
                    int *flags, void *stream);
 
+// The LSTM step and the T projection of a row set's live prefix r < *ndev (bound: its static bound; g = rows[r] = r) -- the launches of
+// one step of jlm_score_frames and jlm_generate_frames.  f32_copy: the plain f32 copy of the new state an untied split-row model's
+// vocabulary GEMMs read (its T); T: the projection's destination (not written on untied models: T is the state there).
+static int rows_lstm_step(const jlm_decode_model *m, const void *h_in, const float *c_in, void *h_out, float *c_out, const int *rows,
+                          const int *prev, const int *word, float *f32_copy, int bound, const int *ndev, void *stream) {
+    if (m->split_lstm)
+        return jlm_lstm_step_xg(h_in, c_in, m->H, h_out, c_out, rows, prev, word, m->wt8, m->xgate8, m->H, m->gate_descale, m->h_scale,
+                                m->untied ? f32_copy : nullptr, bound, ndev, stream);
+    return jlm_lstm_step((const float *)h_in, c_in, m->H, (float *)h_out, c_out, rows, prev, word, m->emb, m->ld_emb, m->wt,
+                         m->gate_bias, m->kpad, m->H, m->E, bound, ndev, stream);
+}
+
+static int rows_t_projection(const jlm_decode_model *m, const void *h_out, const int *rows, float *T, int bound, const int *ndev,
+                             void *stream) {
+    if (m->untied) return 0;
+    if (m->split_lstm)
+        return jlm_gemm_nt_split(h_out, m->H, rows, m->pmt_split, m->H, nullptr, T, m->ldt, rows, nullptr, m->t_descale, bound, m->n_t,
+                                 m->H, ndev, stream);
+    return jlm_gemm_nt((const float *)h_out, m->H, rows, m->pmt, m->H, nullptr, T, m->ldt, rows, nullptr, bound, m->n_t, m->H, ndev,
+                       stream);
+}
+
 // Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),
 // T, the full-vocabulary normaliser as the frame loop launches it for kind 0, and the fold into -log p of the target word.
 extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
@@ -368,23 +390,9 @@ extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan 
         const int *prev = t == 0 ? p->prev0 : p->rows;
         float *T = t_is_h ? (float *)h_out : p->T;
         JLM_TRY(stamp(t, 0));
-        if (bound > 0) {
-            if (m->split_lstm)
-                JLM_TRY(jlm_lstm_step_xg(h_in, c_in, m->H, h_out, c_out, p->rows, prev, word, m->wt8, m->xgate8, m->H, m->gate_descale,
-                                         m->h_scale, m->untied ? p->T : nullptr, bound, ndev, stream));
-            else
-                JLM_TRY(jlm_lstm_step((const float *)h_in, c_in, m->H, (float *)h_out, c_out, p->rows, prev, word, m->emb, m->ld_emb,
-                                      m->wt, m->gate_bias, m->kpad, m->H, m->E, bound, ndev, stream));
-        }
+        if (bound > 0) JLM_TRY(rows_lstm_step(m, h_in, c_in, h_out, c_out, p->rows, prev, word, p->T, bound, ndev, stream));
         JLM_TRY(stamp(t, 1));
-        if (bound > 0 && !m->untied) {
-            if (m->split_lstm)
-                JLM_TRY(jlm_gemm_nt_split(h_out, m->H, p->rows, m->pmt_split, m->H, nullptr, T, m->ldt, p->rows, nullptr, m->t_descale,
-                                          bound, m->n_t, m->H, ndev, stream));
-            else
-                JLM_TRY(jlm_gemm_nt((const float *)h_out, m->H, p->rows, m->pmt, m->H, nullptr, T, m->ldt, p->rows, nullptr, bound,
-                                    m->n_t, m->H, ndev, stream));
-        }
+        if (bound > 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, bound, ndev, stream));
         JLM_TRY(stamp(t, 2));
         int n_parts = 0;
         if (bound > 0 && !m->self_norm) {
@@ -398,6 +406,58 @@ extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan 
             JLM_TRY(jlm_score_fold(m->segs, m->n_segs, m->b2, T, m->ldt, p->part, R, n_parts, m->self_norm, target, ndev, bound,
                                    p->nll_seq, p->nll_tok ? p->nll_tok + (size_t)t * R : nullptr, p->flags, stream));
         JLM_TRY(stamp(t, 4));
+    }
+    return 0;
+}
+
+// Ancestral sampling (include/jlm_hip.h jlm_generate_frames): the prompt frames step the LSTM of their live prefix only; every drawing
+// frame steps all rows, projects T, materialises the full-vocabulary logits (one jlm_gemm_nt per segment, columns v_start .. v_end of
+// plan.logits, + b2) and draws with sample_rows_kernel, which also writes the word the next frame consumes.
+extern "C" int jlm_generate_frames(const jlm_decode_model *m, const jlm_generate_plan *p, void *stream, void *const *events) {
+    const int R = p->n_rows, P = p->n_prompt, N = p->n_words;
+    if (R < 0 || P < 1 || N < 0 || !p->rows || !p->prev || !p->prompt || !p->n_live || !p->n_live_host || !p->word || !p->ids || !p->nll ||
+        !p->logits)
+        return -1;
+    if (R == 0 || N == 0) return 0;
+    if (m->split_lstm && !m->wt8) return -2;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
+    if (p->n_live_host[P - 1] != R) return -1;                  // every row is live at the last prompt frame (right-aligned prompts)
+    const bool t_is_h = m->untied && !m->split_lstm;
+    if (!t_is_h && !p->T) return -1;
+    hipStream_t main_s = (hipStream_t)stream;
+    auto stamp = [&](int f, int i) -> int {
+        if (!events) return 0;
+        return (int)hipEventRecord((hipEvent_t)events[(size_t)f * JLM_GENERATE_EVENTS_PER_FRAME + i], main_s);
+    };
+    const int F = P + N - 1;
+    for (int f = 0; f < F; ++f) {
+        const bool prompt = f < P;
+        const int bound = prompt ? p->n_live_host[f] : R;
+        if (bound < 0 || bound > R) return -1;
+        const int *ndev = prompt ? p->n_live + f : nullptr;
+        const int *word = prompt ? p->prompt + (size_t)f * R : p->word;
+        const int *prev = prompt ? p->prev + (size_t)f * R : p->rows;
+        void *h_in = p->h[f & 1], *h_out = p->h[(f + 1) & 1];
+        float *c_in = p->c[f & 1], *c_out = p->c[(f + 1) & 1];
+        float *T = t_is_h ? (float *)h_out : p->T;
+        JLM_TRY(stamp(f, 0));
+        if (bound > 0) JLM_TRY(rows_lstm_step(m, h_in, c_in, h_out, c_out, p->rows, prev, word, p->T, bound, ndev, stream));
+        JLM_TRY(stamp(f, 1));
+        const int k = f - (P - 1);                                   // the draw of this frame, if any
+        if (k >= 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, R, nullptr, stream));
+        JLM_TRY(stamp(f, 2));
+        if (k >= 0)
+            for (int i = 0; i < m->n_segs; ++i) {
+                const jlm_segment &sg = m->segs[i];
+                JLM_TRY(jlm_gemm_nt(T + sg.t_off, m->ldt, nullptr, sg.B, sg.ldb, nullptr, p->logits + sg.v_start, p->ld_logits, nullptr,
+                                    m->b2 + sg.v_start, R, sg.v_end - sg.v_start, sg.k, nullptr, stream));
+            }
+        JLM_TRY(stamp(f, 3));
+        if (k >= 0)
+            JLM_TRY(jlm_sample_rows(p->logits, p->ld_logits, V, R, nullptr, p->temperature, p->seed, k, p->row_id, nullptr, p->done,
+                                    p->stop_id, m->self_norm, p->word, p->ids + (size_t)k * R, p->nll + (size_t)k * R, p->flags, stream));
+        JLM_TRY(stamp(f, 4));
     }
     return 0;
 }

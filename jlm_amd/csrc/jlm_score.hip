@@ -136,3 +136,263 @@ int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, co
     JLM_LAUNCH_CHECK();
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// sample_rows_kernel -- one ancestral-sampling draw per live row of materialised f32 logits y[r, 0:n_cols] (jlm_sample_rows,
+// include/jlm_hip.h; the last kernel of a jlm_generate_frames frame).  What the reference's sample(pred, temperature) does on the host
+// (decoder/model.py:28-33, 213-245), as an inverse CDF in word-id order with counter-based random numbers.
+//
+// One workgroup of SR_WAVES waves per row.  The row is read as 16-byte chunks (4 words): an "iteration" is 64 consecutive chunks, one
+// per lane (coalesced, 1 KB per wave load), and wave w owns the contiguous iterations [w * ipw, (w + 1) * ipw) -- wave spans in word
+// order.  Three passes over a row:
+//   1  max m (and the lowest id attaining it: the greedy draw), every wave over its span, merged in wave order.
+//   2  per iteration, each lane's chunk mass ((e0 + e1) + e2) + e3 (e = expf((y - m) / tau) in f32, summed in f64), an inclusive
+//      Hillis-Steele scan of those over the 64 lanes, and the wave total W_w += the scan's last lane; beside it the tau = 1 sum
+//      S1 = sum expf(y - m) (lane-sequential, xor-tree over the wave) for the nll.  S = ((W_0 + W_1) + W_2) + W_3.
+//   3  t = u S; the wave w whose prefix first exceeds t re-reads its span ALONE, recomputing pass 2's chunk masses and scans in the
+//      same order (bit-identical W_w chain), and stops in the iteration where acc + total > t - P_w: the first lane whose
+//      acc + scan > t - P_w, then the first word of that lane's chunk whose running sum crosses.  Where rounding leaves no crossing
+//      (t - P_w rounded up, or a lane's own sum short of its scan value by an ulp) the draw is the last word with non-zero mass
+//      before that point.
+// The summation order is a fixed function of n_cols and the launch shape: the same row gives the same draw on every run.
+#define SR_WAVES 4
+#define SR_THREADS (64 * SR_WAVES)
+#define SR_UNROLL 4
+
+__device__ __forceinline__ double sr_uniform(unsigned long long seed, int step, int row) {
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (((unsigned long long)(unsigned)step << 32) | ((unsigned long long)(unsigned)row + 1ull));
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return ((double)(z >> 11) + 0.5) * 0x1.0p-53;
+}
+
+// chunk c's words; words past n_cols read as -inf (the row's padding is never trusted)
+__device__ __forceinline__ f32x4 sr_load(const f32x4 *row, int c, int n4, int n_cols) {
+    f32x4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (c < n4) {
+        v = row[c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * c + j >= n_cols) v[j] = -INFINITY;
+    }
+    return v;
+}
+
+// the tempered masses of a chunk (pass 2 and pass 3 call this same code, so both see the same bits)
+__device__ __forceinline__ f32x4 sr_mass(const f32x4 v, float m, float inv_tau) {
+    f32x4 e;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) e[j] = expf((v[j] - m) * inv_tau);
+    return e;
+}
+
+__device__ __forceinline__ double sr_chunk_sum(const f32x4 e) {
+    double c = (double)e[0];
+    c += (double)e[1];
+    c += (double)e[2];
+    c += (double)e[3];
+    return c;
+}
+
+__device__ __forceinline__ double sr_scan(double c, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double t = __shfl_up(c, off);
+        if (lane >= off) c += t;
+    }
+    return c;
+}
+
+template <int SELF_NORM>
+__global__ __launch_bounds__(SR_THREADS) void sample_rows_kernel(
+    const float *__restrict__ y, int ld, int n_cols, const int *__restrict__ n_dev, int n_rows_max, int greedy, float inv_tau,
+    unsigned long long seed, int step, const int *__restrict__ row_id, const int *__restrict__ forced, int *__restrict__ done,
+    int stop_id, int *__restrict__ word, int *__restrict__ ids, double *__restrict__ nll, int *flags) {
+    const int r = blockIdx.x;
+    const int n = n_dev ? min(*n_dev, n_rows_max) : n_rows_max;
+    if (r >= n) return;                                   // uniform over the workgroup: no barrier is skipped by part of it
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (forced && forced[r] >= 0) {                       // a forced (prompt) position: its word passes through
+        if (tid == 0) { word[r] = forced[r]; ids[r] = -1; nll[r] = 0.0; }
+        return;
+    }
+    if (done && done[r]) {                                // a row that has drawn its stop word: masked (its word stays valid)
+        if (tid == 0) { ids[r] = -1; nll[r] = 0.0; }
+        return;
+    }
+    const f32x4 *row = reinterpret_cast<const f32x4 *>(y + (size_t)r * ld);
+    const int n4 = (n_cols + 3) >> 2, n_it = (n4 + 63) >> 6;
+    const int ipw = (n_it + SR_WAVES - 1) / SR_WAVES;
+    const int it0 = wv * ipw, it1 = min(it0 + ipw, n_it);
+    __shared__ float s_m[SR_WAVES];
+    __shared__ int s_i[SR_WAVES];
+    __shared__ double s_w[SR_WAVES], s_s1[SR_WAVES];
+
+    // ---- pass 1: max, lowest id attaining it
+    float m = -INFINITY;
+    int mi = 0x7fffffff;
+    for (int it = it0; it < it1; it += SR_UNROLL) {
+        f32x4 v[SR_UNROLL];
+#pragma unroll
+        for (int k = 0; k < SR_UNROLL; ++k) v[k] = it + k < it1 ? sr_load(row, (it + k) * 64 + lane, n4, n_cols) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+        for (int k = 0; k < SR_UNROLL; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (v[k][j] > m) { m = v[k][j]; mi = 4 * ((it + k) * 64 + lane) + j; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float m2 = __shfl_xor(m, off);
+        const int i2 = __shfl_xor(mi, off);
+        if (m2 > m || (m2 == m && i2 < mi)) { m = m2; mi = i2; }
+    }
+    if (lane == 0) { s_m[wv] = m; s_i[wv] = mi; }
+    __syncthreads();
+    m = s_m[0];
+    mi = s_i[0];
+    for (int w = 1; w < SR_WAVES; ++w)
+        if (s_m[w] > m) { m = s_m[w]; mi = s_i[w]; }      // waves in word order: a tie keeps the earlier wave's (lower) id
+
+    // ---- pass 2: the tempered chunk masses' scans (wave totals) and the tau = 1 sum
+    const bool fin_m = m > -INFINITY && m < INFINITY;
+    const bool same = inv_tau == 1.0f;
+    double W = 0.0, s1 = 0.0;
+    if (fin_m && !(greedy && SELF_NORM)) {
+        for (int it = it0; it < it1; it += SR_UNROLL) {
+            f32x4 v[SR_UNROLL];
+#pragma unroll
+            for (int k = 0; k < SR_UNROLL; ++k) v[k] = it + k < it1 ? sr_load(row, (it + k) * 64 + lane, n4, n_cols) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+            for (int k = 0; k < SR_UNROLL; ++k) {
+                if (it + k >= it1) break;                 // wave-uniform
+                const f32x4 e1 = sr_mass(v[k], m, 1.0f);
+                if (!SELF_NORM) {
+                    s1 += (double)e1[0];
+                    s1 += (double)e1[1];
+                    s1 += (double)e1[2];
+                    s1 += (double)e1[3];
+                }
+                if (!greedy) {
+                    const f32x4 e = same ? e1 : sr_mass(v[k], m, inv_tau);
+                    const double s = sr_scan(sr_chunk_sum(e), lane);
+                    W += __shfl(s, 63);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s1 += __shfl_xor(s1, off);
+    if (lane == 0) { s_w[wv] = W; s_s1[wv] = s1; }
+    __syncthreads();
+    double S = 0.0, S1 = 0.0;
+    for (int w = 0; w < SR_WAVES; ++w) { S += s_w[w]; S1 += s_s1[w]; }
+    const bool ok = fin_m && (greedy || (S > 0.0 && S < INFINITY)) && (SELF_NORM || (S1 > 0.0 && S1 < INFINITY));
+    if (!ok) {                                            // a NaN / inf logit: flagged; the row's next word stays a valid id
+        if (tid == 0) {
+            if (flags) atomicOr(flags, 1);
+            ids[r] = -1;
+            nll[r] = __longlong_as_double(0x7ff8000000000000LL);
+            word[r] = 0;
+            if (done) done[r] = 1;
+        }
+        return;
+    }
+
+    // ---- pass 3: the crossing
+    int pick = mi, writer = 0;
+    if (!greedy) {
+        const double t = sr_uniform(seed, step, row_id ? row_id[r] : r) * S;
+        int ws = -1;
+        double tp = INFINITY, P = 0.0;
+        for (int w = 0; w < SR_WAVES; ++w) {
+            const double Pn = P + s_w[w];
+            if (Pn > t) { ws = w; tp = t - P; break; }
+            P = Pn;
+        }
+        if (ws < 0)                                       // u S rounded up to S: the last word with mass, i.e. of the last such wave
+            for (int w = 0; w < SR_WAVES; ++w)
+                if (s_w[w] > 0.0) ws = w;
+        if (wv != ws) return;
+        writer = ws * 64;
+        double acc = 0.0;
+        int last = -1;                                    // the lane's last word with non-zero mass so far
+        pick = -1;
+        bool crossed = false;
+        for (int it = it0; it < it1 && !crossed; it += SR_UNROLL) {
+            f32x4 v[SR_UNROLL];
+#pragma unroll
+            for (int k = 0; k < SR_UNROLL; ++k) v[k] = it + k < it1 ? sr_load(row, (it + k) * 64 + lane, n4, n_cols) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+            for (int k = 0; k < SR_UNROLL; ++k) {
+                if (it + k >= it1) break;
+                const int c = (it + k) * 64 + lane;
+                const f32x4 e = same ? sr_mass(v[k], m, 1.0f) : sr_mass(v[k], m, inv_tau);
+                const double s = sr_scan(sr_chunk_sum(e), lane);
+                const double total = __shfl(s, 63);
+                int lnz = -1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (e[j] > 0.0f) lnz = 4 * c + j;
+                if (acc + total > tp) {
+                    const unsigned long long b = __ballot(acc + s > tp);     // lane 63 at least: its scan value is `total`
+                    const int l = __ffsll(b) - 1;
+                    const double prev = __shfl_up(s, 1);
+                    int cand = -1;
+                    if (lane == l) {
+                        double cum = lane == 0 ? 0.0 : prev;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            cum += (double)e[j];
+                            if (cand < 0 && acc + cum > tp) cand = 4 * c + j;
+                        }
+                        if (cand < 0) cand = lnz;
+                    }
+                    int val = lane < l ? lnz : (lane == l ? cand : -1);
+                    val = max(val, last);
+#pragma unroll
+                    for (int off = 32; off >= 1; off >>= 1) val = max(val, __shfl_xor(val, off));
+                    pick = val;
+                    crossed = true;
+                    break;
+                }
+                acc += total;
+                if (lnz >= 0) last = lnz;
+            }
+        }
+        if (!crossed) {                                   // rounding left no crossing in the span: its last word with mass
+            int val = last;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) val = max(val, __shfl_xor(val, off));
+            pick = val;
+        }
+        if (pick < 0 || pick >= n_cols) pick = mi;       // (unreachable: wave ws holds mass)
+    }
+    if (tid != writer) return;
+    const float yv = y[(size_t)r * ld + pick];
+    ids[r] = pick;
+    word[r] = pick;
+    nll[r] = SELF_NORM ? -(double)yv : ((double)m + log(S1)) - (double)yv;
+    if (done && pick == stop_id) done[r] = 1;
+}
+
+extern "C" int jlm_sample_rows(const float *y, int ld_y, int n_cols, int n_rows_max, const int *n_dev, double temperature,
+                               uint64_t seed, int step, const int *row_id, const int *forced, int *done, int stop_id, int self_norm,
+                               int *word, int *ids, double *nll, int *flags, void *stream) {
+    if (n_cols < 1 || ld_y % 4 != 0 || ld_y < ((n_cols + 3) & ~3) || ((uintptr_t)y & 15) != 0) return -1;
+    if (!(temperature >= 0.0 && temperature < INFINITY) || !word || !ids || !nll) return -1;
+    if (n_rows_max <= 0) return 0;
+    const int greedy = temperature == 0.0;
+    const float inv_tau = greedy ? 1.0f : (float)(1.0 / temperature);
+    if (!greedy && !(inv_tau > 0.0f && inv_tau < INFINITY)) return -1;
+    const dim3 grid(n_rows_max);
+    if (self_norm)
+        hipLaunchKernelGGL(sample_rows_kernel<1>, grid, dim3(SR_THREADS), 0, (hipStream_t)stream, y, ld_y, n_cols, n_dev, n_rows_max,
+                           greedy, inv_tau, (unsigned long long)seed, step, row_id, forced, done, stop_id, word, ids, nll, flags);
+    else
+        hipLaunchKernelGGL(sample_rows_kernel<0>, grid, dim3(SR_THREADS), 0, (hipStream_t)stream, y, ld_y, n_cols, n_dev, n_rows_max,
+                           greedy, inv_tau, (unsigned long long)seed, step, row_id, forced, done, stop_id, word, ids, nll, flags);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}

@@ -16,6 +16,9 @@
 //   torch.ops.jlm.frame_times(Plan) -> Tensor [n_frames, 5] milliseconds of the last timed decode (after it finished)
 //   torch.ops.jlm.score_frames(Model, state row sets, ..., word, target, n_live, nll outputs, ...)
 //                             teacher-forced scoring of many sequences: ONE op (jlm_score_frames; LSTM_Model.score)
+//   torch.ops.jlm.sample_rows(y, ..., word, ids, nll, flags)   one draw per row of materialised logits (jlm_sample_rows)
+//   torch.ops.jlm.generate_frames(Model, state row sets, logits, prompt arrays, ..., ids, nll, ...)
+//                             batched ancestral sampling: ONE op (jlm_generate_frames; LSTM_Model.generate)
 //   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
@@ -524,6 +527,96 @@ Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0,
     return out;
 }
 
+// one draw per row of f32 logits y [n_rows, ld] (jlm_sample_rows, include/jlm_hip.h).  seed: the uint64 seed's bits as int64.
+void sample_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, double temperature, int64_t seed,
+                 int64_t step, const OptTensor &row_id, const OptTensor &forced, const OptTensor &done, int64_t stop_id, bool self_norm,
+                 const Tensor &word, const Tensor &ids, const Tensor &nll, const OptTensor &flags) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    auto opt_ok = [&](const OptTensor &t, at::ScalarType ty, int64_t n) { return !t.has_value() || !t->defined() || is(*t, ty, n); };
+    TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.sample_rows: y [n_rows, ld] float32");
+    TORCH_CHECK(is(word, at::kInt, n_rows) && is(ids, at::kInt, n_rows) && is(nll, at::kDouble, n_rows) && opt_ok(n_dev, at::kInt, 1) &&
+                    opt_ok(row_id, at::kInt, n_rows) && opt_ok(forced, at::kInt, n_rows) && opt_ok(done, at::kInt, n_rows) &&
+                    opt_ok(flags, at::kInt, 1),
+                "jlm.sample_rows: int32 word / ids / row_id / forced / done [n_rows], n_dev / flags [1]; float64 nll [n_rows]");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    jlm_check(jlm_sample_rows(ptr<const float>(y, "y"), (int)ld, (int)n_cols, (int)n_rows, optr<const int>(n_dev, "n_dev"), temperature,
+                              (uint64_t)seed, (int)step, optr<const int>(row_id, "row_id"), optr<const int>(forced, "forced"),
+                              optr<int>(done, "done"), (int)stop_id, self_norm ? 1 : 0, ptr<int>(word, "word"), ptr<int>(ids, "ids"),
+                              ptr<double>(nll, "nll"), optr<int>(flags, "flags"), stream_of(y)),
+              "jlm_sample_rows");
+}
+
+// batched ancestral sampling (jlm_generate_frames, include/jlm_hip.h): state row sets h0/c0 and h1/c1 (ping-pong), T [n_rows, ldt]
+// unless the model is untied f32, logits [n_rows, ld_logits]; rows / row_id / word / done [n_rows], prev / prompt [n_prompt][n_rows],
+// n_live [n_prompt] int32 and its host copy; ids [n_words][n_rows] int32, nll [n_words][n_rows] f64, flags one int32.  Every id must
+// lie in [0, V): the caller checks (jlm_amd/generate.py).  -> timed: [frames, 4] milliseconds per frame (LSTM step, T projection,
+// logit GEMMs, draw) after waiting for the last frame; else an empty tensor and nothing waits.
+Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
+                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &row_id,
+                       const Tensor &word, const OptTensor &done, int64_t stop_id, double temperature, int64_t seed, const Tensor &ids,
+                       const Tensor &nll, const OptTensor &flags, int64_t n_rows, int64_t n_prompt, int64_t n_words, bool timed) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, P = n_prompt, N = n_words;
+    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(R >= 0 && P >= 1 && N >= 0 && (int64_t)n_live_host.size() == P, "jlm.generate_frames: n_live_host holds one count per prompt frame");
+    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= R, "jlm.generate_frames: a live-row count outside [0, n_rows]");
+    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
+                    is(c0, at::kFloat, R * m.H) && is(c1, at::kFloat, R * m.H),
+                "jlm.generate_frames: state row sets [n_rows, H] of 4-byte values");
+    TORCH_CHECK(is(rows, at::kInt, R) && is(row_id, at::kInt, R) && is(word, at::kInt, R) && (!has(done) || is(*done, at::kInt, R)) &&
+                    is(prev, at::kInt, P * R) && is(prompt, at::kInt, P * R) && is(n_live, at::kInt, P),
+                "jlm.generate_frames: int32 rows / row_id / word / done [n_rows], prev / prompt [n_prompt][n_rows], n_live [n_prompt]");
+    TORCH_CHECK(is(ids, at::kInt, N * R) && is(nll, at::kDouble, N * R) && (!has(flags) || is(*flags, at::kInt, 1)),
+                "jlm.generate_frames: int32 ids / float64 nll [n_words][n_rows], int32 flags");
+    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.generate_frames: T [n_rows, ldt] float32");
+    TORCH_CHECK(is(logits, at::kFloat, R * ld_logits), "jlm.generate_frames: logits [n_rows, ld_logits] float32");
+    jlm_generate_plan p{};
+    p.n_rows = (int)R; p.n_prompt = (int)P; p.n_words = (int)N;
+    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+    p.T = optr<float>(T, "T");
+    p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits;
+    p.rows = ptr<const int>(rows, "rows"); p.prev = ptr<const int>(prev, "prev"); p.prompt = ptr<const int>(prompt, "prompt");
+    p.n_live = ptr<const int>(n_live, "n_live");
+    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
+    p.n_live_host = live_host.data();
+    p.row_id = ptr<const int>(row_id, "row_id"); p.word = ptr<int>(word, "word"); p.done = optr<int>(done, "done");
+    p.stop_id = (int)stop_id; p.temperature = temperature; p.seed = (uint64_t)seed;
+    p.ids = ptr<int>(ids, "ids"); p.nll = ptr<double>(nll, "nll"); p.flags = optr<int>(flags, "flags");
+    const int dev = h0.device().index();
+    const c10::hip::HIPGuard device_guard(dev);
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
+    const int64_t F = N > 0 ? P + N - 1 : 0;
+    std::vector<hipEvent_t> ev;
+    struct Destroy {
+        std::vector<hipEvent_t> &ev;
+        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } destroy{ev};
+    if (timed)
+        for (int64_t i = 0; i < F * JLM_GENERATE_EVENTS_PER_FRAME; ++i) {
+            hipEvent_t e;
+            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
+            ev.push_back(e);
+        }
+    {
+        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
+        jlm_check(jlm_generate_frames(&m, &p, st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), "jlm_generate_frames");
+    }
+    if (!timed || F == 0 || R == 0) return at::empty({0}, at::kDouble);
+    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
+    Tensor out = at::zeros({F, JLM_GENERATE_EVENTS_PER_FRAME - 1}, at::kDouble);
+    auto a = out.accessor<double, 2>();
+    for (int64_t f = 0; f < F; ++f)
+        for (int i = 0; i + 1 < JLM_GENERATE_EVENTS_PER_FRAME; ++i) {
+            float ms = 0.0f;
+            jlm_check((int)hipEventElapsedTime(&ms, ev[f * JLM_GENERATE_EVENTS_PER_FRAME + i], ev[f * JLM_GENERATE_EVENTS_PER_FRAME + i + 1]),
+                      "hipEventElapsedTime");
+            a[f][i] = ms;
+        }
+    return out;
+}
+
 int64_t abi_version() { return jlm_abi_version(); }
 int64_t beam_step_max_cands(int64_t beam, int64_t n_frames, int64_t mode) { return jlm_beam_step_max_cands((int)beam, (int)n_frames, (int)mode); }
 
@@ -558,6 +651,14 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
           "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed) -> Tensor",
           score_frames);
+    m.def("sample_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, float temperature, int seed, int step, Tensor? row_id, "
+          "Tensor? forced, Tensor(a!)? done, int stop_id, bool self_norm, Tensor(b!) word, Tensor(c!) ids, Tensor(d!) nll, Tensor(e!)? flags) -> ()",
+          sample_rows);
+    m.def("generate_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev, Tensor prompt, Tensor n_live, int[] n_live_host, Tensor row_id, "
+          "Tensor(g!) word, Tensor(h!)? done, int stop_id, float temperature, int seed, Tensor(i!) ids, Tensor(j!) nll, Tensor(k!)? flags, "
+          "int n_rows, int n_prompt, int n_words, bool timed) -> Tensor",
+          generate_frames);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

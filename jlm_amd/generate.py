@@ -1,0 +1,267 @@
+"""Batched ancestral sampling on the device: ``LSTM_Model.generate`` and ``python -m jlm_amd.generate``.
+
+The reference checks a language model by sampling from it: decoder/model.py:213-245 starts at ``<eos>`` and draws words one
+``predict()`` at a time with ``sample(pred, temperature)`` (model.py:28-33), and train/test.py is an interactive form of the same
+check.  Here one call is ONE op (``torch.ops.jlm.generate_frames``, csrc/jlm_decode.hip ``jlm_generate_frames``) over many rows: per
+frame the LSTM step, the T projection, the full-vocabulary logits (``jlm_gemm_nt`` per segment) and ``sample_rows_kernel``
+(csrc/jlm_score.hip), which draws each row's next word by an inverse CDF in word-id order and feeds it to the next frame on the device.
+
+Semantics (pinned by tests/test_generate_cpu.py and tests/test_gpu_generate.py):
+  - row r starts from the zero state, consumes its prompt teacher-forced, then draws ``n_words`` words, each from
+    softmax(y / temperature) over the full vocabulary (temperature 0: the argmax, the lowest id winning a tie);
+  - draw ``step`` of row ``row`` (its index in the caller's list) uses u = :func:`uniform` (seed, step, row), so the result does not
+    depend on how rows are cut into calls or on the other rows' prompts;
+  - nll is the draw's -log p at temperature 1 (score()'s convention: lse - y, -y for self-normalised models).
+
+Prompts are right-aligned: rows are sorted by prompt length, longest first, so the rows a prompt frame steps are a prefix and every
+row draws at the same frames.
+"""
+import argparse
+import sys
+import time
+
+import numpy as np
+
+from . import _lib
+from . import config as _config
+from . import ops as _ops
+from .score import check_ids
+
+# the logit buffer is rows x V x 4 bytes (V = 100 k: 1 GB at 2 560 rows); 2 560 rows fill the logit GEMM's tiles on every CU
+MAX_ROWS = 2560
+GENERATE_BUDGET_BYTES = 3 << 29
+# <eos>: index 1 of both Vocab and CharVocab (the lexicon's first entry, behind <unk>; jlm_amd/data.py) -- the reference's starting_text
+EOS_ID = 1
+
+_M64 = (1 << 64) - 1
+
+
+def uniform(seed, step, row):
+    """The draw's uniform u in (0, 1): splitmix64 of a (step, row) counter (include/jlm_hip.h jlm_sample_rows).  numpy-broadcasting
+    over ``step`` and ``row``; -> float64 array."""
+    with np.errstate(over="ignore"):
+        step = np.asarray(step, dtype=np.uint64)
+        row = np.asarray(row, dtype=np.uint64)
+        z = np.uint64(int(seed) & _M64) + np.uint64(0x9E3779B97F4A7C15) * ((step << np.uint64(32)) | (row + np.uint64(1)))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
+
+
+def inverse_cdf(mass, u):
+    """The draw for masses ``mass`` (one row, word-id order) and u: the smallest i with cumsum(mass)[i] > u * sum(mass); the last word
+    with non-zero mass when rounding leaves no crossing."""
+    c = np.cumsum(np.asarray(mass, dtype=np.float64))
+    i = int(np.searchsorted(c, u * c[-1], side="right"))
+    if i >= len(c):
+        i = int(np.nonzero(np.asarray(mass) > 0)[0][-1])
+    return i
+
+
+def check_args(prompts, n_words, temperature, seed, stop_id, V):
+    """ValueError for anything the kernels cannot take, before any launch.  -> prompts as int64 arrays"""
+    if isinstance(n_words, bool) or not isinstance(n_words, (int, np.integer)) or n_words < 0:
+        raise ValueError("n_words must be an integer >= 0 (got %r)" % (n_words,))
+    t = float(temperature)
+    if not np.isfinite(t) or t < 0:
+        raise ValueError("temperature must be finite and >= 0 (got %r)" % (temperature,))
+    if not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= _M64:
+        raise ValueError("seed must be an integer in [0, 2^64) (got %r)" % (seed,))
+    if prompts is None:
+        prompts = [[EOS_ID]]
+    out = []
+    for i, p in enumerate(prompts):
+        a = np.asarray(p, dtype=np.int64).ravel()
+        if a.size == 0:
+            raise ValueError("prompt %d is empty (a row needs at least one word to start from; the reference starts at <eos>)" % i)
+        check_ids(a, V, "generate (prompt %d)" % i)
+        out.append(a)
+    if len(out) >= 2 ** 31:
+        raise ValueError("too many rows")
+    if stop_id is not None:
+        check_ids([stop_id], V, "generate (stop_id)")
+    return out
+
+
+def plan_rows(lengths, max_rows):
+    """Rows sorted by prompt length, longest first (stable), cut into chunks of at most ``max_rows``.  -> list of dict(idx = the
+    caller's row of each chunk row, lens, n_prompt = the longest, n_live [n_prompt] = rows a prompt frame steps)."""
+    if max_rows < 1:
+        raise ValueError("max_rows must be >= 1")
+    lens = np.asarray(lengths, dtype=np.int64)
+    order = np.argsort(-lens, kind="stable")
+    chunks = []
+    for i in range(0, len(order), max_rows):
+        idx = order[i:i + max_rows]
+        L = lens[idx]
+        P = int(L[0])
+        n_live = (L[None, :] >= P - np.arange(P)[:, None]).sum(axis=1).astype(np.int32)
+        chunks.append(dict(idx=idx, lens=L, n_prompt=P, n_live=n_live))
+    return chunks
+
+
+def prompt_arrays(prompts, n_prompt):
+    """prompt / prev [n_prompt, R] int32 of right-aligned prompts (longest first): row r consumes its prompt at frames
+    n_prompt - len .. n_prompt - 1 and starts from the zero state (prev -1) at the first of them; elsewhere prev = r.  Positions
+    before a row's start hold word 0 and prev -1 (never read: the row is not live there)."""
+    R = len(prompts)
+    prompt = np.zeros((n_prompt, R), dtype=np.int32)
+    prev = np.tile(np.arange(R, dtype=np.int32), (n_prompt, 1))
+    for r, p in enumerate(prompts):
+        f0 = n_prompt - len(p)
+        prompt[f0:, r] = p
+        prev[:f0 + 1, r] = -1
+    return prompt, prev
+
+
+def truncate(ids, stop_id):
+    """a row's draws up to and including its first ``stop_id`` (all of them without one)"""
+    if stop_id is None:
+        return ids
+    hit = np.nonzero(ids == stop_id)[0]
+    return ids[:hit[0] + 1] if len(hit) else ids
+
+
+class Generator:
+    """The device side of a sampling call over a :class:`jlm_amd.model.DeviceModel`."""
+
+    def __init__(self, dev_model):
+        self.m = dev_model
+        self.torch = dev_model.torch
+        self.last_frame_ms = None         # [frames, 4] of the last timed call: LSTM step, T projection, logit GEMMs, draw
+
+    @property
+    def ld_logits(self):
+        return (self.m.V + 3) // 4 * 4
+
+    def row_bytes(self, n_prompt, n_words):
+        m = self.m
+        return (self.ld_logits + 4 * m.H + m.ldt) * 4 + n_prompt * 8 + n_words * 12 + 32
+
+    def max_rows(self, n_prompt, n_words):
+        """rows per call: MAX_ROWS, fewer when the call's buffers would exceed GENERATE_BUDGET_BYTES"""
+        k = GENERATE_BUDGET_BYTES // self.row_bytes(n_prompt, n_words)
+        return int(max(1, min(MAX_ROWS, k, (0x7ffffff0 // max(self.m.H // 4, 1)) - 1)))
+
+    def run(self, prompts, row_id, n_words, temperature, seed, stop_id=None, timed=False):
+        """One call over rows already sorted by prompt length (longest first).  row_id [R]: the caller's index of each row.
+        -> (ids [n_words, R] int32, nll [n_words, R] float64); a stopped row's later positions hold -1 / 0."""
+        torch, m = self.torch, self.m
+        R = len(prompts)
+        P = len(prompts[0])
+        prompt, prev = prompt_arrays(prompts, P)
+        n_live = (np.array([len(p) for p in prompts])[None, :] >= P - np.arange(P)[:, None]).sum(axis=1).astype(np.int32)
+        dev, f32, i32, f64 = m.device, torch.float32, torch.int32, torch.float64
+        s = int(seed) & _M64
+        s = s - (1 << 64) if s >= 1 << 63 else s
+        with m._ctx():
+            e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
+            hs = [e((R, m.H), f32), e((R, m.H), f32)]
+            cs = [e((R, m.H), f32), e((R, m.H), f32)]
+            untied_f32 = m.mode == "untied" and not m.split_lstm
+            T = None if untied_f32 else e((R, m.ldt), f32)
+            logits = e((R, self.ld_logits), f32)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+            rows = torch.arange(R, device=dev, dtype=i32)
+            word = torch.zeros(R, device=dev, dtype=i32)
+            done = torch.zeros(R, device=dev, dtype=i32) if stop_id is not None else None
+            ids = torch.full((n_words, R), -1, device=dev, dtype=i32)
+            nll = torch.zeros((n_words, R), device=dev, dtype=f64)
+            flags = torch.zeros(1, device=dev, dtype=i32)
+            ms = _ops.backend().generate_frames(m.decode_model(), hs[0], cs[0], hs[1], cs[1], T, logits, self.ld_logits, rows, up(prev),
+                                                up(prompt), up(n_live), [int(x) for x in n_live], up(row_id), word, done,
+                                                -1 if stop_id is None else int(stop_id), float(temperature), s, ids, nll, flags,
+                                                R, P, int(n_words), bool(timed))
+            if timed:
+                self.last_frame_ms = ms.numpy()
+            fl = int(flags.cpu()[0])
+            ids_h = ids.cpu().numpy()
+            nll_h = nll.cpu().numpy()
+        if fl:
+            raise _lib.JlmHipError("sample_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)" % fl)
+        return ids_h, nll_h
+
+
+def generate(gen, prompts, n_words, temperature=1.0, seed=0, stop_id=None, max_rows=None):
+    """LSTM_Model.generate: see there."""
+    prompts = check_args(prompts, n_words, temperature, seed, stop_id, gen.m.V)
+    lens = [len(p) for p in prompts]
+    ids_out = [np.zeros(0, dtype=np.int64) for _ in prompts]
+    nll_out = [np.zeros(0, dtype=np.float64) for _ in prompts]
+    if n_words == 0 or not prompts:
+        return ids_out, nll_out
+    if max_rows is None:
+        max_rows = gen.max_rows(max(lens), n_words)
+    for ch in plan_rows(lens, max_rows):
+        idx = ch["idx"]
+        ids, nll = gen.run([prompts[i] for i in idx], idx.astype(np.int32), int(n_words), temperature, seed, stop_id)
+        for j, i in enumerate(idx):
+            x = truncate(ids[:, j].astype(np.int64), stop_id)
+            ids_out[i] = x
+            nll_out[i] = nll[:len(x), j].copy()
+    return ids_out, nll_out
+
+
+def encode_prompt(text, vocab):
+    """``--prompt`` as ids: <eos>, then the words through Vocab.w2i (a character model: the characters of the surfaces through
+    CharVocab.c2i) with <unk> for anything outside it, as perplexity.encode_lines encodes a line -- without its trailing <eos>.
+    -> (ids, number of <unk> fallbacks)"""
+    from .data import CharVocab
+    from .perplexity import encode_lines
+    if text is None or not text.strip():
+        return [EOS_ID], 0
+    enc, n_unk = encode_lines([text], vocab)
+    eos = vocab.c2i["<eos>"] if isinstance(vocab, CharVocab) else vocab.w2i["<eos>"]
+    return [eos] + enc[0][:-1], n_unk
+
+
+def render(ids, vocab):
+    """the reference's print: ' '.join(x.split('/')[0] ...) over the words (a character model: the characters, joined)"""
+    from .data import CharVocab
+    if isinstance(vocab, CharVocab):
+        return "".join(vocab.i2c.get(int(i), "<unk>") for i in ids)
+    return " ".join(vocab.i2w[int(i)].split("/")[0] for i in ids)
+
+
+def main(argv=None):
+    from .data import CharVocab, Vocab
+    ap = argparse.ArgumentParser(description="Sample word sequences from a dumped model on the device (reference decoder/model.py:213-245)")
+    ap.add_argument("--root", default=None, help="JLM root (data/, train/experiments/); default $JLM_ROOT")
+    ap.add_argument("-e", "--experiment_id", type=int, default=0)
+    ap.add_argument("--comp", type=int, default=0, help="compressed weights (lstm_weights_comp_<comp>.pkl)")
+    ap.add_argument("-n", "--rows", type=int, default=1, help="samples to draw")
+    ap.add_argument("--words", type=int, default=100, help="words per sample")
+    ap.add_argument("--temperature", type=float, default=1.0, help="0 = greedy")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--prompt", default=None, help='words to continue, "w/r w/r ..." (default: start at <eos>)')
+    ap.add_argument("--stop-at-eos", action="store_true", help="end a sample after it draws <eos>")
+    ap.add_argument("--show-nll", action="store_true", help="append each sample's total -log p and its word count")
+    args = ap.parse_args(argv)
+    if args.root:
+        _config.set_root(args.root)
+    from .model import LSTM_Model
+    config = _config.load_config_dict(args.experiment_id)
+    vocab = (CharVocab if config.get("char_rnn") else Vocab)(config["vocab_size"])
+    prompt, n_unk = encode_prompt(args.prompt, vocab)
+    if n_unk:
+        print("prompt: %d word(s) outside the vocabulary read as <unk>" % n_unk, file=sys.stderr)
+    model = LSTM_Model(experiment_id=args.experiment_id, comp=args.comp)
+    t0 = time.time()
+    ids, nll = model.generate([prompt] * args.rows, args.words, temperature=args.temperature, seed=args.seed,
+                              stop_id=EOS_ID if args.stop_at_eos else None)
+    dt = time.time() - t0
+    head = render(prompt[1:], vocab)
+    sep = "" if isinstance(vocab, CharVocab) or not head else " "
+    for x, l in zip(ids, nll):
+        line = head + sep + render(x, vocab)
+        if args.show_nll:
+            line += "\t%.4f\t%d" % (float(l.sum()), len(x))
+        print(line)
+    n_tok = sum(len(x) for x in ids)
+    print("rows: {}  words: {}  words/s: {:.0f}".format(len(ids), n_tok, n_tok / dt if dt > 0 else float("inf")), file=sys.stderr)
+    return ids, nll
+
+
+if __name__ == "__main__":
+    main()

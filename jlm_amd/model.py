@@ -1032,6 +1032,20 @@ class LSTM_Model():
         _seq, tok, h2, c2 = self._scorer().run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
         return np.ascontiguousarray(tok.T), h2, c2
 
+    def generate(self, prompts=None, n_words=100, temperature=1.0, seed=0, stop_id=None, max_rows=None):
+        """Ancestral sampling on the device (jlm_amd/generate.py): the reference's sampling loop (model.py:213-245, one predict() and
+        one sample() per word) for many rows at once.  ``prompts``: R word-id lists of length >= 1 (None: one row starting at <eos>, the
+        reference's starting_text).  Row r starts from the zero state, consumes its prompt, then draws ``n_words`` words from
+        softmax(y / temperature) (0: greedy, the lowest id winning a tie) with the counter-based u of generate.uniform(seed, step, r);
+        with ``stop_id`` a row ends after drawing it.  -> (ids, nll): per row an int64 array of its draws and a float64 array of their
+        -log p at temperature 1 (score()'s convention).  ValueError for a bad argument before anything runs; JlmHipError when the
+        device flags a non-finite logit or log-normaliser."""
+        from .generate import Generator, generate
+        g = getattr(self, "_gen", None)
+        if g is None:
+            g = self._gen = Generator(self.dev)
+        return generate(g, prompts, n_words, temperature, seed, stop_id, max_rows)
+
 
 def show_prob(model, w2i, inputs):
     """Per-word -log p of a word sequence and their total (the reference's show_prob, model.py:208-211, which reads
