@@ -181,6 +181,18 @@ int jlm_vocab_lse_partials_split(const void *Bsplit, int ldb, int n_vocab, int K
 int jlm_gemm_nt_split(const void *A, int lda, const int *a_rows, const void *B, int ldb, const int *b_rows,
                       float *C, int ldc, const int *c_rows, const float *bias, float descale,
                       int M, int N, int K, const int *m_dev, void *stream);
+/* ABI 12 (additive): which path jlm_gemm_nt_split takes for an M x N launch (pure host; the launcher asks here).  JLM_T_STAGES and
+ * JLM_T_XCD are read once per process.  With three stages (the default) and at most 256 tiles of 64 x 64:
+ *   0 gemm_split3_kernel<Cfg64, ..., 3>, linear tile map (JLM_T_XCD=0)
+ *   1 gemm_split3_kernel<Cfg64, ..., 3>, XCD map 1: the column tiles of a row tile on one XCD (default)
+ * otherwise gemm_split_kernel, linear map:
+ *   2 gemm_split_kernel<Cfg64>   fewer than 512 tiles of 128 x 128
+ *   3 gemm_split_kernel<Cfg128>  the rest */
+#define JLM_T_SPLIT3_LINEAR 0
+#define JLM_T_SPLIT3_XCD 1
+#define JLM_T_CFG64 2
+#define JLM_T_CFG128 3
+int jlm_gemm_nt_split_form(int M, int N);
 
 /* One column of split rows from a vector: dst[r][col] = split(v[r] * scale). */
 int jlm_pack_split_f16_col(const float *v, int rows, float scale, void *dst, int ld_dst, int col, void *stream);
@@ -206,6 +218,10 @@ int jlm_vocab_lse_split(const jlm_segment *segs_host, const float *t_scale, cons
                         const float *T, int ldt, const int *rows,
                         float *part, int ld_part, int max_parts,
                         int n_rows_max, const int *n_dev, void *stream);
+/* ABI 12 (additive): the waves per workgroup of jlm_vocab_lse_split's kernel (pure host; the launcher asks here): 8
+ * vocab_lse_split8_kernel (256 rows per workgroup, default), 4 vocab_lse_split_kernel (128 rows, two workgroups per CU;
+ * JLM_LSE_WAVES=4, read once per process). */
+int jlm_vocab_lse_split_form(void);
 
 /* Word-list groups: one per (sentence, frame).  Group j covers hypothesis rows
  * g0[j] .. g0[j]+cnt[cnt_idx[j]]-1 and the word list number l = wl_base +
@@ -380,6 +396,54 @@ int jlm_vocab_lse_mixed(const jlm_segment *segs_host, const float *descale, cons
 int jlm_vocab_lse_mixed_fr(const jlm_segment *segs_host, const float *descale, const float *s8, const float *bias2, int n_segs,
                         const void *Tm, int ld_tm, float *part, int ld_part, int max_parts, int n_rows_max,
                         const int *n_dev, void *stream);
+
+/* ABI 12 (additive): which kernel jlm_vocab_lse_mixed (fixed_ref = 0) / jlm_vocab_lse_mixed_fr (fixed_ref = 1) launches for these
+ * segments (pure host, no HIP call; the launchers ask here).  has_bias2: whether bias2 is non-NULL.  -1 / -2 exactly when the launcher
+ * refuses the segments (bad count; a shape no form hosts, formats or bias forms mixed within a launch, mx6 rows at k = 512); the
+ * launcher's other refusals (ld_tm, n_rows_max, max_parts) do not depend on the form.  JLM_MX_WIDE and JLM_MX6_WIDE are read once per
+ * process.  int8 planes (csrc/jlm_mixed.hip: eight waves, 256 rows per workgroup; csrc/jlm_mixed_w.hip: the wide kernel, four waves):
+ *    0 MX_KERNEL_DSOFTMAX       vocab_lse_mixed_kernel<true, false, 7, 13, 4, 7, 2, 4>   the D-softmax* 200 / 100 / 50 shapes
+ *    1 MX_KERNEL_GENERIC        vocab_lse_mixed_kernel<false, false, ...>               every other bias-column shape
+ *    2 MX_KERNEL_TIED           vocab_lse_mixed_kernel<true, true, 8, 16>               tied k = 256 under JLM_MX_WIDE=0
+ *    3 MX_KERNEL_GENERIC_XB     vocab_lse_mixed_kernel<false, true, ...>                external-bias k = 64, 128, 192
+ *    4 MXW_KERNEL_DSOFTMAX      vocab_lse_mixedw_kernel<2, false, false, ...>           the D-softmax* shapes under JLM_MX_WIDE=1
+ *                                                                                        (ignores fixed_ref)
+ *    5 MXW_KERNEL_K512          vocab_lse_mixedw_kernel<1, true, false, 16, 32>         one segment of k = 512, 128 rows per workgroup
+ *    6 MXW_KERNEL_TIED          vocab_lse_mixedw_kernel<2, true, false, 8, 16>          tied k = 256 (default)
+ *    7 MXW_KERNEL_K512_FR       vocab_lse_mixedw_kernel<1, true, true, 16, 32>          5 without a running maximum
+ *    8 MXW_KERNEL_TIED_FR       vocab_lse_mixedw_kernel<2, true, true, 8, 16>           6 without a running maximum
+ * mx6 planes (every s8[i] = 0; csrc/jlm_mx6.hip eight waves, csrc/jlm_mx6w.hip four waves; the _FR forms only where every descale is 1):
+ *    9 MX6_KERNEL_DSOFTMAX      vocab_lse_mx6_kernel<true, false, false, ...>           the D-softmax* shapes (default)
+ *   10 MX6_KERNEL_GENERIC       vocab_lse_mx6_kernel<false, false, false, ...>          every other bias-column shape
+ *   11 MX6_KERNEL_TIED          vocab_lse_mx6_kernel<true, true, false, 8, 16>          tied k = 256 under JLM_MX6_WIDE=0
+ *   12 MX6_KERNEL_GENERIC_XB    vocab_lse_mx6_kernel<false, true, false, ...>           external-bias k = 64, 128, 192
+ *   13 MX6_KERNEL_DSOFTMAX_FR   vocab_lse_mx6_kernel<true, false, true, ...>            9 without a running maximum
+ *   14 MX6_KERNEL_TIED_FR       vocab_lse_mx6_kernel<true, true, true, 8, 16>           11 without a running maximum
+ *   15 MX6W_KERNEL_DSOFTMAX     vocab_lse_mx6w_kernel<false, false, ...>                the D-softmax* shapes under JLM_MX6_WIDE=1
+ *   16 MX6W_KERNEL_DSOFTMAX_FR  vocab_lse_mx6w_kernel<false, true, ...>                 15 without a running maximum
+ *   17 MX6W_KERNEL_TIED         vocab_lse_mx6w_kernel<true, false, 8, 16>               tied k = 256 (default)
+ *   18 MX6W_KERNEL_TIED_FR      vocab_lse_mx6w_kernel<true, true, 8, 16>                17 without a running maximum */
+#define JLM_LSE_MX_DSOFTMAX 0
+#define JLM_LSE_MX_GENERIC 1
+#define JLM_LSE_MX_TIED 2
+#define JLM_LSE_MX_GENERIC_XB 3
+#define JLM_LSE_MXW_DSOFTMAX 4
+#define JLM_LSE_MXW_K512 5
+#define JLM_LSE_MXW_TIED 6
+#define JLM_LSE_MXW_K512_FR 7
+#define JLM_LSE_MXW_TIED_FR 8
+#define JLM_LSE_MX6_DSOFTMAX 9
+#define JLM_LSE_MX6_GENERIC 10
+#define JLM_LSE_MX6_TIED 11
+#define JLM_LSE_MX6_GENERIC_XB 12
+#define JLM_LSE_MX6_DSOFTMAX_FR 13
+#define JLM_LSE_MX6_TIED_FR 14
+#define JLM_LSE_MX6W_DSOFTMAX 15
+#define JLM_LSE_MX6W_DSOFTMAX_FR 16
+#define JLM_LSE_MX6W_TIED 17
+#define JLM_LSE_MX6W_TIED_FR 18
+int jlm_vocab_lse_mixed_form(const jlm_segment *segs_host, const float *descale, const float *s8, int has_bias2, int n_segs,
+                             int fixed_ref);
 
 /* One launch over segments of BOTH formats (csrc/jlm_split.hip, vocab_lse_hybrid_kernel): mixed[i].B != NULL runs segment i on
  * its mixed rows (mixed[i].ldb = 32 nb; mx_descale[i], mx_s8[i] as for jlm_vocab_lse_mixed; Tm = rows packed by

@@ -128,6 +128,9 @@ _SIGS = {
     "jlm_score_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), P, P], c_int),
     "jlm_sample_rows": ([P, c_int, c_int, c_int, P, c_double, c_uint64, c_int, P, P, P, c_int, c_int, P, P, P, P, P], c_int),
     "jlm_generate_frames": ([POINTER(DecodeModel), POINTER(GeneratePlan), P, P], c_int),
+    "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
+    "jlm_vocab_lse_split_form": ([], c_int),
+    "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -789,6 +789,21 @@ extern "C" int jlm_gemm_nt(const float *Ap, int lda, const int *a_rows, const fl
     return launch_gemm2<Cfg128>(A, B, K, epi, 0, (hipStream_t)stream);
 }
 
+// The one place jlm_gemm_nt_split's path is chosen (include/jlm_hip.h lists the forms): the launcher and the tests ask here.
+extern "C" int jlm_gemm_nt_split_form(int M, int N) {
+    const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+    const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
+    static int stages = -1;                    // 3 stages: 17.4 -> 13.8 us on the T projection; 4 and 6 are no better
+    if (stages < 0) { const char *e = getenv("JLM_T_STAGES"); stages = e ? atoi(e) : 3; }
+    // XCD map 1: the column tiles of one row tile run on the same XCD, so a gathered A row crosses the fabric into ONE L2
+    // instead of up to tiles_n of them (T projection: 36.6 MB fetched per launch for 9.4 MB of operands with the linear map).
+    // JLM_T_XCD=0: the linear map; any other value: map 1
+    static int txcd = -1;
+    if (txcd < 0) { const char *e = getenv("JLM_T_XCD"); txcd = e ? atoi(e) : 1; }
+    if (tiles64 <= 256 && stages == 3) return txcd == 0 ? JLM_T_SPLIT3_LINEAR : JLM_T_SPLIT3_XCD;
+    return tiles128 < 512 ? JLM_T_CFG64 : JLM_T_CFG128;
+}
+
 // Split-f16 form of jlm_gemm_nt (operands = split rows, strides in 4-byte units).  (The round-1 split LSTM step that lived here,
 // jlm_lstm_step_split, left with ABI 9: the decode has used jlm_lstm_step_xg since round 2 -- HISTORY.md.)
 extern "C" int jlm_gemm_nt_split(const void *Ap, int lda, const int *a_rows, const void *Bp, int ldb, const int *b_rows,
@@ -800,16 +815,10 @@ extern "C" int jlm_gemm_nt_split(const void *Ap, int lda, const int *a_rows, con
     B.base = reinterpret_cast<const float *>(Bp); B.map = b_rows; B.ld = ldb; B.nrows = N; B.ndev = nullptr;
     EpiStore epi;
     epi.C = C; epi.c_map = c_rows; epi.ldc = ldc; epi.bias = bias; epi.scale = descale;
-    long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-    const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-    static int stages = -1;                    // 3 stages: 17.4 -> 13.8 us on the T projection; 4 and 6 are no better
-    if (stages < 0) { const char *e = getenv("JLM_T_STAGES"); stages = e ? atoi(e) : 3; }
-    // XCD map 1: the column tiles of one row tile run on the same XCD, so a gathered A row crosses the fabric into ONE L2
-    // instead of up to tiles_n of them (T projection: 36.6 MB fetched per launch for 9.4 MB of operands with the linear map)
-    static int txcd = -1;
-    if (txcd < 0) { const char *e = getenv("JLM_T_XCD"); txcd = e ? atoi(e) : 1; }
-    if (tiles64 <= 256 && stages == 3) return launch_gemm_split3<Cfg64, PlainRows, PlainRows, EpiStore, 3>(A, B, K, epi, txcd, (hipStream_t)stream);
-    if (tiles128 < 512) return launch_gemm_split<Cfg64>(A, B, K, epi, 0, (hipStream_t)stream);
+    const int form = jlm_gemm_nt_split_form(M, N);
+    if (form == JLM_T_SPLIT3_LINEAR || form == JLM_T_SPLIT3_XCD)
+        return launch_gemm_split3<Cfg64, PlainRows, PlainRows, EpiStore, 3>(A, B, K, epi, form == JLM_T_SPLIT3_XCD ? 1 : 0, (hipStream_t)stream);
+    if (form == JLM_T_CFG64) return launch_gemm_split<Cfg64>(A, B, K, epi, 0, (hipStream_t)stream);
     return launch_gemm_split<Cfg128>(A, B, K, epi, 0, (hipStream_t)stream);
 }
 

@@ -494,12 +494,81 @@ extern "C" int jlm_pack_t_mixed6(const jlm_segment *segs_host, const float *t_sc
     return pack_t_mixed_impl(segs_host, t_scale, n_segs, T, ldt, rows, n_rows_max, n_dev, Tm, ld_tm, stream, 1);
 }
 
-// the mx6 form (jlm_mx6.hip: FP6 cross terms on the block-scaled matrix instruction)
-int jlm_mx6_launch(const MxArgs &a, bool xbias, int fixed_ref, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev, int n_ptiles,
+// the mx6 form (jlm_mx6.hip: FP6 cross terms on the block-scaled matrix instruction); form = JLM_LSE_MX6_* / JLM_LSE_MX6W_*
+int jlm_mx6_launch(int form, const MxArgs &a, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev, int n_ptiles,
                    int lds, hipStream_t st);
 // the wide form of the D-softmax* kernel (jlm_mixed_w.hip: four waves of 64 rows, row operands in accumulation registers)
 int jlm_mx_wide_launch(int which, const MxArgs &a, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
                        int n_ptiles, int lds, hipStream_t st);
+
+#ifndef JLM_MX6_WIDE_DEFAULT
+#define JLM_MX6_WIDE_DEFAULT -1
+#endif
+
+// The one place jlm_vocab_lse_mixed(_fr)'s kernel is chosen (the ids: include/jlm_hip.h); the launcher and the tests ask here.
+// -1 / -2: the launcher refuses these segments.
+extern "C" int jlm_vocab_lse_mixed_form(const jlm_segment *segs_host, const float *descale, const float *s8, int has_bias2, int n_segs,
+                                        int fixed_ref) {
+    if (n_segs < 1 || n_segs > JLM_MAX_SEGMENTS) return -1;
+    // ABI 11: s8[i] == 0 for every segment = mx6 rows (jlm_mx6_body.h); one format per launch
+    int n6 = 0;
+    for (int i = 0; i < n_segs; ++i) n6 += s8[i] == 0.0f;
+    if (n6 && n6 != n_segs) return -2;
+    bool xbias = false, k512 = false;
+    // which kernel: 0 the D-softmax* shapes (inlined), 1 any other bias-column shape, 2 tied k = 256 (inlined), 3 other external-bias shapes
+    int which = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        const jlm_segment &sg = segs_host[i];
+        const int nb = mx_seg_blocks(sg);
+        // (a single segment of sixteen blocks in the external-bias form -- k = 512: an untied model's vocabulary matrix -- runs on the
+        //  wide kernel's one-row-set form, jlm_mixed_w.hip; every other shape has at most eight blocks)
+        k512 = n_segs == 1 && nb == 16 && sg.k == 512;
+        if (nb < 1 || (nb > MX_MAX_NB && !k512) || sg.k % 4 || sg.t_off % 4) return -2;
+        if ((long)(sg.v_end - sg.v_start) * nb * 128 >= (1l << 31)) return -2;        // 32-bit buffer offsets
+        const bool xb = sg.k + 2 > 32 * nb;                  // no bias columns: the biases come from bias2 (base-2 units)
+        if (i == 0) { xbias = xb; which = xb ? 2 : 0; }
+        if (xb != xbias || (xb && (!has_bias2 || nb % 2))) return -2;      // one form per launch; external-bias bodies exist for even nb
+        const int mtt = mx_blocks_per_tile(nb);
+        if ((sg.v_end - sg.v_start + 32 * mtt - 1) / (32 * mtt) > 65535) return -2;
+        const int ns16 = (sg.k + 2 + 15) / 16;
+        if (xb) { if (nb != 8) which = 3; }
+        else if (!((nb == 7 && ns16 == 13) || (nb == 4 && ns16 == 7) || (nb == 2 && ns16 == 4))) which = 1;
+    }
+    if (n6) {
+        if (k512) return -2;
+        // (the mx6 forms without a running maximum take the accumulators as base-2 logits: only for launches whose descale is 1)
+        int fr6 = fixed_ref;
+        for (int i = 0; i < n_segs; ++i) fr6 &= descale[i] == 1.0f;
+        // JLM_MX6_WIDE: 1 the wide kernel (jlm_mx6w.hip) for every shape it hosts -- the D-softmax* shapes and k = 256 with external
+        // biases (which 0 and 2) -- 0 the eight-wave kernel, -1 (default) where it measures faster: the tied k = 256 shapes, 98-100 vs
+        // 107 us at V = 50 k / 2 560 rows, 1 384 vs 1 500 us at V = 100 k / 20 480 rows; the D-softmax* launch measures the same on both
+        // (60.5-60.9 vs 59.6-59.9 us) and stays on the eight-wave kernel (profiles/r06_g_mx6_wide.txt) -- as for the int8 planes
+        static int wide6 = -1;
+        if (wide6 < 0) { const char *e = getenv("JLM_MX6_WIDE"); wide6 = e ? atoi(e) : JLM_MX6_WIDE_DEFAULT; }
+        if ((wide6 > 0 || (wide6 < 0 && xbias)) && (which == 0 || which == 2))
+            return (which == 2 ? JLM_LSE_MX6W_TIED : JLM_LSE_MX6W_DSOFTMAX) + (fr6 ? 1 : 0);
+        // the forms without a running maximum exist for the inlined shapes
+        if (fr6 && which == 0) return JLM_LSE_MX6_DSOFTMAX_FR;
+        if (fr6 && which == 2) return JLM_LSE_MX6_TIED_FR;
+        return JLM_LSE_MX6_DSOFTMAX + which;
+    }
+    // fixed_ref (jlm_vocab_lse_mixed_fr): the wide kernel's forms WITHOUT a running maximum -- s = sum 2^y against the reference 0, slices
+    // (0, s) -- where a form exists (tied k = 256, k = 512); any other shape runs as usual.  -3 % on those launches (113.5 vs 117 us,
+    // 1 589 vs 1 634 us at configs[2]'s shape: profiles/r05_u_fixed_ref.txt).  Valid while a row's largest base-2 logit stays within
+    // +-100 or so (f32 range, 2^16 words): the caller's decision (DeviceModel measures its model at load); a row outside it yields s = 0 or
+    // inf, never a plausible number.
+    // (The eight-wave kernel's D-softmax* bodies were built in this form too and measured SLOWER -- 68.9-73.8 vs 67.0 us per launch,
+    //  profiles/r05_v_fixed_ref_dsoftmax.txt -- and left as they were: that launch ignores the flag.)
+    if (k512) return fixed_ref ? JLM_LSE_MXW_K512_FR : JLM_LSE_MXW_K512;
+    // JLM_MX_WIDE: 1 the wide kernel (jlm_mixed_w.hip) for every shape it hosts, 0 never, -1 (default) where it measures faster: the tied
+    // k = 256 shapes -- 116.6-118.0 vs 122.7-124.5 us at V = 50 k / 2 560 rows, 1 691 vs 1 813 us at V = 100 k / 20 480 rows; the
+    // D-softmax* launch measures the same on both (70.5 vs 70.0 us) and stays on the eight-wave kernel (profiles/r05_r_wide_tied.txt)
+    static int wide = -1;
+    if (wide < 0) { const char *e = getenv("JLM_MX_WIDE"); wide = e ? atoi(e) : JLM_MX_WIDE_DEFAULT; }
+    if (which == 0 && wide > 0) return JLM_LSE_MXW_DSOFTMAX;
+    if (which == 2 && wide != 0) return fixed_ref ? JLM_LSE_MXW_TIED_FR : JLM_LSE_MXW_TIED;
+    return JLM_LSE_MX_DSOFTMAX + which;
+}
 
 static int vocab_lse_mixed_impl(const jlm_segment *segs_host, const float *descale, const float *s8, const float *bias2, int n_segs,
                                 const void *Tm, int ld_tm, float *part, int ld_part, int max_parts, int n_rows_max,
@@ -518,30 +587,20 @@ static int vocab_lse_mixed_impl(const jlm_segment *segs_host, const float *desca
     // 68.9 us, the decode 2.04 vs 2.06 ms per step); pipelined launches are capped by the CU share below that anyway.  1: multiples of 8
     if (np8 < 0) { const char *e = getenv("JLM_MX_NP8"); np8 = e ? atoi(e) : 0; }
     int ntiles[JLM_MAX_SEGMENTS];
-    int rows_wg = 256;                                   // hypothesis rows per workgroup (128: the wide kernel's k = 512 form)
-    // ABI 11: s8[i] == 0 for every segment = mx6 rows (jlm_mx6_body.h); one format per launch
-    int n6 = 0;
-    for (int i = 0; i < n_segs; ++i) n6 += s8[i] == 0.0f;
-    if (n6 && n6 != n_segs) return -2;
+    const int form = jlm_vocab_lse_mixed_form(segs_host, descale, s8, bias2 != nullptr, n_segs, fixed_ref);
+    if (form < 0) return form;
+    // hypothesis rows per workgroup (128: the wide kernel's k = 512 form)
+    const int rows_wg = form == JLM_LSE_MXW_K512 || form == JLM_LSE_MXW_K512_FR ? 128 : 256;
     // (Round 6 also built 512-row workgroups -- two row sets per wave for the segments of up to four 32-k blocks, the 200-wide one walking
     //  its two 256-row halves in turn: half the fragment reads and LDS-DMA per row for 60 % of the launch.  Correct, and no faster:
     //  61-62 us against 59.8; LDS instructions -29 %, wave cycles +6 % (profiles/r06_k_pair512.txt, r06_l_pmc_mx6_forms.txt).  Removed.)
     double ctile[JLM_MAX_SEGMENTS], total = 0.0;
     long n_tiles_all = 0;
     int lds_max = 0, tm_off = 0;
-    bool xbias = false;
     for (int i = 0; i < n_segs; ++i) {
         const jlm_segment &sg = segs_host[i];
-        const int nb = mx_seg_blocks(sg);
-        // (a single segment of sixteen blocks in the external-bias form -- k = 512: an untied model's vocabulary matrix -- runs on the
-        //  wide kernel's one-row-set form, jlm_mixed_w.hip; every other shape has at most eight blocks)
-        const bool k512 = n_segs == 1 && nb == 16 && sg.k == 512;
-        if (nb < 1 || (nb > MX_MAX_NB && !k512) || sg.k % 4 || sg.t_off % 4) return -2;
-        if ((long)(sg.v_end - sg.v_start) * nb * 128 >= (1l << 31)) return -2;        // 32-bit buffer offsets
+        const int nb = mx_seg_blocks(sg);                    // (the shapes were checked by jlm_vocab_lse_mixed_form)
         const bool xb = sg.k + 2 > 32 * nb;                  // no bias columns: the biases come from bias2 (base-2 units)
-        if (k512) rows_wg = 128;
-        if (i == 0) xbias = xb;
-        if (xb != xbias || (xb && (!bias2 || nb % 2))) return -2;      // one form per launch; external-bias bodies exist for even nb
         MxSeg &m = a.seg[i];
         m.bias2 = xb ? bias2 + sg.v_start : nullptr;
         m.B = reinterpret_cast<const unsigned char *>(sg.B);
@@ -552,7 +611,6 @@ static int vocab_lse_mixed_impl(const jlm_segment *segs_host, const float *desca
         m.cs = s8[i] * (1.0f / 2048.0f);
         const int mtt = mx_blocks_per_tile(nb);
         ntiles[i] = (m.n_vocab + 32 * mtt - 1) / (32 * mtt);
-        if (ntiles[i] > 65535) return -2;
         const int ns16 = xb ? 2 * nb : (sg.k + 2 + 15) / 16;
         // cost of a tile ~ its matrix instructions (f16 steps + two int8 per 32-k block, per 32-word block) + a per-tile constant,
         // in the units of the split kernel's model (half k-steps of a 128-word tile)
@@ -631,45 +689,17 @@ static int vocab_lse_mixed_impl(const jlm_segment *segs_host, const float *desca
     a.n_sub = n_sub;
     if (n_sub > max_parts) return -1;
     const int lds = lds_max;
-    if (n6) {
-        if (rows_wg == 128) return -2;
-        // (the mx6 forms without a running maximum take the accumulators as base-2 logits: only for launches whose descale is 1)
-        int fr6 = fixed_ref;
-        for (int i = 0; i < n_segs; ++i) fr6 &= descale[i] == 1.0f;
-        if (int rc = jlm_mx6_launch(a, xbias, fr6, Tm, ld_tm, reinterpret_cast<float2 *>(part), ld_part, n_rows_max, n_dev, n_ptiles, lds,
-                                    (hipStream_t)stream)) return rc;
-        return n_sub;
-    }
-    // which kernel: 0 the D-softmax* shapes (inlined), 1 any other bias-column shape, 2 tied k = 256 (inlined), 3 other external-bias shapes
-    int which = xbias ? 2 : 0;
-    for (int i = 0; i < n_segs; ++i) {
-        const int nb = a.seg[i].nb, ns16 = (a.seg[i].k + 2 + 15) / 16;
-        if (xbias) { if (nb != 8) which = 3; }
-        else if (!((nb == 7 && ns16 == 13) || (nb == 4 && ns16 == 7) || (nb == 2 && ns16 == 4))) which = 1;
-    }
     float2 *part2 = reinterpret_cast<float2 *>(part);
     hipStream_t st = (hipStream_t)stream;
-    static int wide = -1;
-    if (wide < 0) { const char *e = getenv("JLM_MX_WIDE"); wide = e ? atoi(e) : JLM_MX_WIDE_DEFAULT; }
-    // fixed_ref (jlm_vocab_lse_mixed_fr): the wide kernel's forms WITHOUT a running maximum -- s = sum 2^y against the reference 0, slices
-    // (0, s) -- where a form exists (tied k = 256, k = 512); any other shape runs as usual.  -3 % on those launches (113.5 vs 117 us,
-    // 1 589 vs 1 634 us at configs[2]'s shape: profiles/r05_u_fixed_ref.txt).  Valid while a row's largest base-2 logit stays within
-    // (The eight-wave kernel's D-softmax* bodies were built in this form too and measured SLOWER -- 68.9-73.8 vs 67.0 us per launch,
-    //  profiles/r05_v_fixed_ref_dsoftmax.txt -- and left as they were: that launch ignores the flag.)
-    // +-100 or so (f32 range, 2^16 words): the caller's decision (DeviceModel measures its model at load); a row outside it yields s = 0 or
-    // inf, never a plausible number.
-    const int fixref = fixed_ref;
-    if (rows_wg == 128) {
-        if (int rc = jlm_mx_wide_launch(fixref ? 3 : 1, a, Tm, ld_tm, part2, ld_part, n_rows_max, n_dev, n_ptiles, lds, st)) return rc;
+    if (form >= JLM_LSE_MX6_DSOFTMAX) {
+        if (int rc = jlm_mx6_launch(form, a, Tm, ld_tm, part2, ld_part, n_rows_max, n_dev, n_ptiles, lds, st)) return rc;
         return n_sub;
     }
-    // JLM_MX_WIDE: 1 the wide kernel (jlm_mixed_w.hip) for every shape it hosts, 0 never, -1 (default) where it measures faster: the tied
-    // k = 256 shapes -- 116.6-118.0 vs 122.7-124.5 us at V = 50 k / 2 560 rows, 1 691 vs 1 813 us at V = 100 k / 20 480 rows; the
-    // D-softmax* launch measures the same on both (70.5 vs 70.0 us) and stays on the eight-wave kernel (profiles/r05_r_wide_tied.txt)
-    if ((which == 0 && wide > 0) || (which == 2 && wide != 0)) {
-        if (int rc = jlm_mx_wide_launch(which == 2 && fixref ? 4 : which, a, Tm, ld_tm, part2, ld_part, n_rows_max, n_dev, n_ptiles, lds, st)) return rc;
+    if (form >= JLM_LSE_MXW_DSOFTMAX) {
+        if (int rc = jlm_mx_wide_launch(form - JLM_LSE_MXW_DSOFTMAX, a, Tm, ld_tm, part2, ld_part, n_rows_max, n_dev, n_ptiles, lds, st)) return rc;
         return n_sub;
     }
+    const int which = form;
     static JlmLdsGrant grant[4];
     const void *fns[4] = {reinterpret_cast<const void *>(MX_KERNEL_DSOFTMAX), reinterpret_cast<const void *>(MX_KERNEL_GENERIC),
                           reinterpret_cast<const void *>(MX_KERNEL_TIED), reinterpret_cast<const void *>(MX_KERNEL_GENERIC_XB)};

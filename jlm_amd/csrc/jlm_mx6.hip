@@ -79,36 +79,18 @@ __global__ __launch_bounds__(512, 1) void vocab_lse_mx6_kernel(MxArgs a, const u
 
 }  // namespace
 
-// the wide form (jlm_mx6w.hip: four waves of 64 rows): the shapes it hosts, its launch
-bool jlm_mx6w_hosts(const MxArgs &a, bool xbias);
-int jlm_mx6w_launch(const MxArgs &a, bool xbias, int fixed_ref, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
+// the wide form (jlm_mx6w.hip: four waves of 64 rows); which = form - JLM_LSE_MX6W_DSOFTMAX
+int jlm_mx6w_launch(int which, const MxArgs &a, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
                     int n_ptiles, int lds, hipStream_t st);
 
-#ifndef JLM_MX6_WIDE_DEFAULT
-#define JLM_MX6_WIDE_DEFAULT -1
-#endif
-
-// which kernel: the D-softmax* shapes (inlined), any other bias-column shape, tied k = 256 (inlined), other external-bias shapes.
-// JLM_MX6_WIDE: 1 the wide kernel for every shape it hosts, 0 the eight-wave kernel, -1 (default) where it measures faster -- the tied
-// k = 256 shapes: 98-100 vs 107 us at V = 50 k / 2 560 rows, 1 384 vs 1 500 us at V = 100 k / 20 480 rows; the D-softmax* launch measures
-// the same on both (60.5-60.9 vs 59.6-59.9 us) and stays on the eight-wave kernel (profiles/r06_g_mx6_wide.txt) -- as for the int8 planes.
+// form: JLM_LSE_MX6_* (this file) or JLM_LSE_MX6W_* (the wide kernel), as jlm_vocab_lse_mixed_form (jlm_mixed.hip) chose it.
 // Returns 0, -3 (LDS grant) or a negative HIP error like its caller.
-int jlm_mx6_launch(const MxArgs &a, bool xbias, int fixed_ref, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
+int jlm_mx6_launch(int form, const MxArgs &a, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
                    int n_ptiles, int lds, hipStream_t st) {
-    static int wide = -1;
-    if (wide < 0) { const char *e = getenv("JLM_MX6_WIDE"); wide = e ? atoi(e) : JLM_MX6_WIDE_DEFAULT; }
-    if ((wide > 0 || (wide < 0 && xbias)) && jlm_mx6w_hosts(a, xbias))
-        return jlm_mx6w_launch(a, xbias, fixed_ref, Tm, ld_tm, part, ld_part, n_rows_max, n_dev, n_ptiles, lds, st);
-    int which = xbias ? 2 : 0;
-    for (int i = 0; i < a.n_segs; ++i) {
-        const int nb = a.seg[i].nb, ns16 = (a.seg[i].k + 2 + 15) / 16;
-        if (xbias) { if (nb != 8) which = 3; }
-        else if (!((nb == 7 && ns16 == 13) || (nb == 4 && ns16 == 7) || (nb == 2 && ns16 == 4))) which = 1;
-    }
-    // fixed_ref: the forms without a running maximum exist for the inlined shapes (4: D-softmax*, 5: tied k = 256); the caller passes it
-    // only for launches whose descale is 1 (the accumulators are base-2 logits)
-    if (fixed_ref && which == 0) which = 4;
-    if (fixed_ref && which == 2) which = 5;
+    if (form >= JLM_LSE_MX6W_DSOFTMAX)
+        return jlm_mx6w_launch(form - JLM_LSE_MX6W_DSOFTMAX, a, Tm, ld_tm, part, ld_part, n_rows_max, n_dev, n_ptiles, lds, st);
+    const int which = form - JLM_LSE_MX6_DSOFTMAX;
+    if (which < 0 || which > 5) return -1;
     static JlmLdsGrant grant[6];
     const void *fns[6] = {reinterpret_cast<const void *>(MX6_KERNEL_DSOFTMAX), reinterpret_cast<const void *>(MX6_KERNEL_GENERIC),
                           reinterpret_cast<const void *>(MX6_KERNEL_TIED), reinterpret_cast<const void *>(MX6_KERNEL_GENERIC_XB),

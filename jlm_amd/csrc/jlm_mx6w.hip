@@ -390,20 +390,12 @@ __global__ __launch_bounds__(256, 1) void vocab_lse_mx6w_kernel(MxArgs a, const 
 
 }  // namespace
 
-// the shapes the wide mx6 kernel hosts: the D-softmax* 200 / 100 / 50 model (bias columns) and segments of k = 256 with external biases
-bool jlm_mx6w_hosts(const MxArgs &a, bool xbias) {
-    for (int i = 0; i < a.n_segs; ++i) {
-        const int nb = a.seg[i].nb, ns16 = (a.seg[i].k + 2 + 15) / 16;
-        if (xbias) { if (nb != 8) return false; }
-        else if (!((nb == 7 && ns16 == 13) || (nb == 4 && ns16 == 7) || (nb == 2 && ns16 == 4))) return false;
-    }
-    return true;
-}
-
-// Returns 0, -3 (LDS grant) or a negative HIP error like its caller (jlm_mx6_launch, jlm_mx6.hip).
-int jlm_mx6w_launch(const MxArgs &a, bool xbias, int fixed_ref, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
+// which: 0 the D-softmax* 200 / 100 / 50 model (bias columns), 2 segments of k = 256 with external biases; + 1: without a running
+// maximum (jlm_vocab_lse_mixed_form, jlm_mixed.hip, chooses).  Returns 0, -3 (LDS grant) or a negative HIP error like its caller
+// (jlm_mx6_launch, jlm_mx6.hip).
+int jlm_mx6w_launch(int which, const MxArgs &a, const void *Tm, int ld_tm, float2 *part, int ld_part, int n_rows_max, const int *n_dev,
                     int n_ptiles, int lds, hipStream_t st) {
-    const int which = (xbias ? 2 : 0) + (fixed_ref ? 1 : 0);
+    if (which < 0 || which > 3) return -1;
     static JlmLdsGrant grant[4];
     const void *fns[4] = {reinterpret_cast<const void *>(MX6W_KERNEL_DSOFTMAX), reinterpret_cast<const void *>(MX6W_KERNEL_DSOFTMAX_FR),
                           reinterpret_cast<const void *>(MX6W_KERNEL_TIED), reinterpret_cast<const void *>(MX6W_KERNEL_TIED_FR)};

@@ -819,6 +819,14 @@ __global__ __launch_bounds__(512, 1) void vocab_lse_split8_kernel(LseSplitArgs a
     vocab_lse_split_main<8>(a, T, ldt, rows, part, ld_part, n_rows_max, n_dev, n_ptiles);
 }
 
+// JLM_LSE_WAVES=4: the four-wave kernel; anything else the eight-wave one.  The one place the choice is made: jlm_vocab_lse_split
+// and the tests ask here.
+extern "C" int jlm_vocab_lse_split_form(void) {
+    static int nw = -1;
+    if (nw < 0) { const char *e = getenv("JLM_LSE_WAVES"); nw = (e && atoi(e) == 4) ? 4 : 8; }
+    return nw;
+}
+
 // Host side: equal-cost columns over the concatenated segments, one resident round of workgroups.
 // Returns the number of partial slices written (fold them with jlm_lse_combine), or <0.
 extern "C" int jlm_vocab_lse_split(const jlm_segment *segs_host, const float *t_scale, const float *descale,
@@ -858,8 +866,7 @@ extern "C" int jlm_vocab_lse_split(const jlm_segment *segs_host, const float *t_
         total += ctile[i] * ntiles[i];
         n_tiles_all += ntiles[i];
     }
-    static int nw = -1;
-    if (nw < 0) { const char *e = getenv("JLM_LSE_WAVES"); nw = (e && atoi(e) == 4) ? 4 : 8; }
+    const int nw = jlm_vocab_lse_split_form();
     const int n_ptiles = (n_rows_max + 32 * nw - 1) / (32 * nw);
     int cap = max_parts < LSES_MAX_SUB ? max_parts : LSES_MAX_SUB;
     cap -= n_segs - 1;                          // slices: one per column + one per segment boundary a column straddles

@@ -67,7 +67,116 @@ def lstm_step_form(H, has_rows, has_h_f32, n_rows_max, forced):
     return dflt if serves(dflt) else 1
 
 
+def _atoi_env(name, unset):
+    """an environment variable as C's atoi reads it; `unset` when it is not set"""
+    v = os.environ.get(name)
+    if v is None:
+        return unset
+    m = re.match(r"\s*[+-]?\d+", v)
+    return int(m.group()) if m else 0
+
+
+# include/jlm_hip.h jlm_vocab_lse_mixed_form ids
+MX_FORMS = ("MX_KERNEL_DSOFTMAX", "MX_KERNEL_GENERIC", "MX_KERNEL_TIED", "MX_KERNEL_GENERIC_XB",
+            "MXW_KERNEL_DSOFTMAX", "MXW_KERNEL_K512", "MXW_KERNEL_TIED", "MXW_KERNEL_K512_FR", "MXW_KERNEL_TIED_FR",
+            "MX6_KERNEL_DSOFTMAX", "MX6_KERNEL_GENERIC", "MX6_KERNEL_TIED", "MX6_KERNEL_GENERIC_XB", "MX6_KERNEL_DSOFTMAX_FR",
+            "MX6_KERNEL_TIED_FR", "MX6W_KERNEL_DSOFTMAX", "MX6W_KERNEL_DSOFTMAX_FR", "MX6W_KERNEL_TIED", "MX6W_KERNEL_TIED_FR")
+MX_FORM = {name: i for i, name in enumerate(MX_FORMS)}
+# include/jlm_hip.h jlm_gemm_nt_split_form ids
+T_FORMS = ("SPLIT3_LINEAR", "SPLIT3_XCD", "CFG64", "CFG128")
+
+
+def lse_mixed_form(segs, descale, s8, has_bias2, fixed_ref, mx_wide=-1, mx6_wide=-1):
+    """include/jlm_hip.h jlm_vocab_lse_mixed_form with JLM_MX_WIDE = mx_wide, JLM_MX6_WIDE = mx6_wide (-1: unset); segs: (v_start, v_end,
+    k, t_off, ldb) per segment.  The int8 planes: the D-softmax* shapes (bias columns, (blocks, f16 steps) in {(7, 13), (4, 7), (2, 4)}) on
+    the eight-wave kernel (the wide one under JLM_MX_WIDE=1, which has no fixed-reference form), other bias-column shapes on the generic
+    eight-wave kernel, tied k = 256 on the wide kernel (the eight-wave one under JLM_MX_WIDE=0), other external-bias shapes on the generic
+    external-bias kernel, one k = 512 segment on the wide kernel's one-row-set form.  mx6 rows (every s8 = 0): the same shapes, the wide
+    kernel for tied k = 256 by default and for the D-softmax* shapes too under JLM_MX6_WIDE=1, never under 0; the fixed-reference forms
+    only where every descale is 1; no k = 512."""
+    n = len(segs)
+    if n < 1 or n > 8:
+        return -1
+    n6 = sum(float(x) == 0.0 for x in s8)
+    if n6 and n6 != n:
+        return -2
+    xbias = k512 = False
+    which = 0
+    for i, (v0, v1, k, t_off, ldb) in enumerate(segs):
+        nb = ldb // 32 if k > 0 and ldb % 32 == 0 and ldb // 32 in ((k + 2 + 31) // 32, (k + 31) // 32) else -1
+        k512 = n == 1 and nb == 16 and k == 512
+        if nb < 1 or (nb > 8 and not k512) or k % 4 or t_off % 4:
+            return -2
+        if (v1 - v0) * nb * 128 >= 1 << 31:
+            return -2
+        xb = k + 2 > 32 * nb
+        if i == 0:
+            xbias, which = xb, (2 if xb else 0)
+        if xb != xbias or (xb and (not has_bias2 or nb % 2)):
+            return -2
+        mtt = 8 if nb <= 2 else 4 if nb <= 4 else 2 if nb <= 8 else 1
+        if (v1 - v0 + 32 * mtt - 1) // (32 * mtt) > 65535:
+            return -2
+        ns16 = (k + 2 + 15) // 16
+        if xb:
+            which = 3 if nb != 8 else which
+        elif (nb, ns16) not in ((7, 13), (4, 7), (2, 4)):
+            which = 1
+    if n6:
+        if k512:
+            return -2
+        fr6 = bool(fixed_ref) and all(float(d) == 1.0 for d in descale)
+        if (mx6_wide > 0 or (mx6_wide < 0 and xbias)) and which in (0, 2):
+            return MX_FORM["MX6W_KERNEL_TIED" if which == 2 else "MX6W_KERNEL_DSOFTMAX"] + int(fr6)
+        if fr6 and which == 0:
+            return MX_FORM["MX6_KERNEL_DSOFTMAX_FR"]
+        if fr6 and which == 2:
+            return MX_FORM["MX6_KERNEL_TIED_FR"]
+        return MX_FORM["MX6_KERNEL_DSOFTMAX"] + which
+    if k512:
+        return MX_FORM["MXW_KERNEL_K512_FR" if fixed_ref else "MXW_KERNEL_K512"]
+    if which == 0 and mx_wide > 0:
+        return MX_FORM["MXW_KERNEL_DSOFTMAX"]
+    if which == 2 and mx_wide != 0:
+        return MX_FORM["MXW_KERNEL_TIED_FR" if fixed_ref else "MXW_KERNEL_TIED"]
+    return which
+
+
+def lse_split_form(waves_env):
+    """include/jlm_hip.h jlm_vocab_lse_split_form: 4 under JLM_LSE_WAVES=4, else 8"""
+    return 4 if waves_env == 4 else 8
+
+
+def gemm_nt_split_form(M, N, stages=3, xcd=1):
+    """include/jlm_hip.h jlm_gemm_nt_split_form with JLM_T_STAGES = stages, JLM_T_XCD = xcd: the three-stage kernel where at most 256 tiles
+    of 64 x 64 cover the launch (0 linear tile map, 1 XCD map), else 2 Cfg64 below 512 tiles of 128 x 128, 3 Cfg128"""
+    tiles128 = ((M + 127) // 128) * ((N + 127) // 128)
+    tiles64 = ((M + 63) // 64) * ((N + 63) // 64)
+    if tiles64 <= 256 and stages == 3:
+        return 0 if xcd == 0 else 1
+    return 2 if tiles128 < 512 else 3
+
+
 class FakeLib:
+    @staticmethod
+    def jlm_vocab_lse_mixed_form(segs, descale, s8, has_bias2, n_segs, fixed_ref):
+        """ABI 12: the kernel jlm_vocab_lse_mixed(_fr) launches; JLM_MX_WIDE / JLM_MX6_WIDE as the library reads them"""
+        if n_segs < 1 or n_segs > 8:
+            return -1
+        sg = [(segs[i].v_start, segs[i].v_end, segs[i].k, segs[i].t_off, segs[i].ldb) for i in range(n_segs)]
+        return lse_mixed_form(sg, [descale[i] for i in range(n_segs)], [s8[i] for i in range(n_segs)], has_bias2, fixed_ref,
+                              _atoi_env("JLM_MX_WIDE", -1), _atoi_env("JLM_MX6_WIDE", -1))
+
+    @staticmethod
+    def jlm_vocab_lse_split_form():
+        """ABI 12: waves per workgroup of jlm_vocab_lse_split"""
+        return lse_split_form(_atoi_env("JLM_LSE_WAVES", 8))
+
+    @staticmethod
+    def jlm_gemm_nt_split_form(M, N):
+        """ABI 12: the path jlm_gemm_nt_split takes"""
+        return gemm_nt_split_form(M, N, _atoi_env("JLM_T_STAGES", 3), _atoi_env("JLM_T_XCD", 1))
+
     def jlm_abi_version(self):
         return 12
 

@@ -174,6 +174,22 @@ def test_lstm_step_xg_forced_forms(variant, tmp_path_factory):
     check_forced_child(variant, tmp_path_factory)
 
 
+@pytest.mark.parametrize("setting", ["JLM_MX_WIDE=1", "JLM_MX_WIDE=0", "JLM_MX6_WIDE=1", "JLM_MX6_WIDE=0", "JLM_LSE_WAVES=4",
+                                     "JLM_T_STAGES=4", "JLM_T_XCD=0"])
+def test_vocab_lse_forced_forms(setting, tmp_path):
+    """Every A/B form of the vocabulary normaliser and the T projection, whatever the launcher would pick: JLM_MX_WIDE = 1 (the wide int8
+    D-softmax* kernel) / 0 (the eight-wave int8 tied kernel), JLM_MX6_WIDE = 1 / 0 (the same for mx6 rows, with and without the fixed
+    reference), JLM_LSE_WAVES=4 (the four-wave split kernel), JLM_T_STAGES=4 (the two-stage Cfg64 / Cfg128 paths at every shape),
+    JLM_T_XCD=0 (the three-stage kernel on the linear tile map).  A child per setting -- the variables are read once per process -- runs
+    the cases of test_gpu_lse_forms.py that launcher serves and the kernel tests here (test_vocab_lse_mixed*, test_vocab_lse_split,
+    test_gemm_nt_split); every case the forced form serves must have run and reported the forced form."""
+    import os
+    if os.environ.get("JLM_LSE_FORMS_OUT"):
+        pytest.skip("inside a child")
+    from tests.test_gpu_lse_forms import check_forced_child
+    check_forced_child(setting, tmp_path)
+
+
 @pytest.mark.parametrize("H,R,use_rows", [(64, 10, False), (64, 200, True), (512, 700, True), (512, 2560, True), (128, 161, True),
                                          (512, 159, False),
                                          # the W-stationary persistent kernel (H = 512 with a row list): one tile per workgroup at 2 560 rows; two
