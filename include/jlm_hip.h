@@ -678,6 +678,65 @@ typedef struct {
 #define JLM_GENERATE_EVENTS_PER_FRAME 5
 int jlm_generate_frames(const jlm_decode_model *model_host, const jlm_generate_plan *plan_host, void *stream, void *const *events);
 
+/* ------------------------------------------------------------------------
+ * Next-word prediction and beam-search completion (LSTM_Model.predict_top / complete, jlm_amd/complete.py): the reference's
+ * find_top_N (decoder/model.py:25-26, an argsort of one host-side distribution) for many rows, and an n-best continuation loop.
+ *
+ * jlm_topk_rows: per row r < n_rows of f32 logits y[r * ld_y + 0 .. n_cols) (ld_y % 4 == 0, ld_y >= n_cols rounded up to 4, y 16-byte
+ * aligned; the row is read once), its k best words ranked by y descending, equal logits lower id first (the greedy draw's rule):
+ * ids[r * ld_out + i], i < k, and nll[r * ld_out + i] = lse - y in f64 with lse = m + log S, m = max y, S = sum_j expf(y_j - m_j)
+ * rescaled in f64 to m (f32 exp, f64 sums, a fixed order for a given n_cols; within ~1e-7 of the f64 lse); self_norm: nll = -y.
+ * A non-finite max or sum: *flags |= 1 (flags may be NULL), the row's ids -1 and nll NaN.  1 <= k <= min(JLM_TOPK_MAX, n_cols),
+ * ld_out >= k.  Returns 0, -1 for arguments the kernel cannot handle, or a hipError_t. */
+#define JLM_TOPK_MAX 64
+int jlm_topk_rows(const float *y, int ld_y, int n_cols, int n_rows, int k, int self_norm, int *ids, double *nll, int ld_out, int *flags,
+                  void *stream);
+
+/* jlm_beam_merge: one beam-search selection per prompt p < n_prompts over per-row top-`beam` lists (jlm_topk_rows with k = ld_out =
+ * beam).  first != 0: the prompt's one candidate row is p, its score 0; else rows p * beam + j, j < beam (rank j of the previous beam)
+ * with score[row] and finished[row].  A candidate is (score + nll, parent rank j, word); a finished parent gives one carry (its score,
+ * word -1) instead of its row's list.  The beam best by (score ascending, parent rank ascending, word ascending) -- per row taken in
+ * list order, equal f64 scores lower word first -- go to rows q = p * beam + i, i = rank: score[q], finished[q] (a carry, or a word
+ * equal to stop_id when stop_id >= 0), word[q] (the word the next LSTM step consumes: the word, or for a carry max(stop_id, 0)),
+ * prev[q] (the parent's row: first ? p : p * beam + j), and the back-pointers bp_parent[q] = j, bp_word[q] (-1: carry),
+ * bp_nll[q] (0: carry).  score / finished are read and written in place.  Returns 0, -1 for bad arguments, or a hipError_t. */
+int jlm_beam_merge(const int *cand_ids, const double *cand_nll, int beam, int n_prompts, int first, int stop_id, int *word, int *prev,
+                   double *score, int *finished, int *bp_parent, int *bp_word, double *bp_nll, void *stream);
+
+/* The beam-search loop.  n_prompts prompts, RIGHT-aligned on n_prompt frames and sorted longest first, as jlm_generate_plan's rows:
+ * prompt frames step the live prefix r < n_live[f] of rows 0 .. n_prompts - 1, consuming prompt[f][r] and continuing prev[f][r].
+ * The last prompt frame (f = n_prompt - 1) is selecting frame 0: the T projection, the logits and jlm_topk_rows over those n_prompts
+ * rows, then jlm_beam_merge (first = 1).  Each later frame f (selecting frame k = f - n_prompt + 1, up to n_words - 1) steps all
+ * R = n_prompts * beam rows, consuming word[r] and continuing row prev_row[r] of the set being read (what the previous merge wrote),
+ * then the T projection, the logits, jlm_topk_rows and jlm_beam_merge (first = 0).  Back-pointers of frame k at bp_*[k * R + q].
+ * After the call score[q] / finished[q] hold the final beam, rank i of prompt p at q = p * beam + i.  State h[2] / c[2] ping-pong as
+ * jlm_generate_plan's. */
+typedef struct {
+    int n_prompts, beam, n_prompt, n_words;
+    void *h[2]; float *c[2];        /* [R, H] state row sets, R = n_prompts * beam */
+    float *T;                       /* [R, ldt] f32 (as jlm_generate_plan.T) */
+    float *logits; int ld_logits;   /* [R, ld_logits] f32, ld_logits >= V rounded up to 4 */
+    const int *rows;                /* [R] device: 0, 1, ..., R - 1 */
+    const int *prev, *prompt;       /* [n_prompt][n_prompts] device */
+    const int *n_live;              /* [n_prompt] device */
+    const int *n_live_host;         /* [n_prompt] host */
+    int *cand_ids; double *cand_nll;    /* [R][beam] device: the per-row lists */
+    int *word, *prev_row;           /* [R] device: the next frame's inputs (the merge writes them) */
+    double *score; int *finished;   /* [R] device */
+    int stop_id;                    /* < 0: none */
+    int *bp_parent, *bp_word;       /* [n_words][R] device */
+    double *bp_nll;                 /* [n_words][R] device */
+    int *flags;                     /* one device int or NULL */
+} jlm_complete_plan;
+
+/* Enqueues n_prompt + n_words - 1 frames of [LSTM step (the launches jlm_generate_frames makes), and on selecting frames the T
+ * projection, jlm_gemm_nt per segment into plan.logits (+ b2), jlm_topk_rows, jlm_beam_merge].  No host synchronisation.  events (may
+ * be NULL): JLM_COMPLETE_EVENTS_PER_FRAME * frames hipEvent_t, recorded on `stream` [0] before the LSTM step [1] after it [2] after the
+ * T projection [3] after the logit GEMMs [4] after the selection [5] after the merge (prompt frames: empty brackets after [1]).
+ * 1 <= beam <= min(JLM_TOPK_MAX, V).  Returns 0, -2 for a model outside the loop's shapes, -1 / a hipError_t as the launchers do. */
+#define JLM_COMPLETE_EVENTS_PER_FRAME 6
+int jlm_complete_frames(const jlm_decode_model *model_host, const jlm_complete_plan *plan_host, void *stream, void *const *events);
+
 #ifdef __cplusplus
 }
 #endif

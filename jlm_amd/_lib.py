@@ -81,6 +81,15 @@ class GeneratePlan(Structure):
                 ("flags", c_void_p)]
 
 
+class CompletePlan(Structure):
+    """jlm_complete_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_prompts", c_int), ("beam", c_int), ("n_prompt", c_int), ("n_words", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2),
+                ("T", c_void_p), ("logits", c_void_p), ("ld_logits", c_int), ("rows", c_void_p), ("prev", c_void_p), ("prompt", c_void_p),
+                ("n_live", c_void_p), ("n_live_host", POINTER(c_int)), ("cand_ids", c_void_p), ("cand_nll", c_void_p),
+                ("word", c_void_p), ("prev_row", c_void_p), ("score", c_void_p), ("finished", c_void_p), ("stop_id", c_int),
+                ("bp_parent", c_void_p), ("bp_word", c_void_p), ("bp_nll", c_void_p), ("flags", c_void_p)]
+
+
 P = c_void_p
 _SIGS = {
     "jlm_abi_version": ([], c_int),
@@ -128,6 +137,9 @@ _SIGS = {
     "jlm_score_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), P, P], c_int),
     "jlm_sample_rows": ([P, c_int, c_int, c_int, P, c_double, c_uint64, c_int, P, P, P, c_int, c_int, P, P, P, P, P], c_int),
     "jlm_generate_frames": ([POINTER(DecodeModel), POINTER(GeneratePlan), P, P], c_int),
+    "jlm_topk_rows": ([P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P], c_int),
+    "jlm_beam_merge": ([P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P], c_int),
+    "jlm_complete_frames": ([POINTER(DecodeModel), POINTER(CompletePlan), P, P], c_int),
     "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_split_form": ([], c_int),
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),

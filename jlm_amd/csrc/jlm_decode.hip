@@ -362,6 +362,17 @@ static int rows_t_projection(const jlm_decode_model *m, const void *h_out, const
                        stream);
 }
 
+// The full-vocabulary logits of rows 0 .. n_rows - 1 of T: one jlm_gemm_nt per segment into columns v_start .. v_end of `logits`
+// (+ b2) -- the logit GEMMs of jlm_generate_frames and jlm_complete_frames.
+static int rows_logits(const jlm_decode_model *m, const float *T, float *logits, int ld_logits, int n_rows, void *stream) {
+    for (int i = 0; i < m->n_segs; ++i) {
+        const jlm_segment &sg = m->segs[i];
+        JLM_TRY(jlm_gemm_nt(T + sg.t_off, m->ldt, nullptr, sg.B, sg.ldb, nullptr, logits + sg.v_start, ld_logits, nullptr,
+                            m->b2 + sg.v_start, n_rows, sg.v_end - sg.v_start, sg.k, nullptr, stream));
+    }
+    return 0;
+}
+
 // Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),
 // T, the full-vocabulary normaliser as the frame loop launches it for kind 0, and the fold into -log p of the target word.
 extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
@@ -447,17 +458,67 @@ extern "C" int jlm_generate_frames(const jlm_decode_model *m, const jlm_generate
         const int k = f - (P - 1);                                   // the draw of this frame, if any
         if (k >= 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, R, nullptr, stream));
         JLM_TRY(stamp(f, 2));
-        if (k >= 0)
-            for (int i = 0; i < m->n_segs; ++i) {
-                const jlm_segment &sg = m->segs[i];
-                JLM_TRY(jlm_gemm_nt(T + sg.t_off, m->ldt, nullptr, sg.B, sg.ldb, nullptr, p->logits + sg.v_start, p->ld_logits, nullptr,
-                                    m->b2 + sg.v_start, R, sg.v_end - sg.v_start, sg.k, nullptr, stream));
-            }
+        if (k >= 0) JLM_TRY(rows_logits(m, T, p->logits, p->ld_logits, R, stream));
         JLM_TRY(stamp(f, 3));
         if (k >= 0)
             JLM_TRY(jlm_sample_rows(p->logits, p->ld_logits, V, R, nullptr, p->temperature, p->seed, k, p->row_id, nullptr, p->done,
                                     p->stop_id, m->self_norm, p->word, p->ids + (size_t)k * R, p->nll + (size_t)k * R, p->flags, stream));
         JLM_TRY(stamp(f, 4));
+    }
+    return 0;
+}
+
+// Beam-search completion (include/jlm_hip.h jlm_complete_frames): the prompt frames as jlm_generate_frames' over the n_prompts prompt
+// rows; selecting frame 0 projects, materialises and selects from those rows alone (a prompt's beam starts from its one
+// distribution); every later frame steps all n_prompts * beam rows from the rows the previous merge chose, then the T projection, the
+// logit GEMMs, topk_rows_kernel and beam_merge_kernel, which writes the next frame's word / prev row and the back-pointers.
+extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p, void *stream, void *const *events) {
+    const int NP = p->n_prompts, B = p->beam, P = p->n_prompt, N = p->n_words;
+    if (NP < 0 || B < 1 || B > JLM_TOPK_MAX || P < 1 || N < 0 || !p->rows || !p->prev || !p->prompt || !p->n_live || !p->n_live_host ||
+        !p->logits || !p->cand_ids || !p->cand_nll || !p->word || !p->prev_row || !p->score || !p->finished || !p->bp_parent ||
+        !p->bp_word || !p->bp_nll)
+        return -1;
+    if (NP == 0 || N == 0) return 0;
+    if (m->split_lstm && !m->wt8) return -2;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    if (B > V || (long long)NP * B > 0x7fffffff) return -1;
+    const int R = NP * B;
+    if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
+    if (p->n_live_host[P - 1] != NP) return -1;                 // every prompt is live at the last prompt frame (right-aligned)
+    const bool t_is_h = m->untied && !m->split_lstm;
+    if (!t_is_h && !p->T) return -1;
+    hipStream_t main_s = (hipStream_t)stream;
+    auto stamp = [&](int f, int i) -> int {
+        if (!events) return 0;
+        return (int)hipEventRecord((hipEvent_t)events[(size_t)f * JLM_COMPLETE_EVENTS_PER_FRAME + i], main_s);
+    };
+    const int F = P + N - 1;
+    for (int f = 0; f < F; ++f) {
+        const bool prompt = f < P;
+        const int bound = prompt ? p->n_live_host[f] : R;
+        if (bound < 0 || (prompt && bound > NP)) return -1;
+        const int *ndev = prompt ? p->n_live + f : nullptr;
+        const int *word = prompt ? p->prompt + (size_t)f * NP : p->word;
+        const int *prev = prompt ? p->prev + (size_t)f * NP : p->prev_row;
+        void *h_in = p->h[f & 1], *h_out = p->h[(f + 1) & 1];
+        float *c_in = p->c[f & 1], *c_out = p->c[(f + 1) & 1];
+        float *T = t_is_h ? (float *)h_out : p->T;
+        JLM_TRY(stamp(f, 0));
+        if (bound > 0) JLM_TRY(rows_lstm_step(m, h_in, c_in, h_out, c_out, p->rows, prev, word, p->T, bound, ndev, stream));
+        JLM_TRY(stamp(f, 1));
+        const int k = f - (P - 1);                                   // the selecting frame, if any
+        const int n_sel = k == 0 ? NP : R;
+        if (k >= 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, n_sel, nullptr, stream));
+        JLM_TRY(stamp(f, 2));
+        if (k >= 0) JLM_TRY(rows_logits(m, T, p->logits, p->ld_logits, n_sel, stream));
+        JLM_TRY(stamp(f, 3));
+        if (k >= 0)
+            JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, n_sel, B, m->self_norm, p->cand_ids, p->cand_nll, B, p->flags, stream));
+        JLM_TRY(stamp(f, 4));
+        if (k >= 0)
+            JLM_TRY(jlm_beam_merge(p->cand_ids, p->cand_nll, B, NP, k == 0, p->stop_id, p->word, p->prev_row, p->score, p->finished,
+                                   p->bp_parent + (size_t)k * R, p->bp_word + (size_t)k * R, p->bp_nll + (size_t)k * R, stream));
+        JLM_TRY(stamp(f, 5));
     }
     return 0;
 }

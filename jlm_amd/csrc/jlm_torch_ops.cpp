@@ -19,6 +19,10 @@
 //   torch.ops.jlm.sample_rows(y, ..., word, ids, nll, flags)   one draw per row of materialised logits (jlm_sample_rows)
 //   torch.ops.jlm.generate_frames(Model, state row sets, logits, prompt arrays, ..., ids, nll, ...)
 //                             batched ancestral sampling: ONE op (jlm_generate_frames; LSTM_Model.generate)
+//   torch.ops.jlm.topk_rows(y, ..., k, ids, nll, flags)        the k best words of every row of materialised logits (jlm_topk_rows)
+//   torch.ops.jlm.beam_merge(cand_ids, cand_nll, ...)          one beam selection per prompt (jlm_beam_merge)
+//   torch.ops.jlm.complete_frames(Model, state row sets, logits, prompt arrays, ..., back-pointers, ...)
+//                             beam-search completion: ONE op (jlm_complete_frames; LSTM_Model.complete / predict_top)
 //   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
@@ -617,6 +621,120 @@ Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     return out;
 }
 
+// the k best words of every row of f32 logits y [n_rows, ld] with their -log p (jlm_topk_rows, include/jlm_hip.h): ids int32 and nll
+// float64 [n_rows, ld_out].
+void topk_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, int64_t k, bool self_norm, const Tensor &ids, const Tensor &nll,
+               int64_t ld_out, const OptTensor &flags) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.topk_rows: y [n_rows, ld] float32");
+    TORCH_CHECK(is(ids, at::kInt, n_rows * ld_out) && is(nll, at::kDouble, n_rows * ld_out) &&
+                    (!flags.has_value() || !flags->defined() || is(*flags, at::kInt, 1)),
+                "jlm.topk_rows: int32 ids / float64 nll [n_rows, ld_out], int32 flags [1]");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    jlm_check(jlm_topk_rows(ptr<const float>(y, "y"), (int)ld, (int)n_cols, (int)n_rows, (int)k, self_norm ? 1 : 0, ptr<int>(ids, "ids"),
+                            ptr<double>(nll, "nll"), (int)ld_out, optr<int>(flags, "flags"), stream_of(y)),
+              "jlm_topk_rows");
+}
+
+// one beam selection per prompt over per-row top-`beam` lists (jlm_beam_merge, include/jlm_hip.h): cand_ids int32 / cand_nll float64
+// [rows, beam]; word / prev / score (float64) / finished / bp_* [n_prompts * beam].
+void beam_merge(const Tensor &cand_ids, const Tensor &cand_nll, int64_t beam, int64_t n_prompts, bool first, int64_t stop_id,
+                const Tensor &word, const Tensor &prev, const Tensor &score, const Tensor &finished, const Tensor &bp_parent,
+                const Tensor &bp_word, const Tensor &bp_nll) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    const int64_t R = n_prompts * beam;
+    TORCH_CHECK(beam >= 1 && n_prompts >= 0 && is(cand_ids, at::kInt, R * beam) && is(cand_nll, at::kDouble, R * beam),
+                "jlm.beam_merge: cand_ids int32 / cand_nll float64 [n_prompts * beam, beam]");
+    TORCH_CHECK(is(word, at::kInt, R) && is(prev, at::kInt, R) && is(score, at::kDouble, R) && is(finished, at::kInt, R) &&
+                    is(bp_parent, at::kInt, R) && is(bp_word, at::kInt, R) && is(bp_nll, at::kDouble, R),
+                "jlm.beam_merge: int32 word / prev / finished / bp_parent / bp_word, float64 score / bp_nll [n_prompts * beam]");
+    const c10::hip::HIPGuard device_guard(cand_ids.device().index());
+    jlm_check(jlm_beam_merge(ptr<const int>(cand_ids, "cand_ids"), ptr<const double>(cand_nll, "cand_nll"), (int)beam, (int)n_prompts,
+                             first ? 1 : 0, (int)stop_id, ptr<int>(word, "word"), ptr<int>(prev, "prev"), ptr<double>(score, "score"),
+                             ptr<int>(finished, "finished"), ptr<int>(bp_parent, "bp_parent"), ptr<int>(bp_word, "bp_word"),
+                             ptr<double>(bp_nll, "bp_nll"), stream_of(cand_ids)),
+              "jlm_beam_merge");
+}
+
+// beam-search completion (jlm_complete_frames, include/jlm_hip.h): state row sets h0/c0 and h1/c1 [R, H] (ping-pong, R = n_prompts *
+// beam), T [R, ldt] unless the model is untied f32, logits [R, ld_logits]; rows [R], prev / prompt [n_prompt][n_prompts], n_live
+// [n_prompt] int32 and its host copy; cand_ids / cand_nll [R, beam]; word / prev_row / score / finished [R]; bp_* [n_words][R]; flags
+// one int32.  Every id must lie in [0, V): the caller checks (jlm_amd/complete.py).  -> timed: [frames, 5] milliseconds per frame (LSTM
+// step, T projection, logit GEMMs, selection, merge) after waiting for the last frame; else an empty tensor and nothing waits.
+Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
+                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &cand_ids,
+                       const Tensor &cand_nll, const Tensor &word, const Tensor &prev_row, const Tensor &score, const Tensor &finished,
+                       int64_t stop_id, const Tensor &bp_parent, const Tensor &bp_word, const Tensor &bp_nll, const OptTensor &flags,
+                       int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed) {
+    const jlm_decode_model &m = model->m;
+    const int64_t NP = n_prompts, B = beam, P = n_prompt, N = n_words, R = n_prompts * beam;
+    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(NP >= 0 && B >= 1 && P >= 1 && N >= 0 && (int64_t)n_live_host.size() == P,
+                "jlm.complete_frames: n_live_host holds one count per prompt frame");
+    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= NP, "jlm.complete_frames: a live-row count outside [0, n_prompts]");
+    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
+                    is(c0, at::kFloat, R * m.H) && is(c1, at::kFloat, R * m.H),
+                "jlm.complete_frames: state row sets [n_prompts * beam, H] of 4-byte values");
+    TORCH_CHECK(is(rows, at::kInt, R) && is(prev, at::kInt, P * NP) && is(prompt, at::kInt, P * NP) && is(n_live, at::kInt, P),
+                "jlm.complete_frames: int32 rows [R], prev / prompt [n_prompt][n_prompts], n_live [n_prompt]");
+    TORCH_CHECK(is(cand_ids, at::kInt, R * B) && is(cand_nll, at::kDouble, R * B) && is(word, at::kInt, R) && is(prev_row, at::kInt, R) &&
+                    is(score, at::kDouble, R) && is(finished, at::kInt, R),
+                "jlm.complete_frames: cand_ids int32 / cand_nll float64 [R, beam]; int32 word / prev_row / finished, float64 score [R]");
+    TORCH_CHECK(is(bp_parent, at::kInt, N * R) && is(bp_word, at::kInt, N * R) && is(bp_nll, at::kDouble, N * R) &&
+                    (!has(flags) || is(*flags, at::kInt, 1)),
+                "jlm.complete_frames: int32 bp_parent / bp_word, float64 bp_nll [n_words][R], int32 flags");
+    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.complete_frames: T [R, ldt] float32");
+    TORCH_CHECK(is(logits, at::kFloat, R * ld_logits), "jlm.complete_frames: logits [R, ld_logits] float32");
+    jlm_complete_plan p{};
+    p.n_prompts = (int)NP; p.beam = (int)B; p.n_prompt = (int)P; p.n_words = (int)N;
+    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+    p.T = optr<float>(T, "T");
+    p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits;
+    p.rows = ptr<const int>(rows, "rows"); p.prev = ptr<const int>(prev, "prev"); p.prompt = ptr<const int>(prompt, "prompt");
+    p.n_live = ptr<const int>(n_live, "n_live");
+    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
+    p.n_live_host = live_host.data();
+    p.cand_ids = ptr<int>(cand_ids, "cand_ids"); p.cand_nll = ptr<double>(cand_nll, "cand_nll");
+    p.word = ptr<int>(word, "word"); p.prev_row = ptr<int>(prev_row, "prev_row");
+    p.score = ptr<double>(score, "score"); p.finished = ptr<int>(finished, "finished");
+    p.stop_id = (int)stop_id;
+    p.bp_parent = ptr<int>(bp_parent, "bp_parent"); p.bp_word = ptr<int>(bp_word, "bp_word"); p.bp_nll = ptr<double>(bp_nll, "bp_nll");
+    p.flags = optr<int>(flags, "flags");
+    const int dev = h0.device().index();
+    const c10::hip::HIPGuard device_guard(dev);
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
+    const int64_t F = N > 0 ? P + N - 1 : 0;
+    std::vector<hipEvent_t> ev;
+    struct Destroy {
+        std::vector<hipEvent_t> &ev;
+        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } destroy{ev};
+    if (timed)
+        for (int64_t i = 0; i < F * JLM_COMPLETE_EVENTS_PER_FRAME; ++i) {
+            hipEvent_t e;
+            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
+            ev.push_back(e);
+        }
+    {
+        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
+        jlm_check(jlm_complete_frames(&m, &p, st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), "jlm_complete_frames");
+    }
+    if (!timed || F == 0 || NP == 0) return at::empty({0}, at::kDouble);
+    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
+    Tensor out = at::zeros({F, JLM_COMPLETE_EVENTS_PER_FRAME - 1}, at::kDouble);
+    auto a = out.accessor<double, 2>();
+    for (int64_t f = 0; f < F; ++f)
+        for (int i = 0; i + 1 < JLM_COMPLETE_EVENTS_PER_FRAME; ++i) {
+            float ms = 0.0f;
+            jlm_check((int)hipEventElapsedTime(&ms, ev[f * JLM_COMPLETE_EVENTS_PER_FRAME + i], ev[f * JLM_COMPLETE_EVENTS_PER_FRAME + i + 1]),
+                      "hipEventElapsedTime");
+            a[f][i] = ms;
+        }
+    return out;
+}
+
 int64_t abi_version() { return jlm_abi_version(); }
 int64_t beam_step_max_cands(int64_t beam, int64_t n_frames, int64_t mode) { return jlm_beam_step_max_cands((int)beam, (int)n_frames, (int)mode); }
 
@@ -659,6 +777,17 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(g!) word, Tensor(h!)? done, int stop_id, float temperature, int seed, Tensor(i!) ids, Tensor(j!) nll, Tensor(k!)? flags, "
           "int n_rows, int n_prompt, int n_words, bool timed) -> Tensor",
           generate_frames);
+    m.def("topk_rows(Tensor y, int ld, int n_cols, int n_rows, int k, bool self_norm, Tensor(a!) ids, Tensor(b!) nll, int ld_out, "
+          "Tensor(c!)? flags) -> ()",
+          topk_rows);
+    m.def("beam_merge(Tensor cand_ids, Tensor cand_nll, int beam, int n_prompts, bool first, int stop_id, Tensor(a!) word, Tensor(b!) prev, "
+          "Tensor(c!) score, Tensor(d!) finished, Tensor(e!) bp_parent, Tensor(f!) bp_word, Tensor(g!) bp_nll) -> ()",
+          beam_merge);
+    m.def("complete_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev, Tensor prompt, Tensor n_live, int[] n_live_host, Tensor(g!) cand_ids, "
+          "Tensor(h!) cand_nll, Tensor(i!) word, Tensor(j!) prev_row, Tensor(k!) score, Tensor(l!) finished, int stop_id, Tensor(m!) bp_parent, "
+          "Tensor(n!) bp_word, Tensor(o!) bp_nll, Tensor(p!)? flags, int n_prompts, int beam, int n_prompt, int n_words, bool timed) -> Tensor",
+          complete_frames);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

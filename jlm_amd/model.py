@@ -1046,6 +1046,30 @@ class LSTM_Model():
             g = self._gen = Generator(self.dev)
         return generate(g, prompts, n_words, temperature, seed, stop_id, max_rows)
 
+    def _completer(self):
+        from .complete import Completer
+        c = getattr(self, "_comp", None)
+        if c is None:
+            c = self._comp = Completer(self.dev)
+        return c
+
+    def predict_top(self, contexts, n=10, max_rows=None):
+        """The ``n`` most probable next words after each context, on the device (jlm_amd/complete.py; the reference's
+        find_top_N(predict(...), N), model.py:25-26, without the host-side softmax and argsort).  ``contexts``: word-id lists of length
+        >= 1, each consumed from the zero state as generate() consumes a prompt.  -> per context (ids int64 [n], logp float64 [n]),
+        most probable first, equal logits lower id first; logp = y - lse (self_norm: y).  1 <= n <= min(64, V)."""
+        from .complete import predict_top
+        return predict_top(self._completer(), contexts, n, max_rows)
+
+    def complete(self, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None):
+        """Deterministic beam search over the LM, separately for each prompt (jlm_amd/complete.py).  A hypothesis's score is its summed
+        -log p (f64); each frame keeps the ``beam_width`` best by (score, parent's rank, word id); with ``stop_id`` a hypothesis ending
+        in it is finished and carried unchanged.  -> per prompt ``n_best`` (default beam_width) tuples (ids int64, nll float64 per
+        word, total), total ascending.  ValueError for a bad argument before anything runs; JlmHipError when the device flags a
+        non-finite logit or log-normaliser."""
+        from .complete import complete
+        return complete(self._completer(), prompts, n_words, beam_width, n_best, stop_id, max_rows)
+
 
 def show_prob(model, w2i, inputs):
     """Per-word -log p of a word sequence and their total (the reference's show_prob, model.py:208-211, which reads
