@@ -272,8 +272,8 @@ int jlm_wordlist_lse_perm(const jlm_segment *segs_host, int n_segs, const float 
 
 /* jlm_wordlist_lse on split rows, single-segment models (seg->B = split rows scaled by 2^eB,
  * t_scale = 2^eT, descale = 2^-(eT+eB) as for jlm_vocab_lse_split; b2 is added in the fold).
- * max_words = longest word list among the groups (<= 4064).  Returns -2 when the shape is outside
- * the kernel (k > 256, beam > 32, longer lists): use jlm_wordlist_lse then. */
+ * max_words = longest word list among the groups (<= 4064; shorter lists run too when called here).  Returns -2 when
+ * the shape is outside the kernel (k > 256, beam > 64, longer lists; jlm_wordlist_lse_form): use jlm_wordlist_lse then. */
 int jlm_wordlist_lse_split(const jlm_segment *seg_host, float t_scale, float descale, const float *b2,
                            const float *T, int ldt,
                            const int *g0, const int *cnt, const int *cnt_idx,
@@ -286,11 +286,38 @@ int jlm_wordlist_lse_split(const jlm_segment *seg_host, float t_scale, float des
  * sentence s merges the words wl[wl_off[wl_base + s] .. wl_off[wl_base + s + 1]) into its running
  * (run_max, run_sum) and refreshes lse -- what jlm_wordlist_lse(merge = 1) does for n_old_frames * n_sent
  * groups, but with one workgroup per sentence gathering the list once.  rmax = n_sent * beam.
- * Returns -2 outside the kernel's shape (max_words > 128, k > 256, beam > 32). */
+ * Returns -2 outside the kernel's shape (max_words > 128, k > 256, beam > 64; jlm_wordlist_merge_form). */
 int jlm_wordlist_merge_split(const jlm_segment *seg_host, float t_scale, float descale, const float *b2,
                              const float *T, int ldt, const int *cnt, int n_sent, int beam, int n_old_frames,
                              const int *wl, const int *wl_off, int wl_base, int max_words,
                              float *run_max, double *run_sum, double *lse, void *stream);
+
+/* ABI 12 (additive): which kernel the word-list normaliser launches (pure host, no HIP call).  jlm_decode_frames,
+ * jlm_wordlist_lse(_perm), jlm_wordlist_lse_split and jlm_wordlist_merge_split ask here and decide nowhere else.
+ * segs_host / n_segs: the f32 segments; split_seg: the split rows of a single-segment model (NULL: none); has_wl_w:
+ * whether a weight-word list is given (the *_perm entry points); max_words: the longest list of the launch.
+ * JLM_WORDLIST_MFMA (read once per process; 0 switches the matrix-pipe form off) is the only setting.
+ *   0 JLM_WL_F32          wordlist_kernel<1> (csrc/jlm_beam.hip): any segments, any k, any beam, weight-word lists
+ *   1 JLM_WL_MFMA         wordlist_lse_mfma_kernel<NK> (csrc/jlm_gemm.hip), NK = ceil(k / 32): one f32 segment,
+ *                         1 <= k <= 256, beam <= 64, no weight-word list, JLM_WORDLIST_MFMA unset or non-zero
+ *   2 JLM_WL_SPLIT        wordlist_lse_split_kernel<NS> (csrc/jlm_split.hip), NS = 2 / 4 / 8 / 12 / 16 for ceil(k / 16)
+ *                         up to that: split rows, one segment, beam <= 64, 128 <= max_words <= 4064, no weight-word list
+ *   3 JLM_WL_MERGE_SPLIT  wordlist_merge_split_kernel<NS> (csrc/jlm_split.hip), NS = 4 / 8 / 12 / 16: the incremental
+ *                         back-fill on split rows, one segment, beam <= 64, max_words <= 128
+ * jlm_wordlist_lse_form returns 0, 1 or 2, or -1 for segments the f32 kernels refuse (bad count, k / ldb / t_off / ldt
+ * not multiples of 4, rows past LDS).  jlm_wordlist_merge_form returns 3, or else the group-wise merge through
+ * jlm_wordlist_lse(_split) with merge = 1: what jlm_wordlist_lse_form(segs, n, split_seg, 0, ...) returns. */
+#define JLM_WL_F32 0
+#define JLM_WL_MFMA 1
+#define JLM_WL_SPLIT 2
+#define JLM_WL_MERGE_SPLIT 3
+#define JLM_WL_SPLIT_MIN_WORDS 128
+#define JLM_WL_SPLIT_MAX_WORDS 4064
+#define JLM_WL_MERGE_MAX_WORDS 128
+int jlm_wordlist_lse_form(const jlm_segment *segs_host, int n_segs, const jlm_segment *split_seg, int has_wl_w, int ldt,
+                          int beam, int max_words);
+int jlm_wordlist_merge_form(const jlm_segment *segs_host, int n_segs, const jlm_segment *split_seg, int ldt, int beam,
+                            int max_words);
 
 /* ------------------------------------------------------------------------
  * Lattice of a batch (CSR, built on the host by jlm_amd/lattice.py following

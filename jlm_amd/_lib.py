@@ -143,6 +143,8 @@ _SIGS = {
     "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_split_form": ([], c_int),
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),
+    "jlm_wordlist_lse_form": ([POINTER(Segment), c_int, POINTER(Segment), c_int, c_int, c_int, c_int], c_int),
+    "jlm_wordlist_merge_form": ([POINTER(Segment), c_int, POINTER(Segment), c_int, c_int, c_int], c_int),
 }
 EXPORTS = sorted(_SIGS)
 

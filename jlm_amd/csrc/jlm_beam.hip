@@ -200,6 +200,38 @@ extern "C" int jlm_edge_logits_perm(const jlm_segment *segs_host, int n_segs, co
     return 0;
 }
 
+// split rows the split-row word-list kernels (csrc/jlm_split.hip) can read: 1 .. 16 f16 k-steps, rows of whole 16-value granules
+static bool wl_split_hosts(const jlm_segment &s, int ldt) {
+    const int ns = (s.k + 15) / 16;
+    return ns >= 1 && ns <= 16 && s.k % 4 == 0 && s.ldb % 16 == 0 && s.ldb >= ns * 16 && s.t_off % 4 == 0 && ldt % 4 == 0;
+}
+
+// The one place the word-list normaliser's kernel is chosen (include/jlm_hip.h lists the forms): jlm_decode_frames,
+// jlm_wordlist_lse_perm and the three launchers ask here.  Split rows (deep gather ring) from 128 words on, where the gather of
+// the list dominates; the matrix pipe on f32 rows for single-segment models up to k = 256; the f32 kernel for the rest.
+extern "C" int jlm_wordlist_lse_form(const jlm_segment *segs_host, int n_segs, const jlm_segment *split_seg, int has_wl_w, int ldt,
+                                     int beam, int max_words) {
+    if (split_seg && n_segs == 1 && !has_wl_w && beam <= 64 && max_words >= JLM_WL_SPLIT_MIN_WORDS &&
+        max_words <= JLM_WL_SPLIT_MAX_WORDS && wl_split_hosts(*split_seg, ldt))
+        return JLM_WL_SPLIT;
+    SegTable t;
+    if (seg_table(segs_host, n_segs, t) || ldt % 4) return -1;
+    static int use_mfma = -1;
+    if (use_mfma < 0) { const char *e = getenv("JLM_WORDLIST_MFMA"); use_mfma = e ? atoi(e) : 1; }
+    if (!has_wl_w && use_mfma && n_segs == 1 && beam <= 64 && segs_host[0].k >= 1 && segs_host[0].k <= 256) return JLM_WL_MFMA;
+    if (wl_lds_bytes(beam, ldt) > 160 * 1024) return -1;
+    return JLM_WL_F32;
+}
+
+// The incremental decoder's back-fill of a frame's new words into every older row: one workgroup per sentence on split rows for
+// lists of at most 128 words (the whole list in LDS), else the group-wise merge through the word-list normaliser's form.
+extern "C" int jlm_wordlist_merge_form(const jlm_segment *segs_host, int n_segs, const jlm_segment *split_seg, int ldt, int beam,
+                                       int max_words) {
+    if (split_seg && n_segs == 1 && beam <= 64 && max_words <= JLM_WL_MERGE_MAX_WORDS && wl_split_hosts(*split_seg, ldt))
+        return JLM_WL_MERGE_SPLIT;
+    return jlm_wordlist_lse_form(segs_host, n_segs, split_seg, 0, ldt, beam, max_words);
+}
+
 // matrix-pipe form for single-segment models (jlm_gemm.hip)
 extern "C" int jlm_wordlist_lse_mfma(const jlm_segment *seg_host, const float *b2, const float *T, int ldt, const int *g0,
                                      const int *cnt, const int *cnt_idx, const int *wl, const int *wl_off,
@@ -221,15 +253,12 @@ extern "C" int jlm_wordlist_lse_perm(const jlm_segment *segs_host, int n_segs, c
     SegTable t;
     if (seg_table(segs_host, n_segs, t) || ldt % 4) return -1;
     if (n_groups <= 0) return 0;
-    static int use_mfma = -1;
-    if (use_mfma < 0) { const char *e = getenv("JLM_WORDLIST_MFMA"); use_mfma = e ? atoi(e) : 1; }
-    if (!wl_w && use_mfma && n_segs == 1 && beam <= 64 && segs_host[0].k <= 256) {
-        int r = jlm_wordlist_lse_mfma(segs_host, b2, T, ldt, g0, cnt, cnt_idx, wl, wl_off, wl_idx, wl_base, run_max, run_sum,
-                                      lse, merge, beam, n_groups, stream);
-        if (r != -2) return r;
-    }
-    size_t lds = wl_lds_bytes(beam, ldt);
-    if (lds > 160 * 1024) return -1;
+    const int form = jlm_wordlist_lse_form(segs_host, n_segs, nullptr, wl_w != nullptr, ldt, beam, 0);
+    if (form < 0) return -1;
+    if (form == JLM_WL_MFMA)
+        return jlm_wordlist_lse_mfma(segs_host, b2, T, ldt, g0, cnt, cnt_idx, wl, wl_off, wl_idx, wl_base, run_max, run_sum,
+                                     lse, merge, beam, n_groups, stream);
+    const size_t lds = wl_lds_bytes(beam, ldt);
     static JlmLdsGrant grant;
     if (int rc = jlm_grant_lds(grant, reinterpret_cast<const void *>(wordlist_kernel<1>), (int)lds)) return rc;
     hipLaunchKernelGGL(wordlist_kernel<1>, dim3(n_groups), dim3(WL_THREADS), lds, (hipStream_t)stream, t, b2, T, ldt,

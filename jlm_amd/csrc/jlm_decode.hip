@@ -155,7 +155,6 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
     const int rmax = B * beam;
     const bool dynamic = p->kind == 2, select = p->kind == 1, full = p->kind == 0;
     const int mode = m->self_norm ? 1 : (dynamic ? 2 : 0);
-    const bool wl_split = m->split_segs != nullptr && m->n_segs == 1 && beam <= 64;
     jlm_beam_state st = *st_in;
     hipStream_t main_s = (hipStream_t)stream, side_s = events ? nullptr : (hipStream_t)side_stream;
     // events != NULL: JLM_EVENTS_PER_FRAME timing events per frame, recorded on `stream` (no side stream then, so that
@@ -167,15 +166,13 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
     hipEvent_t join = nullptr;
     int pending_parts = 0;
 
-    // word-list normaliser: split rows (deep gather ring) for lists of 128 .. 4064 words, else the f32 kernel
+    // word-list normaliser: the kernel jlm_wordlist_lse_form names (split rows for lists of 128 .. 4064 words)
     auto wl_lse = [&](const int *g0, const int *cidx, const int *words, const int *off, const int *idx, int base, int merge,
                       int n_groups, int max_words) -> int {
-        if (wl_split && max_words >= 128 && max_words <= 4064) {
-            int r = jlm_wordlist_lse_split(m->split_segs, m->split_t_scale[0], m->split_descale[0], m->b2, p->T, m->ldt, g0,
-                                           st.cnt, cidx, words, off, idx, base, max_words, p->run_max, p->run_sum, st.lse,
-                                           merge, beam, n_groups, stream);
-            if (r != -2) return r;
-        }
+        if (jlm_wordlist_lse_form(m->segs, m->n_segs, m->split_segs, 0, m->ldt, beam, max_words) == JLM_WL_SPLIT)
+            return jlm_wordlist_lse_split(m->split_segs, m->split_t_scale[0], m->split_descale[0], m->b2, p->T, m->ldt, g0,
+                                          st.cnt, cidx, words, off, idx, base, max_words, p->run_max, p->run_sum, st.lse,
+                                          merge, beam, n_groups, stream);
         return jlm_wordlist_lse(m->segs, m->n_segs, m->b2, p->T, m->ldt, g0, st.cnt, cidx, words, off, idx, base,
                                 p->run_max, p->run_sum, st.lse, merge, beam, n_groups, stream);
     };
@@ -202,13 +199,12 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
         }
         JLM_TRY(stamp(f, 0));
         if (dynamic && !m->self_norm && f >= 2) {
-            int r = -2;
-            if (wl_split && p->dd_max <= 128)
-                r = jlm_wordlist_merge_split(m->split_segs, m->split_t_scale[0], m->split_descale[0], m->b2, p->T, m->ldt,
-                                             st.cnt, B, beam, f - 1, p->dd_words, p->dd_off, f * B, p->dd_max, p->run_max,
-                                             p->run_sum, st.lse, stream);
-            if (r == -2) r = wl_lse(p->g0, p->cidx, p->dd_words, p->dd_off, p->sidx, f * B, 1, (f - 1) * B, p->dd_max);
-            JLM_TRY(r);
+            if (jlm_wordlist_merge_form(m->segs, m->n_segs, m->split_segs, m->ldt, beam, p->dd_max) == JLM_WL_MERGE_SPLIT)
+                JLM_TRY(jlm_wordlist_merge_split(m->split_segs, m->split_t_scale[0], m->split_descale[0], m->b2, p->T, m->ldt,
+                                                 st.cnt, B, beam, f - 1, p->dd_words, p->dd_off, f * B, p->dd_max, p->run_max,
+                                                 p->run_sum, st.lse, stream));
+            else
+                JLM_TRY(wl_lse(p->g0, p->cidx, p->dd_words, p->dd_off, p->sidx, f * B, 1, (f - 1) * B, p->dd_max));
         }
         JLM_TRY(stamp(f, 1));
         st.lse_part = pending_parts ? p->part : nullptr;

@@ -1281,9 +1281,9 @@ extern "C" int jlm_wordlist_lse_mfma(const jlm_segment *seg_host, const float *b
                                      const int *cnt, const int *cnt_idx, const int *wl, const int *wl_off,
                                      const int *wl_idx, int wl_base, float *run_max, double *run_sum, double *lse,
                                      int merge, int beam, int n_groups, void *stream) {
+    if (jlm_wordlist_lse_form(seg_host, 1, nullptr, 0, ldt, beam, 0) != JLM_WL_MFMA) return -2;
     const jlm_segment sg = *seg_host;
     const int nk = (sg.k + BK - 1) / BK;
-    if (nk < 1 || nk > 8 || sg.k % 4 || sg.ldb % 4 || sg.t_off % 4 || ldt % 4 || beam > 64) return -2;
     if (n_groups <= 0) return 0;
     const int lds = 4 * (2 * 32 * 32 + 2 * 32) * 4;
     hipStream_t st = (hipStream_t)stream;

@@ -1190,7 +1190,7 @@ extern "C" int jlm_vocab_lse_hybrid(const jlm_segment *segs_host_in, const float
 // barrier in the loop, only the wave's own s_waitcnt vmcnt(chunks still allowed in flight).
 // The list's word ids and biases are staged in LDS once (the DMA addresses and the fold need them).
 #define WLS_RING 3
-#define WLS_MAX_WORDS 4096
+#define WLS_MAX_WORDS 4096                     // LDS for word ids and biases: JLM_WL_SPLIT_MAX_WORDS + one tile
 
 template <int NS>
 __global__ __launch_bounds__(256) void wordlist_lse_split_kernel(
@@ -1355,8 +1355,8 @@ extern "C" int jlm_wordlist_lse_split(const jlm_segment *seg_host, float t_scale
                                       double *run_sum, double *lse, int merge, int beam, int n_groups, void *stream) {
     const jlm_segment sg = *seg_host;
     const int ns = (sg.k + 15) / 16;
-    if (ns < 1 || ns > 16 || sg.k % 4 || sg.ldb % 16 || sg.ldb < ns * 16 || sg.t_off % 4 || ldt % 4 || beam > 64) return -2;
-    if (max_words > WLS_MAX_WORDS - 32) return -2;
+    // called here the kernel takes lists of any length up to its LDS; JLM_WL_SPLIT_MIN_WORDS is where the decode prefers it
+    if (jlm_wordlist_lse_form(seg_host, 1, seg_host, 0, ldt, beam, max(max_words, JLM_WL_SPLIT_MIN_WORDS)) != JLM_WL_SPLIT) return -2;
     if (n_groups <= 0) return 0;
     const int lds = (4 * WLS_RING * 32 * 64 + 2 * WLS_MAX_WORDS) * 4;
     hipStream_t st = (hipStream_t)stream;
@@ -1387,7 +1387,7 @@ extern "C" int jlm_wordlist_lse_split(const jlm_segment *seg_host, float t_scale
 // rows in blocks of 32 (row operands split on the fly, 3 f16 MFMAs per k-step) and merge the list's
 // (max, sum exp) into each row's running pair.  Rows: g = frame * rmax + sentence * beam + slot,
 // slot < cnt[frame * n_sent + sentence] (the layout of jlm_beam_state).
-#define WLM_MAX_WORDS 128
+#define WLM_MAX_WORDS JLM_WL_MERGE_MAX_WORDS
 
 template <int NS>
 __global__ __launch_bounds__(256) void wordlist_merge_split_kernel(
@@ -1510,8 +1510,7 @@ extern "C" int jlm_wordlist_merge_split(const jlm_segment *seg_host, float t_sca
                                         double *run_sum, double *lse, void *stream) {
     const jlm_segment sg = *seg_host;
     const int ns = (sg.k + 15) / 16;
-    if (ns < 1 || ns > 16 || sg.k % 4 || sg.ldb % 16 || sg.ldb < ns * 16 || sg.t_off % 4 || ldt % 4 || beam > 64) return -2;
-    if (max_words > WLM_MAX_WORDS) return -2;
+    if (jlm_wordlist_merge_form(seg_host, 1, seg_host, ldt, beam, max_words) != JLM_WL_MERGE_SPLIT) return -2;
     if (n_sent <= 0 || n_old_frames <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
 #define JLM_WLM_LAUNCH(N)                                                                                                  \

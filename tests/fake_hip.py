@@ -157,7 +157,70 @@ def gemm_nt_split_form(M, N, stages=3, xcd=1):
     return 2 if tiles128 < 512 else 3
 
 
+# include/jlm_hip.h jlm_wordlist_lse_form / jlm_wordlist_merge_form ids
+WL_FORMS = ("F32", "MFMA", "SPLIT", "MERGE_SPLIT")
+WL_FORM = {name: i for i, name in enumerate(WL_FORMS)}
+
+
+def _wl_split_hosts(split, ldt):
+    """split rows (v_start, v_end, k, t_off, ldb) the split-row word-list kernels read: 1 .. 16 f16 k-steps, whole granules"""
+    k, t_off, ldb = split[2], split[3], split[4]
+    ns = (k + 15) // 16
+    return 1 <= ns <= 16 and k % 4 == 0 and ldb % 16 == 0 and ldb >= ns * 16 and t_off % 4 == 0 and ldt % 4 == 0
+
+
+def wordlist_lse_form(segs, split, has_wl_w, ldt, beam, max_words, mfma=1):
+    """include/jlm_hip.h jlm_wordlist_lse_form with JLM_WORDLIST_MFMA = mfma; segs: (v_start, v_end, k, t_off, ldb) per f32 segment,
+    split: the same for the split rows or None.  Split rows for one segment, beam <= 64 and 128 .. 4064 words; the matrix pipe for one
+    f32 segment of k <= 256 and beam <= 64; the f32 kernel for the rest, weight-word lists included; -1 where the f32 kernels refuse."""
+    if split is not None and len(segs) == 1 and not has_wl_w and beam <= 64 and 128 <= max_words <= 4064 and _wl_split_hosts(split, ldt):
+        return WL_FORM["SPLIT"]
+    if not 1 <= len(segs) <= 8 or ldt % 4 or any(k % 4 or ldb % 4 or t_off % 4 for _, _, k, t_off, ldb in segs):
+        return -1
+    if not has_wl_w and mfma and len(segs) == 1 and beam <= 64 and 1 <= segs[0][2] <= 256:
+        return WL_FORM["MFMA"]
+    if (16 * ldt + 4 * 16 * 2) * 4 > 160 * 1024:
+        return -1
+    return WL_FORM["F32"]
+
+
+def wordlist_merge_form(segs, split, ldt, beam, max_words, mfma=1):
+    """include/jlm_hip.h jlm_wordlist_merge_form: one workgroup per sentence on split rows for lists of at most 128 words (one segment,
+    beam <= 64), else the group-wise merge in the word-list normaliser's form"""
+    if split is not None and len(segs) == 1 and beam <= 64 and max_words <= 128 and _wl_split_hosts(split, ldt):
+        return WL_FORM["MERGE_SPLIT"]
+    return wordlist_lse_form(segs, split, 0, ldt, beam, max_words, mfma)
+
+
+def _seg_tuple(sg):
+    return (sg.v_start, sg.v_end, sg.k, sg.t_off, sg.ldb)
+
+
+def _split_arg(split_seg):
+    if split_seg is None:
+        return None
+    if hasattr(split_seg, "contents"):
+        return _seg_tuple(split_seg.contents) if split_seg else None
+    return _seg_tuple(split_seg[0] if not hasattr(split_seg, "k") else split_seg)
+
+
 class FakeLib:
+    @staticmethod
+    def jlm_wordlist_lse_form(segs, n_segs, split_seg, has_wl_w, ldt, beam, max_words):
+        """ABI 12: the kernel the word-list normaliser launches; JLM_WORDLIST_MFMA as the library reads it"""
+        if not 1 <= n_segs <= 8:
+            return -1
+        return wordlist_lse_form([_seg_tuple(segs[i]) for i in range(n_segs)], _split_arg(split_seg), has_wl_w, ldt, beam, max_words,
+                                 _atoi_env("JLM_WORDLIST_MFMA", 1))
+
+    @staticmethod
+    def jlm_wordlist_merge_form(segs, n_segs, split_seg, ldt, beam, max_words):
+        """ABI 12: the kernel the incremental decoder's back-fill launches"""
+        sp = _split_arg(split_seg)
+        if sp is not None and n_segs == 1 and beam <= 64 and max_words <= 128 and _wl_split_hosts(sp, ldt):
+            return WL_FORM["MERGE_SPLIT"]
+        return FakeLib.jlm_wordlist_lse_form(segs, n_segs, split_seg, 0, ldt, beam, max_words)
+
     @staticmethod
     def jlm_vocab_lse_mixed_form(segs, descale, s8, has_bias2, n_segs, fixed_ref):
         """ABI 12: the kernel jlm_vocab_lse_mixed(_fr) launches; JLM_MX_WIDE / JLM_MX6_WIDE as the library reads them"""
@@ -260,29 +323,26 @@ class FakeLib:
         dynamic, select, full = p.kind == 2, p.kind == 1, p.kind == 0
         mode = 1 if m.self_norm else (2 if dynamic else 0)
         split = bool(m.split_segs)
-        wl_split = split and m.n_segs == 1 and beam <= 64
         tile_form = full and not m.self_norm and any(m.segs[i].k > 256 for i in range(m.n_segs))
         off = lambda base, n: (base or 0) + 4 * n
 
         def wl_lse(g0, cidx, words, woff, idx, base, merge, n_groups, max_words):
-            if wl_split and 128 <= max_words <= 4064:
-                r = self.jlm_wordlist_lse_split(m.split_segs, m.split_t_scale[0], m.split_descale[0], m.b2, p.T, m.ldt, g0,
-                                                st.cnt, cidx, words, woff, idx, base, max_words, p.run_max, p.run_sum,
-                                                st.lse, merge, beam, n_groups, stream)
-                if r != -2:
-                    return r
+            if self.jlm_wordlist_lse_form(m.segs, m.n_segs, m.split_segs if split else None, 0, m.ldt, beam, max_words) == WL_FORM["SPLIT"]:
+                return self.jlm_wordlist_lse_split(m.split_segs, m.split_t_scale[0], m.split_descale[0], m.b2, p.T, m.ldt, g0,
+                                                   st.cnt, cidx, words, woff, idx, base, max_words, p.run_max, p.run_sum,
+                                                   st.lse, merge, beam, n_groups, stream)
             return self.jlm_wordlist_lse(m.segs, m.n_segs, m.b2, p.T, m.ldt, g0, st.cnt, cidx, words, woff, idx, base,
                                          p.run_max, p.run_sum, st.lse, merge, beam, n_groups, stream)
 
         pending = 0
         for f in range(F):
             if dynamic and not m.self_norm and f >= 2:
-                r = -2
-                if wl_split and p.dd_max <= 128:
+                if self.jlm_wordlist_merge_form(m.segs, m.n_segs, m.split_segs if split else None, m.ldt, beam,
+                                                p.dd_max) == WL_FORM["MERGE_SPLIT"]:
                     r = self.jlm_wordlist_merge_split(m.split_segs, m.split_t_scale[0], m.split_descale[0], m.b2, p.T, m.ldt,
                                                       st.cnt, B, beam, f - 1, p.dd_words, p.dd_off, f * B, p.dd_max,
                                                       p.run_max, p.run_sum, st.lse, stream)
-                if r == -2:
+                else:
                     r = wl_lse(p.g0, p.cidx, p.dd_words, p.dd_off, p.sidx, f * B, 1, (f - 1) * B, p.dd_max)
                 if r:
                     return r
@@ -1029,7 +1089,7 @@ class FakeLib:
                                max_words, run_max, run_sum, lse, merge, beam, n_groups, stream):
         """jlm_wordlist_lse for one segment whose matrix is given as split rows"""
         sg = seg._obj if hasattr(seg, "_obj") else (seg[0] if not hasattr(seg, "k") else seg)
-        if sg.k > 256 or sg.ldb % 16 or beam > 64 or max_words > 4096 - 32:
+        if wordlist_lse_form([_seg_tuple(sg)], _seg_tuple(sg), 0, ldt, beam, max(max_words, 128)) != WL_FORM["SPLIT"]:
             return -2
         nv = sg.v_end - sg.v_start
         Bfull = self._split_read(sg.B, nv, sg.ldb)[:, :sg.k]
@@ -1063,7 +1123,7 @@ class FakeLib:
                                  wl_base, max_words, run_max, run_sum, lse, stream):
         """every older row of every sentence merges the sentence's new words (jlm_wordlist_lse merge=1 per cell)"""
         sg = seg._obj if hasattr(seg, "_obj") else (seg[0] if not hasattr(seg, "k") else seg)
-        if sg.k > 256 or sg.ldb % 16 or beam > 64 or max_words > 128:
+        if wordlist_merge_form([_seg_tuple(sg)], _seg_tuple(sg), ldt, beam, max_words) != WL_FORM["MERGE_SPLIT"]:
             return -2
         nv = sg.v_end - sg.v_start
         Bfull = self._split_read(sg.B, nv, sg.ldb)[:, :sg.k]

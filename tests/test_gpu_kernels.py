@@ -190,6 +190,17 @@ def test_vocab_lse_forced_forms(setting, tmp_path):
     check_forced_child(setting, tmp_path)
 
 
+def test_wordlist_forced_forms(tmp_path):
+    """JLM_WORDLIST_MFMA=0: the single-segment word-list normaliser on the f32 kernel instead of the matrix pipe.  A child -- the
+    variable is read once per process -- runs test_gpu_wordlist_forms.py, test_wordlist_lse and the vocabulary-selection / incremental
+    decodes of test_gpu_decode.py; every case the matrix pipe would have served must have run and reported JLM_WL_F32."""
+    import os
+    if os.environ.get("JLM_WL_FORMS_OUT"):
+        pytest.skip("inside a child")
+    from tests.test_gpu_wordlist_forms import check_forced_child
+    check_forced_child(tmp_path)
+
+
 @pytest.mark.parametrize("H,R,use_rows", [(64, 10, False), (64, 200, True), (512, 700, True), (512, 2560, True), (128, 161, True),
                                          (512, 159, False),
                                          # the W-stationary persistent kernel (H = 512 with a row list): one tile per workgroup at 2 560 rows; two
