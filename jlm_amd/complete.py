@@ -25,11 +25,11 @@ import time
 
 import numpy as np
 
-from . import _lib
 from . import config as _config
 from . import generate as _gen
 from . import ops as _ops
-from .score import check_ids
+from . import rowsets
+from .rowsets import check_ids, is_int
 
 MAX_BEAM = 64                        # JLM_TOPK_MAX: one lane per rank in the merge, one selection round per rank in the row kernel
 MAX_ROWS = _gen.MAX_ROWS
@@ -37,40 +37,28 @@ COMPLETE_BUDGET_BYTES = _gen.GENERATE_BUDGET_BYTES
 EOS_ID = _gen.EOS_ID
 
 
-def _is_int(x):
-    return not isinstance(x, bool) and isinstance(x, (int, np.integer))
-
-
 def check_args(prompts, n_words, beam_width, n_best, stop_id, V):
     """ValueError for anything the kernels cannot take, before any launch.  -> (prompts as int64 arrays, n_best)"""
-    if not _is_int(n_words) or n_words < 1:
+    if not is_int(n_words) or n_words < 1:
         raise ValueError("n_words must be an integer >= 1 (got %r)" % (n_words,))
-    if not _is_int(beam_width) or not 1 <= beam_width <= min(MAX_BEAM, V):
+    if not is_int(beam_width) or not 1 <= beam_width <= min(MAX_BEAM, V):
         raise ValueError("beam_width must be an integer in [1, %d] (got %r)" % (min(MAX_BEAM, V), beam_width))
     if n_best is None:
         n_best = int(beam_width)
-    if not _is_int(n_best) or not 1 <= n_best <= beam_width:
+    if not is_int(n_best) or not 1 <= n_best <= beam_width:
         raise ValueError("n_best must be an integer in [1, beam_width = %d] (got %r)" % (beam_width, n_best))
-    out = []
-    for i, p in enumerate(prompts):
-        a = np.asarray(p, dtype=np.int64).ravel()
-        if a.size == 0:
-            raise ValueError("prompt %d is empty (a prompt needs at least one word; the reference starts at <eos>)" % i)
-        check_ids(a, V, "complete (prompt %d)" % i)
-        out.append(a)
+    out = rowsets.check_prompts(prompts, V, "complete", "a prompt needs at least one word")
     if stop_id is not None:
-        if not _is_int(stop_id):
+        if not is_int(stop_id):
             raise ValueError("stop_id must be an integer word id (got %r)" % (stop_id,))
         check_ids([stop_id], V, "complete (stop_id)")
     return out, int(n_best)
 
 
 def plan_prompts(lengths, beam_width, max_rows):
-    """Prompts sorted by length, longest first (stable), cut into chunks of at most max(1, max_rows // beam_width) prompts: a prompt's
-    rows never split across calls.  -> generate.plan_rows' chunks (idx = the caller's prompt of each chunk prompt)."""
-    if max_rows < 1:
-        raise ValueError("max_rows must be >= 1")
-    return _gen.plan_rows(lengths, max(1, int(max_rows) // int(beam_width)))
+    """generate's row plan (rowsets.plan_prompts) cut into chunks of at most max(1, max_rows // beam_width) prompts: a prompt's rows
+    never split across calls.  (idx = the caller's prompt of each chunk prompt.)"""
+    return rowsets.plan_prompts(lengths, max_rows, beam_width)
 
 
 # ------------------------------------------------------------------------------------------------- numpy restatements (the tests')
@@ -147,40 +135,26 @@ class Completer:
         self.torch = dev_model.torch
         self.last_frame_ms = None         # [frames, 5] of the last timed call: LSTM step, T projection, logit GEMMs, selection, merge
 
-    @property
-    def ld_logits(self):
-        return (self.m.V + 3) // 4 * 4
-
     def row_bytes(self, n_prompt, n_words, beam):
         m = self.m
-        return (self.ld_logits + 4 * m.H + m.ldt) * 4 + beam * 12 + n_words * 16 + n_prompt * 8 + 48
+        return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + beam * 12 + n_words * 16 + n_prompt * 8 + 48
 
-    def max_rows(self, n_prompt, n_words, beam):
-        """rows (prompts x beam) per call: MAX_ROWS, fewer when the call's buffers would exceed COMPLETE_BUDGET_BYTES"""
-        k = COMPLETE_BUDGET_BYTES // self.row_bytes(n_prompt, n_words, beam)
-        return int(max(1, min(MAX_ROWS, k, (0x7ffffff0 // max(self.m.H // 4, 1)) - 1)))
-
-    def run(self, prompts, n_words, beam, stop_id=None, timed=False):
-        """One call over prompts already sorted by length (longest first).  -> (bp_parent, bp_word [n_words, R] int32, bp_nll
-        [n_words, R] float64, score [R] float64), R = len(prompts) * beam, rank i of prompt p at row p * beam + i."""
+    def run(self, prompts, n_words, beam, stop_id=None, timed=False, n_live=None):
+        """One call over prompts already sorted by length (longest first).  n_live: the chunk's live counts from plan_prompts (None:
+        rowsets.live_counts of the prompts).  -> (bp_parent, bp_word [n_words, R] int32, bp_nll [n_words, R] float64, score [R]
+        float64), R = len(prompts) * beam, rank i of prompt p at row p * beam + i."""
         torch, m = self.torch, self.m
-        NP, B = len(prompts), int(beam)
+        if n_live is None:
+            n_live = rowsets.live_counts([len(p) for p in prompts])
+        NP, B, P = len(prompts), int(beam), len(n_live)
         R = NP * B
-        P = len(prompts[0])
-        prompt, prev = _gen.prompt_arrays(prompts, P)
-        n_live = (np.array([len(p) for p in prompts])[None, :] >= P - np.arange(P)[:, None]).sum(axis=1).astype(np.int32)
-        dev, f32, i32, f64 = m.device, torch.float32, torch.int32, torch.float64
+        prompt, prev = rowsets.prompt_arrays(prompts, P)
+        dev, i32, f64 = m.device, torch.int32, torch.float64
         with m._ctx():
-            e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
-            hs = [e((R, m.H), f32), e((R, m.H), f32)]
-            cs = [e((R, m.H), f32), e((R, m.H), f32)]
-            untied_f32 = m.mode == "untied" and not m.split_lstm
-            T = None if untied_f32 else e((R, m.ldt), f32)
-            logits = e((R, self.ld_logits), f32)
+            rs = rowsets.RowSets(m, R, logits=True)
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-            rows = torch.arange(R, device=dev, dtype=i32)
-            cand_ids = e((R, B), i32)
-            cand_nll = e((R, B), f64)
+            cand_ids = torch.empty((R, B), device=dev, dtype=i32)
+            cand_nll = torch.empty((R, B), device=dev, dtype=f64)
             word = torch.zeros(R, device=dev, dtype=i32)
             prev_row = torch.zeros(R, device=dev, dtype=i32)
             score = torch.zeros(R, device=dev, dtype=f64)
@@ -188,18 +162,14 @@ class Completer:
             bp_parent = torch.zeros((n_words, R), device=dev, dtype=i32)
             bp_word = torch.full((n_words, R), -1, device=dev, dtype=i32)
             bp_nll = torch.zeros((n_words, R), device=dev, dtype=f64)
-            flags = torch.zeros(1, device=dev, dtype=i32)
-            ms = _ops.backend().complete_frames(m.decode_model(), hs[0], cs[0], hs[1], cs[1], T, logits, self.ld_logits, rows, up(prev),
-                                                up(prompt), up(n_live), [int(x) for x in n_live], cand_ids, cand_nll, word, prev_row,
-                                                score, finished, -1 if stop_id is None else int(stop_id), bp_parent, bp_word, bp_nll,
-                                                flags, NP, B, P, int(n_words), bool(timed))
+            ms = _ops.backend().complete_frames(m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, up(prev), up(prompt),
+                                                up(n_live), [int(x) for x in n_live], cand_ids, cand_nll, word, prev_row, score,
+                                                finished, -1 if stop_id is None else int(stop_id), bp_parent, bp_word, bp_nll, rs.flags,
+                                                NP, B, P, int(n_words), bool(timed))
             if timed:
                 self.last_frame_ms = ms.numpy()
-            fl = int(flags.cpu()[0])
-            out = (bp_parent.cpu().numpy(), bp_word.cpu().numpy(), bp_nll.cpu().numpy(), score.cpu().numpy())
-        if fl:
-            raise _lib.JlmHipError("topk_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)" % fl)
-        return out
+            rs.check_flags("topk_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)")
+            return bp_parent.cpu().numpy(), bp_word.cpu().numpy(), bp_nll.cpu().numpy(), score.cpu().numpy()
 
 
 def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None):
@@ -210,10 +180,10 @@ def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, m
         return out
     lens = [len(p) for p in prompts]
     if max_rows is None:
-        max_rows = comp.max_rows(max(lens), n_words, beam_width)
+        max_rows = rowsets.clamp_rows(MAX_ROWS, COMPLETE_BUDGET_BYTES, comp.row_bytes(max(lens), n_words, beam_width), comp.m.H)
     for ch in plan_prompts(lens, beam_width, max_rows):
         idx = ch["idx"]
-        bp_parent, bp_word, bp_nll, score = comp.run([prompts[i] for i in idx], int(n_words), int(beam_width), stop_id)
+        bp_parent, bp_word, bp_nll, score = comp.run([prompts[i] for i in idx], int(n_words), int(beam_width), stop_id, n_live=ch["n_live"])
         for j, i in enumerate(idx):
             out[i] = backtrace(bp_parent, bp_word, bp_nll, score, j, int(beam_width), n_best, stop_id)
     return out
@@ -226,12 +196,10 @@ def predict_top(comp, contexts, n=10, max_rows=None):
 
 
 def main(argv=None):
-    from .data import CharVocab, Vocab
+    from .data import CharVocab, load_vocab
     ap = argparse.ArgumentParser(description="Predict next words or complete phrases by beam search on the device "
                                              "(reference decoder/model.py:25-26 find_top_N)")
-    ap.add_argument("--root", default=None, help="JLM root (data/, train/experiments/); default $JLM_ROOT")
-    ap.add_argument("-e", "--experiment_id", type=int, default=0)
-    ap.add_argument("--comp", type=int, default=0, help="compressed weights (lstm_weights_comp_<comp>.pkl)")
+    _config.add_model_args(ap)
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--prompt", default=None, help='words to continue, "w/r w/r ..." (default: start at <eos>)')
     src.add_argument("--file", default=None, help="one prompt per line")
@@ -241,11 +209,8 @@ def main(argv=None):
     ap.add_argument("--top", type=int, default=None, metavar="N", help="next-word mode: the N most probable next words")
     ap.add_argument("--stop-at-eos", action="store_true", help="end a completion after <eos>")
     args = ap.parse_args(argv)
-    if args.root:
-        _config.set_root(args.root)
+    _cfg, vocab = load_vocab(args)
     from .model import LSTM_Model
-    config = _config.load_config_dict(args.experiment_id)
-    vocab = (CharVocab if config.get("char_rnn") else Vocab)(config["vocab_size"])
     if args.file:
         with open(args.file, encoding="utf-8") as f:
             texts = [l.rstrip("\n") for l in f if l.strip()]

@@ -32,6 +32,13 @@ def set_root(path):
     return root_path
 
 
+def add_model_args(ap):
+    """the flags that pick a dumped model, shared by the command-line tools (argparse ``ap``); data.load_vocab reads them"""
+    ap.add_argument("--root", default=None, help="JLM root (data/, train/experiments/); default $JLM_ROOT")
+    ap.add_argument("-e", "--experiment_id", type=int, default=0)
+    ap.add_argument("--comp", type=int, default=0, help="compressed weights (lstm_weights_comp_<comp>.pkl)")
+
+
 class ExperimentConfig:
     """Attribute view over a config.json dict (reference config.py:21-26)."""
 

@@ -369,48 +369,79 @@ static int rows_logits(const jlm_decode_model *m, const float *T, float *logits,
     return 0;
 }
 
+// The frame loops over row sets.  An untied f32 model's T is the state row set the step wrote; every other model has its own T rows
+// (an untied split-row model: the f32 copy the step writes beside the split rows).
+static bool t_is_state(const jlm_decode_model *m) { return m->untied && !m->split_lstm; }
+
+// -2: a split-row model without wt8 / xgate8 (DeviceModel builds them together); -1: no T rows where T is not the state
+static int rows_refuse(const jlm_decode_model *m, const float *T) { return m->split_lstm && !m->wt8 ? -2 : !T && !t_is_state(m) ? -1 : 0; }
+
+// event i of frame f, per_frame events a frame (none when the call is untimed: events NULL)
+struct Stamps {
+    void *const *events;
+    int per_frame;
+    void *stream;
+    int operator()(int f, int i) const {
+        return events ? (int)hipEventRecord((hipEvent_t)events[(size_t)f * per_frame + i], (hipStream_t)stream) : 0;
+    }
+};
+
+// frame f reads state set f % 2 and writes the other; T: where the T projection writes (the written set when t_is_state)
+struct PingPong {
+    void *h_in, *h_out;
+    float *c_in, *c_out, *T;
+    PingPong(const jlm_decode_model *m, void *const h[2], float *const c[2], float *T_rows, int f)
+        : h_in(h[f & 1]), h_out(h[(f + 1) & 1]), c_in(c[f & 1]), c_out(c[(f + 1) & 1]), T(t_is_state(m) ? (float *)h_out : T_rows) {}
+};
+
+// Stamp 0, the LSTM step and stamp 1 of frame f of jlm_generate_frames / jlm_complete_frames.  A prompt frame (f < n_prompt) steps
+// the live prefix n_live_host[f] of the right-aligned prompts, from row f of prompt / prev (stride: the rows of a prompt frame --
+// n_rows in generate, n_prompts in complete); every later frame steps all n_rows rows from word / prev_rows.
+template <class Plan>
+static int frame_lstm_step(const jlm_decode_model *m, const Plan *p, const PingPong &s, const Stamps &stamp, int f, int stride,
+                           const int *prev_rows, int n_rows, void *stream) {
+    const bool in_prompt = f < p->n_prompt;
+    const int bound = in_prompt ? p->n_live_host[f] : n_rows;
+    if (bound < 0 || (in_prompt && bound > stride)) return -1;
+    JLM_TRY(stamp(f, 0));
+    if (bound > 0)
+        JLM_TRY(rows_lstm_step(m, s.h_in, s.c_in, s.h_out, s.c_out, p->rows, in_prompt ? p->prev + (size_t)f * stride : prev_rows,
+                               in_prompt ? p->prompt + (size_t)f * stride : p->word, p->T, bound, in_prompt ? p->n_live + f : nullptr,
+                               stream));
+    return stamp(f, 1);
+}
+
 // Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),
 // T, the full-vocabulary normaliser as the frame loop launches it for kind 0, and the fold into -log p of the target word.
 extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
     const int R = p->n_rows, S = p->n_steps;
     if (R < 0 || S < 0 || !p->rows || !p->prev0 || !p->word || !p->target || !p->n_live || !p->nll_seq) return -1;
     if (R == 0 || S == 0) return 0;
-    if (m->split_lstm && !m->wt8) return -2;        // (a split-row model always carries wt8 / xgate8: DeviceModel builds them together)
+    JLM_TRY(rows_refuse(m, p->T));
     if (!m->self_norm && (!p->part || p->max_parts < 1)) return -1;
-    // an untied f32 model's T is the state row set the step wrote; every other model has its own T rows (untied split-row models:
-    // the f32 copy the step writes beside the split rows)
-    const bool t_is_h = m->untied && !m->split_lstm;
-    if (!t_is_h && !p->T) return -1;
-    hipStream_t main_s = (hipStream_t)stream;
-    auto stamp = [&](int t, int i) -> int {
-        if (!events) return 0;
-        return (int)hipEventRecord((hipEvent_t)events[(size_t)t * JLM_SCORE_EVENTS_PER_STEP + i], main_s);
-    };
+    const Stamps stamp{events, JLM_SCORE_EVENTS_PER_STEP, stream};
     for (int t = 0; t < S; ++t) {
         const int bound = p->n_live_host ? p->n_live_host[t] : R;
         if (bound < 0 || bound > R) return -1;
         const int *ndev = p->n_live + t;
         const int *word = p->word + (size_t)t * R, *target = p->target + (size_t)t * R;
-        // ping-pong: step t reads set t % 2 and writes the other (word[] and prev[] are indexed by the row: g = rows[r] = r)
-        void *h_in = p->h[t & 1], *h_out = p->h[(t + 1) & 1];
-        float *c_in = p->c[t & 1], *c_out = p->c[(t + 1) & 1];
+        const PingPong s(m, p->h, p->c, p->T, t);         // (word[] and prev[] are indexed by the row: g = rows[r] = r)
         const int *prev = t == 0 ? p->prev0 : p->rows;
-        float *T = t_is_h ? (float *)h_out : p->T;
         JLM_TRY(stamp(t, 0));
-        if (bound > 0) JLM_TRY(rows_lstm_step(m, h_in, c_in, h_out, c_out, p->rows, prev, word, p->T, bound, ndev, stream));
+        if (bound > 0) JLM_TRY(rows_lstm_step(m, s.h_in, s.c_in, s.h_out, s.c_out, p->rows, prev, word, p->T, bound, ndev, stream));
         JLM_TRY(stamp(t, 1));
-        if (bound > 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, bound, ndev, stream));
+        if (bound > 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, bound, ndev, stream));
         JLM_TRY(stamp(t, 2));
         int n_parts = 0;
         if (bound > 0 && !m->self_norm) {
             FullLse fl;
-            JLM_TRY(full_lse_pack(m, T, p->rows, bound, ndev, p->Tm, p->ld_tm, false, fl, stream));
-            JLM_TRY(full_lse_run(m, fl, T, h_out, p->Tm, p->ld_tm, p->rows, R, bound, bound, ndev, p->part, p->max_parts, 0, &n_parts,
+            JLM_TRY(full_lse_pack(m, s.T, p->rows, bound, ndev, p->Tm, p->ld_tm, false, fl, stream));
+            JLM_TRY(full_lse_run(m, fl, s.T, s.h_out, p->Tm, p->ld_tm, p->rows, R, bound, bound, ndev, p->part, p->max_parts, 0, &n_parts,
                                  stream));
         }
         JLM_TRY(stamp(t, 3));
         if (bound > 0)
-            JLM_TRY(jlm_score_fold(m->segs, m->n_segs, m->b2, T, m->ldt, p->part, R, n_parts, m->self_norm, target, ndev, bound,
+            JLM_TRY(jlm_score_fold(m->segs, m->n_segs, m->b2, s.T, m->ldt, p->part, R, n_parts, m->self_norm, target, ndev, bound,
                                    p->nll_seq, p->nll_tok ? p->nll_tok + (size_t)t * R : nullptr, p->flags, stream));
         JLM_TRY(stamp(t, 4));
     }
@@ -426,35 +457,19 @@ extern "C" int jlm_generate_frames(const jlm_decode_model *m, const jlm_generate
         !p->logits)
         return -1;
     if (R == 0 || N == 0) return 0;
-    if (m->split_lstm && !m->wt8) return -2;
+    JLM_TRY(rows_refuse(m, p->T));
     const int V = m->segs[m->n_segs - 1].v_end;
     if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
     if (p->n_live_host[P - 1] != R) return -1;                  // every row is live at the last prompt frame (right-aligned prompts)
-    const bool t_is_h = m->untied && !m->split_lstm;
-    if (!t_is_h && !p->T) return -1;
-    hipStream_t main_s = (hipStream_t)stream;
-    auto stamp = [&](int f, int i) -> int {
-        if (!events) return 0;
-        return (int)hipEventRecord((hipEvent_t)events[(size_t)f * JLM_GENERATE_EVENTS_PER_FRAME + i], main_s);
-    };
+    const Stamps stamp{events, JLM_GENERATE_EVENTS_PER_FRAME, stream};
     const int F = P + N - 1;
     for (int f = 0; f < F; ++f) {
-        const bool prompt = f < P;
-        const int bound = prompt ? p->n_live_host[f] : R;
-        if (bound < 0 || bound > R) return -1;
-        const int *ndev = prompt ? p->n_live + f : nullptr;
-        const int *word = prompt ? p->prompt + (size_t)f * R : p->word;
-        const int *prev = prompt ? p->prev + (size_t)f * R : p->rows;
-        void *h_in = p->h[f & 1], *h_out = p->h[(f + 1) & 1];
-        float *c_in = p->c[f & 1], *c_out = p->c[(f + 1) & 1];
-        float *T = t_is_h ? (float *)h_out : p->T;
-        JLM_TRY(stamp(f, 0));
-        if (bound > 0) JLM_TRY(rows_lstm_step(m, h_in, c_in, h_out, c_out, p->rows, prev, word, p->T, bound, ndev, stream));
-        JLM_TRY(stamp(f, 1));
+        const PingPong s(m, p->h, p->c, p->T, f);
+        JLM_TRY(frame_lstm_step(m, p, s, stamp, f, R, p->rows, R, stream));
         const int k = f - (P - 1);                                   // the draw of this frame, if any
-        if (k >= 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, R, nullptr, stream));
+        if (k >= 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, R, nullptr, stream));
         JLM_TRY(stamp(f, 2));
-        if (k >= 0) JLM_TRY(rows_logits(m, T, p->logits, p->ld_logits, R, stream));
+        if (k >= 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, R, stream));
         JLM_TRY(stamp(f, 3));
         if (k >= 0)
             JLM_TRY(jlm_sample_rows(p->logits, p->ld_logits, V, R, nullptr, p->temperature, p->seed, k, p->row_id, nullptr, p->done,
@@ -475,38 +490,22 @@ extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete
         !p->bp_word || !p->bp_nll)
         return -1;
     if (NP == 0 || N == 0) return 0;
-    if (m->split_lstm && !m->wt8) return -2;
+    JLM_TRY(rows_refuse(m, p->T));
     const int V = m->segs[m->n_segs - 1].v_end;
     if (B > V || (long long)NP * B > 0x7fffffff) return -1;
     const int R = NP * B;
     if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
     if (p->n_live_host[P - 1] != NP) return -1;                 // every prompt is live at the last prompt frame (right-aligned)
-    const bool t_is_h = m->untied && !m->split_lstm;
-    if (!t_is_h && !p->T) return -1;
-    hipStream_t main_s = (hipStream_t)stream;
-    auto stamp = [&](int f, int i) -> int {
-        if (!events) return 0;
-        return (int)hipEventRecord((hipEvent_t)events[(size_t)f * JLM_COMPLETE_EVENTS_PER_FRAME + i], main_s);
-    };
+    const Stamps stamp{events, JLM_COMPLETE_EVENTS_PER_FRAME, stream};
     const int F = P + N - 1;
     for (int f = 0; f < F; ++f) {
-        const bool prompt = f < P;
-        const int bound = prompt ? p->n_live_host[f] : R;
-        if (bound < 0 || (prompt && bound > NP)) return -1;
-        const int *ndev = prompt ? p->n_live + f : nullptr;
-        const int *word = prompt ? p->prompt + (size_t)f * NP : p->word;
-        const int *prev = prompt ? p->prev + (size_t)f * NP : p->prev_row;
-        void *h_in = p->h[f & 1], *h_out = p->h[(f + 1) & 1];
-        float *c_in = p->c[f & 1], *c_out = p->c[(f + 1) & 1];
-        float *T = t_is_h ? (float *)h_out : p->T;
-        JLM_TRY(stamp(f, 0));
-        if (bound > 0) JLM_TRY(rows_lstm_step(m, h_in, c_in, h_out, c_out, p->rows, prev, word, p->T, bound, ndev, stream));
-        JLM_TRY(stamp(f, 1));
+        const PingPong s(m, p->h, p->c, p->T, f);
+        JLM_TRY(frame_lstm_step(m, p, s, stamp, f, NP, p->prev_row, R, stream));
         const int k = f - (P - 1);                                   // the selecting frame, if any
         const int n_sel = k == 0 ? NP : R;
-        if (k >= 0) JLM_TRY(rows_t_projection(m, h_out, p->rows, T, n_sel, nullptr, stream));
+        if (k >= 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, n_sel, nullptr, stream));
         JLM_TRY(stamp(f, 2));
-        if (k >= 0) JLM_TRY(rows_logits(m, T, p->logits, p->ld_logits, n_sel, stream));
+        if (k >= 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, n_sel, stream));
         JLM_TRY(stamp(f, 3));
         if (k >= 0)
             JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, n_sel, B, m->self_norm, p->cand_ids, p->cand_nll, B, p->flags, stream));

@@ -461,6 +461,55 @@ int64_t lse_probe(const c10::intrusive_ptr<JlmModel> &model, const Tensor &rowli
     return rc;
 }
 
+// The checks the row-set frame ops share (score_frames, generate_frames, complete_frames): n_live_host holds n_counts live-row
+// counts, one per `unit`, each in [0, max_live]; h0 / c0 and h1 / c1 are the two ping-pong state row sets of n_rows rows of H 4-byte
+// values (c: float32).
+void check_row_sets(const char *op, const jlm_decode_model &m, int64_t n_rows, const Tensor &h0, const Tensor &c0, const Tensor &h1,
+                    const Tensor &c1, const std::vector<int64_t> &n_live_host, int64_t n_counts, const char *unit, int64_t max_live) {
+    const int64_t R = n_rows;
+    auto is_f32 = [](const Tensor &t, int64_t n) { return t.defined() && t.scalar_type() == at::kFloat && t.numel() >= n; };
+    TORCH_CHECK(R >= 0 && n_counts >= 0 && (int64_t)n_live_host.size() == n_counts, "jlm.", op, ": n_live_host holds one count per ", unit);
+    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= max_live, "jlm.", op, ": a live-row count outside [0, ", max_live, "]");
+    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
+                    is_f32(c0, R * m.H) && is_f32(c1, R * m.H),
+                "jlm.", op, ": state row sets [", R, ", H] of 4-byte values");
+}
+
+// Enqueue one frame op, launch(stream, events), on the current stream of device `dev` under the enqueue lock.  Timed: with
+// n_frames x per_frame events, and -> [n_frames, per_frame - 1] milliseconds between each frame's consecutive events after waiting
+// for the last.  Untimed, or with no frame recorded (n_frames = 0): an empty tensor, and nothing waits.
+template <class Launch>
+Tensor launch_frames(const char *what, int dev, bool timed, int64_t n_frames, int per_frame, Launch launch) {
+    const c10::hip::HIPGuard device_guard(dev);
+    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
+    std::vector<hipEvent_t> ev;
+    struct Destroy {
+        std::vector<hipEvent_t> &ev;
+        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    } destroy{ev};
+    if (timed)
+        for (int64_t i = 0; i < n_frames * per_frame; ++i) {
+            hipEvent_t e;
+            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
+            ev.push_back(e);
+        }
+    {
+        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
+        jlm_check(launch(st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), what);
+    }
+    if (!timed || n_frames == 0) return at::empty({0}, at::kDouble);
+    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
+    Tensor out = at::zeros({n_frames, per_frame - 1}, at::kDouble);
+    auto a = out.accessor<double, 2>();
+    for (int64_t f = 0; f < n_frames; ++f)
+        for (int i = 0; i + 1 < per_frame; ++i) {
+            float ms = 0.0f;
+            jlm_check((int)hipEventElapsedTime(&ms, ev[f * per_frame + i], ev[f * per_frame + i + 1]), "hipEventElapsedTime");
+            a[f][i] = ms;
+        }
+    return out;
+}
+
 // teacher-forced scoring of n_rows sequences / streams over n_steps steps (jlm_score_frames, include/jlm_hip.h): state row sets h0/c0
 // (read by step 0) and h1/c1, ping-pong; T / Tm / part as the model's normaliser needs them; word / target [n_steps][n_rows] int32;
 // n_live [n_steps] int32 on the device and its host copy; nll_seq [n_rows] f64 (accumulated), nll_tok [n_steps][n_rows] f64 (optional),
@@ -475,11 +524,7 @@ Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0,
     const int64_t R = n_rows, S = n_steps;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
     auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    TORCH_CHECK(R >= 0 && S >= 0 && (int64_t)n_live_host.size() == S, "jlm.score_frames: n_live_host holds one count per step");
-    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= R, "jlm.score_frames: a live-row count outside [0, n_rows]");
-    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
-                    is(c0, at::kFloat, R * m.H) && is(c1, at::kFloat, R * m.H),
-                "jlm.score_frames: state row sets [n_rows, H] of 4-byte values");
+    check_row_sets("score_frames", m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
     TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
                     is(n_live, at::kInt, S),
                 "jlm.score_frames: int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
@@ -499,36 +544,8 @@ Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0,
     std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
     p.n_live_host = live_host.data();
     p.nll_seq = ptr<double>(nll_seq, "nll_seq"); p.nll_tok = optr<double>(nll_tok, "nll_tok"); p.flags = optr<int>(flags, "flags");
-    const int dev = h0.device().index();
-    const c10::hip::HIPGuard device_guard(dev);
-    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
-    std::vector<hipEvent_t> ev;
-    struct Destroy {
-        std::vector<hipEvent_t> &ev;
-        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } destroy{ev};
-    if (timed)
-        for (int64_t i = 0; i < S * JLM_SCORE_EVENTS_PER_STEP; ++i) {
-            hipEvent_t e;
-            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
-            ev.push_back(e);
-        }
-    {
-        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
-        jlm_check(jlm_score_frames(&m, &p, st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), "jlm_score_frames");
-    }
-    if (!timed || S == 0) return at::empty({0}, at::kDouble);
-    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
-    Tensor out = at::zeros({S, JLM_SCORE_EVENTS_PER_STEP - 1}, at::kDouble);
-    auto a = out.accessor<double, 2>();
-    for (int64_t t = 0; t < S; ++t)
-        for (int i = 0; i + 1 < JLM_SCORE_EVENTS_PER_STEP; ++i) {
-            float ms = 0.0f;
-            jlm_check((int)hipEventElapsedTime(&ms, ev[t * JLM_SCORE_EVENTS_PER_STEP + i], ev[t * JLM_SCORE_EVENTS_PER_STEP + i + 1]),
-                      "hipEventElapsedTime");
-            a[t][i] = ms;
-        }
-    return out;
+    return launch_frames("jlm_score_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_score_frames(&m, &p, st, ev); });
 }
 
 // one draw per row of f32 logits y [n_rows, ld] (jlm_sample_rows, include/jlm_hip.h).  seed: the uint64 seed's bits as int64.
@@ -564,11 +581,8 @@ Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     const int64_t R = n_rows, P = n_prompt, N = n_words;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
     auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    TORCH_CHECK(R >= 0 && P >= 1 && N >= 0 && (int64_t)n_live_host.size() == P, "jlm.generate_frames: n_live_host holds one count per prompt frame");
-    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= R, "jlm.generate_frames: a live-row count outside [0, n_rows]");
-    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
-                    is(c0, at::kFloat, R * m.H) && is(c1, at::kFloat, R * m.H),
-                "jlm.generate_frames: state row sets [n_rows, H] of 4-byte values");
+    TORCH_CHECK(P >= 1 && N >= 0, "jlm.generate_frames: n_prompt >= 1 and n_words >= 0");
+    check_row_sets("generate_frames", m, R, h0, c0, h1, c1, n_live_host, P, "prompt frame", R);
     TORCH_CHECK(is(rows, at::kInt, R) && is(row_id, at::kInt, R) && is(word, at::kInt, R) && (!has(done) || is(*done, at::kInt, R)) &&
                     is(prev, at::kInt, P * R) && is(prompt, at::kInt, P * R) && is(n_live, at::kInt, P),
                 "jlm.generate_frames: int32 rows / row_id / word / done [n_rows], prev / prompt [n_prompt][n_rows], n_live [n_prompt]");
@@ -588,37 +602,8 @@ Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     p.row_id = ptr<const int>(row_id, "row_id"); p.word = ptr<int>(word, "word"); p.done = optr<int>(done, "done");
     p.stop_id = (int)stop_id; p.temperature = temperature; p.seed = (uint64_t)seed;
     p.ids = ptr<int>(ids, "ids"); p.nll = ptr<double>(nll, "nll"); p.flags = optr<int>(flags, "flags");
-    const int dev = h0.device().index();
-    const c10::hip::HIPGuard device_guard(dev);
-    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
-    const int64_t F = N > 0 ? P + N - 1 : 0;
-    std::vector<hipEvent_t> ev;
-    struct Destroy {
-        std::vector<hipEvent_t> &ev;
-        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } destroy{ev};
-    if (timed)
-        for (int64_t i = 0; i < F * JLM_GENERATE_EVENTS_PER_FRAME; ++i) {
-            hipEvent_t e;
-            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
-            ev.push_back(e);
-        }
-    {
-        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
-        jlm_check(jlm_generate_frames(&m, &p, st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), "jlm_generate_frames");
-    }
-    if (!timed || F == 0 || R == 0) return at::empty({0}, at::kDouble);
-    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
-    Tensor out = at::zeros({F, JLM_GENERATE_EVENTS_PER_FRAME - 1}, at::kDouble);
-    auto a = out.accessor<double, 2>();
-    for (int64_t f = 0; f < F; ++f)
-        for (int i = 0; i + 1 < JLM_GENERATE_EVENTS_PER_FRAME; ++i) {
-            float ms = 0.0f;
-            jlm_check((int)hipEventElapsedTime(&ms, ev[f * JLM_GENERATE_EVENTS_PER_FRAME + i], ev[f * JLM_GENERATE_EVENTS_PER_FRAME + i + 1]),
-                      "hipEventElapsedTime");
-            a[f][i] = ms;
-        }
-    return out;
+    return launch_frames("jlm_generate_frames", h0.device().index(), timed, N > 0 && R > 0 ? P + N - 1 : 0, JLM_GENERATE_EVENTS_PER_FRAME,
+                         [&](hipStream_t st, void *const *ev) { return jlm_generate_frames(&m, &p, st, ev); });
 }
 
 // the k best words of every row of f32 logits y [n_rows, ld] with their -log p (jlm_topk_rows, include/jlm_hip.h): ids int32 and nll
@@ -671,12 +656,8 @@ Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     const int64_t NP = n_prompts, B = beam, P = n_prompt, N = n_words, R = n_prompts * beam;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
     auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    TORCH_CHECK(NP >= 0 && B >= 1 && P >= 1 && N >= 0 && (int64_t)n_live_host.size() == P,
-                "jlm.complete_frames: n_live_host holds one count per prompt frame");
-    for (int64_t x : n_live_host) TORCH_CHECK(x >= 0 && x <= NP, "jlm.complete_frames: a live-row count outside [0, n_prompts]");
-    TORCH_CHECK(h0.numel() >= R * m.H && h1.numel() >= R * m.H && h0.element_size() == 4 && h1.element_size() == 4 &&
-                    is(c0, at::kFloat, R * m.H) && is(c1, at::kFloat, R * m.H),
-                "jlm.complete_frames: state row sets [n_prompts * beam, H] of 4-byte values");
+    TORCH_CHECK(NP >= 0 && B >= 1 && P >= 1 && N >= 0, "jlm.complete_frames: n_prompts >= 0, beam >= 1, n_prompt >= 1 and n_words >= 0");
+    check_row_sets("complete_frames", m, R, h0, c0, h1, c1, n_live_host, P, "prompt frame", NP);
     TORCH_CHECK(is(rows, at::kInt, R) && is(prev, at::kInt, P * NP) && is(prompt, at::kInt, P * NP) && is(n_live, at::kInt, P),
                 "jlm.complete_frames: int32 rows [R], prev / prompt [n_prompt][n_prompts], n_live [n_prompt]");
     TORCH_CHECK(is(cand_ids, at::kInt, R * B) && is(cand_nll, at::kDouble, R * B) && is(word, at::kInt, R) && is(prev_row, at::kInt, R) &&
@@ -702,37 +683,8 @@ Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     p.stop_id = (int)stop_id;
     p.bp_parent = ptr<int>(bp_parent, "bp_parent"); p.bp_word = ptr<int>(bp_word, "bp_word"); p.bp_nll = ptr<double>(bp_nll, "bp_nll");
     p.flags = optr<int>(flags, "flags");
-    const int dev = h0.device().index();
-    const c10::hip::HIPGuard device_guard(dev);
-    hipStream_t st = c10::hip::getCurrentHIPStream(dev).stream();
-    const int64_t F = N > 0 ? P + N - 1 : 0;
-    std::vector<hipEvent_t> ev;
-    struct Destroy {
-        std::vector<hipEvent_t> &ev;
-        ~Destroy() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } destroy{ev};
-    if (timed)
-        for (int64_t i = 0; i < F * JLM_COMPLETE_EVENTS_PER_FRAME; ++i) {
-            hipEvent_t e;
-            jlm_check((int)hipEventCreate(&e), "hipEventCreate");
-            ev.push_back(e);
-        }
-    {
-        const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
-        jlm_check(jlm_complete_frames(&m, &p, st, timed ? reinterpret_cast<void *const *>(ev.data()) : nullptr), "jlm_complete_frames");
-    }
-    if (!timed || F == 0 || NP == 0) return at::empty({0}, at::kDouble);
-    jlm_check((int)hipEventSynchronize(ev.back()), "hipEventSynchronize");
-    Tensor out = at::zeros({F, JLM_COMPLETE_EVENTS_PER_FRAME - 1}, at::kDouble);
-    auto a = out.accessor<double, 2>();
-    for (int64_t f = 0; f < F; ++f)
-        for (int i = 0; i + 1 < JLM_COMPLETE_EVENTS_PER_FRAME; ++i) {
-            float ms = 0.0f;
-            jlm_check((int)hipEventElapsedTime(&ms, ev[f * JLM_COMPLETE_EVENTS_PER_FRAME + i], ev[f * JLM_COMPLETE_EVENTS_PER_FRAME + i + 1]),
-                      "hipEventElapsedTime");
-            a[f][i] = ms;
-        }
-    return out;
+    return launch_frames("jlm_complete_frames", h0.device().index(), timed, N > 0 && NP > 0 ? P + N - 1 : 0, JLM_COMPLETE_EVENTS_PER_FRAME,
+                         [&](hipStream_t st, void *const *ev) { return jlm_complete_frames(&m, &p, st, ev); });
 }
 
 int64_t abi_version() { return jlm_abi_version(); }

@@ -24,6 +24,11 @@ class Vocab(object):
     def __len__(self):
         return len(self.w2i)
 
+    @property
+    def t2i(self):
+        """the id of every token the model reads and predicts: the words (a CharVocab: the characters)"""
+        return self.w2i
+
 
 class CharVocab(Vocab):
     """reference train/data.py:28-47: the word vocabulary plus ``c2i`` / ``i2c`` over the characters of the in-vocabulary words'
@@ -41,3 +46,16 @@ class CharVocab(Vocab):
 
     def __len__(self):
         return len(self.c2i)
+
+    @property
+    def t2i(self):
+        return self.c2i
+
+
+def load_vocab(args):
+    """The command-line tools' prologue over config.add_model_args' flags: --root re-roots the paths, then the experiment's config
+    is read.  -> (config dict, its vocabulary: a CharVocab for a character model, else a Vocab)"""
+    if args.root:
+        _config.set_root(args.root)
+    config = _config.load_config_dict(args.experiment_id)
+    return config, (CharVocab if config.get("char_rnn") else Vocab)(config["vocab_size"])

@@ -22,10 +22,11 @@ import time
 
 import numpy as np
 
-from . import _lib
 from . import config as _config
 from . import ops as _ops
-from .score import check_ids
+from . import rowsets
+from .rowsets import check_ids, prompt_arrays
+from .rowsets import plan_prompts as plan_rows     # one row per prompt
 
 # the logit buffer is rows x V x 4 bytes (V = 100 k: 1 GB at 2 560 rows); 2 560 rows fill the logit GEMM's tiles on every CU
 MAX_ROWS = 2560
@@ -68,51 +69,12 @@ def check_args(prompts, n_words, temperature, seed, stop_id, V):
         raise ValueError("temperature must be finite and >= 0 (got %r)" % (temperature,))
     if not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= _M64:
         raise ValueError("seed must be an integer in [0, 2^64) (got %r)" % (seed,))
-    if prompts is None:
-        prompts = [[EOS_ID]]
-    out = []
-    for i, p in enumerate(prompts):
-        a = np.asarray(p, dtype=np.int64).ravel()
-        if a.size == 0:
-            raise ValueError("prompt %d is empty (a row needs at least one word to start from; the reference starts at <eos>)" % i)
-        check_ids(a, V, "generate (prompt %d)" % i)
-        out.append(a)
+    out = rowsets.check_prompts([[EOS_ID]] if prompts is None else prompts, V, "generate", "a row needs at least one word to start from")
     if len(out) >= 2 ** 31:
         raise ValueError("too many rows")
     if stop_id is not None:
         check_ids([stop_id], V, "generate (stop_id)")
     return out
-
-
-def plan_rows(lengths, max_rows):
-    """Rows sorted by prompt length, longest first (stable), cut into chunks of at most ``max_rows``.  -> list of dict(idx = the
-    caller's row of each chunk row, lens, n_prompt = the longest, n_live [n_prompt] = rows a prompt frame steps)."""
-    if max_rows < 1:
-        raise ValueError("max_rows must be >= 1")
-    lens = np.asarray(lengths, dtype=np.int64)
-    order = np.argsort(-lens, kind="stable")
-    chunks = []
-    for i in range(0, len(order), max_rows):
-        idx = order[i:i + max_rows]
-        L = lens[idx]
-        P = int(L[0])
-        n_live = (L[None, :] >= P - np.arange(P)[:, None]).sum(axis=1).astype(np.int32)
-        chunks.append(dict(idx=idx, lens=L, n_prompt=P, n_live=n_live))
-    return chunks
-
-
-def prompt_arrays(prompts, n_prompt):
-    """prompt / prev [n_prompt, R] int32 of right-aligned prompts (longest first): row r consumes its prompt at frames
-    n_prompt - len .. n_prompt - 1 and starts from the zero state (prev -1) at the first of them; elsewhere prev = r.  Positions
-    before a row's start hold word 0 and prev -1 (never read: the row is not live there)."""
-    R = len(prompts)
-    prompt = np.zeros((n_prompt, R), dtype=np.int32)
-    prev = np.tile(np.arange(R, dtype=np.int32), (n_prompt, 1))
-    for r, p in enumerate(prompts):
-        f0 = n_prompt - len(p)
-        prompt[f0:, r] = p
-        prev[:f0 + 1, r] = -1
-    return prompt, prev
 
 
 def truncate(ids, stop_id):
@@ -131,56 +93,37 @@ class Generator:
         self.torch = dev_model.torch
         self.last_frame_ms = None         # [frames, 4] of the last timed call: LSTM step, T projection, logit GEMMs, draw
 
-    @property
-    def ld_logits(self):
-        return (self.m.V + 3) // 4 * 4
-
     def row_bytes(self, n_prompt, n_words):
         m = self.m
-        return (self.ld_logits + 4 * m.H + m.ldt) * 4 + n_prompt * 8 + n_words * 12 + 32
+        return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + n_prompt * 8 + n_words * 12 + 32
 
-    def max_rows(self, n_prompt, n_words):
-        """rows per call: MAX_ROWS, fewer when the call's buffers would exceed GENERATE_BUDGET_BYTES"""
-        k = GENERATE_BUDGET_BYTES // self.row_bytes(n_prompt, n_words)
-        return int(max(1, min(MAX_ROWS, k, (0x7ffffff0 // max(self.m.H // 4, 1)) - 1)))
-
-    def run(self, prompts, row_id, n_words, temperature, seed, stop_id=None, timed=False):
-        """One call over rows already sorted by prompt length (longest first).  row_id [R]: the caller's index of each row.
-        -> (ids [n_words, R] int32, nll [n_words, R] float64); a stopped row's later positions hold -1 / 0."""
+    def run(self, prompts, row_id, n_words, temperature, seed, stop_id=None, timed=False, n_live=None):
+        """One call over rows already sorted by prompt length (longest first).  row_id [R]: the caller's index of each row.  n_live:
+        the chunk's live counts from plan_rows (None: rowsets.live_counts of the prompts).  -> (ids [n_words, R] int32, nll
+        [n_words, R] float64); a stopped row's later positions hold -1 / 0."""
         torch, m = self.torch, self.m
-        R = len(prompts)
-        P = len(prompts[0])
+        if n_live is None:
+            n_live = rowsets.live_counts([len(p) for p in prompts])
+        R, P = len(prompts), len(n_live)
         prompt, prev = prompt_arrays(prompts, P)
-        n_live = (np.array([len(p) for p in prompts])[None, :] >= P - np.arange(P)[:, None]).sum(axis=1).astype(np.int32)
-        dev, f32, i32, f64 = m.device, torch.float32, torch.int32, torch.float64
+        dev, i32 = m.device, torch.int32
         s = int(seed) & _M64
         s = s - (1 << 64) if s >= 1 << 63 else s
         with m._ctx():
-            e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
-            hs = [e((R, m.H), f32), e((R, m.H), f32)]
-            cs = [e((R, m.H), f32), e((R, m.H), f32)]
-            untied_f32 = m.mode == "untied" and not m.split_lstm
-            T = None if untied_f32 else e((R, m.ldt), f32)
-            logits = e((R, self.ld_logits), f32)
+            rs = rowsets.RowSets(m, R, logits=True)
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-            rows = torch.arange(R, device=dev, dtype=i32)
             word = torch.zeros(R, device=dev, dtype=i32)
             done = torch.zeros(R, device=dev, dtype=i32) if stop_id is not None else None
             ids = torch.full((n_words, R), -1, device=dev, dtype=i32)
-            nll = torch.zeros((n_words, R), device=dev, dtype=f64)
-            flags = torch.zeros(1, device=dev, dtype=i32)
-            ms = _ops.backend().generate_frames(m.decode_model(), hs[0], cs[0], hs[1], cs[1], T, logits, self.ld_logits, rows, up(prev),
-                                                up(prompt), up(n_live), [int(x) for x in n_live], up(row_id), word, done,
-                                                -1 if stop_id is None else int(stop_id), float(temperature), s, ids, nll, flags,
+            nll = torch.zeros((n_words, R), device=dev, dtype=torch.float64)
+            ms = _ops.backend().generate_frames(m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, up(prev), up(prompt),
+                                                up(n_live), [int(x) for x in n_live], up(row_id), word, done,
+                                                -1 if stop_id is None else int(stop_id), float(temperature), s, ids, nll, rs.flags,
                                                 R, P, int(n_words), bool(timed))
             if timed:
                 self.last_frame_ms = ms.numpy()
-            fl = int(flags.cpu()[0])
-            ids_h = ids.cpu().numpy()
-            nll_h = nll.cpu().numpy()
-        if fl:
-            raise _lib.JlmHipError("sample_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)" % fl)
-        return ids_h, nll_h
+            rs.check_flags("sample_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)")
+            return ids.cpu().numpy(), nll.cpu().numpy()
 
 
 def generate(gen, prompts, n_words, temperature=1.0, seed=0, stop_id=None, max_rows=None):
@@ -192,10 +135,10 @@ def generate(gen, prompts, n_words, temperature=1.0, seed=0, stop_id=None, max_r
     if n_words == 0 or not prompts:
         return ids_out, nll_out
     if max_rows is None:
-        max_rows = gen.max_rows(max(lens), n_words)
+        max_rows = rowsets.clamp_rows(MAX_ROWS, GENERATE_BUDGET_BYTES, gen.row_bytes(max(lens), n_words), gen.m.H)
     for ch in plan_rows(lens, max_rows):
         idx = ch["idx"]
-        ids, nll = gen.run([prompts[i] for i in idx], idx.astype(np.int32), int(n_words), temperature, seed, stop_id)
+        ids, nll = gen.run([prompts[i] for i in idx], idx.astype(np.int32), int(n_words), temperature, seed, stop_id, n_live=ch["n_live"])
         for j, i in enumerate(idx):
             x = truncate(ids[:, j].astype(np.int64), stop_id)
             ids_out[i] = x
@@ -207,13 +150,11 @@ def encode_prompt(text, vocab):
     """``--prompt`` as ids: <eos>, then the words through Vocab.w2i (a character model: the characters of the surfaces through
     CharVocab.c2i) with <unk> for anything outside it, as perplexity.encode_lines encodes a line -- without its trailing <eos>.
     -> (ids, number of <unk> fallbacks)"""
-    from .data import CharVocab
     from .perplexity import encode_lines
     if text is None or not text.strip():
         return [EOS_ID], 0
     enc, n_unk = encode_lines([text], vocab)
-    eos = vocab.c2i["<eos>"] if isinstance(vocab, CharVocab) else vocab.w2i["<eos>"]
-    return [eos] + enc[0][:-1], n_unk
+    return [vocab.t2i["<eos>"]] + enc[0][:-1], n_unk
 
 
 def render(ids, vocab):
@@ -225,11 +166,9 @@ def render(ids, vocab):
 
 
 def main(argv=None):
-    from .data import CharVocab, Vocab
+    from .data import CharVocab, load_vocab
     ap = argparse.ArgumentParser(description="Sample word sequences from a dumped model on the device (reference decoder/model.py:213-245)")
-    ap.add_argument("--root", default=None, help="JLM root (data/, train/experiments/); default $JLM_ROOT")
-    ap.add_argument("-e", "--experiment_id", type=int, default=0)
-    ap.add_argument("--comp", type=int, default=0, help="compressed weights (lstm_weights_comp_<comp>.pkl)")
+    _config.add_model_args(ap)
     ap.add_argument("-n", "--rows", type=int, default=1, help="samples to draw")
     ap.add_argument("--words", type=int, default=100, help="words per sample")
     ap.add_argument("--temperature", type=float, default=1.0, help="0 = greedy")
@@ -238,11 +177,8 @@ def main(argv=None):
     ap.add_argument("--stop-at-eos", action="store_true", help="end a sample after it draws <eos>")
     ap.add_argument("--show-nll", action="store_true", help="append each sample's total -log p and its word count")
     args = ap.parse_args(argv)
-    if args.root:
-        _config.set_root(args.root)
+    _cfg, vocab = load_vocab(args)
     from .model import LSTM_Model
-    config = _config.load_config_dict(args.experiment_id)
-    vocab = (CharVocab if config.get("char_rnn") else Vocab)(config["vocab_size"])
     prompt, n_unk = encode_prompt(args.prompt, vocab)
     if n_unk:
         print("prompt: %d word(s) outside the vocabulary read as <unk>" % n_unk, file=sys.stderr)

@@ -998,20 +998,32 @@ class LSTM_Model():
             pred = self.predict([inp])[0]
         return [-np.log(p) for p in probs]
 
+    def _driver(self, cls):
+        """this model's row-set driver of class ``cls``, made on first use: _scorer, _generator and _completer below"""
+        drivers = self.__dict__.setdefault("_drivers", {})
+        if cls not in drivers:
+            drivers[cls] = cls(self.dev)
+        return drivers[cls]
+
     def _scorer(self):
-        s = getattr(self, "_score", None)
-        if s is None:
-            from .score import Scorer
-            s = self._score = Scorer(self.dev)
-        return s
+        from .score import Scorer
+        return self._driver(Scorer)
+
+    def _generator(self):
+        from .generate import Generator
+        return self._driver(Generator)
+
+    def _completer(self):
+        from .complete import Completer
+        return self._driver(Completer)
 
     def score(self, sequences, start, per_token=True, max_rows=None):
         """evaluate() for many sequences at once, on the device (jlm_amd/score.py).  ``sequences``: word-id lists of any length
         (0 included).  Sequence s is scored as ``evaluate(start, s)`` scores it: step 0 consumes ``start`` from the zero state and is
         scored on s[0], step t consumes s[t-1] and is scored on s[t].  -> one float64 array of per-word -log p per sequence, in input
         order (per_token=False: one float64 array of the per-sequence sums).  Sequences are sorted by length and cut into calls of
-        at most ``max_rows`` rows (default: Scorer.max_rows, from the buffers' size).  ValueError for an id outside [0, V) before
-        anything runs; JlmHipError when the device flags a log-normaliser that is not finite."""
+        at most ``max_rows`` rows (default: from the buffers' size, score.SCORE_BUDGET_BYTES).  ValueError for an id outside [0, V)
+        before anything runs; JlmHipError when the device flags a log-normaliser that is not finite."""
         from .score import score_sequences
         return score_sequences(self._scorer(), sequences, start, per_token, max_rows)
 
@@ -1040,18 +1052,8 @@ class LSTM_Model():
         with ``stop_id`` a row ends after drawing it.  -> (ids, nll): per row an int64 array of its draws and a float64 array of their
         -log p at temperature 1 (score()'s convention).  ValueError for a bad argument before anything runs; JlmHipError when the
         device flags a non-finite logit or log-normaliser."""
-        from .generate import Generator, generate
-        g = getattr(self, "_gen", None)
-        if g is None:
-            g = self._gen = Generator(self.dev)
-        return generate(g, prompts, n_words, temperature, seed, stop_id, max_rows)
-
-    def _completer(self):
-        from .complete import Completer
-        c = getattr(self, "_comp", None)
-        if c is None:
-            c = self._comp = Completer(self.dev)
-        return c
+        from .generate import generate
+        return generate(self._generator(), prompts, n_words, temperature, seed, stop_id, max_rows)
 
     def predict_top(self, contexts, n=10, max_rows=None):
         """The ``n`` most probable next words after each context, on the device (jlm_amd/complete.py; the reference's

@@ -20,16 +20,13 @@ import time
 import numpy as np
 
 from . import config as _config
-from .data import CharVocab, Vocab
+from .data import CharVocab, load_vocab
 
 
 def encode_lines(lines, vocab):
     """-> (one id list per line, ending in <eos>; number of <unk> fallbacks).  train/data.py:60-69."""
     out, n_unk = [], 0
-    if isinstance(vocab, CharVocab):
-        table, unk, eos = vocab.c2i, vocab.c2i["<unk>"], vocab.c2i["<eos>"]
-    else:
-        table, unk, eos = vocab.w2i, vocab.w2i["<unk>"], vocab.w2i["<eos>"]
+    table, unk, eos = vocab.t2i, vocab.t2i["<unk>"], vocab.t2i["<eos>"]
     for line in lines:
         words = line.strip().split(" ")
         if isinstance(vocab, CharVocab):
@@ -74,27 +71,21 @@ def stream_perplexity(model, stream, batch_size, num_steps):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Test perplexity of a dumped model on the device (reference train/train.py:101-102)")
-    ap.add_argument("--root", default=None, help="JLM root (data/, train/experiments/); default $JLM_ROOT")
-    ap.add_argument("-e", "--experiment_id", type=int, default=0)
-    ap.add_argument("--comp", type=int, default=0, help="compressed weights (lstm_weights_comp_<comp>.pkl)")
+    _config.add_model_args(ap)
     ap.add_argument("--file", default=None, help="text to score, one sentence per line (default: <root>/data/test.txt)")
     ap.add_argument("--mode", choices=("sentence", "stream"), default="stream")
     ap.add_argument("-b", "--batch_size", type=int, default=None, help="stream mode: parallel streams (default: the config's, else 64)")
     ap.add_argument("--num_steps", type=int, default=20, help="stream mode: steps per chunk")
     ap.add_argument("-es", type=int, default=0, help="score the first N lines only (0 = all)")
     args = ap.parse_args(argv)
-    if args.root:
-        _config.set_root(args.root)
+    config, vocab = load_vocab(args)
     from .model import LSTM_Model
-    config = _config.load_config_dict(args.experiment_id)
-    vocab = (CharVocab if config.get("char_rnn") else Vocab)(config["vocab_size"])
     path = args.file or os.path.join(_config.data_path, "test.txt")
     sents, n_unk = encode_lines(read_lines(path, args.es), vocab)
     model = LSTM_Model(experiment_id=args.experiment_id, comp=args.comp)
     t0 = time.time()
     if args.mode == "sentence":
-        eos = vocab.c2i["<eos>"] if isinstance(vocab, CharVocab) else vocab.w2i["<eos>"]
-        pp, _total, n_tok = sentence_perplexity(model, sents, eos)
+        pp, _total, n_tok = sentence_perplexity(model, sents, vocab.t2i["<eos>"])
     else:
         bs = args.batch_size or int(config.get("batch_size", 64))
         stream = [i for s in sents for i in s]

@@ -12,21 +12,13 @@ command-line front end.
 """
 import numpy as np
 
-from . import _lib
 from . import ops as _ops
+from .rowsets import RowSets, check_ids, clamp_rows
 
 # rows per call: the gate GEMM is most efficient at large row counts (37-40 % of the MFMA peak at 20 480 rows, 28 % at 2 560:
 # BENCH_r06); a call's buffers are bounded by SCORE_BUDGET_BYTES besides
 MAX_ROWS = 20480
 SCORE_BUDGET_BYTES = 2 << 30
-
-
-def check_ids(arr, V, what):
-    """ValueError unless every id of ``arr`` lies in [0, V) -- before anything is launched (the kernels index with them)."""
-    a = np.asarray(arr)
-    if a.size and (a.min() < 0 or a.max() >= V):
-        bad = a[(a < 0) | (a >= V)].ravel()[0]
-        raise ValueError("%s: word id %d outside the model's vocabulary [0, %d)" % (what, int(bad), V))
 
 
 def plan_rows(lengths, max_rows):
@@ -90,12 +82,6 @@ class Scorer:
         n_parts = 0 if m.self_norm else max(m.n_vocab_tiles, 1)
         return (4 * m.H + m.ldt + (m.ld_tm or 0)) * 4 + n_parts * 8 + 16 + n_steps * (8 + (8 if per_token else 0))
 
-    def max_rows(self, n_steps, per_token=True):
-        """the default row budget of a call: MAX_ROWS, fewer when the call's buffers would exceed SCORE_BUDGET_BYTES, and within the
-        LSTM-step kernels' addressing (rows x H / 4 < 2^31)"""
-        k = SCORE_BUDGET_BYTES // self.row_bytes(n_steps, per_token)
-        return int(max(1, min(MAX_ROWS, k, (0x7ffffff0 // max(self.m.H // 4, 1)) - 1)))
-
     def run(self, word, target, n_live, h=None, c=None, per_token=True, timed=False):
         """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
         the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
@@ -107,48 +93,39 @@ class Scorer:
         check_ids(word, m.V, "score")
         check_ids(target, m.V, "score")
         n_live = [int(x) for x in n_live]
-        dev, f32, i32, f64 = m.device, torch.float32, torch.int32, torch.float64
+        dev, i32, f64 = m.device, torch.int32, torch.float64
         with m._ctx():
-            e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)
-            hs = [e((R, m.H), f32), e((R, m.H), f32)]
-            cs = [e((R, m.H), f32), e((R, m.H), f32)]
-            rows = torch.arange(R, device=dev, dtype=i32)
+            rs = RowSets(m, R)
             if h is None:
                 prev0 = torch.full((R,), -1, device=dev, dtype=i32)
             else:
                 if tuple(h.shape) != (R, m.H) or tuple(c.shape) != (R, m.H):
                     raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (R, m.H, tuple(h.shape), tuple(c.shape)))
-                hs[0].copy_(h)
-                cs[0].copy_(c)
-                prev0 = rows
-            untied_f32 = m.mode == "untied" and not m.split_lstm
-            T = None if untied_f32 else e((R, m.ldt), f32)
+                rs.h[0].copy_(h)
+                rs.c[0].copy_(c)
+                prev0 = rs.rows
             part, n_parts = None, 0
             if not m.self_norm:
                 n_parts = max(m.n_vocab_tiles, 1)
-                part = e((n_parts, R, 2), f32)
+                part = torch.empty((n_parts, R, 2), device=dev, dtype=torch.float32)
             Tm = None
             if part is not None and getattr(m, "ld_tm", 0):
-                Tm = torch.zeros(((R + 31) // 32 * 32, m.ld_tm), device=dev, dtype=f32)     # whole 32-row blocks (jlm_hip.h)
+                Tm = torch.zeros(((R + 31) // 32 * 32, m.ld_tm), device=dev, dtype=torch.float32)     # whole 32-row blocks (jlm_hip.h)
             wd = torch.from_numpy(word).to(dev)
             tg = torch.from_numpy(target).to(dev)
             nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
             nll_seq = torch.zeros(R, device=dev, dtype=f64)
             nll_tok = torch.zeros((S, R), device=dev, dtype=f64) if per_token else None
-            flags = torch.zeros(1, device=dev, dtype=i32)
-            ms = _ops.backend().score_frames(m.decode_model(), hs[0], cs[0], hs[1], cs[1], T, Tm, int(m.ld_tm or 0), part, n_parts, rows,
-                                             prev0, wd, tg, nl, n_live, nll_seq, nll_tok, flags, R, S, bool(timed))
+            ms = _ops.backend().score_frames(m.decode_model(), *rs.state(), Tm, int(m.ld_tm or 0), part, n_parts, rs.rows, prev0, wd, tg,
+                                             nl, n_live, nll_seq, nll_tok, rs.flags, R, S, bool(timed))
             if timed:
                 self.last_step_ms = ms.numpy()
-            fl = int(flags.cpu()[0])
+            rs.check_flags("score_fold_kernel flagged a target outside the model's segments (flags %d)",
+                           "a log-normaliser is not finite: this model's logits left the range the fixed-reference normaliser covers "
+                           "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
             seq = nll_seq.cpu().numpy()
             tok = nll_tok.cpu().numpy() if per_token else None
-        if fl & 1:
-            raise _lib.JlmHipError("a log-normaliser is not finite: this model's logits left the range the fixed-reference normaliser covers "
-                                   "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
-        if fl:
-            raise _lib.JlmHipError("score_fold_kernel flagged a target outside the model's segments (flags %d)" % fl)
-        return seq, tok, hs[S % 2], cs[S % 2]
+        return seq, tok, rs.h[S % 2], rs.c[S % 2]
 
 
 def score_sequences(scorer, sequences, start, per_token=True, max_rows=None):
@@ -161,7 +138,7 @@ def score_sequences(scorer, sequences, start, per_token=True, max_rows=None):
     lens = [len(s) for s in seqs]
     longest = max(lens) if lens else 0
     if max_rows is None:
-        max_rows = scorer.max_rows(longest, per_token)
+        max_rows = clamp_rows(MAX_ROWS, SCORE_BUDGET_BYTES, scorer.row_bytes(longest, per_token), scorer.m.H)
     out = [np.zeros(L, dtype=np.float64) for L in lens] if per_token else np.zeros(len(seqs), dtype=np.float64)
     for ch in plan_rows(lens, max_rows):
         idx = ch["idx"]

@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-from jlm_amd import _lib, complete as C, config as jconfig, generate as G, ops as _ops     # noqa: E402
-from oracle import jlm_oracle as orc                                                       # noqa: E402
+from jlm_amd import _lib, complete as C, ops as _ops                                      # noqa: E402
+from tests.gpu_rows import UNTIED_F32, fixture_model, load_model, lse, oracle_lm, ragged_prompts     # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -161,26 +161,6 @@ SMALL = ["small-tied", "small-untied", "small-dsoftmax", "small-vtable", "small-
          "small-vtable-sn", "small-char", "peaked20-vtable"]
 
 
-def _model(root):
-    jconfig.set_root(root)
-    from jlm_amd.model import LSTM_Model
-    return LSTM_Model(experiment_id=1)
-
-
-def _oracle_lm(root):
-    return orc.OracleDecoder(root, 1).model
-
-
-def _prompts(R, V, seed, lo=1, hi=6):
-    rng = np.random.RandomState(seed)
-    return [[G.EOS_ID] + list(rng.randint(2, V, size=rng.randint(lo, hi + 1) - 1)) for _ in range(R)]
-
-
-def _lse(y):
-    m = y.max()
-    return m + np.log(np.exp(y - m).sum())
-
-
 def _device_beams(model, prompts, N, B, stop_id=None):
     """one device call over the prompts (sorted longest first here) -> (order, bp_parent, bp_word, bp_nll, score)"""
     order = np.argsort(-np.array([len(p) for p in prompts]), kind="stable")
@@ -207,7 +187,7 @@ def oracle_follow(lm, prompt, bp_parent, bp_word, bp_nll, score, p, N, B, stop_i
                 cands.append((b["s"], j, -1))
                 continue
             y = Y[j]
-            nll = -y if sn else _lse(y) - y
+            nll = -y if sn else lse(y) - y
             tot = b["s"] + nll
             top = np.argsort(tot, kind="stable")[:B + 1]
             cands.extend((float(tot[w]), j, int(w)) for w in top)
@@ -230,7 +210,7 @@ def oracle_follow(lm, prompt, bp_parent, bp_word, bp_nll, score, p, N, B, stop_i
                 nb.append(dict(par))
                 continue
             y = Y[j]
-            on = -y[w] if sn else _lse(y) - y[w]
+            on = -y[w] if sn else lse(y) - y[w]
             assert abs(n - on) <= TOK_ATOL, (k, i, n, on)
             h2, c2 = lm.lstm_cell(np.array([w]), par["h"][None], par["c"][None])
             nb.append(dict(h=h2[0], c=c2[0], s=par["s"] + on, fin=stop_id is not None and w == stop_id, n=par["n"] + 1))
@@ -240,13 +220,12 @@ def oracle_follow(lm, prompt, bp_parent, bp_word, bp_nll, score, p, N, B, stop_i
     return agree, amb
 
 
-def _e2e(name, fx, R, N, B, stop_id=None, seed=0):
-    f = fx(name)
-    model = _model(f["root"])
+def _e2e(name, fx, monkeypatch, R, N, B, stop_id=None, seed=0):
+    f, model = fixture_model(fx, name, monkeypatch)
     V = model.dev.V
-    prompts = _prompts(R, V, seed=len(name) + seed)
+    prompts = ragged_prompts(R, V, seed=len(name) + seed)
     order, bp_parent, bp_word, bp_nll, score = _device_beams(model, prompts, N, B, stop_id)
-    lm = _oracle_lm(f["root"])
+    lm = oracle_lm(f["root"])
     agree = amb = 0
     for p, i in enumerate(order):
         a, b = oracle_follow(lm, prompts[i], bp_parent, bp_word, bp_nll, score, p, N, B, stop_id)
@@ -273,30 +252,30 @@ def _e2e(name, fx, R, N, B, stop_id=None, seed=0):
     return model, prompts, res
 
 
-@pytest.mark.parametrize("name", SMALL)
-def test_complete_matches_oracle(name, fx):
-    _e2e(name, fx, R=6, N=5, B=6)
+@pytest.mark.parametrize("name", SMALL + [UNTIED_F32])
+def test_complete_matches_oracle(name, fx, monkeypatch):
+    _e2e(name, fx, monkeypatch, R=6, N=5, B=6)
 
 
-def test_complete_mid_vtable_against_oracle(fx):
-    _e2e("mid-vtable", fx, R=3, N=3, B=4)
+def test_complete_mid_vtable_against_oracle(fx, monkeypatch):
+    _e2e("mid-vtable", fx, monkeypatch, R=3, N=3, B=4)
 
 
-def test_complete_stop_id_against_oracle(fx):
+def test_complete_stop_id_against_oracle(fx, monkeypatch):
     f = fx("small-vtable")
-    model = _model(f["root"])
-    prompts = _prompts(8, model.dev.V, seed=len("small-vtable") + 4)          # _e2e's prompts for seed 4
+    model = load_model(f["root"])
+    prompts = ragged_prompts(8, model.dev.V, seed=len("small-vtable") + 4)          # _e2e's prompts for seed 4
     res = model.complete(prompts, 6, beam_width=5)
     stop = int(np.bincount(np.concatenate([h[0][:3] for r in res for h in r])).argmax())    # a word the beams reach early
-    _m, _p, res2 = _e2e("small-vtable", fx, R=8, N=6, B=5, stop_id=stop, seed=4)
+    _m, _p, res2 = _e2e("small-vtable", fx, monkeypatch, R=8, N=6, B=5, stop_id=stop, seed=4)
     assert any(len(h[0]) < 6 for r in res2 for h in r)                 # some hypothesis finished and was carried
 
 
 @pytest.mark.parametrize("name", ["small-vtable", "small-tied-sn", "small-char", "peaked20-vtable"])
 def test_beam1_is_greedy_and_predict_top(name, fx):
     f = fx(name)
-    model = _model(f["root"])
-    prompts = _prompts(20, model.dev.V, seed=7, hi=8)
+    model = load_model(f["root"])
+    prompts = ragged_prompts(20, model.dev.V, seed=7, hi=8)
     greedy, gnll = model.generate(prompts, 7, temperature=0.0)
     res = model.complete(prompts, 7, beam_width=1)
     top = model.predict_top(prompts, n=1)
@@ -320,8 +299,8 @@ def test_beam1_is_greedy_and_predict_top(name, fx):
 @pytest.mark.parametrize("name", ["small-vtable", "small-untied", "small-char"])
 def test_complete_repeat_cuts_and_neighbours(name, fx):
     f = fx(name)
-    model = _model(f["root"])
-    prompts = _prompts(23, model.dev.V, seed=11, lo=1, hi=9)
+    model = load_model(f["root"])
+    prompts = ragged_prompts(23, model.dev.V, seed=11, lo=1, hi=9)
     B, N = 7, 5
 
     def same(a, b, exact=False):
@@ -346,7 +325,7 @@ def test_complete_repeat_cuts_and_neighbours(name, fx):
 
 def test_complete_errors(fx):
     f = fx("small-tied")
-    model = _model(f["root"])
+    model = load_model(f["root"])
     V = model.dev.V
     for kw in (dict(prompts=[[V]]), dict(prompts=[[]]), dict(n_words=0), dict(beam_width=65), dict(beam_width=0),
                dict(n_best=11), dict(stop_id=V)):

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-from jlm_amd import _lib, config as jconfig, generate as G, ops as _ops     # noqa: E402
-from oracle import jlm_oracle as orc                                        # noqa: E402
+from jlm_amd import _lib, generate as G, ops as _ops                                     # noqa: E402
+from tests.gpu_rows import UNTIED_F32, fixture_model, load_model, lse, oracle_lm, ragged_prompts     # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -68,12 +68,6 @@ def _check_draw(y, temperature, u, got, tol):
     return False
 
 
-def _lse(y):
-    y = np.asarray(y, dtype=np.float64)
-    m = y.max()
-    return m + np.log(np.exp(y - m).sum())
-
-
 def _kernel_case(y, temperature, seed=5, steps=3, self_norm=False):
     R, n = y.shape
     ambiguous = total = 0
@@ -88,7 +82,7 @@ def _kernel_case(y, temperature, seed=5, steps=3, self_norm=False):
                 assert ids[r] == int(np.argmax(y[r]))
             else:
                 ambiguous += not _check_draw(y[r], temperature, u[r], int(ids[r]), 1e-9)
-            want = -float(y[r, ids[r]]) if self_norm else _lse(y[r]) - float(y[r, ids[r]])
+            want = -float(y[r, ids[r]]) if self_norm else lse(y[r]) - float(y[r, ids[r]])
             assert abs(nll[r] - want) <= 1e-6, (r, nll[r], want)
             total += 1
     assert ambiguous <= max(1, total // 100), (ambiguous, total)
@@ -169,21 +163,6 @@ SMALL = ["small-tied", "small-untied", "small-dsoftmax", "small-vtable", "small-
          "wide-vtable", "wide-dsoftmax", "wideh-vtable", "wide128-tied", "small-char"]
 
 
-def _model(root):
-    jconfig.set_root(root)
-    from jlm_amd.model import LSTM_Model
-    return LSTM_Model(experiment_id=1)
-
-
-def _oracle_lm(root):
-    return orc.OracleDecoder(root, 1).model
-
-
-def _prompts(R, V, seed, lo=1, hi=6):
-    rng = np.random.RandomState(seed)
-    return [[G.EOS_ID] + list(rng.randint(2, V, size=rng.randint(lo, hi + 1) - 1)) for _ in range(R)]
-
-
 def oracle_follow(lm, prompts, ids, temperature, seed, n_words):
     """the oracle teacher-forced on the device's draws: -> (agreeing draws, ambiguous draws, oracle nll per row)"""
     sn = lm.config["self_norm"]
@@ -196,7 +175,7 @@ def oracle_follow(lm, prompts, ids, temperature, seed, n_words):
         nll = []
         for k, w in enumerate(x):
             y = lm.project(h)[0]
-            nll.append(-y[w] if sn else _lse(y) - y[w])
+            nll.append(-y[w] if sn else lse(y) - y[w])
             if temperature == 0:
                 srt = np.sort(y)
                 if w == int(np.argmax(y)):
@@ -221,17 +200,16 @@ def oracle_follow(lm, prompts, ids, temperature, seed, n_words):
     return agree, amb, out
 
 
-@pytest.mark.parametrize("name", SMALL + ["peaked20-vtable"])
-def test_generate_matches_oracle(name, fx):
-    f = fx(name)
-    model = _model(f["root"])
+@pytest.mark.parametrize("name", SMALL + ["peaked20-vtable", UNTIED_F32])
+def test_generate_matches_oracle(name, fx, monkeypatch):
+    f, model = fixture_model(fx, name, monkeypatch)
     V = model.dev.V
     R, N = (12, 10) if name.startswith("peaked") else (40, 12)
-    prompts = _prompts(R, V, seed=len(name))
+    prompts = ragged_prompts(R, V, seed=len(name))
     ids, nll = model.generate(prompts, N, temperature=1.0, seed=77)
     assert len(ids) == R and all(len(x) == N and x.dtype == np.int64 for x in ids)
     assert all(l.dtype == np.float64 for l in nll)
-    agree, amb, onll = oracle_follow(_oracle_lm(f["root"]), prompts, ids, 1.0, 77, N)
+    agree, amb, onll = oracle_follow(oracle_lm(f["root"]), prompts, ids, 1.0, 77, N)
     assert amb <= max(1, (agree + amb) // 50), (agree, amb)
     for r in range(R):
         np.testing.assert_allclose(nll[r], onll[r], rtol=0, atol=TOK_ATOL, err_msg="%s row %d" % (name, r))
@@ -245,10 +223,10 @@ def test_generate_matches_oracle(name, fx):
                                               ("small-dsoftmax", 0.05), ("small-untied", 10.0)])
 def test_generate_temperatures_against_oracle(name, temperature, fx):
     f = fx(name)
-    model = _model(f["root"])
-    prompts = _prompts(10, model.dev.V, seed=3)
+    model = load_model(f["root"])
+    prompts = ragged_prompts(10, model.dev.V, seed=3)
     ids, nll = model.generate(prompts, 8, temperature=temperature, seed=5)
-    agree, amb, onll = oracle_follow(_oracle_lm(f["root"]), prompts, ids, temperature, 5, 8)
+    agree, amb, onll = oracle_follow(oracle_lm(f["root"]), prompts, ids, temperature, 5, 8)
     assert amb <= 1, (agree, amb)
     for r in range(len(prompts)):
         np.testing.assert_allclose(nll[r], onll[r], rtol=0, atol=TOK_ATOL)
@@ -257,9 +235,9 @@ def test_generate_temperatures_against_oracle(name, temperature, fx):
 @pytest.mark.parametrize("name", ["small-vtable", "small-char", "wide-vtable"])
 def test_generate_cut_mixed_and_repeat(name, fx):
     f = fx(name)
-    model = _model(f["root"])
+    model = load_model(f["root"])
     V = model.dev.V
-    prompts = _prompts(37, V, seed=11, lo=1, hi=9)
+    prompts = ragged_prompts(37, V, seed=11, lo=1, hi=9)
     ids, nll = model.generate(prompts, 9, temperature=0.8, seed=2 ** 64 - 3)
     # bit-identical run to run
     ids2, nll2 = model.generate(prompts, 9, temperature=0.8, seed=2 ** 64 - 3)
@@ -279,8 +257,8 @@ def test_generate_cut_mixed_and_repeat(name, fx):
 
 def test_generate_stop_id(fx):
     f = fx("small-vtable")
-    model = _model(f["root"])
-    prompts = _prompts(64, model.dev.V, seed=12)
+    model = load_model(f["root"])
+    prompts = ragged_prompts(64, model.dev.V, seed=12)
     full, full_nll = model.generate(prompts, 20, temperature=1.5, seed=9)
     counts = np.bincount(np.concatenate(full), minlength=model.dev.V)
     stop = int(np.argmax(counts))
@@ -296,7 +274,7 @@ def test_generate_stop_id(fx):
 
 def test_generate_default_prompt_and_errors(fx):
     f = fx("small-tied")
-    model = _model(f["root"])
+    model = load_model(f["root"])
     ids, nll = model.generate(None, 5, seed=1)
     assert len(ids) == 1 and len(ids[0]) == 5
     one, _ = model.generate([[G.EOS_ID]], 5, seed=1)
@@ -321,16 +299,16 @@ def test_first_word_frequencies_g_test(fx):
     """65 536 rows from <eos>: the first draws' frequencies against the oracle's distribution (G-test, bins with an expectation
     under 5 pooled)"""
     f = fx("peaked20-vtable")
-    model = _model(f["root"])
+    model = load_model(f["root"])
     V = model.dev.V
     R = 65536
     ids, _nll = model.generate([[G.EOS_ID]] * R, 1, temperature=1.0, seed=2024)
     obs = np.bincount(np.array([x[0] for x in ids]), minlength=V).astype(np.float64)
-    lm = _oracle_lm(f["root"])
+    lm = oracle_lm(f["root"])
     h, c = lm.zero_state(1)
     h, c = lm.lstm_cell(np.array([G.EOS_ID]), h, c)
     y = lm.project(h)[0]
-    p = np.exp(y - _lse(y))
+    p = np.exp(y - lse(y))
     exp = p * R
     big = exp >= 5
     O = np.append(obs[big], obs[~big].sum())

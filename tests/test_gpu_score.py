@@ -12,7 +12,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 from jlm_amd import _lib, config as jconfig, synth      # noqa: E402
-from oracle import jlm_oracle as orc                    # noqa: E402
+from tests.gpu_rows import UNTIED_F32, fixture_model, load_model, lse, oracle_lm     # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -21,15 +21,6 @@ TOK_ATOL = 1e-5
 
 def sent_atol(L):
     return min(2e-5, 1e-6 * (L + 1) + 2e-6)
-
-
-def _oracle_lm(root):
-    return orc.OracleDecoder(root, 1).model
-
-
-def _logsumexp(y):
-    m = y.max(axis=1, keepdims=True)
-    return (m + np.log(np.exp(y - m).sum(axis=1, keepdims=True)))[:, 0]
 
 
 def oracle_nll(lm, seqs, start, h=None, c=None):
@@ -50,17 +41,11 @@ def oracle_nll(lm, seqs, start, h=None, c=None):
         y = lm.project(hl)
         tgt = np.array([seqs[r][t] for r in idx])
         yt = y[np.arange(len(idx)), tgt]
-        nll = -yt if sn else _logsumexp(y) - yt
+        nll = -yt if sn else lse(y) - yt
         for j, r in enumerate(idx):
             out[r][t] = nll[j]
         words[idx] = tgt
     return out, h, c
-
-
-def _model(root):
-    jconfig.set_root(root)
-    from jlm_amd.model import LSTM_Model
-    return LSTM_Model(experiment_id=1)
 
 
 def _ragged(n, V, seed, lo=0, hi=40):
@@ -100,11 +85,10 @@ SMALL = ["small-tied", "small-untied", "small-dsoftmax", "small-vtable", "small-
          "wide-vtable", "wide-dsoftmax", "wideh-vtable", "wide128-tied"]
 
 
-@pytest.mark.parametrize("name", SMALL)
-def test_score_matches_oracle(name, fx):
-    f = fx(name)
-    model = _model(f["root"])
-    lm = _oracle_lm(f["root"])
+@pytest.mark.parametrize("name", SMALL + [UNTIED_F32])
+def test_score_matches_oracle(name, fx, monkeypatch):
+    f, model = fixture_model(fx, name, monkeypatch)
+    lm = oracle_lm(f["root"])
     V = model.dev.V
     seqs = _ragged(300, V, seed=7)
     start = 1
@@ -130,13 +114,13 @@ def test_score_full_size_call_against_oracle_sample(name, knob, fx, monkeypatch)
     if knob:
         monkeypatch.setenv(knob, "0")
     f = fx(name)
-    model = _model(f["root"])
+    model = load_model(f["root"])
     V = model.dev.V
     seqs = _ragged(2700, V, seed=11)
     got = model.score(seqs, 1)
     assert model.dev.V == V and len(got) == 2700
     sample = list(range(0, 2700, 113))
-    lm = _oracle_lm(f["root"])
+    lm = oracle_lm(f["root"])
     want, _h, _c = oracle_nll(lm, [seqs[i] for i in sample], 1)
     peaked = name.startswith("peaked")
     over = _check_bars([got[i] for i in sample], want, (name, knob), sentence_bar=not peaked)
@@ -150,19 +134,19 @@ def test_score_full_size_call_against_oracle_sample(name, knob, fx, monkeypatch)
 def test_score_forced_forms(name, knob, value, fx, monkeypatch):
     monkeypatch.setenv(knob, value)
     f = fx(name)
-    model = _model(f["root"])
+    model = load_model(f["root"])
     if knob == "JLM_LSE_MIXED":
         assert not model.dev.mixed_idx
     if knob == "JLM_PRECISION":
         assert not model.dev.split_lstm and model.dev.split_array is None
     seqs = _ragged(300, model.dev.V, seed=3)
-    want, _h, _c = oracle_nll(_oracle_lm(f["root"]), seqs, 1)
+    want, _h, _c = oracle_nll(oracle_lm(f["root"]), seqs, 1)
     _check(model.score(seqs, 1), want, (name, knob))
 
 
 def test_score_agrees_with_evaluate(fx):
     f = fx("small-vtable")
-    model = _model(f["root"])
+    model = load_model(f["root"])
     seqs = _ragged(6, model.dev.V, seed=5, lo=0, hi=12)
     got = model.score(seqs, 1)
     for s, g in zip(seqs, got):
@@ -171,7 +155,7 @@ def test_score_agrees_with_evaluate(fx):
 
 def test_alone_and_in_a_batch(fx):
     f = fx("wide-vtable")
-    model = _model(f["root"])
+    model = load_model(f["root"])
     seqs = _ragged(300, model.dev.V, seed=9, lo=1)
     batch = model.score(seqs, 1)
     for i in (0, 17, 299):
@@ -181,7 +165,7 @@ def test_alone_and_in_a_batch(fx):
 @pytest.mark.parametrize("name", ["small-vtable", "wide-vtable", "small-untied"])
 def test_streams_carry_state(name, fx):
     f = fx(name)
-    model = _model(f["root"])
+    model = load_model(f["root"])
     rng = np.random.RandomState(2)
     B, n = 37, 12
     x = rng.randint(0, model.dev.V, size=(B, 2 * n))
@@ -192,13 +176,13 @@ def test_streams_carry_state(name, fx):
     assert np.array_equal(np.concatenate([a, b], axis=1), whole)         # bit-identical
     assert torch.equal(h2, hw) and torch.equal(c2, cw)
     # the oracle over the same streams, state carried
-    lm = _oracle_lm(f["root"])
+    lm = oracle_lm(f["root"])
     want = np.zeros((B, 2 * n))
     hh, cc = lm.zero_state(B)
     for t in range(2 * n):
         hh, cc = lm.lstm_cell(x[:, t], hh, cc)
         yy = lm.project(hh)
-        want[:, t] = _logsumexp(yy) - yy[np.arange(B), y[:, t]]
+        want[:, t] = lse(yy) - yy[np.arange(B), y[:, t]]
     np.testing.assert_allclose(whole, want, rtol=0, atol=TOK_ATOL)
     np.testing.assert_allclose(np.exp(whole.mean()), np.exp(want.mean()), rtol=1e-5)
 
@@ -215,7 +199,7 @@ def test_perplexity_module(name, fx, capsys):
     vocab = (CharVocab if f["cfg"].get("char_rnn") else Vocab)(V)
     sents, _unk = perplexity.encode_lines(perplexity.read_lines(os.path.join(f["root"], "data", "test.txt")), vocab)
     eos = vocab.c2i["<eos>"] if isinstance(vocab, CharVocab) else vocab.w2i["<eos>"]
-    lm = _oracle_lm(f["root"])
+    lm = oracle_lm(f["root"])
     want_s, _h, _c = oracle_nll(lm, sents, eos)
     pp_s = np.exp(sum(w.sum() for w in want_s) / sum(len(s) for s in sents))
     got = perplexity.main(["--root", f["root"], "-e", "1", "--mode", "sentence"])
@@ -228,7 +212,7 @@ def test_perplexity_module(name, fx, capsys):
     for t in range(x.shape[1]):
         hh, cc = lm.lstm_cell(x[:, t], hh, cc)
         yy = lm.project(hh)
-        tot += (_logsumexp(yy) - yy[np.arange(4), y[:, t]]).sum()
+        tot += (lse(yy) - yy[np.arange(4), y[:, t]]).sum()
     got = perplexity.main(["--root", f["root"], "-e", "1", "--mode", "stream", "-b", "4", "--num_steps", "5"])
     assert "Test perplexity: {}".format(got) in capsys.readouterr().out
     np.testing.assert_allclose(got, np.exp(tot / x.size), rtol=1e-5)
@@ -250,7 +234,7 @@ def test_nonfinite_normaliser_raises(tmp_path, monkeypatch):
             w[key] = [b * np.float32(600.0) for b in w[key]] if isinstance(w[key], list) else w[key] * np.float32(600.0)
     with open(wp, "wb") as fh:
         pickle.dump(w, fh)
-    model = _model(root)
+    model = load_model(root)
     m = model.dev
     assert m.mixed_idx and not m.lse_fixed_ref
     seqs = _ragged(8, m.V, seed=4, lo=2, hi=9)

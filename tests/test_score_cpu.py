@@ -7,7 +7,8 @@ import pytest
 from jlm_amd import config as jconfig, synth
 from jlm_amd.data import CharVocab, Vocab
 from jlm_amd.perplexity import encode_lines, read_lines
-from jlm_amd.score import check_ids, plan_rows, sentence_arrays, stream_layout
+from jlm_amd.rowsets import check_ids
+from jlm_amd.score import plan_rows, sentence_arrays, stream_layout
 
 
 def test_encoding_falls_back_to_unk_and_ends_lines_with_eos(fx):
@@ -113,7 +114,7 @@ def test_bad_ids_raise_before_any_launch(fx, monkeypatch):
     from jlm_amd import score as jscore
 
     class _Dev:
-        V = 2000
+        V, H = 2000, 8
 
     class _NoLaunch(jscore.Scorer):
         def __init__(self):
@@ -122,8 +123,8 @@ def test_bad_ids_raise_before_any_launch(fx, monkeypatch):
         def run(self, *a, **k):
             raise AssertionError("launched")
 
-        def max_rows(self, n_steps, per_token=True):
-            return 16
+        def row_bytes(self, n_steps, per_token=True):
+            return 1 << 20
 
     for seqs, start in (([[1, 2], [3, 2000]], 1), ([[1, 2]], -3), ([[1], [-1, 4]], 1)):
         with pytest.raises(ValueError):
