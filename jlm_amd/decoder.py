@@ -70,6 +70,7 @@ class _CellTooLarge(Exception):
 
 class Decoder():
     dynamic = False
+    char_model = False           # the class decodes character models (config['char_rnn']): CharRNNDecoder
     # jlm_beam_step keeps the candidates of one (frame, sentence) cell -- nodes ending there x beam -- in one wave's LDS: 12 bytes
     # each of 160 KB, less what the beam and the frame count take (jlm_beam_step_max_cands: the launcher's own formula).
     # Sentences with a larger cell (hundreds of homophones at a wide beam) take the host-side search (_decode_unpruned with the
@@ -79,7 +80,7 @@ class Decoder():
 
     def __init__(self, experiment_id=0, comp=0, device=None):
         self.config = _config.load_config_dict(experiment_id)
-        if self.config.get('char_rnn') and type(self).__name__ != "CharRNNDecoder":
+        if self.config.get('char_rnn') and not self.char_model:
             raise ValueError("experiment %r is a character model (config['char_rnn']): its softmax runs over characters, decode it with "
                              "CharRNNDecoder (jlm_amd/decoder_char.py; reference decoder/eval.py:43-44)" % (experiment_id,))
         self._load_vocab()
@@ -134,7 +135,7 @@ class Decoder():
         hypotheses the beam kept become one more probe (DeviceModel.calibrate_on_paths: the worst probe decides).  Only for a model
         that kept mixed rows (a model on split rows has nothing to re-decide); JLM_CALIB_PATHS=0: off."""
         m = self.model.dev
-        if self._paths_calibrated or os.environ.get("JLM_CALIB_PATHS", "1") == "0" or not getattr(m, "mixed_idx", None) \
+        if self._paths_calibrated or os.environ.get("JLM_CALIB_PATHS", "1") == "0" or m.mixed is None \
                 or float(os.environ.get("JLM_MIXED_MAX_LSE_RMS", "1")) <= 0.0:
             return
         self._paths_calibrated = True
@@ -163,9 +164,9 @@ class Decoder():
         self.perf_sen = 0
         unk = self.w2i.get("<unk>", 0)
         paths = [[self.w2i.get(w, unk) for w in words] for res in nbest for _s, words in res if words]
-        before = (m.mixed_fmt, list(m.mixed_idx))
+        before = m.mixed
         m.calibrate_on_paths(paths, first_word=self.w2i.get("<eos>", 0))
-        if (m.mixed_fmt, list(m.mixed_idx)) != before:
+        if (m.mixed_fmt, m.mixed_idx) != (before.fmt, before.idx):
             self._engine = DecodeEngine(m)     # (plans of the form the model had are of no use to the one it has now)
             self.pipeline_depth = self._engine.n_streams
         self.lattice_vocab, self.backward_lookup, self.last_lattice = None, None, None

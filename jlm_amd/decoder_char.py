@@ -55,6 +55,7 @@ class CharRNNDecoder(Decoder):
     """``CharRNNDecoder(experiment_id=0, comp=0)`` / ``.decode(input, topN=10, beam_width=10, vocab_select=False, samples=0,
     top_sampling=False, random_sampling=False) -> [(neg_log_prob, [display string, ...])]`` (decoder.py:244-341) plus
     ``decode_batch``.  ``beam_width=None`` keeps every candidate (:330: exponential; ``max_unpruned_paths`` bounds a frame)."""
+    char_model = True
 
     def __init__(self, experiment_id=0, comp=0, device=None):
         self.config = _config.load_config_dict(experiment_id)

@@ -18,6 +18,8 @@ libjlm_hip.so (exact-f32 MFMA), bound as torch custom ops (jlm_amd/ops.py).  :cl
 panels in HBM and is shared with the batched decoders, which never come back
 to numpy between frames.
 """
+import contextlib
+import itertools
 import json
 import os
 import pickle
@@ -29,6 +31,7 @@ import numpy as np
 from . import _lib
 from . import config as _config
 from . import ops as _ops
+from .rowformats import LOG2E, MIXED_SHAPES, MixedRows, MixedSegment, mixed_exponents, mixed_layout, mixed_shape, plane_scale, pow2_below
 
 GATES = "ifog"
 
@@ -212,7 +215,6 @@ class DeviceModel:
         segs_cfg = [tuple(s) for s in config["embedding_seg"]]
         self.seg_B = []          # device blocks [V_i, pad4(k_i)]
         self.segments = []       # dicts: v_start v_end k t_off ldb
-        self.vt_packed = []      # (unused since the V-tables are folded into the T GEMM)
         self.pmt = None
         if self.mode == "untied":
             self.ldt = H
@@ -286,27 +288,36 @@ class DeviceModel:
         if self.precision not in ("f16x3", "f32"):
             raise ValueError("JLM_PRECISION must be f16x3 or f32 (got %r)" % self.precision)
         self.split_array = None          # not None: the split-f16 segment table [(dict, tensor)] exists
-        self.mixed_idx, self.ld_tm, self.b2_log2, self.mixed_spread = [], 0, None, []
-        self.lse_fixed_ref = 0
+        self.mixed = None                # rowformats.MixedRows: the normaliser runs on mixed rows; None: on split rows
+        self.mixed_calib, self.mixed_spread = None, []
+        self._decode_cache = None
+        # largest value each T column can take (None: T is the state itself, |h| < 1); probe rows taken from real decodes
+        self._t_bound, self._extra_probe_words = None, []
         self.split_lstm = False
         self.um_split = None
         if self.precision == "f16x3" and (self.stationary_ok or self.mode == "untied"):
-            self._build_split(None if self.pmt is None else np.abs(pmt).sum(axis=1))
+            self._t_bound = None if self.pmt is None else np.abs(pmt).sum(axis=1)
+            self._build_split()
 
-    def _build_split(self, t_bound):
+    # the record's fields under the names the decoders, bench.py and the tests read
+    mixed_idx, seg_mixed, mixed_segments, mixed_t_scale, mixed_descale, mixed_s8 = (
+        property(lambda self, f=f: [] if self.mixed is None else [getattr(s, f) for s in self.mixed.segs])
+        for f in ("idx", "packed", "seg", "t_scale", "descale", "s8"))
+    b2_log2 = property(lambda self: None if self.mixed is None else self.mixed.b2_log2)
+    mixed_head_split = property(lambda self: [] if self.mixed is None else list(self.mixed.head_split))
+    mixed_fmt = property(lambda self: None if self.mixed is None else self.mixed.fmt)
+    ld_tm = property(lambda self: 0 if self.mixed is None else self.mixed.ld_tm)
+    lse_fixed_ref = property(lambda self: int(self.mixed is not None and self.mixed.fixed_ref),      # (assignable: tests force the form)
+                             lambda self, flag: setattr(self, "mixed", self.mixed.with_fixed_ref(flag)))
+
+    def _build_split(self):
         """Split rows of every segment's matrix.  Scales are powers of two: 2^eB puts max|B| at
         <= 2^14, 2^eT puts the largest value a T column can take (|h| < 1, so |T_j| <= sum_i |PM_ij|)
         times log2(e) at <= 2^15 -- both inside the f16 range with their low halves out of the
         subnormals."""
-        torch, O = self.torch, _ops.backend()
-        n = self.n_segs
+        torch, O, t_bound = self.torch, _ops.backend(), self._t_bound
         self.split_t_scale, self.split_descale, self.split_bias_col = [], [], []
         self.seg_split, self.split_segments = [], []
-
-        def pow2_below(limit, value):
-            if not (value > 0.0) or not np.isfinite(value):
-                return 0
-            return int(np.clip(np.floor(np.log2(limit / value)), -40, 40))
 
         with self._ctx():
             for i, sg in enumerate(self.segments if self.stationary_ok else []):
@@ -323,7 +334,7 @@ class DeviceModel:
                 tb = 1.0 if t_bound is None else float(t_bound[sg["t_off"]:sg["t_off"] + k].max())
                 if bias_col >= 0:
                     tb = max(tb, 1.0)
-                eT = pow2_below(2.0 ** 15, tb * 1.4426950408889634)
+                eT = pow2_below(2.0 ** 15, tb * LOG2E)
                 dst = torch.zeros((max(nv, 1), k16), dtype=torch.float32, device=self.device)
                 if nv:
                     O.pack_split_f16(self.seg_B[i], 0, nv, k, sg["ldb"], float(2.0 ** eB), dst, 0, k16)
@@ -382,8 +393,6 @@ class DeviceModel:
                 del wt8
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
-            self._t_bound, self._pow2_below = t_bound, pow2_below
-            self._extra_probe_words = []
             self._select_mixed_format()
 
     def _select_mixed_format(self):
@@ -392,27 +401,15 @@ class DeviceModel:
         a model it does not pass on -- or a shape it does not host -- gets the int8 planes (and their two-format launches)
         exactly as before, then split rows.  JLM_LSE_MX6=0: int8 planes only.  Called at load and once more by the decoder with
         probe rows taken from real decodes (``calibrate_on_paths``)."""
-        t_bound, pow2_below = self._t_bound, self._pow2_below
-        self._decode_model = None
-        self.lse_fixed_ref = 0
-        self.mixed_calib = None
-        self.mixed_fmt, mx6_calib = None, None
+        self.mixed, self.mixed_calib, mx6_calib = None, None, None
         formats = (["mx6"] if os.environ.get("JLM_LSE_MX6", "1") != "0" else []) + ["int8"]
         with self._ctx():
             for fmt in formats:
-                if self.stationary_ok:
-                    self._build_mixed(t_bound, pow2_below, fmt)
-                elif fmt == "int8" and self.mode == "untied":
-                    self._build_mixed_untied(pow2_below)
-                else:
-                    continue
-                self.mixed_fmt = fmt if self.mixed_idx else None
-                self._calibrate_mixed()
+                self.mixed, self.mixed_calib = self._calibrate_mixed(self._build_mixed(fmt))
                 if fmt == "mx6":
                     mx6_calib = self.mixed_calib
-                if self.mixed_idx:
+                if self.mixed is not None:
                     break
-        self.mixed_fmt = self.mixed_fmt if self.mixed_idx else None
         if self.mixed_calib is not None:
             self.mixed_calib["fmt"] = self.mixed_fmt
             if mx6_calib is not None and mx6_calib is not self.mixed_calib:
@@ -425,8 +422,8 @@ class DeviceModel:
         lattice search actually visits, on top of the seeded word draws of ``CALIB_PROBES``.  The format cascade runs again with that
         probe among the others (the worst probe decides); returns the new ``mixed_calib``."""
         paths = [list(map(int, p)) for p in paths if len(p)]
-        if not paths or not getattr(self, "split_lstm", False) or not hasattr(self, "_pow2_below"):
-            return getattr(self, "mixed_calib", None)
+        if not paths or not self.split_lstm:
+            return self.mixed_calib
         R = self.CALIB_ROWS
         S = int(min(max_steps, max(len(p) for p in paths) + 1))
         w = np.zeros((S, R), dtype=np.int32)
@@ -452,17 +449,84 @@ class DeviceModel:
     # acceptance of a form: rms <= limit AND no probe row above CALIB_MAX_FACTOR x limit (Gaussian-like error: max / rms = 4 .. 5 over 256 rows)
     CALIB_MAX_FACTOR = 8.0
 
-    def _head_split_possible(self):
+    def _head_split_possible(self, rows):
         """the first segment's head can stay on split rows: every segment on mixed rows in a shape the two-format launch hosts
         (csrc/jlm_split.hip jlm_vocab_lse_hybrid: k + 2 <= 208 with bias columns), the first one the model's first words"""
         if self.mode == "untied" or self.split_array is None:
             return False
-        if list(self.mixed_idx) != list(range(self.n_segs)) or not self.mixed_segments or self.mixed_segments[0]["v_start"] != 0:
+        segs = [s.seg for s in rows.segs]
+        if rows.idx != list(range(self.n_segs)) or segs[0]["v_start"] != 0:
             return False
-        return all(tuple(x) in self.MIXED_SHAPES for x in (((sg["k"] + 2 + 31) // 32, (sg["k"] + 2 + 15) // 16) for sg in self.mixed_segments)) \
-            and all(sg["ldb"] == 32 * ((sg["k"] + 2 + 31) // 32) for sg in self.mixed_segments)
+        return all(mixed_shape(sg["k"]) in self.MIXED_SHAPES and sg["ldb"] == 32 * mixed_shape(sg["k"])[0] for sg in segs)
 
-    def _calibrate_mixed(self):
+    def _build_probes(self):
+        """Round 6 (verdict item 3): the contexts a trained model sees are not uniform-random words three steps from the zero state.  Every
+        form is measured on CALIB_PROBES -- (kind, steps, seed): uniform word ids (round 4's probe) and ids drawn ~ 1 / rank (the lexicon
+        is sorted by frequency, reference data.py:33,44: frequent words give the state its usual size) over a longer chain, two seeds
+        each -- and is accepted only if it passes on ALL of them: the figure recorded is the WORST probe's."""
+        R = self.CALIB_ROWS
+        i32 = lambda a: self.torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+        def probe(kind, S, seed, words):
+            G = (S + 1) * R
+            w = np.zeros(G, dtype=np.int32)          # (the first R rows are the zero state)
+            w[R:] = words
+            return dict(kind=kind, steps=S, seed=seed, G=G, rowlist=i32(np.arange(G)), prev=i32(np.arange(G) - R), word=i32(w), lse0=None)
+        probes = []
+        for kind, S, seed in self.CALIB_PROBES:
+            rng = np.random.RandomState(self.CALIB_SEED + seed)
+            if kind == "zipf":       # P(rank r) ~ 1 / (r + 1): inverse transform of the log-uniform density
+                words = np.minimum((np.exp(rng.random_sample(S * R) * np.log(self.V + 1.0)) - 1.0).astype(np.int64), self.V - 1)
+            else:
+                words = rng.randint(0, self.V, size=S * R)
+            probes.append(probe(kind, S, seed, words))
+        for j, pw in enumerate(self._extra_probe_words):      # [steps, rows] word ids from real decodes (calibrate_on_paths)
+            probes.append(probe("paths", int(pw.shape[0]), j, np.asarray(pw, dtype=np.int32).reshape(-1)))
+        return probes
+
+    def _probe_lse(self, rows, pr, form):
+        """log-normalisers of a probe's rows in form 0 (split rows) or 1 (the mixed rows ``rows``), or a reason they cannot be had"""
+        torch, dev, R, H, G = self.torch, self.device, self.CALIB_ROWS, self.H, pr["G"]
+        max_parts = max(128, (self.V + 127) // 128 + 1)      # (form 0 of an untied model: one slice per 128-word tile)
+        dm = self.decode_model(rows)
+        with self._ctx():
+            h = torch.zeros((G, H), dtype=torch.float32, device=dev)
+            c = torch.zeros((G, H), dtype=torch.float32, device=dev)
+            T = torch.zeros((G, self.ldt), dtype=torch.float32, device=dev)
+            Tm = torch.zeros(((R + 31) // 32 * 32, rows.ld_tm), dtype=torch.float32, device=dev)
+            part = torch.zeros((max_parts, R, 2), dtype=torch.float32, device=dev)
+            try:
+                n = int(_ops.backend().lse_probe(dm, pr["rowlist"], pr["prev"], pr["word"], pr["steps"], R, h, c, T, Tm, rows.ld_tm, form,
+                                                 part, max_parts))
+            except (RuntimeError, _lib.JlmHipError) as e:        # a launcher refused (stride check, LDS grant, ...): not a load failure
+                return "the load-time probe failed (%s): split rows" % str(e).splitlines()[0][:160]
+            if n < 1:
+                return "the load-time probe does not cover this model (code %d): split rows" % n
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            p = part[:n].double().cpu().numpy()
+        with np.errstate(divide="ignore"):
+            v = np.where(p[:, :, 1] > 0, p[:, :, 0] + np.log(p[:, :, 1]), -np.inf)
+        mx = v.max(axis=0)
+        return mx + np.log(np.exp(v - mx).sum(axis=0))
+
+    def _measure(self, rows, probes):
+        """(worst rms, worst max, per-probe list) of the mixed rows ``rows`` against split rows, over every probe -- or a reason"""
+        per = []
+        for pr in probes:
+            if pr["lse0"] is None:
+                r0 = self._probe_lse(rows, pr, 0)
+                if isinstance(r0, str):
+                    return r0
+                pr["lse0"] = r0
+            r = self._probe_lse(rows, pr, 1)
+            if isinstance(r, str):
+                return r
+            d = r - pr["lse0"]
+            per.append(dict(kind=pr["kind"], steps=pr["steps"], seed=pr["seed"], rms=float(np.sqrt(np.mean(d ** 2))), max=float(np.abs(d).max())))
+        return max(x["rms"] for x in per), max(x["max"] for x in per), per
+
+    def _calibrate_mixed(self, rows):
         """Load-time calibration of the mixed rows ON THIS MODEL (round 4).  The int8 cross terms are good to ~2^-20 of |t||b| per
         product (three f16 passes: 2^-23), so the error of the log-normaliser grows with the model's logit range and with how peaked
         its next-word distributions are -- neither of which the blocks' spread (``_build_mixed``) sees: output embeddings x 20
@@ -473,212 +537,97 @@ class DeviceModel:
         The root-mean-square difference of the two log-normalisers is the per-frame error the mixed rows add to a path score (the
         split form's own error is 10x below it wherever it matters); above ``JLM_MIXED_MAX_LSE_RMS`` the model stays on split
         rows.  Measured on the trained-model-like fixtures (numpy emulation and GPU): the worst path score of 20-kana sentences moves
-        by ~10 x this rms, so the default 1.0e-6 keeps scores inside 1e-5, half the test suite's tolerance.  ``mixed_calib`` records the measurement either way (bench.py prints it)."""
-        self.mixed_calib = None
-        self.mixed_head_split = []
-        if not getattr(self, "mixed_idx", None):
-            return
+        by ~10 x this rms, so the default 1.0e-6 keeps scores inside 1e-5, half the test suite's tolerance.
+        ``rows``: the candidate (None: nothing to calibrate).  -> (the rows the model keeps, or None for split rows; ``mixed_calib``, which
+        records the measurement either way -- bench.py prints it -- or None when nothing was measured)."""
         limit = float(os.environ.get("JLM_MIXED_MAX_LSE_RMS", "1.5e-6"))
-        if not (limit > 0.0):
-            return
-
-        def drop(reason, **kw):
-            """the model stays on split rows; mixed_calib says why (bench.py prints it)"""
-            self.mixed_calib = dict(kept=False, limit=limit, reason=reason, **kw)
-            self.mixed_idx, self.seg_mixed, self.mixed_segments = [], [], []
-            self.mixed_t_scale, self.mixed_descale, self.mixed_s8 = [], [], []
-            self.ld_tm, self.b2_log2 = 0, None
-            self.mixed_head_split = []
-            self.lse_fixed_ref = 0
-            self._decode_model = None
-
+        if rows is None or not (limit > 0.0):
+            return rows, None
+        # the model stays on split rows; mixed_calib says why
+        refused = lambda reason, **kw: (None, dict(kept=False, limit=limit, reason=reason, **kw))
         # (round 5, ADVICE) a model the probe cannot run on -- no split LSTM step, no projection panel -- must not keep the int8
         # planes on the spread gate alone (that gate misses peaked logits): it stays on split rows
-        untied = self.mode == "untied"
-        if not self.split_lstm or (untied and self.um_split is None) or (not untied and self.pmt_split is None):
-            return drop("the load-time probe does not cover this model (no split LSTM step / projection panel): split rows")
-        torch, O = self.torch, _ops.backend()
-        R, H = self.CALIB_ROWS, self.H
-        dev = self.device
-        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        max_parts = max(128, (self.V + 127) // 128 + 1)      # (form 0 of an untied model: one slice per 128-word tile)
-
-        # Round 6 (verdict item 3): the contexts a trained model sees are not uniform-random words three steps from the zero state.  Every
-        # form is measured on CALIB_PROBES -- (kind, steps, seed): uniform word ids (round 4's probe) and ids drawn ~ 1 / rank (the lexicon
-        # is sorted by frequency, reference data.py:33,44: frequent words give the state its usual size) over a longer chain, two seeds
-        # each -- and is accepted only if it passes on ALL of them: the figure recorded is the WORST probe's.
-        probes = []
-        for kind, S, seed in self.CALIB_PROBES:
-            rng = np.random.RandomState(self.CALIB_SEED + seed)
-            G = (S + 1) * R
-            w = np.zeros(G, dtype=np.int32)
-            if kind == "zipf":       # P(rank r) ~ 1 / (r + 1): inverse transform of the log-uniform density
-                w[R:] = np.minimum((np.exp(rng.random_sample(S * R) * np.log(self.V + 1.0)) - 1.0).astype(np.int64), self.V - 1)
-            else:
-                w[R:] = rng.randint(0, self.V, size=S * R)
-            probes.append(dict(kind=kind, steps=S, seed=seed, G=G, rowlist=i32(np.arange(G)), prev=i32(np.arange(G) - R), word=i32(w), lse0=None))
-        for j, pw in enumerate(getattr(self, "_extra_probe_words", None) or []):      # [steps, rows] word ids from real decodes (calibrate_on_paths)
-            S = int(pw.shape[0])
-            G = (S + 1) * R
-            w = np.zeros(G, dtype=np.int32)
-            w[R:] = np.asarray(pw, dtype=np.int32).reshape(-1)
-            probes.append(dict(kind="paths", steps=S, seed=j, G=G, rowlist=i32(np.arange(G)), prev=i32(np.arange(G) - R), word=i32(w), lse0=None))
-
-        def probe(form, pr):
-            """log-normalisers of a probe's rows in the given form (the model object as it stands), or a reason they cannot be had"""
-            dm = self.decode_model()
-            G = pr["G"]
-            with self._ctx():
-                h = torch.zeros((G, H), dtype=torch.float32, device=dev)
-                c = torch.zeros((G, H), dtype=torch.float32, device=dev)
-                T = torch.zeros((G, self.ldt), dtype=torch.float32, device=dev)
-                Tm = torch.zeros(((R + 31) // 32 * 32, self.ld_tm), dtype=torch.float32, device=dev)
-                part = torch.zeros((max_parts, R, 2), dtype=torch.float32, device=dev)
-                try:
-                    n = int(O.lse_probe(dm, pr["rowlist"], pr["prev"], pr["word"], pr["steps"], R, h, c, T, Tm, self.ld_tm, form, part, max_parts))
-                except (RuntimeError, _lib.JlmHipError) as e:        # a launcher refused (stride check, LDS grant, ...): not a load failure
-                    return "the load-time probe failed (%s): split rows" % str(e).splitlines()[0][:160]
-                if n < 1:
-                    return "the load-time probe does not cover this model (code %d): split rows" % n
-                if dev.type == "cuda":
-                    torch.cuda.synchronize(dev)
-                p = part[:n].double().cpu().numpy()
-            with np.errstate(divide="ignore"):
-                v = np.where(p[:, :, 1] > 0, p[:, :, 0] + np.log(p[:, :, 1]), -np.inf)
-            mx = v.max(axis=0)
-            return mx + np.log(np.exp(v - mx).sum(axis=0))
-
-        def measure():
-            """(worst rms, worst max, per-probe list) of form 1 as the model stands against form 0, over every probe -- or a reason"""
-            per = []
-            for pr in probes:
-                if pr["lse0"] is None:
-                    r0 = probe(0, pr)
-                    if isinstance(r0, str):
-                        return r0
-                    pr["lse0"] = r0
-                r = probe(1, pr)
-                if isinstance(r, str):
-                    return r
-                d = r - pr["lse0"]
-                per.append(dict(kind=pr["kind"], steps=pr["steps"], seed=pr["seed"], rms=float(np.sqrt(np.mean(d ** 2))), max=float(np.abs(d).max())))
-            return max(x["rms"] for x in per), max(x["max"] for x in per), per
-
+        if not self.split_lstm or (self.um_split if self.mode == "untied" else self.pmt_split) is None:
+            return refused("the load-time probe does not cover this model (no split LSTM step / projection panel): split rows")
+        probes = self._build_probes()
+        measure = lambda cand: self._measure(cand, probes)
         ok = lambda rms, worst, f=1.0: bool(np.isfinite(rms) and rms <= f * limit and worst <= self.CALIB_MAX_FACTOR * f * limit)
-        r = measure()
+        r = measure(rows)
         if isinstance(r, str):
-            return drop(r)
+            return refused(r)
         rms, worst, per = r
-        keep = ok(rms, worst)
         lse0_all = np.concatenate([pr["lse0"] for pr in probes])
-        self.mixed_calib = dict(rows=R, steps=[pr["steps"] for pr in probes], lse_rms_diff=rms, lse_max_diff=worst, limit=limit, kept=keep,
-                                lse_mean=float(np.mean(lse0_all)), probes=per, margin=(limit / rms if rms > 0 else float("inf")))
-        # Round 5 (ABI 10): above the limit, keep the words that carry the error on split rows and the rest on mixed rows
-        # (jlm_vocab_lse_hybrid).  The error of a log-normaliser is the probability-weighted mean of its words' logit errors, and a
-        # trained model's mass sits on the frequent words -- the low ids (the lexicon is sorted by frequency, decoder.py:54-77; D-softmax's
-        # segments are cut along it).  Measured on logits of +-20 (peaked20-vtable): the first segment's 12 000 words carry 0.935 of the
-        # mass and all of the 3.1e-6 rms; the other 38 000 add 2e-8.  Two forms, tried in order of cost:
-        #   a HEAD of the first segment (HEAD_SPLITS words; none by default -- see there) on split rows, accepted at half the limit;
-        #   the whole first segment on split rows, the others mixed -- accepted at the limit like any other form.
-        if not keep and np.isfinite(rms) and self._head_split_possible() and getattr(self, "mixed_fmt", None) != "mx6":
-            full = dict(lse_rms_diff_all_mixed=rms, lse_max_diff_all_mixed=worst)
-            for cut in self.HEAD_SPLITS:
-                if cut >= self.mixed_segments[0]["v_end"] - self.mixed_segments[0]["v_start"]:
-                    break
-                self.mixed_head_split = [cut] + [0] * (len(self.mixed_idx) - 1)
-                self._decode_model = None
-                r = measure()
-                if isinstance(r, str):
+        seen = dict(rows=self.CALIB_ROWS, steps=[pr["steps"] for pr in probes], lse_mean=float(np.mean(lse0_all)))
+        calib = dict(seen, lse_rms_diff=rms, lse_max_diff=worst, limit=limit, kept=ok(rms, worst), probes=per,
+                     margin=(limit / rms if rms > 0 else float("inf")))
+        if not calib["kept"] and np.isfinite(rms) and rows.fmt != "mx6" and self._head_split_possible(rows):
+            rows, rms, worst, per = self._mass_on_split_rows(rows, measure, ok, calib)
+        if calib["kept"]:
+            rows = self._try_fixed_ref(rows, measure, ok, calib, float(np.abs(lse0_all).max()) * LOG2E)
+            return rows, calib
+        return refused("log-normaliser rms difference above the limit", lse_rms_diff=rms, lse_max_diff=worst, probes=per,
+                       margin=limit / max(rms, 1e-300), **seen)
+
+    def _mass_on_split_rows(self, rows, measure, ok, calib):
+        """Round 5 (ABI 10): above the limit, keep the words that carry the error on split rows and the rest on mixed rows
+        (jlm_vocab_lse_hybrid).  The error of a log-normaliser is the probability-weighted mean of its words' logit errors, and a
+        trained model's mass sits on the frequent words -- the low ids (the lexicon is sorted by frequency, decoder.py:54-77; D-softmax's
+        segments are cut along it).  Measured on logits of +-20 (peaked20-vtable): the first segment's 12 000 words carry 0.935 of the
+        mass and all of the 3.1e-6 rms; the other 38 000 add 2e-8.  Two forms, tried in order of cost:
+          a HEAD of the first segment (HEAD_SPLITS words; none by default -- see there) on split rows, accepted at half the limit;
+          the whole first segment on split rows, the others mixed -- accepted at the limit like any other form.
+        -> (the form that passed -- ``calib`` then says kept -- or ``rows``, the all-mixed figures, the probes' last figures)"""
+        limit, full_rms, full_worst, per = calib["limit"], calib["lse_rms_diff"], calib["lse_max_diff"], calib["probes"]
+        nv0 = rows.segs[0].seg["v_end"] - rows.segs[0].seg["v_start"]
+        heads = [(rows.with_head(cut), 0.5, dict(head_split=cut)) for cut in itertools.takewhile(lambda c: c < nv0, self.HEAD_SPLITS)]
+        whole = [(rows.without_first_segment(), 1.0, dict(head_split=nv0, split_segments=[0]))] if len(rows.segs) > 1 else []
+        for forms in (heads, whole):
+            for cand, f, note in forms:
+                r = measure(cand)
+                if isinstance(r, str):            # (a head the launch refuses: the longer ones are not tried)
                     break
                 rms, worst, per = r
-                if ok(rms, worst, 0.5):
-                    keep = True
-                    self.mixed_calib.update(full, lse_rms_diff=rms, lse_max_diff=worst, kept=True, head_split=cut, probes=per, margin=limit / max(rms, 1e-300))
-                    break
-            if not keep:
-                self.mixed_head_split, self._decode_model = [], None
-                if len(self.mixed_idx) > 1:
-                    saved = (list(self.mixed_idx), list(self.seg_mixed), list(self.mixed_segments), list(self.mixed_t_scale),
-                             list(self.mixed_descale), list(self.mixed_s8), self.ld_tm)
-                    nv0 = self.mixed_segments[0]["v_end"] - self.mixed_segments[0]["v_start"]
-                    for lst in (self.mixed_idx, self.seg_mixed, self.mixed_segments, self.mixed_t_scale, self.mixed_descale, self.mixed_s8):
-                        del lst[0]
-                    self.ld_tm = (sum(msg["ldb"] * 4 for msg in self.mixed_segments) + 4 * 8 + 15) // 16 * 4
-                    r = measure()
-                    if not isinstance(r, str):
-                        rms, worst, per = r
-                        if ok(rms, worst):
-                            keep = True
-                            self.mixed_calib.update(full, lse_rms_diff=rms, lse_max_diff=worst, kept=True, head_split=nv0,
-                                                    split_segments=[0], probes=per, margin=limit / max(rms, 1e-300))
-                    if not keep:
-                        (self.mixed_idx, self.seg_mixed, self.mixed_segments, self.mixed_t_scale, self.mixed_descale, self.mixed_s8,
-                         self.ld_tm) = saved
-                        self._decode_model = None
-                if not keep:
-                    rms, worst = full["lse_rms_diff_all_mixed"], full["lse_max_diff_all_mixed"]
-        # Round 5: the normaliser without a running maximum (jlm_vocab_lse_mixed_fr: sum 2^y against the reference 0, three VALU
-        # instructions per logit less; the wide kernel's tied k = 256 and k = 512 forms) is safe while a row's largest base-2 logit stays
-        # within +-100 (f32 range over 2^16 words).  log Z bounds the largest logit from above and, minus log V, from below: a model whose
-        # probe rows keep |log Z| log2 e under FIXED_REF_MAX_BITS = 40 (28 nats; Gaussian fixtures: 16, logits of +-20: ~30) has 60 bits to
-        # spare either way.  A row that leaves the range comes back as s = 0 or inf and DecodeEngine.collect raises.  JLM_MX_FIXREF=0: off.
-        bits = float(np.abs(lse0_all).max()) * 1.4426950408889634
-        self.lse_fixed_ref = int(keep and np.isfinite(bits) and bits <= self.FIXED_REF_MAX_BITS and os.environ.get("JLM_MX_FIXREF", "1") != "0"
-                                 and len(self.mixed_idx) == self.n_segs and not any(self.mixed_head_split))      # (jlm_vocab_lse_mixed_fr: every segment on mixed rows)
-        if self.lse_fixed_ref:
+                if ok(rms, worst, f):
+                    calib.update(note, lse_rms_diff_all_mixed=full_rms, lse_max_diff_all_mixed=full_worst, lse_rms_diff=rms,
+                                 lse_max_diff=worst, kept=True, probes=per, margin=limit / max(rms, 1e-300))
+                    return cand, rms, worst, per
+        return rows, full_rms, full_worst, per
+
+    def _try_fixed_ref(self, rows, measure, ok, calib, bits):
+        """Round 5: the normaliser without a running maximum (jlm_vocab_lse_mixed_fr: sum 2^y against the reference 0, three VALU
+        instructions per logit less; the wide kernel's tied k = 256 and k = 512 forms) is safe while a row's largest base-2 logit stays
+        within +-100 (f32 range over 2^16 words).  log Z bounds the largest logit from above and, minus log V, from below: a model whose
+        probe rows keep |log Z| log2 e (``bits``) under FIXED_REF_MAX_BITS = 40 (28 nats; Gaussian fixtures: 16, logits of +-20: ~30) has
+        60 bits to spare either way.  A row that leaves the range comes back as s = 0 or inf and DecodeEngine.collect raises.
+        JLM_MX_FIXREF=0: off.  -> ``rows`` with the flag where the form may run"""
+        if (np.isfinite(bits) and bits <= self.FIXED_REF_MAX_BITS and os.environ.get("JLM_MX_FIXREF", "1") != "0"
+                and len(rows.segs) == self.n_segs and not any(rows.head_split)):      # (jlm_vocab_lse_mixed_fr: every segment on mixed rows)
             # (round-5 advice) the bound alone enabled the form; now the FORM ITSELF runs on the probe rows (jlm_lse_probe launches
             # jlm_vocab_lse_mixed_fr when the model object carries the flag) and must reproduce form 0 like the running-maximum form did
-            self._decode_model = None            # (the probes above ran on a model object built without the flag)
-            r = measure()
+            cand = rows.with_fixed_ref(True)
+            r = measure(cand)
             fr_rms, fr_worst = (float("inf"), float("inf")) if isinstance(r, str) else r[:2]
-            self.mixed_calib.update(fixed_ref_lse_rms_diff=fr_rms, fixed_ref_lse_max_diff=fr_worst)
-            if not ok(fr_rms, fr_worst):
-                self.lse_fixed_ref = 0
-            self._decode_model = None
-        self.mixed_calib.update(lse_abs_max_bits=bits, fixed_ref=bool(self.lse_fixed_ref))
-        if not keep:
-            drop("log-normaliser rms difference above the limit", rows=R, steps=[pr["steps"] for pr in probes], lse_rms_diff=rms, lse_max_diff=worst,
-                 lse_mean=float(np.mean(lse0_all)), probes=per, margin=limit / max(rms, 1e-300))
+            calib.update(fixed_ref_lse_rms_diff=fr_rms, fixed_ref_lse_max_diff=fr_worst)
+            if ok(fr_rms, fr_worst):
+                rows = cand
+        calib.update(lse_abs_max_bits=bits, fixed_ref=rows.fixed_ref)
+        return rows
 
-    # (k + 2 -> 32-k blocks, 16-k f16 steps) with inlined mixed-row bodies: k = 200, 100, 50 (csrc/jlm_mixed.hip MX_KERNEL_DSOFTMAX; the
-    # first two also in csrc/jlm_split.hip vocab_lse_hybrid_kernel, beside split-row bodies for other short segments)
-    MIXED_SHAPES = ((7, 13), (4, 7), (2, 4))
+    MIXED_SHAPES = MIXED_SHAPES          # (rowformats; here for callers that host other shapes)
 
-    def _build_mixed(self, t_bound, pow2_below, fmt="int8"):
-        """Mixed rows (f16 hi + int8 cross-term planes, include/jlm_hip.h ABI 7) of the segments with a hosted shape (k = 200, 100, 50
-        of BASELINE configs[1]): all of them -> jlm_vocab_lse_mixed; the other segments must be ones the hybrid kernel runs on
-        split rows (k <= 64 with a bias column), else the model stays on split rows alone.  JLM_LSE_MIXED=0
-        switches the form off.  Scales: 2^eB puts max(|B|, |b2| log2 e) at <= 2^14 (the bias rides in two f16 columns), the int8
-        scale s8 is the power of two at or above max|f16(B 2^eB)| / 127, 2^eT as for the split rows."""
-        self.mixed_idx, self.seg_mixed, self.mixed_segments = [], [], []
-        self.mixed_t_scale, self.mixed_descale, self.mixed_s8 = [], [], []
-        self.ld_tm = 0
+    def _build_mixed(self, fmt):
+        """Mixed rows (f16 hi + int8 or FP6 cross-term planes, include/jlm_hip.h ABI 7 / 11) of the segments rowformats.mixed_layout
+        gives them to: the hosted shapes (k = 200, 100, 50 of BASELINE configs[1]) -> jlm_vocab_lse_mixed, beside split-row segments
+        -> the hybrid kernel; contractions that fill their last block (tied k = 256; round 5: an untied model's UM^T [V, H = 512],
+        whose hypothesis side is the state itself, model.py:189-191) carry no bias columns.  -> rowformats.MixedRows, or None: split
+        rows.  JLM_LSE_MIXED=0 switches the form off.  Scales: rowformats.mixed_exponents, plane_scale."""
         if os.environ.get("JLM_LSE_MIXED", "1") == "0" or self.self_norm:
-            return
-        torch, O = self.torch, _ops.backend()
-        take, xbias = [], set()
-        for i, sg in enumerate(self.segments):
-            nv, k = sg["v_end"] - sg["v_start"], sg["k"]
-            if nv > 0 and ((k + 2 + 31) // 32, (k + 2 + 15) // 16) in self.MIXED_SHAPES:
-                take.append(i)
-            elif nv > 0 and k % 64 == 0 and k <= 256:
-                # a contraction that fills its last block (tied k = 256): no columns left for the bias -- rows of k / 32 blocks, the
-                # biases (x log2 e) go to the kernel separately (jlm_vocab_lse_mixed, bias2)
-                take.append(i)
-                xbias.add(i)
-            elif not (nv > 0 and k <= 64 and self.split_bias_col[i] == k):
-                return
-        if not take or (xbias and len(xbias) != len(self.segments)):      # (one bias form per launch)
-            return
-        # the packer of the hypothesis rows holds a row's blocks in one wave: 32 blocks per row at most (jlm_mixed_t_stride: -2)
-        if sum((self.segments[i]["k"] // 32) if i in xbias else (self.segments[i]["k"] + 2 + 31) // 32 for i in take) > 32:
-            return
-        # the hybrid launch (mixed + split segments) hosts the mixed bodies with bias columns (k = 200, 100, 50): any other mix stays on split rows
-        if len(take) != len(self.segments) and any(((self.segments[i]["k"] + 2 + 31) // 32, (self.segments[i]["k"] + 2 + 15) // 16)
-                                                   not in self.MIXED_SHAPES for i in take):
-            return
-        if fmt == "mx6" and len(take) != len(self.segments):        # (the two-format launch hosts int8 planes only)
-            return
+            return None
+        layout = mixed_layout(self.segments, fmt, self.split_bias_col, self.mode == "untied", self.MIXED_SHAPES)
+        if layout is None:
+            return None
+        take, xbias = layout
+        torch, O, t_bound = self.torch, _ops.backend(), self._t_bound
         # The int8 planes carry ONE scale per segment (the power of two at or above max|hi| / 127): the quantisation step of a word's hi8
         # is max|B| / 254 whatever the word's own size, so the error grows with the block's spread max|B| / rms B: Gaussian-like blocks
         # (spread ~5) 8e-6 of the row's logit scale and 3e-7 on the log-sum-exp; 0.1 % entries at 30 sigma (spread 80) 1e-4 -- the
@@ -686,129 +635,73 @@ class DeviceModel:
         # in tests/fake_hip.py).  Blocks with heavy tails stay on split rows, whose error does not depend on the distribution.
         # (mx6 planes carry a scale per 32 k-values of every word: no spread gate -- heavy-tailed blocks measure 6-10 x BETTER than on
         #  int8 planes, tests/test_mx6_emulation.py; the load-time calibration decides)
-        limit = float(os.environ.get("JLM_MIXED_MAX_SPREAD", "8"))
         self.mixed_spread = []
         for i in take:
             blk = self.seg_B[i]
             rms = float(blk.pow(2).mean().sqrt().item())
             self.mixed_spread.append(float(blk.abs().max().item()) / rms if rms > 0.0 else float("inf"))
-        if fmt != "mx6" and max(self.mixed_spread) > limit:
-            return
-        LOG2E = 1.4426950408889634
+        if fmt != "mx6" and max(self.mixed_spread) > float(os.environ.get("JLM_MIXED_MAX_SPREAD", "8")):
+            return None
+        segs = []
         for i in take:
-            sg = self.segments[i]
+            sg, blk = self.segments[i], self.seg_B[i]
             nv, k = sg["v_end"] - sg["v_start"], sg["k"]
-            nb = k // 32 if i in xbias else (k + 2 + 31) // 32
-            bmax = float(self.seg_B[i].abs().max().item())
-            if i not in xbias:
-                bmax = max(bmax, float(self.b2[sg["v_start"]:sg["v_end"]].abs().max().item()) * LOG2E)
-            eB = pow2_below(2.0 ** 14, bmax)
-            hmax = float((self.seg_B[i] * float(2.0 ** eB)).to(torch.float16).to(torch.float32).abs().max().item())
-            s8 = 0.0 if fmt == "mx6" else 2.0 ** int(np.ceil(np.log2(max(hmax, 2.0 ** -100) / 127.0)))      # (ABI 11: s8 = 0 selects the FP6 planes)
+            nb = k // 32 if i in xbias else mixed_shape(k)[0]
+            bmax = float(blk.abs().max().item())
+            b2max = None if i in xbias else float(self.b2[sg["v_start"]:sg["v_end"]].abs().max().item())
             tb = 1.0 if t_bound is None else max(float(t_bound[sg["t_off"]:sg["t_off"] + k].max()), 1.0)
-            eT = pow2_below(2.0 ** 15, tb * LOG2E)
-            if fmt == "mx6":
-                # mx6 operands want eT + eB = 0: the accumulators are then base-2 logits themselves (descale = 1) and the fold needs no
-                # multiply -- and no running maximum where the loader allows the fixed reference (exp2 + add per logit).  The FP6 planes
-                # carry their own block scales, so only the f16 hi planes feel the choice: any exponent that keeps an operand's largest
-                # value between 2^-3 and the top of the f16 range leaves its typical values normal (what falls into the subnormals is
-                # good to 2^-25 absolute, below the FP6 planes' own step).  Balanced: largest |B| 2^e = largest |T| log2 e 2^-e.
-                lo = max(eB - 17, -eT)
-                hi = min(eB, 17 - eT, 13)                        # (new eT = -e >= -13: the bias constant 2^(eT - 11) must stay representable)
-                if lo <= hi:
-                    bal = int(round(0.5 * (np.log2(max(tb * LOG2E, 1e-30)) - np.log2(max(bmax, 1e-30)))))
-                    eB = int(min(max(bal, lo), hi))
-                    eT = -eB
+            eB, eT = mixed_exponents(fmt, bmax, b2max, tb)
+            s8 = plane_scale(fmt, float((blk * float(2.0 ** eB)).to(torch.float16).to(torch.float32).abs().max().item()))
             dst = torch.zeros((nv, 32 * nb), dtype=torch.float32, device=self.device)
-            O.pack_mixed(self.seg_B[i], 0, nv, k, sg["ldb"], self.b2, sg["v_start"], float(2.0 ** eB), float(2.0 ** eB * LOG2E), float(s8),
+            O.pack_mixed(blk, 0, nv, k, sg["ldb"], self.b2, sg["v_start"], float(2.0 ** eB), float(2.0 ** eB * LOG2E), float(s8),
                          dst, 32 * nb)
-            self.mixed_idx.append(i)
-            self.seg_mixed.append(dst)
-            self.mixed_segments.append(dict(v_start=sg["v_start"], v_end=sg["v_end"], k=k, t_off=sg["t_off"], ldb=32 * nb))
-            self.mixed_t_scale.append(2.0 ** eT)
-            self.mixed_descale.append(2.0 ** -(eT + eB))
-            self.mixed_s8.append(s8)
-        self.b2_log2 = (self.b2 * LOG2E).contiguous() if xbias else None
-        # stride of the packed hypothesis rows (jlm_mixed_t_stride): the segments' 128-byte blocks + JLM_MAX_SEGMENTS scale floats
-        nbytes = sum(msg["ldb"] * 4 for msg in self.mixed_segments) + 4 * 8
-        self.ld_tm = (nbytes + 15) // 16 * 4
-
-    def _build_mixed_untied(self, pow2_below):
-        """Round 5: an untied model's vocabulary matrix UM^T [V, H] as mixed rows when H = 512 -- sixteen 32-k blocks per word, no
-        bias columns (the biases x log2 e go to the kernel separately) -- for jlm_vocab_lse_mixed's wide one-row-set form
-        (csrc/jlm_mixed_w.hip: the hypothesis rows' operands fill a wave's 256 accumulation registers).  The hypothesis side is
-        the state itself (model.py:189-191; |h| < 1: 2^eT = 2^14).  Same gates as ``_build_mixed``: JLM_LSE_MIXED=0, the blocks'
-        spread, then the load-time calibration (``_calibrate_mixed``)."""
-        if os.environ.get("JLM_LSE_MIXED", "1") == "0" or self.self_norm or self.H != 512 or self.n_segs != 1:
-            return
-        torch, O = self.torch, _ops.backend()
-        sg, blk = self.segments[0], self.seg_B[0]
-        nv, k = sg["v_end"] - sg["v_start"], sg["k"]
-        if k != self.H or nv <= 0 or nv * 16 * 128 >= (1 << 31):
-            return
-        rms = float(blk.pow(2).mean().sqrt().item())
-        self.mixed_spread = [float(blk.abs().max().item()) / rms if rms > 0.0 else float("inf")]
-        if self.mixed_spread[0] > float(os.environ.get("JLM_MIXED_MAX_SPREAD", "8")):
-            return
-        LOG2E = 1.4426950408889634
-        nb = k // 32
-        eB = pow2_below(2.0 ** 14, float(blk.abs().max().item()))
-        hmax = float((blk * float(2.0 ** eB)).to(torch.float16).to(torch.float32).abs().max().item())
-        s8 = 2.0 ** int(np.ceil(np.log2(max(hmax, 2.0 ** -100) / 127.0)))
-        eT = pow2_below(2.0 ** 15, LOG2E)
-        dst = torch.zeros((nv, 32 * nb), dtype=torch.float32, device=self.device)
-        O.pack_mixed(blk, 0, nv, k, sg["ldb"], self.b2, sg["v_start"], float(2.0 ** eB), float(2.0 ** eB * LOG2E), float(s8), dst, 32 * nb)
-        self.mixed_idx, self.seg_mixed = [0], [dst]
-        self.mixed_segments = [dict(v_start=sg["v_start"], v_end=sg["v_end"], k=k, t_off=sg["t_off"], ldb=32 * nb)]
-        self.mixed_t_scale, self.mixed_descale, self.mixed_s8 = [2.0 ** eT], [2.0 ** -(eT + eB)], [s8]
-        self.b2_log2 = (self.b2 * LOG2E).contiguous()
-        self.ld_tm = (32 * nb * 4 + 4 * 8 + 15) // 16 * 4
+            segs.append(MixedSegment(i, dst, dict(v_start=sg["v_start"], v_end=sg["v_end"], k=k, t_off=sg["t_off"], ldb=32 * nb),
+                                     2.0 ** eT, 2.0 ** -(eT + eB), s8))
+        return MixedRows(fmt, tuple(segs), (self.b2 * LOG2E).contiguous() if xbias else None)
 
     def _ctx(self):
         """every launch of this model happens with ITS device current (streams, events and the launches of the HIP runtime
         follow the current device, not the tensors')"""
-        if self.device.type == "cuda":
-            return self.torch.cuda.device(self.device)
-        import contextlib
-        return contextlib.nullcontext()
+        return self.torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
 
-    def decode_model(self):
-        """torch.classes.jlm.Model of this model (jlm_decode_model, include/jlm_hip.h): what the frame-loop op needs to
-        enqueue a whole batch by itself.  The object keeps the tensors it points into alive."""
-        d = getattr(self, "_decode_model", None)
-        if d is None:
-            O = _ops.backend()
-            t = dict(b2=self.b2, emb=self.emb, wt=self.wt, gate_bias=self.gate_bias)
-            if getattr(self, "b2_log2", None) is not None:
-                t["b2_log2"] = self.b2_log2
-            i = dict(H=self.H, ldt=self.ldt, untied=int(self.mode == "untied"), self_norm=int(self.self_norm),
-                     split_lstm=int(self.split_lstm), ld_emb=self.Epad, kpad=self.kpad, E=self.Epad, lse_fixed_ref=int(getattr(self, "lse_fixed_ref", 0)),
-                     n_t=(self.pmt.shape[0] if self.pmt is not None else 0))
-            f = {}
-            if self.pmt is not None:
-                t["pmt"] = self.pmt
-            if self.split_lstm:
-                t.update(wt8=self.wt8, xgate8=self.xgate8)
-                if self.pmt_split is not None:
-                    t["pmt_split"] = self.pmt_split
-                if self.um_split is not None:
-                    t["untied_split"] = self.um_split
-                    f["untied_descale"] = self.um_descale
-                f.update(gate_descale=self.gate_descale, h_scale=self.h_scale, t_descale=self.t_descale)
-            meta = lambda segs: [int(sg[k]) for sg in segs for k in ("v_start", "v_end", "k", "t_off", "ldb")]
-            if self.split_array is not None:
-                sp = (list(self.seg_split), meta(self.split_segments), [float(x) for x in self.split_t_scale],
-                      [float(x) for x in self.split_descale], [int(x) for x in self.split_bias_col])
-            else:
-                sp = ([], [], [], [], [])
-            if (self.split_array is not None or self.mode == "untied") and getattr(self, "mixed_idx", None):
-                mx = ([int(x) for x in self.mixed_idx], list(self.seg_mixed), meta(self.mixed_segments),
-                      [float(x) for x in self.mixed_t_scale], [float(x) for x in self.mixed_descale], [float(x) for x in self.mixed_s8],
-                      [int(x) for x in (getattr(self, "mixed_head_split", None) or [])])
-            else:
-                mx = ([], [], [], [], [], [], [])
-            d = self._decode_model = O.Model(t, i, f, list(self.seg_B), meta(self.segments), *(sp + mx))
-        return d
+    def decode_model(self, rows=None):
+        """torch.classes.jlm.Model of this model (jlm_decode_model, include/jlm_hip.h) with its normaliser on the mixed rows ``rows``
+        (default: the model's own choice, ``self.mixed``): what the frame-loop op needs to enqueue a whole batch by itself.  The
+        object keeps the tensors it points into alive; the last one built is kept for the record it was built from."""
+        rows = self.mixed if rows is None else rows
+        if self._decode_cache is not None and self._decode_cache[0] is rows:
+            return self._decode_cache[1]
+        O = _ops.backend()
+        t = dict(b2=self.b2, emb=self.emb, wt=self.wt, gate_bias=self.gate_bias)
+        if rows is not None and rows.b2_log2 is not None:
+            t["b2_log2"] = rows.b2_log2
+        i = dict(H=self.H, ldt=self.ldt, untied=int(self.mode == "untied"), self_norm=int(self.self_norm),
+                 split_lstm=int(self.split_lstm), ld_emb=self.Epad, kpad=self.kpad, E=self.Epad,
+                 lse_fixed_ref=int(rows is not None and rows.fixed_ref), n_t=(self.pmt.shape[0] if self.pmt is not None else 0))
+        f = {}
+        if self.pmt is not None:
+            t["pmt"] = self.pmt
+        if self.split_lstm:
+            t.update(wt8=self.wt8, xgate8=self.xgate8)
+            if self.pmt_split is not None:
+                t["pmt_split"] = self.pmt_split
+            if self.um_split is not None:
+                t["untied_split"] = self.um_split
+                f["untied_descale"] = self.um_descale
+            f.update(gate_descale=self.gate_descale, h_scale=self.h_scale, t_descale=self.t_descale)
+        meta = lambda segs: [int(sg[k]) for sg in segs for k in ("v_start", "v_end", "k", "t_off", "ldb")]
+        if self.split_array is not None:
+            sp = (list(self.seg_split), meta(self.split_segments), [float(x) for x in self.split_t_scale],
+                  [float(x) for x in self.split_descale], [int(x) for x in self.split_bias_col])
+        else:
+            sp = ([], [], [], [], [])
+        if rows is not None:
+            mx = (rows.idx, [s.packed for s in rows.segs], meta(s.seg for s in rows.segs), [float(s.t_scale) for s in rows.segs],
+                  [float(s.descale) for s in rows.segs], [float(s.s8) for s in rows.segs], [int(x) for x in rows.head_split])
+        else:
+            mx = ([], [], [], [], [], [], [])
+        self._decode_cache = (rows, O.Model(t, i, f, list(self.seg_B), meta(self.segments), *(sp + mx)))
+        return self._decode_cache[1]
 
     # -- launch helpers of LSTM_Model.predict / project (f32 operands, torch's current stream) --------------------
     def lstm_step(self, h_in, c_in, h_out, c_out, prev, word, n_rows):

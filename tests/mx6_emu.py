@@ -14,7 +14,7 @@ gate predicted -- without a GPU.  Operand layout of the scaled instruction as de
 (profiles/r06_a_fp6_probe.txt)."""
 import numpy as np
 
-LOG2E = 1.4426950408889634
+from jlm_amd.rowformats import LOG2E, mixed_exponents
 
 
 # ------------------------------------------------------------------------------------------------ FP6 e2m3 with a block scale
@@ -185,23 +185,16 @@ def output_segments(cfg, weights):
     return [(PM, np.asarray(w["LM"], dtype=np.float32), 0, V)]
 
 
-def pow2_below(limit, value):
-    if not (value > 0.0) or not np.isfinite(value):
-        return 0
-    return int(np.clip(np.floor(np.log2(limit / value)), -40, 40))
-
-
 def lse_by_form(cfg, weights, h, forms=("split", "mixed", "mx6")):
     """log-normalisers (base e) of the probe rows: {'exact': [rows], form: [rows]} plus per-form worst logit error relative to the
-    rows' logit scale.  Scales as DeviceModel._build_mixed chooses them: 2^eB puts max|B| at <= 2^14, 2^eT the T bound x log2 e at <= 2^15"""
+    rows' logit scale.  Scales as DeviceModel._build_mixed chooses them for int8 planes (rowformats.mixed_exponents): 2^eB puts max|B| at <= 2^14, 2^eT the T bound x log2 e at <= 2^15"""
     segs = output_segments(cfg, weights)
     b2 = np.asarray(weights["b2"], dtype=np.float64)
     ys = {f: [] for f in ("exact",) + tuple(forms)}
     for panel, B, s, e in segs:
         t32 = (h @ panel).astype(np.float32)
         tb = max(float(np.abs(panel).sum(axis=0).max()), 1.0)
-        eT = pow2_below(2.0 ** 15, tb * LOG2E)
-        eB = pow2_below(2.0 ** 14, max(float(np.abs(B).max()), float(np.abs(b2[s:e]).max()) * LOG2E))
+        eB, eT = mixed_exponents("int8", float(np.abs(B).max()), float(np.abs(b2[s:e]).max()), tb)
         ts = (t32 * np.float32(2.0 ** eT * LOG2E)).astype(np.float32)        # base-2 logit units, as jlm_pack_t_mixed
         bs = (B * np.float32(2.0 ** eB)).astype(np.float32)
         de = 2.0 ** -(eT + eB) / LOG2E

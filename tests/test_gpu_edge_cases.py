@@ -365,7 +365,7 @@ def test_fixed_reference_normaliser_overflow_is_loud(name, tmp_path, monkeypatch
     sents = synth.make_ragged_sentences(4, 4, 9, seed=321, alphabet=f["alphabet"])
     ok = d.decode_batch(sents, beam_width=4)                   # the running-maximum form copes with any range
     assert all(np.isfinite(s) for r in ok for s, _ in r)
-    m.lse_fixed_ref, m._decode_model = 1, None
+    m.lse_fixed_ref = 1
     d._engine.m = m
     with pytest.raises(_lib.JlmHipError, match="not finite"):
         d.decode_batch(sents, beam_width=4)

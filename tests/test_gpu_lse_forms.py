@@ -31,12 +31,12 @@ import pytest
 
 torch = pytest.importorskip("torch")
 from jlm_amd import _lib                                                                    # noqa: E402
+from jlm_amd.rowformats import LOG2E, mixed_exponents, plane_scale                           # noqa: E402
 from tests.fake_hip import FakeLib, MX_FORM, MX_FORMS, T_FORMS, _atoi_env                   # noqa: E402
 from tests.test_gpu_kernels import _pack, _pack_t, _split_segments, _st                     # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-LOG2E = 1.4426950408889634
 V = 2011
 BOUNDS = (40, 300, 2560, 5200)
 BIG = 20480                                   # with V = 50 000, the default-launched forms, sampled rows
@@ -189,15 +189,8 @@ def problem(widths, bound, regime, vocab=V):
     return _PROBLEMS[key]
 
 
-def _pow2_below(limit, value):
-    """as DeviceModel's: the largest e with value 2^e <= limit"""
-    if not (value > 0.0) or not np.isfinite(value):
-        return 0
-    return int(np.clip(np.floor(np.log2(limit / value)), -40, 40))
-
-
 def _mixed_rows(L, P, fmt):
-    """mixed rows of every segment scaled as DeviceModel._build_mixed scales them: 2^eB puts max(|B|, |b2| log2 e) at <= 2^14, s8 the
+    """mixed rows of every segment scaled as DeviceModel._build_mixed scales them (jlm_amd/rowformats.py): 2^eB puts max(|B|, |b2| log2 e) at <= 2^14, s8 the
     power of two at or above max |f16(B 2^eB)| / 127, 2^eT puts the segment's largest |T| log2 e at <= 2^15; mx6 rows: eT + eB = 0,
     balanced between the two operands (descale 1: the fixed-reference forms run)"""
     n = len(P.widths)
@@ -206,20 +199,10 @@ def _mixed_rows(L, P, fmt):
     keep = []
     for i, k in enumerate(P.widths):
         nv, B = P.cut[i + 1] - P.cut[i], P.Bs[i]
-        bmax = float(np.abs(B).max())
-        if k % 32:
-            bmax = max(bmax, float(np.abs(P.b2[P.cut[i]:P.cut[i + 1]]).max()) * LOG2E)
-        eB = _pow2_below(2.0 ** 14, bmax)
+        b2max = float(np.abs(P.b2[P.cut[i]:P.cut[i + 1]]).max()) if k % 32 else None       # (a full last block: the biases travel apart)
         tb = max(float(np.abs(P.T[:, P.t_off[i]:P.t_off[i] + k]).max()), 1.0)
-        eT_i = _pow2_below(2.0 ** 15, tb * LOG2E)
-        if fmt == "mx6":
-            lo, hi = max(eB - 17, -eT_i), min(eB, 17 - eT_i, 13)
-            if lo <= hi:
-                bal = int(round(0.5 * (np.log2(tb * LOG2E) - np.log2(bmax))))
-                eB = int(min(max(bal, lo), hi))
-                eT_i = -eB
-        hmax = float(np.abs((B * np.float32(2.0 ** eB)).astype(np.float16).astype(np.float32)).max())
-        s_b = 0.0 if fmt == "mx6" else 2.0 ** int(np.ceil(np.log2(hmax / 127.0)))
+        eB, eT_i = mixed_exponents(fmt, float(np.abs(B).max()), b2max, tb)
+        s_b = plane_scale(fmt, float(np.abs((B * np.float32(2.0 ** eB)).astype(np.float16).astype(np.float32)).max()))
         nb = k // 32 if k % 32 == 0 else (k + 2 + 31) // 32
         dst = torch.zeros((nv, 32 * nb), dtype=torch.float32, device="cuda")
         assert L.jlm_pack_mixed(P.Bg[i].data_ptr(), nv, k, k, P.b2g.data_ptr() + 4 * P.cut[i], 2.0 ** eB, 2.0 ** eB * LOG2E, s_b,

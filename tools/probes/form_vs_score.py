@@ -16,14 +16,14 @@ orig = DM._calibrate_mixed
 
 def forced(form):
     """a _calibrate_mixed that measures as usual, then adopts `form` whatever the figures say"""
-    def cal(self):
+    def cal(self, rows):
         if form == "split":
             os.environ["JLM_MIXED_MAX_LSE_RMS"] = "1e-30"
         elif form == "mixed":
             os.environ["JLM_MIXED_MAX_LSE_RMS"] = "1.0"
         elif form == "first-split":
             os.environ["JLM_MIXED_MAX_LSE_RMS"] = "1e-6"; DM.HEAD_SPLITS = (1 << 30,)
-        orig(self)
+        return orig(self, rows)
     return cal
 
 
@@ -40,8 +40,7 @@ for case in want:
             os.environ["JLM_MIXED_MAX_LSE_RMS"] = "0"
             dec = Decoder(1)
             m = dec.model.dev
-            m.mixed_head_split = [int(form)] + [0] * (len(m.mixed_idx) - 1)
-            m.lse_fixed_ref, m._decode_model = 0, None
+            m.mixed = m.mixed.with_head(int(form)).with_fixed_ref(False)
             calib = "head %s (forced)" % form
         else:
             DM._calibrate_mixed = forced(form)
@@ -67,5 +66,5 @@ for case in want:
             d = [abs(a[0] - b[0]) for a, b in zip(o, g)]
             md = max(md, max(d)); sq += d
         print("%-28s form %-12s mixed segments %s heads %s: 1-best %d/%d  max |score diff| %.2e  rms %.2e   [%s]" % (
-            name, form, list(m.mixed_idx), list(getattr(m, "mixed_head_split", [])), best, len(sents), md, float(np.sqrt(np.mean(np.square(sq)))), calib), flush=True)
+            name, form, list(m.mixed_idx), m.mixed_head_split, best, len(sents), md, float(np.sqrt(np.mean(np.square(sq)))), calib), flush=True)
         del dec
