@@ -764,6 +764,32 @@ typedef struct {
 #define JLM_COMPLETE_EVENTS_PER_FRAME 6
 int jlm_complete_frames(const jlm_decode_model *model_host, const jlm_complete_plan *plan_host, void *stream, void *const *events);
 
+/* ------------------------------------------------------------------------
+ * Scalar k-means compression of one weight tensor (jlm_amd/compress.py kmeans_compress; the reference's train/comp.py:20-48,
+ * scikit-learn KMeans over the flattened weights).  Greedy k-means++ seeding, then Lloyd's iteration, all sums in integers so that
+ * the result does not depend on the launch shape or on the order of any accumulation:
+ *   mn = min x, mx = max x, e = 36 - (binary exponent of mx - mn as frexp gives it), q_i = min(rint((x_i - mn) 2^e), 2^36 - 1) in f64;
+ *   seeding on the histogram of q_i >> 18 (2^18 bins): centre 0 = the bin holding point floor(u N) in bin order; round r >= 1 draws
+ *   trials = 2 + floor(ln K) bins with probability ~ count * D^2 (D = bin distance to the nearest chosen centre), target =
+ *   floor(u * total) with u = splitmix64(seed, r, t) 2^-64 (sample_rows_kernel's mixer of (r << 32) | (t + 1), all 64 bits), the
+ *   first bin whose inclusive prefix exceeds it, and keeps the trial that leaves the smallest total (lowest t on a tie); a round
+ *   whose total is 0 repeats the previous centre.  A seeded bin v starts Lloyd at q = (v << 18) + 2^17;
+ *   Lloyd on q with centres sorted ascending: i belongs to #{j : c_j + c_(j+1) < 2 q_i}; c_j <- floor((sum + count / 2) / count),
+ *   an empty centre stays; it stops after the pass whose largest |shift| <= floor(tol (mx - mn) 2^e), or after max_iter passes;
+ *   code_i against the final centres, codebook_j = (float)(mn + c_j 2^-e), ascending.
+ * x: n float32 on the device, 16-byte aligned; code: n bytes, 4-byte aligned; codebook: 2^bit float32; scratch: JLM_KMEANS_SCRATCH_BYTES
+ * on the device, 16-byte aligned, contents arbitrary.  1 <= n <= JLM_KMEANS_MAX_N (every total fits 64 bits), 1 <= bit <= 8,
+ * max_iter >= 1, tol >= 0.  grid: workgroups of the streaming passes (0: four per compute unit); the result does not depend on it.
+ * The call WAITS on `stream` (the range, and every JLM_KMEANS_SYNC_EVERY Lloyd passes one flag word, come to the host).
+ * info_host[4]: [0] Lloyd passes run [1] 1 for a constant tensor (codebook all mn, codes 0) [2] 1 when x holds a NaN or an infinity
+ * (nothing else is written) [3] 0.  ms_host (may be NULL): milliseconds by HIP events of [0] range [1] histogram [2] seeding
+ * [3] all Lloyd passes, host waits included [4] final assignment.  Returns 0, -1 for bad arguments, or a hipError_t. */
+#define JLM_KMEANS_MAX_N (1ll << 27)
+#define JLM_KMEANS_SCRATCH_BYTES ((2u << 20) + 16384u + 65536u)
+#define JLM_KMEANS_SYNC_EVERY 8
+int jlm_kmeans1d(const float *x, long long n, int bit, uint64_t seed, int max_iter, double tol, unsigned char *code, float *codebook,
+                 void *scratch, int grid, int *info_host, float *ms_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

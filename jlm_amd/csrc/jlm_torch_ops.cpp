@@ -23,6 +23,8 @@
 //   torch.ops.jlm.beam_merge(cand_ids, cand_nll, ...)          one beam selection per prompt (jlm_beam_merge)
 //   torch.ops.jlm.complete_frames(Model, state row sets, logits, prompt arrays, ..., back-pointers, ...)
 //                             beam-search completion: ONE op (jlm_complete_frames; LSTM_Model.complete / predict_top)
+//   torch.ops.jlm.kmeans1d(x, bit, seed, max_iter, tol, code, codebook, scratch, grid, timed)
+//                             scalar k-means compression of one weight tensor: ONE op (jlm_kmeans1d; jlm_amd/compress.py)
 //   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
@@ -687,6 +689,31 @@ Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
                          [&](hipStream_t st, void *const *ev) { return jlm_complete_frames(&m, &p, st, ev); });
 }
 
+// scalar k-means compression of one tensor (jlm_kmeans1d, include/jlm_hip.h): x float32 [n], code uint8 [n], codebook float32 [2^bit],
+// scratch uint8 [JLM_KMEANS_SCRATCH_BYTES].  The op waits for its stream.  -> float64 [9] on the host: Lloyd passes, constant, non-finite,
+// 0, then (timed) milliseconds of range, histogram, seeding, Lloyd passes, final assignment.
+Tensor kmeans1d(const Tensor &x, int64_t bit, int64_t seed, int64_t max_iter, double tol, const Tensor &code, const Tensor &codebook,
+                const Tensor &scratch, int64_t grid, bool timed) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    const int64_t n = x.defined() ? x.numel() : 0;
+    TORCH_CHECK(n >= 1 && n <= JLM_KMEANS_MAX_N && is(x, at::kFloat, n), "jlm.kmeans1d: x float32, 1 .. 2^27 values");
+    TORCH_CHECK(bit >= 1 && bit <= 8 && max_iter >= 1 && max_iter <= INT32_MAX && seed >= 0 && grid >= 0 && grid <= (1 << 20),
+                "jlm.kmeans1d: 1 <= bit <= 8, max_iter >= 1, seed >= 0, 0 <= grid <= 2^20");
+    TORCH_CHECK(is(code, at::kByte, n) && is(codebook, at::kFloat, int64_t(1) << bit) && is(scratch, at::kByte, JLM_KMEANS_SCRATCH_BYTES),
+                "jlm.kmeans1d: code uint8 [n], codebook float32 [2^bit], scratch uint8 [JLM_KMEANS_SCRATCH_BYTES]");
+    const c10::hip::HIPGuard device_guard(x.device().index());
+    int info[4] = {0, 0, 0, 0};
+    float ms[5] = {0, 0, 0, 0, 0};
+    jlm_check(jlm_kmeans1d(ptr<const float>(x, "x"), (long long)n, (int)bit, (uint64_t)seed, (int)max_iter, tol, ptr<unsigned char>(code, "code"),
+                           ptr<float>(codebook, "codebook"), ptr<void>(scratch, "scratch"), (int)grid, info, timed ? ms : nullptr, stream_of(x)),
+              "jlm_kmeans1d");
+    Tensor out = at::zeros({9}, at::TensorOptions().dtype(at::kDouble));
+    double *o = out.data_ptr<double>();
+    for (int i = 0; i < 4; ++i) o[i] = info[i];
+    for (int i = 0; i < 5; ++i) o[4 + i] = ms[i];
+    return out;
+}
+
 int64_t abi_version() { return jlm_abi_version(); }
 int64_t beam_step_max_cands(int64_t beam, int64_t n_frames, int64_t mode) { return jlm_beam_step_max_cands((int)beam, (int)n_frames, (int)mode); }
 
@@ -740,6 +767,9 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(h!) cand_nll, Tensor(i!) word, Tensor(j!) prev_row, Tensor(k!) score, Tensor(l!) finished, int stop_id, Tensor(m!) bp_parent, "
           "Tensor(n!) bp_word, Tensor(o!) bp_nll, Tensor(p!)? flags, int n_prompts, int beam, int n_prompt, int n_words, bool timed) -> Tensor",
           complete_frames);
+    m.def("kmeans1d(Tensor x, int bit, int seed, int max_iter, float tol, Tensor(a!) code, Tensor(b!) codebook, Tensor(c!) scratch, int grid, "
+          "bool timed) -> Tensor",
+          kmeans1d);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }
