@@ -790,6 +790,49 @@ int jlm_complete_frames(const jlm_decode_model *model_host, const jlm_complete_p
 int jlm_kmeans1d(const float *x, long long n, int bit, uint64_t seed, int max_iter, double tol, unsigned char *code, float *codebook,
                  void *scratch, int grid, int *info_host, float *ms_host, void *stream);
 
+/* ---- training (csrc/jlm_train.hip; jlm_amd/train.py DeviceStepper).  Additive: the ABI version stays 12.
+ * Every sum below has one writer and a fixed order: a training step gives the same bits run after run.  All pointers are device
+ * pointers to float32 unless said otherwise; every entry launches on `stream` and returns 0, -1 for bad arguments, or a hipError_t.
+ *
+ * The dropout mask of an [N, width] array (rows in time-major order) is a pure function of (key, row * width + column):
+ *   keep <=> (splitmix64 finaliser of key + 0x9E3779B97F4A7C15 (element + 1)) >> 40 < thr,   thr = ceil(keep 2^24),
+ * kept values are multiplied by `scale` (1 / keep), the others are zero.  thr = 2^24: everything is kept. */
+
+/* C[M, N] (ldc) (+)= A B (+ bias[N]) with A[m, k] = A[m sam + k sak] and B[k, n] = B[k sbk + n sbn]: the NT, TN (row-contracting) and
+ * NN forms by strides.  Per output element an f32 fmaf chain in k order.  accumulate: add to what C holds. */
+int jlm_train_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, float *C, int ldc,
+                   int M, int N, int K, int accumulate, const float *bias, void *stream);
+/* x[r, :E] = mask (.) emb[ids[r], :E] (ids int32; an id outside [0, V) gives a zero row) */
+int jlm_train_embed_rows(const float *emb, int ld_emb, int V, const int *ids, int n_rows, int E, float *x, uint64_t key,
+                         unsigned thr, float scale, void *stream);
+/* z [B, 4H]: pre-activations i | f | o | g -> activations in place; c = c_prev f + g i; h = tanh(c) o; r = mask (.) h, the mask of rows
+ * [row0, row0 + B) of the [N, H] array */
+int jlm_train_cell_fwd(float *z, const float *c_prev, float *c, float *h, float *r, int B, int H, long long row0, uint64_t key,
+                       unsigned thr, float scale, void *stream);
+/* dh = mask (.) dr + dh_next (dh_next may be NULL); dc [B, H] in: the gradient of c from the step after, out: of c_prev; dz [B, 4H] */
+int jlm_train_cell_bwd(const float *gates, const float *c, const float *c_prev, const float *dr, const float *dh_next, float *dc,
+                       float *dz, int B, int H, long long row0, uint64_t key, unsigned thr, float scale, void *stream);
+/* the (max, sum exp) of y[row, :n_cols] merged into run_m / run_s [n_rows] (first: they are overwritten) */
+int jlm_train_lse_update(const float *y, int ld, int n_cols, int n_rows, float *run_m, float *run_s, int first, void *stream);
+/* y: the logits of words [v0, v0 + n_cols) -> dy = s (p (1 + nw2 lse) - onehot) in place, p = exp(y - lse), lse = run_m + log run_s;
+ * tgt_logit[row] = y[row, target[row] - v0] where the target (int32) falls into the chunk.  n_rows <= 65535 */
+int jlm_train_dy(float *y, int ld, int n_cols, int v0, int n_rows, const float *run_m, const float *run_s, const int *target,
+                 float *tgt_logit, float s, float nw2, void *stream);
+/* out[c] (+)= sum over rows of a[r, c], in row order */
+int jlm_train_colsum(const float *a, int ld, int n_rows, int n_cols, float *out, int accumulate, void *stream);
+/* ce_out[0] (float64) = mean over rows of lse - tgt_logit.  Where the training loss ce + nw mean(lse^2) is not finite in f32 (nw:
+ * norm_weight, 0 without self-normalisation) ce_out[0] = +inf and flag[0] = 1 */
+int jlm_train_ce(const float *run_m, const float *run_s, const float *tgt_logit, int n_rows, float nw, double *ce_out, int *flag,
+                 void *stream);
+/* demb[w - v_lo, e] += sum over the rows r that read word w of mask (.) dx[r, col0 + e], rows in index order, for the words in
+ * [v_lo, v_hi) and e < n_cols: the target is that range of words and columns of the [V, width] gradient.  dx [n, ld_dx], the mask that of
+ * the [n, width] array; ids_sorted int32 [n] ascending, perm int64 [n] the row of each (a stable sort) */
+int jlm_train_scatter_rows(const float *dx, int ld_dx, int col0, int n_cols, int width, const int *ids_sorted, const long long *perm,
+                           int n, float *demb, int ld, int v_lo, int v_hi, uint64_t key, unsigned thr, float scale, void *stream);
+/* TensorFlow's Adam (beta1 0.9, beta2 0.999, eps 1e-8) over n values, n a multiple of 4, pointers 16-byte aligned; lr_t =
+ * lr sqrt(1 - beta2^t) / (1 - beta1^t) from the host.  flag (may be NULL): nothing is updated once flag[0] != 0 */
+int jlm_train_adam(float *w, const float *g, float *m, float *v, long long n, float lr_t, const int *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ has not been built (``python -c 'import __graft_entry__ as g; g.build()'``) and
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_uint, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # JLM_HIP_LIB: developer override used by tools/ab_lib.sh to A/B two builds of the same ABI
@@ -146,6 +146,16 @@ _SIGS = {
     "jlm_wordlist_lse_form": ([POINTER(Segment), c_int, POINTER(Segment), c_int, c_int, c_int, c_int], c_int),
     "jlm_wordlist_merge_form": ([POINTER(Segment), c_int, POINTER(Segment), c_int, c_int, c_int], c_int),
     "jlm_kmeans1d": ([P, c_longlong, c_int, c_uint64, c_int, c_double, P, P, P, c_int, POINTER(c_int), POINTER(c_float), P], c_int),
+    "jlm_train_gemm": ([P, c_longlong, c_longlong, P, c_longlong, c_longlong, P, c_int, c_int, c_int, c_int, c_int, P, P], c_int),
+    "jlm_train_embed_rows": ([P, c_int, c_int, P, c_int, c_int, P, c_uint64, c_uint, c_float, P], c_int),
+    "jlm_train_cell_fwd": ([P, P, P, P, P, c_int, c_int, c_longlong, c_uint64, c_uint, c_float, P], c_int),
+    "jlm_train_cell_bwd": ([P, P, P, P, P, P, P, c_int, c_int, c_longlong, c_uint64, c_uint, c_float, P], c_int),
+    "jlm_train_lse_update": ([P, c_int, c_int, c_int, P, P, c_int, P], c_int),
+    "jlm_train_dy": ([P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P], c_int),
+    "jlm_train_colsum": ([P, c_int, c_int, c_int, P, c_int, P], c_int),
+    "jlm_train_ce": ([P, P, P, c_int, c_float, P, P, P], c_int),
+    "jlm_train_scatter_rows": ([P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, c_int, c_int, c_uint64, c_uint, c_float, P], c_int),
+    "jlm_train_adam": ([P, P, P, P, c_longlong, c_float, P, P], c_int),
 }
 EXPORTS = sorted(_SIGS)
 

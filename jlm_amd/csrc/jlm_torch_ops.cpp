@@ -25,6 +25,7 @@
 //                             beam-search completion: ONE op (jlm_complete_frames; LSTM_Model.complete / predict_top)
 //   torch.ops.jlm.kmeans1d(x, bit, seed, max_iter, tol, code, codebook, scratch, grid, timed)
 //                             scalar k-means compression of one weight tensor: ONE op (jlm_kmeans1d; jlm_amd/compress.py)
+//   torch.ops.jlm.train_*       the kernels of a training step, one op per launcher (jlm_train.hip; jlm_amd/train.py DeviceStepper)
 //   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
@@ -714,6 +715,125 @@ Tensor kmeans1d(const Tensor &x, int64_t bit, int64_t seed, int64_t max_iter, do
     return out;
 }
 
+// ---- training (csrc/jlm_train.hip; jlm_amd/train.py DeviceStepper).  The operands may be VIEWS of larger buffers (a row or column range of
+// the flat parameter buffer, a chunk of the logits scratch): `reach` elements from the view's first must lie inside its storage.
+template <class T> T *vptr(const Tensor &t, at::ScalarType ty, int64_t reach, const char *name) {
+    TORCH_CHECK(t.defined() && t.is_cuda() && t.scalar_type() == ty, "jlm.train: `", name, "` must be a GPU tensor of the documented type");
+    const int64_t have = (int64_t)(t.storage().nbytes() / t.element_size()) - t.storage_offset();
+    TORCH_CHECK(reach >= 1 && reach <= have, "jlm.train: `", name, "` reaches ", reach, " elements, its storage holds ", have);
+    return reinterpret_cast<T *>(t.data_ptr());
+}
+int64_t span(int64_t rows, int64_t ld, int64_t cols) { return (rows - 1) * ld + cols; }
+
+void train_gemm(const Tensor &A, int64_t sam, int64_t sak, const Tensor &B, int64_t sbk, int64_t sbn, const Tensor &C, int64_t ldc, int64_t M,
+                int64_t N, int64_t K, bool accumulate, const OptTensor &bias) {
+    TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX && ldc >= N && ldc <= INT32_MAX && sam >= 1 &&
+                sak >= 1 && sbk >= 1 && sbn >= 1, "jlm.train_gemm: bad shape");
+    const c10::hip::HIPGuard device_guard(C.device().index());
+    const bool has_bias = bias.has_value() && bias->defined();
+    jlm_check(jlm_train_gemm(vptr<const float>(A, at::kFloat, (M - 1) * sam + (K - 1) * sak + 1, "A"), sam, sak,
+                             vptr<const float>(B, at::kFloat, (K - 1) * sbk + (N - 1) * sbn + 1, "B"), sbk, sbn,
+                             vptr<float>(C, at::kFloat, span(M, ldc, N), "C"), (int)ldc, (int)M, (int)N, (int)K, accumulate ? 1 : 0,
+                             has_bias ? vptr<const float>(*bias, at::kFloat, N, "bias") : nullptr, stream_of(C)),
+              "jlm_train_gemm");
+}
+
+void train_embed_rows(const Tensor &emb, int64_t ld_emb, int64_t V, const Tensor &ids, int64_t n_rows, int64_t E, const Tensor &x, int64_t key,
+                      int64_t thr, double scale) {
+    TORCH_CHECK(n_rows >= 1 && E >= 1 && ld_emb >= E && V >= 1 && V <= INT32_MAX && n_rows * E <= INT32_MAX && thr >= 0 && thr <= (1 << 24),
+                "jlm.train_embed_rows: bad shape");
+    const c10::hip::HIPGuard device_guard(x.device().index());
+    jlm_check(jlm_train_embed_rows(vptr<const float>(emb, at::kFloat, span(V, ld_emb, E), "emb"), (int)ld_emb, (int)V,
+                                   vptr<const int>(ids, at::kInt, n_rows, "ids"), (int)n_rows, (int)E, vptr<float>(x, at::kFloat, n_rows * E, "x"),
+                                   (uint64_t)key, (unsigned)thr, (float)scale, stream_of(x)),
+              "jlm_train_embed_rows");
+}
+
+void train_cell_fwd(const Tensor &z, const Tensor &c_prev, const Tensor &c, const Tensor &h, const Tensor &r, int64_t B, int64_t H, int64_t row0,
+                    int64_t key, int64_t thr, double scale) {
+    TORCH_CHECK(B >= 1 && H >= 1 && B * H * 4 <= INT32_MAX && row0 >= 0 && thr >= 0 && thr <= (1 << 24), "jlm.train_cell_fwd: bad shape");
+    const c10::hip::HIPGuard device_guard(z.device().index());
+    jlm_check(jlm_train_cell_fwd(vptr<float>(z, at::kFloat, 4 * B * H, "z"), vptr<const float>(c_prev, at::kFloat, B * H, "c_prev"),
+                                 vptr<float>(c, at::kFloat, B * H, "c"), vptr<float>(h, at::kFloat, B * H, "h"), vptr<float>(r, at::kFloat, B * H, "r"),
+                                 (int)B, (int)H, (long long)row0, (uint64_t)key, (unsigned)thr, (float)scale, stream_of(z)),
+              "jlm_train_cell_fwd");
+}
+
+void train_cell_bwd(const Tensor &gates, const Tensor &c, const Tensor &c_prev, const Tensor &dr, const OptTensor &dh_next, const Tensor &dc,
+                    const Tensor &dz, int64_t B, int64_t H, int64_t row0, int64_t key, int64_t thr, double scale) {
+    TORCH_CHECK(B >= 1 && H >= 1 && B * H * 4 <= INT32_MAX && row0 >= 0 && thr >= 0 && thr <= (1 << 24), "jlm.train_cell_bwd: bad shape");
+    const c10::hip::HIPGuard device_guard(dz.device().index());
+    const bool has_next = dh_next.has_value() && dh_next->defined();
+    jlm_check(jlm_train_cell_bwd(vptr<const float>(gates, at::kFloat, 4 * B * H, "gates"), vptr<const float>(c, at::kFloat, B * H, "c"),
+                                 vptr<const float>(c_prev, at::kFloat, B * H, "c_prev"), vptr<const float>(dr, at::kFloat, B * H, "dr"),
+                                 has_next ? vptr<const float>(*dh_next, at::kFloat, B * H, "dh_next") : nullptr,
+                                 vptr<float>(dc, at::kFloat, B * H, "dc"), vptr<float>(dz, at::kFloat, 4 * B * H, "dz"), (int)B, (int)H,
+                                 (long long)row0, (uint64_t)key, (unsigned)thr, (float)scale, stream_of(dz)),
+              "jlm_train_cell_bwd");
+}
+
+void train_lse_update(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const Tensor &run_m, const Tensor &run_s, bool first) {
+    TORCH_CHECK(n_cols >= 1 && n_rows >= 1 && ld >= n_cols && ld <= INT32_MAX && n_rows <= INT32_MAX, "jlm.train_lse_update: bad shape");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    jlm_check(jlm_train_lse_update(vptr<const float>(y, at::kFloat, span(n_rows, ld, n_cols), "y"), (int)ld, (int)n_cols, (int)n_rows,
+                                   vptr<float>(run_m, at::kFloat, n_rows, "run_m"), vptr<float>(run_s, at::kFloat, n_rows, "run_s"),
+                                   first ? 1 : 0, stream_of(y)),
+              "jlm_train_lse_update");
+}
+
+void train_dy(const Tensor &y, int64_t ld, int64_t n_cols, int64_t v0, int64_t n_rows, const Tensor &run_m, const Tensor &run_s,
+              const Tensor &target, const Tensor &tgt_logit, double s, double nw2) {
+    TORCH_CHECK(n_cols >= 1 && n_rows >= 1 && n_rows <= 65535 && ld >= n_cols && ld <= INT32_MAX && v0 >= 0 && v0 + n_cols <= INT32_MAX,
+                "jlm.train_dy: bad shape");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    jlm_check(jlm_train_dy(vptr<float>(y, at::kFloat, span(n_rows, ld, n_cols), "y"), (int)ld, (int)n_cols, (int)v0, (int)n_rows,
+                           vptr<const float>(run_m, at::kFloat, n_rows, "run_m"), vptr<const float>(run_s, at::kFloat, n_rows, "run_s"),
+                           vptr<const int>(target, at::kInt, n_rows, "target"), vptr<float>(tgt_logit, at::kFloat, n_rows, "tgt_logit"), (float)s,
+                           (float)nw2, stream_of(y)),
+              "jlm_train_dy");
+}
+
+void train_colsum(const Tensor &a, int64_t ld, int64_t n_rows, int64_t n_cols, const Tensor &out, bool accumulate) {
+    TORCH_CHECK(n_cols >= 1 && n_rows >= 1 && ld >= n_cols && ld <= INT32_MAX && n_rows <= INT32_MAX, "jlm.train_colsum: bad shape");
+    const c10::hip::HIPGuard device_guard(a.device().index());
+    jlm_check(jlm_train_colsum(vptr<const float>(a, at::kFloat, span(n_rows, ld, n_cols), "a"), (int)ld, (int)n_rows, (int)n_cols,
+                               vptr<float>(out, at::kFloat, n_cols, "out"), accumulate ? 1 : 0, stream_of(a)),
+              "jlm_train_colsum");
+}
+
+void train_ce(const Tensor &run_m, const Tensor &run_s, const Tensor &tgt_logit, int64_t n_rows, double nw, const Tensor &ce_out,
+              const Tensor &flag) {
+    TORCH_CHECK(n_rows >= 1 && n_rows <= INT32_MAX, "jlm.train_ce: bad shape");
+    const c10::hip::HIPGuard device_guard(run_m.device().index());
+    jlm_check(jlm_train_ce(vptr<const float>(run_m, at::kFloat, n_rows, "run_m"), vptr<const float>(run_s, at::kFloat, n_rows, "run_s"),
+                           vptr<const float>(tgt_logit, at::kFloat, n_rows, "tgt_logit"), (int)n_rows, (float)nw, vptr<double>(ce_out, at::kDouble, 1, "ce_out"),
+                           vptr<int>(flag, at::kInt, 1, "flag"), stream_of(run_m)),
+              "jlm_train_ce");
+}
+
+void train_scatter_rows(const Tensor &dx, int64_t ld_dx, int64_t col0, int64_t n_cols, int64_t width, const Tensor &ids_sorted, const Tensor &perm,
+                        int64_t n, const Tensor &demb, int64_t ld, int64_t v_lo, int64_t v_hi, int64_t key, int64_t thr, double scale) {
+    TORCH_CHECK(n >= 1 && n <= INT32_MAX && n_cols >= 1 && col0 >= 0 && col0 + n_cols <= width && ld_dx >= width && ld_dx <= INT32_MAX &&
+                ld >= n_cols && ld <= INT32_MAX && v_lo >= 0 && v_hi > v_lo && v_hi <= INT32_MAX && thr >= 0 && thr <= (1 << 24),
+                "jlm.train_scatter_rows: bad shape");
+    const c10::hip::HIPGuard device_guard(demb.device().index());
+    jlm_check(jlm_train_scatter_rows(vptr<const float>(dx, at::kFloat, span(n, ld_dx, width), "dx"), (int)ld_dx, (int)col0, (int)n_cols, (int)width,
+                                     vptr<const int>(ids_sorted, at::kInt, n, "ids_sorted"), vptr<const long long>(perm, at::kLong, n, "perm"),
+                                     (int)n, vptr<float>(demb, at::kFloat, span(v_hi - v_lo, ld, n_cols), "demb"), (int)ld, (int)v_lo, (int)v_hi,
+                                     (uint64_t)key, (unsigned)thr, (float)scale, stream_of(demb)),
+              "jlm_train_scatter_rows");
+}
+
+void train_adam(const Tensor &w, const Tensor &g, const Tensor &m, const Tensor &v, int64_t n, double lr_t, const OptTensor &flag) {
+    TORCH_CHECK(n >= 4 && n % 4 == 0, "jlm.train_adam: n must be a positive multiple of 4");
+    const c10::hip::HIPGuard device_guard(w.device().index());
+    const bool has_flag = flag.has_value() && flag->defined();
+    jlm_check(jlm_train_adam(vptr<float>(w, at::kFloat, n, "w"), vptr<const float>(g, at::kFloat, n, "g"), vptr<float>(m, at::kFloat, n, "m"),
+                             vptr<float>(v, at::kFloat, n, "v"), (long long)n, (float)lr_t,
+                             has_flag ? vptr<const int>(*flag, at::kInt, 1, "flag") : nullptr, stream_of(w)),
+              "jlm_train_adam");
+}
+
 int64_t abi_version() { return jlm_abi_version(); }
 int64_t beam_step_max_cands(int64_t beam, int64_t n_frames, int64_t mode) { return jlm_beam_step_max_cands((int)beam, (int)n_frames, (int)mode); }
 
@@ -770,6 +890,22 @@ TORCH_LIBRARY(jlm, m) {
     m.def("kmeans1d(Tensor x, int bit, int seed, int max_iter, float tol, Tensor(a!) code, Tensor(b!) codebook, Tensor(c!) scratch, int grid, "
           "bool timed) -> Tensor",
           kmeans1d);
+    m.def("train_gemm(Tensor A, int sam, int sak, Tensor B, int sbk, int sbn, Tensor(a!) C, int ldc, int M, int N, int K, bool accumulate, "
+          "Tensor? bias) -> ()", train_gemm);
+    m.def("train_embed_rows(Tensor emb, int ld_emb, int V, Tensor ids, int n_rows, int E, Tensor(a!) x, int key, int thr, float scale) -> ()",
+          train_embed_rows);
+    m.def("train_cell_fwd(Tensor(a!) z, Tensor c_prev, Tensor(b!) c, Tensor(c!) h, Tensor(d!) r, int B, int H, int row0, int key, int thr, "
+          "float scale) -> ()", train_cell_fwd);
+    m.def("train_cell_bwd(Tensor gates, Tensor c, Tensor c_prev, Tensor dr, Tensor? dh_next, Tensor(a!) dc, Tensor(b!) dz, int B, int H, "
+          "int row0, int key, int thr, float scale) -> ()", train_cell_bwd);
+    m.def("train_lse_update(Tensor y, int ld, int n_cols, int n_rows, Tensor(a!) run_m, Tensor(b!) run_s, bool first) -> ()", train_lse_update);
+    m.def("train_dy(Tensor(a!) y, int ld, int n_cols, int v0, int n_rows, Tensor run_m, Tensor run_s, Tensor target, Tensor(b!) tgt_logit, "
+          "float s, float nw2) -> ()", train_dy);
+    m.def("train_colsum(Tensor a, int ld, int n_rows, int n_cols, Tensor(a!) out, bool accumulate) -> ()", train_colsum);
+    m.def("train_ce(Tensor run_m, Tensor run_s, Tensor tgt_logit, int n_rows, float nw, Tensor(a!) ce_out, Tensor(b!) flag) -> ()", train_ce);
+    m.def("train_scatter_rows(Tensor dx, int ld_dx, int col0, int n_cols, int width, Tensor ids_sorted, Tensor perm, int n, Tensor(a!) demb, "
+          "int ld, int v_lo, int v_hi, int key, int thr, float scale) -> ()", train_scatter_rows);
+    m.def("train_adam(Tensor(a!) w, Tensor g, Tensor(b!) m, Tensor(c!) v, int n, float lr_t, Tensor? flag) -> ()", train_adam);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

@@ -1,0 +1,381 @@
+// jlm_train.hip -- the kernels of one training step of the LSTM language model (jlm_amd/train.py DeviceStepper).
+// The graph is the reference's train/model.py RNNLM_Model; jlm_amd/train.py ReferenceStepper restates it in float64 and is what these
+// kernels are judged against.  Every sum has ONE writer and a fixed order (no float atomics): a step gives the same bits run after run.
+//
+// train_gemm_kernel     C (+)= A B (+ bias) over operands given by element strides: the NT form (both K-contiguous), the row-contracting
+//                       TN form (dW = X^T dZ, dEmb = dY^T P) and the NN form (dP += dY Emb).  64 x 64 tile, 4 x 4 per lane, an exact f32
+//                       fmaf chain in k order per output element; the k tile sits in LDS once and is read along either axis.
+// embed_rows_kernel     x = mask (.) Emb[id]: the step's input rows.
+// cell_fwd_kernel       z -> i, f, o, g (kept, in place), c, h, and the dropped output r = mask (.) h.
+// cell_bwd_kernel       dh = mask (.) dr + dh_next, dc -> dz [B, 4H], dc_prev.
+// lse_update_kernel     one wave per row: the chunk's (max, sum exp) merged into the row's running pair, chunks in launch order.
+// dy_kernel             logits of a chunk -> dy = s (p (1 + 2 nw lse) - onehot) in place; the target's logit is met on the way.
+// colsum_kernel         out[c] (+)= sum over rows in row order (db2 of a chunk, the gate biases).
+// ce_kernel             one workgroup: ce = mean(lse - y[target]) in f64 -> the pass's loss slot; a non-finite loss raises the flag word.
+// scatter_rows_kernel   dEmb[w] += sum of mask (.) dx over the rows that read word w: the ids sorted, one wave per distinct word, index order.
+// adam_kernel           TensorFlow's Adam over the flat parameter buffer, 16-byte accesses; a raised flag word stops every update.
+//
+// The dropout mask is a pure function of (key, element): element = row * width + column of the [N, width] array in time-major row order,
+// keep <=> splitmix64(key + G (element + 1)) >> 40 < thr, thr = ceil(keep 2^24); key = splitmix64 of (seed, step, site) from the host.
+#include "jlm_common.h"
+
+#include <math.h>
+
+typedef unsigned long long u64;
+
+#define TG_BM 64
+#define TG_BN 64
+#define TG_BK 16
+#define TG_LD (TG_BM + 4)
+
+__device__ __forceinline__ bool tr_keep(u64 key, u64 elem, unsigned thr) {
+    u64 z = key + 0x9E3779B97F4A7C15ull * (elem + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (unsigned)(z >> 40) < thr;
+}
+
+__global__ __launch_bounds__(256) void train_gemm_kernel(const float *__restrict__ A, long long sam, long long sak,
+                                                         const float *__restrict__ B, long long sbk, long long sbn, float *C, long long ldc,
+                                                         int M, int N, int K, int accumulate, const float *__restrict__ bias, int a_kfast,
+                                                         int b_nfast) {
+    __shared__ __attribute__((aligned(16))) float As[TG_BK][TG_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[TG_BK][TG_LD];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int m0 = blockIdx.y * TG_BM, n0 = blockIdx.x * TG_BN;
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
+    for (int k0 = 0; k0 < K; k0 += TG_BK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + i * 256;
+            int mm, kk;
+            if (a_kfast) { kk = idx & 15; mm = idx >> 4; } else { mm = idx & 63; kk = idx >> 6; }
+            const int gm = m0 + mm, gk = k0 + kk;
+            As[kk][mm] = (gm < M && gk < K) ? A[(long long)gm * sam + (long long)gk * sak] : 0.0f;
+            int nn;
+            if (b_nfast) { nn = idx & 63; kk = idx >> 6; } else { kk = idx & 15; nn = idx >> 4; }
+            const int gn = n0 + nn, gk2 = k0 + kk;
+            Bs[kk][nn] = (gn < N && gk2 < K) ? B[(long long)gk2 * sbk + (long long)gn * sbn] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < TG_BK; ++kk) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(&As[kk][ty * 4]);
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(&Bs[kk][tx * 4]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int gm = m0 + ty * 4 + i;
+        if (gm >= M) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int gn = n0 + tx * 4 + j;
+            if (gn >= N) continue;
+            float v = acc[i][j];
+            if (bias) v += bias[gn];
+            float *c = C + (long long)gm * ldc + gn;
+            if (accumulate) v += *c;
+            *c = v;
+        }
+    }
+}
+
+extern "C" int jlm_train_gemm(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, float *C, int ldc,
+                              int M, int N, int K, int accumulate, const float *bias, void *stream) {
+    if (!A || !B || !C || M < 1 || N < 1 || K < 1 || ldc < N || sam < 1 || sak < 1 || sbk < 1 || sbn < 1) return -1;
+    const long long gy = (M + TG_BM - 1) / TG_BM, gx = (N + TG_BN - 1) / TG_BN;
+    if (gy > 65535 || gx > 2147483647ll) return -1;
+    hipLaunchKernelGGL(train_gemm_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, A, sam, sak, B, sbk, sbn, C,
+                       (long long)ldc, M, N, K, accumulate, bias, sak == 1 ? 1 : 0, sbn == 1 ? 1 : 0);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- input rows
+__global__ __launch_bounds__(256) void embed_rows_kernel(const float *__restrict__ emb, int ld_emb, int V, const int *__restrict__ ids,
+                                                         int n_rows, int E, float *__restrict__ x, u64 key, unsigned thr, float scale) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)n_rows * E) return;
+    const int r = (int)(i / E), e = (int)(i % E);
+    const int w = ids[r];
+    float v = 0.0f;
+    if (w >= 0 && w < V && tr_keep(key, (u64)i, thr)) v = emb[(long long)w * ld_emb + e] * scale;
+    x[i] = v;
+}
+
+extern "C" int jlm_train_embed_rows(const float *emb, int ld_emb, int V, const int *ids, int n_rows, int E, float *x, uint64_t key,
+                                    unsigned thr, float scale, void *stream) {
+    if (!emb || !ids || !x || n_rows < 1 || E < 1 || ld_emb < E || V < 1) return -1;
+    const long long n = (long long)n_rows * E;
+    hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, emb, ld_emb, V, ids, n_rows,
+                       E, x, (u64)key, thr, scale);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- the LSTM cell
+__device__ __forceinline__ float tr_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// z [B, 4H] (i | f | o | g pre-activations) -> the activations in place; c, h [B, H]; r = mask (.) h.  row0: the step's first row in the
+// [N, H] time-major array the mask is defined over.
+__global__ __launch_bounds__(256) void cell_fwd_kernel(float *__restrict__ z, const float *__restrict__ c_prev, float *__restrict__ c,
+                                                       float *__restrict__ h, float *__restrict__ r, int B, int H, long long row0, u64 key,
+                                                       unsigned thr, float scale) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= B * H) return;
+    const int b = idx / H, j = idx % H;
+    float *zr = z + (long long)b * 4 * H;
+    const float gi = tr_sigmoid(zr[j]), gf = tr_sigmoid(zr[H + j]), go = tr_sigmoid(zr[2 * H + j]), gg = tanhf(zr[3 * H + j]);
+    zr[j] = gi; zr[H + j] = gf; zr[2 * H + j] = go; zr[3 * H + j] = gg;
+    const float cc = fmaf(c_prev[idx], gf, gg * gi);
+    const float hh = tanhf(cc) * go;
+    c[idx] = cc;
+    h[idx] = hh;
+    r[idx] = tr_keep(key, (u64)(row0 * H) + (u64)idx, thr) ? hh * scale : 0.0f;
+}
+
+extern "C" int jlm_train_cell_fwd(float *z, const float *c_prev, float *c, float *h, float *r, int B, int H, long long row0, uint64_t key,
+                                  unsigned thr, float scale, void *stream) {
+    if (!z || !c_prev || !c || !h || !r || B < 1 || H < 1 || row0 < 0 || (long long)B * H > 2147483647ll) return -1;
+    hipLaunchKernelGGL(cell_fwd_kernel, dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z, c_prev, c, h, r, B, H,
+                       row0, (u64)key, thr, scale);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// gates [B, 4H] (activations), c, c_prev [B, H]; dr [B, H]: the gradient of the dropped output; dh_next [B, H] or NULL; dc [B, H] in / out
+// (NULL-free: the caller zeroes it before the last step); dz [B, 4H] out.
+__global__ __launch_bounds__(256) void cell_bwd_kernel(const float *__restrict__ gates, const float *__restrict__ c,
+                                                       const float *__restrict__ c_prev, const float *__restrict__ dr,
+                                                       const float *__restrict__ dh_next, float *__restrict__ dc, float *__restrict__ dz,
+                                                       int B, int H, long long row0, u64 key, unsigned thr, float scale) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= B * H) return;
+    const int b = idx / H, j = idx % H;
+    const float *g = gates + (long long)b * 4 * H;
+    const float gi = g[j], gf = g[H + j], go = g[2 * H + j], gg = g[3 * H + j];
+    float dh = tr_keep(key, (u64)(row0 * H) + (u64)idx, thr) ? dr[idx] * scale : 0.0f;
+    if (dh_next) dh += dh_next[idx];
+    const float tc = tanhf(c[idx]);
+    const float dcc = dc[idx] + dh * go * (1.0f - tc * tc);
+    float *d = dz + (long long)b * 4 * H;
+    d[j] = dcc * gg * gi * (1.0f - gi);
+    d[H + j] = dcc * c_prev[idx] * gf * (1.0f - gf);
+    d[2 * H + j] = dh * tc * go * (1.0f - go);
+    d[3 * H + j] = dcc * gi * (1.0f - gg * gg);
+    dc[idx] = dcc * gf;
+}
+
+extern "C" int jlm_train_cell_bwd(const float *gates, const float *c, const float *c_prev, const float *dr, const float *dh_next, float *dc,
+                                  float *dz, int B, int H, long long row0, uint64_t key, unsigned thr, float scale, void *stream) {
+    if (!gates || !c || !c_prev || !dr || !dc || !dz || B < 1 || H < 1 || row0 < 0 || (long long)B * H > 2147483647ll) return -1;
+    hipLaunchKernelGGL(cell_bwd_kernel, dim3((unsigned)((B * H + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gates, c, c_prev, dr,
+                       dh_next, dc, dz, B, H, row0, (u64)key, thr, scale);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- the vocabulary loss
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void lse_update_kernel(const float *__restrict__ y, long long ld, int n_cols, int n_rows,
+                                                         float *__restrict__ run_m, float *__restrict__ run_s, int first) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n_rows) return;
+    const float *yr = y + (long long)row * ld;
+    float m = JLM_NEG_BIG;
+    for (int c = lane; c < n_cols; c += 64) m = fmaxf(m, yr[c]);
+    m = wave_max(m);
+    float s = 0.0f;
+    for (int c = lane; c < n_cols; c += 64) s += expf(yr[c] - m);
+    s = wave_sum(s);
+    if (lane == 0) {
+        float M0 = JLM_NEG_BIG, S0 = 0.0f;
+        if (!first) { M0 = run_m[row]; S0 = run_s[row]; }
+        lse_merge(M0, S0, m, s);
+        run_m[row] = M0;
+        run_s[row] = S0;
+    }
+}
+
+extern "C" int jlm_train_lse_update(const float *y, int ld, int n_cols, int n_rows, float *run_m, float *run_s, int first, void *stream) {
+    if (!y || !run_m || !run_s || n_cols < 1 || n_rows < 1 || ld < n_cols) return -1;
+    hipLaunchKernelGGL(lse_update_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, y, (long long)ld, n_cols,
+                       n_rows, run_m, run_s, first);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// y [n_rows, ld]: the logits of words [v0, v0 + n_cols) -> dy in place.  s = 1 / N; nw2 = 2 norm_weight (0: no self-normalisation term).
+__global__ __launch_bounds__(256) void dy_kernel(float *__restrict__ y, long long ld, int n_cols, int v0, int n_rows,
+                                                 const float *__restrict__ run_m, const float *__restrict__ run_s,
+                                                 const int *__restrict__ target, float *__restrict__ tgt_logit, float s, float nw2) {
+    const int row = blockIdx.y;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows || c >= n_cols) return;
+    const float lse = run_m[row] + logf(run_s[row]);
+    float *p = y + (long long)row * ld + c;
+    const float v = *p;
+    const bool hit = target[row] == v0 + c;
+    if (hit) tgt_logit[row] = v;
+    const float pr = expf(v - lse);
+    *p = s * (fmaf(pr * nw2, lse, pr) - (hit ? 1.0f : 0.0f));
+}
+
+extern "C" int jlm_train_dy(float *y, int ld, int n_cols, int v0, int n_rows, const float *run_m, const float *run_s, const int *target,
+                            float *tgt_logit, float s, float nw2, void *stream) {
+    if (!y || !run_m || !run_s || !target || !tgt_logit || n_cols < 1 || n_rows < 1 || n_rows > 65535 || ld < n_cols || v0 < 0) return -1;
+    hipLaunchKernelGGL(dy_kernel, dim3((unsigned)((n_cols + 255) / 256), (unsigned)n_rows), dim3(256), 0, (hipStream_t)stream, y,
+                       (long long)ld, n_cols, v0, n_rows, run_m, run_s, target, tgt_logit, s, nw2);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ a, long long ld, int n_rows, int n_cols, float *__restrict__ out,
+                                                     int accumulate) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cols) return;
+    float s = 0.0f;
+    for (int r = 0; r < n_rows; ++r) s += a[(long long)r * ld + c];
+    out[c] = accumulate ? out[c] + s : s;
+}
+
+extern "C" int jlm_train_colsum(const float *a, int ld, int n_rows, int n_cols, float *out, int accumulate, void *stream) {
+    if (!a || !out || n_rows < 1 || n_cols < 1 || ld < n_cols) return -1;
+    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, (long long)ld, n_rows,
+                       n_cols, out, accumulate);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// nw: norm_weight (0 without self-normalisation).  The training loss is ce + nw mean(lse^2); where that is not finite IN F32 (an lse
+// whose square overflows counts) the step is flagged and its slot holds +inf, so that the host can name the step.
+__global__ __launch_bounds__(256) void ce_kernel(const float *__restrict__ run_m, const float *__restrict__ run_s,
+                                                 const float *__restrict__ tgt_logit, int n_rows, float nw, double *__restrict__ ce_out,
+                                                 int *__restrict__ flag) {
+    __shared__ double part[256];
+    double s = 0.0;
+    int bad = 0;
+    for (int r = threadIdx.x; r < n_rows; r += 256) {
+        const float lse = run_m[r] + logf(run_s[r]);
+        s += (double)lse - (double)tgt_logit[r];
+        bad |= !isfinite(lse) || (nw != 0.0f && !isfinite(nw * (lse * lse)));
+    }
+    bad = __syncthreads_or(bad);
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double ce = part[0] / (double)n_rows;
+        if (bad || !isfinite(ce) || !isfinite((float)ce)) {
+            ce_out[0] = (double)INFINITY;
+            flag[0] = 1;
+        } else {
+            ce_out[0] = ce;
+        }
+    }
+}
+
+extern "C" int jlm_train_ce(const float *run_m, const float *run_s, const float *tgt_logit, int n_rows, float nw, double *ce_out, int *flag,
+                            void *stream) {
+    if (!run_m || !run_s || !tgt_logit || !ce_out || !flag || n_rows < 1) return -1;
+    hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, run_m, run_s, tgt_logit, n_rows, nw, ce_out, flag);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- the input side of dEmb
+// ids_sorted [n]: the step's input ids ascending; perm [n]: the row each came from (a stable sort: rows ascending within a word).
+// One wave per position that opens a run of equal ids; it adds the run's rows in index order and adds the sum to the word's row of the
+// target, which nobody else writes in this launch.  The target holds the words [v_lo, v_hi) and columns [col0, col0 + n_cols) of the
+// [V, width] gradient (a D_softmax block, LM0 of a V_table model, or everything); words outside the range are left alone.
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const float *__restrict__ dx, int ld_dx, int col0, int n_cols, int width,
+                                                           const int *__restrict__ ids_sorted, const long long *__restrict__ perm, int n,
+                                                           float *__restrict__ demb, int ld, int v_lo, int v_hi, u64 key, unsigned thr,
+                                                           float scale) {
+    const int pos = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (pos >= n) return;
+    const int w = ids_sorted[pos];
+    if (w < v_lo || w >= v_hi || (pos > 0 && ids_sorted[pos - 1] == w)) return;
+    for (int e = lane; e < n_cols; e += 64) {
+        float s = 0.0f;
+        for (int q = pos; q < n && ids_sorted[q] == w; ++q) {
+            const long long r = perm[q];
+            if (r < 0 || r >= n) continue;
+            if (tr_keep(key, (u64)r * (u64)width + (u64)(col0 + e), thr)) s += dx[r * ld_dx + col0 + e] * scale;
+        }
+        demb[(long long)(w - v_lo) * ld + e] += s;
+    }
+}
+
+extern "C" int jlm_train_scatter_rows(const float *dx, int ld_dx, int col0, int n_cols, int width, const int *ids_sorted,
+                                      const long long *perm, int n, float *demb, int ld, int v_lo, int v_hi, uint64_t key, unsigned thr,
+                                      float scale, void *stream) {
+    if (!dx || !ids_sorted || !perm || !demb || n < 1 || n_cols < 1 || col0 < 0 || col0 + n_cols > width || ld_dx < width || ld < n_cols ||
+        v_lo < 0 || v_hi <= v_lo)
+        return -1;
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dx, ld_dx, col0, n_cols, width,
+                       ids_sorted, perm, n, demb, ld, v_lo, v_hi, (u64)key, thr, scale);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- Adam
+// TensorFlow's form: m <- b1 m + (1 - b1) g; v <- b2 v + (1 - b2) g^2; w <- w - lr_t m / (sqrt(v) + eps); lr_t from the host.
+__device__ __forceinline__ void adam_one(float &w, float g, float &m, float &v, float lr_t) {
+    m = fmaf(0.9f, m, 0.1f * g);
+    v = fmaf(0.999f, v, 0.001f * (g * g));
+    w -= lr_t * m / (sqrtf(v) + 1e-8f);
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, long long n4, float lr_t, const int *__restrict__ flag) {
+    if (flag && flag[0]) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        f32x4 ww = reinterpret_cast<f32x4 *>(w)[i], mm = reinterpret_cast<f32x4 *>(m)[i], vv = reinterpret_cast<f32x4 *>(v)[i];
+        const f32x4 gg = reinterpret_cast<const f32x4 *>(g)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float w1 = ww[k], m1 = mm[k], v1 = vv[k];
+            adam_one(w1, gg[k], m1, v1, lr_t);
+            ww[k] = w1; mm[k] = m1; vv[k] = v1;
+        }
+        reinterpret_cast<f32x4 *>(w)[i] = ww;
+        reinterpret_cast<f32x4 *>(m)[i] = mm;
+        reinterpret_cast<f32x4 *>(v)[i] = vv;
+    }
+}
+
+// n: a multiple of 4 (the flat parameter buffer pads every tensor to 16 bytes); all four pointers 16-byte aligned
+extern "C" int jlm_train_adam(float *w, const float *g, float *m, float *v, long long n, float lr_t, const int *flag, void *stream) {
+    if (!w || !g || !m || !v || n < 4 || (n & 3) || ((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return -1;
+    const long long n4 = n / 4;
+    long long grid = (n4 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, n4, lr_t, flag);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
