@@ -497,6 +497,14 @@ int jlm_vocab_lse_hybrid(const jlm_segment *segs_host, const float *t_scale, con
  * 0: no cell fits (beam or frame count too large).  Pure host function, no GPU needed. */
 int jlm_beam_step_max_cands(int beam, int n_frames, int mode);
 
+/* Additive (ABI 12): the dynamic LDS one launch asks for -- the launchers' own formulas -- so that the residency budget of the small
+ * per-frame kernels beside a resident normaliser workgroup can be checked without a GPU.
+ * jlm_beam_step_lds_bytes: jlm_beam_step's one-piece kernel for this beam, frame count, mode and max_cands; 0: bad arguments.
+ * jlm_vocab_lse_mixed_lds_bytes: jlm_vocab_lse_mixed(_fr) for these segments (mixed or mx6 rows); -1 / -2: shapes it refuses.
+ * Pure host functions. */
+int jlm_beam_step_lds_bytes(int beam, int n_frames, int mode, int max_cands);
+int jlm_vocab_lse_mixed_lds_bytes(const jlm_segment *segs_host, int n_segs);
+
 /* K10: n-best read-out.  For sentence s and rank r < cnt at its last frame:
  * out_nodes[(s*beam+r)*stride + d] = node ids from the LAST word back to the
  * root, out_len = number of nodes, out_score = path score (decoder.py:237). */

@@ -120,6 +120,8 @@ _SIGS = {
                                  P, P, P, P], c_int),
     "jlm_beam_step": ([POINTER(Lattice), POINTER(BeamState), c_int, c_int, c_int, P], c_int),
     "jlm_beam_step_max_cands": ([c_int, c_int, c_int], c_int),
+    "jlm_beam_step_lds_bytes": ([c_int, c_int, c_int, c_int], c_int),
+    "jlm_vocab_lse_mixed_lds_bytes": ([POINTER(Segment), c_int], c_int),
     "jlm_pack_mixed": ([P, c_int, c_int, c_int, P, c_float, c_float, c_float, P, c_int, P], c_int),
     "jlm_vocab_lse_hybrid": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), POINTER(c_int), POINTER(Segment), POINTER(c_float),
                               POINTER(c_float), POINTER(c_int), c_int, P, P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, P], c_int),

@@ -315,7 +315,7 @@ __device__ __forceinline__ void wave_argmin(double &v, int &i) {
 }
 
 template <int MODE>
-__global__ __launch_bounds__(64) void beam_step_kernel(jlm_lattice lat, jlm_beam_state st, int frame, int max_cands) {
+__global__ __launch_bounds__(64, 8) void beam_step_kernel(jlm_lattice lat, jlm_beam_state st, int frame, int max_cands) {
     extern __shared__ __attribute__((aligned(16))) double keys[];   // [max_cands] | MODE 2: [n_frames*beam] | int [max_cands] | [beam] | int [n_frames] | winners: [beam] double, [beam] int
     const int s = blockIdx.x, lane = threadIdx.x;
     const int B = lat.n_sent, beam = lat.beam, rmax = B * beam;
@@ -417,17 +417,18 @@ __global__ __launch_bounds__(64) void beam_step_kernel(jlm_lattice lat, jlm_beam
                 sf[u] = lat.node_start[n[u]];
             }
             bool ok[U];
-            int gp[U];
             double scv[U], lsv[U], ysv[U];
             float ev[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 ok[u] = (c0 + 64 * u < C) && k[u] < cnt_s[sf[u]];
-                gp[u] = sf[u] * rmax + s * beam + (ok[u] ? k[u] : 0);
+                const int gp = sf[u] * rmax + s * beam + (ok[u] ? k[u] : 0);
                 ev[u] = st.edge[(size_t)n[u] * beam + k[u]];
-                scv[u] = (MODE == 2) ? 0.0 : st.score[gp[u]];
-                lsv[u] = (MODE == 1) ? 0.0 : st.lse[gp[u]];
-                ysv[u] = (MODE == 2) ? st.ysum[gp[u]] : 0.0;
+                scv[u] = (MODE == 2) ? 0.0 : st.score[gp];
+                lsv[u] = (MODE == 1) ? 0.0 : st.lse[gp];
+                ysv[u] = (MODE == 2) ? st.ysum[gp] : 0.0;
+                // (the predecessor row is written here, not beside the key: it need not stay in a register while the loads are in flight)
+                if (c0 + 64 * u < C) gp_of[c0 + 64 * u] = ok[u] ? gp : -1;
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -442,7 +443,6 @@ __global__ __launch_bounds__(64) void beam_step_kernel(jlm_lattice lat, jlm_beam
                     ++nvalid;
                 }
                 if constexpr (reg0 >= 0) kreg[reg0 + u] = sc; else keys[c] = sc;
-                gp_of[c] = ok[u] ? gp[u] : -1;
                 if (sc < bv) { bv = sc; bi = c; }          // ascending c: ties keep the lower index
             }
         };
@@ -751,6 +751,12 @@ extern "C" int jlm_beam_step_max_cands(int beam, int n_frames, int mode) {
     if (total > (1u << 22)) total = 1u << 22;
     total = total / 256 * 256;
     return total > (size_t)one ? (int)total : one;
+}
+
+// the dynamic LDS jlm_beam_step asks for (one-piece kernel), for the residency budget beside the normaliser; 0: bad arguments
+extern "C" int jlm_beam_step_lds_bytes(int beam, int n_frames, int mode, int max_cands) {
+    if (beam < 1 || beam > JLM_MAX_BEAM || n_frames < 1 || mode < 0 || mode > 2 || max_cands < 1 || max_cands > (1 << 22)) return 0;
+    return (int)beam_step_lds_bytes(beam, n_frames, mode, max_cands);
 }
 
 extern "C" int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *st_host, int frame, int mode,

@@ -89,16 +89,23 @@ __global__ __launch_bounds__(256) void pack_mixed_kernel(const float *__restrict
 // the bias constants 2^eT / 2^(eT-11) at columns k, k + 1 of the f16 part, and at the END of the row JLM_MAX_SEGMENTS floats: the
 // row's int8 scale per segment (the power of two at or above max |hi| / 127).  One wave per row; done ONCE per row and frame --
 // the vocabulary kernel's workgroups (24 columns per row tile) only load the result.
+// f16 of the EXACT product a b (one rounding, v_fma_mixlo_f16): how the int8 packer's f16 part has always been rounded -- the compiler's
+// contraction of (_Float16)(a * b); spelt out so that a restructured loop cannot turn it into the twice-rounded v_mul + v_cvt
+__device__ __forceinline__ _Float16 mx_mul_f16(float a, float b) {
+    unsigned r = 0;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
+    return __builtin_bit_cast(_Float16, (unsigned short)r);
+}
 struct MxTSeg { int k, t_off, nb, tm_off; float t_scale, tc; };      // tc = 0: no bias columns (k = 32 nb)
 struct MxTArgs { int n_segs; MxTSeg seg[JLM_MAX_SEGMENTS]; };
 
-__global__ __launch_bounds__(256) void pack_t_mixed_kernel(MxTArgs a, const float *__restrict__ T, int ldt, const int *__restrict__ rows,
+__global__ __launch_bounds__(256, 8) void pack_t_mixed_kernel(MxTArgs a, const float *__restrict__ T, int ldt, const int *__restrict__ rows,
                                                            int n_rows_max, const int *__restrict__ n_dev, unsigned char *__restrict__ Tm,
                                                            int ld_tm) {
     // four rows per workgroup, one wave each; lane l owns the 16-value group l of the row's groups (two per 32-k block, all segments
     // concatenated: 26 groups for the D-softmax* 200 / 100 / 50 rows): its 16 values are loaded once and stay in registers
     const int n = n_dev ? min(*n_dev, n_rows_max) : n_rows_max;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));      // the wave's row: row, pointers and scales in scalar registers
     if (r >= n) return;
     const int g = rows ? rows[r] : r;
     const int lane = threadIdx.x & 63;
@@ -120,13 +127,17 @@ __global__ __launch_bounds__(256) void pack_t_mixed_kernel(MxTArgs a, const floa
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int k0 = 16 * gs + 4 * q;
-            v[q] = *reinterpret_cast<const f32x4 *>(trow + sg.t_off + ((act && k0 < sg.k) ? k0 : 0));
+            v[q] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(trow) + 4u * (unsigned)(sg.t_off + ((act && k0 < sg.k) ? k0 : 0)));
         }
+        // (k is a multiple of 4 -- pack_t_mixed_impl refuses any other (`sg.k % 4`), and this placement breaks if it ever stops doing so:
+        //  the bias constants can only sit at values 0, 4, 8, 12 of a group and the slot behind)
+        const int d = act ? sg.k - 16 * gs : -2;      // values e < d of the group are real, e = d and d + 1 the bias constants
+        const float tc1 = sg.tc * (1.0f / 2048.0f);
         float amax = 0.0f;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) amax = fmaxf(amax, (act && 16 * gs + 4 * q + e < sg.k) ? fabsf((float)(_Float16)(v[q][e] * sg.t_scale)) : 0.0f);
+            for (int e = 0; e < 4; ++e) amax = fmaxf(amax, 4 * q + e < d ? fabsf((float)mx_mul_f16(sg.t_scale, v[q][e])) : 0.0f);
         // per segment: the maximum over the lanes that hold it
         float smax = 0.0f;
         for (int sj = 0; sj < a.n_segs; ++sj) {
@@ -137,7 +148,7 @@ __global__ __launch_bounds__(256) void pack_t_mixed_kernel(MxTArgs a, const floa
             if (lane == 0 && grp0 == 0) {
                 const float w = x * (1.0f / 127.0f);
                 const int bt = (__float_as_int(w) + 0x007fffff) & 0x7f800000;
-                *reinterpret_cast<float *>(oblk + mx_tm_scale(ld_tm, r, sj)) = x > 0.0f ? __int_as_float(bt) : 1.0f;
+                *reinterpret_cast<float *>(oblk + (unsigned)mx_tm_scale(ld_tm, r, sj)) = x > 0.0f ? __int_as_float(bt) : 1.0f;
             }
         }
         if (!act) return;
@@ -146,31 +157,34 @@ __global__ __launch_bounds__(256) void pack_t_mixed_kernel(MxTArgs a, const floa
         const float s_t = smax > 0.0f ? __int_as_float(bits) : 1.0f;
         const float inv_h = 1.0f / s_t, inv_l = inv_h * 2048.0f;
         const int j = gs >> 1, half = gs & 1;
-        _Float16 hi[16];
+        // granules of the row's block j: 2 half, 2 half + 1 (f16 hi), 4 + half (hi8), 6 + half (lo8).  Each f16 granule leaves as soon as
+        // its eight values are converted: the sixteen f16 do not stay live beside the int8 words (the kernel has to fit 64 registers)
         int ph[4], pl[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int wh = 0, wl = 0;
+        for (int hq = 0; hq < 2; ++hq) {
+            _Float16 hi[8];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = 16 * gs + 4 * q + e;
-                const bool real = k < sg.k;
-                const float x = real ? v[q][e] * sg.t_scale : (k == sg.k ? sg.tc : (k == sg.k + 1 ? sg.tc * (1.0f / 2048.0f) : 0.0f));
-                const _Float16 h = (_Float16)x;
-                hi[4 * q + e] = h;
-                const float hf_ = (float)h;
-                const int qh = real ? (int)rintf(hf_ * inv_h) : 0;
-                const int ql = real ? (int)rintf((x - hf_) * inv_l) : 0;
-                wh |= (max(min(qh, 127), -127) & 0xff) << (8 * e);
-                wl |= (max(min(ql, 127), -127) & 0xff) << (8 * e);
+            for (int q = 2 * hq; q < 2 * hq + 2; ++q) {
+                int wh = 0, wl = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool real = 4 * q + e < d;
+                    const float c = e == 0 ? (4 * q == d ? sg.tc : 0.0f) : e == 1 ? (4 * q + 1 == d + 1 ? tc1 : 0.0f) : 0.0f;
+                    const float x = real ? v[q][e] * sg.t_scale : c;
+                    const _Float16 h = real ? mx_mul_f16(sg.t_scale, v[q][e]) : (_Float16)c;
+                    hi[4 * (q & 1) + e] = h;
+                    const float hf_ = (float)h;
+                    const int qh = real ? (int)rintf(hf_ * inv_h) : 0;
+                    const int ql = real ? (int)rintf((x - hf_) * inv_l) : 0;
+                    wh |= (max(min(qh, 127), -127) & 0xff) << (8 * e);
+                    wl |= (max(min(ql, 127), -127) & 0xff) << (8 * e);
+                }
+                ph[q] = wh; pl[q] = wl;
             }
-            ph[q] = wh; pl[q] = wl;
+            *reinterpret_cast<f32x4 *>(oblk + (unsigned)mx_tm_granule(sg.tm_off, j * 8 + 2 * half + hq, r)) = *reinterpret_cast<const f32x4 *>(hi);
         }
-        // granules of the row's block j: 2 half, 2 half + 1 (f16 hi), 4 + half (hi8), 6 + half (lo8)
-        *reinterpret_cast<f32x4 *>(oblk + mx_tm_granule(sg.tm_off, j * 8 + 2 * half, r)) = *reinterpret_cast<const f32x4 *>(hi);
-        *reinterpret_cast<f32x4 *>(oblk + mx_tm_granule(sg.tm_off, j * 8 + 2 * half + 1, r)) = *reinterpret_cast<const f32x4 *>(hi + 8);
-        *reinterpret_cast<i32x4 *>(oblk + mx_tm_granule(sg.tm_off, j * 8 + 4 + half, r)) = i32x4{ph[0], ph[1], ph[2], ph[3]};
-        *reinterpret_cast<i32x4 *>(oblk + mx_tm_granule(sg.tm_off, j * 8 + 6 + half, r)) = i32x4{pl[0], pl[1], pl[2], pl[3]};
+        *reinterpret_cast<i32x4 *>(oblk + (unsigned)mx_tm_granule(sg.tm_off, j * 8 + 4 + half, r)) = i32x4{ph[0], ph[1], ph[2], ph[3]};
+        *reinterpret_cast<i32x4 *>(oblk + (unsigned)mx_tm_granule(sg.tm_off, j * 8 + 6 + half, r)) = i32x4{pl[0], pl[1], pl[2], pl[3]};
     }
 }
 
@@ -239,10 +253,10 @@ __global__ __launch_bounds__(256) void pack_mx6_kernel(const float *__restrict__
 // g0 .. g0 + 31, lanes 32-63: the hi6 plane of the same groups) -- the quantiser is ~20 VALU instructions per value, and with a lane
 // per group and BOTH planes (the int8 packer's assignment) the launch took 12-14 us where the int8 one takes 9.
 // The halves are SWAPPED against the vocabulary rows (half 0 = lo6, half 1 = hi6): the instruction pairs k-slot with k-slot.
-__global__ __launch_bounds__(256) void pack_t_mx6_kernel(MxTArgs a, const float *__restrict__ T, int ldt, const int *__restrict__ rows,
+__global__ __launch_bounds__(256, 8) void pack_t_mx6_kernel(MxTArgs a, const float *__restrict__ T, int ldt, const int *__restrict__ rows,
                                                          int n_rows_max, const int *__restrict__ n_dev, unsigned char *__restrict__ Tm, int ld_tm) {
     const int n = n_dev ? min(*n_dev, n_rows_max) : n_rows_max;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));      // the wave's row: row, pointers and scales in scalar registers
     if (r >= n) return;
     const int g = rows ? rows[r] : r;
     const int lane = threadIdx.x & 63;
@@ -251,7 +265,8 @@ __global__ __launch_bounds__(256) void pack_t_mx6_kernel(MxTArgs a, const float 
     unsigned char *oblk = Tm + mx_tm_block(r, ld_tm);
     int total = 0;
     for (int si = 0; si < a.n_segs; ++si) total += 2 * a.seg[si].nb;
-    for (int g0 = 0; g0 < total; g0 += 32) {
+    {   // 32 groups per wave: the launcher's grid has ceil(total / 32) workgroups per four rows (y)
+        const int g0 = blockIdx.y * 32;
         const int grp = g0 + (lane & 31);
         int si = 0, base = 0;
         while (si + 1 < a.n_segs && grp >= base + 2 * a.seg[si].nb) { base += 2 * a.seg[si].nb; ++si; }
@@ -262,38 +277,50 @@ __global__ __launch_bounds__(256) void pack_t_mx6_kernel(MxTArgs a, const float 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int k0 = 16 * gs + 4 * q;
-            v[q] = *reinterpret_cast<const f32x4 *>(trow + sg.t_off + ((act && k0 < sg.k) ? k0 : 0));
+            v[q] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(trow) + 4u * (unsigned)(sg.t_off + ((act && k0 < sg.k) ? k0 : 0)));
         }
-        _Float16 hi[16];
+        // (k is a multiple of 4 -- pack_t_mixed_impl refuses any other (`sg.k % 4`), and this placement breaks if it ever stops doing so:
+        //  the bias constants can only sit at e = 0, 4, 8, 12 and the slot behind)
+        const int d = act ? sg.k - 16 * gs : -2;      // values e < d of the group are real, e = d and d + 1 the bias constants
+        const float tc1 = sg.tc * (1.0f / 2048.0f);
+        const int j = gs >> 1, half = gs & 1;
+        unsigned h_even = 0;
+        unsigned hw[4];                               // this lane's eight f16 (values 8 sl .. 8 sl + 7), two to a dword
         float val[16];
         float amax = 0.0f;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int k = 16 * gs + e;
-            const bool real = act && k < sg.k;
-            float x = real ? v[e >> 2][e & 3] * sg.t_scale : (k == sg.k ? sg.tc : (k == sg.k + 1 ? sg.tc * (1.0f / 2048.0f) : 0.0f));
+            const bool real = e < d;
+            const float c = (e & 3) == 0 ? (e == d ? sg.tc : 0.0f) : (e & 3) == 1 ? (e == d + 1 ? tc1 : 0.0f) : 0.0f;
+            float x = real ? v[e >> 2][e & 3] * sg.t_scale : c;
             asm volatile("" : "+v"(x));               // (the scaled value is used twice: jlm_common.h jlm_split2)
             _Float16 h = (_Float16)x;
             asm volatile("" : "+v"(h));
-            hi[e] = h;
             val[e] = real ? (sl ? (float)h : x - (float)h) : 0.0f;
             amax = fmaxf(amax, fabsf(val[e]));
+            // the f16 part is kept two to a dword and only the half this lane stores: eight registers less than the sixteen f16 held singly
+            const unsigned hb = __builtin_bit_cast(unsigned short, h);
+            if (e & 1) {
+                const unsigned pair = h_even | (hb << 16);
+                hw[(e & 7) >> 1] = (e < 8 || sl) ? pair : hw[(e & 7) >> 1];
+            } else {
+                h_even = hb;
+            }
         }
         amax = fmaxf(amax, __shfl_xor(amax, 1));
         if (act) {
+            // the f16 part: granules 2 half, 2 half + 1 of the block -- one each from the group's two lanes
+            *reinterpret_cast<i32x4 *>(oblk + (unsigned)mx_tm_granule(sg.tm_off, j * 8 + 2 * half + sl, r)) = i32x4{(int)hw[0], (int)hw[1], (int)hw[2], (int)hw[3]};
             const int byte = mx6_block_byte(amax);
             unsigned c[16], pw[3];
 #pragma unroll
             for (int e = 0; e < 16; ++e) c[e] = mx6_code(val[e], byte);
             mx6_pack16(c, pw);
-            const int j = gs >> 1, half = gs & 1;
-            // the f16 part: granules 2 half, 2 half + 1 of the block -- one each from the group's two lanes
-            *reinterpret_cast<f32x4 *>(oblk + mx_tm_granule(sg.tm_off, j * 8 + 2 * half + sl, r)) = *reinterpret_cast<const f32x4 *>(hi + 8 * sl);
             // plane sl: dwords 0-3 in granule 4 + 2 sl, dwords 4-5 in granule 5 at byte 8 sl; this lane holds dwords 3 half .. 3 half + 2
-            unsigned char *ga = oblk + mx_tm_granule(sg.tm_off, j * 8 + 4 + 2 * sl, r), *g5 = oblk + mx_tm_granule(sg.tm_off, j * 8 + 5, r) + 8 * sl;
+            unsigned char *ga = oblk + (unsigned)mx_tm_granule(sg.tm_off, j * 8 + 4 + 2 * sl, r), *g5 = oblk + (unsigned)mx_tm_granule(sg.tm_off, j * 8 + 5, r) + 8 * sl;
             if (half == 0) {
                 *reinterpret_cast<unsigned *>(ga + 0) = pw[0]; *reinterpret_cast<unsigned *>(ga + 4) = pw[1]; *reinterpret_cast<unsigned *>(ga + 8) = pw[2];
-                (oblk + mx_tm_granule(sg.tm_off, 7, r))[8 * sl + j] = (unsigned char)byte;
+                (oblk + (unsigned)mx_tm_granule(sg.tm_off, 7, r))[8 * sl + j] = (unsigned char)byte;
             } else {
                 *reinterpret_cast<unsigned *>(ga + 12) = pw[0]; *reinterpret_cast<unsigned *>(g5 + 0) = pw[1]; *reinterpret_cast<unsigned *>(g5 + 4) = pw[2];
             }
@@ -473,8 +500,9 @@ static int pack_t_mixed_impl(const jlm_segment *segs_host, const float *t_scale,
     }
     if (fmt6) {
         for (int i = 0; i < n_segs; ++i) if (a.seg[i].nb > 8) return -2;      // (a row's scale bytes: eight per half)
-        hipLaunchKernelGGL(pack_t_mx6_kernel, dim3((n_rows_max + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, T, ldt, rows, n_rows_max, n_dev,
-                           reinterpret_cast<unsigned char *>(Tm), ld_tm);
+        const int total_groups = off / 64;                   // 16-value groups per row: two per 128-byte block, off = the blocks' bytes
+        hipLaunchKernelGGL(pack_t_mx6_kernel, dim3((n_rows_max + 3) / 4, (total_groups + 31) / 32), dim3(256), 0, (hipStream_t)stream, a, T, ldt,
+                           rows, n_rows_max, n_dev, reinterpret_cast<unsigned char *>(Tm), ld_tm);
     } else {
         hipLaunchKernelGGL(pack_t_mixed_kernel, dim3((n_rows_max + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, T, ldt, rows, n_rows_max, n_dev,
                            reinterpret_cast<unsigned char *>(Tm), ld_tm);
@@ -570,6 +598,28 @@ extern "C" int jlm_vocab_lse_mixed_form(const jlm_segment *segs_host, const floa
     return JLM_LSE_MX_DSOFTMAX + which;
 }
 
+// dynamic LDS of a launch with a segment of nb blocks: two buffers of one tile (mtt 32-word blocks, the whole contraction), and the tile's
+// biases three deep in the external-bias form
+static int mx_seg_lds_bytes(int nb, bool xb) {
+    const int mtt = mx_blocks_per_tile(nb);
+    return 2 * 32 * mtt * nb * 128 + (xb ? 3 * 32 * mtt * 4 : 0);
+}
+
+// What jlm_vocab_lse_mixed(_fr) asks for these segments (the largest segment's): the launcher's own formula, for the residency budget of
+// the kernels that run beside the normaliser (tests/test_kernel_residency_cpu.py).  -1 / -2: shapes the launcher refuses.
+// Pure host function.
+extern "C" int jlm_vocab_lse_mixed_lds_bytes(const jlm_segment *segs_host, int n_segs) {
+    if (n_segs < 1 || n_segs > JLM_MAX_SEGMENTS) return -1;
+    int lds_max = 0;
+    for (int i = 0; i < n_segs; ++i) {
+        const int nb = mx_seg_blocks(segs_host[i]);
+        if (nb < 1 || nb > 16) return -2;
+        const int lds_i = mx_seg_lds_bytes(nb, segs_host[i].k + 2 > 32 * nb);
+        if (lds_i > lds_max) lds_max = lds_i;
+    }
+    return lds_max;
+}
+
 static int vocab_lse_mixed_impl(const jlm_segment *segs_host, const float *descale, const float *s8, const float *bias2, int n_segs,
                                 const void *Tm, int ld_tm, float *part, int ld_part, int max_parts, int n_rows_max,
                                 const int *n_dev, void *stream, int fixed_ref) {
@@ -620,7 +670,7 @@ static int vocab_lse_mixed_impl(const jlm_segment *segs_host, const float *desca
         // (per-shape block costs fitted to single-segment launches -- 2.15 : 1.28 : 1 for k = 200 / 100 / 50 -- cut the three-segment
         //  launch WORSE than this formula's 1.95 : 1.35 : 1 (72.6 vs 70.5 us); what is left between the columns is the XCDs' clocks:
         //  equal cycles per workgroup within 2 %, 1.81-1.92 GHz from XCD to XCD on one chip -- tools/probes/mixed_wg_timeline.py)
-        const int lds_i = 2 * 32 * mtt * nb * 128 + (xb ? 3 * 32 * mtt * 4 : 0);
+        const int lds_i = mx_seg_lds_bytes(nb, xb);
         if (lds_i > lds_max) lds_max = lds_i;
         total += ctile[i] * ntiles[i];
         n_tiles_all += ntiles[i];
