@@ -841,6 +841,22 @@ int jlm_train_scatter_rows(const float *dx, int ld_dx, int col0, int n_cols, int
  * lr sqrt(1 - beta2^t) / (1 - beta1^t) from the host.  flag (may be NULL): nothing is updated once flag[0] != 0 */
 int jlm_train_adam(float *w, const float *g, float *m, float *v, long long n, float lr_t, const int *flag, void *stream);
 
+/* ---- fine-tuning the codebooks of a k-means compressed model (jlm_amd/finetune.py).  Additive: ABI 12.
+ * A compressed model's weights are w[i] = book[gid[i]] over the flat parameter buffer: book holds every tensor's codebook, tensor t at
+ * t K (K = 2^bit); gid[i] = t K + code for a coded element, -1 for the padding between tensors.  The codes never change. */
+#define JLM_CODEBOOK_CHUNK 4096
+/* w[i] = gid[i] >= 0 ? book[gid[i]] : 0 for i < n (an id >= n_book gives 0 too).  gid int32 [n]; n a multiple of 4, gid and w 16-byte
+ * aligned (the accesses to both are 16 bytes wide). */
+int jlm_train_expand_codes(const float *book, int n_book, const int *gid, float *w, long long n, void *stream);
+/* gbook[j] = the sum of g[i] over the elements i with gid[i] == j, for j < n_groups.  order int32 [n_order]: the offsets of the coded
+ * elements sorted by (gid, offset); chunks int32 [n_chunks][3] = (group, begin, length), ascending: every group's run of `order` in
+ * pieces of at most JLM_CODEBOOK_CHUNK; partial float64 [n_chunks] scratch.  Two launches: one wave per chunk (lane l adds elements
+ * l, l + 64, ... in that order in f64, the lane sums meet in one xor butterfly) -> partial; one lane per group adds its partials in
+ * chunk order in f64 and stores the f32 rounding, 0 for a group without chunks.  One writer per sum, a fixed order, no atomics: the
+ * bits do not depend on the launch shape.  An offset outside [0, n) or a chunk outside [0, n_order) contributes nothing. */
+int jlm_train_codebook_grad(const float *g, long long n, const int *order, long long n_order, const int *chunks, int n_chunks,
+                            int n_groups, double *partial, float *gbook, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,9 @@ integer sum, so the bytes that come out do not depend on the launch shape or on 
     mean ``(sum + count // 2) // count`` of its values, an empty centre stays; the iteration stops after the pass whose largest shift
     is ``<= floor(tol (mx - mn) 2^e)`` or after ``max_iter`` passes;
   - codes are the assignment against the final centres; ``codebook[j] = float32(mn + c_j 2^-e)``, ASCENDING (scikit-learn's order is
-    arbitrary; ascending is this package's).  A constant tensor: codebook all ``mn``, codes 0.
+    arbitrary; ascending is this package's).  A constant tensor: codebook all ``mn``, codes 0.  Ascending is how k-means LEAVES a
+    codebook, not something a reader may rely on: ``jlm_amd.finetune`` retrains the entries and they need not stay in order.  Every
+    reader decodes with ``take(codebook, code)``.
 
 There is no CPU fallback: ``kmeans_compress`` needs the GPU, like the rest of the package.
 """
@@ -217,8 +219,6 @@ def compress_experiment(experiment_id, bit=8, debug=True, seed=0, max_iter=300, 
     for k, v in weights.items():
         if isinstance(v, list):
             raise ValueError("tensor %r is a D_softmax block list: train/comp.py cannot compress it either" % (k,))
-    cdir = os.path.join(wdir, "comp_{}".format(bit))
-    os.makedirs(cdir, exist_ok=True)
     decoded, dump, report = {}, {}, []
     for k, v in weights.items():
         v = np.asarray(v)
@@ -233,14 +233,26 @@ def compress_experiment(experiment_id, bit=8, debug=True, seed=0, max_iter=300, 
         power = float((v.astype(np.float64) ** 2).sum())
         report.append(dict(name=k, shape=tuple(v.shape), iterations=last_info.get("n_iter"), inertia=inertia,
                            rel_rms=math.sqrt(inertia / power) if power > 0 else 0.0, seconds=dt))
-        if debug:
-            np.savetxt(os.path.join(cdir, "{}_code.txt".format(k)), code.astype(int), fmt="%i")
+    write_compressed(experiment_id, bit, dump, debug)
+    return report
+
+
+def write_compressed(experiment_id, bit, dump, debug):
+    """The files of a compressed experiment from ``dump`` (name -> (code, codebook [2^bit, 1])): weights/lstm_weights_comp_{bit}.pkl
+    (``take(codebook, code)`` per tensor), weights/comp_{bit}/lstm_weights_comp_dump.pkl and, with ``debug``, the text dumps beside
+    it.  ``compress_experiment`` and ``jlm_amd.finetune`` both write through here."""
+    wdir = _weights.weights_dir(experiment_id)
+    cdir = os.path.join(wdir, "comp_{}".format(bit))
+    os.makedirs(cdir, exist_ok=True)
+    decoded = {k: _weights.decode_codebook(code, book) for k, (code, book) in dump.items()}
+    if debug:
+        for k, (code, book) in dump.items():
+            np.savetxt(os.path.join(cdir, "{}_code.txt".format(k)), np.asarray(code).astype(int), fmt="%i")
             np.savetxt(os.path.join(cdir, "{}_codebook.txt".format(k)), book)
     with open(os.path.join(wdir, "lstm_weights_comp_{}.pkl".format(bit)), "wb") as f:
         pickle.dump(decoded, f)
     with open(os.path.join(cdir, "lstm_weights_comp_dump.pkl"), "wb") as f:
         pickle.dump(dump, f)
-    return report
 
 
 def format_report(report):

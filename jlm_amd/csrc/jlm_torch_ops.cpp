@@ -26,6 +26,8 @@
 //   torch.ops.jlm.kmeans1d(x, bit, seed, max_iter, tol, code, codebook, scratch, grid, timed)
 //                             scalar k-means compression of one weight tensor: ONE op (jlm_kmeans1d; jlm_amd/compress.py)
 //   torch.ops.jlm.train_*       the kernels of a training step, one op per launcher (jlm_train.hip; jlm_amd/train.py DeviceStepper)
+//   torch.ops.jlm.train_expand_codes / train_codebook_grad
+//                               fine-tuning the codebooks of a compressed model (jlm_amd/finetune.py CodebookDeviceStepper)
 //   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
@@ -834,6 +836,30 @@ void train_adam(const Tensor &w, const Tensor &g, const Tensor &m, const Tensor 
               "jlm_train_adam");
 }
 
+// ---- fine-tuning the codebooks of a compressed model (jlm_amd/finetune.py)
+void train_expand_codes(const Tensor &book, const Tensor &gid, const Tensor &w, int64_t n) {
+    TORCH_CHECK(n >= 4 && n % 4 == 0, "jlm.train_expand_codes: n must be a positive multiple of 4");
+    TORCH_CHECK(book.defined() && book.numel() >= 1 && book.numel() <= INT32_MAX, "jlm.train_expand_codes: an empty codebook buffer");
+    const c10::hip::HIPGuard device_guard(w.device().index());
+    jlm_check(jlm_train_expand_codes(vptr<const float>(book, at::kFloat, book.numel(), "book"), (int)book.numel(),
+                                     vptr<const int>(gid, at::kInt, n, "gid"), vptr<float>(w, at::kFloat, n, "w"), (long long)n, stream_of(w)),
+              "jlm_train_expand_codes");
+}
+
+void train_codebook_grad(const Tensor &g, const Tensor &order, const Tensor &chunks, int64_t n_chunks, int64_t n_groups, const Tensor &partial,
+                         const Tensor &gbook) {
+    TORCH_CHECK(n_chunks >= 0 && n_chunks <= INT32_MAX / 3 && n_groups >= 1 && n_groups <= INT32_MAX, "jlm.train_codebook_grad: bad shape");
+    TORCH_CHECK(g.defined() && g.numel() >= 1 && order.defined(), "jlm.train_codebook_grad: g and order must be tensors");
+    const c10::hip::HIPGuard device_guard(gbook.device().index());
+    const int64_t n_order = order.numel();
+    jlm_check(jlm_train_codebook_grad(vptr<const float>(g, at::kFloat, g.numel(), "g"), (long long)g.numel(),
+                                      n_order ? vptr<const int>(order, at::kInt, n_order, "order") : nullptr, (long long)n_order,
+                                      n_chunks ? vptr<const int>(chunks, at::kInt, 3 * n_chunks, "chunks") : nullptr, (int)n_chunks,
+                                      (int)n_groups, n_chunks ? vptr<double>(partial, at::kDouble, n_chunks, "partial") : nullptr,
+                                      vptr<float>(gbook, at::kFloat, n_groups, "gbook"), stream_of(gbook)),
+              "jlm_train_codebook_grad");
+}
+
 int64_t abi_version() { return jlm_abi_version(); }
 int64_t beam_step_max_cands(int64_t beam, int64_t n_frames, int64_t mode) { return jlm_beam_step_max_cands((int)beam, (int)n_frames, (int)mode); }
 
@@ -906,6 +932,9 @@ TORCH_LIBRARY(jlm, m) {
     m.def("train_scatter_rows(Tensor dx, int ld_dx, int col0, int n_cols, int width, Tensor ids_sorted, Tensor perm, int n, Tensor(a!) demb, "
           "int ld, int v_lo, int v_hi, int key, int thr, float scale) -> ()", train_scatter_rows);
     m.def("train_adam(Tensor(a!) w, Tensor g, Tensor(b!) m, Tensor(c!) v, int n, float lr_t, Tensor? flag) -> ()", train_adam);
+    m.def("train_expand_codes(Tensor book, Tensor gid, Tensor(a!) w, int n) -> ()", train_expand_codes);
+    m.def("train_codebook_grad(Tensor g, Tensor order, Tensor chunks, int n_chunks, int n_groups, Tensor(a!) partial, Tensor(b!) gbook) -> ()",
+          train_codebook_grad);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

@@ -14,6 +14,9 @@
 // ce_kernel             one workgroup: ce = mean(lse - y[target]) in f64 -> the pass's loss slot; a non-finite loss raises the flag word.
 // scatter_rows_kernel   dEmb[w] += sum of mask (.) dx over the rows that read word w: the ids sorted, one wave per distinct word, index order.
 // adam_kernel           TensorFlow's Adam over the flat parameter buffer, 16-byte accesses; a raised flag word stops every update.
+// expand_codes_kernel   w = book[gid]: the weights of a compressed model from its codebooks (fine-tuning).
+// codebook_partial_kernel, codebook_combine_kernel
+//                       the codebook gradient: per code the sum of its elements' weight gradients, in f64, a fixed order, one writer.
 //
 // The dropout mask is a pure function of (key, element): element = row * width + column of the [N, width] array in time-major row order,
 // keep <=> splitmix64(key + G (element + 1)) >> 40 < thr, thr = ceil(keep 2^24); key = splitmix64 of (seed, step, site) from the host.
@@ -22,6 +25,7 @@
 #include <math.h>
 
 typedef unsigned long long u64;
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 #define TG_BM 64
 #define TG_BN 64
@@ -376,6 +380,83 @@ extern "C" int jlm_train_adam(float *w, const float *g, float *m, float *v, long
     long long grid = (n4 + 255) / 256;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, n4, lr_t, flag);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- codebook fine-tuning
+// (jlm_amd/finetune.py).  The weights of a compressed model are w[i] = book[gid[i]]: gid = tensor * K + code for a
+// coded element of the flat parameter buffer, -1 for the padding between tensors.
+__global__ __launch_bounds__(256) void expand_codes_kernel(const float *__restrict__ book, int n_book, const int *__restrict__ gid,
+                                                           float *__restrict__ w, long long n4) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const i32x4 id = reinterpret_cast<const i32x4 *>(gid)[i];
+        f32x4 v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (id[k] >= 0 && id[k] < n_book) ? book[id[k]] : 0.0f;
+        reinterpret_cast<f32x4 *>(w)[i] = v;
+    }
+}
+
+extern "C" int jlm_train_expand_codes(const float *book, int n_book, const int *gid, float *w, long long n, void *stream) {
+    if (!book || !gid || !w || n_book < 1 || n < 4 || (n & 3) || ((uintptr_t)gid | (uintptr_t)w) & 15) return -1;
+    const long long n4 = n / 4;
+    long long grid = (n4 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(expand_codes_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, book, n_book, gid, w, n4);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// The codebook gradient: gbook[j] = sum of g over the elements whose gid is j.  order [n_order]: the offsets of the coded elements sorted
+// by (gid, offset); chunks [n_chunks][3] = (group, begin, length): every group's run of `order` cut into pieces of at most
+// JLM_CODEBOOK_CHUNK, ascending in group, then in begin.
+// First launch: one wave per chunk.  Lane l adds elements l, l + 64, ... of the chunk in that order in f64; the 64 lane sums meet in the
+// xor butterfly 32, 16, 8, 4, 2, 1 (f64 addition commutes, so every lane holds the same bits); lane 0 writes the chunk's f64 sum.
+__global__ __launch_bounds__(256) void codebook_partial_kernel(const float *__restrict__ g, long long n, const int *__restrict__ order,
+                                                               long long n_order, const int *__restrict__ chunks, int n_chunks,
+                                                               double *__restrict__ partial) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= n_chunks) return;
+    const long long begin = chunks[3 * c + 1], len = chunks[3 * c + 2];
+    double s = 0.0;
+    if (begin >= 0 && len > 0 && begin + len <= n_order) {
+        for (long long e = lane; e < len; e += 64) {
+            const long long i = order[begin + e];
+            if (i >= 0 && i < n) s += (double)g[i];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) partial[c] = s;
+}
+
+// Second launch: one lane per group.  The group's chunks are consecutive in the table: found by bisection, added in chunk order in f64,
+// rounded to f32 once.  A group without chunks gets 0.
+__global__ __launch_bounds__(256) void codebook_combine_kernel(const int *__restrict__ chunks, int n_chunks, int n_groups,
+                                                               const double *__restrict__ partial, float *__restrict__ gbook) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_groups) return;
+    int lo = 0, hi = n_chunks;                   // the first chunk whose group is >= j
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (chunks[3 * mid] < j) lo = mid + 1; else hi = mid;
+    }
+    double s = 0.0;
+    for (int c = lo; c < n_chunks && chunks[3 * c] == j; ++c) s += partial[c];
+    gbook[j] = (float)s;
+}
+
+extern "C" int jlm_train_codebook_grad(const float *g, long long n, const int *order, long long n_order, const int *chunks, int n_chunks,
+                                       int n_groups, double *partial, float *gbook, void *stream) {
+    if (!g || !gbook || n < 1 || n_order < 0 || n_chunks < 0 || n_groups < 1 || (n_chunks > 0 && (!order || !chunks || !partial))) return -1;
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(codebook_partial_kernel, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, n, order,
+                           n_order, chunks, n_chunks, partial);
+        JLM_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(codebook_combine_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, chunks,
+                       n_chunks, n_groups, partial, gbook);
     JLM_LAUNCH_CHECK();
     return 0;
 }

@@ -394,6 +394,11 @@ class ReferenceStepper(_StepperBase):
         np.add.at(demb, ids, (dZ @ IM.T) * mask_in)
         g.update(embedding_grads(w, d, demb))
         self._g = g
+        self._update(g)
+
+    def _update(self, g):
+        """the tail of a training step: Adam over every tensor (a subclass updates something else: jlm_amd/finetune.py)"""
+        w = self.w
         self.t += 1
         for key, idx, a in list(_items(w)):
             if idx is None:
@@ -539,6 +544,13 @@ class DeviceStepper(_StepperBase):
             raise NonFiniteLoss(bad[0] if len(bad) else 0)
         return out
 
+    def _update(self):
+        """the tail of a training step, inside the step's device context: Adam over the flat parameter buffer (a subclass updates
+        something else: jlm_amd/finetune.py)"""
+        self.t += 1
+        self.ops.train_adam(self.W, self.G, self.M, self.Vv, self.n_flat, adam_lr_t(self.lr, self.t), self.flag)
+        self._mark("adam")
+
     # ---- the embedding's forms
     def _assemble_embedding(self):
         d, O, E = self.d, self.ops, self.d["E"]
@@ -665,9 +677,7 @@ class DeviceStepper(_StepperBase):
                         O.train_gemm(D, E, 1, p[vt], 1, E, g[blk], k, e0 - s0, k, E, True, None)
                         O.train_gemm(p[blk], 1, k, D, E, 1, g[vt], E, k, E, e0 - s0, True, None)
                 self._mark("weight_gradients")
-                self.t += 1
-                O.train_adam(self.W, self.G, self.M, self.Vv, self.n_flat, adam_lr_t(self.lr, self.t), self.flag)
-                self._mark("adam")
+                self._update()
             self.Hs[:B].copy_(self.Hs[T * B:])
             self.Cs[:B].copy_(self.Cs[T * B:])
 
@@ -689,12 +699,13 @@ def run_epoch(stepper, data, batch_size, num_steps, train, verbose=10):
     return float(np.exp(np.mean(stepper.losses())))
 
 
-def fit(stepper, train_data, dev_data, test_data, parameters, log=print, save=None, verbose=10):
+def fit(stepper, train_data, dev_data, test_data, parameters, log=print, save=None, verbose=10, best_pp=float("inf")):
     """train/train.py:80-102: per epoch a training and a validation pass; ``save(weights)`` when the validation perplexity improves;
     stop when epoch - best_epoch > early_stopping; then the test pass with the current weights, and one with the saved best.
+    ``best_pp``: the validation perplexity an epoch has to beat to be saved (fine-tuning starts from a model that has one).
     -> dict(best_epoch, best_valid_pp, history = [(train_pp, valid_pp)], test_pp, best_test_pp, best_weights)"""
     B, T = int(parameters["batch_size"]), int(parameters["num_steps"])
-    best_pp, best_epoch, best_weights, history = float("inf"), 0, None, []
+    best_pp, best_epoch, best_weights, history = float(best_pp), 0, None, []
     epoch = 0
     for epoch in range(int(parameters["max_epochs"])):
         log("Epoch {}".format(epoch))

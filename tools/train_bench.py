@@ -12,8 +12,13 @@
   chunk sweep   mid-tied, B = 128: the step time with TRAIN_CHUNK_BYTES = 32, 64, 128, 256 and 512 MiB
   CPU           one float32 step of the same graph by torch autograd on this machine's CPUs (mid-tied, B = 128): what there was before
   --profile N   instead of all that: N plain steps of mid-vtable at B = 128, to be run under `rocprofv3 --kernel-trace --stats --`
+  --finetune BIT [BIT ...]
+                instead of all that: the codebook fine-tuning step (jlm_amd.finetune.CodebookDeviceStepper) beside the plain training
+                step, IN THE SAME RUN: mid-tied and mid-vtable at B = 128, the codes of every tensor from kmeans_compress at BIT bits;
+                the same warm-up, timed steps and regions for both steppers, and the fine-tuning step's phases by HIP events
+                (codebook_grad, adam, expand take the place of the plain step's adam)
 
-    python tools/train_bench.py [--quick] [--profile N]
+    python tools/train_bench.py [--quick] [--profile N] [--finetune BIT ...]
 """
 import argparse
 import json
@@ -52,14 +57,64 @@ def _region(st, batches, torch):
     return time.perf_counter() - t0
 
 
+def _timed(st, batches, n_warm, torch):
+    """-> (the three regions' seconds, sorted; per-phase ms of a step over 10 marked steps)"""
+    _region(st, batches[:n_warm], torch)
+    secs = sorted(_region(st, batches, torch) for _ in range(3))
+    st.losses()
+    st.timed = True
+    for x, y in batches[:10]:
+        st.step_async(x, y)
+    ph = {k: round(v / 10, 4) for k, v in st.phase_ms().items()}
+    st.timed = False
+    return secs, ph
+
+
+def finetune_leg(bits, n_timed, n_warm, kw):
+    import torch
+    from jlm_amd import compress, finetune as F, train as T
+    out = {"bench": "finetune", "device": torch.cuda.get_device_name(0), "num_steps": T_STEPS, "batch_size": 128, "timed_steps": n_timed,
+           "warmup": n_warm, "codebook_chunk": F.CODEBOOK_CHUNK}
+    for name in ("mid-tied", "mid-vtable"):
+        cfg, w = _model(name)
+        batches = _batches(50000, 128, n_timed)
+        st = T.DeviceStepper(cfg, w, 128, T_STEPS, **kw)
+        secs, ph = _timed(st, batches, n_warm, torch)
+        plain_ms = secs[1] / n_timed * 1e3
+        out["%s plain" % name] = {"step_ms": round(plain_ms, 3), "regions_s": [round(s, 4) for s in secs], "phase_ms": ph,
+                                  "parameters": int(sum(n for _k, _i, _s, _o, n in st.layout))}
+        del st
+        torch.cuda.empty_cache()
+        for bit in bits:
+            t0 = time.perf_counter()
+            pairs = {k: compress.kmeans_compress(v, bit) for k, v in w.items()}
+            t1 = time.perf_counter()
+            st = F.CodebookDeviceStepper(cfg, {k: c for k, (c, _b) in pairs.items()}, {k: b for k, (_c, b) in pairs.items()}, 128, T_STEPS, **kw)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            secs, ph = _timed(st, batches, n_warm, torch)
+            step_ms = secs[1] / n_timed * 1e3
+            out["%s %d bit" % (name, bit)] = {
+                "step_ms": round(step_ms, 3), "plain_step_ms": round(plain_ms, 3), "ratio": round(step_ms / plain_ms, 4),
+                "regions_s": [round(s, 4) for s in secs], "phase_ms": ph, "groups": st.n_groups, "chunks": st.n_chunks,
+                "compress_s": round(t1 - t0, 3), "stepper_setup_s": round(t2 - t1, 3)}
+            del st
+            torch.cuda.empty_cache()
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--quick", action="store_true", help="10 timed steps per region, B = 128 only")
     ap.add_argument("--profile", type=int, default=0, metavar="N")
+    ap.add_argument("--finetune", type=int, nargs="+", default=None, metavar="BIT")
     args = ap.parse_args(argv)
     import torch
     from jlm_amd import train as T
     kw = dict(lr=1e-3, dropout=0.9, norm_weight=0.1, seed=1)
+    if args.finetune:
+        return finetune_leg(args.finetune, *((10, 3) if args.quick else (50, 10)), kw)
     if args.profile:
         cfg, w = _model("mid-vtable")
         st = T.DeviceStepper(cfg, w, 128, T_STEPS, **kw)
