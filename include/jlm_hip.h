@@ -680,6 +680,25 @@ int jlm_sample_rows(const float *y, int ld_y, int n_cols, int n_rows_max, const 
                     const int *row_id, const int *forced, int *done, int stop_id, int self_norm, int *word, int *ids, double *nll,
                     int *flags, void *stream);
 
+/* jlm_sample_rows_trunc: jlm_sample_rows' draw over a truncated distribution; every argument it shares with jlm_sample_rows means
+ * what it means there.  Words are ranked by (y_j descending, id ascending): a rank order of the logits, so it does not depend on
+ * the temperature.  With the masses w_j = expf((y_j - m) * inv) of jlm_sample_rows:
+ *   top_k   the kept set K is the first min(top_k, n_cols) words in rank order; top_k <= 0 or >= n_cols: off (K is every word).
+ *   top_p   (0 < top_p; >= 1: off) within K, the shortest prefix in rank order whose mass is >= top_p * mass(K); at least one word.
+ *           Top-k first, then top-p on what it kept.  The cut compares exact fixed-point sums of the f32 masses (each rounded to a
+ *           multiple of 2^-s, s = min(52, 62 - ceil(log2 n_cols))), so it does not depend on the order of summation.
+ *   draw    jlm_sample_rows' inverse CDF in word-id order over the kept words only, with the same u: the smallest kept i with
+ *           sum_{kept j <= i} w_j > u S_kept; if rounding leaves no crossing, the last kept word with mass.
+ *   temperature 0: greedy as jlm_sample_rows, whatever top_k and top_p are; top_k = 1 is the same argmax (lowest id on a tie).
+ * nll[r] is unchanged: the draw's -log p under the FULL distribution at tau = 1 (lse - y; self_norm: -y), comparable with
+ * jlm_score_frames.  forced, done / stop_id, n_dev and flags behave as in jlm_sample_rows (a NaN anywhere in a row flags it).  With
+ * both off, or temperature 0, this IS jlm_sample_rows (the same kernel).  The selection reads a row a bounded number of times
+ * (at most 9.75 with the draw, whatever top_k, top_p and n_cols are) and the result is bit-identical run to run.
+ * Returns 0, -1 for arguments the kernel cannot handle (top_p <= 0 or NaN included), or a hipError_t. */
+int jlm_sample_rows_trunc(const float *y, int ld_y, int n_cols, int n_rows_max, const int *n_dev, double temperature, uint64_t seed,
+                          int step, const int *row_id, const int *forced, int *done, int stop_id, int self_norm, int top_k, double top_p,
+                          int *word, int *ids, double *nll, int *flags, void *stream);
+
 /* The sampling loop.  Row r < n_rows is one prompt; prompts are RIGHT-aligned on n_prompt frames (the caller sorts rows by prompt
  * length, longest first, so the rows live at prompt frame f are the prefix r < n_live[f]; every row is live at frame n_prompt - 1).
  * Frame f < n_prompt consumes prompt[f][r] and continues row prev[f][r] (-1: the zero state, at a row's first frame); frame
@@ -712,6 +731,10 @@ typedef struct {
  * outside the loop's shapes, -1 / a hipError_t as the launchers do. */
 #define JLM_GENERATE_EVENTS_PER_FRAME 5
 int jlm_generate_frames(const jlm_decode_model *model_host, const jlm_generate_plan *plan_host, void *stream, void *const *events);
+
+/* jlm_generate_frames with every draw made by jlm_sample_rows_trunc(..., top_k, top_p, ...): the same loop, plan and event brackets. */
+int jlm_generate_frames_trunc(const jlm_decode_model *model_host, const jlm_generate_plan *plan_host, int top_k, double top_p,
+                              void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
  * Next-word prediction and beam-search completion (LSTM_Model.predict_top / complete, jlm_amd/complete.py): the reference's

@@ -139,6 +139,9 @@ _SIGS = {
     "jlm_score_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), P, P], c_int),
     "jlm_sample_rows": ([P, c_int, c_int, c_int, P, c_double, c_uint64, c_int, P, P, P, c_int, c_int, P, P, P, P, P], c_int),
     "jlm_generate_frames": ([POINTER(DecodeModel), POINTER(GeneratePlan), P, P], c_int),
+    "jlm_sample_rows_trunc": ([P, c_int, c_int, c_int, P, c_double, c_uint64, c_int, P, P, P, c_int, c_int, c_int, c_double, P, P, P, P, P],
+                              c_int),
+    "jlm_generate_frames_trunc": ([POINTER(DecodeModel), POINTER(GeneratePlan), c_int, c_double, P, P], c_int),
     "jlm_topk_rows": ([P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P], c_int),
     "jlm_beam_merge": ([P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P], c_int),
     "jlm_complete_frames": ([POINTER(DecodeModel), POINTER(CompletePlan), P, P], c_int),

@@ -450,8 +450,11 @@ extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan 
 
 // Ancestral sampling (include/jlm_hip.h jlm_generate_frames): the prompt frames step the LSTM of their live prefix only; every drawing
 // frame steps all rows, projects T, materialises the full-vocabulary logits (one jlm_gemm_nt per segment, columns v_start .. v_end of
-// plan.logits, + b2) and draws with sample_rows_kernel, which also writes the word the next frame consumes.
-extern "C" int jlm_generate_frames(const jlm_decode_model *m, const jlm_generate_plan *p, void *stream, void *const *events) {
+// plan.logits, + b2) and draws with sample_rows_kernel, which also writes the word the next frame consumes.  With top_k / top_p on
+// (jlm_generate_frames_trunc) the draw is sample_rows_trunc_kernel's; jlm_sample_rows_trunc launches the untruncated kernel when
+// both are off.
+static int generate_frames(const jlm_decode_model *m, const jlm_generate_plan *p, int top_k, double top_p, void *stream,
+                           void *const *events) {
     const int R = p->n_rows, P = p->n_prompt, N = p->n_words;
     if (R < 0 || P < 1 || N < 0 || !p->rows || !p->prev || !p->prompt || !p->n_live || !p->n_live_host || !p->word || !p->ids || !p->nll ||
         !p->logits)
@@ -472,11 +475,22 @@ extern "C" int jlm_generate_frames(const jlm_decode_model *m, const jlm_generate
         if (k >= 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, R, stream));
         JLM_TRY(stamp(f, 3));
         if (k >= 0)
-            JLM_TRY(jlm_sample_rows(p->logits, p->ld_logits, V, R, nullptr, p->temperature, p->seed, k, p->row_id, nullptr, p->done,
-                                    p->stop_id, m->self_norm, p->word, p->ids + (size_t)k * R, p->nll + (size_t)k * R, p->flags, stream));
+            JLM_TRY(jlm_sample_rows_trunc(p->logits, p->ld_logits, V, R, nullptr, p->temperature, p->seed, k, p->row_id, nullptr, p->done,
+                                          p->stop_id, m->self_norm, top_k, top_p, p->word, p->ids + (size_t)k * R,
+                                          p->nll + (size_t)k * R, p->flags, stream));
         JLM_TRY(stamp(f, 4));
     }
     return 0;
+}
+
+extern "C" int jlm_generate_frames(const jlm_decode_model *m, const jlm_generate_plan *p, void *stream, void *const *events) {
+    return generate_frames(m, p, 0, 1.0, stream, events);
+}
+
+extern "C" int jlm_generate_frames_trunc(const jlm_decode_model *m, const jlm_generate_plan *p, int top_k, double top_p, void *stream,
+                                         void *const *events) {
+    if (!(top_p > 0.0)) return -1;
+    return generate_frames(m, p, top_k, top_p, stream, events);
 }
 
 // Beam-search completion (include/jlm_hip.h jlm_complete_frames): the prompt frames as jlm_generate_frames' over the n_prompts prompt

@@ -19,6 +19,8 @@
 //   torch.ops.jlm.sample_rows(y, ..., word, ids, nll, flags)   one draw per row of materialised logits (jlm_sample_rows)
 //   torch.ops.jlm.generate_frames(Model, state row sets, logits, prompt arrays, ..., ids, nll, ...)
 //                             batched ancestral sampling: ONE op (jlm_generate_frames; LSTM_Model.generate)
+//   torch.ops.jlm.sample_rows_trunc / generate_frames_trunc(..., top_k, top_p, ...)
+//                             the same two with a top-k / nucleus cut of every draw (jlm_sample_rows_trunc, jlm_generate_frames_trunc)
 //   torch.ops.jlm.topk_rows(y, ..., k, ids, nll, flags)        the k best words of every row of materialised logits (jlm_topk_rows)
 //   torch.ops.jlm.beam_merge(cand_ids, cand_nll, ...)          one beam selection per prompt (jlm_beam_merge)
 //   torch.ops.jlm.complete_frames(Model, state row sets, logits, prompt arrays, ..., back-pointers, ...)
@@ -572,21 +574,50 @@ void sample_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, co
               "jlm_sample_rows");
 }
 
+// sample_rows with a top-k / nucleus cut of the draw (jlm_sample_rows_trunc, include/jlm_hip.h): top_k <= 0 or >= n_cols and
+// top_p >= 1 mean off.
+void sample_rows_trunc(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, double temperature,
+                       int64_t seed, int64_t step, const OptTensor &row_id, const OptTensor &forced, const OptTensor &done,
+                       int64_t stop_id, bool self_norm, int64_t top_k, double top_p, const Tensor &word, const Tensor &ids,
+                       const Tensor &nll, const OptTensor &flags) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    auto opt_ok = [&](const OptTensor &t, at::ScalarType ty, int64_t n) { return !t.has_value() || !t->defined() || is(*t, ty, n); };
+    TORCH_CHECK(top_p > 0.0, "jlm.sample_rows_trunc: top_p in (0, 1] (>= 1: off)");
+    TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.sample_rows_trunc: y [n_rows, ld] float32");
+    TORCH_CHECK(is(word, at::kInt, n_rows) && is(ids, at::kInt, n_rows) && is(nll, at::kDouble, n_rows) && opt_ok(n_dev, at::kInt, 1) &&
+                    opt_ok(row_id, at::kInt, n_rows) && opt_ok(forced, at::kInt, n_rows) && opt_ok(done, at::kInt, n_rows) &&
+                    opt_ok(flags, at::kInt, 1),
+                "jlm.sample_rows_trunc: int32 word / ids / row_id / forced / done [n_rows], n_dev / flags [1]; float64 nll [n_rows]");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    const int k = (int)std::min<int64_t>(std::max<int64_t>(top_k, 0), INT32_MAX);
+    jlm_check(jlm_sample_rows_trunc(ptr<const float>(y, "y"), (int)ld, (int)n_cols, (int)n_rows, optr<const int>(n_dev, "n_dev"),
+                                    temperature, (uint64_t)seed, (int)step, optr<const int>(row_id, "row_id"),
+                                    optr<const int>(forced, "forced"), optr<int>(done, "done"), (int)stop_id, self_norm ? 1 : 0, k, top_p,
+                                    ptr<int>(word, "word"), ptr<int>(ids, "ids"), ptr<double>(nll, "nll"), optr<int>(flags, "flags"),
+                                    stream_of(y)),
+              "jlm_sample_rows_trunc");
+}
+
 // batched ancestral sampling (jlm_generate_frames, include/jlm_hip.h): state row sets h0/c0 and h1/c1 (ping-pong), T [n_rows, ldt]
 // unless the model is untied f32, logits [n_rows, ld_logits]; rows / row_id / word / done [n_rows], prev / prompt [n_prompt][n_rows],
 // n_live [n_prompt] int32 and its host copy; ids [n_words][n_rows] int32, nll [n_words][n_rows] f64, flags one int32.  Every id must
 // lie in [0, V): the caller checks (jlm_amd/generate.py).  -> timed: [frames, 4] milliseconds per frame (LSTM step, T projection,
 // logit GEMMs, draw) after waiting for the last frame; else an empty tensor and nothing waits.
-Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
-                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
-                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &row_id,
-                       const Tensor &word, const OptTensor &done, int64_t stop_id, double temperature, int64_t seed, const Tensor &ids,
-                       const Tensor &nll, const OptTensor &flags, int64_t n_rows, int64_t n_prompt, int64_t n_words, bool timed) {
+// generate_frames_trunc: the same with every draw cut to its top_k words and then its top_p nucleus (jlm_generate_frames_trunc);
+// top_k <= 0 (or >= V) and top_p >= 1 mean off, and with both off it is generate_frames.
+Tensor generate_frames_trunc(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1,
+                             const Tensor &c1, const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows,
+                             const Tensor &prev, const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host,
+                             const Tensor &row_id, const Tensor &word, const OptTensor &done, int64_t stop_id, double temperature,
+                             int64_t seed, const Tensor &ids, const Tensor &nll, const OptTensor &flags, int64_t n_rows, int64_t n_prompt,
+                             int64_t n_words, bool timed, int64_t top_k, double top_p) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, P = n_prompt, N = n_words;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
     auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(P >= 1 && N >= 0, "jlm.generate_frames: n_prompt >= 1 and n_words >= 0");
+    TORCH_CHECK(top_p > 0.0, "jlm.generate_frames_trunc: top_p in (0, 1] (>= 1: off)");
+    top_k = std::min<int64_t>(std::max<int64_t>(top_k, 0), INT32_MAX);
     check_row_sets("generate_frames", m, R, h0, c0, h1, c1, n_live_host, P, "prompt frame", R);
     TORCH_CHECK(is(rows, at::kInt, R) && is(row_id, at::kInt, R) && is(word, at::kInt, R) && (!has(done) || is(*done, at::kInt, R)) &&
                     is(prev, at::kInt, P * R) && is(prompt, at::kInt, P * R) && is(n_live, at::kInt, P),
@@ -607,8 +638,20 @@ Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     p.row_id = ptr<const int>(row_id, "row_id"); p.word = ptr<int>(word, "word"); p.done = optr<int>(done, "done");
     p.stop_id = (int)stop_id; p.temperature = temperature; p.seed = (uint64_t)seed;
     p.ids = ptr<int>(ids, "ids"); p.nll = ptr<double>(nll, "nll"); p.flags = optr<int>(flags, "flags");
-    return launch_frames("jlm_generate_frames", h0.device().index(), timed, N > 0 && R > 0 ? P + N - 1 : 0, JLM_GENERATE_EVENTS_PER_FRAME,
-                         [&](hipStream_t st, void *const *ev) { return jlm_generate_frames(&m, &p, st, ev); });
+    const bool trunc = top_k > 0 || top_p < 1.0;
+    return launch_frames(trunc ? "jlm_generate_frames_trunc" : "jlm_generate_frames", h0.device().index(), timed,
+                         N > 0 && R > 0 ? P + N - 1 : 0, JLM_GENERATE_EVENTS_PER_FRAME, [&](hipStream_t st, void *const *ev) {
+                             return trunc ? jlm_generate_frames_trunc(&m, &p, (int)top_k, top_p, st, ev) : jlm_generate_frames(&m, &p, st, ev);
+                         });
+}
+
+Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
+                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &row_id,
+                       const Tensor &word, const OptTensor &done, int64_t stop_id, double temperature, int64_t seed, const Tensor &ids,
+                       const Tensor &nll, const OptTensor &flags, int64_t n_rows, int64_t n_prompt, int64_t n_words, bool timed) {
+    return generate_frames_trunc(model, h0, c0, h1, c1, T, logits, ld_logits, rows, prev, prompt, n_live, std::move(n_live_host), row_id,
+                                 word, done, stop_id, temperature, seed, ids, nll, flags, n_rows, n_prompt, n_words, timed, 0, 1.0);
 }
 
 // the k best words of every row of f32 logits y [n_rows, ld] with their -log p (jlm_topk_rows, include/jlm_hip.h): ids int32 and nll
@@ -902,6 +945,15 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(g!) word, Tensor(h!)? done, int stop_id, float temperature, int seed, Tensor(i!) ids, Tensor(j!) nll, Tensor(k!)? flags, "
           "int n_rows, int n_prompt, int n_words, bool timed) -> Tensor",
           generate_frames);
+    m.def("sample_rows_trunc(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, float temperature, int seed, int step, Tensor? row_id, "
+          "Tensor? forced, Tensor(a!)? done, int stop_id, bool self_norm, int top_k, float top_p, Tensor(b!) word, Tensor(c!) ids, "
+          "Tensor(d!) nll, Tensor(e!)? flags) -> ()",
+          sample_rows_trunc);
+    m.def("generate_frames_trunc(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, "
+          "Tensor(e!)? T, Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev, Tensor prompt, Tensor n_live, int[] n_live_host, "
+          "Tensor row_id, Tensor(g!) word, Tensor(h!)? done, int stop_id, float temperature, int seed, Tensor(i!) ids, Tensor(j!) nll, "
+          "Tensor(k!)? flags, int n_rows, int n_prompt, int n_words, bool timed, int top_k, float top_p) -> Tensor",
+          generate_frames_trunc);
     m.def("topk_rows(Tensor y, int ld, int n_cols, int n_rows, int k, bool self_norm, Tensor(a!) ids, Tensor(b!) nll, int ld_out, "
           "Tensor(c!)? flags) -> ()",
           topk_rows);

@@ -937,16 +937,19 @@ class LSTM_Model():
         _seq, tok, h2, c2 = self._scorer().run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
         return np.ascontiguousarray(tok.T), h2, c2
 
-    def generate(self, prompts=None, n_words=100, temperature=1.0, seed=0, stop_id=None, max_rows=None):
+    def generate(self, prompts=None, n_words=100, temperature=1.0, seed=0, stop_id=None, max_rows=None, top_k=None, top_p=None):
         """Ancestral sampling on the device (jlm_amd/generate.py): the reference's sampling loop (model.py:213-245, one predict() and
         one sample() per word) for many rows at once.  ``prompts``: R word-id lists of length >= 1 (None: one row starting at <eos>, the
         reference's starting_text).  Row r starts from the zero state, consumes its prompt, then draws ``n_words`` words from
         softmax(y / temperature) (0: greedy, the lowest id winning a tie) with the counter-based u of generate.uniform(seed, step, r);
-        with ``stop_id`` a row ends after drawing it.  -> (ids, nll): per row an int64 array of its draws and a float64 array of their
-        -log p at temperature 1 (score()'s convention).  ValueError for a bad argument before anything runs; JlmHipError when the
-        device flags a non-finite logit or log-normaliser."""
+        with ``stop_id`` a row ends after drawing it.  ``top_k`` (integer >= 1) keeps the k most probable words of every draw, ranked by
+        (logit descending, id ascending); ``top_p`` (0 < p <= 1) then keeps the shortest head of those whose mass reaches p times
+        theirs (nucleus sampling); the draw is the same inverse CDF over the kept words, renormalised.  None, top_k >= V and
+        top_p >= 1 mean off.  -> (ids, nll): per row an int64 array of its draws and a float64 array of their -log p at temperature 1
+        under the full, untruncated distribution (score()'s convention, whatever top_k and top_p are).  ValueError for a bad
+        argument before anything runs; JlmHipError when the device flags a non-finite logit or log-normaliser."""
         from .generate import generate
-        return generate(self._generator(), prompts, n_words, temperature, seed, stop_id, max_rows)
+        return generate(self._generator(), prompts, n_words, temperature, seed, stop_id, max_rows, top_k, top_p)
 
     def predict_top(self, contexts, n=10, max_rows=None):
         """The ``n`` most probable next words after each context, on the device (jlm_amd/complete.py; the reference's

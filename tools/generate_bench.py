@@ -4,6 +4,8 @@
   rows            256, 1 024 and 2 560 rows from <eos>, 20 draws each, temperature 1
   per frame       event times of LSTM step / T projection / logit GEMMs / draw at each row count (Generator.run(timed=True)),
                   the logit GEMMs' share of a frame, and tokens/s from the events
+  truncation      the draw bracket and the frame with top_k = 40, top_p = 0.9 and both, beside the untruncated draw (the same
+                  timed call; mid-vtable at 256 and 2 560 rows, mid-tied at 2 560)
   baseline        the host loop of model.main (one predict() and one sample() per word) at one row
 
     python tools/generate_bench.py [--root DIR] [--repeats N] [--quick]
@@ -76,6 +78,17 @@ def main(argv=None):
                                                "total": round(tot * 1e3, 2)},
                                   "logit_gemm_frac": round(float(med[2]) / tot, 4), "draw_frac": round(float(med[3]) / tot, 4),
                                   "tokens_per_s_from_events": round(R / (tot * 1e-3), 1)}
+            if R == 2560 or (R == 256 and name == "mid-vtable"):
+                trunc = res["rows_%d" % R]["truncated_frame_us"] = {}
+                for label, k, p in (("none", None, None), ("top_k_40", 40, None), ("top_p_0.9", None, 0.9), ("top_k_40_top_p_0.9", 40, 0.9)):
+                    draws = []
+                    for _ in range(reps):
+                        gen.run([np.array([G.EOS_ID])] * R, np.arange(R, dtype=np.int32), N, 1.0, 1, timed=True, top_k=k, top_p=p)
+                        draws.append(np.median(gen.last_frame_ms, axis=0))
+                    med = np.median(draws, axis=0)
+                    trunc[label] = {"logit_gemm": round(float(med[2]) * 1e3, 2), "draw": round(float(med[3]) * 1e3, 2),
+                                    "draw_min_max": [round(float(np.min(draws, axis=0)[3]) * 1e3, 2), round(float(np.max(draws, axis=0)[3]) * 1e3, 2)],
+                                    "total": round(float(med.sum()) * 1e3, 2)}
         if name == "mid-vtable":
             # the host loop it replaces: model.main's predict() + sample() per word, one row
             n_host = 10 if args.quick else 50
