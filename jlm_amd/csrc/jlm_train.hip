@@ -8,7 +8,7 @@
 // embed_rows_kernel     x = mask (.) Emb[id]: the step's input rows.
 // cell_fwd_kernel       z -> i, f, o, g (kept, in place), c, h, and the dropped output r = mask (.) h.
 // cell_bwd_kernel       dh = mask (.) dr + dh_next, dc -> dz [B, 4H], dc_prev.
-// lse_update_kernel     one wave per row: the chunk's (max, sum exp) merged into the row's running pair, chunks in launch order.
+// lse_update_kernel     one wave per row: the chunk's (max, sum exp), granule of 64 words by granule, merged into the row's running pair.
 // dy_kernel             logits of a chunk -> dy = s (p (1 + 2 nw lse) - onehot) in place; the target's logit is met on the way.
 // colsum_kernel         out[c] (+)= sum over rows in row order (db2 of a chunk, the gate biases).
 // ce_kernel             one workgroup: ce = mean(lse - y[target]) in f64 -> the pass's loss slot; a non-finite loss raises the flag word.
@@ -202,21 +202,24 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// The chunk is met in granules of 64 words from its first: a granule's (max, sum exp) comes from one value per lane through the xor
+// butterflies and is merged into the row's running pair, granules in order.  A chunk that starts at a multiple of 64 words of the
+// vocabulary (DeviceStepper's windows do) therefore leaves the same bits as any other cut of the same words into such chunks.
 __global__ __launch_bounds__(256) void lse_update_kernel(const float *__restrict__ y, long long ld, int n_cols, int n_rows,
                                                          float *__restrict__ run_m, float *__restrict__ run_s, int first) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n_rows) return;
     const float *yr = y + (long long)row * ld;
-    float m = JLM_NEG_BIG;
-    for (int c = lane; c < n_cols; c += 64) m = fmaxf(m, yr[c]);
-    m = wave_max(m);
-    float s = 0.0f;
-    for (int c = lane; c < n_cols; c += 64) s += expf(yr[c] - m);
-    s = wave_sum(s);
-    if (lane == 0) {
-        float M0 = JLM_NEG_BIG, S0 = 0.0f;
-        if (!first) { M0 = run_m[row]; S0 = run_s[row]; }
+    float M0 = JLM_NEG_BIG, S0 = 0.0f;                     // every lane carries the pair: the butterflies leave all lanes the same bits
+    if (!first) { M0 = run_m[row]; S0 = run_s[row]; }
+    for (int c0 = 0; c0 < n_cols; c0 += 64) {
+        const int c = c0 + lane;
+        const float v = c < n_cols ? yr[c] : JLM_NEG_BIG;
+        const float m = wave_max(v);
+        const float s = wave_sum(c < n_cols ? expf(v - m) : 0.0f);
         lse_merge(M0, S0, m, s);
+    }
+    if (lane == 0) {
         run_m[row] = M0;
         run_s[row] = S0;
     }

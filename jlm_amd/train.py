@@ -469,7 +469,8 @@ class DeviceStepper(_StepperBase):
             self.dc, self.dh = z(B, H), z(B, H)
             self.run_m, self.run_s, self.tgt = z(N), z(N), z(N)
             budget = TRAIN_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
-            self.Vc = int(min(V, max(64, budget // (4 * N) // 4 * 4)))
+            # a multiple of 64 words: every window then starts on a granule of train_lse_update, and the normaliser does not depend on Vc
+            self.Vc = int(min(V, max(64, budget // (4 * N) // 64 * 64)))
             self.Y = z(N, self.Vc)
             self.flag = z(1, dtype=torch.int32)
             self.ce = z(256, dtype=torch.float64)

@@ -97,19 +97,11 @@ def test_codebook_grad_without_chunks():
 _models = {}
 
 
-def _grid_quantise(v, K):
-    """a tensor on K evenly spaced levels between its extremes (Glorot weights are uniform, so this is close to what k-means finds, at
-    no cost): -> (code uint8, codebook float32 [K, 1]).  At K = 256 the 64-element biases leave most codes empty."""
-    book = np.linspace(float(v.min()), float(v.max()), K).astype(np.float32)
-    code = np.rint((v.astype(np.float64) - float(v.min())) / (float(v.max()) - float(v.min())) * (K - 1)).astype(np.uint8)
-    return code, book.reshape(K, 1)
-
-
 def _model(mode, bit):
     """(cfg, codes, books): Glorot weights quantised per tensor (computed once per case)"""
     if (mode, bit) not in _models:
         cfg = synth.make_config(600, 64, 32, mode, [(32, 0, 150), (16, 150, 360), (8, 360, None)], True)
-        pairs = {k: _grid_quantise(v, 1 << bit) for k, v in T.init_weights(cfg, None, 101).items()}
+        pairs = {k: tc.grid_quantise(v, 1 << bit) for k, v in T.init_weights(cfg, None, 101).items()}
         _models[(mode, bit)] = (cfg, {k: c for k, (c, _b) in pairs.items()}, {k: b for k, (_c, b) in pairs.items()})
     return _models[(mode, bit)]
 
@@ -119,12 +111,6 @@ def _batch(V, B, Tn, seed):
     return rng.randint(0, V, (B, Tn)), rng.randint(0, V, (B, Tn))
 
 
-def _image(st):
-    w, b, c = st.weights(), st.codebooks(), st.codes()
-    for k in c:
-        assert w[k].dtype == np.float32 and w[k].tobytes() == np.take(b[k], c[k]).tobytes(), k
-
-
 @pytest.mark.parametrize("mode,bit,B,Tn", [("tied", 3, 32, 10), ("tied", 8, 32, 10), ("vtable", 3, 32, 10), ("vtable", 8, 32, 10),
                                            ("vtable", 3, 13, 7)])
 def test_one_step(mode, bit, B, Tn):
@@ -132,7 +118,7 @@ def test_one_step(mode, bit, B, Tn):
     kw = dict(lr=1e-3, dropout=0.9, norm_weight=0.1, seed=42)
     ref = F.CodebookReferenceStepper(cfg, codes, books, B, Tn, **kw)
     dev = F.CodebookDeviceStepper(cfg, codes, books, B, Tn, **kw)
-    _image(dev)
+    tc.codebook_image(dev)
     for k in codes:
         assert dev.codebooks()[k].tobytes() == books[k].tobytes()
     rng = np.random.RandomState(4)
@@ -147,7 +133,7 @@ def test_one_step(mode, bit, B, Tn):
     print("worst relative codebook-gradient deviation per tensor: %s" % {k: "%.1e" % v for k, v in worst.items()})
     for k, v in worst.items():
         assert v <= 1e-4, (k, v)
-    _image(dev)
+    tc.codebook_image(dev)
     assert any(dev.codebooks()[k].tobytes() != books[k].tobytes() for k in codes)
     for k in codes:
         assert np.array_equal(dev.codes()[k], codes[k])
@@ -178,7 +164,7 @@ def test_twenty_steps(mode, bit, lr):
         assert np.any(bd[k][~empty] != books[k][~empty]), k
         n_empty += int(empty.sum())
     assert (n_empty > 0) == (bit == 8)
-    _image(dev)
+    tc.codebook_image(dev)
 
 
 # ---- 11, 12. the driver

@@ -1,5 +1,6 @@
-"""Shared helpers of tests/test_train_cpu.py and tests/test_gpu_train.py: the Markov corpus, the model configurations, and the training
-graph restated in torch (autograd) -- the test's own words for reference train/model.py, independent of jlm_amd.train's backward pass."""
+"""Shared helpers of tests/test_train_cpu.py, tests/test_gpu_train.py and tests/test_gpu_train_shapes.py: the Markov corpus, the model
+configurations (the odd-sized one among them), and the training graph restated in torch (autograd) -- the test's own words for
+reference train/model.py, independent of jlm_amd.train's backward pass."""
 import os
 
 import numpy as np
@@ -154,3 +155,61 @@ def flat_items(w):
                 yield "%s[%d]" % (k, i), np.asarray(a)
         else:
             yield k, np.asarray(w[k])
+
+
+# ---- the odd-sized model of tests/test_gpu_train_shapes.py: no size a multiple of 4, so the flat parameter buffer has padding
+ODD_V, ODD_H = 157, 23
+ODD_SEGS = [(19, 0, 40), (9, 40, 93), (5, 93, None)]
+
+
+def odd_cfg(mode, self_norm=True):
+    """V = 157, H = 23, segment widths 19 / 9 / 5: E = 19 (tied, V_table) or 33 (D_softmax).  b2, PM, LM, LM1, VT1 and VT2 have sizes
+    that are no multiple of 4, so the device's flat buffer pads them."""
+    return small_cfg(mode, ODD_V, ODD_H, 19, self_norm, segs=ODD_SEGS)
+
+
+def batch(V, B, Tn, seed):
+    rng = np.random.RandomState(seed)
+    return rng.randint(0, V, (B, Tn)), rng.randint(0, V, (B, Tn))
+
+
+def carried_state(B, H, seed):
+    """a non-zero h, c ~ N(0, 0.3): with it no gradient tensor of a step is identically zero"""
+    rng = np.random.RandomState(seed)
+    return rng.normal(0, 0.3, (B, H)).astype(np.float32), rng.normal(0, 0.3, (B, H)).astype(np.float32)
+
+
+def padding_mask(layout, n_flat):
+    """bool [n_flat]: True on the words of DeviceStepper's flat buffer that belong to no tensor"""
+    pad = np.ones(int(n_flat), dtype=bool)
+    for _key, _idx, _shape, off, n in layout:
+        pad[off:off + n] = False
+    return pad
+
+
+def worst_relative(got, want):
+    """per tensor: the largest deviation in units of the reference tensor's largest magnitude (dump-shaped dicts)"""
+    want, got = dict(flat_items(want)), dict(flat_items(got))
+    assert sorted(want) == sorted(got)
+    out = {}
+    for k in want:
+        scale = np.abs(want[k]).max()
+        assert scale > 0, k                                  # an all-zero reference tensor would make its bar vacuous
+        out[k] = float(np.abs(got[k] - want[k]).max() / scale)
+    return out
+
+
+# ---- fine-tuning: the quantiser and the image check of tests/test_gpu_finetune.py and tests/test_gpu_train_shapes.py
+def grid_quantise(v, K):
+    """a tensor on K evenly spaced levels between its extremes (Glorot weights are uniform, so this is close to what k-means finds, at
+    no cost): -> (code uint8, codebook float32 [K, 1]).  At K = 256 the 64-element biases leave most codes empty."""
+    book = np.linspace(float(v.min()), float(v.max()), K).astype(np.float32)
+    code = np.rint((v.astype(np.float64) - float(v.min())) / (float(v.max()) - float(v.min())) * (K - 1)).astype(np.uint8)
+    return code, book.reshape(K, 1)
+
+
+def codebook_image(st):
+    """every weight of a fine-tuning stepper is exactly take(codebook, code), float32"""
+    w, b, c = st.weights(), st.codebooks(), st.codes()
+    for k in c:
+        assert w[k].dtype == np.float32 and w[k].tobytes() == np.take(b[k], c[k]).tobytes(), k
