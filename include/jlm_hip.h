@@ -407,6 +407,20 @@ int jlm_pack_t_mixed(const jlm_segment *segs_host, const float *t_scale, int n_s
  *   jlm_decode_model.mixed_s8[i] = 0 for every mixed segment makes jlm_decode_frames / jlm_lse_probe use the two above. */
 int jlm_pack_t_mixed6(const jlm_segment *segs_host, const float *t_scale, int n_segs, const float *T, int ldt, const int *rows,
                       int n_rows_max, const int *n_dev, void *Tm, int ld_tm, void *stream);
+/* ABI 12 (additive): the tail of a decode frame between the T projection and the normaliser as ONE launch (csrc/jlm_frame_tail.hip) --
+ * jlm_pack_t_mixed6 of the frame's live rows and jlm_edge_logits of its cells, to the bit.  One workgroup per cell j < n_groups of
+ * frame `frame` (cell j is sentence j: g0, cnt_idx, wl_idx, sent_len and live_base are indexed by j, so the caller passes the frame's
+ * slices): it stages the cell's rows T[g0[j] .. + min(cnt[cnt_idx[j]], beam)) in LDS once, writes edge[] for the words of list
+ * wl_base + wl_idx[j] like jlm_edge_logits, and -- when frame < sent_len[j], i.e. the rows are in the frame's live list -- packs row
+ * g0[j] + slot into Tm at the compact row live_base[j] + slot (what beam_step_kernel recorded), like jlm_pack_t_mixed6 over that list.
+ * segs: the f32 segments of the edge logits; mixed_segs / t_scale / n_mixed / ld_tm: as jlm_pack_t_mixed6.
+ * -2: a shape the kernel does not host (beam > 16, k > 256, more than 8 blocks in a segment, more than 32 KB of LDS): the caller
+ * launches the two kernels.  jlm_pack_edge_mx6_lds_bytes: the launch's LDS at row stride ldt (pure host; -1: ldt not a multiple of 4). */
+int jlm_pack_edge_mx6(const jlm_segment *segs_host, int n_segs, const float *b2, const jlm_segment *mixed_segs, const float *t_scale,
+                      int n_mixed, const float *T, int ldt, const int *g0, const int *cnt, const int *cnt_idx, const int *wl,
+                      const int *wl_off, const int *wl_idx, int wl_base, const int *wl_out, float *edge, int beam, int n_groups,
+                      const int *sent_len, const int *live_base, int frame, void *Tm, int ld_tm, void *stream);
+int jlm_pack_edge_mx6_lds_bytes(int ldt);
 /* segs[i].B = mixed rows, segs[i].ldb = 32 nb, segs[i].k the true contraction length; descale[i] = 2^-(eT_i + eB_i), s8[i] as
  * above; Tm = the packed hypothesis rows.  Same partial-slice contract and return value as jlm_vocab_lse_split; -2: a shape
  * this form does not take (more than 8 blocks; segments of both bias forms in one launch).

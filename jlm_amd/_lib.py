@@ -130,6 +130,9 @@ _SIGS = {
     "jlm_pack_t_mixed6": ([POINTER(Segment), POINTER(c_float), c_int, P, c_int, P, c_int, P, P, c_int, P], c_int),
     "jlm_vocab_lse_mixed": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), P, c_int, P, c_int, P, c_int, c_int, c_int, P, P],
                             c_int),
+    "jlm_pack_edge_mx6": ([POINTER(Segment), c_int, P, POINTER(Segment), POINTER(c_float), c_int, P, c_int, P, P, P, P, P, P, c_int, P, P,
+                           c_int, c_int, P, P, c_int, P, c_int, P], c_int),
+    "jlm_pack_edge_mx6_lds_bytes": ([c_int], c_int),
     "jlm_backtrace": ([POINTER(Lattice), POINTER(BeamState), P, P, P, c_int, P], c_int),
     "jlm_vocab_lse_mixed_fr": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), P, c_int, P, c_int, P, c_int, c_int, c_int, P, P],
                             c_int),

@@ -2,6 +2,7 @@
 // Host code only: it enqueues the launchers of jlm_gemm.hip / jlm_split.hip / jlm_beam.hip in the order
 // jlm_amd/engine.py documents, so a batch costs one FFI call instead of ~170.
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 #include "../../include/jlm_hip.h"
 
 namespace {
@@ -192,6 +193,29 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
 #else
 #define JLM_SKIPPED(bit) 0
 #endif
+    // The fused frame tail (jlm_pack_edge_mx6, csrc/jlm_frame_tail.hip): the full-vocabulary decode of a model whose every segment is on
+    // mx6 rows packs the live rows inside the edge-logit launch -- one launch and one pass over T less per frame.  JLM_FUSE_TAIL=0 keeps
+    // the two launches (A/B runs); so does a probe build that leaves one of the two out, so that the probe means what it says.
+    jlm_segment tail_segs[JLM_MAX_SEGMENTS];
+    float tail_ts[JLM_MAX_SEGMENTS];
+    bool fuse_tail = false;
+    if (full && !m->self_norm && !full_lse_tile_form(m) && jlm_model_mx6(m) && m->split_segs && p->Tm && st.live_base && !JLM_SKIPPED(1 | 32)) {
+        static const bool on = [] { const char *e = getenv("JLM_FUSE_TAIL"); return !e || atoi(e) != 0; }();
+        fuse_tail = on;
+        for (int i = 0; i < m->n_segs && fuse_tail; ++i) {
+            if (!m->mixed_segs[i].B || m->mixed_s8[i] != 0.0f) {
+                fuse_tail = false;
+                break;
+            }
+            tail_segs[i] = m->mixed_segs[i];
+            tail_ts[i] = m->mixed_t_scale[i];
+        }
+        // (no groups: the launcher only says whether it hosts the shape -- beam <= 16, k <= 256, 32 KB of LDS)
+        if (fuse_tail && jlm_pack_edge_mx6(m->segs, m->n_segs, m->b2, tail_segs, tail_ts, m->n_segs, p->T, m->ldt, p->g0, st.cnt, p->cidx, p->sg_word,
+                                           p->sg_off, p->sidx, 0, p->sg_node, p->edge, beam, 0, lat->sent_len, st.live_base, 0, p->Tm, p->ld_tm,
+                                           stream) != 0)
+            fuse_tail = false;
+    }
     for (int f = 0; f < F; ++f) {
         if (join) {
             JLM_HIP(hipStreamWaitEvent(main_s, join, 0));
@@ -237,19 +261,23 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
         // the packed rows of the normaliser's mixed segments, behind T (the normaliser itself runs after the edge logits: full_lse_run);
         // slices of a tile-form normaliser (k > 256) are folded by the next frame's beam step like the others
         FullLse fl;
-        if (full) JLM_TRY(full_lse_pack(m, p->T, rows, f == 0 ? B : rmax, ndev, p->Tm, p->ld_tm, JLM_SKIPPED(32), fl, stream));
+        if (full) JLM_TRY(full_lse_pack(m, p->T, rows, f == 0 ? B : rmax, ndev, p->Tm, p->ld_tm, JLM_SKIPPED(32) || fuse_tail, fl, stream));
         const int cell = f * B;
         void *est = stream;
-        if (side_s) {          // the edge logits need only T: they run beside the normaliser
+        if (fuse_tail) {       // packing and edge logits in one launch behind T, on the main stream: nothing is left to run beside the normaliser
+            JLM_TRY(jlm_pack_edge_mx6(m->segs, m->n_segs, m->b2, tail_segs, tail_ts, m->n_segs, p->T, m->ldt, p->g0 + cell, st.cnt, p->cidx + cell,
+                                      p->sg_word, p->sg_off, p->sidx, cell, p->sg_node, p->edge, beam, B, lat->sent_len, st.live_base + cell, f,
+                                      p->Tm, p->ld_tm, stream));
+        } else if (side_s) {   // the edge logits need only T: they run beside the normaliser
             hipEvent_t fork;
             JLM_HIP(g_events.get(&fork));
             JLM_HIP(hipEventRecord(fork, main_s));
             JLM_HIP(hipStreamWaitEvent(side_s, fork, 0));
             est = side_stream;
         }
-        if (!JLM_SKIPPED(1)) JLM_TRY(jlm_edge_logits_perm(m->segs, m->n_segs, m->b2, p->T, m->ldt, p->g0 + cell, st.cnt, p->cidx + cell, p->sg_word,
+        if (!fuse_tail && !JLM_SKIPPED(1)) JLM_TRY(jlm_edge_logits_perm(m->segs, m->n_segs, m->b2, p->T, m->ldt, p->g0 + cell, st.cnt, p->cidx + cell, p->sg_word,
                                      perm ? p->sg_wword : nullptr, p->sg_off, p->sidx, cell, p->sg_node, p->edge, beam, B, est));
-        if (side_s) {
+        if (side_s && !fuse_tail) {
             JLM_HIP(g_events.get(&join));
             JLM_HIP(hipEventRecord(join, side_s));
         }
