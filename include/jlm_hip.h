@@ -764,6 +764,18 @@ int jlm_generate_frames_trunc(const jlm_decode_model *model_host, const jlm_gene
 int jlm_topk_rows(const float *y, int ld_y, int n_cols, int n_rows, int k, int self_norm, int *ids, double *nll, int ld_out, int *flags,
                   void *stream);
 
+/* jlm_topk_rows with each row's candidates restricted to a word set.  mask: [n_sets][ld_mask] 32-bit words on the device, bit w & 31 of
+ * word w >> 5 of set s says that word w is allowed (ld_mask >= ceil(n_cols / 32)); row_set: [n_rows] device ints, the set of row r, or
+ * -1 for an unrestricted row, which loads no mask and gives jlm_topk_rows' output bit for bit.  The log-normaliser is jlm_topk_rows':
+ * it runs over every word of the row, in the same order and arithmetic, so nll stays -log p under the full distribution and a
+ * disallowed word may hold the row's maximum.  Only allowed words are ranked (y descending, id ascending; NaN never ranks, -inf
+ * does).  A restricted row with m < k rankable words returns those m, then ids -1 and nll +inf at m .. k - 1: no error, no flag.  A
+ * non-finite max or sum flags the row as jlm_topk_rows does (ids -1, nll NaN), whether or not the offending word is allowed; so does a
+ * row_set[r] outside [-1, n_sets), which indexes nothing (torch.ops.jlm.topk_rows_masked refuses it on the host).  Argument checks as
+ * jlm_topk_rows, and n_sets >= 0, row_set != NULL, with n_sets > 0 mask != NULL and ld_mask as above.  n_sets = 0 needs no mask. */
+int jlm_topk_rows_masked(const float *y, int ld_y, int n_cols, int n_rows, int k, int self_norm, const unsigned *mask, int ld_mask,
+                         int n_sets, const int *row_set, int *ids, double *nll, int ld_out, int *flags, void *stream);
+
 /* jlm_beam_merge: one beam-search selection per prompt p < n_prompts over per-row top-`beam` lists (jlm_topk_rows with k = ld_out =
  * beam).  first != 0: the prompt's one candidate row is p, its score 0; else rows p * beam + j, j < beam (rank j of the previous beam)
  * with score[row] and finished[row].  A candidate is (score + nll, parent rank j, word); a finished parent gives one carry (its score,
@@ -808,6 +820,15 @@ typedef struct {
  * 1 <= beam <= min(JLM_TOPK_MAX, V).  Returns 0, -2 for a model outside the loop's shapes, -1 / a hipError_t as the launchers do. */
 #define JLM_COMPLETE_EVENTS_PER_FRAME 6
 int jlm_complete_frames(const jlm_decode_model *model_host, const jlm_complete_plan *plan_host, void *stream, void *const *events);
+
+/* jlm_complete_frames with the first generated word of prompt p restricted to set prompt_set[p] (device ints [n_prompts], -1:
+ * unrestricted) of mask [n_sets][ld_mask] (device, as jlm_topk_rows_masked's): selecting frame 0 selects with jlm_topk_rows_masked,
+ * every later frame is jlm_complete_frames'.  The same loop, plan and event brackets.  A set with fewer than `beam` rankable words
+ * leaves frame 0's list padded with (-1, +inf); jlm_beam_merge turns a padded candidate into a finished hypothesis of score +inf (word
+ * -1), which is carried, never expanded, ranks behind every finite candidate and leaves the beam as soon as the live hypotheses offer
+ * `beam` candidates: the caller drops final hypotheses whose score is not finite. */
+int jlm_complete_frames_masked(const jlm_decode_model *model_host, const jlm_complete_plan *plan_host, const unsigned *mask, int ld_mask,
+                               int n_sets, const int *prompt_set, void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
  * Scalar k-means compression of one weight tensor (jlm_amd/compress.py kmeans_compress; the reference's train/comp.py:20-48,

@@ -148,6 +148,8 @@ _SIGS = {
     "jlm_topk_rows": ([P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P], c_int),
     "jlm_beam_merge": ([P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P], c_int),
     "jlm_complete_frames": ([POINTER(DecodeModel), POINTER(CompletePlan), P, P], c_int),
+    "jlm_topk_rows_masked": ([P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P], c_int),
+    "jlm_complete_frames_masked": ([POINTER(DecodeModel), POINTER(CompletePlan), P, c_int, c_int, P, P, P], c_int),
     "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_split_form": ([], c_int),
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),

@@ -18,6 +18,13 @@ Semantics (pinned by tests/test_complete_cpu.py and tests/test_gpu_complete.py):
 Per-row top-``beam_width`` lists are enough: within a row the key orders by nll, then id -- the row kernel's order.
 
 Prompts are right-aligned and sorted longest first (generate's row plan); a prompt's ``beam_width`` rows stay in one call.
+
+Word sets (``predict_top(allowed=)``, ``complete(first_allowed=)``; ``LSTM_Model.predict_reading`` / ``complete_reading`` over a
+:class:`jlm_amd.readings.ReadingIndex`): frame 0 selects each prompt's candidates among the words of its set only
+(``torch.ops.jlm.complete_frames_masked``, ``topk_rows_masked_kernel``), every later frame is free.  The log-normaliser still runs
+over the whole vocabulary, so scores stay -log p under the full distribution, comparable with ``score()``.  A set smaller than the
+beam pads frame 0's list with (-1, +inf): such a candidate becomes a finished hypothesis of infinite score that is never expanded,
+and hypotheses whose total is not finite are dropped from the result.
 """
 import argparse
 import sys
@@ -29,6 +36,7 @@ from . import config as _config
 from . import generate as _gen
 from . import ops as _ops
 from . import rowsets
+from .readings import ReadingIndex
 from .rowsets import check_ids, is_int
 
 MAX_BEAM = 64                        # JLM_TOPK_MAX: one lane per rank in the merge, one selection round per rank in the row kernel
@@ -55,6 +63,26 @@ def check_args(prompts, n_words, beam_width, n_best, stop_id, V):
     return out, int(n_best)
 
 
+def check_allowed(allowed, n_prompts, V, what):
+    """``allowed`` / ``first_allowed``: None, or per prompt None (unrestricted) or word ids.  ValueError before any launch for a wrong
+    length or an id outside [0, V).  -> None, or per prompt None or the set's ids (int64, ascending, each once)"""
+    if allowed is None:
+        return None
+    if len(allowed) != n_prompts:
+        raise ValueError("%s: one entry per prompt, each None or an array of word ids (%d prompts)" % (what, n_prompts))
+    out = []
+    for a in allowed:
+        if a is None:
+            out.append(None)
+            continue
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("%s: a word set is a one-dimensional array of integer word ids" % what)
+        check_ids(a, V, what)
+        out.append(np.unique(a.astype(np.int64)))
+    return out
+
+
 def plan_prompts(lengths, beam_width, max_rows):
     """generate's row plan (rowsets.plan_prompts) cut into chunks of at most max(1, max_rows // beam_width) prompts: a prompt's rows
     never split across calls.  (idx = the caller's prompt of each chunk prompt.)"""
@@ -73,6 +101,26 @@ def topk_reference(y, k, self_norm=False):
     m = yd.max()
     lse = m + np.log(np.exp(yd - m).sum())
     return order.astype(np.int64), lse - yd[order]
+
+
+def topk_masked_reference(y, k, allowed, self_norm=False):
+    """The masked row kernel restated: the k best of the ``allowed`` words of f32 logits ``y`` (one row), ranked as topk_reference
+    ranks (a NaN logit never ranks), with nll = lse - y where the lse runs over EVERY word of the row (self_norm: -y); fewer than k
+    rankable words: padded with id -1 and nll +inf.  -> (ids int64 [k], nll float64 [k])"""
+    y = np.asarray(y, dtype=np.float32)
+    yd = y.astype(np.float64)
+    a = np.unique(np.asarray(allowed, dtype=np.int64).reshape(-1))
+    a = a[~np.isnan(yd[a])]
+    order = a[np.lexsort((a, -yd[a]))][:k]
+    ids = np.full(k, -1, dtype=np.int64)
+    nll = np.full(k, np.inf)
+    ids[:len(order)] = order
+    if self_norm:
+        nll[:len(order)] = -yd[order]
+    else:
+        m = yd.max()
+        nll[:len(order)] = (m + np.log(np.exp(yd - m).sum())) - yd[order]
+    return ids, nll
 
 
 def merge_reference(cand_ids, cand_nll, score, finished, beam, n_prompts, first, stop_id=-1):
@@ -139,10 +187,11 @@ class Completer:
         m = self.m
         return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + beam * 12 + n_words * 16 + n_prompt * 8 + 48
 
-    def run(self, prompts, n_words, beam, stop_id=None, timed=False, n_live=None):
+    def run(self, prompts, n_words, beam, stop_id=None, timed=False, n_live=None, first_sets=None):
         """One call over prompts already sorted by length (longest first).  n_live: the chunk's live counts from plan_prompts (None:
-        rowsets.live_counts of the prompts).  -> (bp_parent, bp_word [n_words, R] int32, bp_nll [n_words, R] float64, score [R]
-        float64), R = len(prompts) * beam, rank i of prompt p at row p * beam + i."""
+        rowsets.live_counts of the prompts).  first_sets: None, or per prompt None or the word ids its first word is chosen among
+        (the masked op; None leaves the call exactly what it was).  -> (bp_parent, bp_word [n_words, R] int32, bp_nll [n_words, R]
+        float64, score [R] float64), R = len(prompts) * beam, rank i of prompt p at row p * beam + i."""
         torch, m = self.torch, self.m
         if n_live is None:
             n_live = rowsets.live_counts([len(p) for p in prompts])
@@ -162,41 +211,60 @@ class Completer:
             bp_parent = torch.zeros((n_words, R), device=dev, dtype=i32)
             bp_word = torch.full((n_words, R), -1, device=dev, dtype=i32)
             bp_nll = torch.zeros((n_words, R), device=dev, dtype=f64)
-            ms = _ops.backend().complete_frames(m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, up(prev), up(prompt),
-                                                up(n_live), [int(x) for x in n_live], cand_ids, cand_nll, word, prev_row, score,
-                                                finished, -1 if stop_id is None else int(stop_id), bp_parent, bp_word, bp_nll, rs.flags,
-                                                NP, B, P, int(n_words), bool(timed))
+            args = (m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, up(prev), up(prompt), up(n_live),
+                    [int(x) for x in n_live], cand_ids, cand_nll, word, prev_row, score, finished, -1 if stop_id is None else int(stop_id),
+                    bp_parent, bp_word, bp_nll, rs.flags, NP, B, P, int(n_words), bool(timed))
+            if first_sets is None:
+                ms = _ops.backend().complete_frames(*args)
+            else:
+                restricted = [p for p in range(NP) if first_sets[p] is not None]
+                mask, index = ReadingIndex.mask([first_sets[p] for p in restricted], m.V)
+                prompt_set = [-1] * NP
+                for p, s in zip(restricted, index):
+                    prompt_set[p] = int(s)
+                ms = _ops.backend().complete_frames_masked(*args, torch.from_numpy(mask.view(np.int32)).to(dev), mask.shape[1],
+                                                           mask.shape[0], prompt_set)
             if timed:
                 self.last_frame_ms = ms.numpy()
             rs.check_flags("topk_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)")
             return bp_parent.cpu().numpy(), bp_word.cpu().numpy(), bp_nll.cpu().numpy(), score.cpu().numpy()
 
 
-def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None):
+def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, first_allowed=None):
     """LSTM_Model.complete: see there."""
     prompts, n_best = check_args(prompts, n_words, beam_width, n_best, stop_id, comp.m.V)
+    sets = check_allowed(first_allowed, len(prompts), comp.m.V, "complete (first_allowed)")
     out = [None] * len(prompts)
     if not prompts:
         return out
-    lens = [len(p) for p in prompts]
+    run = list(range(len(prompts)))                      # the prompts that reach the device: an empty set has no completion
+    if sets is not None:
+        run = [i for i in run if sets[i] is None or len(sets[i])]
+        for i in range(len(prompts)):
+            out[i] = []
+        if not run:
+            return out
+    lens = [len(prompts[i]) for i in run]
     if max_rows is None:
         max_rows = rowsets.clamp_rows(MAX_ROWS, COMPLETE_BUDGET_BYTES, comp.row_bytes(max(lens), n_words, beam_width), comp.m.H)
     for ch in plan_prompts(lens, beam_width, max_rows):
-        idx = ch["idx"]
-        bp_parent, bp_word, bp_nll, score = comp.run([prompts[i] for i in idx], int(n_words), int(beam_width), stop_id, n_live=ch["n_live"])
+        idx = [run[j] for j in ch["idx"]]
+        bp_parent, bp_word, bp_nll, score = comp.run([prompts[i] for i in idx], int(n_words), int(beam_width), stop_id, n_live=ch["n_live"],
+                                                     first_sets=None if sets is None else [sets[i] for i in idx])
         for j, i in enumerate(idx):
             out[i] = backtrace(bp_parent, bp_word, bp_nll, score, j, int(beam_width), n_best, stop_id)
+            if sets is not None:                         # a set smaller than the beam: the padding's hypotheses have infinite totals
+                out[i] = [h for h in out[i] if np.isfinite(h[2])]
     return out
 
 
-def predict_top(comp, contexts, n=10, max_rows=None):
+def predict_top(comp, contexts, n=10, max_rows=None, allowed=None):
     """LSTM_Model.predict_top: see there.  Frame 0 of complete(contexts, 1, beam_width=n)."""
-    res = complete(comp, contexts, 1, beam_width=n, max_rows=max_rows)
+    res = complete(comp, contexts, 1, beam_width=n, max_rows=max_rows, first_allowed=allowed)
     return [(np.array([h[0][0] for h in r], dtype=np.int64), -np.array([h[1][0] for h in r], dtype=np.float64)) for r in res]
 
 
-def main(argv=None):
-    from .data import CharVocab, load_vocab
+def build_parser():
     ap = argparse.ArgumentParser(description="Predict next words or complete phrases by beam search on the device "
                                              "(reference decoder/model.py:25-26 find_top_N)")
     _config.add_model_args(ap)
@@ -208,8 +276,22 @@ def main(argv=None):
     ap.add_argument("--n-best", type=int, default=None, help="completions to print per prompt (default: the beam width)")
     ap.add_argument("--top", type=int, default=None, metavar="N", help="next-word mode: the N most probable next words")
     ap.add_argument("--stop-at-eos", action="store_true", help="end a completion after <eos>")
+    ap.add_argument("--reading", default=None, metavar="KANA",
+                    help="only words whose reading starts with KANA (hiragana or katakana): with --top the next words, else the first "
+                         "word of every completion")
+    ap.add_argument("--exact", action="store_true", help="with --reading: the reading equals KANA")
+    return ap
+
+
+def main(argv=None):
+    from .data import CharVocab, load_vocab
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.exact and args.reading is None:
+        ap.error("--exact needs --reading")
     _cfg, vocab = load_vocab(args)
+    if args.reading is not None and isinstance(vocab, CharVocab):
+        ap.error("--reading needs a word model: a character model's softmax is not over words")
     from .model import LSTM_Model
     if args.file:
         with open(args.file, encoding="utf-8") as f:
@@ -226,8 +308,10 @@ def main(argv=None):
     model = LSTM_Model(experiment_id=args.experiment_id, comp=args.comp)
     sep = "" if isinstance(vocab, CharVocab) else " "
     t0 = time.time()
+    readings = None if args.reading is None else [args.reading] * len(prompts)
     if args.top is not None:
-        res = model.predict_top(prompts, n=args.top)
+        res = (model.predict_top(prompts, n=args.top) if readings is None else
+               model.predict_reading(prompts, readings, n=args.top, exact=args.exact))
         dt = time.time() - t0
         for b, (p, (ids, logp)) in enumerate(zip(prompts, res)):
             if b:
@@ -237,8 +321,9 @@ def main(argv=None):
                 print("%s%s%s\t%.4f" % (head, sep if head else "", _gen.render([w], vocab), -lp))
         n_out = sum(len(r[0]) for r in res)
     else:
-        res = model.complete(prompts, args.words, beam_width=args.beam, n_best=args.n_best,
-                             stop_id=EOS_ID if args.stop_at_eos else None)
+        kw = dict(beam_width=args.beam, n_best=args.n_best, stop_id=EOS_ID if args.stop_at_eos else None)
+        res = (model.complete(prompts, args.words, **kw) if readings is None else
+               model.complete_reading(prompts, readings, args.words, exact=args.exact, **kw))
         dt = time.time() - t0
         for b, (p, hyps) in enumerate(zip(prompts, res)):
             if b:

@@ -525,7 +525,9 @@ extern "C" int jlm_generate_frames_trunc(const jlm_decode_model *m, const jlm_ge
 // rows; selecting frame 0 projects, materialises and selects from those rows alone (a prompt's beam starts from its one
 // distribution); every later frame steps all n_prompts * beam rows from the rows the previous merge chose, then the T projection, the
 // logit GEMMs, topk_rows_kernel and beam_merge_kernel, which writes the next frame's word / prev row and the back-pointers.
-extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p, void *stream, void *const *events) {
+// prompt_set (jlm_complete_frames_masked; NULL: none): selecting frame 0's rows, one per prompt, select within their word sets.
+static int complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p, const unsigned *mask, int ld_mask, int n_sets,
+                           const int *prompt_set, void *stream, void *const *events) {
     const int NP = p->n_prompts, B = p->beam, P = p->n_prompt, N = p->n_words;
     if (NP < 0 || B < 1 || B > JLM_TOPK_MAX || P < 1 || N < 0 || !p->rows || !p->prev || !p->prompt || !p->n_live || !p->n_live_host ||
         !p->logits || !p->cand_ids || !p->cand_nll || !p->word || !p->prev_row || !p->score || !p->finished || !p->bp_parent ||
@@ -549,7 +551,10 @@ extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete
         JLM_TRY(stamp(f, 2));
         if (k >= 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, n_sel, stream));
         JLM_TRY(stamp(f, 3));
-        if (k >= 0)
+        if (k == 0 && prompt_set)
+            JLM_TRY(jlm_topk_rows_masked(p->logits, p->ld_logits, V, n_sel, B, m->self_norm, mask, ld_mask, n_sets, prompt_set, p->cand_ids,
+                                         p->cand_nll, B, p->flags, stream));
+        else if (k >= 0)
             JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, n_sel, B, m->self_norm, p->cand_ids, p->cand_nll, B, p->flags, stream));
         JLM_TRY(stamp(f, 4));
         if (k >= 0)
@@ -558,4 +563,14 @@ extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete
         JLM_TRY(stamp(f, 5));
     }
     return 0;
+}
+
+extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p, void *stream, void *const *events) {
+    return complete_frames(m, p, nullptr, 0, 0, nullptr, stream, events);
+}
+
+extern "C" int jlm_complete_frames_masked(const jlm_decode_model *m, const jlm_complete_plan *p, const unsigned *mask, int ld_mask,
+                                          int n_sets, const int *prompt_set, void *stream, void *const *events) {
+    if (!prompt_set || n_sets < 0 || (n_sets > 0 && !mask)) return -1;
+    return complete_frames(m, p, mask, ld_mask, n_sets, prompt_set, stream, events);
 }

@@ -15,6 +15,10 @@
 //   Ranking: y descending, then id ascending -- the greedy draw's rule (sample_rows_kernel).  At the end wave 0 selects the row's
 //   top k from the waves' lists; nll = (m + log S) - y in f64 (self_norm: -y).  A non-finite max or sum: *flags |= 1, ids -1, nll NaN.
 //
+//   topk_rows_masked_kernel is the same body (topk_row<SELF_NORM, MASKED = 1>) with each row's candidates restricted to a word set:
+//   a bit mask per set, four bits per 16-byte chunk, read beside the logits.  The lse is untouched by the mask; a set with fewer than
+//   k rankable words pads its list with (-1, +inf).  A row of set -1 loads no mask and is the unmasked row bit for bit.
+//
 // beam_merge_kernel -- one wave per prompt, lane j = the previous beam's rank j.  A lane's candidates are its row's list in order
 // (score = parent score + nll, f64: non-decreasing along the list), or, for a finished parent, one carry (score unchanged, word -1).
 // B rounds: each lane offers its best remaining candidate by (score, word id) -- the list order, but where f64 rounding makes
@@ -74,11 +78,13 @@ __device__ int tk_select(float *sy, int *si, int n, int k, int lane) {
     return kk;
 }
 
-template <int SELF_NORM>
-__global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__restrict__ y, int ld, int n_cols, int n_rows, int k,
-                                                               int *__restrict__ ids, double *__restrict__ nll, int ld_out, int *flags) {
-    const int r = blockIdx.x;
-    if (r >= n_rows) return;
+// One row.  MASKED: only the words whose bit is set in mrow (bit w & 31 of word w >> 5) enter the lists and the threshold test -- the
+// max and the sum still run over every word, in the same order -- and a row with fewer than k rankable words pads its output with
+// (-1, +inf) instead of flagging; mrow NULL is an unrestricted row: no mask is loaded and every branch below is the unmasked one.
+// bad (MASKED only): the row's set index is out of range; the row is flagged.
+template <int SELF_NORM, int MASKED>
+__device__ __forceinline__ void topk_row(const float *__restrict__ y, int ld, int n_cols, int r, int k, const unsigned *__restrict__ mrow,
+                                         bool bad, int *__restrict__ ids, double *__restrict__ nll, int ld_out, int *flags) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     __shared__ float s_y[TK_WAVES * TK_CAP];
     __shared__ int s_i[TK_WAVES * TK_CAP];
@@ -100,11 +106,16 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
     float th = -INFINITY;                                // then: the k-th entry's logit
     for (int it = it0; it < it1; it += TK_UNROLL) {
         f32x4 v[TK_UNROLL];
+        unsigned mb[TK_UNROLL];
 #pragma unroll
         for (int u = 0; u < TK_UNROLL; ++u) {
             const int c = (it + u) * 64 + lane;
             v[u] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             if (it + u < it1 && c < n4) v[u] = row[c];
+            if (MASKED) {                                // the chunk's four bits sit in one word (its first word id is 4 c), which is
+                mb[u] = 0;                               // read with the logits and only where they are: 4 c < n_cols <= 32 * ld_mask
+                if (mrow && it + u < it1 && c < n4) mb[u] = mrow[c >> 3] >> (4 * (c & 7));
+            }
         }
         if (!SELF_NORM) {
             float cm = -INFINITY;
@@ -134,6 +145,10 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
             bool p[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) p[j] = w0 + j < n_cols && (full ? v[u][j] > th : v[u][j] == v[u][j]);
+            if (MASKED && mrow) {                        // block-uniform
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p[j] = p[j] && ((mb[u] >> j) & 1u);
+            }
             if (__ballot(p[0] | p[1] | p[2] | p[3]) == 0ull) continue;
             if (cnt + 4 * 64 > TK_CAP) {
                 cnt = tk_select(sy, si, cnt, k, lane);
@@ -184,17 +199,42 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
         total += s_n[w];
     }
     const int kk = total > 0 ? tk_select(s_y, s_i, total, k, lane) : 0;
-    const bool ok = M > -INFINITY && M < INFINITY && kk == k && (SELF_NORM || (S > 0.0 && S < INFINITY));
+    const bool padded = MASKED && mrow;                  // a restricted row may hold fewer than k rankable words
+    const bool ok = M > -INFINITY && M < INFINITY && (kk == k || padded) && (SELF_NORM || (S > 0.0 && S < INFINITY)) && !(MASKED && bad);
     if (!ok) {
         if (lane == 0 && flags) atomicOr(flags, 1);
         if (lane < k) { ids[(size_t)r * ld_out + lane] = -1; nll[(size_t)r * ld_out + lane] = __longlong_as_double(0x7ff8000000000000LL); }
         return;
     }
-    if (lane < k) {
+    if (lane < (MASKED ? kk : k)) {                      // (not MASKED: kk == k here)
         const float yv = s_y[lane];
         ids[(size_t)r * ld_out + lane] = s_i[lane];
         nll[(size_t)r * ld_out + lane] = SELF_NORM ? -(double)yv : ((double)M + log(S)) - (double)yv;
+    } else if (MASKED && lane < k) {
+        ids[(size_t)r * ld_out + lane] = -1;
+        nll[(size_t)r * ld_out + lane] = INFINITY;
     }
+}
+
+template <int SELF_NORM>
+__global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__restrict__ y, int ld, int n_cols, int n_rows, int k,
+                                                               int *__restrict__ ids, double *__restrict__ nll, int ld_out, int *flags) {
+    const int r = blockIdx.x;
+    if (r >= n_rows) return;
+    topk_row<SELF_NORM, 0>(y, ld, n_cols, r, k, nullptr, false, ids, nll, ld_out, flags);
+}
+
+// topk_rows_kernel with row r restricted to the words of set row_set[r] of mask [n_sets][ld_mask] (-1: unrestricted)
+template <int SELF_NORM>
+__global__ __launch_bounds__(TK_THREADS) void topk_rows_masked_kernel(const float *__restrict__ y, int ld, int n_cols, int n_rows, int k,
+                                                                      const unsigned *__restrict__ mask, int ld_mask, int n_sets,
+                                                                      const int *__restrict__ row_set, int *__restrict__ ids,
+                                                                      double *__restrict__ nll, int ld_out, int *flags) {
+    const int r = blockIdx.x;
+    if (r >= n_rows) return;
+    const int s = row_set[r];                            // block-uniform
+    const bool bad = s < -1 || s >= n_sets;              // (the torch op refuses it on the host; a C caller's is flagged, never indexed)
+    topk_row<SELF_NORM, 1>(y, ld, n_cols, r, k, s >= 0 && !bad ? mask + (size_t)s * ld_mask : nullptr, bad, ids, nll, ld_out, flags);
 }
 
 extern "C" int jlm_topk_rows(const float *y, int ld_y, int n_cols, int n_rows, int k, int self_norm, int *ids, double *nll, int ld_out,
@@ -208,6 +248,23 @@ extern "C" int jlm_topk_rows(const float *y, int ld_y, int n_cols, int n_rows, i
     else
         hipLaunchKernelGGL(topk_rows_kernel<0>, dim3(n_rows), dim3(TK_THREADS), 0, (hipStream_t)stream, y, ld_y, n_cols, n_rows, k, ids,
                            nll, ld_out, flags);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int jlm_topk_rows_masked(const float *y, int ld_y, int n_cols, int n_rows, int k, int self_norm, const unsigned *mask,
+                                    int ld_mask, int n_sets, const int *row_set, int *ids, double *nll, int ld_out, int *flags,
+                                    void *stream) {
+    if (n_cols < 1 || ld_y % 4 != 0 || ld_y < ((n_cols + 3) & ~3) || ((uintptr_t)y & 15) != 0) return -1;
+    if (k < 1 || k > JLM_TOPK_MAX || k > n_cols || ld_out < k || !ids || !nll) return -1;
+    if (n_sets < 0 || !row_set || (n_sets > 0 && (!mask || ld_mask < (n_cols + 31) / 32))) return -1;
+    if (n_rows <= 0) return 0;
+    if (self_norm)
+        hipLaunchKernelGGL(topk_rows_masked_kernel<1>, dim3(n_rows), dim3(TK_THREADS), 0, (hipStream_t)stream, y, ld_y, n_cols, n_rows, k,
+                           mask, ld_mask, n_sets, row_set, ids, nll, ld_out, flags);
+    else
+        hipLaunchKernelGGL(topk_rows_masked_kernel<0>, dim3(n_rows), dim3(TK_THREADS), 0, (hipStream_t)stream, y, ld_y, n_cols, n_rows, k,
+                           mask, ld_mask, n_sets, row_set, ids, nll, ld_out, flags);
     JLM_LAUNCH_CHECK();
     return 0;
 }

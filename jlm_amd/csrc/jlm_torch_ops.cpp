@@ -25,6 +25,9 @@
 //   torch.ops.jlm.beam_merge(cand_ids, cand_nll, ...)          one beam selection per prompt (jlm_beam_merge)
 //   torch.ops.jlm.complete_frames(Model, state row sets, logits, prompt arrays, ..., back-pointers, ...)
 //                             beam-search completion: ONE op (jlm_complete_frames; LSTM_Model.complete / predict_top)
+//   torch.ops.jlm.topk_rows_masked / complete_frames_masked(..., mask, ld_mask, n_sets, row_set / prompt_set)
+//                             the same two with rows / first words restricted to word sets (jlm_topk_rows_masked,
+//                             jlm_complete_frames_masked; LSTM_Model.predict_reading / complete_reading)
 //   torch.ops.jlm.kmeans1d(x, bit, seed, max_iter, tol, code, codebook, scratch, grid, timed)
 //                             scalar k-means compression of one weight tensor: ONE op (jlm_kmeans1d; jlm_amd/compress.py)
 //   torch.ops.jlm.train_*       the kernels of a training step, one op per launcher (jlm_train.hip; jlm_amd/train.py DeviceStepper)
@@ -669,6 +672,41 @@ void topk_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, int6
               "jlm_topk_rows");
 }
 
+// A word-set mask and its per-row set indices, checked on the host and the indices put on the device (jlm_topk_rows_masked, include/
+// jlm_hip.h): mask int32 [n_sets, ld_mask] holding the 32-bit words' bits, row_set one index in [-1, n_sets) per row.
+Tensor check_word_sets(const char *op, const Tensor &mask, int64_t ld_mask, int64_t n_sets, int64_t n_cols, const std::vector<int64_t> &row_set,
+                       int64_t n_rows, const Tensor &like) {
+    TORCH_CHECK(n_sets >= 0 && n_sets <= INT32_MAX && ld_mask >= 0 && ld_mask <= INT32_MAX && (n_sets == 0 || ld_mask >= (n_cols + 31) / 32) &&
+                    mask.defined() && mask.scalar_type() == at::kInt && mask.numel() >= n_sets * ld_mask,
+                "jlm.", op, ": mask int32 [n_sets, ld_mask] with ld_mask >= ceil(n_cols / 32) = ", (n_cols + 31) / 32);
+    TORCH_CHECK((int64_t)row_set.size() == n_rows, "jlm.", op, ": one set index per row (", n_rows, ")");
+    Tensor host = at::full({std::max<int64_t>(n_rows, 1)}, -1, at::kInt);      // (never empty: the entry point wants a pointer)
+    for (size_t r = 0; r < row_set.size(); ++r) {
+        TORCH_CHECK(row_set[r] >= -1 && row_set[r] < n_sets, "jlm.", op, ": set index ", row_set[r], " of row ", r, " outside [-1, ", n_sets, ")");
+        host.data_ptr<int>()[r] = (int)row_set[r];
+    }
+    return host.to(like.device());
+}
+
+// topk_rows with row r restricted to the words of set row_set[r] of `mask` (jlm_topk_rows_masked, include/jlm_hip.h); -1: unrestricted.
+void topk_rows_masked(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, int64_t k, bool self_norm, const Tensor &mask,
+                      int64_t ld_mask, int64_t n_sets, std::vector<int64_t> row_set, const Tensor &ids, const Tensor &nll, int64_t ld_out,
+                      const OptTensor &flags) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.topk_rows_masked: y [n_rows, ld] float32");
+    TORCH_CHECK(is(ids, at::kInt, n_rows * ld_out) && is(nll, at::kDouble, n_rows * ld_out) &&
+                    (!flags.has_value() || !flags->defined() || is(*flags, at::kInt, 1)),
+                "jlm.topk_rows_masked: int32 ids / float64 nll [n_rows, ld_out], int32 flags [1]");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    on_gpu(y, "y");
+    const Tensor sets = check_word_sets("topk_rows_masked", mask, ld_mask, n_sets, n_cols, row_set, n_rows, y);
+    jlm_check(jlm_topk_rows_masked(ptr<const float>(y, "y"), (int)ld, (int)n_cols, (int)n_rows, (int)k, self_norm ? 1 : 0,
+                                   n_sets > 0 ? ptr<const unsigned>(mask, "mask") : nullptr, (int)ld_mask, (int)n_sets,
+                                   ptr<const int>(sets, "row_set"), ptr<int>(ids, "ids"), ptr<double>(nll, "nll"), (int)ld_out,
+                                   optr<int>(flags, "flags"), stream_of(y)),
+              "jlm_topk_rows_masked");
+}
+
 // one beam selection per prompt over per-row top-`beam` lists (jlm_beam_merge, include/jlm_hip.h): cand_ids int32 / cand_nll float64
 // [rows, beam]; word / prev / score (float64) / finished / bp_* [n_prompts * beam].
 void beam_merge(const Tensor &cand_ids, const Tensor &cand_nll, int64_t beam, int64_t n_prompts, bool first, int64_t stop_id,
@@ -694,12 +732,14 @@ void beam_merge(const Tensor &cand_ids, const Tensor &cand_nll, int64_t beam, in
 // [n_prompt] int32 and its host copy; cand_ids / cand_nll [R, beam]; word / prev_row / score / finished [R]; bp_* [n_words][R]; flags
 // one int32.  Every id must lie in [0, V): the caller checks (jlm_amd/complete.py).  -> timed: [frames, 5] milliseconds per frame (LSTM
 // step, T projection, logit GEMMs, selection, merge) after waiting for the last frame; else an empty tensor and nothing waits.
-Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+// complete_frames_masked (jlm_complete_frames_masked): the same with prompt p's first word restricted to set prompt_set[p] of `mask`.
+Tensor complete_frames_masked(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
                        const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
                        const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &cand_ids,
                        const Tensor &cand_nll, const Tensor &word, const Tensor &prev_row, const Tensor &score, const Tensor &finished,
                        int64_t stop_id, const Tensor &bp_parent, const Tensor &bp_word, const Tensor &bp_nll, const OptTensor &flags,
-                       int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed) {
+                       int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed, const OptTensor &mask,
+                       int64_t ld_mask, int64_t n_sets, std::vector<int64_t> prompt_set) {
     const jlm_decode_model &m = model->m;
     const int64_t NP = n_prompts, B = beam, P = n_prompt, N = n_words, R = n_prompts * beam;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
@@ -731,8 +771,31 @@ Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     p.stop_id = (int)stop_id;
     p.bp_parent = ptr<int>(bp_parent, "bp_parent"); p.bp_word = ptr<int>(bp_word, "bp_word"); p.bp_nll = ptr<double>(bp_nll, "bp_nll");
     p.flags = optr<int>(flags, "flags");
-    return launch_frames("jlm_complete_frames", h0.device().index(), timed, N > 0 && NP > 0 ? P + N - 1 : 0, JLM_COMPLETE_EVENTS_PER_FRAME,
-                         [&](hipStream_t st, void *const *ev) { return jlm_complete_frames(&m, &p, st, ev); });
+    const bool masked = has(mask);
+    Tensor sets;
+    if (masked) {
+        const c10::hip::HIPGuard device_guard(h0.device().index());
+        on_gpu(logits, "logits");
+        sets = check_word_sets("complete_frames_masked", *mask, ld_mask, n_sets, m.segs[m.n_segs - 1].v_end, prompt_set, NP, logits);
+    }
+    const unsigned *mask_p = masked && n_sets > 0 ? ptr<const unsigned>(*mask, "mask") : nullptr;
+    const int *sets_p = masked ? ptr<const int>(sets, "prompt_set") : nullptr;
+    return launch_frames(masked ? "jlm_complete_frames_masked" : "jlm_complete_frames", h0.device().index(), timed,
+                         N > 0 && NP > 0 ? P + N - 1 : 0, JLM_COMPLETE_EVENTS_PER_FRAME, [&](hipStream_t st, void *const *ev) {
+                             return masked ? jlm_complete_frames_masked(&m, &p, mask_p, (int)ld_mask, (int)n_sets, sets_p, st, ev)
+                                           : jlm_complete_frames(&m, &p, st, ev);
+                         });
+}
+
+Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
+                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &cand_ids,
+                       const Tensor &cand_nll, const Tensor &word, const Tensor &prev_row, const Tensor &score, const Tensor &finished,
+                       int64_t stop_id, const Tensor &bp_parent, const Tensor &bp_word, const Tensor &bp_nll, const OptTensor &flags,
+                       int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed) {
+    return complete_frames_masked(model, h0, c0, h1, c1, T, logits, ld_logits, rows, prev, prompt, n_live, std::move(n_live_host), cand_ids,
+                                  cand_nll, word, prev_row, score, finished, stop_id, bp_parent, bp_word, bp_nll, flags, n_prompts, beam,
+                                  n_prompt, n_words, timed, c10::nullopt, 0, 0, {});
 }
 
 // scalar k-means compression of one tensor (jlm_kmeans1d, include/jlm_hip.h): x float32 [n], code uint8 [n], codebook float32 [2^bit],
@@ -965,6 +1028,15 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(h!) cand_nll, Tensor(i!) word, Tensor(j!) prev_row, Tensor(k!) score, Tensor(l!) finished, int stop_id, Tensor(m!) bp_parent, "
           "Tensor(n!) bp_word, Tensor(o!) bp_nll, Tensor(p!)? flags, int n_prompts, int beam, int n_prompt, int n_words, bool timed) -> Tensor",
           complete_frames);
+    m.def("topk_rows_masked(Tensor y, int ld, int n_cols, int n_rows, int k, bool self_norm, Tensor mask, int ld_mask, int n_sets, "
+          "int[] row_set, Tensor(a!) ids, Tensor(b!) nll, int ld_out, Tensor(c!)? flags) -> ()",
+          topk_rows_masked);
+    m.def("complete_frames_masked(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, "
+          "Tensor(e!)? T, Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev, Tensor prompt, Tensor n_live, int[] n_live_host, "
+          "Tensor(g!) cand_ids, Tensor(h!) cand_nll, Tensor(i!) word, Tensor(j!) prev_row, Tensor(k!) score, Tensor(l!) finished, int stop_id, "
+          "Tensor(m!) bp_parent, Tensor(n!) bp_word, Tensor(o!) bp_nll, Tensor(p!)? flags, int n_prompts, int beam, int n_prompt, int n_words, "
+          "bool timed, Tensor? mask, int ld_mask, int n_sets, int[] prompt_set) -> Tensor",
+          complete_frames_masked);
     m.def("kmeans1d(Tensor x, int bit, int seed, int max_iter, float tol, Tensor(a!) code, Tensor(b!) codebook, Tensor(c!) scratch, int grid, "
           "bool timed) -> Tensor",
           kmeans1d);

@@ -951,22 +951,55 @@ class LSTM_Model():
         from .generate import generate
         return generate(self._generator(), prompts, n_words, temperature, seed, stop_id, max_rows, top_k, top_p)
 
-    def predict_top(self, contexts, n=10, max_rows=None):
+    def reading_index(self):
+        """this model's :class:`jlm_amd.readings.ReadingIndex` over ``Vocab(config['vocab_size'])``, built on first use.  ValueError
+        for a character model: its softmax is not over words."""
+        if "_reading_index" not in self.__dict__:
+            if self.config.get("char_rnn"):
+                raise ValueError("a reading index needs a word model: a character model's softmax is not over words")
+            from .data import Vocab
+            from .readings import ReadingIndex
+            self._reading_index = ReadingIndex(Vocab(self.config["vocab_size"]))
+        return self._reading_index
+
+    def _reading_sets(self, readings, n, exact):
+        if isinstance(readings, str) or len(readings) != n:
+            raise ValueError("readings: one string per context (%d contexts)" % n)
+        index = self.reading_index()
+        return [index.lookup(r, exact=exact) for r in readings]
+
+    def predict_top(self, contexts, n=10, max_rows=None, allowed=None):
         """The ``n`` most probable next words after each context, on the device (jlm_amd/complete.py; the reference's
         find_top_N(predict(...), N), model.py:25-26, without the host-side softmax and argsort).  ``contexts``: word-id lists of length
         >= 1, each consumed from the zero state as generate() consumes a prompt.  -> per context (ids int64 [n], logp float64 [n]),
-        most probable first, equal logits lower id first; logp = y - lse (self_norm: y).  1 <= n <= min(64, V)."""
+        most probable first, equal logits lower id first; logp = y - lse (self_norm: y).  1 <= n <= min(64, V).
+        ``allowed``: None, or per context None or an array of word ids: that context's words are chosen among these only (the masked
+        selection, csrc topk_rows_masked_kernel), and its result has min(n, size of the set) entries -- none, without reaching the
+        device, for an empty set.  logp stays y - lse over the WHOLE vocabulary: it is not renormalised over the set."""
         from .complete import predict_top
-        return predict_top(self._completer(), contexts, n, max_rows)
+        return predict_top(self._completer(), contexts, n, max_rows, allowed)
 
-    def complete(self, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None):
+    def predict_reading(self, contexts, readings, n=10, exact=False, max_rows=None):
+        """predict_top among the words whose reading starts with (``exact``: equals) ``readings[i]``, one string per context, hiragana
+        or katakana -- what a predictive keyboard asks at every keystroke.  The sets come from reading_index()."""
+        return self.predict_top(contexts, n, max_rows, allowed=self._reading_sets(readings, len(contexts), exact))
+
+    def complete_reading(self, prompts, readings, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, exact=False):
+        """complete() with the first generated word of prompt i chosen among the words whose reading starts with (``exact``: equals)
+        ``readings[i]``; the later words are free."""
+        return self.complete(prompts, n_words, beam_width, n_best, stop_id, max_rows,
+                             first_allowed=self._reading_sets(readings, len(prompts), exact))
+
+    def complete(self, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, first_allowed=None):
         """Deterministic beam search over the LM, separately for each prompt (jlm_amd/complete.py).  A hypothesis's score is its summed
         -log p (f64); each frame keeps the ``beam_width`` best by (score, parent's rank, word id); with ``stop_id`` a hypothesis ending
         in it is finished and carried unchanged.  -> per prompt ``n_best`` (default beam_width) tuples (ids int64, nll float64 per
         word, total), total ascending.  ValueError for a bad argument before anything runs; JlmHipError when the device flags a
-        non-finite logit or log-normaliser."""
+        non-finite logit or log-normaliser.  ``first_allowed``: None, or per prompt None or an array of word ids the FIRST generated
+        word is chosen among (later words are free).  A set smaller than the beam leaves fewer first words than ranks; hypotheses
+        whose total is not finite are dropped, so such a prompt may return fewer than ``n_best`` results, and an empty set gives []."""
         from .complete import complete
-        return complete(self._completer(), prompts, n_words, beam_width, n_best, stop_id, max_rows)
+        return complete(self._completer(), prompts, n_words, beam_width, n_best, stop_id, max_rows, first_allowed)
 
 
 def show_prob(model, w2i, inputs):

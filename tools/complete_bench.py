@@ -8,7 +8,13 @@
   baseline        the host form of one next-word query: predict() and an argsort of the [1, V] distribution (the reference's
                   find_top_N) at one row
 
-    python tools/complete_bench.py [--root DIR] [--repeats N] [--beam B] [--words N] [--quick]
+  --reading       instead: prediction from a typed reading prefix on mid-vtable.  256, 1 024 and 2 560 contexts from <eos>, context p
+                  restricted to the words whose reading starts with kana p % 80 (LSTM_Model.predict_reading): the event time of the
+                  first frame's selection with the sets (topk_rows_masked_kernel) beside the same rows' unrestricted selection
+                  (topk_rows_kernel), alternating, median and range of the repeats; queries/s of predict_reading; and the host form of
+                  one such query: predict(), a Python filter to the set and an argsort, at one row
+
+    python tools/complete_bench.py [--root DIR] [--repeats N] [--beam B] [--words N] [--quick] [--reading]
 
 words/s = rows x words / wall seconds of the call (upload, launches, read-back of the back-pointers, backtrace), median of the
 repeats after one warm-up call.
@@ -47,6 +53,51 @@ def _median_time(fn, repeats):
     return float(np.median(ts))
 
 
+def reading_leg(root, reps, B, quick):
+    """the --reading leg: see the module docstring"""
+    import torch
+    from jlm_amd import complete as C, synth
+    _d, model = _model(root, "mid-vtable")
+    m = model.dev
+    index = model.reading_index()
+    comp = C.Completer(m)
+    res = {"V": m.V, "beam": B}
+    stat = lambda a: {"median_us": round(float(np.median(a)) * 1e3, 2), "min_us": round(float(np.min(a)) * 1e3, 2),
+                      "max_us": round(float(np.max(a)) * 1e3, 2)}
+    for R in (256, 1024, 2560):
+        ctx = [np.array([C.EOS_ID])] * R
+        prefixes = [synth.KANA[p % len(synth.KANA)] for p in range(R)]
+        sets = [index.lookup(x) for x in prefixes]
+
+        def select_ms(first_sets):
+            comp.run(ctx, 1, B, timed=True, first_sets=first_sets)
+            return comp.last_frame_ms[0][3]              # frame 0's selection bracket
+
+        select_ms(None), select_ms(sets)
+        plain, masked = [], []
+        for _ in range(reps):                            # alternating: the two see the same machine
+            plain.append(select_ms(None))
+            masked.append(select_ms(sets))
+        t = _median_time(lambda: model.predict_reading([[C.EOS_ID]] * R, prefixes, n=B), reps)
+        res["rows_%d" % R] = {"set_words_mean": round(float(np.mean([len(s) for s in sets])), 1), "select_unmasked": stat(plain),
+                              "select_masked": stat(masked),
+                              "masked_over_unmasked": round(float(np.median(masked) / np.median(plain)), 4),
+                              "predict_reading_s": round(t, 5), "queries_per_s": round(R / t, 1)}
+        torch.cuda.empty_cache()
+    n_host = 10 if quick else 50
+    allowed = index.lookup(synth.KANA[0])
+    model.hidden = np.zeros((1, m.H))
+    model.cell = np.zeros((1, m.H))
+    model.predict([C.EOS_ID])
+    t0 = time.perf_counter()
+    for _ in range(n_host):
+        pred = model.predict([C.EOS_ID])[0]
+        allowed[np.argsort(-pred[0][allowed])[:B]]       # the filter and argsort a caller without the device path writes
+    t = time.perf_counter() - t0
+    res["host_predict_filter_argsort_1_row"] = {"queries": n_host, "s": round(t, 4), "queries_per_s": round(n_host / t, 1)}
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--root", default=None, help="fixture directory (default: a temporary one)")
@@ -54,12 +105,17 @@ def main(argv=None):
     ap.add_argument("--beam", type=int, default=8)
     ap.add_argument("--words", type=int, default=10)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--reading", action="store_true", help="the reading-prefix leg instead of the completion one")
     args = ap.parse_args(argv)
     root = args.root or tempfile.mkdtemp(prefix="jlm_complete_bench_")
     reps = 2 if args.quick else args.repeats
     N, B = args.words, args.beam
     import torch
     from jlm_amd import complete as C
+    if args.reading:
+        out = {"bench": "complete-reading", "device": torch.cuda.get_device_name(0), "mid-vtable": reading_leg(root, reps, B, args.quick)}
+        print(json.dumps(out))
+        return out
     out = {"bench": "complete", "device": torch.cuda.get_device_name(0), "words_per_row": N, "beam": B}
     parts = ("lstm", "t_proj", "logit_gemm", "select", "merge")
     for name in ("mid-vtable", "mid-tied"):
