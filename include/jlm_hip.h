@@ -607,6 +607,12 @@ typedef struct {
     /* ABI 7, kind 0 with model.mixed_segs: [n_sent * beam][ld_tm] packed hypothesis rows of the frame being stepped
      * (jlm_pack_t_mixed over the model's mixed segments, right behind the T projection; ld_tm = jlm_mixed_t_stride of those) */
     void *Tm; int ld_tm;
+    /* Left context (additive, ABI 12; both NULL: every sentence starts at <eos> from the zero state).  [n_sent * beam] device ints that
+     * jlm_seed_context wrote: frame 0's LSTM step reads prev / word of sentence s's root row (g = s * beam) from them instead of
+     * from jlm_beam_state.bp / .word -- it continues state row ctx_prev[g] (a row past the pool's n_frames * n_sent * beam rows, or
+     * -1) and consumes ctx_word[g].  bp of frame 0 stays -1: jlm_backtrace stops at the root as before.  h / c then hold n_sent
+     * more rows behind the pool. */
+    const int *ctx_prev, *ctx_word;
 } jlm_decode_plan;
 
 /* Returns 0 or a hipError_t.  st_host->lse_part / n_parts are managed by the call.  A full-vocabulary
@@ -829,6 +835,40 @@ int jlm_complete_frames(const jlm_decode_model *model_host, const jlm_complete_p
  * `beam` candidates: the caller drops final hypotheses whose score is not finite. */
 int jlm_complete_frames_masked(const jlm_decode_model *model_host, const jlm_complete_plan *plan_host, const unsigned *mask, int ld_mask,
                                int n_sets, const int *prompt_set, void *stream, void *const *events);
+
+/* ------------------------------------------------------------------------
+ * Left context of a decode (LSTM_Model.prime, Decoder.decode(context=), jlm_amd/context.py).  Sentence s with the committed words
+ * ctx_s has the history hist = [<eos>] + ctx_s; its decode is the reference's with the root hypothesis consuming hist[-1] from the
+ * state reached by consuming hist[:-1] from the zero state.
+ *
+ * The priming loop: row r < n_rows consumes its words RIGHT-aligned on n_steps frames, rows sorted longest first, as
+ * jlm_generate_plan's prompt frames: frame f steps the live prefix r < n_live[f], consuming word[f][r] and continuing row prev[f][r]
+ * of the set being read (-1 at a row's first frame: the zero state).  State h[2] / c[2] ping-pong as jlm_score_plan's: the state
+ * after the last frame is in set n_steps % 2.  A row without words never steps (its state rows are not written). */
+typedef struct {
+    int n_rows, n_steps;
+    void *h[2]; float *c[2];        /* [n_rows, H] state row sets */
+    const int *rows;                /* [n_rows] device: 0, 1, ..., n_rows - 1 */
+    const int *prev, *word;         /* [n_steps][n_rows] device */
+    const int *n_live;              /* [n_steps] device */
+    const int *n_live_host;         /* [n_steps] host */
+} jlm_prime_plan;
+
+/* Enqueues n_steps LSTM steps and nothing else (jlm_lstm_step_xg on split-row models, jlm_lstm_step otherwise; no f32 copy of the
+ * state, no T projection, no normaliser, no host synchronisation).  Returns 0, -2 for a model outside the loop's shapes, -1 / a
+ * hipError_t as the launchers do. */
+int jlm_prime_frames(const jlm_decode_model *model_host, const jlm_prime_plan *plan_host, void *stream);
+
+/* Seeds a decode plan with primed states (seed_context_kernel, one launch, plain vector stores).  For sentence s < n_sent with
+ * r = idx[s] (a row of the primed set, 0 <= r < n_src; a sentence with r outside that range is left alone):
+ *   has[r] != 0: rows r of src_h / src_c -> rows G + s of dst_h / dst_c, as H / 4 16-byte records each (the state-row format of the
+ *                model, split or f32, is copied as it is), and ctx_prev[s * beam] = G + s;
+ *   has[r] == 0: (the history is <eos> alone) nothing is copied, ctx_prev[s * beam] = -1;
+ *   ctx_word[s * beam] = last[r].
+ * Entries of ctx_prev / ctx_word at other positions are not written.  H % 4 == 0; every pointer 16-byte aligned; (G + n_sent) x H / 4
+ * < 2^31 (the LSTM step's addressing).  Returns 0, -1 for bad arguments, or a hipError_t. */
+int jlm_seed_context(const void *src_h, const float *src_c, int H, const int *last, const int *has, int n_src, const int *idx,
+                     int n_sent, int beam, long long G, void *dst_h, float *dst_c, int *ctx_prev, int *ctx_word, void *stream);
 
 /* ------------------------------------------------------------------------
  * Scalar k-means compression of one weight tensor (jlm_amd/compress.py kmeans_compress; the reference's train/comp.py:20-48,

@@ -59,7 +59,8 @@ class DecodePlan(Structure):
                 ("dd_words", c_void_p), ("dd_off", c_void_p), ("dd_max", c_int),
                 ("run_max", c_void_p), ("run_sum", c_void_p), ("part", c_void_p), ("max_parts", c_int), ("lse_cu_share_pct", c_int),
                 ("out_nodes", c_void_p), ("out_len", c_void_p), ("out_score", c_void_p), ("stride", c_int),
-                ("di_wwords", c_void_p), ("sg_wword", c_void_p), ("Tm", c_void_p), ("ld_tm", c_int)]
+                ("di_wwords", c_void_p), ("sg_wword", c_void_p), ("Tm", c_void_p), ("ld_tm", c_int),
+                ("ctx_prev", c_void_p), ("ctx_word", c_void_p)]
 
 
 
@@ -79,6 +80,12 @@ class GeneratePlan(Structure):
                 ("n_live", c_void_p), ("n_live_host", POINTER(c_int)), ("row_id", c_void_p), ("word", c_void_p), ("done", c_void_p),
                 ("stop_id", c_int), ("temperature", c_double), ("seed", c_uint64), ("ids", c_void_p), ("nll", c_void_p),
                 ("flags", c_void_p)]
+
+
+class PrimePlan(Structure):
+    """jlm_prime_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("rows", c_void_p), ("prev", c_void_p),
+                ("word", c_void_p), ("n_live", c_void_p), ("n_live_host", POINTER(c_int))]
 
 
 class CompletePlan(Structure):
@@ -150,6 +157,8 @@ _SIGS = {
     "jlm_complete_frames": ([POINTER(DecodeModel), POINTER(CompletePlan), P, P], c_int),
     "jlm_topk_rows_masked": ([P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P], c_int),
     "jlm_complete_frames_masked": ([POINTER(DecodeModel), POINTER(CompletePlan), P, c_int, c_int, P, P, P], c_int),
+    "jlm_prime_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P], c_int),
+    "jlm_seed_context": ([P, P, c_int, P, P, c_int, P, c_int, c_int, c_longlong, P, P, P, P, P], c_int),
     "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_split_form": ([], c_int),
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),

@@ -2,6 +2,7 @@
 // Host code only: it enqueues the launchers of jlm_gemm.hip / jlm_split.hip / jlm_beam.hip in the order
 // jlm_amd/engine.py documents, so a batch costs one FFI call instead of ~170.
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include "../../include/jlm_hip.h"
 
@@ -240,14 +241,17 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
         if (f == F - 1) break;
         const int *rows = st.live + (size_t)f * rmax;
         const int *ndev = st.n_live + f;
+        // frame 0 with a left context: the root rows continue the primed states jlm_seed_context left behind the pool
+        const bool seeded = f == 0 && p->ctx_prev && p->ctx_word;
+        const int *step_prev = seeded ? p->ctx_prev : st.bp, *step_word = seeded ? p->ctx_word : st.word;
         if (JLM_SKIPPED(4)) {
         } else if (m->split_lstm && m->wt8)
-            JLM_TRY(jlm_lstm_step_xg(p->h, p->c, m->H, p->h, p->c, rows, st.bp, st.word, m->wt8, m->xgate8, m->H,
+            JLM_TRY(jlm_lstm_step_xg(p->h, p->c, m->H, p->h, p->c, rows, step_prev, step_word, m->wt8, m->xgate8, m->H,
                                      m->gate_descale, m->h_scale, m->untied ? p->T : nullptr, rmax, ndev, stream));
         else if (m->split_lstm)
             return -2;              // (a split-row model always carries wt8 / xgate8: DeviceModel builds them together)
         else
-            JLM_TRY(jlm_lstm_step((const float *)p->h, p->c, m->H, (float *)p->h, p->c, rows, st.bp, st.word, m->emb,
+            JLM_TRY(jlm_lstm_step((const float *)p->h, p->c, m->H, (float *)p->h, p->c, rows, step_prev, step_word, m->emb,
                                   m->ld_emb, m->wt, m->gate_bias, m->kpad, m->H, m->E, rmax, ndev, stream));
         JLM_TRY(stamp(f, 3));
         if (!m->untied && !JLM_SKIPPED(2)) {
@@ -437,6 +441,67 @@ static int frame_lstm_step(const jlm_decode_model *m, const Plan *p, const PingP
                                in_prompt ? p->prompt + (size_t)f * stride : p->word, p->T, bound, in_prompt ? p->n_live + f : nullptr,
                                stream));
     return stamp(f, 1);
+}
+
+// The priming loop (include/jlm_hip.h jlm_prime_frames): the LSTM step of the live prefix of right-aligned word rows, frame by frame,
+// and nothing else -- the state a decode with a left context starts from.
+extern "C" int jlm_prime_frames(const jlm_decode_model *m, const jlm_prime_plan *p, void *stream) {
+    const int R = p->n_rows, S = p->n_steps;
+    if (R < 0 || S < 0) return -1;
+    if (R == 0 || S == 0) return 0;
+    if (!p->rows || !p->prev || !p->word || !p->n_live || !p->n_live_host || !p->h[0] || !p->h[1] || !p->c[0] || !p->c[1]) return -1;
+    if (m->split_lstm && !m->wt8) return -2;
+    for (int f = 0; f < S; ++f) {
+        const int bound = p->n_live_host[f];
+        if (bound < 0 || bound > R) return -1;
+        if (bound == 0) continue;
+        void *h_in = p->h[f & 1], *h_out = p->h[(f + 1) & 1];
+        float *c_in = p->c[f & 1], *c_out = p->c[(f + 1) & 1];
+        const int *prev = p->prev + (size_t)f * R, *word = p->word + (size_t)f * R, *ndev = p->n_live + f;
+        if (m->split_lstm)
+            JLM_TRY(jlm_lstm_step_xg(h_in, c_in, m->H, h_out, c_out, p->rows, prev, word, m->wt8, m->xgate8, m->H, m->gate_descale,
+                                     m->h_scale, nullptr, bound, ndev, stream));
+        else
+            JLM_TRY(jlm_lstm_step((const float *)h_in, c_in, m->H, (float *)h_out, c_out, p->rows, prev, word, m->emb, m->ld_emb, m->wt,
+                                  m->gate_bias, m->kpad, m->H, m->E, bound, ndev, stream));
+    }
+    return 0;
+}
+
+// seed_context_kernel (include/jlm_hip.h jlm_seed_context): workgroup s gathers the primed state of sentence s behind the plan's pool,
+// 16 bytes a lane and trip, and lane 0 writes the root row's prev / word.
+__global__ void __launch_bounds__(256) seed_context_kernel(const uint4 *__restrict__ src_h, const uint4 *__restrict__ src_c, int rec,
+                                                           const int *__restrict__ last, const int *__restrict__ has, int n_src,
+                                                           const int *__restrict__ idx, int beam, long long G, uint4 *__restrict__ dst_h,
+                                                           uint4 *__restrict__ dst_c, int *__restrict__ ctx_prev, int *__restrict__ ctx_word) {
+    const int s = blockIdx.x;
+    const int r = idx[s];
+    if (r < 0 || r >= n_src) return;
+    const bool state = has[r] != 0;
+    if (state) {
+        const size_t from = (size_t)r * rec, to = ((size_t)G + s) * rec;
+        for (int i = threadIdx.x; i < rec; i += blockDim.x) {
+            dst_h[to + i] = src_h[from + i];
+            dst_c[to + i] = src_c[from + i];
+        }
+    }
+    if (threadIdx.x == 0) {
+        ctx_prev[(size_t)s * beam] = state ? (int)(G + s) : -1;
+        ctx_word[(size_t)s * beam] = last[r];
+    }
+}
+
+extern "C" int jlm_seed_context(const void *src_h, const float *src_c, int H, const int *last, const int *has, int n_src, const int *idx,
+                                int n_sent, int beam, long long G, void *dst_h, float *dst_c, int *ctx_prev, int *ctx_word, void *stream) {
+    if (n_sent < 0 || n_src < 0 || beam < 1 || H < 4 || H % 4 != 0 || G < 0) return -1;
+    if (n_sent == 0) return 0;
+    if (!src_h || !src_c || !last || !has || !idx || !dst_h || !dst_c || !ctx_prev || !ctx_word) return -1;
+    if ((G + n_sent) * (long long)(H / 4) >= 0x7ffffff0ll) return -1;
+    if ((((uintptr_t)src_h | (uintptr_t)src_c | (uintptr_t)dst_h | (uintptr_t)dst_c) & 15) != 0) return -1;
+    const int rec = H / 4;
+    seed_context_kernel<<<dim3(n_sent), dim3(rec >= 256 ? 256 : (rec + 63) / 64 * 64), 0, (hipStream_t)stream>>>(
+        (const uint4 *)src_h, (const uint4 *)src_c, rec, last, has, n_src, idx, beam, G, (uint4 *)dst_h, (uint4 *)dst_c, ctx_prev, ctx_word);
+    return (int)hipGetLastError();
 }
 
 // Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),

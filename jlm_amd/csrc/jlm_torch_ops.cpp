@@ -28,6 +28,10 @@
 //   torch.ops.jlm.topk_rows_masked / complete_frames_masked(..., mask, ld_mask, n_sets, row_set / prompt_set)
 //                             the same two with rows / first words restricted to word sets (jlm_topk_rows_masked,
 //                             jlm_complete_frames_masked; LSTM_Model.predict_reading / complete_reading)
+//   torch.ops.jlm.prime_frames(Model, state row sets, rows, prev, word, n_live, ...)
+//                             the state after a left context: LSTM steps only, ONE op (jlm_prime_frames; LSTM_Model.prime)
+//   torch.ops.jlm.seed_context(Plan, src_h, src_c, last, has, idx)
+//                             primed states gathered behind a plan's pool for frame 0 (jlm_seed_context; Decoder.decode(context=))
 //   torch.ops.jlm.kmeans1d(x, bit, seed, max_iter, tol, code, codebook, scratch, grid, timed)
 //                             scalar k-means compression of one weight tensor: ONE op (jlm_kmeans1d; jlm_amd/compress.py)
 //   torch.ops.jlm.train_*       the kernels of a training step, one op per launcher (jlm_train.hip; jlm_amd/train.py DeviceStepper)
@@ -208,6 +212,7 @@ struct JlmPlan : torch::CustomClassHolder {
     std::vector<hipEvent_t> events;         // JLM_EVENTS_PER_FRAME per frame, created on first timed decode
     int timed_frames = 0;                   // frames of the last timed decode (0: the last decode was not timed)
     int device = -1;
+    int ctx_H = 0;                          // a plan with a left context: the state rows' width (0: no such plan)
 
     JlmPlan(TDict t, IDict i) : tensors(std::move(t)) {
         const Tensor *ints = find(tensors, "ints");
@@ -249,6 +254,17 @@ struct JlmPlan : torch::CustomClassHolder {
         p.out_score = tptr<double>(tensors, "out_score"); p.stride = (int)geti(i, "stride");
         // ABI 11: one spare element behind the trace lengths = the batch's flag word (jlm_beam_state.flags): it travels back with them
         if (p.out_len && find(tensors, "out_len")->numel() > (int64_t)lat.n_sent * lat.beam) st.flags = p.out_len + (size_t)lat.n_sent * lat.beam;
+        // a plan for decodes with a left context: the root rows' prev / word (seed_context writes them) and n_sent more state rows
+        p.ctx_prev = tptr<const int>(tensors, "ctx_prev"); p.ctx_word = tptr<const int>(tensors, "ctx_word");
+        if (p.ctx_prev || p.ctx_word) {
+            const int64_t rmax = (int64_t)lat.n_sent * lat.beam, rows = (int64_t)frames_cap * rmax + lat.n_sent, H = geti(i, "H");
+            TORCH_CHECK(p.ctx_prev && p.ctx_word && find(tensors, "ctx_prev")->numel() >= rmax && find(tensors, "ctx_word")->numel() >= rmax &&
+                            find(tensors, "ctx_prev")->scalar_type() == at::kInt && find(tensors, "ctx_word")->scalar_type() == at::kInt,
+                        "jlm.Plan: ctx_prev and ctx_word come together, int32 [n_sent * beam]");
+            TORCH_CHECK(H > 0 && p.h && p.c && find(tensors, "h")->numel() >= rows * H && find(tensors, "c")->numel() >= rows * H,
+                        "jlm.Plan: a plan with a left context holds n_sent state rows behind the pool (and names H)");
+            ctx_H = (int)H;
+        }
         TORCH_CHECK(st.score && st.lse && st.bp && st.node && st.word && st.cnt && st.live && st.n_live && st.live_base && p.h && p.c &&
                         p.T && p.edge && p.out_nodes && p.out_len && p.out_score && lat.n_sent > 0 && lat.beam > 0 && frames_cap > 0,
                     "jlm.Plan: a required buffer is missing");
@@ -518,6 +534,51 @@ Tensor launch_frames(const char *what, int dev, bool timed, int64_t n_frames, in
             a[f][i] = ms;
         }
     return out;
+}
+
+// The state a decode with a left context starts from (jlm_prime_frames, include/jlm_hip.h): n_steps LSTM steps over right-aligned word
+// rows, nothing else.  State row sets h0/c0 and h1/c1, ping-pong (the result is in set n_steps % 2); rows [n_rows], prev / word
+// [n_steps][n_rows], n_live [n_steps] int32 and its host copy.  Every id must lie in [0, V): the caller checks (jlm_amd/context.py).
+void prime_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                  const Tensor &rows, const Tensor &prev, const Tensor &word, const Tensor &n_live, std::vector<int64_t> n_live_host,
+                  int64_t n_rows, int64_t n_steps) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    check_row_sets("prime_frames", m, R, h0, c0, h1, c1, n_live_host, S, "frame", R);
+    TORCH_CHECK(is(rows, at::kInt, R) && is(prev, at::kInt, S * R) && is(word, at::kInt, S * R) && is(n_live, at::kInt, S),
+                "jlm.prime_frames: int32 rows [n_rows], prev / word [n_steps][n_rows], n_live [n_steps]");
+    TORCH_CHECK(R * (int64_t)std::max(m.H / 4, 1) < 0x7ffffff0ll, "jlm.prime_frames: rows x H / 4 must stay below 2^31");
+    jlm_prime_plan p{};
+    p.n_rows = (int)R; p.n_steps = (int)S;
+    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+    p.rows = ptr<const int>(rows, "rows"); p.prev = ptr<const int>(prev, "prev"); p.word = ptr<const int>(word, "word");
+    p.n_live = ptr<const int>(n_live, "n_live");
+    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
+    p.n_live_host = live_host.data();
+    (void)launch_frames("jlm_prime_frames", h0.device().index(), false, 0, 1,
+                        [&](hipStream_t st, void *const *) { return jlm_prime_frames(&m, &p, st); });
+}
+
+// The primed states of a batch's sentences gathered behind the plan's state pool, and the root rows' prev / word (jlm_seed_context):
+// one launch on the current stream, in front of the plan's frame loop.  src_h / src_c [n_src, H] in the model's state-row format,
+// last / has [n_src] int32, idx [n_sent] int32 on the device (the caller keeps 0 <= idx < n_src).
+void seed_context(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &src_h, const Tensor &src_c, const Tensor &last, const Tensor &has,
+                  const Tensor &idx) {
+    JlmPlan &pl = *plan;
+    TORCH_CHECK(pl.ctx_H > 0 && pl.p.ctx_prev && pl.p.ctx_word, "jlm.seed_context: the plan was made without ctx_prev / ctx_word");
+    const int64_t H = pl.ctx_H, n_src = last.numel();
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(src_h.defined() && src_h.element_size() == 4 && src_h.numel() >= n_src * H && is(src_c, at::kFloat, n_src * H) &&
+                    is(last, at::kInt, n_src) && is(has, at::kInt, n_src) && is(idx, at::kInt, pl.lat.n_sent),
+                "jlm.seed_context: src_h / src_c [n_src, H] of 4-byte values, int32 last / has [n_src], idx [n_sent]");
+    const c10::hip::HIPGuard device_guard(pl.device);
+    const long long G = (long long)pl.frames_cap * pl.lat.n_sent * pl.lat.beam;
+    jlm_check(jlm_seed_context(ptr<const void>(src_h, "src_h"), ptr<const float>(src_c, "src_c"), (int)H, ptr<const int>(last, "last"),
+                               ptr<const int>(has, "has"), (int)n_src, ptr<const int>(idx, "idx"), pl.lat.n_sent, pl.lat.beam, G, pl.p.h,
+                               pl.p.c, const_cast<int *>(pl.p.ctx_prev), const_cast<int *>(pl.p.ctx_word),
+                               c10::hip::getCurrentHIPStream(pl.device).stream()),
+              "jlm_seed_context");
 }
 
 // teacher-forced scoring of n_rows sequences / streams over n_steps steps (jlm_score_frames, include/jlm_hip.h): state row sets h0/c0
@@ -1059,6 +1120,10 @@ TORCH_LIBRARY(jlm, m) {
     m.def("train_expand_codes(Tensor book, Tensor gid, Tensor(a!) w, int n) -> ()", train_expand_codes);
     m.def("train_codebook_grad(Tensor g, Tensor order, Tensor chunks, int n_chunks, int n_groups, Tensor(a!) partial, Tensor(b!) gbook) -> ()",
           train_codebook_grad);
+    m.def("prime_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor rows, "
+          "Tensor prev, Tensor word, Tensor n_live, int[] n_live_host, int n_rows, int n_steps) -> ()", prime_frames);
+    m.def("seed_context(__torch__.torch.classes.jlm.Plan plan, Tensor src_h, Tensor src_c, Tensor last, Tensor has, Tensor idx) -> ()",
+          seed_context);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

@@ -194,11 +194,25 @@ class Decoder():
                 self.perf_log_lstm.append(t_lstm)
                 self.perf_log_softmax.append(t_soft)
 
+    def _context(self, context, n, single=False):
+        """the ``context=`` argument of decode / decode_batch as None or a jlm_amd.context.DecodeContext over the call's n inputs"""
+        if context is None:
+            return None
+        from . import context as _context
+        return _context.resolve(self.model, context, n, self.w2i, single=single)
+
     def decode_batch(self, inputs, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-                     random_sampling=False):
+                     random_sampling=False, context=None):
+        """``context`` (keyword): the words committed in front of every input -- a list with one entry per input (None, empty, or a
+        sequence of word ids / lexicon strings; a string outside the vocabulary reads as <unk>), or a ContextState of one row per input
+        (``self.model.prime``), which any number of calls may reuse.  Input i is decoded as the continuation of
+        [<eos>] + context[i] (jlm_amd/context.py); scores are -log p(path | that history).  None, or nothing but empty entries: the
+        reference's decode."""
         inputs = list(inputs)
+        ctx = self._context(context, len(inputs))
         if beam_width is None:       # the reference's unpruned search, sentence at a time on the host
-            return [self._decode_unpruned(x, topN, vocab_select, samples, top_sampling, random_sampling) for x in inputs]
+            return [self._decode_unpruned(x, topN, vocab_select, samples, top_sampling, random_sampling,
+                                          context=ctx.host_row(i) if ctx is not None else None) for i, x in enumerate(inputs)]
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
             raise ValueError("beam_width must be 1..%d on the GPU path (or None: the unpruned host-side search)" % self.MAX_BEAM)
         if not inputs:
@@ -206,12 +220,14 @@ class Decoder():
         if self.compat_quirks and not vocab_select and self.lattice_vocab:
             # decoder.py:176: `if self.lattice_vocab:` is still true after an earlier vocab_select call, so the full-vocabulary
             # call indexes the OLD list: ValueError for a word outside it, else the old list is what the rows are normalised over
+            if ctx is not None:
+                raise ValueError("compat_quirks: the stale-vocabulary path of the reference takes no left context")
             return [self._decode_stale_vocab(x, topN, beam_width) for x in inputs]
         if not all(inputs):        # (an empty string / list is falsy)
             # the reference's loop over an empty input leaves the <eos> path alone: [(0.0, [])] (decoder.py:220-241)
             keep = [i for i, x in enumerate(inputs) if len(x)]
             sub = self.decode_batch([inputs[i] for i in keep], topN, beam_width, vocab_select, samples, top_sampling,
-                                    random_sampling) if keep else []
+                                    random_sampling, context=ctx.sub(keep) if ctx is not None else None) if keep else []
             out = [[(0.0, [])] for _ in inputs]
             for i, r in zip(keep, sub):
                 out[i] = r
@@ -241,7 +257,8 @@ class Decoder():
             self.last_lattice = lat
             if vocab_select and (len(inputs) - 1) in idx:
                 self.lattice_vocab = lists[idx.index(len(inputs) - 1)]      # the reference leaves the LAST sentence's list behind
-            return idx, self._engine.submit(lat, "static", vocab=vocab, topN=topN, timing=self.perf_timing)
+            return idx, self._engine.submit(lat, "static", vocab=vocab, topN=topN, timing=self.perf_timing,
+                                            context=(ctx.state, [ctx.rows[j] for j in idx]) if ctx is not None else None)
 
         workers = 1 if (samples and random_sampling) else self.prefetch_workers
         try:
@@ -252,14 +269,14 @@ class Decoder():
             heavy = set(e.sentences)
             rest = [i for i in range(len(inputs)) if i not in heavy]
             sub = self.decode_batch([inputs[i] for i in rest], topN, beam_width, vocab_select, samples, top_sampling,
-                                    random_sampling) if rest else []
+                                    random_sampling, context=ctx.sub(rest) if ctx is not None else None) if rest else []
             out = [None] * len(inputs)
             for i, r in zip(rest, sub):
                 out[i] = r
             lv_last = self.lattice_vocab
             for i in sorted(heavy):
                 out[i] = self._decode_unpruned(inputs[i], topN, vocab_select, samples, top_sampling, random_sampling,
-                                               beam_width=beam_width)
+                                               beam_width=beam_width, context=ctx.host_row(i) if ctx is not None else None)
             if (len(inputs) - 1) not in heavy:
                 self.lattice_vocab = lv_last      # (the reference leaves the LAST sentence's list behind)
             return out
@@ -363,11 +380,13 @@ class Decoder():
             chunks.append(cur)
         return chunks
 
-    def _decode_unpruned(self, input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=None, vocab=None):
+    def _decode_unpruned(self, input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=None, vocab=None,
+                         context=None):
         """Decoder.decode of the reference with ``beam_width=None`` (decoder.py:220-241), statement for statement on the
         host: every candidate survives, each frame is one ``predict_with_context`` call over all of its paths (the GPU
         kernels behind LSTM_Model's numpy API), the result is the final frame in generation order, unsorted.  Also the
-        engine of :meth:`_decode_stale_vocab` (a beam and a fixed vocabulary list)."""
+        engine of :meth:`_decode_stale_vocab` (a beam and a fixed vocabulary list).  ``context``: None, or (h [1, H], c [1, H], word)
+        -- the primed state read back and the last word of the history: what the root consumes, and from where."""
         import math
         import numpy as np
         if len(input) == 0:
@@ -380,7 +399,7 @@ class Decoder():
         col = (lambda w: vocab.index(w)) if vocab is not None else (lambda w: w)       # ValueError for a word outside the list
         H = self.model.hidden_size
         # a path: (score, nodes tuple, word id of its last node); per frame also its state rows and probability rows
-        frames = {0: dict(paths=[(0.0, (), ends[0][0][2])])}
+        frames = {0: dict(paths=[(0.0, (), ends[0][0][2] if context is None else int(context[2]))])}
         for i in range(len(input) + 1):
             if i > 0:
                 paths = []
@@ -400,7 +419,7 @@ class Decoder():
             if i == len(input):
                 break                                        # (the reference steps the last frame too and drops the result)
             if i == 0:
-                hid, cel = np.zeros((1, H)), np.zeros((1, H))
+                hid, cel = (np.zeros((1, H)), np.zeros((1, H))) if context is None else (np.asarray(context[0]), np.asarray(context[1]))
             else:
                 hid = np.stack([frames[f]["h"][k] for f, k in cur["src"]])
                 cel = np.stack([frames[f]["c"][k] for f, k in cur["src"]])
@@ -456,8 +475,11 @@ class Decoder():
             yield item
 
     def decode(self, input, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-               random_sampling=False):
-        out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling)[0]
+               random_sampling=False, context=None):
+        """``context`` (keyword): the words committed in front of ``input`` -- one sequence of word ids / lexicon strings, or a
+        ContextState of one row (see decode_batch)."""
+        ctx = self._context(context, 1, single=True)
+        out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling, context=ctx)[0]
         if len(input):
             # the reference's shape: dict frame -> [Node] (decoder.py:79-135), what _build_lattice returns
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]

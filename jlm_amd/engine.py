@@ -72,11 +72,13 @@ class _Plan:
         self.key, self.caps = key, dict(caps)
         kind, vmode, B, beam, F = key[:5]
         perm = bool(key[6]) if len(key) > 6 else False       # reference-compatibility lists (dynamic x segmented, see submit)
+        ctx = bool(key[7]) if len(key) > 7 else False        # a plan for batches with a left context (submit(context=))
         self.B, self.beam, self.F = B, beam, F
         rmax, ncell = B * beam, F * B
         G = F * rmax
         # the LSTM-step kernels address state rows as 16-byte records through a 31-bit index (csrc/jlm_gate.hip): H / 4 records per row
-        if G * max(m.H // 4, 1) >= 0x7ffffff0:
+        # (a plan with a left context keeps the sentences' primed states in B more rows behind the pool: frame 0 reads rows G .. G + B - 1)
+        if (G + (B if ctx else 0)) * max(m.H // 4, 1) >= 0x7ffffff0:
             raise ValueError("a decode plan of %d state rows of %d units is beyond the LSTM-step kernels' addressing (rows x H / 4 < 2^31): "
                              "decode fewer sentences per batch (Decoder.max_batch)" % (G, m.H))
         self.rmax, self.G, self.ncell = rmax, G, ncell
@@ -118,7 +120,7 @@ class _Plan:
         self.n_live = torch.zeros(F, device=dev, dtype=i32)
         self.edge = e(max(caps["nodes"], 1) * beam, f32)
         H, ldt = m.H, m.ldt
-        self.h, self.c = e((G, H), f32), e((G, H), f32)
+        self.h, self.c = e((G + (B if ctx else 0), H), f32), e((G + (B if ctx else 0), H), f32)
         # untied models: T is the state itself -- the same buffer on the f32 path; with split state rows, their plain f32 copy
         self.T = (e((G, H), f32) if m.split_lstm else self.h) if m.mode == "untied" else e((G, ldt), f32)
         self.run_max = self.run_sum = self.part = None
@@ -143,18 +145,25 @@ class _Plan:
         self.h_score = pin(torch.empty(rmax, dtype=f64))
         self.h_nlive = pin(torch.empty(F, dtype=i32))
         self.busy = False
+        # left context: the root rows' prev / word (seed_context_kernel writes entries s * beam), the batch's rows of the primed state
+        self.ctx_prev = self.ctx_word = self.ctx_idx = self.ctx_idx_host = self.ctx_state = None
+        if ctx:
+            self.ctx_prev, self.ctx_word = torch.full((rmax,), -1, device=dev, dtype=i32), torch.zeros(rmax, device=dev, dtype=i32)
+            self.ctx_idx, self.ctx_idx_host = torch.zeros(B, device=dev, dtype=i32), pin(torch.zeros(B, dtype=i32))
         self.nbytes = sum(t.numel() * t.element_size() for t in vars(self).values() if isinstance(t, torch.Tensor) and t.device == dev)
         # torch.classes.jlm.Plan: the same buffers as jlm_lattice / jlm_beam_state / jlm_decode_plan for the frame-loop op
         tensors = dict(ints=self.dev_ints, score=self.score, lse=self.lse, bp=self.bp, node=self.node, word=self.word,
                        cnt=self.cnt, live=self.live, n_live=self.n_live, live_base=self.live_base, edge=self.edge, h=self.h,
                        c=self.c, T=self.T, out_nodes=self.out_nodes, out_len=self.out_len, out_score=self.out_score)
-        for name in ("ysum", "run_max", "run_sum", "part", "Tm"):
+        for name in ("ysum", "run_max", "run_sum", "part", "Tm", "ctx_prev", "ctx_word"):
             if getattr(self, name) is not None:
                 tensors[name] = getattr(self, name)
         ints = dict(n_sent=B, beam=beam, frames=F, kind=2 if dynamic else (1 if vmode == "select" else 0),
                     max_cands=caps["cands"], max_parts=self.n_part, stride=self.stride)
         if self.Tm is not None:
             ints["ld_tm"] = m.ld_tm
+        if ctx:
+            ints["H"] = H
         ints.update({"off_" + n: o for n, o in self.ioff.items()})
         self.obj = ops.backend().Plan(tensors, ints)
 
@@ -227,12 +236,12 @@ class DecodeEngine:
         return self.m._ctx()
 
     # ------------------------------------------------------------------ plans
-    def _plan_for(self, kind, vmode, lat, need, size_class=(), perm=False):
+    def _plan_for(self, kind, vmode, lat, need, size_class=(), perm=False, ctx=False):
         # Buffers are sized for the frame count rounded up to 8 so that ragged inputs (every chunk has its own longest
         # sentence) share plans instead of allocating ~1 GB of state rows and pinned staging per distinct length; the
         # frame loop runs lat.n_frames.
         fkey = _round_up(lat.n_frames, 8)
-        key = (kind, vmode, lat.n_sent, lat.beam, fkey, size_class, bool(perm))
+        key = (kind, vmode, lat.n_sent, lat.beam, fkey, size_class, bool(perm)) + ((True,) if ctx else ())
         for i, p in enumerate(self.plans):
             if p.key == key and p.fits(need) and not p.busy:
                 self.plans.append(self.plans.pop(i))
@@ -258,17 +267,19 @@ class DecodeEngine:
         return p
 
     # ----------------------------------------------------------------- decode
-    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False):
+    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None):
         """Enqueue one batch (upload, the frame-loop op, asynchronous read-back) and return a
         ticket for :meth:`collect`.  Nothing here waits for the GPU.  Successive calls use
         alternating streams (see __init__); every ticket owns its plan's buffers until collected.
         timing=True: HIP events around the kernel groups of every frame (one stream, no side stream);
         timing="inflight": the same events recorded on the batch's own stream of the PIPELINED submit -- a kernel's time
-        then includes what it loses to the other batches in flight (bench.py: `frac_in_pipeline`)."""
+        then includes what it loses to the other batches in flight (bench.py: `frac_in_pipeline`).
+        context: None, or (ContextState, the state's row of every sentence of ``lat``): the sentences' primed states are gathered behind
+        the plan's pool by one launch in front of the frame loop, on the batch's stream (jlm_amd/context.py)."""
         torch = self.torch
         with self._submit_lock, self._ctx():          # (the plan list and the stream rotation are shared by every submitting thread)
             if self.device.type != "cuda" or self.n_streams < 2 or (timing and timing != "inflight"):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context)
             if len(self._streams) != self.n_streams:
                 # the launch streams are shared by every engine on the device: each also gets a side stream inside the op, and
                 # streams beyond the GPU's hardware queues (GPU_MAX_HW_QUEUES, jlm_amd/__init__.py) serialise one another --
@@ -283,9 +294,9 @@ class DecodeEngine:
             if not cur.query():                                  # after whatever the caller queued (weight uploads, ...);
                 strm.wait_stream(cur)                            # nothing pending there in the steady state: no event, no wait
             with torch.cuda.stream(strm):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context)
 
-    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing):
+    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None):
         torch = self.torch
         dynamic = kind == "dynamic"
         vmode = "dynamic" if dynamic else ("select" if vocab is not None else "full")
@@ -304,9 +315,20 @@ class DecodeEngine:
         # dyn_lists[4:6] (optional): the weight-row words of the reference-compatibility mode (DynamicDecoder.compat_quirks on
         # D-softmax / D-softmax* models): per init-list position and per lattice edge (include/jlm_hip.h, jlm_decode_plan)
         perm = dynamic and len(dyn_lists) >= 6 and dyn_lists[4] is not None
-        p = self._plan_for(kind, vmode, lat, need, size_class, perm)
+        if context is not None:
+            state, rows = context
+            rows = np.asarray(rows, dtype=np.int32).reshape(-1)
+            if state.m is not self.m or rows.shape[0] != lat.n_sent or (rows.size and (rows.min() < 0 or rows.max() >= state.n)):
+                raise ValueError("context: one row of a ContextState of this model per sentence of the batch")
+        p = self._plan_for(kind, vmode, lat, need, size_class, perm, ctx=context is not None)
         p.busy = True
         try:
+            if context is not None:
+                # the primed rows of this batch's sentences -> rows G + s of the plan's pool, prev / word of the root rows: one launch
+                p.ctx_state = state          # (kept until the batch is collected: the gather reads it on this stream)
+                p.ctx_idx_host.numpy()[:] = rows
+                p.ctx_idx.copy_(p.ctx_idx_host, non_blocking=True)
+                ops.backend().seed_context(p.obj, state.h, state.c, state.last, state.has, p.ctx_idx)
             done = self._enqueue(p, lat, vocab, dyn_lists, dynamic, perm, max_words, topN, timing)
         except BaseException:
             # nothing may keep the plan: launches already enqueued finish first, then its buffers are free again
@@ -418,6 +440,7 @@ class DecodeEngine:
                 if self.keep_n_live:
                     self.last_n_live = p.h_nlive.numpy()[:lat.n_frames].copy()
         self.last_state = p
+        p.ctx_state = None
         if int(p.h_len[-1]) != 0:
             # (ABI 11) the beam step met a log-normaliser that is not finite: a row's sum of 2^y overflowed (or vanished) in the fixed-reference
             # normaliser -- an overflowed row's hypotheses would score -inf and be pruned, leaving a plausible but wrong n-best

@@ -6,7 +6,11 @@ loader (eval.py:125-166), same log file name/body and the same printed summary
 lines (eval.py:65-122) -- those strings are the file format the golden vectors
 pin.  Extras: ``--root`` (artefact directory; the reference freezes it from
 ``__file__``), ``--batch N`` decodes N sentences per GPU launch sequence instead
-of one (identical output, much faster).
+of one (identical output, much faster), ``--context_words N`` (``-cw``) converts every
+sentence in the middle of its text: its first min(N, words - 1) gold words are the
+left context (``Decoder.decode(context=)``), the kana of the rest is the input and
+the hit is judged on the rest's surface; the log name gains ``_ctx_N``.  With 0
+(the default) name and body of the log are what they were.
 
     python -m jlm_amd.eval --root /path/to/artifacts -e 1 -es 100 -b 10 [--batch 256]
 """
@@ -42,6 +46,8 @@ def build_parser():
         parser.add_argument("--" + name, "-" + short, type=typ, default=default, help=text)
     parser.add_argument("--root", default=None, help="artefact root (data/, train/experiments/)")
     parser.add_argument("--batch", type=int, default=1, help="sentences decoded per batch on the GPU")
+    parser.add_argument("--context_words", "-cw", type=int, default=0,
+                        help="gold words of every sentence given to the decoder as left context (the rest is converted)")
     return parser
 
 
@@ -64,6 +70,10 @@ class Evaluator:
         else:
             self.vocab = Vocab(self.config['vocab_size'])
         self.w2i = self.vocab.w2i
+        self.context_words = max(0, int(getattr(args, "context_words", 0) or 0))
+        if self.context_words and (args.use_ngram or self.config['char_rnn']):
+            raise ValueError("--context_words: the n-gram and character decoders take no left context")
+        self.contexts = None             # with --context_words: every loaded sentence's context tokens (load_eval_set)
         self.decoder = self._make_decoder()
         if hasattr(self.decoder, "perf_timing"):
             self.decoder.perf_timing = True       # the log's per-step times (eval.py:104-121) need the per-frame events
@@ -85,19 +95,28 @@ class Evaluator:
     def log_name(self):
         a = self.args
         kind = "ngram_{}".format(a.ngram_order) if a.use_ngram else "neural"
-        return _LOG_NAME.format(kind, a.experiment_id, a.dynamic_decoding, a.eval_size, a.beam_size, a.comp, a.vocab_select,
+        name = _LOG_NAME.format(kind, a.experiment_id, a.dynamic_decoding, a.eval_size, a.beam_size, a.comp, a.vocab_select,
                                 a.samples, a.top_sampling, a.random_sampling)
+        if self.context_words:
+            name = name[:-len(".txt")] + "_ctx_{}.txt".format(self.context_words)
+        return name
 
     def _decode_all(self, inputs):
         a = self.args
         kw = dict(beam_width=a.beam_size, vocab_select=a.vocab_select, samples=a.samples,
                   top_sampling=a.top_sampling, random_sampling=a.random_sampling)
         step = max(1, a.batch)
+        ctx = self.contexts if self.context_words else None
         if step == 1:                 # sentence at a time, as the reference does
+            if ctx is not None:
+                return [self.decoder.decode(x, context=c, **kw) for x, c in zip(inputs, ctx)]
             return [self.decoder.decode(x, **kw) for x in inputs]
         out = []
         for i in range(0, len(inputs), step):
-            out.extend(self.decoder.decode_batch(inputs[i:i + step], **kw))
+            if ctx is not None:
+                out.extend(self.decoder.decode_batch(inputs[i:i + step], context=ctx[i:i + step], **kw))
+            else:
+                out.extend(self.decoder.decode_batch(inputs[i:i + step], **kw))
         return out
 
     def _timing_lines(self):
@@ -142,9 +161,12 @@ class Evaluator:
 
     def load_eval_set(self):
         """The first ``eval_size`` lines of data/test.txt whose tokens are all in-vocabulary (eval.py:125-166):
-        x = the tokens' readings (the surface where a token has none), y = their surfaces, both concatenated."""
+        x = the tokens' readings (the surface where a token has none), y = their surfaces, both concatenated.  With
+        --context_words N the first min(N, tokens - 1) tokens of a line go to ``self.contexts`` and x, y are those of the rest."""
+        from .context import split_sentence
         want = self.args.eval_size
         xs, ys = [], []
+        self.contexts = [] if self.context_words else None
         with open(os.path.join(_config.data_path, 'test.txt'), 'r', encoding='utf-8') as f:
             lines = f.readlines()
         print('take {} for evaluation from all {} lines'.format(want, len(lines)))
@@ -152,6 +174,9 @@ class Evaluator:
             tokens = line.strip().split(' ')
             if any(self.decoder._check_oov(t) for t in tokens):
                 continue
+            if self.context_words:
+                ctx, tokens = split_sentence(tokens, self.context_words)
+                self.contexts.append(ctx)
             xs.append(''.join(_reading(t) for t in tokens))
             ys.append(''.join(_surface(t) for t in tokens))
             if len(xs) >= want:
