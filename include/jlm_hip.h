@@ -369,9 +369,30 @@ typedef struct {
  * max_cands >= beam * (largest number of nodes ending at one (frame, sentence)).
  * 1 <= beam <= JLM_MAX_BEAM (the reference has no limit, decoder.py:227-229); a cell's candidates live in one wave's
  * LDS -- in one piece up to ~13 k, above that chunk by chunk with the chunks' winners merged (round 6: same order, same result);
- * -1 when max_cands exceeds jlm_beam_step_max_cands(beam, n_frames, mode). */
+ * -1 when max_cands exceeds jlm_beam_step_max_cands(beam, n_frames, mode).
+ * Every cell at frame <= sent_len holds at least one node: the real lattice always has the raw-kana fallback, so an empty cell
+ * is not a case (the kernels clamp a lane's candidate to C - 1 and assume C >= 1). */
 int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *st_host,
                   int frame, int mode, int max_cands, void *stream);
+
+/* ABI 12 (additive): which kernel jlm_beam_step / jlm_backtrace launches for a shape (pure host, no HIP call; the launchers ask
+ * here and decide nowhere else).  JLM_BEAM_CHUNK=<candidates> (every launch through the chunked kernel with that chunk size) and
+ * JLM_BACKTRACE_WAVE=0 (the thread-per-path kernel for every shape) are read once per process and take part.
+ *   0 JLM_BEAM_STEP_ONE_PIECE  beam_step_kernel<mode>: the cell's keys in one wave's LDS (max_cands up to ~13 k at beam 10)
+ *   1 JLM_BEAM_STEP_CHUNKED    beam_step_chunked_kernel<mode>: chunk by chunk, then a selection over the chunk winners
+ * jlm_beam_step_form returns -1 where jlm_beam_step refuses the shape (beam, n_frames or mode out of range; chunk winners past LDS).
+ *   0 JLM_BACKTRACE_WAVE4      backtrace_wave_kernel<4>:  beam <= 64, n_frames x beam <= 256
+ *   1 JLM_BACKTRACE_WAVE8      backtrace_wave_kernel<8>:  beam <= 64, n_frames x beam <= 512
+ *   2 JLM_BACKTRACE_WAVE16     backtrace_wave_kernel<16>: beam <= 64, n_frames x beam <= 1024
+ *   3 JLM_BACKTRACE_THREAD     backtrace_kernel (a thread per path): every other shape */
+#define JLM_BEAM_STEP_ONE_PIECE 0
+#define JLM_BEAM_STEP_CHUNKED 1
+#define JLM_BACKTRACE_WAVE4 0
+#define JLM_BACKTRACE_WAVE8 1
+#define JLM_BACKTRACE_WAVE16 2
+#define JLM_BACKTRACE_THREAD 3
+int jlm_beam_step_form(int beam, int n_frames, int mode, int max_cands);
+int jlm_backtrace_form(int beam, int n_frames);
 
 /* ABI 7: the vocabulary projection + log-sum-exp with the two cross terms of the split product on the INT8 matrix pipe
  * (csrc/jlm_mixed.hip; reference project + softmax, decoder/model.py:141-193, 15-20).

@@ -164,6 +164,8 @@ _SIGS = {
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),
     "jlm_wordlist_lse_form": ([POINTER(Segment), c_int, POINTER(Segment), c_int, c_int, c_int, c_int], c_int),
     "jlm_wordlist_merge_form": ([POINTER(Segment), c_int, POINTER(Segment), c_int, c_int, c_int], c_int),
+    "jlm_beam_step_form": ([c_int, c_int, c_int, c_int], c_int),
+    "jlm_backtrace_form": ([c_int, c_int], c_int),
     "jlm_kmeans1d": ([P, c_longlong, c_int, c_uint64, c_int, c_double, P, P, P, c_int, POINTER(c_int), POINTER(c_float), P], c_int),
     "jlm_train_gemm": ([P, c_longlong, c_longlong, P, c_longlong, c_longlong, P, c_int, c_int, c_int, c_int, c_int, P, P], c_int),
     "jlm_train_embed_rows": ([P, c_int, c_int, P, c_int, c_int, P, c_uint64, c_uint, c_float, P], c_int),

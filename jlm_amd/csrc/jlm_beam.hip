@@ -759,6 +759,35 @@ extern "C" int jlm_beam_step_lds_bytes(int beam, int n_frames, int mode, int max
     return (int)beam_step_lds_bytes(beam, n_frames, mode, max_cands);
 }
 
+// The one place the beam step's kernel is chosen (include/jlm_hip.h lists the forms): jlm_beam_step and jlm_beam_step_form ask here.
+// One piece while the cell's keys fit one wave's LDS; chunk by chunk above that, or for every launch under JLM_BEAM_CHUNK=<candidates>
+// (read once per process; tests: ordinary cells in several chunks); refused where the chunk winners do not fit either.
+struct BeamStepPlan { int form, cap, nch; size_t lds; };
+static BeamStepPlan beam_step_plan(int beam, int n_frames, int mode, int max_cands) {
+    BeamStepPlan p = {-1, 0, 0, 0};
+    if (mode < 0 || mode > 2 || beam < 1 || beam > JLM_MAX_BEAM || n_frames < 1) return p;
+    if (max_cands < 1) max_cands = 1;
+    const size_t lds = beam_step_lds_bytes(beam, n_frames, mode, max_cands);
+    static const int chunk_env = getenv("JLM_BEAM_CHUNK") ? atoi(getenv("JLM_BEAM_CHUNK")) : 0;
+    if (lds > 160 * 1024 || chunk_env > 0) {
+        const int cap = chunk_env > 0 ? chunk_env : beam_step_chunk_cap(beam, n_frames, mode);
+        if (cap <= 0) return p;
+        const int nch = (max_cands + cap - 1) / cap;
+        const size_t lds_c = beam_step_chunked_lds_bytes(beam, n_frames, mode, cap, nch);
+        if (lds_c > 160 * 1024) return p;
+        p.form = JLM_BEAM_STEP_CHUNKED; p.cap = cap; p.nch = nch; p.lds = lds_c;
+        return p;
+    }
+    p.form = JLM_BEAM_STEP_ONE_PIECE; p.lds = lds;
+    return p;
+}
+
+extern "C" int jlm_beam_step_form(int beam, int n_frames, int mode, int max_cands) {
+    return beam_step_plan(beam, n_frames, mode, max_cands).form;
+}
+
+// Every cell at frame <= sent_len holds at least one node (the lattice always has the raw-kana fallback, jlm_amd/lattice.py): an empty
+// cell is not a case the kernels serve -- their clamp of a lane's candidate to C - 1 assumes C >= 1.
 extern "C" int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *st_host, int frame, int mode,
                              int max_cands, void *stream) {
     const jlm_lattice lat = *lat_host;
@@ -769,15 +798,11 @@ extern "C" int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *
     if (lat.beam < 1 || lat.beam > JLM_MAX_BEAM) return -1;
     if (st.lse_part && (!st.live_base || st.n_parts < 1 || mode != 0)) return -1;
     if (max_cands < 1) max_cands = 1;
-    const size_t lds = beam_step_lds_bytes(lat.beam, lat.n_frames, mode, max_cands);
-    // JLM_BEAM_CHUNK=<candidates>: every launch through the chunked kernel with that chunk size (tests: ordinary cells in several chunks)
-    static const int chunk_env = getenv("JLM_BEAM_CHUNK") ? atoi(getenv("JLM_BEAM_CHUNK")) : 0;
-    if (lds > 160 * 1024 || chunk_env > 0) {
-        const int cap = chunk_env > 0 ? chunk_env : beam_step_chunk_cap(lat.beam, lat.n_frames, mode);
-        if (cap <= 0) return -1;
-        const int nch = (max_cands + cap - 1) / cap;
-        const size_t lds_c = beam_step_chunked_lds_bytes(lat.beam, lat.n_frames, mode, cap, nch);
-        if (lds_c > 160 * 1024) return -1;
+    const BeamStepPlan plan = beam_step_plan(lat.beam, lat.n_frames, mode, max_cands);
+    if (plan.form < 0) return -1;
+    if (plan.form == JLM_BEAM_STEP_CHUNKED) {
+        const int cap = plan.cap, nch = plan.nch;
+        const size_t lds_c = plan.lds;
         const void *fc = mode == 0 ? (const void *)beam_step_chunked_kernel<0>
                        : mode == 1 ? (const void *)beam_step_chunked_kernel<1> : (const void *)beam_step_chunked_kernel<2>;
         static JlmLdsGrant grant_c[3];
@@ -789,6 +814,7 @@ extern "C" int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *
         JLM_LAUNCH_CHECK();
         return 0;
     }
+    const size_t lds = plan.lds;
     const void *fn = mode == 0 ? (const void *)beam_step_kernel<0>
                    : mode == 1 ? (const void *)beam_step_kernel<1> : (const void *)beam_step_kernel<2>;
     static JlmLdsGrant grant[3];
@@ -873,19 +899,30 @@ __global__ __launch_bounds__(64) void backtrace_wave_kernel(jlm_lattice lat, jlm
     }
 }
 
+// The one place the backtrace's kernel is chosen (include/jlm_hip.h lists the forms): jlm_backtrace and jlm_backtrace_form ask here.
+// A wave per sentence for beam <= 64 and n_frames x beam <= 256 / 512 / 1024 rows (4 / 8 / 16 registers per lane); a thread per path
+// for the rest, and for every shape under JLM_BACKTRACE_WAVE=0 (read once per process; A/B, tests).
+static int backtrace_form(int beam, int n_frames) {
+    static const int wave_env = getenv("JLM_BACKTRACE_WAVE") ? atoi(getenv("JLM_BACKTRACE_WAVE")) : 1;
+    const long rows = (long)n_frames * beam;
+    if (wave_env && beam <= 64 && rows <= 64 * 16)
+        return rows <= 64 * 4 ? JLM_BACKTRACE_WAVE4 : rows <= 64 * 8 ? JLM_BACKTRACE_WAVE8 : JLM_BACKTRACE_WAVE16;
+    return JLM_BACKTRACE_THREAD;
+}
+
+extern "C" int jlm_backtrace_form(int beam, int n_frames) { return backtrace_form(beam, n_frames); }
+
 extern "C" int jlm_backtrace(const jlm_lattice *lat_host, const jlm_beam_state *st_host, int *out_nodes, int *out_len,
                              double *out_score, int stride, void *stream) {
     const jlm_lattice lat = *lat_host;
     const jlm_beam_state st = *st_host;
     const int total = lat.n_sent * lat.beam;
     if (total <= 0) return 0;
-    // JLM_BACKTRACE_WAVE=0: the thread-per-path kernel for every shape (A/B, tests)
-    static const int wave_env = getenv("JLM_BACKTRACE_WAVE") ? atoi(getenv("JLM_BACKTRACE_WAVE")) : 1;
-    const long rows = (long)lat.n_frames * lat.beam;
-    if (wave_env && lat.beam <= 64 && rows <= 64 * 16) {
+    const int form = backtrace_form(lat.beam, lat.n_frames);
+    if (form != JLM_BACKTRACE_THREAD) {
         const dim3 grid(lat.n_sent), block(64);
-        if (rows <= 64 * 4) hipLaunchKernelGGL(backtrace_wave_kernel<4>, grid, block, 0, (hipStream_t)stream, lat, st, out_nodes, out_len, out_score, stride);
-        else if (rows <= 64 * 8) hipLaunchKernelGGL(backtrace_wave_kernel<8>, grid, block, 0, (hipStream_t)stream, lat, st, out_nodes, out_len, out_score, stride);
+        if (form == JLM_BACKTRACE_WAVE4) hipLaunchKernelGGL(backtrace_wave_kernel<4>, grid, block, 0, (hipStream_t)stream, lat, st, out_nodes, out_len, out_score, stride);
+        else if (form == JLM_BACKTRACE_WAVE8) hipLaunchKernelGGL(backtrace_wave_kernel<8>, grid, block, 0, (hipStream_t)stream, lat, st, out_nodes, out_len, out_score, stride);
         else hipLaunchKernelGGL(backtrace_wave_kernel<16>, grid, block, 0, (hipStream_t)stream, lat, st, out_nodes, out_len, out_score, stride);
         JLM_LAUNCH_CHECK();
         return 0;

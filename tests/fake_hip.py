@@ -192,6 +192,50 @@ def wordlist_merge_form(segs, split, ldt, beam, max_words, mfma=1):
     return wordlist_lse_form(segs, split, 0, ldt, beam, max_words, mfma)
 
 
+# include/jlm_hip.h jlm_beam_step_form / jlm_backtrace_form ids
+BEAM_STEP_FORMS = ("ONE_PIECE", "CHUNKED")
+BEAM_STEP_FORM = {name: i for i, name in enumerate(BEAM_STEP_FORMS)}
+BACKTRACE_FORMS = ("WAVE4", "WAVE8", "WAVE16", "THREAD")
+BACKTRACE_FORM = {name: i for i, name in enumerate(BACKTRACE_FORMS)}
+JLM_MAX_BEAM = 1024
+
+
+def beam_step_lds(beam, n_frames, mode, c):
+    """csrc/jlm_beam.hip beam_step_lds_bytes: the one-piece kernel's LDS with c candidates"""
+    return (c * 8 + (n_frames * beam * 8 if mode == 2 else 0) + ((c + 1) & ~1) * 4 + beam * 8 + ((n_frames + 1) & ~1) * 4 + beam * 12 + 8)
+
+
+def beam_step_form(beam, n_frames, mode, max_cands, chunk=0):
+    """include/jlm_hip.h jlm_beam_step_form with JLM_BEAM_CHUNK = chunk (0: unset): one piece while the keys fit 160 KB of LDS, else (or
+    for every launch with chunk > 0) chunk by chunk; -1 for shapes jlm_beam_step refuses -- arguments out of range, or chunk winners
+    (16 bytes per chunk and rank, one more int per rank) that do not fit beside one chunk"""
+    if mode not in (0, 1, 2) or beam < 1 or beam > JLM_MAX_BEAM or n_frames < 1:
+        return -1
+    max_cands = max(max_cands, 1)
+    lim = 160 * 1024
+    if beam_step_lds(beam, n_frames, mode, max_cands) <= lim and chunk <= 0:
+        return BEAM_STEP_FORM["ONE_PIECE"]
+    cap = chunk
+    if cap <= 0:
+        fixed = beam_step_lds(beam, n_frames, mode, 0)
+        cap = 0 if fixed + 256 * 12 > lim else (lim - fixed) // 12 // 2 // 256 * 256
+    if cap <= 0:
+        return -1
+    nch = (max_cands + cap - 1) // cap
+    if beam_step_lds(beam, n_frames, mode, cap) + (beam + (beam & 1)) * 4 + nch * beam * 16 > lim:
+        return -1
+    return BEAM_STEP_FORM["CHUNKED"]
+
+
+def backtrace_form(beam, n_frames, wave=1):
+    """include/jlm_hip.h jlm_backtrace_form with JLM_BACKTRACE_WAVE = wave: a wave per sentence for beam <= 64 and n_frames x beam <= 256 /
+    512 / 1024 rows, a thread per path for the rest and for every shape with wave = 0"""
+    rows = n_frames * beam
+    if wave and beam <= 64 and rows <= 1024:
+        return BACKTRACE_FORM["WAVE4" if rows <= 256 else "WAVE8" if rows <= 512 else "WAVE16"]
+    return BACKTRACE_FORM["THREAD"]
+
+
 def _seg_tuple(sg):
     return (sg.v_start, sg.v_end, sg.k, sg.t_off, sg.ldb)
 
@@ -239,6 +283,16 @@ class FakeLib:
     def jlm_gemm_nt_split_form(M, N):
         """ABI 12: the path jlm_gemm_nt_split takes"""
         return gemm_nt_split_form(M, N, _atoi_env("JLM_T_STAGES", 3), _atoi_env("JLM_T_XCD", 1))
+
+    @staticmethod
+    def jlm_beam_step_form(beam, n_frames, mode, max_cands):
+        """ABI 12: the kernel jlm_beam_step launches; JLM_BEAM_CHUNK as the library reads it"""
+        return beam_step_form(beam, n_frames, mode, max_cands, _atoi_env("JLM_BEAM_CHUNK", 0))
+
+    @staticmethod
+    def jlm_backtrace_form(beam, n_frames):
+        """ABI 12: the kernel jlm_backtrace launches; JLM_BACKTRACE_WAVE as the library reads it"""
+        return backtrace_form(beam, n_frames, _atoi_env("JLM_BACKTRACE_WAVE", 1))
 
     def jlm_abi_version(self):
         return 12
@@ -1179,6 +1233,7 @@ class FakeLib:
         if fused:
             if live_base is None or st.n_parts < 1 or mode != 0:
                 return -1
+            flags = view(st.flags, 1, np.int32) if _p(st.flags) else None
             pv = view(st.lse_part, st.n_parts * st.ld_part * 2, np.float32).reshape(st.n_parts, st.ld_part, 2).astype(np.float64)
         for s in range(B):
             fs = frame * B + s
@@ -1189,8 +1244,14 @@ class FakeLib:
                 fp = (frame - 1) * B + s
                 for r in range(int(cnt[fp])):
                     q = pv[:, int(live_base[fp]) + r]
-                    mx = q[:, 0].max()
-                    lse[(frame - 1) * rmax + s * beam + r] = mx + np.log((q[:, 1] * np.exp(q[:, 0] - mx)).sum())
+                    with np.errstate(all="ignore"):
+                        mx = q[:, 0].max()
+                        l = mx + np.log((q[:, 1] * np.exp(q[:, 0] - mx)).sum())
+                    if not abs(l) < 1.0e300:   # inf / nan (jlm_beam_state.flags): the batch is flagged, the value replaced, the search goes on
+                        if flags is not None:
+                            flags[0] |= 1
+                        l = 1.0e30
+                    lse[(frame - 1) * rmax + s * beam + r] = l
             nb, ne = int(end_off[fs]), int(end_off[fs + 1])
             gout = frame * rmax + s * beam
             if frame == 0:

@@ -142,21 +142,47 @@ def lstm_xg_f64(h_np, c_np, W, xg, prev, word):
     return hn, cn
 
 
-@pytest.mark.parametrize("chunk", ["48", "256"])
+@pytest.mark.parametrize("chunk", ["48", "64", "256"])
 def test_beam_step_chunked_on_ordinary_cells(chunk):
-    """JLM_BEAM_CHUNK: every beam step through the chunked kernel (csrc/jlm_beam.hip beam_step_chunked_kernel) with chunks of 48 / 256
+    """JLM_BEAM_CHUNK: every beam step through the chunked kernel (csrc/jlm_beam.hip beam_step_chunked_kernel) with chunks of 48 / 64 / 256
     candidates, so that ordinary cells are cut into several -- the kernel tests of all three modes incl. the fused fold of the vocabulary
-    partials, and the decodes whose per-frame beams the reference's traces pin (static, vocabulary selection, incremental).  The
+    partials, every case of test_gpu_beam_forms.py (ties across chunk boundaries, every index a winner, beams above one wave, reused
+    state, the non-finite branch of the chunked kernel's fold), and the decodes whose per-frame beams the reference's traces pin (static,
+    vocabulary selection, incremental).  Every case that launches asserts that jlm_beam_step_form reports the chunked kernel; a case
+    whose chunk winners do not fit LDS must be refused by the form query before any launch and is skipped there with that reason.  The
     variable is read once per process, hence the child."""
     import os, subprocess, sys
     env = dict(os.environ, JLM_BEAM_CHUNK=chunk)
     here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), os.path.join(here, "test_gpu_decode.py"), "-q", "-x", "-m", "gpu",
-                        "-k", "(test_beam_step_and_backtrace or test_beam_step_fused_combine or test_per_frame_beams_match_reference_traces)"
-                              " and not 64-6-300"],        # (19 k candidates in chunks of 48: more chunk winners than LDS)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), os.path.join(here, "test_gpu_decode.py"),
+                        os.path.join(here, "test_gpu_beam_forms.py"), "-q", "-x", "-m", "gpu", "-rs",
+                        "-k", "(test_beam_step_and_backtrace or test_beam_step_fused_combine or test_per_frame_beams_match_reference_traces"
+                              " or test_gpu_beam_forms) and not 64-6-300"],        # (19 k candidates in chunks of 48: more chunk winners than LDS)
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "failed" not in r.stdout, r.stdout[-1000:]
+    skips = [ln for ln in r.stdout.splitlines() if ln.startswith("SKIPPED") and "test_gpu_beam_forms" in ln]
+    assert all("do not fit LDS" in ln for ln in skips), skips
+    import re
+    refused = sum(int(re.match(r"SKIPPED \[(\d+)\]", ln).group(1)) for ln in skips)
+    print("JLM_BEAM_CHUNK=%s: %s; %d refused by the form query" % (chunk, r.stdout.strip().splitlines()[-1], refused))
+
+
+def test_backtrace_thread_per_path_forced():
+    """JLM_BACKTRACE_WAVE=0: the thread-per-path backtrace (csrc/jlm_beam.hip backtrace_kernel) for every shape the wave kernels would
+    serve -- the backtrace cases of test_gpu_beam_forms.py (the limits of every wave form, both strides, long sentences, reused state) and
+    test_beam_step_and_backtrace; every case asserts that jlm_backtrace_form reports thread-per-path.  The variable is read once per
+    process, hence the child."""
+    import os, subprocess, sys
+    env = dict(os.environ, JLM_BACKTRACE_WAVE="0")
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), os.path.join(here, "test_gpu_beam_forms.py"), "-q", "-x",
+                        "-m", "gpu", "-k", "test_beam_step_and_backtrace or test_backtrace_forms or test_long_sentences or test_reused_state"
+                                           " or test_boundaries_of_c"],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert " passed" in r.stdout and "failed" not in r.stdout and "skipped" not in r.stdout, r.stdout[-1000:]
+    print("JLM_BACKTRACE_WAVE=0: %s" % r.stdout.strip().splitlines()[-1])
 
 
 @pytest.mark.parametrize("variant", ["1", "2", "3", "4", "2-ws_l7", "2-ws_cx2", "2-ws_cx8", "2-ws_cx16"])
@@ -699,6 +725,14 @@ def test_beam_step_and_backtrace(L, mode, B, beam, F, max_nodes):
     P = _beam_problem(np.random.default_rng(B * 100 + beam + F), B, beam, F, max_nodes)
     if max_nodes >= 300:
         assert P["max_cands"] > 13312 and L.jlm_beam_step_max_cands(beam, F, mode) > P["max_cands"]
+    # the forms this case launches (ABI 12): the library's answer, the numpy restatement's, and the one the case is meant for
+    from tests.fake_hip import BACKTRACE_FORM, BEAM_STEP_FORM, _atoi_env
+    form = L.jlm_beam_step_form(beam, F, mode, P["max_cands"])
+    assert form == FK.jlm_beam_step_form(beam, F, mode, P["max_cands"])
+    assert form == BEAM_STEP_FORM["CHUNKED" if max_nodes >= 300 or _atoi_env("JLM_BEAM_CHUNK", 0) > 0 else "ONE_PIECE"]
+    bform = L.jlm_backtrace_form(beam, F)
+    assert bform == FK.jlm_backtrace_form(beam, F)
+    assert bform == BACKTRACE_FORM["THREAD" if _atoi_env("JLM_BACKTRACE_WAVE", 1) == 0 else "WAVE4" if F * beam <= 256 else "WAVE8"]
     want = _run_beam(FK, P, mode, False, 5)
     got = _run_beam(L, P, mode, True, 5)
     np.testing.assert_array_equal(got["cnt"], want["cnt"])
@@ -764,6 +798,9 @@ def _run_beam_fused(lib, P, cuda, n_parts):
 @pytest.mark.parametrize("B,beam,F,max_nodes,n_parts", [(7, 10, 9, 12, 24), (64, 3, 6, 40, 5), (3, 20, 22, 70, 96)])
 def test_beam_step_fused_combine(L, B, beam, F, max_nodes, n_parts):
     P = _beam_problem(np.random.default_rng(B * 100 + beam + F), B, beam, F, max_nodes)
+    from tests.fake_hip import BEAM_STEP_FORM, _atoi_env
+    assert L.jlm_beam_step_form(beam, F, 0, P["max_cands"]) == FK.jlm_beam_step_form(beam, F, 0, P["max_cands"]) == \
+        BEAM_STEP_FORM["CHUNKED" if _atoi_env("JLM_BEAM_CHUNK", 0) > 0 else "ONE_PIECE"]
     want = _run_beam_fused(FK, P, False, n_parts)
     got = _run_beam_fused(L, P, True, n_parts)
     np.testing.assert_array_equal(got["cnt"], want["cnt"])
@@ -779,16 +816,27 @@ def test_beam_step_fused_combine(L, B, beam, F, max_nodes, n_parts):
                 np.testing.assert_allclose(got["lse"][sl], want["lse"][sl], rtol=0, atol=1e-9)
 
 
-@pytest.mark.parametrize("R,C,sn", [(3, 2000, 0), (10, 50000, 0), (4, 301, 1)])
+@pytest.mark.parametrize("R,C,sn", [(3, 2000, 0), (10, 50000, 0), (4, 301, 1), (3, 1, 0), (3, 63, 0), (3, 257, 0)])
 def test_softmax_rows(L, R, C, sn):
     rng = np.random.default_rng(R + C)
     ld = (C + 3) // 4 * 4
-    y, yg = _pair(rng.standard_normal((R, ld)).astype(np.float32) * 3)
+    y_np = rng.standard_normal((R, ld)).astype(np.float32) * 3
+    edges = C <= 257 and not sn
+    if edges:                                           # one column, one short of a wave, one past the block: a row of equal logits, and a
+        y_np[1, :C] = 0.75                              # row whose maximum is 80 with the rest at -80 (no overflow, the sum is still 1)
+        y_np[2, :C] = -80.0
+        y_np[2, C // 2] = 80.0
+    y, yg = _pair(y_np)
     p, pg = _pair(np.zeros((R, ld), dtype=np.float32))
     assert FK.jlm_softmax_rows(y.data_ptr(), p.data_ptr(), ld, R, C, sn, 0) == 0
     assert L.jlm_softmax_rows(yg.data_ptr(), pg.data_ptr(), ld, R, C, sn, _st()) == 0
     torch.cuda.synchronize()
-    np.testing.assert_allclose(pg.cpu().numpy()[:, :C], p.numpy()[:, :C], rtol=3e-5, atol=1e-9)
+    got = pg.cpu().numpy()
+    np.testing.assert_allclose(got[:, :C], p.numpy()[:, :C], rtol=3e-5, atol=1e-9)
+    if edges:
+        np.testing.assert_allclose(got[1, :C], np.full(C, 1.0 / C, np.float32), rtol=3e-5, atol=0)
+        assert got[2, C // 2] == 1.0 and got[2, :C].sum() == 1.0
+        assert (got[:, C:] == 0.0).all()                # the padding columns stay untouched
 
 
 def _pack_t(L, fmt):
