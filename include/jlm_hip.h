@@ -892,6 +892,29 @@ int jlm_seed_context(const void *src_h, const float *src_c, int H, const int *la
                      int n_sent, int beam, long long G, void *dst_h, float *dst_c, int *ctx_prev, int *ctx_word, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Prediction of an unfinished last word behind a static decode (Decoder.decode_predict; ABI 12, additive).
+ * One launch (tail_predict_kernel, csrc/jlm_tail.hip), one workgroup per sentence, on the stream of the jlm_decode_frames whose pools
+ * it reads: T / ldt, score, lse, cnt, bp, node of that decode (n_sent, beam, n_frames as its lattice has them; rmax = n_sent * beam).
+ * ids [n_ids]: the vocabulary's words sorted by (reading, id) (jlm_amd/readings.py ReadingIndex.ids).  Sentence s has the spans
+ * sp_off[s] .. sp_off[s + 1]; span j names the frame sp_frame[j] and the words ids[sp_lo[j] .. sp_hi[j]).  A span whose frame is outside
+ * [0, n_frames) or whose words are outside ids[] or empty is skipped.
+ * Candidates of a sentence: for every span in order, every word of it in order, every slot k < min(cnt[frame * n_sent + s], beam) of
+ * row g = frame * rmax + s * beam + k:  (score[g] + lse[g]) - (double)logit  in f64 (mode 1, self-normalised: score[g] - logit), the
+ * logit bit-equal to jlm_edge_logits' for that (row, word) (wordlist_kernel's arithmetic).  Candidate index = position in that order.
+ * The n_out (1 .. 64) best by (score, candidate index) ascending -- a NaN score never ranks -- are written at [s * n_out + rank]:
+ * out_score, out_row (g), out_word, and the parent's trace as jlm_backtrace writes it: out_nodes[(s * n_out + rank) * stride + d] from
+ * node[g] back to the root, out_len.  Ranks beyond the candidate count: (+inf, -1, -1, length 0); a sentence without spans writes
+ * only those.  chunk: candidates selected per round with the winners carried so far (LDS holds n_out + chunk + 512 candidates and
+ * 16 rows of T whatever the candidate count; 0: 4096); the result does not depend on it.  No atomics; one writer per address.
+ * The caller keeps a sentence's candidate count below 2^31.
+ * Returns 0, -1 for bad arguments (n_out, beam above JLM_MAX_BEAM, ldt % 4, segments, a null pointer, a chunk whose LDS does not fit),
+ * -3, or a hipError_t. */
+int jlm_tail_predict(const jlm_segment *segs_host, int n_segs, const float *b2, const float *T, int ldt, int n_sent, int beam,
+                     int n_frames, const double *score, const double *lse, const int *cnt, const int *bp, const int *node, int mode,
+                     const int *ids, int n_ids, const int *sp_off, const int *sp_frame, const int *sp_lo, const int *sp_hi, int n_out,
+                     int chunk, double *out_score, int *out_row, int *out_word, int *out_nodes, int *out_len, int stride, void *stream);
+
+/* ------------------------------------------------------------------------
  * Scalar k-means compression of one weight tensor (jlm_amd/compress.py kmeans_compress; the reference's train/comp.py:20-48,
  * scikit-learn KMeans over the flattened weights).  Greedy k-means++ seeding, then Lloyd's iteration, all sums in integers so that
  * the result does not depend on the launch shape or on the order of any accumulation:

@@ -159,6 +159,8 @@ _SIGS = {
     "jlm_complete_frames_masked": ([POINTER(DecodeModel), POINTER(CompletePlan), P, c_int, c_int, P, P, P], c_int),
     "jlm_prime_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P], c_int),
     "jlm_seed_context": ([P, P, c_int, P, P, c_int, P, c_int, c_int, c_longlong, P, P, P, P, P], c_int),
+    "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,
+                          P, P, P, P, P, c_int, P], c_int),
     "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_split_form": ([], c_int),
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),

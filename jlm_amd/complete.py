@@ -280,7 +280,32 @@ def build_parser():
                     help="only words whose reading starts with KANA (hiragana or katakana): with --top the next words, else the first "
                          "word of every completion")
     ap.add_argument("--exact", action="store_true", help="with --reading: the reading equals KANA")
+    ap.add_argument("--convert", default=None, metavar="KANA",
+                    help="convert KANA whose last word may be unfinished (Decoder.decode_predict): prints the conversions and the "
+                         "predictions of the last word; --prompt is the left context, -b the beam, --n-best the lists' length")
     return ap
+
+
+def convert_main(args, vocab, prompts):
+    """--convert: one (conversions, predictions) pair per prompt, printed as two lists"""
+    from .decoder import Decoder
+    dec = Decoder(experiment_id=args.experiment_id, comp=args.comp)
+    n = 10 if args.n_best is None else args.n_best
+    t0 = time.time()
+    res = dec.decode_predict_batch([args.convert] * len(prompts), topN=n, beam_width=args.beam, context=[list(p[1:]) for p in prompts])
+    dt = time.time() - t0
+    for b, (p, (conv, pred)) in enumerate(zip(prompts, res)):
+        if b:
+            print()
+        head = _gen.render(p[1:], vocab)
+        for title, lst in (("conversions", conv), ("predictions", pred)):
+            print("%s%s:" % (title, " after " + head if head else ""))
+            for score, words in lst:
+                print("%s\t%.4f" % (" ".join(w.split("/")[0] for w in words), score))
+    n_out = sum(len(c) + len(q) for c, q in res)
+    print("inputs: {}  lists: {}  paths/s: {:.0f}".format(len(prompts), 2 * len(prompts), n_out / dt if dt > 0 else float("inf")),
+          file=sys.stderr)
+    return res
 
 
 def main(argv=None):
@@ -305,6 +330,10 @@ def main(argv=None):
         n_unk += u
     if n_unk:
         print("prompts: %d word(s) outside the vocabulary read as <unk>" % n_unk, file=sys.stderr)
+    if args.convert is not None:
+        if args.reading is not None or args.top is not None or isinstance(vocab, CharVocab):
+            ap.error("--convert is a mode of its own (no --reading / --top), on a word model")
+        return convert_main(args, vocab, prompts)
     model = LSTM_Model(experiment_id=args.experiment_id, comp=args.comp)
     sep = "" if isinstance(vocab, CharVocab) else " "
     t0 = time.time()

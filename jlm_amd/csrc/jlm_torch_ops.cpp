@@ -32,6 +32,9 @@
 //                             the state after a left context: LSTM steps only, ONE op (jlm_prime_frames; LSTM_Model.prime)
 //   torch.ops.jlm.seed_context(Plan, src_h, src_c, last, has, idx)
 //                             primed states gathered behind a plan's pool for frame 0 (jlm_seed_context; Decoder.decode(context=))
+//   torch.ops.jlm.tail_predict(Model, Plan, ids, sp_off, sp_frame, sp_lo, sp_hi, n_out, chunk, out_score, out_row, out_word, out_nodes,
+//                              out_len, stride)
+//                             predictions of an unfinished last word behind a plan's decode (jlm_tail_predict; Decoder.decode_predict)
 //   torch.ops.jlm.kmeans1d(x, bit, seed, max_iter, tol, code, codebook, scratch, grid, timed)
 //                             scalar k-means compression of one weight tensor: ONE op (jlm_kmeans1d; jlm_amd/compress.py)
 //   torch.ops.jlm.train_*       the kernels of a training step, one op per launcher (jlm_train.hip; jlm_amd/train.py DeviceStepper)
@@ -581,6 +584,36 @@ void seed_context(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &src_h, 
               "jlm_seed_context");
 }
 
+// The predictions of an unfinished last word behind a plan's static decode (jlm_tail_predict): one launch on the current stream, which
+// must be the one the plan's decode_frames / decode_batch ran on -- it reads that decode's pools.  ids [n_ids] int32: the vocabulary
+// sorted by (reading, id); sp_off [n_sent + 1], sp_frame / sp_lo / sp_hi [n_spans] int32: the batch's spans; out_score [n_sent * n_out]
+// f64, out_row / out_word / out_len [n_sent * n_out] int32, out_nodes [n_sent * n_out, stride] int32.  chunk 0: the launcher's default.
+void tail_predict(const c10::intrusive_ptr<JlmModel> &model, const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &ids, const Tensor &sp_off,
+                  const Tensor &sp_frame, const Tensor &sp_lo, const Tensor &sp_hi, int64_t n_out, int64_t chunk, const Tensor &out_score,
+                  const Tensor &out_row, const Tensor &out_word, const Tensor &out_nodes, const Tensor &out_len, int64_t stride) {
+    JlmPlan &pl = *plan;
+    const jlm_decode_model &m = model->m;
+    const int64_t B = pl.lat.n_sent, R = B * n_out;
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(pl.p.kind != 2 && pl.lat.n_frames >= 1, "jlm.tail_predict: the plan must have run a static decode");
+    TORCH_CHECK(n_out >= 1 && n_out <= 64 && stride >= 1 && chunk >= 0 && chunk <= (1 << 20), "jlm.tail_predict: n_out is 1 .. 64, stride >= 1, chunk >= 0");
+    TORCH_CHECK(is(ids, at::kInt, 1) && is(sp_off, at::kInt, B + 1) && sp_frame.defined() && is(sp_lo, at::kInt, sp_frame.numel()) &&
+                    is(sp_hi, at::kInt, sp_frame.numel()) && sp_frame.scalar_type() == at::kInt && sp_frame.numel() >= 1,
+                "jlm.tail_predict: int32 ids, sp_off [n_sent + 1], sp_frame / sp_lo / sp_hi of one length");
+    TORCH_CHECK(is(out_score, at::kDouble, R) && is(out_row, at::kInt, R) && is(out_word, at::kInt, R) && is(out_len, at::kInt, R) &&
+                    is(out_nodes, at::kInt, R * stride),
+                "jlm.tail_predict: outputs of n_sent * n_out entries (out_nodes: x stride)");
+    const c10::hip::HIPGuard device_guard(pl.device);
+    const std::lock_guard<std::mutex> lock(g_enqueue_mutex);          // (the launcher's one-time kernel attribute)
+    jlm_check(jlm_tail_predict(m.segs, m.n_segs, m.b2, pl.p.T, m.ldt, pl.lat.n_sent, pl.lat.beam, pl.lat.n_frames, pl.st.score, pl.st.lse,
+                               pl.st.cnt, pl.st.bp, pl.st.node, m.self_norm ? 1 : 0, ptr<const int>(ids, "ids"), (int)ids.numel(),
+                               ptr<const int>(sp_off, "sp_off"), ptr<const int>(sp_frame, "sp_frame"), ptr<const int>(sp_lo, "sp_lo"),
+                               ptr<const int>(sp_hi, "sp_hi"), (int)n_out, (int)chunk, ptr<double>(out_score, "out_score"),
+                               ptr<int>(out_row, "out_row"), ptr<int>(out_word, "out_word"), ptr<int>(out_nodes, "out_nodes"),
+                               ptr<int>(out_len, "out_len"), (int)stride, c10::hip::getCurrentHIPStream(pl.device).stream()),
+              "jlm_tail_predict");
+}
+
 // teacher-forced scoring of n_rows sequences / streams over n_steps steps (jlm_score_frames, include/jlm_hip.h): state row sets h0/c0
 // (read by step 0) and h1/c1, ping-pong; T / Tm / part as the model's normaliser needs them; word / target [n_steps][n_rows] int32;
 // n_live [n_steps] int32 on the device and its host copy; nll_seq [n_rows] f64 (accumulated), nll_tok [n_steps][n_rows] f64 (optional),
@@ -1124,6 +1157,9 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor prev, Tensor word, Tensor n_live, int[] n_live_host, int n_rows, int n_steps) -> ()", prime_frames);
     m.def("seed_context(__torch__.torch.classes.jlm.Plan plan, Tensor src_h, Tensor src_c, Tensor last, Tensor has, Tensor idx) -> ()",
           seed_context);
+    m.def("tail_predict(__torch__.torch.classes.jlm.Model model, __torch__.torch.classes.jlm.Plan plan, Tensor ids, Tensor sp_off, "
+          "Tensor sp_frame, Tensor sp_lo, Tensor sp_hi, int n_out, int chunk, Tensor(a!) out_score, Tensor(b!) out_row, Tensor(c!) out_word, "
+          "Tensor(d!) out_nodes, Tensor(e!) out_len, int stride) -> ()", tail_predict);
     m.def("abi_version() -> int", abi_version);
     m.def("beam_step_max_cands(int beam, int n_frames, int mode) -> int", beam_step_max_cands);
 }

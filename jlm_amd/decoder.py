@@ -487,6 +487,115 @@ class Decoder():
         return out
 
 
+    # ------------------------------------------------------------------ conversion of an unfinished reading
+    MAX_PREDICTIONS = 64         # jlm_tail_predict's n_out: one thread per rank
+    _EMPTY_INPUT = "ア"      # an empty input is decoded as this one kana for the sake of its frame 0: the root's distribution
+
+    def _tail_spans(self, text, index):
+        """the tail starts of one input: [(s, lo, hi)] for every s in [0, len) at which vocabulary words properly extend text[s:]"""
+        return index.tail_spans(text if isinstance(text, str) else "".join(text))
+
+    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None):
+        """Conversion while the user types: every input is kana whose LAST word may be unfinished.  -> per input a pair
+        (conversions, predictions).  ``conversions`` is ``decode_batch(inputs, topN, beam_width, context=context)``'s list, the very
+        launches and bits.  ``predictions`` is [(score, [word, ...])], at most ``topN`` (1 .. 64), ascending: the best paths that cover
+        input[:s] with lattice words -- a hypothesis the beam kept at frame s -- and end in one vocabulary word whose reading starts with
+        input[s:] and is longer, over every such s; score = the hypothesis's score - log p(word | it) under the full vocabulary.  Ties
+        keep (s, the word's (reading, id) order, the hypothesis's rank).  The two lists are not merged: a path with one word fewer scores
+        better.  An empty input gives ([(0.0, [])], the likeliest words that have a reading at all).  One more launch per batch behind
+        the frame loop (jlm_tail_predict); only (frame, lo, hi) triples travel per sentence, never word lists.
+        ValueError before any launch: ``beam_width=None``, ``topN`` outside 1 .. 64, compat_quirks with a stale vocabulary, a sentence
+        with a lattice cell the device beam step cannot hold.  TypeError for the other decoders: their rows are not normalised over the
+        full vocabulary, or are not words."""
+        if self.dynamic or self.char_model:
+            raise TypeError("%s has no decode_predict: the last word is predicted from rows normalised over the full word vocabulary "
+                            "(the static Decoder)" % type(self).__name__)
+        inputs = list(inputs)
+        if beam_width is None:
+            raise ValueError("decode_predict needs a beam (beam_width=None is the unpruned host-side search)")
+        if not 1 <= int(beam_width) <= self.MAX_BEAM:
+            raise ValueError("beam_width must be 1..%d" % self.MAX_BEAM)
+        if isinstance(topN, bool) or int(topN) != topN or not 1 <= int(topN) <= self.MAX_PREDICTIONS:
+            raise ValueError("topN must be an integer in 1..%d (got %r)" % (self.MAX_PREDICTIONS, topN))
+        topN, beam_width = int(topN), int(beam_width)
+        if self.compat_quirks and self.lattice_vocab:
+            raise ValueError("compat_quirks: the stale-vocabulary path of the reference normalises over an old word list; predictions need "
+                             "the full vocabulary")
+        if not inputs:
+            return []
+        import numpy as np
+        index = self.model.reading_index()
+        # the batches of decode_batch over the inputs that have kana (the same chunks: the same bits), then the empty inputs as one more
+        full = [i for i, x in enumerate(inputs) if len(x)]
+        empty = [i for i, x in enumerate(inputs) if not len(x)]
+        texts = [x if len(x) else self._EMPTY_INPUT for x in inputs]
+        sub = [inputs[i] for i in full]
+        chunks = [[full[j] for j in c] for c in self._chunks(sub, beam_width)] if full else []
+        for a in range(0, len(empty), self.max_batch):
+            chunks.append(empty[a:a + self.max_batch])
+
+        def prepare(idx):
+            lat = BatchLattice(self._builder, [texts[j] for j in idx], beam_width, pool=self._engine.staging_pool)
+            self._check_cells(lat, idx, beam_width)
+            spans = [self._tail_spans(inputs[j], index) if len(inputs[j]) else [(0,) + tuple(index.ranges(""))[1:]] for j in idx]
+            off = np.zeros(len(idx) + 1, dtype=np.int32)
+            np.cumsum([len(s) for s in spans], out=off[1:])
+            flat = np.array([t for s in spans for t in s], dtype=np.int32).reshape(-1, 3)
+            return idx, lat, (off, flat[:, 0].copy(), flat[:, 1].copy(), flat[:, 2].copy())
+
+        # every lattice before the first launch (the priming of the contexts included): a refusal leaves nothing enqueued
+        prepared = []
+        try:
+            for item in self._prefetched(prepare, chunks, self.prefetch_workers):
+                prepared.append(item)
+        except _CellTooLarge as e:
+            for _idx, lat, _sp in prepared:
+                lat.release()
+            raise ValueError("decode_predict: input(s) %s have a lattice cell with more candidates than the device beam step holds at "
+                             "beam %d (decode_batch would search them on the host); convert them with decode" %
+                             (", ".join("%d (%r)" % (i, inputs[i]) for i in sorted(e.sentences)), beam_width))
+        ctx = self._context(context.context, 1, single=True) if isinstance(context, _Single) else self._context(context, len(inputs))
+        if getattr(self, "_predict_ids", None) is None:
+            import torch
+            self._predict_ids = torch.from_numpy(np.ascontiguousarray(index.ids, dtype=np.int32)).to(self.model.dev.device)
+        out = [None] * len(inputs)
+
+        def finish(idx, ticket):
+            for j, r in zip(idx, self._engine.collect(ticket)):
+                out[j] = r if len(inputs[j]) else ([(0.0, [])], r[1])
+            if ticket[1] is not self.last_lattice:
+                ticket[1].release()
+            self._log_perf()
+
+        def submit(item):
+            idx, lat, sp = item
+            self.last_lattice = lat
+            return idx, self._engine.submit(lat, "static", topN=topN, timing=self.perf_timing,
+                                            context=(ctx.state, [ctx.rows[j] for j in idx]) if ctx is not None else None,
+                                            predict=(sp, self._predict_ids, self.i2w, topN))
+
+        self._run_pipeline(iter(prepared), len(chunks), submit, finish, depth=self.depth_for(max(len(c) for c in chunks), beam_width))
+        self.perf_sen += len(full)
+        return out
+
+    def decode_predict(self, input, topN=10, beam_width=10, context=None):
+        """:meth:`decode_predict_batch` of one input -> (conversions, predictions); ``context`` as :meth:`decode` takes it."""
+        if self.dynamic or self.char_model:
+            raise TypeError("%s has no decode_predict (see Decoder.decode_predict_batch)" % type(self).__name__)
+        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context))[0]
+        if len(input):
+            self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
+                                    for f, nodes in enumerate(self.last_lattice.backward_lookup(0))}
+        return out
+
+
+class _Single:
+    """the ``context=`` of a one-input call on its way through the batch method: resolved there, after the argument checks"""
+
+    def __init__(self, context):
+        self.context = context
+
+
 def __getattr__(name):
     """``from decoder import Decoder, CharRNNDecoder`` (reference decoder/eval.py:7): the character-model decoder lives in
     jlm_amd/decoder_char.py (which imports this module), resolved on first use"""

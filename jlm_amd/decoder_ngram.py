@@ -77,3 +77,9 @@ class NGramDecoder():
 
     def decode_batch(self, inputs, **kw):
         return [self.decode(x, **kw) for x in inputs]
+
+    def decode_predict(self, *a, **kw):
+        """the static neural Decoder's: an n-gram model has no rows normalised over the full vocabulary to predict the last word from"""
+        raise TypeError("NGramDecoder has no decode_predict: the last word is predicted from the static Decoder's full-vocabulary rows")
+
+    decode_predict_batch = decode_predict

@@ -73,6 +73,7 @@ class _Plan:
         kind, vmode, B, beam, F = key[:5]
         perm = bool(key[6]) if len(key) > 6 else False       # reference-compatibility lists (dynamic x segmented, see submit)
         ctx = bool(key[7]) if len(key) > 7 else False        # a plan for batches with a left context (submit(context=))
+        n_pred = int(key[8]) if len(key) > 8 else 0          # a plan for batches whose last word is predicted (submit(predict=)): its n_out
         self.B, self.beam, self.F = B, beam, F
         rmax, ncell = B * beam, F * B
         G = F * rmax
@@ -150,6 +151,17 @@ class _Plan:
         if ctx:
             self.ctx_prev, self.ctx_word = torch.full((rmax,), -1, device=dev, dtype=i32), torch.zeros(rmax, device=dev, dtype=i32)
             self.ctx_idx, self.ctx_idx_host = torch.zeros(B, device=dev, dtype=i32), pin(torch.zeros(B, dtype=i32))
+        # predictions of the last word (jlm_tail_predict): the batch's spans (sp_off [B + 1] | frame | lo | hi, each [caps["spans"]]) and the outputs
+        self.n_pred = n_pred
+        if n_pred:
+            ns, R = caps["spans"], B * n_pred
+            self.pr_off = (0, _round_up(B + 1, 4), _round_up(B + 1, 4) + ns, _round_up(B + 1, 4) + 2 * ns, _round_up(B + 1, 4) + 3 * ns)
+            self.pr_host = pin(torch.zeros(self.pr_off[-1], dtype=i32))
+            self.pr_ints = torch.zeros(self.pr_off[-1], device=dev, dtype=i32)
+            self.pr_score, self.pr_row, self.pr_word, self.pr_len = e(R, f64), e(R, i32), e(R, i32), e(R, i32)
+            self.pr_nodes = e((R, self.stride), i32)
+            self.h_pr_score, self.h_pr_row, self.h_pr_word = pin(torch.empty(R, dtype=f64)), pin(torch.empty(R, dtype=i32)), pin(torch.empty(R, dtype=i32))
+            self.h_pr_len, self.h_pr_nodes = pin(torch.empty(R, dtype=i32)), pin(torch.empty((R, self.stride), dtype=i32))
         self.nbytes = sum(t.numel() * t.element_size() for t in vars(self).values() if isinstance(t, torch.Tensor) and t.device == dev)
         # torch.classes.jlm.Plan: the same buffers as jlm_lattice / jlm_beam_state / jlm_decode_plan for the frame-loop op
         tensors = dict(ints=self.dev_ints, score=self.score, lse=self.lse, bp=self.bp, node=self.node, word=self.word,
@@ -236,12 +248,14 @@ class DecodeEngine:
         return self.m._ctx()
 
     # ------------------------------------------------------------------ plans
-    def _plan_for(self, kind, vmode, lat, need, size_class=(), perm=False, ctx=False):
+    def _plan_for(self, kind, vmode, lat, need, size_class=(), perm=False, ctx=False, n_pred=0):
         # Buffers are sized for the frame count rounded up to 8 so that ragged inputs (every chunk has its own longest
         # sentence) share plans instead of allocating ~1 GB of state rows and pinned staging per distinct length; the
         # frame loop runs lat.n_frames.
         fkey = _round_up(lat.n_frames, 8)
-        key = (kind, vmode, lat.n_sent, lat.beam, fkey, size_class, bool(perm)) + ((True,) if ctx else ())
+        # (a left context, and a predicted last word, add an element each: every other plan keeps its key)
+        key = (kind, vmode, lat.n_sent, lat.beam, fkey, size_class, bool(perm)) + ((bool(ctx),) if (ctx or n_pred) else ()) + \
+            ((int(n_pred),) if n_pred else ())
         for i, p in enumerate(self.plans):
             if p.key == key and p.fits(need) and not p.busy:
                 self.plans.append(self.plans.pop(i))
@@ -267,7 +281,7 @@ class DecodeEngine:
         return p
 
     # ----------------------------------------------------------------- decode
-    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None):
+    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None, predict=None):
         """Enqueue one batch (upload, the frame-loop op, asynchronous read-back) and return a
         ticket for :meth:`collect`.  Nothing here waits for the GPU.  Successive calls use
         alternating streams (see __init__); every ticket owns its plan's buffers until collected.
@@ -275,11 +289,16 @@ class DecodeEngine:
         timing="inflight": the same events recorded on the batch's own stream of the PIPELINED submit -- a kernel's time
         then includes what it loses to the other batches in flight (bench.py: `frac_in_pipeline`).
         context: None, or (ContextState, the state's row of every sentence of ``lat``): the sentences' primed states are gathered behind
-        the plan's pool by one launch in front of the frame loop, on the batch's stream (jlm_amd/context.py)."""
+        the plan's pool by one launch in front of the frame loop, on the batch's stream (jlm_amd/context.py).
+        predict: None, or ((sp_off [n_sent + 1], sp_frame, sp_lo, sp_hi), ids, words, n_out): the batch's spans in CSR (sentence s: the
+        frames its unfinished tail may start at and the range of ``ids`` -- the device copy of ReadingIndex.ids -- of the words whose
+        reading properly extends the tail from there), ``words`` the id -> string list; one more launch behind the frame loop
+        (jlm_tail_predict) selects the n_out best (hypothesis, extension word) pairs per sentence, and :meth:`collect` returns
+        (conversions, predictions) pairs (static full-vocabulary decodes only)."""
         torch = self.torch
         with self._submit_lock, self._ctx():          # (the plan list and the stream rotation are shared by every submitting thread)
             if self.device.type != "cuda" or self.n_streams < 2 or (timing and timing != "inflight"):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict)
             if len(self._streams) != self.n_streams:
                 # the launch streams are shared by every engine on the device: each also gets a side stream inside the op, and
                 # streams beyond the GPU's hardware queues (GPU_MAX_HW_QUEUES, jlm_amd/__init__.py) serialise one another --
@@ -294,9 +313,9 @@ class DecodeEngine:
             if not cur.query():                                  # after whatever the caller queued (weight uploads, ...);
                 strm.wait_stream(cur)                            # nothing pending there in the steady state: no event, no wait
             with torch.cuda.stream(strm):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict)
 
-    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None):
+    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None, predict=None):
         torch = self.torch
         dynamic = kind == "dynamic"
         vmode = "dynamic" if dynamic else ("select" if vocab is not None else "full")
@@ -320,7 +339,24 @@ class DecodeEngine:
             rows = np.asarray(rows, dtype=np.int32).reshape(-1)
             if state.m is not self.m or rows.shape[0] != lat.n_sent or (rows.size and (rows.min() < 0 or rows.max() >= state.n)):
                 raise ValueError("context: one row of a ContextState of this model per sentence of the batch")
-        p = self._plan_for(kind, vmode, lat, need, size_class, perm, ctx=context is not None)
+        if predict is not None:
+            if dynamic or vocab is not None:
+                raise ValueError("predict: the last word is predicted behind a static full-vocabulary decode only")
+            sp = [np.asarray(a, dtype=np.int32).reshape(-1) for a in predict[0]]
+            n_pred = int(predict[3])
+            if not 1 <= n_pred <= 64 or sp[0].shape[0] != lat.n_sent + 1 or not (sp[1].shape == sp[2].shape == sp[3].shape) or \
+                    int(sp[0][0]) != 0 or int(sp[0][-1]) != sp[1].shape[0] or (np.diff(sp[0]) < 0).any():
+                raise ValueError("predict: n_out is 1 .. 64, the spans are CSR over the batch's sentences")
+            sent_of = np.repeat(np.arange(lat.n_sent), np.diff(sp[0]))
+            if sp[1].size and (sp[1].min() < 0 or (sp[1] >= np.asarray(lat.sent_len)[sent_of]).any() or (sp[2] > sp[3]).any()):
+                raise ValueError("predict: a span's frame lies inside its sentence (0 <= frame < length), its words are ids[lo:hi]")
+            # a sentence's candidate index is an int32 on the device
+            per = np.zeros(lat.n_sent, dtype=np.int64)
+            np.add.at(per, sent_of, (sp[3] - sp[2]).astype(np.int64))
+            if int(per.max()) * lat.beam >= 2 ** 31:
+                raise ValueError("predict: a sentence has 2^31 or more (hypothesis, word) candidates")
+            need["spans"] = int(sp[1].shape[0])
+        p = self._plan_for(kind, vmode, lat, need, size_class, perm, ctx=context is not None, n_pred=n_pred if predict is not None else 0)
         p.busy = True
         try:
             if context is not None:
@@ -330,6 +366,8 @@ class DecodeEngine:
                 p.ctx_idx.copy_(p.ctx_idx_host, non_blocking=True)
                 ops.backend().seed_context(p.obj, state.h, state.c, state.last, state.has, p.ctx_idx)
             done = self._enqueue(p, lat, vocab, dyn_lists, dynamic, perm, max_words, topN, timing)
+            if predict is not None:
+                done = self._enqueue_predict(p, sp, predict[1], n_pred)
         except BaseException:
             # nothing may keep the plan: launches already enqueued finish first, then its buffers are free again
             if self.device.type == "cuda":
@@ -339,7 +377,31 @@ class DecodeEngine:
                     pass
             p.busy = False
             raise
+        if predict is not None:
+            return (p, lat, topN, timing, done, predict[2])
         return (p, lat, topN, timing, done)
+
+    PREDICT_CHUNK = 0        # jlm_tail_predict's `chunk` (0: the launcher's default; tests move the chunk boundary)
+
+    def _enqueue_predict(self, p, sp, ids, n_pred):
+        """the spans' upload, jlm_tail_predict and the read-back of its outputs, behind the batch's frame loop on the same stream"""
+        torch = self.torch
+        o, h = p.pr_off, p.pr_host.numpy()
+        h[:sp[0].shape[0]] = sp[0]
+        for k in (1, 2, 3):
+            h[o[k]:o[k] + sp[k].shape[0]] = sp[k]
+        p.pr_ints.copy_(p.pr_host, non_blocking=True)
+        ops.backend().tail_predict(self.m.decode_model(), p.obj, ids, p.pr_ints[o[0]:o[1]], p.pr_ints[o[1]:o[2]], p.pr_ints[o[2]:o[3]],
+                                   p.pr_ints[o[3]:o[4]], int(n_pred), int(self.PREDICT_CHUNK), p.pr_score, p.pr_row, p.pr_word, p.pr_nodes,
+                                   p.pr_len, int(p.stride))
+        for dst, src in ((p.h_pr_score, p.pr_score), (p.h_pr_row, p.pr_row), (p.h_pr_word, p.pr_word), (p.h_pr_len, p.pr_len),
+                         (p.h_pr_nodes, p.pr_nodes)):
+            dst.copy_(src, non_blocking=True)
+        done = None
+        if self.device.type == "cuda":
+            done = torch.cuda.Event(blocking=self.blocking_sync)
+            done.record()
+        return done
 
     def _enqueue(self, p, lat, vocab, dyn_lists, dynamic, perm, max_words, topN, timing):
         torch = self.torch
@@ -427,7 +489,7 @@ class DecodeEngine:
 
     def collect(self, ticket):
         """Wait for a submitted batch and build its n-best lists."""
-        p, lat, topN, timing, done = ticket
+        p, lat, topN, timing, done = ticket[:5]
         with self._ctx():
             if done is not None:
                 done.synchronize()
@@ -456,7 +518,27 @@ class DecodeEngine:
                 raise _lib.JlmHipError("a path score is not finite: this model's logits left the range the fixed-reference normaliser covers "
                                        "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
         out = self._read_out(lat, p.h_nodes.numpy(), p.h_len.numpy()[:-1], p.h_score.numpy(), topN)
+        if len(ticket) > 5:
+            out = list(zip(out, self._read_predictions(lat, p, ticket[5])))
         p.busy = False
+        return out
+
+    @staticmethod
+    def _read_predictions(lat, p, words):
+        """[(score, [word, ...])] per sentence from jlm_tail_predict's outputs: the parent's trace (root dropped, as the n-best read-out drops
+        it) followed by the extension word; a sentence's list ends at its first padded rank"""
+        n = p.n_pred
+        score, row, word = p.h_pr_score.numpy(), p.h_pr_row.numpy(), p.h_pr_word.numpy()
+        ln, nodes = p.h_pr_len.numpy(), p.h_pr_nodes.numpy()
+        out = []
+        for s in range(lat.n_sent):
+            lst = []
+            for o in range(s * n, (s + 1) * n):
+                if row[o] < 0:
+                    break
+                path = lat.words_of(nodes[o, :max(int(ln[o]) - 1, 0)][::-1]).tolist() if ln[o] > 1 else []
+                lst.append((float(score[o]), path + [words[int(word[o])]]))
+            out.append(lst)
         return out
 
     def decode(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, keep_state=False):

@@ -10,7 +10,11 @@ of one (identical output, much faster), ``--context_words N`` (``-cw``) converts
 sentence in the middle of its text: its first min(N, words - 1) gold words are the
 left context (``Decoder.decode(context=)``), the kana of the rest is the input and
 the hit is judged on the rest's surface; the log name gains ``_ctx_N``.  With 0
-(the default) name and body of the log are what they were.
+(the default) name and body of the log are what they were.  ``--cut_last N`` drops
+the last N kana of every sentence's reading -- the last word is unfinished, as
+while the user types -- converts it with ``Decoder.decode_predict`` and judges the
+PREDICTIONS: how often the full target string is the first prediction, among
+them, or missed -- the keystrokes a model saves; the log name gains ``_cut_N``.
 
     python -m jlm_amd.eval --root /path/to/artifacts -e 1 -es 100 -b 10 [--batch 256]
 """
@@ -48,6 +52,9 @@ def build_parser():
     parser.add_argument("--batch", type=int, default=1, help="sentences decoded per batch on the GPU")
     parser.add_argument("--context_words", "-cw", type=int, default=0,
                         help="gold words of every sentence given to the decoder as left context (the rest is converted)")
+    parser.add_argument("--cut_last", type=int, default=0,
+                        help="drop the last N kana of every reading and count how often the full target is among the predictions of "
+                             "the unfinished last word (Decoder.decode_predict)")
     return parser
 
 
@@ -73,6 +80,9 @@ class Evaluator:
         self.context_words = max(0, int(getattr(args, "context_words", 0) or 0))
         if self.context_words and (args.use_ngram or self.config['char_rnn']):
             raise ValueError("--context_words: the n-gram and character decoders take no left context")
+        self.cut_last = max(0, int(getattr(args, "cut_last", 0) or 0))
+        if self.cut_last and (args.use_ngram or self.config['char_rnn'] or args.dynamic_decoding or args.vocab_select):
+            raise ValueError("--cut_last: the last word is predicted by the static decoder over the full vocabulary")
         self.contexts = None             # with --context_words: every loaded sentence's context tokens (load_eval_set)
         self.decoder = self._make_decoder()
         if hasattr(self.decoder, "perf_timing"):
@@ -99,6 +109,8 @@ class Evaluator:
                                 a.samples, a.top_sampling, a.random_sampling)
         if self.context_words:
             name = name[:-len(".txt")] + "_ctx_{}.txt".format(self.context_words)
+        if self.cut_last:
+            name = name[:-len(".txt")] + "_cut_{}.txt".format(self.cut_last)
         return name
 
     def _decode_all(self, inputs):
@@ -118,6 +130,41 @@ class Evaluator:
             else:
                 out.extend(self.decoder.decode_batch(inputs[i:i + step], **kw))
         return out
+
+    def _predict_all(self, inputs):
+        """the predictions of every input's unfinished last word (--cut_last)"""
+        a = self.args
+        step = max(1, a.batch)
+        ctx = self.contexts if self.context_words else None
+        out = []
+        for i in range(0, len(inputs), step):
+            res = self.decoder.decode_predict_batch(inputs[i:i + step], beam_width=a.beam_size,
+                                                    context=ctx[i:i + step] if ctx is not None else None)
+            out.extend(pred for _conv, pred in res)
+        return out
+
+    def evaluate_cut(self):
+        """--cut_last N: -> (first prediction hits, hits further down the list, misses); the three add up to the sentences loaded"""
+        n = self.cut_last
+        hits = {"best hit": 0, "nbest hit": 0, "no hit": 0}
+        with open(self.log_name(), 'w', encoding='utf-8') as log:
+            inputs, targets = self.load_eval_set()
+            cut = [x[:max(len(x) - n, 0)] for x in inputs]
+            t_start = time.time()
+            for x, y, preds in zip(cut, targets, self._predict_all(cut)):
+                sentences = [''.join(_surface(w) for w in words) for _score, words in preds]
+                verdict = "best hit" if sentences and y == sentences[0] else ("nbest hit" if y in sentences else "no hit")
+                hits[verdict] += 1
+                log.write(verdict + '\n')
+                log.write('{}\t{}\n'.format(y, x))
+                log.writelines(s + '\n' for s in sentences)
+            summary = 'cut_last {} pred_best_hit {} pred_nbest_hit {} pred_miss {} eval_size {}'.format(
+                n, hits["best hit"], hits["nbest hit"], hits["no hit"], len(inputs))
+            log.write(summary)
+            log.write("--- %s seconds ---" % (time.time() - t_start))
+            print(summary)
+            print("--- %s seconds ---" % (time.time() - t_start))
+        return hits["best hit"], hits["nbest hit"], hits["no hit"]
 
     def _timing_lines(self):
         a, d = self.args, self.decoder
@@ -203,7 +250,8 @@ def main(argv=None):
     if args.root:
         _config.set_root(args.root)
     os.makedirs('eval', exist_ok=True)
-    return Evaluator(args).evaluate()
+    ev = Evaluator(args)
+    return ev.evaluate_cut() if ev.cut_last else ev.evaluate()
 
 
 if __name__ == '__main__':

@@ -60,6 +60,30 @@ class ReadingIndex:
         hi = bisect.bisect_right(self.readings, prefix) if exact else bisect.bisect_left(self.readings, prefix + "\U0010ffff")
         return np.sort(self.ids[lo:hi])
 
+    def ranges(self, prefix):
+        """-> (lo, mid, hi): ``ids[lo:mid]`` are the words whose reading equals ``prefix``, ``ids[mid:hi]`` the words whose reading
+        starts with it and is longer (its proper extensions), both in (reading, id) order -- contiguous because the index is sorted so.
+        Hiragana is folded to katakana first.  ``Decoder.decode_predict`` sends such (lo, hi) pairs to the device, never word lists."""
+        return self._ranges(to_katakana(prefix))
+
+    def _ranges(self, prefix):
+        """:meth:`ranges` of a prefix already in katakana"""
+        lo = bisect.bisect_left(self.readings, prefix)
+        mid = bisect.bisect_right(self.readings, prefix, lo)
+        hi = bisect.bisect_left(self.readings, prefix + "\U0010ffff", mid)
+        return lo, mid, hi
+
+    def tail_spans(self, text):
+        """[(s, mid, hi)] for every s in [0, len(text)) at which some word's reading properly extends text[s:]: the tail starts of an
+        input whose last word is unfinished (``Decoder.decode_predict``).  The input is folded to katakana once."""
+        text = to_katakana(text)
+        out = []
+        for s in range(len(text)):
+            _lo, mid, hi = self._ranges(text[s:])
+            if hi > mid:
+                out.append((s, mid, hi))
+        return out
+
     @staticmethod
     def mask(id_lists, V):
         """Bit masks of word-id lists: -> (uint32 [n_sets, ceil(V / 32)], the set index of each list).  Bit w & 31 of word w >> 5 of
