@@ -131,14 +131,31 @@ int jlm_vocab_lse_stationary(const jlm_segment *segs_host, int n_segs, const flo
  * so that max|x| * scale stays below 65504.  jlm_pack_split_f16 writes the
  * blocks that cover k rounded up to 16 values (zero padded) and leaves the rest
  * of each destination row alone, so a matrix can be packed in column ranges
- * with different scales (dst / src advanced by a multiple of 16 values). */
+ * with different scales (dst / src advanced by a multiple of 16 values).
+ * The format, to the bit (tests/operand_cases.py split_pair; every writer is held
+ * to it byte for byte by tests/test_gpu_operand_formats.py):
+ *   x  = f32(src * scale)   ONE f32 rounding of the product (none for a power of two)
+ *   hi = f16(x)             round to nearest even; f16 subnormals are kept
+ *   lo = f16(x - hi)        x - hi is exact in f32; lo is taken against THIS hi
+ * for every writer of split rows: this packer, jlm_pack_split_f16_col and the
+ * split-row epilogue of the LSTM step (x = h' * h_scale; with the f32 copy of
+ * h' requested, the split rows are exactly the split of that copy).  hi is never
+ * rounded from the exact product while lo is taken from the f32 one: the launcher
+ * also takes scales that are no power of two, and there the two would disagree
+ * about hi on every f16 rounding tie of x.  A finite x gives finite halves with
+ * |lo| <= ulp(hi) / 2 and f16(hi + lo) == hi -- but where a residual within 2^-12
+ * of half an ulp rounds up to exactly that half ulp under an odd hi (a tie).
+ * Written: the blocks covering k rounded up to 16 values, columns k .. zero;
+ * nothing else. */
 int jlm_pack_split_f16(const float *src, int rows, int k, int ld, float scale,
                        void *dst, int ld_dst, void *stream);
 
 /* ABI 4: k-means compressed weights (train/comp.py:52-80; selected by decoder/model.py:74-78 through `comp`): per tensor a
  * uint8 code array and a float32 codebook of <= 256 entries.  dst[r][c] = codebook[code[r][c]] for c < k, on the device
  * (what np.take(codebook, code) does on the host in train/comp.py:70): the codes stay resident, the float panel is
- * expanded from them where the kernels need it. */
+ * expanded from them where the kernels need it.  Codebook entries are copied bit for bit (-0.0, subnormals, inf, NaN
+ * payloads); a code >= n_codes gives +0.0 (the kernel's table of 256 entries is zero-filled behind the book), never a read past the
+ * book.  Columns k .. ld_dst of a destination row are left alone. */
 int jlm_dequant_u8(const uint8_t *code, int rows, int k, int ld_code, const float *codebook, int n_codes,
                    float *dst, int ld_dst, void *stream);
 
@@ -194,7 +211,8 @@ int jlm_gemm_nt_split(const void *A, int lda, const int *a_rows, const void *B, 
 #define JLM_T_CFG128 3
 int jlm_gemm_nt_split_form(int M, int N);
 
-/* One column of split rows from a vector: dst[r][col] = split(v[r] * scale). */
+/* One column of split rows from a vector: dst[r][col] = split(v[r] * scale) -- hi and lo as jlm_pack_split_f16 defines them, two f16
+ * stores per row; the other 15 values of the touched 32-byte block and every other block are left alone. */
 int jlm_pack_split_f16_col(const float *v, int rows, float scale, void *dst, int ld_dst, int col, void *stream);
 
 /* jlm_vocab_lse_stationary on split rows: segs[i].B = split rows of the
@@ -402,7 +420,19 @@ int jlm_backtrace_form(int beam, int n_frames);
  * the f16 part as columns k (hi of b2 2^eB log2 e) and k + 1 (its f16 residual x 2^11), so a row has nb = ceil((k + 2) / 32)
  * blocks (ld_dst = 32 nb in 4-byte units, nb <= 8) -- or, for k a multiple of 32, nb = k / 32 and no bias columns (below).
  * jlm_pack_mixed: src [rows, k] f32 (stride ld) and bias [rows] -> dst; scale = 2^eB, bias_scale = 2^eB log2 e, s8 = the
- * segment's int8 scale (a power of two >= max |f16(src scale)| / 127). */
+ * segment's int8 scale (a power of two >= max |f16(src scale)| / 127).  k is a multiple of 4 (-1 otherwise).
+ * The format, to the bit (tests/operand_cases.py mixed_row_bytes / t_row_bytes; tests/test_gpu_operand_formats.py):
+ *   vocabulary rows   x = f32(src scale) (exact: a power of two), hi = f16(x), lo = x - hi (f32, not rounded to f16);
+ *                     hi8 = rint(hi / s8), lo8 = rint(lo / (s8 / 2048)): ties to even, then clipped to +-127; zero behind k.
+ *                     Bias columns: xb = f32(bias bias_scale) (one f32 rounding), column k = f16(xb), column k + 1 =
+ *                     f16((xb - f16(xb)) 2048), zeros for bias = NULL; the f16 columns behind them zero.  Every byte of a row's nb
+ *                     blocks is written.
+ *   hypothesis rows   m = f32(2^eT log2 e).  hi = f16 of the EXACT product T m -- ONE rounding (v_fma_mixlo_f16), not f16(f32(T m)) --;
+ *                     the row's scale per segment s = the smallest power of two >= max |hi| / 127 over the segment's k values
+ *                     ((bits(f32(max / 127)) + 0x007fffff) & 0x7f800000; 1.0 for an all-zero segment), hi8 = rint(hi / s),
+ *                     lo8 = rint((f32(T m) - hi) / (s / 2048)), ties to even, clipped to +-127, zero behind k.  Written: every byte
+ *                     of the blocks of rows below min(*n_dev, n_rows_max) and float i < n_segs of their JLM_MAX_SEGMENTS scale
+ *                     floats; the other scale floats, the rows from there on and the rest of the last 32-row block are left alone. */
 int jlm_pack_mixed(const float *src, int rows, int k, int ld, const float *bias, float scale, float bias_scale, float s8,
                    void *dst, int ld_dst, void *stream);
 /* The hypothesis side: T [G, ldt] f32 -> packed rows Tm, COMPACT: packed row r = hypothesis row rows[r] (a frame's live rows: one
@@ -420,7 +450,13 @@ int jlm_pack_t_mixed(const jlm_segment *segs_host, const float *t_scale, int n_s
  * (v_mfma_scale_f32_32x32x64_f8f6f4: one instruction per 32 k-values for both terms, accumulated into the f16 pass's f32 accumulator;
  * csrc/jlm_mx6_body.h, csrc/jlm_mx6.hip; reference project + softmax, decoder/model.py:141-193, 15-20).  Same 128-byte blocks, strides
  * and buffers as the int8 form; granules 4-6 of a block hold the FP6 planes (hi6, lo6) and granule 7 of a row's first block their E8M0
- * scales, one per plane and 32 k-values.  Selected by s8 = 0:
+ * scales, one per plane and 32 k-values.  The f16 plane of BOTH mx6 packers is f16(f32(x scale)) -- two roundings, where the int8
+ * hypothesis-row packer has one --, the FP6 planes are those of that hi and of f32(x scale) - hi over the real k-values: nearest e2m3
+ * value, ties to even, saturating at 7.5, against the smallest power of two s with max <= 7.5 s per plane and block (byte 0 for an all-zero
+ * block).  Vocabulary rows: half 0 = hi6, half 1 = lo6, every byte of a row written (granule 7 zero but for the scale bytes j / 8 + j of
+ * block j in the row's first block).  Hypothesis rows: the halves swapped; of granule 7 only the scale bytes j / 8 + j (j < nb) of a
+ * segment's first block are written -- the rest of that granule, granule 7 of the other blocks and the row's scale floats are left alone.
+ * Selected by s8 = 0:
  *   jlm_pack_mixed(..., s8 = 0, ...)           packs a vocabulary block as mx6 rows (at most 8 blocks per row: k + 2 <= 256 or k = 256);
  *   jlm_pack_t_mixed6                            packs hypothesis rows in that form (same arguments and stride as jlm_pack_t_mixed);
  *   jlm_vocab_lse_mixed(_fr)(..., s8[i] = 0 for EVERY segment, ...)  runs the launch on mx6 rows (-2: formats mixed within a launch,

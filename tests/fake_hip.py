@@ -15,7 +15,8 @@ import re
 import numpy as np
 
 NEG = -3.0e38
-_CT = {np.float32: ctypes.c_float, np.float64: ctypes.c_double, np.int32: ctypes.c_int32, np.float16: ctypes.c_uint16}
+_CT = {np.float32: ctypes.c_float, np.float64: ctypes.c_double, np.int32: ctypes.c_int32, np.float16: ctypes.c_uint16,
+       np.uint32: ctypes.c_uint32}
 
 
 def _p(x):
@@ -721,8 +722,9 @@ class FakeLib:
             return 0
         buf = (ctypes.c_uint8 * (rows * ld_code)).from_address(_p(code))
         cv = np.frombuffer(buf, dtype=np.uint8).reshape(rows, ld_code)[:, :k]
-        book = view(codebook, n_codes, np.float32)
-        out = view(dst, (rows - 1) * ld_dst + k, np.float32)
+        book = np.zeros(256, dtype=np.uint32)            # the kernel's table is zero-filled: a code >= n_codes gives +0.0
+        book[:n_codes] = view(codebook, n_codes, np.uint32)         # (bit patterns: a NaN's payload survives the copy)
+        out = view(dst, (rows - 1) * ld_dst + k, np.uint32)
         for r in range(rows):
             out[r * ld_dst:r * ld_dst + k] = book[cv[r]]
         return 0
@@ -788,7 +790,9 @@ class FakeLib:
 
     def jlm_pack_mixed(self, src, rows, k, ld, bias, scale, bias_scale, s8, dst, ld_dst, stream):
         nb = ld_dst // 32
-        if rows < 0 or k <= 0 or ld < k or ld_dst % 32 or nb not in ((k + 2 + 31) // 32, (k + 31) // 32) or nb > 8:
+        if rows <= 0:
+            return 0
+        if k <= 0 or k % 4 or ld < k or ld_dst % 32 or nb not in ((k + 2 + 31) // 32, (k + 31) // 32) or nb > 8:
             return -1
         cols = k + 2 <= 32 * nb                    # room for the bias columns
         if rows == 0:
@@ -849,7 +853,8 @@ class FakeLib:
         blk[:, :, 80:88] = half0[:, :, 16:24]
         blk[:, :, 88:96] = half1[:, :, 16:24]
         blk[:, :, 96:112] = half1[:, :, :16]
-        blk[:, :, 112:128] = 0
+        if not swap:                                     # vocabulary rows: the rest of granule 7 is zero; the hypothesis-row packer writes
+            blk[:, :, 112:128] = 0                       # its scale bytes only and leaves the rest of the granule (and of the others') alone
         blk[:, 0, 112:112 + nb] = b0
         blk[:, 0, 120:120 + nb] = b1
 
@@ -933,10 +938,15 @@ class FakeLib:
             Tv = np.stack([view(_p(T) + 4 * (int(r) * ldt + sg.t_off), sg.k, np.float32) for r in g])
             x = np.zeros((n, 32 * nb), dtype=np.float32)
             x[:, :sg.k] = Tv * np.float32(float(t_scale[i]) * 1.4426950408889634)
-            amax = np.abs(x.astype(np.float16).astype(np.float32)).max(axis=1)
+            # the f16 plane is rounded ONCE, from the exact product (pack_t_mixed_kernel: v_fma_mixlo_f16) -- 24 x 24 bits are exact in
+            # float64 --; the row maximum and the int8 hi plane are taken from it, the residual against the f32 product x
+            hi = np.zeros((n, 32 * nb), dtype=np.float16)
+            hi[:, :sg.k] = (Tv.astype(np.float64) * np.float64(np.float32(float(t_scale[i]) * 1.4426950408889634))).astype(np.float16)
+            amax = np.abs(hi.astype(np.float32)).max(axis=1)
             with np.errstate(divide="ignore"):
                 s_t = np.where(amax > 0, np.exp2(np.ceil(np.log2(np.maximum(amax, 1e-37) / 127.0))), 1.0).astype(np.float32)
-            hi, h8, l8 = self._quant(x, s_t[:, None])
+            q = lambda v: np.clip(np.rint(v), -127, 127).astype(np.int8)
+            h8, l8 = q(hi.astype(np.float32) / s_t[:, None]), q((x - hi.astype(np.float32)) / (s_t[:, None] / np.float32(2048.0)))
             if sg.k + 2 <= 32 * nb:
                 hi[:, sg.k] = np.float16(t_scale[i])
                 hi[:, sg.k + 1] = np.float16(float(t_scale[i]) / 2048.0)

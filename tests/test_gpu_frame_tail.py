@@ -21,6 +21,7 @@ import pytest
 torch = pytest.importorskip("torch")
 from jlm_amd import _lib            # noqa: E402
 from tests import golden_cases as gc  # noqa: E402
+from tests.operand_cases import tie_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -83,6 +84,10 @@ def _problem(widths, beam):
     T[1] = 0.0                                         # an all-zero row (scale bytes 0), a tiny one, one with zeros in it
     T[2] *= np.float32(2.0 ** -30)
     T[3, ::2] = 0.0
+    # rows whose f32 product with the packer's multiplier f32(2^-4 log2 e) is an f16 rounding tie while the exact product is not
+    # (tests/operand_cases.py tie_values): the fused tail and the two launches must stay on ONE rounding of the f16 plane
+    tie_at = np.arange(0, F * rmax, 5)
+    T[tie_at] = tie_rows(np.float32(np.float32(2.0 ** -4) * np.float32(1.4426950408889634)), len(tie_at), ldt)
     ncell = F * B
     cnt, live_base = np.zeros(ncell, np.int32), np.zeros(ncell, np.int32)
     g0 = (np.arange(F)[:, None] * rmax + np.arange(B)[None, :] * beam).astype(np.int32).reshape(-1)

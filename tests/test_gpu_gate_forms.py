@@ -10,7 +10,8 @@ The form a launch runs is the library's own answer (jlm_lstm_step_form, ABI 12):
 * saturated gates (|z| of 60-90 on a share of the gate columns, zero-state rows among them).
 
 Every case checks h' and c' of the stepped rows against the f64 evaluation of the original f32 operands and against the numpy double
-(FakeLib) on the same split rows, and every row that was not stepped bit for bit.  One operand set per bound: a device count of n steps
+(FakeLib) on the same split rows, and every row that was not stepped bit for bit.  The split rows the epilogue writes are held to the
+format: the split-pair invariants on every stepped row, and, where the f32 copy is written, bytes equal to split_pair(copy x h_scale).  One operand set per bound: a device count of n steps
 the first n entries of the row list, so every case checks a prefix of one result.
 
 Forced forms: test_gpu_kernels.py::test_lstm_step_xg_forced_forms runs this module (and test_lstm_step_xg) in a child per JLM_GATE_V
@@ -26,6 +27,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 from jlm_amd import _lib                                                    # noqa: E402
+from tests import operand_cases as OC                                       # noqa: E402
 from tests.fake_hip import FakeLib, gate_v_env, lstm_step_form              # noqa: E402
 from tests.test_gpu_kernels import _pack, _st, _unsplit, lstm_xg_f64        # noqa: E402
 
@@ -170,8 +172,14 @@ def test_gate_form(L, case):
     c_got = c_out[sel].cpu().numpy()
     np.testing.assert_allclose(h_got, d.hn[:m], rtol=RTOL, atol=ATOL)
     np.testing.assert_allclose(c_got, d.cn[:m], rtol=RTOL, atol=ATOL)
+    # the split-row epilogue writes the format (tests/operand_cases.py): every stepped row keeps the split rows' promises, and with the
+    # f32 copy requested its bytes are split_pair(copy x h_scale) of that copy -- no tolerance
+    h_bytes = h_out[sel].cpu().numpy().view(np.uint8).reshape(m, 4 * H)
+    OC.check_split_pairs(h_bytes)
     if hf32:
-        np.testing.assert_allclose(hf[sel].cpu().numpy(), d.hn[:m], rtol=RTOL, atol=ATOL)
+        hf_got = hf[sel].cpu().numpy()
+        np.testing.assert_allclose(hf_got, d.hn[:m], rtol=RTOL, atol=ATOL)
+        OC.assert_bytes(h_bytes, OC.split_row_bytes(OC.f32_product(hf_got, HS)), "split h' against split_pair(f32 copy x h_scale) (row, byte)")
     k = d.fake_pos < m
     np.testing.assert_allclose(h_got[d.fake_pos[k]], d.fake_h[k], rtol=RTOL, atol=ATOL)
     np.testing.assert_allclose(c_got[d.fake_pos[k]], d.fake_c[k], rtol=RTOL, atol=ATOL)

@@ -7,6 +7,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 from jlm_amd import _lib            # noqa: E402
+from tests import operand_cases as OC  # noqa: E402
 from tests.fake_hip import FakeLib  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -71,7 +72,10 @@ def test_gemm_nt(L, M, N, K, maps):
 
 
 @pytest.mark.parametrize("H,E,R,use_rows", [(64, 32, 10, False), (64, 32, 200, True), (512, 256, 700, True),
-                                            (512, 200, 2560, True), (128, 352, 33, True)])
+                                            (512, 200, 2560, True), (128, 352, 33, True),
+                                            # from 8 192 rows on the launcher takes 128 x 64 tiles (TileCfg<2, 2, 2, 1>: the gate epilogue in two
+                                            # 64-row passes); 8 229 rows leave a partial last tile and keep the numpy double cheap
+                                            (64, 32, 8192 + 37, True)])
 def test_lstm_step(L, H, E, R, use_rows):
     rng = np.random.default_rng(H + E + R)
     V, G = 500, R * 3 + 7
@@ -892,6 +896,9 @@ def test_mx6_packers_match_the_numpy_double(L, widths, R):
     T_np[3] = 0.0                                        # an all-zero row: scale bytes 0, codes 0
     T_np[5, ::2] = 0.0
     T_np[7] *= np.float32(2.0 ** -30)
+    # rows on f16 rounding ties of the f32 product with the packer's multiplier f32(2^-4 log2 e) (tests/operand_cases.py tie_values):
+    # the mx6 packers round the f16 plane TWICE (f32 product, then f16), and so does the double
+    T_np[9::8] = OC.tie_rows(np.float32(np.float32(2.0 ** -4) * np.float32(1.4426950408889634)), len(T_np[9::8]), ldt)
     T = torch.as_tensor(T_np).cuda()
     n = len(widths)
     ld_tm = L.jlm_mixed_t_stride(segs, n)
@@ -917,14 +924,26 @@ def test_mx6_packers_match_the_numpy_double(L, widths, R):
     tsc = [float(ts[i]) for i in range(n)]
     assert FK.jlm_pack_t_mixed6(segs, tsc, n, T_np.ctypes.data, ldt, None, R, None, host_tm.ctypes.data, ld_tm, 0) == 0
     raw = Tm.cpu().numpy().view(np.uint8).reshape(-1)
-    dev_tm = np.zeros_like(host_tm)
+    dev_tm = raw[OC.tm_image_index(R, ld_tm)][:R]
     ngr = sum(segs[i].ldb // 32 for i in range(n)) * 8
-    for r in range(R):
-        blk = (r // 32) * 32 * ld_tm * 4
-        for g in range(ngr):
-            dev_tm[r, 16 * g:16 * g + 16] = raw[blk + g * 512 + (r % 32) * 16: blk + g * 512 + (r % 32) * 16 + 16]
     bad = np.argwhere(dev_tm[:, :16 * ngr] != host_tm[:, :16 * ngr])
     assert len(bad) == 0, ("hypothesis rows differ (row, byte):", bad[:8].tolist())
+    # --- the vocabulary packer over the k list of tests/test_gpu_operand_formats.py, on its rows: quotients on .5, planes that clip, +-0,
+    # biases with zeros among them (bias given and NULL; k = 256 only without bias columns: eight blocks per row at most)
+    for k in [k for k in OC.MIXED_K if k % 4 == 0]:
+        src_np, bias_np = OC.mixed_case_inputs(np.random.default_rng(k + R), 9, k, 4, 1.0)
+        ld_dst = k if k == 256 else (k + 2 + 31) // 32 * 32
+        src_g, bias_g = torch.as_tensor(src_np).cuda(), torch.as_tensor(bias_np).cuda()
+        for with_bias in (True, False):
+            dev = torch.full((9, 4 * ld_dst), 0xA5, dtype=torch.uint8, device="cuda")
+            host = np.full((9, 4 * ld_dst), 0xA5, dtype=np.uint8)
+            assert L.jlm_pack_mixed(src_g.data_ptr(), 9, k, k + 4, bias_g.data_ptr() if with_bias else None, 16.0, 16.0 * 1.4426950408889634, 0.0,
+                                    dev.data_ptr(), ld_dst, _st()) == 0
+            assert FK.jlm_pack_mixed(src_np.ctypes.data, 9, k, k + 4, bias_np.ctypes.data if with_bias else None, 16.0, 16.0 * 1.4426950408889634,
+                                     0.0, host.ctypes.data, ld_dst, 0) == 0
+            torch.cuda.synchronize()
+            bad = np.argwhere(dev.cpu().numpy() != host)
+            assert len(bad) == 0, ("vocabulary rows differ (k, bias, (row, byte)):", k, with_bias, bad[:8].tolist())
 
 
 @pytest.mark.parametrize("V,widths,bounds,R,maxp", [(2000, [200, 100, 52], [0, 700, 1300, 2000], 48, 16), (2000, [200, 100, 52], [0, 700, 1300, 2000], 300, 96),
