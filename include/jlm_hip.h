@@ -738,6 +738,20 @@ typedef struct {
 #define JLM_SCORE_EVENTS_PER_STEP 5
 int jlm_score_frames(const jlm_decode_model *model_host, const jlm_score_plan *plan_host, void *stream, void *const *events);
 
+/* ABI 12 (additive): the last launch of a scoring step on its own (csrc/jlm_score.hip, score_fold_kernel; jlm_score_frames calls it
+ * once per step with the step's rows of target / nll_tok).  For every row r < min(*n_dev, n_rows_max) (n_dev NULL: n_rows_max), with
+ * w = target[r] and the segment sg that holds w:
+ *   lse = log sum_p part[p][r].sum * exp(part[p][r].max) over the n_parts slices part[(p * ld_part + r) * 2 + {0: max, 1: sum exp}]
+ *         (f32 maxima and exponentials, f64 sums; not read and taken as 0 for self_norm != 0)
+ *   y   = T[r * ldt + sg.t_off .. + sg.k) . sg.B[(w - sg.v_start) * sg.ldb .. + sg.k) + b2[w]     (f32, fmaf)
+ *   nll = lse - y (f64);  nll_seq[r] += nll;  nll_tok[r] = nll when nll_tok != NULL.
+ * flags (one device int, may be NULL): |= 1 when a row's lse is not finite (its nll is stored as computed), |= 2 when a row's target
+ * lies in no segment -- that row's nll is NaN, nothing of B, T or b2 is read for it.  Rows from min(*n_dev, n_rows_max) on are left
+ * alone in nll_seq and nll_tok.  -1: n_segs out of range, or ldt / a segment's k, ldb or t_off not a multiple of 4. */
+int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, const float *T, int ldt, const float *part, int ld_part,
+                   int n_parts, int self_norm, const int *target, const int *n_dev, int n_rows_max, double *nll_seq, double *nll_tok,
+                   int *flags, void *stream);
+
 /* ------------------------------------------------------------------------
  * Ancestral sampling (LSTM_Model.generate, jlm_amd/generate.py): what the reference's sample(pred, temperature) and its sampling
  * loop do one predict() at a time on the host (decoder/model.py:28-33, 213-245; train/test.py).

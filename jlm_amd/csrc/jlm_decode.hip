@@ -363,11 +363,6 @@ extern "C" int jlm_lse_probe(const jlm_decode_model *m, const int *rowlist, cons
                                 nullptr, stream);
 }
 
-// jlm_score.hip: the fold of a scoring step (score_fold_kernel)
-int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, const float *T, int ldt, const float *part, int ld_part,
-                   int n_parts, int self_norm, const int *target, const int *n_dev, int n_rows_max, double *nll_seq, double *nll_tok,
-                   int *flags, void *stream);
-
 // The LSTM step and the T projection of a row set's live prefix r < *ndev (bound: its static bound; g = rows[r] = r) -- the launches of
 // one step of jlm_score_frames and jlm_generate_frames.  f32_copy: the plain f32 copy of the new state an untied split-row model's
 // vocabulary GEMMs read (its T); T: the projection's destination (not written on untied models: T is the state there).

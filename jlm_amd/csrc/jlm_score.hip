@@ -9,6 +9,7 @@
 //   logit   lane `sub` takes the 16-byte chunks k4 = sub, sub + 8, ... of the target's weight row and the row of T (all requested
 //           before the first is used), fmaf in k order, three xor-shuffle adds, + b2[w]: wordlist_kernel<0>'s f32 arithmetic
 //           (jlm_edge_logits).
+// Both equalities are held to the bit by tests/test_gpu_score_fold.py, which calls the kernel through jlm_score_fold.
 // Latency-bound and tiny next to the step's three matrix kernels: one slice read per lane and slice row, one weight row per row.
 #include "jlm_common.h"
 
@@ -113,8 +114,8 @@ __global__ __launch_bounds__(SF_THREADS) void score_fold_kernel(
     if (nll_tok) nll_tok[r] = nll;
 }
 
-// (internal: called by jlm_score_frames, jlm_decode.hip) target, nll_tok: the step's row of the [n_steps][n_rows] arrays
-int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, const float *T, int ldt, const float *part, int ld_part,
+// (called by jlm_score_frames, jlm_decode.hip; exported for the tests) target, nll_tok: the step's row of the [n_steps][n_rows] arrays
+extern "C" int jlm_score_fold(const jlm_segment *segs_host, int n_segs, const float *b2, const float *T, int ldt, const float *part, int ld_part,
                    int n_parts, int self_norm, const int *target, const int *n_dev, int n_rows_max, double *nll_seq, double *nll_tok,
                    int *flags, void *stream) {
     if (n_segs < 1 || n_segs > JLM_MAX_SEGMENTS || ldt % 4 != 0) return -1;

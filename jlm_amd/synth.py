@@ -255,6 +255,11 @@ def wide_segs(V):
     return [(200, 0, V // 4), (100, V // 4, (3 * V) // 5), (50, (3 * V) // 5, None)]
 
 
+def odd_segs(widths=(32, 16, 8)):
+    """cuts at 501 / 1 203 over V = 2 003: no segment starts at, and the vocabulary does not end on, a multiple of 4"""
+    return [(widths[0], 0, 501), (widths[1], 501, 1203), (widths[2], 1203, None)]
+
+
 def wideh_segs(V):
     """200 / 100 / 36: two mixed-row shapes and a short segment the hybrid launch keeps on split rows"""
     return [(200, 0, V // 4), (100, V // 4, (3 * V) // 5), (36, (3 * V) // 5, None)]
@@ -302,6 +307,9 @@ def build_fixture(root, name, exp_id=1):
     that their 2 200-word lexicon still gives a dense lattice.  Names:
 
       small-{tied,untied,dsoftmax,vtable}[-sn]   V=2000 H=64 E=32 (unit tests)
+      odd-{tied,untied,dsoftmax,vtable}[-sn]     V=2003 H=64 E=36, segments 32 / 16 / 8 cut at 501 / 1 203: a vocabulary and cuts that are
+                                                  no multiples of 4 (unaligned logit columns, a partial last 4-word chunk)
+      oddw-vtable                                 the same vocabulary and cuts with segments 200 / 100 / 52 (the mixed-row shapes)
       small-char / mid-char                       character models (config char_rnn): tied softmax over the characters of the
                                                   in-vocabulary words' display strings (300 / 3 000 CJK code points), same lexicon sizes
       wide-{vtable,dsoftmax}                      V=2000 H=64, segments 200 / 100 / 50 (the mixed-row shapes, small vocabulary)
@@ -328,6 +336,12 @@ def build_fixture(root, name, exp_id=1):
     if size == "small":
         scale = 0.25                      # keeps the tiny model's logits O(1)
         V, H, E, segs, alphabet = 2000, 64, 32, small_segs(2000), 12
+    elif size == "odd":
+        scale = 0.25
+        V, H, E, segs, alphabet = 2003, 64, 36, odd_segs(), 12
+    elif size == "oddw":
+        scale = 0.1
+        V, H, E, segs, alphabet = 2003, 64, 200, odd_segs((200, 100, 52)), 12
     elif size == "wide":
         scale = 0.1
         V, H, E, segs, alphabet = 2000, 64, 200, wide_segs(2000), 12

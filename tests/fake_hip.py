@@ -1068,6 +1068,50 @@ class FakeLib:
         view(lse, int(g.max()) + 1, np.float64)[g] = mx + np.log(s)
         return 0
 
+    def jlm_score_fold(self, segs, n_segs, b2, T, ldt, part, ld_part, n_parts, self_norm, target, n_dev, n_rows_max, nll_seq, nll_tok,
+                       flags, stream):
+        """Contract (include/jlm_hip.h), in float64 from the f32 operands: nll = lse - y per live row"""
+        if n_segs < 1 or n_segs > 8 or ldt % 4:
+            return -1
+        sgs = [segs[i] for i in range(n_segs)]
+        if any(sg.k % 4 or sg.ldb % 4 or sg.t_off % 4 for sg in sgs):
+            return -1
+        if n_rows_max <= 0:
+            return 0
+        n = _n(n_rows_max, n_dev)
+        if n <= 0:
+            return 0
+        tgt = view(target, n, np.int32)
+        seq = view(nll_seq, n, np.float64)
+        tok = view(nll_tok, n, np.float64) if _p(nll_tok) else None
+        fl = view(flags, 1, np.int32) if _p(flags) else None
+        pv = None
+        if not self_norm:
+            pv = view(part, n_parts * ld_part * 2, np.float32).reshape(n_parts, ld_part, 2)[:, :n].astype(np.float64)
+        for r in range(n):
+            w = int(tgt[r])
+            sg = next((x for x in sgs if x.v_start <= w < x.v_end), None)
+            if sg is None:
+                if fl is not None:
+                    fl[0] |= 2
+                nll = np.nan
+            else:
+                brow = view(sg.B + 4 * (w - sg.v_start) * sg.ldb, sg.k, np.float32).astype(np.float64)
+                trow = view(_p(T) + 4 * (r * ldt + sg.t_off), sg.k, np.float32).astype(np.float64)
+                y = float(np.dot(brow, trow)) + float(view(_p(b2) + 4 * w, 1, np.float32)[0])
+                lse = 0.0
+                if not self_norm:
+                    with np.errstate(all="ignore"):
+                        mx = pv[:, r, 0].max()
+                        lse = mx + np.log((pv[:, r, 1] * np.exp(pv[:, r, 0] - mx)).sum())
+                    if not abs(lse) < 1.0e300 and fl is not None:
+                        fl[0] |= 1
+                nll = lse - y
+            seq[r] += nll
+            if tok is not None:
+                tok[r] = nll
+        return 0
+
     # ------------------------------------------------------------- word lists
     def _segs(self, segs, n_segs):
         return [segs[i] for i in range(n_segs)]

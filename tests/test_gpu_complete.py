@@ -252,7 +252,12 @@ def _e2e(name, fx, monkeypatch, R, N, B, stop_id=None, seed=0):
     return model, prompts, res
 
 
-@pytest.mark.parametrize("name", SMALL + [UNTIED_F32])
+# V = 2 003 cut at 501 / 1 203 (jlm_amd/synth.py): ld_logits > V, every segment's logits start at an unaligned column
+ODD = ["odd-tied", "odd-untied", "odd-dsoftmax", "odd-vtable", "odd-tied-sn", "odd-untied-sn", "odd-dsoftmax-sn", "odd-vtable-sn",
+       "oddw-vtable", "odd-untied@f32"]
+
+
+@pytest.mark.parametrize("name", SMALL + [UNTIED_F32] + ODD)
 def test_complete_matches_oracle(name, fx, monkeypatch):
     _e2e(name, fx, monkeypatch, R=6, N=5, B=6)
 
@@ -321,6 +326,25 @@ def test_complete_repeat_cuts_and_neighbours(name, fx):
     same_all(res, model.complete(prompts, N, beam_width=B, n_best=4, max_rows=1))        # one prompt per call
     for r in (0, 9, 22):                                                                 # alone in its call
         same(res[r], model.complete([prompts[r]], N, beam_width=B, n_best=4)[0])
+
+
+@pytest.mark.parametrize("n_prompts,B", [(1, 1), (1, 64), (33, 3)])
+def test_complete_odd_vocabulary_row_counts(n_prompts, B, fx):
+    """V = 2 003: a call of n_prompts x beam rows gives what the same prompts give inside a call of 40 prompts"""
+    f = fx("odd-vtable")
+    model = load_model(f["root"])
+    assert model.dev.V == 2003
+    prompts = ragged_prompts(40, 2003, seed=17, lo=1, hi=7)
+    N = 4
+    big = model.complete(prompts, N, beam_width=B)
+    got = model.complete(prompts[:n_prompts], N, beam_width=B)
+    assert len(got) == n_prompts
+    for a, b in zip(got, big):
+        assert len(a) == len(b) == B
+        for x, y in zip(a, b):
+            assert np.array_equal(x[0], y[0])
+            np.testing.assert_allclose(x[1], y[1], rtol=0, atol=1e-9)
+            assert abs(x[2] - y[2]) <= 1e-9
 
 
 def test_complete_errors(fx):

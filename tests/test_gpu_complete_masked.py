@@ -341,7 +341,10 @@ def _e2e_reading(name, fx, monkeypatch, R):
     return model, prompts, index
 
 
-@pytest.mark.parametrize("name", ["small-vtable", "small-tied-sn", "small-dsoftmax", UNTIED_F32])
+@pytest.mark.parametrize("name", ["small-vtable", "small-tied-sn", "small-dsoftmax", UNTIED_F32,
+                                  # V = 2 003 cut at 501 / 1 203: the last 16-byte chunk of a logit row, and of the bit mask's four
+                                  # bits per chunk, is partial
+                                  "odd-vtable", "odd-tied", "odd-tied-sn", "odd-dsoftmax", "odd-untied", "oddw-vtable", "odd-untied@f32"])
 def test_reading_prediction_matches_oracle(name, fx, monkeypatch):
     _e2e_reading(name, fx, monkeypatch, R=24)
 
@@ -375,6 +378,46 @@ def test_small_and_empty_sets(fx):
     with pytest.raises(ValueError):
         model.predict_reading(prompts, KANA[0])                               # one string per context
     assert model.complete_reading([prompts[0]], [KANA[40]], 3) == [[]]         # a prefix no word has
+
+
+def test_odd_vocabulary_last_word_and_row_counts(fx):
+    """V = 2 003.  A set that holds only word 2 002 -- the one word of the last, partial chunk -- selects exactly that word, with the
+    oracle's log p; sets on both sides of every segment cut; calls of 1, 31, 32 and 33 contexts give what the same contexts give inside a
+    call of 64"""
+    f = fx("odd-vtable")
+    model = load_model(f["root"])
+    V = model.dev.V
+    assert V == 2003
+    prompts = ragged_prompts(64, V, seed=23, lo=1, hi=7)
+    lm = oracle_lm(f["root"])
+    last = np.array([V - 1], dtype=np.int64)
+    cuts = np.array([0, 500, 501, 1202, 1203, 2002], dtype=np.int64)
+    tail = np.arange(1996, V, dtype=np.int64)                        # the last full chunk and the partial one
+    allowed = [(last, cuts, tail, None)[p % 4] for p in range(64)]
+    top = model.predict_top(prompts, n=6, allowed=allowed)
+    for p in range(64):
+        lp = _oracle_logp(lm, prompts[p])[2]
+        ids, logp = top[p]
+        if allowed[p] is None:
+            a = np.arange(V)
+        else:
+            a = allowed[p]
+        want = a[np.lexsort((a, -lp[a]))][:6]
+        assert len(ids) == min(6, len(a)), p
+        assert sorted(ids.tolist()) == sorted(want.tolist()), (p, ids, want)
+        np.testing.assert_allclose(logp, lp[ids], rtol=0, atol=1e-5)
+        if p % 4 == 0:
+            assert ids.tolist() == [V - 1]
+    for n in (1, 31, 32, 33):
+        got = model.predict_top(prompts[:n], n=6, allowed=allowed[:n])
+        assert len(got) == n
+        for p in range(n):
+            assert np.array_equal(got[p][0], top[p][0]), (n, p)
+            np.testing.assert_allclose(got[p][1], top[p][1], rtol=0, atol=1e-9)
+    # the first generated word of a completion inside the one-word set
+    res = model.complete(prompts[:8], 3, beam_width=4, first_allowed=[last] * 8)
+    for hyps in res:
+        assert len(hyps) == 4 and all(int(h[0][0]) == V - 1 and np.isfinite(h[2]) for h in hyps)
 
 
 @pytest.mark.parametrize("name", ["small-vtable", "small-untied"])

@@ -194,6 +194,42 @@ def test_primed_state_against_the_oracle(name):
         d.model.prime([[-1]])
 
 
+def test_primed_state_odd_vocabulary(fx):
+    """the priming loop on the V = 2 003 model cut at 501 / 1 203: contexts that end and pass through the first and last word of every
+    segment, against the oracle's state at the bars above; calls of 1, 31, 32 and 33 contexts give the rows of a call of 64 at the same
+    bars"""
+    from tests.gpu_rows import load_model, oracle_lm
+    f = fx("odd-vtable")
+    model = load_model(f["root"])
+    assert model.dev.V == 2003
+    lm = oracle_lm(f["root"])
+    rng = np.random.RandomState(41)
+    edges = (0, 500, 501, 1202, 1203, 2002)
+    ctxs = []
+    for i in range(64):
+        c = [int(x) for x in rng.randint(2, 2003, size=rng.randint(1, 7))]
+        c[-1] = edges[i % 6]
+        c[0] = edges[(i // 6) % 6] if len(c) > 1 else c[0]
+        ctxs.append(c)
+    ctxs[5] = []
+    state = model.prime(ctxs)
+    h, c = state.numpy()
+    assert h.shape == (64, 64) == c.shape
+    for i, ids in enumerate(ctxs):
+        assert int(state.last_host[i]) == ([cc.EOS] + ids)[-1] and bool(state.has_host[i]) == bool(ids)
+        if ids:
+            hw, cw = cc.oracle_state(lm, [cc.EOS] + ids[:-1])
+            np.testing.assert_allclose(h[i], hw[0], rtol=1e-4, atol=1e-5)
+            np.testing.assert_allclose(c[i], cw[0], rtol=1e-4, atol=1e-5)
+        else:
+            assert not h[i].any() and not c[i].any()
+    for n in (1, 31, 32, 33):
+        hn, cn = model.prime(ctxs[:n]).numpy()
+        assert hn.shape == (n, 64)
+        np.testing.assert_allclose(hn, h[:n], rtol=1e-4, atol=1e-5)
+        np.testing.assert_allclose(cn, c[:n], rtol=1e-4, atol=1e-5)
+
+
 # ---------------------------------------------------------------------------------------------- the seeding kernel as launched
 @pytest.mark.parametrize("fmt", ["split", "f32"])
 @pytest.mark.parametrize("H", [32, 512])

@@ -200,7 +200,11 @@ def oracle_follow(lm, prompts, ids, temperature, seed, n_words):
     return agree, amb, out
 
 
-@pytest.mark.parametrize("name", SMALL + ["peaked20-vtable", UNTIED_F32])
+# V = 2 003 cut at 501 / 1 203 (jlm_amd/synth.py): ld_logits > V, every segment's logits start at an unaligned column
+ODD = ["odd-tied", "odd-untied", "odd-dsoftmax", "odd-vtable", "odd-tied-sn", "odd-vtable-sn", "oddw-vtable", "odd-untied@f32"]
+
+
+@pytest.mark.parametrize("name", SMALL + ["peaked20-vtable", UNTIED_F32] + ODD)
 def test_generate_matches_oracle(name, fx, monkeypatch):
     f, model = fixture_model(fx, name, monkeypatch)
     V = model.dev.V
@@ -253,6 +257,21 @@ def test_generate_cut_mixed_and_repeat(name, fx):
         solo, solo_nll = model.generate([prompts[r]] * (r + 1), 9, temperature=0.8, seed=2 ** 64 - 3)
         assert np.array_equal(solo[r], ids[r]), r
         np.testing.assert_allclose(solo_nll[r], nll[r], rtol=0, atol=1e-9)
+
+
+def test_generate_odd_vocabulary_row_counts(fx):
+    """V = 2 003: calls of 1, 31, 32 and 33 rows draw what the same rows draw inside a call of 64 (a row's u depends on its index alone)"""
+    f = fx("odd-vtable")
+    model = load_model(f["root"])
+    assert model.dev.V == 2003
+    prompts = ragged_prompts(64, 2003, seed=31, lo=1, hi=7)
+    ids, nll = model.generate(prompts, 9, temperature=0.8, seed=123)
+    for n in (1, 31, 32, 33):
+        got, got_nll = model.generate(prompts[:n], 9, temperature=0.8, seed=123)
+        assert len(got) == n
+        for r in range(n):
+            assert np.array_equal(got[r], ids[r]), (n, r)
+            np.testing.assert_allclose(got_nll[r], nll[r], rtol=0, atol=1e-9)
 
 
 def test_generate_stop_id(fx):

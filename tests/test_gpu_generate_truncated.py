@@ -202,7 +202,11 @@ def test_sample_rows_trunc_rejects_bad_top_p():
 
 # ------------------------------------------------------------------------------------------------------------- end to end
 @pytest.mark.parametrize("name,top_k,top_p", [("small-tied", 5, 0.7), ("small-vtable", 8, None), ("small-vtable", None, 0.6),
-                                              ("small-char", 6, 0.9), ("peaked20-vtable", 5, 0.8), ("small-tied-sn", 4, 0.5)])
+                                              ("small-char", 6, 0.9), ("peaked20-vtable", 5, 0.8), ("small-tied-sn", 4, 0.5),
+                                              # V = 2 003 cut at 501 / 1 203: unaligned segment columns, a partial last chunk
+                                              ("odd-vtable", 8, 0.9), ("odd-vtable", None, 0.6), ("oddw-vtable", 5, 0.7),
+                                              ("odd-tied", 6, None), ("odd-untied", 6, 0.8), ("odd-dsoftmax", 7, 0.8),
+                                              ("odd-tied-sn", 4, 0.5), ("odd-vtable-sn", 5, 0.7)])
 def test_generate_truncated_matches_oracle(name, top_k, top_p, fx):
     f = fx(name)
     model = load_model(f["root"])
@@ -256,6 +260,22 @@ def test_generate_truncated_cut_mixed_and_repeat(name, fx):
         solo, solo_nll = model.generate([prompts[r]] * (r + 1), 9, **kw)
         assert np.array_equal(solo[r], ids[r]), r
         np.testing.assert_allclose(solo_nll[r], nll[r], rtol=0, atol=1e-9)
+
+
+def test_generate_truncated_odd_vocabulary_row_counts(fx):
+    """V = 2 003: calls of 1, 31, 32 and 33 rows draw what the same rows draw inside a call of 64 (a row's u depends on its index alone)"""
+    f = fx("odd-vtable")
+    model = load_model(f["root"])
+    assert model.dev.V == 2003
+    prompts = ragged_prompts(64, 2003, seed=31, lo=1, hi=7)
+    kw = dict(temperature=0.8, seed=123, top_k=6, top_p=0.85)
+    ids, nll = model.generate(prompts, 9, **kw)
+    for n in (1, 31, 32, 33):
+        got, got_nll = model.generate(prompts[:n], 9, **kw)
+        assert len(got) == n
+        for r in range(n):
+            assert np.array_equal(got[r], ids[r]), (n, r)
+            np.testing.assert_allclose(got_nll[r], nll[r], rtol=0, atol=1e-9)
 
 
 def test_generate_truncated_stop_id(fx):

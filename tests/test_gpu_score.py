@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-from jlm_amd import _lib, config as jconfig, synth      # noqa: E402
+from jlm_amd import _lib, config as jconfig, rowsets, synth      # noqa: E402
 from tests.gpu_rows import UNTIED_F32, fixture_model, load_model, lse, oracle_lm     # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -83,15 +83,37 @@ def _check_bars(got, want, tag, sentence_bar):
 
 SMALL = ["small-tied", "small-untied", "small-dsoftmax", "small-vtable", "small-tied-sn", "small-vtable-sn",
          "wide-vtable", "wide-dsoftmax", "wideh-vtable", "wide128-tied"]
+# V = 2 003 cut at 501 / 1 203 (jlm_amd/synth.py): no segment starts at, and the vocabulary does not end on, a multiple of 4
+ODD = ["odd-tied", "odd-untied", "odd-dsoftmax", "odd-vtable", "odd-tied-sn", "odd-vtable-sn", "oddw-vtable"]
+ODD_UNTIED_F32 = "odd-untied@f32"
+ODD_EDGES = (0, 500, 501, 1202, 1203, 2002)         # the first and last word of every segment of the odd fixtures
 
 
-@pytest.mark.parametrize("name", SMALL + [UNTIED_F32])
+def _on_edges(seqs):
+    """the sequences with their first and last words moved onto the segment edges of the odd fixtures, every pair of them in turn: a
+    word is the target of one step and the input of the next"""
+    out = []
+    for i, s in enumerate(seqs):
+        s = list(s)
+        if s:
+            s[-1] = ODD_EDGES[(i // 6) % 6]
+            s[0] = ODD_EDGES[i % 6]
+        out.append(s)
+    return out
+
+
+@pytest.mark.parametrize("name", SMALL + [UNTIED_F32] + ODD + [ODD_UNTIED_F32])
 def test_score_matches_oracle(name, fx, monkeypatch):
     f, model = fixture_model(fx, name, monkeypatch)
     lm = oracle_lm(f["root"])
     V = model.dev.V
     seqs = _ragged(300, V, seed=7)
     start = 1
+    if name.startswith("odd"):
+        assert V == 2003 and (name != ODD_UNTIED_F32 or rowsets.t_is_state(model.dev))
+        seqs = _on_edges(seqs)
+    if name == "oddw-vtable":                        # the 200 / 100 / 52 segments are there for the mixed / mx6 rows
+        assert model.dev.mixed_idx == [0, 1, 2] or os.environ.get("JLM_LSE_MIXED") == "0" or os.environ.get("JLM_PRECISION") == "f32"
     got = model.score(seqs, start)
     assert isinstance(got, list) and all(g.dtype == np.float64 for g in got)
     want, _h, _c = oracle_nll(lm, seqs, start)
@@ -162,7 +184,25 @@ def test_alone_and_in_a_batch(fx):
         np.testing.assert_allclose(model.score([seqs[i]], 1)[0], batch[i], rtol=0, atol=TOK_ATOL)
 
 
-@pytest.mark.parametrize("name", ["small-vtable", "wide-vtable", "small-untied"])
+@pytest.mark.parametrize("start", ODD_EDGES)
+def test_odd_vocabulary_rows_alone_and_in_a_batch(start, fx):
+    """V = 2 003: calls of 1, 31, 32 and 33 rows (the fold's 32 rows per workgroup) give what the same rows give inside a call of 300;
+    start words and targets on the first and last word of every segment"""
+    f = fx("odd-vtable")
+    model = load_model(f["root"])
+    assert model.dev.V == 2003
+    seqs = _on_edges(_ragged(300, 2003, seed=21, lo=1))
+    batch = model.score(seqs, start)
+    want, _h, _c = oracle_nll(oracle_lm(f["root"]), seqs[:33], start)
+    _check(batch[:33], want, ("odd-vtable", start))
+    for n in (1, 31, 32, 33):
+        got = model.score(seqs[:n], start)
+        assert len(got) == n
+        for i in range(n):
+            np.testing.assert_allclose(got[i], batch[i], rtol=0, atol=TOK_ATOL, err_msg="%d rows, row %d" % (n, i))
+
+
+@pytest.mark.parametrize("name", ["small-vtable", "wide-vtable", "small-untied", "odd-vtable", "oddw-vtable", "odd-untied"])
 def test_streams_carry_state(name, fx):
     f = fx(name)
     model = load_model(f["root"])
@@ -170,6 +210,11 @@ def test_streams_carry_state(name, fx):
     B, n = 37, 12
     x = rng.randint(0, model.dev.V, size=(B, 2 * n))
     y = rng.randint(0, model.dev.V, size=(B, 2 * n))
+    if name.startswith("odd"):                       # start words and targets on the segment edges, every pair of them
+        x[:36, 0] = np.tile(ODD_EDGES, 6)
+        y[:36, 0] = np.repeat(ODD_EDGES, 6)
+        x[:36, n] = np.repeat(ODD_EDGES, 6)
+        y[:36, 2 * n - 1] = np.tile(ODD_EDGES, 6)
     whole, hw, cw = model.score_streams(x, y)
     a, h, c = model.score_streams(x[:, :n], y[:, :n])
     b, h2, c2 = model.score_streams(x[:, n:], y[:, n:], h, c)
