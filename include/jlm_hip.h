@@ -908,6 +908,58 @@ int jlm_complete_frames_masked(const jlm_decode_model *model_host, const jlm_com
                                int n_sets, const int *prompt_set, void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
+ * The rank of the word that was actually written (LSTM_Model.rank / rank_streams, jlm_amd/rank.py): top-k accuracy, mean
+ * reciprocal rank, keystroke savings and the position among homophones all follow from it.  Additive to ABI 12.
+ *
+ * jlm_rank_rows: for every row r < min(*n_dev, n_rows_max) (n_dev NULL: n_rows_max) of f32 logits y[r * ld_y + 0 .. n_cols) (ld_y %
+ * 4 == 0, ld_y >= n_cols rounded up to 4, y 16-byte aligned) with t = target[r], and for a set S of word ids, the 0-based
+ *   rank(S) = #{ w in S : y[w] > y[t] } + #{ w in S : w < t and y[w] == y[t] }
+ * -- jlm_topk_rows' order (logit descending, lower id first on a tie), IEEE comparisons: a NaN y[w] is never counted, +-inf compare
+ * as they do.  The normaliser does not enter, so self-normalised and ordinary models rank alike.
+ * rank [n_rows][n_levels + 1] int32:
+ *   column 0       S = every word 0 .. n_cols - 1 (level A)
+ *   column 1 + i   S = { ids[j] : lv_lo[e] <= j < lv_hi[e] }, e = lv_off[t] + i, for i < min(lv_off[t + 1] - lv_off[t], n_levels): entry
+ *                  i of the target's level list, a CSR table over the words (lv_off [n_cols + 1]; spans are cut to [0, n_ids), an id
+ *                  outside [0, n_cols) is no word and nothing is read for it).  ids [n_ids] is ReadingIndex's order, (reading, id).
+ *   every column the target has no entry for holds -1.  lv_off NULL: level A only (ids / lv_lo / lv_hi are not read).
+ * A NaN y[t]: -1 in every column of the row, *flags |= 1.  A target outside [0, n_cols): -1 in every column, *flags |= 2, nothing is
+ * indexed by it.  flags: one device int, may be NULL.  Rows from min(*n_dev, n_rows_max) on are not touched.  The counts are
+ * integers: the result is the same bits run to run and whatever the launch shape.
+ * Returns 0, -1 for arguments the kernel cannot handle (jlm_topk_rows' conditions on y; n_levels outside 0 .. JLM_RANK_MAX_LEVELS;
+ * target or rank NULL; lv_off without lv_lo / lv_hi, or without ids when n_ids > 0), or a hipError_t. */
+#define JLM_RANK_MAX_LEVELS 32
+int jlm_rank_rows(const float *y, int ld_y, int n_cols, int n_rows_max, const int *n_dev, const int *target, const int *ids, int n_ids,
+                  const int *lv_off, const int *lv_lo, const int *lv_hi, int n_levels, int *rank, int *flags, void *stream);
+
+/* The ranking loop: jlm_score_plan's rows, steps, n_live and prev0 (row r is one sequence or stream, step t consumes word[t][r],
+ * the rows live at step t are the prefix r < n_live[t], state sets ping-pong, step 0 continues row prev0[r] of set 0) with the
+ * materialised logits of jlm_generate_plan and the level table of jlm_rank_rows. */
+typedef struct {
+    int n_rows, n_steps;
+    void *h[2]; float *c[2];        /* [n_rows, H] state row sets */
+    float *T;                       /* [n_rows, ldt] f32 (as jlm_score_plan.T) */
+    float *logits; int ld_logits;   /* [n_rows, ld_logits] f32, ld_logits >= V rounded up to 4 */
+    const int *rows;                /* [n_rows] device: 0, 1, ..., n_rows - 1 */
+    const int *prev0;               /* [n_rows] device: the row of set 0 that step 0 continues, -1 = zero state */
+    const int *word, *target;       /* [n_steps][n_rows] device */
+    const int *n_live;              /* [n_steps] device */
+    const int *n_live_host;         /* [n_steps] host copy (bounds the launches' grids), or NULL: n_rows */
+    const int *ids; int n_ids;      /* the level table of jlm_rank_rows (lv_off NULL: level A only) */
+    const int *lv_off, *lv_lo, *lv_hi;
+    int n_levels;
+    int *rank;                      /* [n_steps][n_rows][n_levels + 1] device: the live rows of every step are written */
+    int *flags;                     /* one device int or NULL: jlm_rank_rows' bits */
+} jlm_rank_plan;
+
+/* Enqueues n_steps x [LSTM step and T projection of the live rows (the launches jlm_score_frames makes), jlm_gemm_nt per segment into
+ * plan.logits (+ b2) as jlm_generate_frames makes them on a drawing frame, rank_rows_kernel on target[t]].  No host synchronisation.
+ * events (may be NULL): JLM_RANK_EVENTS_PER_STEP * n_steps hipEvent_t (timing enabled), recorded on `stream`
+ *   [0] before the LSTM step  [1] after it  [2] after the T projection  [3] after the logit GEMMs  [4] after the ranking.
+ * Returns 0, -2 for a model outside the loop's shapes, -1 / a hipError_t as the launchers do. */
+#define JLM_RANK_EVENTS_PER_STEP 5
+int jlm_rank_frames(const jlm_decode_model *model_host, const jlm_rank_plan *plan_host, void *stream, void *const *events);
+
+/* ------------------------------------------------------------------------
  * Left context of a decode (LSTM_Model.prime, Decoder.decode(context=), jlm_amd/context.py).  Sentence s with the committed words
  * ctx_s has the history hist = [<eos>] + ctx_s; its decode is the reference's with the root hypothesis consuming hist[-1] from the
  * state reached by consuming hist[:-1] from the zero state.

@@ -82,6 +82,15 @@ class GeneratePlan(Structure):
                 ("flags", c_void_p)]
 
 
+class RankPlan(Structure):
+    """jlm_rank_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("T", c_void_p),
+                ("logits", c_void_p), ("ld_logits", c_int), ("rows", c_void_p), ("prev0", c_void_p), ("word", c_void_p),
+                ("target", c_void_p), ("n_live", c_void_p), ("n_live_host", POINTER(c_int)), ("ids", c_void_p), ("n_ids", c_int),
+                ("lv_off", c_void_p), ("lv_lo", c_void_p), ("lv_hi", c_void_p), ("n_levels", c_int), ("rank", c_void_p),
+                ("flags", c_void_p)]
+
+
 class PrimePlan(Structure):
     """jlm_prime_plan (include/jlm_hip.h)."""
     _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("rows", c_void_p), ("prev", c_void_p),
@@ -158,6 +167,8 @@ _SIGS = {
     "jlm_complete_frames": ([POINTER(DecodeModel), POINTER(CompletePlan), P, P], c_int),
     "jlm_topk_rows_masked": ([P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, c_int, P, P], c_int),
     "jlm_complete_frames_masked": ([POINTER(DecodeModel), POINTER(CompletePlan), P, c_int, c_int, P, P, P], c_int),
+    "jlm_rank_rows": ([P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P, P, P], c_int),
+    "jlm_rank_frames": ([POINTER(DecodeModel), POINTER(RankPlan), P, P], c_int),
     "jlm_prime_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P], c_int),
     "jlm_seed_context": ([P, P, c_int, P, P, c_int, P, c_int, c_int, c_longlong, P, P, P, P, P], c_int),
     "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,

@@ -536,6 +536,40 @@ extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan 
     return 0;
 }
 
+// Teacher-forced ranking (include/jlm_hip.h jlm_rank_frames): jlm_score_frames' loop over the live rows with the materialised logits
+// of a drawing frame of jlm_generate_frames in the normaliser's place, and rank_rows_kernel (csrc/jlm_rank.hip) on the step's targets.
+extern "C" int jlm_rank_frames(const jlm_decode_model *m, const jlm_rank_plan *p, void *stream, void *const *events) {
+    const int R = p->n_rows, S = p->n_steps;
+    if (R < 0 || S < 0 || !p->rows || !p->prev0 || !p->word || !p->target || !p->n_live || !p->logits || !p->rank) return -1;
+    if (p->n_levels < 0 || p->n_levels > JLM_RANK_MAX_LEVELS) return -1;
+    if (R == 0 || S == 0) return 0;
+    JLM_TRY(rows_refuse(m, p->T));
+    const int V = m->segs[m->n_segs - 1].v_end;
+    if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
+    const Stamps stamp{events, JLM_RANK_EVENTS_PER_STEP, stream};
+    const size_t ld_rank = (size_t)p->n_levels + 1;
+    for (int t = 0; t < S; ++t) {
+        const int bound = p->n_live_host ? p->n_live_host[t] : R;
+        if (bound < 0 || bound > R) return -1;
+        const int *ndev = p->n_live + t;
+        const int *word = p->word + (size_t)t * R, *target = p->target + (size_t)t * R;
+        const PingPong s(m, p->h, p->c, p->T, t);
+        const int *prev = t == 0 ? p->prev0 : p->rows;
+        JLM_TRY(stamp(t, 0));
+        if (bound > 0) JLM_TRY(rows_lstm_step(m, s.h_in, s.c_in, s.h_out, s.c_out, p->rows, prev, word, p->T, bound, ndev, stream));
+        JLM_TRY(stamp(t, 1));
+        if (bound > 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, bound, ndev, stream));
+        JLM_TRY(stamp(t, 2));
+        if (bound > 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, bound, stream));
+        JLM_TRY(stamp(t, 3));
+        if (bound > 0)
+            JLM_TRY(jlm_rank_rows(p->logits, p->ld_logits, V, bound, ndev, target, p->ids, p->n_ids, p->lv_off, p->lv_lo, p->lv_hi, p->n_levels,
+                                  p->rank + (size_t)t * R * ld_rank, p->flags, stream));
+        JLM_TRY(stamp(t, 4));
+    }
+    return 0;
+}
+
 // Ancestral sampling (include/jlm_hip.h jlm_generate_frames): the prompt frames step the LSTM of their live prefix only; every drawing
 // frame steps all rows, projects T, materialises the full-vocabulary logits (one jlm_gemm_nt per segment, columns v_start .. v_end of
 // plan.logits, + b2) and draws with sample_rows_kernel, which also writes the word the next frame consumes.  With top_k / top_p on

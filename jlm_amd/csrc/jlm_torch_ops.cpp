@@ -28,6 +28,10 @@
 //   torch.ops.jlm.topk_rows_masked / complete_frames_masked(..., mask, ld_mask, n_sets, row_set / prompt_set)
 //                             the same two with rows / first words restricted to word sets (jlm_topk_rows_masked,
 //                             jlm_complete_frames_masked; LSTM_Model.predict_reading / complete_reading)
+//   torch.ops.jlm.rank_rows(y, ..., target, ids, lv_off, lv_lo, lv_hi, n_levels, rank, flags)
+//                             the rank of a given word in every row of materialised logits, at every level of its list (jlm_rank_rows)
+//   torch.ops.jlm.rank_frames(Model, state row sets, logits, ..., word, target, n_live, level table, rank, ...)
+//                             teacher-forced ranking of many sequences: ONE op (jlm_rank_frames; LSTM_Model.rank / rank_streams)
 //   torch.ops.jlm.prime_frames(Model, state row sets, rows, prev, word, n_live, ...)
 //                             the state after a left context: LSTM steps only, ONE op (jlm_prime_frames; LSTM_Model.prime)
 //   torch.ops.jlm.seed_context(Plan, src_h, src_c, last, has, idx)
@@ -652,6 +656,87 @@ Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0,
                          [&](hipStream_t st, void *const *ev) { return jlm_score_frames(&m, &p, st, ev); });
 }
 
+// The level table of jlm_rank_rows as tensors, checked: ids [n_ids], lv_off [n_cols + 1], lv_lo / lv_hi of one length, all int32 on the
+// device; without lv_off the other three are not passed on.
+struct RankLevels {
+    const int *ids = nullptr, *off = nullptr, *lo = nullptr, *hi = nullptr;
+    int n_ids = 0;
+    RankLevels(const char *op, const OptTensor &ids_t, const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_cols,
+               int64_t n_levels) {
+        auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+        auto is_int = [&](const OptTensor &t, int64_t n) { return has(t) && t->scalar_type() == at::kInt && t->numel() >= n; };
+        TORCH_CHECK(n_levels >= 0 && n_levels <= JLM_RANK_MAX_LEVELS, "jlm.", op, ": n_levels in 0 .. ", JLM_RANK_MAX_LEVELS);
+        if (!has(lv_off)) return;
+        TORCH_CHECK(is_int(lv_off, n_cols + 1) && is_int(lv_lo, 0) && is_int(lv_hi, 0) && lv_lo->numel() == lv_hi->numel() && is_int(ids_t, 0) &&
+                        ids_t->numel() <= INT32_MAX,
+                    "jlm.", op, ": int32 ids [n_ids], lv_off [n_cols + 1], lv_lo / lv_hi of one length");
+        off = ptr<const int>(*lv_off, "lv_off");
+        n_ids = (int)ids_t->numel();
+        // (an empty table still hands the entry point pointers: it reads none of them through an empty span)
+        ids = n_ids ? ptr<const int>(*ids_t, "ids") : nullptr;
+        lo = lv_lo->numel() ? ptr<const int>(*lv_lo, "lv_lo") : off;
+        hi = lv_hi->numel() ? ptr<const int>(*lv_hi, "lv_hi") : off;
+    }
+};
+
+// the rank of target[r] in row r of f32 logits y [n_rows, ld] at every level of its level list (jlm_rank_rows, include/jlm_hip.h):
+// rank int32 [n_rows, n_levels + 1].
+void rank_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, const Tensor &target,
+               const OptTensor &ids, const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels,
+               const Tensor &rank, const OptTensor &flags) {
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    auto opt_ok = [&](const OptTensor &t, at::ScalarType ty, int64_t n) { return !t.has_value() || !t->defined() || is(*t, ty, n); };
+    TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && ld >= 0 && is(y, at::kFloat, n_rows * ld), "jlm.rank_rows: y [n_rows, ld] float32");
+    const RankLevels lv("rank_rows", ids, lv_off, lv_lo, lv_hi, n_cols, n_levels);
+    TORCH_CHECK(is(target, at::kInt, n_rows) && is(rank, at::kInt, n_rows * (n_levels + 1)) && opt_ok(n_dev, at::kInt, 1) &&
+                    opt_ok(flags, at::kInt, 1),
+                "jlm.rank_rows: int32 target [n_rows], rank [n_rows, n_levels + 1], n_dev / flags [1]");
+    const c10::hip::HIPGuard device_guard(y.device().index());
+    jlm_check(jlm_rank_rows(ptr<const float>(y, "y"), (int)ld, (int)n_cols, (int)n_rows, optr<const int>(n_dev, "n_dev"),
+                            ptr<const int>(target, "target"), lv.ids, lv.n_ids, lv.off, lv.lo, lv.hi, (int)n_levels, ptr<int>(rank, "rank"),
+                            optr<int>(flags, "flags"), stream_of(y)),
+              "jlm_rank_rows");
+}
+
+// teacher-forced ranking of n_rows sequences / streams over n_steps steps (jlm_rank_frames, include/jlm_hip.h): score_frames' state row
+// sets, rows / prev0 / word / target / n_live, generate_frames' logits [n_rows, ld_logits], rank_rows' level table; rank int32
+// [n_steps][n_rows][n_levels + 1].  Every id must lie in [0, V): the caller checks (jlm_amd/rank.py).  -> timed: [n_steps, 4]
+// milliseconds per step (LSTM step, T projection, logit GEMMs, ranking) after waiting for the last step; else an empty tensor.
+Tensor rank_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                   const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0, const Tensor &word,
+                   const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host, const OptTensor &ids, const OptTensor &lv_off,
+                   const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels, const Tensor &rank, const OptTensor &flags, int64_t n_rows,
+                   int64_t n_steps, bool timed) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    check_row_sets("rank_frames", m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
+    TORCH_CHECK(m.n_segs >= 1, "jlm.rank_frames: a model without segments");
+    const int64_t V = m.segs[m.n_segs - 1].v_end;
+    const RankLevels lv("rank_frames", ids, lv_off, lv_lo, lv_hi, V, n_levels);
+    TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
+                    is(n_live, at::kInt, S),
+                "jlm.rank_frames: int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
+    TORCH_CHECK(is(rank, at::kInt, S * R * (n_levels + 1)) && (!has(flags) || is(*flags, at::kInt, 1)),
+                "jlm.rank_frames: int32 rank [n_steps][n_rows][n_levels + 1], int32 flags");
+    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.rank_frames: T [n_rows, ldt] float32");
+    TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.rank_frames: logits [n_rows, ld_logits] float32");
+    jlm_rank_plan p{};
+    p.n_rows = (int)R; p.n_steps = (int)S;
+    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+    p.T = optr<float>(T, "T");
+    p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits;
+    p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
+    p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
+    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
+    p.n_live_host = live_host.data();
+    p.ids = lv.ids; p.n_ids = lv.n_ids; p.lv_off = lv.off; p.lv_lo = lv.lo; p.lv_hi = lv.hi; p.n_levels = (int)n_levels;
+    p.rank = ptr<int>(rank, "rank"); p.flags = optr<int>(flags, "flags");
+    return launch_frames("jlm_rank_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_rank_frames(&m, &p, st, ev); });
+}
+
 // one draw per row of f32 logits y [n_rows, ld] (jlm_sample_rows, include/jlm_hip.h).  seed: the uint64 seed's bits as int64.
 void sample_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, double temperature, int64_t seed,
                  int64_t step, const OptTensor &row_id, const OptTensor &forced, const OptTensor &done, int64_t stop_id, bool self_norm,
@@ -1094,6 +1179,14 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
           "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed) -> Tensor",
           score_frames);
+    m.def("rank_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, Tensor target, Tensor? ids, Tensor? lv_off, Tensor? lv_lo, "
+          "Tensor? lv_hi, int n_levels, Tensor(a!) rank, Tensor(b!)? flags) -> ()",
+          rank_rows);
+    m.def("rank_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, int[] n_live_host, "
+          "Tensor? ids, Tensor? lv_off, Tensor? lv_lo, Tensor? lv_hi, int n_levels, Tensor(g!) rank, Tensor(h!)? flags, int n_rows, "
+          "int n_steps, bool timed) -> Tensor",
+          rank_frames);
     m.def("sample_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, float temperature, int seed, int step, Tensor? row_id, "
           "Tensor? forced, Tensor(a!)? done, int stop_id, bool self_norm, Tensor(b!) word, Tensor(c!) ids, Tensor(d!) nll, Tensor(e!)? flags) -> ()",
           sample_rows);

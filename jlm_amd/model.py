@@ -951,6 +951,39 @@ class LSTM_Model():
         _seq, tok, h2, c2 = self._scorer().run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
         return np.ascontiguousarray(tok.T), h2, c2
 
+    def _ranker(self):
+        from .rank import Ranker
+        return self._driver(Ranker)
+
+    def _rank_levels(self, readings, max_prefix):
+        """the level table of a ranking call: None for ``readings=False``; ValueError for a bad max_prefix or a character model"""
+        if not readings:
+            return None
+        from .rank import check_max_prefix
+        max_prefix = check_max_prefix(max_prefix)
+        return self._ranker().levels(self.reading_index(), max_prefix)
+
+    def rank(self, sequences, start, readings=True, max_prefix=8, max_rows=None):
+        """Where each word of each sequence ranks in the distribution it is predicted from, on the device (jlm_amd/rank.py).
+        Sequences are consumed as score() consumes them: step 0 consumes ``start`` from the zero state and ranks s[0], step t consumes
+        s[t-1] and ranks s[t].  -> per sequence an int32 [len, max_prefix + 3] array of 0-based ranks (logit descending, lower id first
+        on a tie -- predict_top's order): column 0 among all words; column 1 + j, j = 0 .. max_prefix, among the words whose reading
+        starts with the first j kana of the word's reading (what predict_reading ranks after j typed kana); the last column among the
+        words with the same reading (its homophones).  -1 where the word has no such level: every reading column of a word without
+        a reading, prefix levels beyond its reading's length.  ``readings=False``: column 0 alone ([len, 1]; the only form a
+        character model has -- with readings it raises reading_index()'s ValueError).  0 <= max_prefix <= 30.  ValueError for an
+        id outside [0, V) before anything runs; JlmHipError when the logit of a ranked word is NaN."""
+        from .rank import rank_sequences
+        return rank_sequences(self._ranker(), sequences, start, self._rank_levels(readings, max_prefix), max_rows)
+
+    def rank_streams(self, inputs, targets, h=None, c=None, readings=True, max_prefix=8):
+        """The stream form of rank(), as score_streams is of score(): ``inputs`` / ``targets`` [B, n] word ids, row b consuming
+        inputs[b, t] and ranking targets[b, t] at step t, the LSTM state carried from (h, c) -- device tensors [B, H] returned by an
+        earlier call (of this method or of score_streams), None = zero state.  -> (ranks int32 [B, n, max_prefix + 3] in rank()'s
+        columns, h, c)."""
+        from .rank import rank_streams
+        return rank_streams(self._ranker(), inputs, targets, h, c, self._rank_levels(readings, max_prefix))
+
     def generate(self, prompts=None, n_words=100, temperature=1.0, seed=0, stop_id=None, max_rows=None, top_k=None, top_p=None):
         """Ancestral sampling on the device (jlm_amd/generate.py): the reference's sampling loop (model.py:213-245, one predict() and
         one sample() per word) for many rows at once.  ``prompts``: R word-id lists of length >= 1 (None: one row starting at <eos>, the

@@ -12,6 +12,11 @@ score_streams (jlm_amd/score.py):
 
 Encoding follows Corpus.encode_corpus (train/data.py:54-70): words through Vocab.w2i with <unk> for anything outside it and <eos>
 after every line; a character model (config char_rnn) reads the characters of the surfaces through CharVocab.c2i instead.
+
+  --ranks          after the perplexity line, one line on how good the model's candidate lists are over the same tokens, from
+                   LSTM_Model.rank / rank_streams (jlm_amd/rank.py): top-k accuracy (--top), mean reciprocal rank, keystroke
+                   savings of a candidate list of --list words, and the position of the word among its homophones.  A character
+                   model reports the first two only.  Without --ranks nothing of this runs.
 """
 import argparse
 import os
@@ -69,6 +74,44 @@ def stream_perplexity(model, stream, batch_size, num_steps):
     return float(np.exp(total / n_tok)), total, n_tok
 
 
+def sentence_ranks(model, sents, eos, readings, max_prefix):
+    """-> (ranks [tokens, columns], the targets [tokens]) of every line on its own, as sentence_perplexity scores them"""
+    ranks = model.rank(sents, eos, readings=readings, max_prefix=max_prefix)
+    width = ranks[0].shape[1] if ranks else 1
+    return (np.concatenate(ranks) if ranks else np.zeros((0, width), dtype=np.int32)), np.array([t for s in sents for t in s], dtype=np.int64)
+
+
+def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix):
+    """-> (ranks [tokens, columns], the targets [tokens]) over the corpus_iterator chunks, state carried, as stream_perplexity"""
+    from .score import stream_layout
+    x, y = stream_layout(stream, batch_size, num_steps)
+    h = c = None
+    out = []
+    for i in range(x.shape[1] // num_steps):
+        cols = slice(i * num_steps, (i + 1) * num_steps)
+        r, h, c = model.rank_streams(x[:, cols], y[:, cols], h, c, readings=readings, max_prefix=max_prefix)
+        out.append(r)
+    ranks = np.concatenate(out, axis=1)
+    return ranks.reshape(-1, ranks.shape[-1]), y.reshape(-1).astype(np.int64)
+
+
+def ranks_line(ranks, targets, index, tops, list_size):
+    """the --ranks line: top-k accuracy and MRR over every token; with a reading index also keystroke savings and the homophone
+    position over the tokens that have a reading"""
+    from . import rank as _rank
+    acc = _rank.topk_accuracy(ranks, tops)
+    parts = ["top-{}: {:.4f}".format(k, acc[k]) for k in tops] + ["MRR: {:.4f}".format(_rank.mrr(ranks))]
+    if index is not None:
+        ks = _rank.keystrokes(ranks, _rank.reading_lengths(index)[targets], list_size)
+        hp = _rank.homophone_position(ranks)
+        parts += ["keystroke savings (list {}): {:.4f}".format(list_size, ks["savings"]),
+                  "homophone position: {:.3f} (first: {:.4f})".format(hp["mean"], hp["first"]),
+                  "tokens: {} ranked, {} with a reading, {} without".format(len(ranks), ks["tokens"], ks["excluded"])]
+    else:
+        parts.append("tokens: {} ranked".format(len(ranks)))
+    return "  ".join(parts)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Test perplexity of a dumped model on the device (reference train/train.py:101-102)")
     _config.add_model_args(ap)
@@ -77,7 +120,14 @@ def main(argv=None):
     ap.add_argument("-b", "--batch_size", type=int, default=None, help="stream mode: parallel streams (default: the config's, else 64)")
     ap.add_argument("--num_steps", type=int, default=20, help="stream mode: steps per chunk")
     ap.add_argument("-es", type=int, default=0, help="score the first N lines only (0 = all)")
+    ap.add_argument("--ranks", action="store_true", help="also report top-k accuracy, MRR, keystroke savings and homophone position")
+    ap.add_argument("--top", default="1,5,10", help="--ranks: the k of top-k accuracy, comma-separated")
+    ap.add_argument("--list", type=int, default=5, dest="list_size", help="--ranks: words in the candidate list of the keystroke figure")
+    ap.add_argument("--max_prefix", type=int, default=8, help="--ranks: typed kana up to which a word is looked for in the list")
     args = ap.parse_args(argv)
+    tops = [int(k) for k in args.top.split(",") if k.strip()]
+    if args.ranks and (not tops or min(tops) < 1 or args.list_size < 1):
+        ap.error("--top and --list take integers >= 1")
     config, vocab = load_vocab(args)
     from .model import LSTM_Model
     path = args.file or os.path.join(_config.data_path, "test.txt")
@@ -93,6 +143,13 @@ def main(argv=None):
     dt = time.time() - t0
     print("tokens: {}  <unk>: {}  tokens/s: {:.0f}".format(n_tok, n_unk, n_tok / dt if dt > 0 else float("inf")))
     print("Test perplexity: {}".format(pp))
+    if args.ranks:
+        readings = not isinstance(vocab, CharVocab)
+        if args.mode == "sentence":
+            ranks, targets = sentence_ranks(model, sents, vocab.t2i["<eos>"], readings, args.max_prefix)
+        else:
+            ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix)
+        print(ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
     return pp
 
 

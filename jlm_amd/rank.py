@@ -1,0 +1,247 @@
+"""Where the word that was actually written ranks, on the device: ``LSTM_Model.rank`` / ``rank_streams`` and the figures of a
+predictive keyboard that follow from the ranks.
+
+The reference has ``find_top_N`` over one host-side distribution (decoder/model.py:25-26) and nothing that measures how good a
+candidate list is on a corpus.  Here a call is ONE op (``torch.ops.jlm.rank_frames``, csrc/jlm_decode.hip ``jlm_rank_frames``): per
+step the LSTM step and the T projection of the live rows as ``score`` launches them, the full-vocabulary logits as ``generate``
+materialises them (``jlm_gemm_nt`` per segment), and ``rank_rows_kernel`` (csrc/jlm_rank.hip), which counts the words that rank above
+the step's target.  Nothing comes back to the host between steps.
+
+Definitions (include/jlm_hip.h jlm_rank_rows; pinned by tests/test_rank_cpu.py and tests/test_gpu_rank_rows.py).  For a row of logits
+y, its target t and a set S of word ids, the 0-based
+
+    rank(S) = #{ w in S : y[w] > y[t] } + #{ w in S : w < t and y[w] == y[t] }
+
+-- ``predict_top``'s order: logit descending, lower id first on a tie.  The log-normaliser does not enter.  The levels of a target
+whose katakana reading r has n kana (``ReadingIndex.level_table``):
+
+    A    every word;
+    j    for j = 0 .. min(n, max_prefix): the words whose reading starts with r[:j] -- what ``predict_reading`` ranks after j typed kana
+         (j = 0: every word that has a reading);
+    X    the words whose reading equals r: its homophones, the position in a conversion candidate window.
+
+A word without a reading (``<eos>``, ``<unk>``) has level A only; a level a target does not have holds -1.  The result columns are
+A, the prefix levels 0 .. max_prefix, then X: ``max_prefix + 3`` of them (``readings=False``: column A alone).
+
+The metrics at the end of this module are plain numpy over such arrays.
+"""
+import numpy as np
+
+from . import ops as _ops
+from . import rowsets
+from .generate import GENERATE_BUDGET_BYTES, MAX_ROWS
+from .rowsets import RowSets, check_ids
+from .score import plan_rows, sentence_arrays
+
+MAX_PREFIX_LIMIT = 30               # prefix levels 0 .. 30 and level X: the 32 level columns of jlm_rank_rows
+
+
+def check_max_prefix(max_prefix):
+    if not rowsets.is_int(max_prefix) or not 0 <= max_prefix <= MAX_PREFIX_LIMIT:
+        raise ValueError("max_prefix must be an integer in [0, %d] (got %r)" % (MAX_PREFIX_LIMIT, max_prefix))
+    return int(max_prefix)
+
+
+class Levels:
+    """The level table of one (ReadingIndex, max_prefix) on the device: ids, the CSR (off, lo, hi), and its host copy of off."""
+
+    def __init__(self, m, index, max_prefix):
+        torch = m.torch
+        self.index, self.max_prefix = index, max_prefix
+        self.n_levels = max_prefix + 2
+        if index.V != m.V:
+            raise ValueError("the reading index covers %d words, the model %d" % (index.V, m.V))
+        off, lo, hi = index.level_table(max_prefix)
+        self.off_host = off
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(m.device)
+        self.ids, self.off, self.lo, self.hi = up(index.ids), up(off), up(lo), up(hi)
+
+    def args(self):
+        return self.ids, self.off, self.lo, self.hi, self.n_levels
+
+    def to_columns(self, dev_rank, target):
+        """device ranks [N, n_levels + 1] of the targets [N] -> the public columns: level X moved from behind the target's prefix
+        levels to the last column"""
+        out = dev_rank.copy()
+        t = np.asarray(target, dtype=np.int64)
+        cnt = (self.off_host[t + 1] - self.off_host[t]).astype(np.int64)          # 0, or the prefix levels + 1
+        has = np.flatnonzero((cnt > 0) & (cnt < self.n_levels))
+        out[has, self.n_levels] = dev_rank[has, cnt[has]]
+        out[has, cnt[has]] = -1
+        return out
+
+
+class Ranker:
+    """The device side of a ranking call over a :class:`jlm_amd.model.DeviceModel`."""
+
+    def __init__(self, dev_model):
+        self.m = dev_model
+        self.torch = dev_model.torch
+        self.last_step_ms = None          # [n_steps, 4] of the last timed call: LSTM step, T projection, logit GEMMs, ranking
+        self._levels = {}
+
+    def levels(self, index, max_prefix):
+        """the uploaded level table of (index, max_prefix), made on first use"""
+        key = (id(index), int(max_prefix))
+        if key not in self._levels:
+            with self.m._ctx():
+                self._levels[key] = Levels(self.m, index, int(max_prefix))
+        return self._levels[key]
+
+    def row_bytes(self, n_steps, n_levels):
+        m = self.m
+        return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + n_steps * (8 + 4 * (n_levels + 1)) + 32
+
+    def run(self, word, target, n_live, h=None, c=None, levels=None, timed=False):
+        """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
+        the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
+        levels: a :class:`Levels`, None = level A only.  -> (rank [n_steps, R, n_levels + 1] int32 in the device's column order, -1
+        where a row is not live, h, c) -- the state after the last step stays on the device."""
+        torch, m = self.torch, self.m
+        word = np.ascontiguousarray(word, dtype=np.int32)
+        target = np.ascontiguousarray(target, dtype=np.int32)
+        S, R = target.shape
+        check_ids(word, m.V, "rank")
+        check_ids(target, m.V, "rank")
+        n_live = [int(x) for x in n_live]
+        dev, i32 = m.device, torch.int32
+        L = levels.n_levels if levels is not None else 0
+        with m._ctx():
+            rs = RowSets(m, R, logits=True)
+            if h is None:
+                prev0 = torch.full((R,), -1, device=dev, dtype=i32)
+            else:
+                if tuple(h.shape) != (R, m.H) or tuple(c.shape) != (R, m.H):
+                    raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (R, m.H, tuple(h.shape), tuple(c.shape)))
+                rs.h[0].copy_(h)
+                rs.c[0].copy_(c)
+                prev0 = rs.rows
+            wd = torch.from_numpy(word).to(dev)
+            tg = torch.from_numpy(target).to(dev)
+            nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
+            rank = torch.full((S, R, L + 1), -1, device=dev, dtype=i32)
+            table = levels.args() if levels is not None else (None, None, None, None, 0)
+            ms = _ops.backend().rank_frames(m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, prev0, wd, tg, nl, n_live,
+                                            *table, rank, rs.flags, R, S, bool(timed))
+            if timed:
+                self.last_step_ms = ms.numpy()
+            rs.check_flags("rank_rows_kernel flagged a target outside the vocabulary (flags %d)",
+                           "the logit of a target word is NaN: its rank is undefined")
+            out = rank.cpu().numpy()
+        return out, rs.h[S % 2], rs.c[S % 2]
+
+
+def _columns(levels, dev_rank, target):
+    return dev_rank if levels is None else levels.to_columns(dev_rank, target)
+
+
+def rank_sequences(ranker, sequences, start, levels=None, max_rows=None):
+    """LSTM_Model.rank: see there."""
+    V = ranker.m.V
+    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
+    for s in seqs:
+        check_ids(s, V, "rank")
+    check_ids([start], V, "rank (start)")
+    L = levels.n_levels if levels is not None else 0
+    lens = [len(s) for s in seqs]
+    longest = max(lens) if lens else 0
+    if max_rows is None:
+        max_rows = rowsets.clamp_rows(MAX_ROWS, GENERATE_BUDGET_BYTES, ranker.row_bytes(longest, L), ranker.m.H)
+    out = [np.full((n, L + 1), -1, dtype=np.int32) for n in lens]
+    for ch in plan_rows(lens, max_rows):
+        idx = ch["idx"]
+        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
+        rk, _h, _c = ranker.run(word, target, ch["n_live"], levels=levels)
+        for r, i in enumerate(idx):
+            n = int(ch["lens"][r])
+            out[i] = _columns(levels, rk[:n, r, :], target[:n, r])
+    return out
+
+
+def rank_streams(ranker, inputs, targets, h=None, c=None, levels=None):
+    """LSTM_Model.rank_streams: see there."""
+    x = np.asarray(inputs)
+    y = np.asarray(targets)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
+    if (h is None) != (c is None):
+        raise ValueError("carry both h and c, or neither")
+    B, n = x.shape
+    L = levels.n_levels if levels is not None else 0
+    check_ids(x, ranker.m.V, "rank")
+    check_ids(y, ranker.m.V, "rank")
+    if B == 0 or n == 0:
+        return np.full((B, n, L + 1), -1, dtype=np.int32), h, c
+    rk, h2, c2 = ranker.run(x.T, y.T, [B] * n, h=h, c=c, levels=levels)
+    flat = _columns(levels, rk.reshape(n * B, L + 1), np.ascontiguousarray(y.T).reshape(-1))
+    return np.ascontiguousarray(flat.reshape(n, B, L + 1).transpose(1, 0, 2)), h2, c2
+
+
+# ---------------------------------------------------------------------------------------------------------------- metrics (numpy)
+def _stack(ranks):
+    """one [N, columns] array of a rank array, or of a list of them (LSTM_Model.rank's result; [B, n, columns] of rank_streams)"""
+    if isinstance(ranks, np.ndarray):
+        a = ranks
+    else:
+        parts = [np.asarray(r) for r in ranks]
+        a = np.concatenate([p.reshape(-1, p.shape[-1]) for p in parts]) if parts else np.zeros((0, 1), dtype=np.int32)
+    return a.reshape(-1, a.shape[-1]).astype(np.int64)
+
+
+def reading_lengths(index):
+    """[V] int64: the number of kana of every word's reading in a :class:`jlm_amd.readings.ReadingIndex`, 0 for a word without one"""
+    out = np.zeros(index.V, dtype=np.int64)
+    out[index.ids] = [len(r) for r in index.readings]
+    return out
+
+
+def topk_accuracy(ranks, ks):
+    """-> {k: the share of tokens whose target is among the k most probable words} (column A < k)"""
+    a = _stack(ranks)[:, 0]
+    return {int(k): (float(np.mean((a >= 0) & (a < k))) if len(a) else float("nan")) for k in ks}
+
+
+def mrr(ranks):
+    """the mean reciprocal rank 1 / (rank + 1) of column A"""
+    a = _stack(ranks)[:, 0]
+    a = a[a >= 0]
+    return float(np.mean(1.0 / (a + 1.0))) if len(a) else float("nan")
+
+
+def keystrokes(ranks, reading_lengths, list_size):
+    """Keystroke savings of a candidate list of ``list_size`` words.  ``ranks``: arrays with the prefix columns (``readings=True``);
+    ``reading_lengths``: the number of kana of each token's reading, in the same order (0: no reading).  A token of l >= 1 kana costs
+    typed = min{ j <= min(l, max_prefix) : rank_j < list_size } kana -- the first moment its word is in the list -- and l when there
+    is no such j; savings = 1 - sum typed / sum l.  Tokens without a reading are excluded and counted.  The keystroke that SELECTS
+    the word from the list is not counted, on either side: with it, a word offered only once it is typed in full saves nothing and
+    costs one key more.  -> dict(savings, typed, kana, tokens, excluded)"""
+    a = _stack(ranks)
+    if a.shape[1] < 3:
+        raise ValueError("keystrokes needs the prefix levels (rank(..., readings=True))")
+    ell = np.asarray(reading_lengths, dtype=np.int64).reshape(-1)
+    if len(ell) != len(a):
+        raise ValueError("one reading length per token (%d tokens, %d lengths)" % (len(a), len(ell)))
+    if list_size < 1:
+        raise ValueError("list_size must be >= 1")
+    max_prefix = a.shape[1] - 3
+    pre = a[:, 1:max_prefix + 2]                                   # prefix levels 0 .. max_prefix
+    j = np.arange(max_prefix + 1)[None, :]
+    hit = (pre >= 0) & (pre < list_size) & (j <= ell[:, None])
+    first = np.where(hit.any(axis=1), hit.argmax(axis=1), ell)
+    keep = ell >= 1
+    typed, kana = int(first[keep].sum()), int(ell[keep].sum())
+    return dict(savings=(1.0 - typed / kana) if kana else float("nan"), typed=typed, kana=kana, tokens=int(keep.sum()),
+                excluded=int((~keep).sum()))
+
+
+def homophone_position(ranks):
+    """the position of the target among its homophones (column X, the last): -> dict(mean, first = the share at position 0, tokens)
+    over the tokens that have a reading"""
+    a = _stack(ranks)
+    if a.shape[1] < 3:
+        raise ValueError("homophone_position needs level X (rank(..., readings=True))")
+    x = a[:, -1]
+    x = x[x >= 0]
+    if not len(x):
+        return dict(mean=float("nan"), first=float("nan"), tokens=0)
+    return dict(mean=float(x.mean()), first=float(np.mean(x == 0)), tokens=int(len(x)))

@@ -84,6 +84,36 @@ class ReadingIndex:
                 out.append((s, mid, hi))
         return out
 
+    def level_table(self, max_prefix):
+        """The spans of ``ids`` a word is ranked within (``LSTM_Model.rank``, include/jlm_hip.h jlm_rank_rows), for every word at once:
+        -> CSR (off [V + 1], lo, hi) int32.  Word w with the reading r of n kana has the entries off[w] .. off[w + 1]: the prefix levels
+        j = 0 .. min(n, max_prefix), ``ids[lo:hi]`` = the words whose reading starts with r[:j] (j = 0: every word that has a
+        reading), then level X, the words whose reading equals r.  A word without a reading has no entries.  The spans of a word are
+        nested (lo non-decreasing, hi non-increasing), found by bisection inside the span before.  0 <= max_prefix <= 30."""
+        if isinstance(max_prefix, bool) or not isinstance(max_prefix, (int, np.integer)) or not 0 <= max_prefix <= 30:
+            raise ValueError("max_prefix must be an integer in [0, 30] (got %r)" % (max_prefix,))
+        rd = self.readings
+        count = np.zeros(self.V, dtype=np.int64)
+        spans, per_reading = {}, None
+        for pos, (r, w) in enumerate(zip(rd, self.ids)):
+            if pos == 0 or r != rd[pos - 1]:
+                lo, hi = 0, len(rd)
+                per_reading = [(lo, hi)]
+                for j in range(1, min(len(r), int(max_prefix)) + 1):
+                    p = r[:j]
+                    lo = bisect.bisect_left(rd, p, lo, hi)
+                    hi = bisect.bisect_left(rd, p + "\U0010ffff", lo, hi)
+                    per_reading.append((lo, hi))
+                lo = bisect.bisect_left(rd, r, lo, hi)
+                per_reading.append((lo, bisect.bisect_right(rd, r, lo, hi)))
+            spans[int(w)] = per_reading
+            count[int(w)] = len(per_reading)
+        off = np.zeros(self.V + 1, dtype=np.int64)
+        np.cumsum(count, out=off[1:])
+        flat = [s for w in sorted(spans) for s in spans[w]]
+        both = np.asarray(flat, dtype=np.int64).reshape(-1, 2)
+        return off.astype(np.int32), both[:, 0].astype(np.int32), both[:, 1].astype(np.int32)
+
     @staticmethod
     def mask(id_lists, V):
         """Bit masks of word-id lists: -> (uint32 [n_sets, ceil(V / 32)], the set index of each list).  Bit w & 31 of word w >> 5 of
