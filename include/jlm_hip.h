@@ -223,8 +223,12 @@ int jlm_pack_split_f16_col(const float *v, int rows, float scale, void *dst, int
  * bias_col (may be NULL): bias_col[i] = segs[i].k says that column k of the
  * segment's split rows (the first padded one; needs k % 16 != 0) holds
  * b2[word] * 2^eB_i -- the kernel then feeds 1.0 at that position of every T
- * row and the bias costs nothing in the fold; bias_col[i] = -1: b2 is added in
- * the fold.  Same partial-slice contract and return value as
+ * row and the bias costs nothing in the fold.  That 1.0 is scaled and split like
+ * every T value: the column is multiplied by f32(t_scale log2 e) held as f16
+ * hi + lo, which is log2(e) (1 + 6.9e-8) -- the same relative error on every
+ * bias.  The packer of the column owes the correction (jlm_amd/rowformats.py
+ * split_bias_correction; tests/test_gpu_split_logits.py pins it).
+ * bias_col[i] = -1: b2 is added in the fold.  Same partial-slice contract and return value as
  * jlm_vocab_lse_stationary.  The vocabulary is cut into COLUMNS of equal cost
  * (one workgroup per column and 256-row tile), at most 256 / row tiles of them;
  * a column that crosses a segment boundary writes one slice per segment it

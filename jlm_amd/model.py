@@ -31,7 +31,8 @@ import numpy as np
 from . import _lib
 from . import config as _config
 from . import ops as _ops
-from .rowformats import LOG2E, MIXED_SHAPES, MixedRows, MixedSegment, mixed_exponents, mixed_layout, mixed_shape, plane_scale, pow2_below
+from .rowformats import (LOG2E, MIXED_SHAPES, MixedRows, MixedSegment, mixed_exponents, mixed_layout, mixed_shape, plane_scale, pow2_below,
+                         split_bias_correction)
 
 GATES = "ifog"
 
@@ -339,7 +340,14 @@ class DeviceModel:
                 if nv:
                     O.pack_split_f16(self.seg_B[i], 0, nv, k, sg["ldb"], float(2.0 ** eB), dst, 0, k16)
                     if bias_col >= 0:
-                        O.pack_split_f16_col(self.b2, sg["v_start"], nv, float(2.0 ** eB), dst, k16, bias_col)
+                        # hi / lo of the column straight from the float64 product b2 2^eB x correction (the T-side constant of the
+                        # column is log2 e in 22 bits: rowformats.split_bias_correction).  Not through f32: b2 sits on the f32 grid,
+                        # so b2 (1 - 6.9e-8) would round the same way on every word -- one ulp down, 1.7e-8 too far on average.
+                        v = b2seg.double() * (split_bias_correction(2.0 ** eT) * 2.0 ** eB)
+                        hi = v.to(torch.float16)
+                        col = dst.view(torch.float16).view(nv, k16 // 8, 2, 8)[:, bias_col // 8, :, bias_col % 8]
+                        col[:, 0] = hi
+                        col[:, 1] = (v - hi.double()).to(torch.float16)
                 self.split_bias_col.append(bias_col)
                 self.seg_split.append(dst)
                 self.split_segments.append(dict(v_start=sg["v_start"], v_end=sg["v_end"], k=k, t_off=sg["t_off"], ldb=k16))

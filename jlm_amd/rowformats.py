@@ -20,6 +20,20 @@ def pow2_below(limit, value):
     return int(np.clip(np.floor(np.log2(limit / value)), -40, 40))
 
 
+def split_bias_correction(t_scale):
+    """What a bias must be multiplied by before it is packed into the bias column of split rows.  The normaliser kernels feed that
+    column the constant 1.0 like any T value (csrc/jlm_split.hip): scaled by f32(t_scale log2 e) and split into f16 hi + lo.  Those 22
+    bits hold log2(e) (1 + 6.9e-8) -- the same relative error on every word's bias, on every row: with a unigram-like bias of -7 under
+    the model's distribution that is -4.8e-7 on every log-normaliser, the same sign on every token (tests/test_gpu_score_budget.py
+    measured it; it summed to three quarters of a 35-word sentence's score error).  The correction is the exact constant over the held
+    one; the loader applies it in float64 and splits that product into the column's hi / lo itself, so what remains is each word's
+    own rounding to 22 bits."""
+    x = np.float32(np.float32(t_scale) * np.float32(LOG2E))
+    hi = np.float16(x)
+    lo = np.float16(x - np.float32(hi))
+    return float(t_scale) * LOG2E / (float(hi) + float(lo))
+
+
 def mixed_shape(k):
     """(32-k blocks, 16-k f16 steps) of a mixed row that carries its bias in two spare columns"""
     return ((k + 2 + 31) // 32, (k + 2 + 15) // 16)

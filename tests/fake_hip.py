@@ -762,8 +762,12 @@ class FakeLib:
             sp = view(sg.B, nv * sg.ldb * 2, np.float16).reshape(nv, sg.ldb // 8, 2, 8).astype(np.float64)
             Bfull = (sp[:, :, 0, :] + sp[:, :, 1, :]).reshape(nv, sg.ldb)
             y = (Tv * float(t_scale[i])) @ Bfull[:, :sg.k].T * float(descale[i])
-            if bc >= 0:          # the bias column times the 1.0 the kernel feeds (scaled by t_scale like every T value)
-                y = (y + float(t_scale[i]) * Bfull[:, bc][None, :] * float(descale[i])).astype(np.float32)
+            if bc >= 0:          # the bias column times the 1.0 the kernel feeds, scaled like every T value -- by f32(t_scale log2 e) -- and
+                # held as split rows hold it, f16 hi + lo: log2 e in 22 bits (jlm_amd/rowformats.py split_bias_correction undoes it)
+                one = np.float32(np.float32(t_scale[i]) * np.float32(1.4426950408889634))
+                hi = np.float16(one)
+                one = (float(hi) + float(np.float16(one - np.float32(hi)))) * 0.6931471805599453
+                y = (y + one * Bfull[:, bc][None, :] * float(descale[i])).astype(np.float32)
             else:
                 y = y.astype(np.float32) + view(_p(b2) + 4 * sg.v_start, nv, np.float32)
             mx = y.max(axis=1)

@@ -3,7 +3,7 @@ score_fold_kernel) against the oracle's explicit-state OracleLM.predict arithmet
 reference's vectors at 1e-10 by tests/test_oracle_golden.py), and against LSTM_Model.evaluate.
 
 Bars: per token |nll - oracle| <= 1e-5; per sentence the decode's path-score bar min(2e-5, 1e-6 (L + 1) + 2e-6); corpus perplexity
-within a relative 1e-5."""
+within a relative 1e-5 -- on every fixture, peaked20-vtable included (its expected failure is gone: tests/test_gpu_score_budget.py)."""
 import os
 import pickle
 
@@ -56,29 +56,18 @@ def _ragged(n, V, seed, lo=0, hi=40):
 
 def _check(got, want, tag):
     """the three bars, asserted"""
-    _check_bars(got, want, tag, True)
-
-
-def _check_bars(got, want, tag, sentence_bar):
-    """per-token and perplexity bars asserted; the per-sentence bar asserted (sentence_bar) or measured: -> [(row, L, |error|)] over it"""
     tot_g = tot_w = 0.0
     n_tok = 0
-    over = []
     for i, (g, w) in enumerate(zip(got, want)):
         assert len(g) == len(w), (tag, i)
         if len(w):
             np.testing.assert_allclose(g, w, rtol=0, atol=TOK_ATOL, err_msg="%s row %d" % (tag, i))
-            err = abs(g.sum() - w.sum())
-            if sentence_bar:
-                assert err <= sent_atol(len(w)), (tag, i, g.sum() - w.sum())
-            elif err > sent_atol(len(w)):
-                over.append((i, len(w), float(err)))
+            assert abs(g.sum() - w.sum()) <= sent_atol(len(w)), (tag, i, g.sum() - w.sum())
         tot_g += g.sum()
         tot_w += w.sum()
         n_tok += len(w)
     if n_tok:
         np.testing.assert_allclose(np.exp(tot_g / n_tok), np.exp(tot_w / n_tok), rtol=1e-5, err_msg=tag)
-    return over
 
 
 SMALL = ["small-tied", "small-untied", "small-dsoftmax", "small-vtable", "small-tied-sn", "small-vtable-sn",
@@ -129,10 +118,11 @@ def test_score_matches_oracle(name, fx, monkeypatch):
                                        ("peaked20-vtable", "JLM_LSE_MIXED")])
 def test_score_full_size_call_against_oracle_sample(name, knob, fx, monkeypatch):
     """> 2 560 rows in one call: the live prefix shrinks across row tiles of every kernel; the oracle checks a sample of rows.
-    peaked20 (logits of +-20, a trained model's statistics): the per-token and perplexity bars are asserted; the per-sentence
-    bar is measured -- sentences of 28-39 words exceed it by up to 30 % with the loader's mixed rows AND with split rows
-    (profiles/score_a_gpu_tests.log), so it is the f32 state / logit arithmetic over long sentences, not the normaliser's form.
-    Reported as an expected failure with the figures, not hidden under a wider bar."""
+    peaked20 (logits of +-20, a trained model's statistics) used to miss the per-sentence bar on 5-6 of the 24 sampled sentences by up
+    to 30 %, with mixed rows and split rows alike, and was reported as an expected failure.  tests/test_gpu_score_budget.py found the
+    stage -- the normaliser: every bias of the split rows' bias column off by the same 7e-8 relative -- and with that fixed
+    (rowformats.split_bias_correction) the bar holds, the worst sampled sentence at 1.26e-5 of 2e-5: asserted for every sentence,
+    like everywhere else."""
     if knob:
         monkeypatch.setenv(knob, "0")
     f = fx(name)
@@ -144,11 +134,10 @@ def test_score_full_size_call_against_oracle_sample(name, knob, fx, monkeypatch)
     sample = list(range(0, 2700, 113))
     lm = oracle_lm(f["root"])
     want, _h, _c = oracle_nll(lm, [seqs[i] for i in sample], 1)
-    peaked = name.startswith("peaked")
-    over = _check_bars([got[i] for i in sample], want, (name, knob), sentence_bar=not peaked)
-    if over:
-        pytest.xfail("%s (%s): %d of %d sentences over the per-sentence bar min(2e-5, 1e-6 (L + 1) + 2e-6): (row, L, |error|) %s"
-                     % (name, "split rows" if knob else "the loader's normaliser form", len(over), len(sample), over))
+    for i, g, w in zip(sample, [got[i] for i in sample], want):
+        if len(w):
+            print("%s %s row %d, %d words: sentence error %+.3g of %.3g" % (name, knob, i, len(w), g.sum() - w.sum(), sent_atol(len(w))))
+    _check([got[i] for i in sample], want, (name, knob))
 
 
 @pytest.mark.parametrize("knob,value", [("JLM_LSE_MIXED", "0"), ("JLM_LSE_MX6", "0"), ("JLM_MX_FIXREF", "0"), ("JLM_PRECISION", "f32")])

@@ -138,3 +138,16 @@ def test_pack_t_mixed_and_mixed6(widths, R):
     """FakeLib.jlm_pack_t_mixed: the f16 plane, the int8 hi plane and the row maximum from ONE rounding of the exact product T (2^eT log2 e), as
     pack_t_mixed_kernel has them; FakeLib.jlm_pack_t_mixed6 from the f32 product, as pack_t_mx6_kernel"""
     C.run_pack_t(FK, MEM, widths, R)
+
+
+def test_split_bias_correction_undoes_the_held_constant():
+    """the bias column of split rows meets f32(t_scale log2 e) as f16 hi + lo: the correction times that constant is t_scale log2 e"""
+    from jlm_amd.rowformats import LOG2E, split_bias_correction
+    for e in (-3, 0, 5, 9, 11):
+        ts = 2.0 ** e
+        x = np.float32(np.float32(ts) * np.float32(LOG2E))
+        hi = np.float16(x)
+        held = float(hi) + float(np.float16(x - np.float32(hi)))
+        c = split_bias_correction(ts)
+        assert abs(held * c / (ts * LOG2E) - 1.0) <= 1e-15
+        assert abs((1.0 / c - 1.0) - 6.928e-8) <= 1e-10            # log2 e in 22 bits: the same at every power-of-two scale
