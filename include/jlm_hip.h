@@ -199,10 +199,11 @@ int jlm_gemm_nt_split(const void *A, int lda, const int *a_rows, const void *B, 
                       float *C, int ldc, const int *c_rows, const float *bias, float descale,
                       int M, int N, int K, const int *m_dev, void *stream);
 /* ABI 12 (additive): which path jlm_gemm_nt_split takes for an M x N launch (pure host; the launcher asks here).  JLM_T_STAGES and
- * JLM_T_XCD are read once per process.  With three stages (the default) and at most 256 tiles of 64 x 64:
- *   0 gemm_split3_kernel<Cfg64, ..., 3>, linear tile map (JLM_T_XCD=0)
- *   1 gemm_split3_kernel<Cfg64, ..., 3>, XCD map 1: the column tiles of a row tile on one XCD (default)
- * otherwise gemm_split_kernel, linear map:
+ * JLM_T_XCD are read once per process.  With JLM_T_STAGES = 3 (the default: the ring kernel, which since the chain-trips change keeps a
+ * ring of four stages and two fragment register sets) and at most 256 tiles of 64 x 64:
+ *   0 gemm_split3_kernel<Cfg64, ..., 4>, linear tile map (JLM_T_XCD=0)
+ *   1 gemm_split3_kernel<Cfg64, ..., 4>, XCD map 1: the column tiles of a row tile on one XCD (default)
+ * otherwise (any other JLM_T_STAGES: the two-stage kernel, same MFMA order, same bits) gemm_split_kernel, linear map:
  *   2 gemm_split_kernel<Cfg64>   fewer than 512 tiles of 128 x 128
  *   3 gemm_split_kernel<Cfg128>  the rest */
 #define JLM_T_SPLIT3_LINEAR 0
@@ -391,7 +392,8 @@ typedef struct {
  * max_cands >= beam * (largest number of nodes ending at one (frame, sentence)).
  * 1 <= beam <= JLM_MAX_BEAM (the reference has no limit, decoder.py:227-229); a cell's candidates live in one wave's
  * LDS -- in one piece up to ~13 k, above that chunk by chunk with the chunks' winners merged (round 6: same order, same result);
- * -1 when max_cands exceeds jlm_beam_step_max_cands(beam, n_frames, mode).
+ * -1 when max_cands exceeds jlm_beam_step_max_cands(beam, n_frames, mode), and for a state of more than 2^29 rows
+ * (n_frames x n_sent x beam) in the one-piece form, whose kernel addresses score / lse / ysum rows by 32-bit byte offsets.
  * Every cell at frame <= sent_len holds at least one node: the real lattice always has the raw-kana fallback, so an empty cell
  * is not a case (the kernels clamp a lane's candidate to C - 1 and assume C >= 1). */
 int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *st_host,

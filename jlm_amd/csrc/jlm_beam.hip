@@ -314,15 +314,101 @@ __device__ __forceinline__ void wave_argmin(double &v, int &i) {
     v = __hiloint2double(hi, lo);
 }
 
+// The fused fold of both beam-step kernels: the kprev rows of the previous cell sit at part[p * ld_part + base + r], p < n_parts; their
+// log-normalisers go to lse_new[r] (LDS) and lse_out[r].  8 lanes per row, 16 rows per pass (two rows a lane), and the slices of a lane
+// are requested BEAM_FOLD_NB per row at a time before any is used: one memory round trip per 8 * BEAM_FOLD_NB = 32 slices and 16 rows
+// where a load per slice, each waited for, made ceil(n_parts / 8) round trips per 8 rows (the loads never depended on one another).
+// A load past the end is clamped onto the last slice / row and its value dropped, so the batch is straight-line code.  The arithmetic
+// and its order are what they were -- per lane the slices sub, sub + 8, ... ascending, then the xor tree 4, 2, 1 -- with the one
+// rounding the compiler was free to choose written out: the new term's product is rounded, the running sum's is fused (what the
+// per-slice loop compiled to).
+#define BEAM_FOLD_NB 4
+__device__ __forceinline__ void beam_fold_parts(const jlm_beam_state &st, int lane, int kprev, int base, double *lse_new,
+                                                double *lse_out) {
+    const float2 *part = reinterpret_cast<const float2 *>(st.lse_part);
+    const int sub = lane & 7, n_parts = st.n_parts;
+    for (int r0 = 0; r0 < kprev; r0 += 16) {
+        int r[2];
+        const float2 *row[2];
+        float m[2];
+        double sm[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            r[h] = r0 + 8 * h + (lane >> 3);
+            row[h] = part + base + min(r[h], kprev - 1);
+            m[h] = JLM_NEG_BIG;
+            sm[h] = 0.0;
+        }
+        for (int pb = 0; pb < n_parts; pb += 8 * BEAM_FOLD_NB) {
+            float2 v[2][BEAM_FOLD_NB];
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int j = 0; j < BEAM_FOLD_NB; ++j) v[h][j] = row[h][(size_t)min(pb + sub + 8 * j, n_parts - 1) * st.ld_part];
+            __builtin_amdgcn_sched_barrier(0);             // every load of the batch is requested before the first is folded
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int j = 0; j < BEAM_FOLD_NB; ++j)
+                    if (r[h] < kprev && pb + sub + 8 * j < n_parts) {
+                        const float mm = fmaxf(m[h], v[h][j].x);
+                        sm[h] = fma(sm[h], (double)expf(m[h] - mm), __dmul_rn((double)v[h][j].y, (double)expf(v[h][j].x - mm)));
+                        m[h] = mm;
+                    }
+            // every load of the batch has been used or dropped: said out loud (vmcnt(0), the other counters open), so that the
+            // compiler need not guard the next batch's registers with a wait at the loop's head -- that wait would also stand in
+            // front of the FIRST batch and hold it back for whatever load the caller has in flight
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (r0 + 8 * h >= kprev) break;                // (wave-uniform: the shuffles below are taken by all lanes or none)
+            float mh = m[h];
+            double sh = sm[h];
+#pragma unroll
+            for (int off = 4; off >= 1; off >>= 1) {
+                const float m2 = __shfl_xor(mh, off);
+                const double s2 = __shfl_xor(sh, off);
+                const float mm = fmaxf(mh, m2);
+                sh = fma(sh, (double)expf(mh - mm), __dmul_rn(s2, (double)expf(m2 - mm)));
+                mh = mm;
+            }
+            if (sub == 0 && r[h] < kprev) {
+                double l = (double)mh + log(sh);
+                // inf / nan (jlm_beam_state.flags): the batch is flagged and the value replaced by a finite one -- a NaN key would leave
+                // the selection rounds without a winner and the next LSTM step with garbage row indices
+                if (!(fabs(l) < 1.0e300)) { if (st.flags) atomicOr(st.flags, 1); l = 1.0e30; }
+                lse_new[r[h]] = l;
+                lse_out[r[h]] = l;
+            }
+        }
+    }
+}
+
+// base[byte_off / sizeof(T)] with a 32-bit byte offset: off a wave-uniform base the load takes the base from scalar registers and ONE
+// address register per lane (two loads off the same row share it) where a 64-bit lane address costs two per load -- with eight
+// candidates' loads in flight that is what fits the kernel into 64 registers.  (jlm_beam_step refuses states past 2^32 bytes.)
+template <class T>
+__device__ __forceinline__ T beam_ld(const T *base, unsigned byte_off) {
+    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
 template <int MODE>
 __global__ __launch_bounds__(64, 8) void beam_step_kernel(jlm_lattice lat, jlm_beam_state st, int frame, int max_cands) {
     extern __shared__ __attribute__((aligned(16))) double keys[];   // [max_cands] | MODE 2: [n_frames*beam] | int [max_cands] | [beam] | int [n_frames] | winners: [beam] double, [beam] int
     const int s = blockIdx.x, lane = threadIdx.x;
     const int B = lat.n_sent, beam = lat.beam, rmax = B * beam;
-    const int len = lat.sent_len[s];
     const int fs = frame * B + s;
+    // every index the wave needs first is requested here, in one round trip: the sentence's length, the cell's bounds, and the fold's
+    // count and slice position of the previous cell (all readable whatever the length: the tables cover every (frame, sentence))
+    const bool fused = MODE == 0 && st.lse_part != nullptr;
+    const int fprev = frame > 0 ? fs - B : fs;             // (frame 0 reads its own entries and uses neither)
+    const int *lbase = fused ? st.live_base : st.cnt;      // (not fused: likewise)
+    int len = lat.sent_len[s];
+    int nb = lat.end_off[fs], ne = lat.end_off[fs + 1];
+    int kprev = st.cnt[fprev], pbase = lbase[fprev];
+    asm volatile("" : "+s"(len), "+s"(nb), "+s"(ne), "+s"(kprev), "+s"(pbase));   // all five before the first branch on one of them
     if (frame > len) { if (lane == 0) st.cnt[fs] = 0; return; }
-    const int nb = lat.end_off[fs], ne = lat.end_off[fs + 1];
     const int gout = frame * rmax + s * beam;
     const double INF = __longlong_as_double(0x7ff0000000000000LL);
     double *Sarr = keys + max_cands;                                       // MODE 2 only
@@ -337,43 +423,12 @@ __global__ __launch_bounds__(64, 8) void beam_step_kernel(jlm_lattice lat, jlm_b
         K = 1;
     } else {
         // ---- fused fold of the previous frame's vocabulary partials (this sentence's rows)
-        const bool fused = MODE == 0 && st.lse_part != nullptr;
-        const int fprev = (frame - 1) * B + s;
-        for (int f = lane; f < frame; f += 64) cnt_s[f] = st.cnt[f * B + s];
-        const int kprev = st.cnt[fprev];
-        if (fused && kprev > 0) {
-            const int base = st.live_base[fprev];
-            const float2 *part = reinterpret_cast<const float2 *>(st.lse_part);
-            const int sub = lane & 7;
-            for (int r0 = 0; r0 < kprev; r0 += 8) {
-                const int r = r0 + (lane >> 3);
-                float m = JLM_NEG_BIG;
-                double sm = 0.0;
-                if (r < kprev)
-                    for (int p = sub; p < st.n_parts; p += 8) {
-                        const float2 v = part[(size_t)p * st.ld_part + base + r];
-                        const float mm = fmaxf(m, v.x);
-                        sm = sm * (double)expf(m - mm) + (double)v.y * (double)expf(v.x - mm);
-                        m = mm;
-                    }
-#pragma unroll
-                for (int off = 4; off >= 1; off >>= 1) {
-                    const float m2 = __shfl_xor(m, off);
-                    const double s2 = __shfl_xor(sm, off);
-                    const float mm = fmaxf(m, m2);
-                    sm = sm * (double)expf(m - mm) + s2 * (double)expf(m2 - mm);
-                    m = mm;
-                }
-                if (sub == 0 && r < kprev) {
-                    double l = (double)m + log(sm);
-                    // inf / nan (jlm_beam_state.flags): the batch is flagged and the value replaced by a finite one -- a NaN key would leave
-                    // the selection rounds below without a winner and the next LSTM step with garbage row indices
-                    if (!(fabs(l) < 1.0e300)) { if (st.flags) atomicOr(st.flags, 1); l = 1.0e30; }
-                    lse_new[r] = l;
-                    st.lse[(size_t)(frame - 1) * rmax + s * beam + r] = l;
-                }
-            }
-        }
+        //      (this sentence's counts of the first 64 frames are requested before the fold's slices and stored after them: their
+        //       round trip is the fold's, not one of its own in front of it)
+        const int cnt_lane = st.cnt[min(lane, frame - 1) * B + s];
+        if (fused && kprev > 0) beam_fold_parts(st, lane, kprev, pbase, lse_new, st.lse + ((size_t)(frame - 1) * rmax + s * beam));
+        if (lane < frame) cnt_s[lane] = cnt_lane;
+        for (int f = lane + 64; f < frame; f += 64) cnt_s[f] = st.cnt[f * B + s];
         const int C = (ne - nb) * beam;
         if (MODE == 2) {
             // S(g) = sum of the CURRENT log-normalisers of g's ancestors: every path is
@@ -394,10 +449,11 @@ __global__ __launch_bounds__(64, 8) void beam_step_kernel(jlm_lattice lat, jlm_b
             }
         }
         __syncthreads();                                   // lse_new (and Sarr) visible to every lane
-        // ---- keys of this lane's candidates, its running minimum.  Four candidates at a time with the
-        //      loads of each dependency level issued together (start frame; then score / lse / edge of
-        //      the predecessor): a round trip per level and group instead of three per candidate --
-        //      these chains, not the selection, were 18 of the kernel's 22 us.
+        // ---- keys of this lane's candidates, its running minimum.  Several candidates at a time (mode 0: the
+        //      first eight, then four; modes 1 and 2: four) with the loads of each dependency level issued
+        //      together (start frame and edge logit; then score / lse of the predecessor): a round trip per
+        //      level and batch instead of three per candidate -- these chains, not the selection, were 18 of
+        //      the kernel's 22 us.
         int nvalid = 0;
         double bv = INF;
         int bi = 0x7fffffff;
@@ -405,50 +461,100 @@ __global__ __launch_bounds__(64, 8) void beam_step_kernel(jlm_lattice lat, jlm_b
         double kreg[NREG];
 #pragma unroll
         for (int j = 0; j < NREG; ++j) kreg[j] = INF;
-        auto group = [&](int it, auto REG0) {              // candidates lane + 64 (U it + u), u < U
-            constexpr int reg0 = decltype(REG0)::value;    // first register slot of the group, or -1: keys[] in LDS
+        const int gprev = (frame - 1) * rmax + s * beam;     // first row of the previous cell: the rows the fold has just served
+        const int *cell_start = lat.node_start + nb;       // the cell's nodes and edge logits: uniform bases, 32-bit lane offsets
+        const float *cell_edge = st.edge + (size_t)nb * beam;
+        // A candidate has two levels of loads: its node's start frame and its edge logit, which need only its index, and the
+        // predecessor's score / log-normaliser (/ y sum), which need the start frame.  level1 requests the first for NC candidates
+        // lane + 64 (U it + j), level2 the second, and finish makes the keys in ascending candidate order.
+        auto level1 = [&](int it, auto NCc, int *k, int *sf, float *ev) {
+            constexpr int NC = decltype(NCc)::value;
             const int c0 = lane + 64 * U * it;
-            int n[U], k[U], sf[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int c = min(c0 + 64 * u, C - 1);     // past the end: a duplicate, discarded below
-                n[u] = nb + c / beam;
-                k[u] = c % beam;
-                sf[u] = lat.node_start[n[u]];
+            for (int j = 0; j < NC; ++j) {
+                const int c = min(c0 + 64 * j, C - 1);     // past the end: a duplicate of the last, discarded below
+                const int q = (int)((unsigned)c / (unsigned)beam);
+                k[j] = c - q * beam;
+                sf[j] = beam_ld(cell_start, (unsigned)q * 4u);
+                ev[j] = beam_ld(cell_edge, (unsigned)c * 4u);     // (= edge[node * beam + k])
             }
-            bool ok[U];
-            double scv[U], lsv[U], ysv[U];
-            float ev[U];
+        };
+        auto level2 = [&](int it, auto NCc, const int *k, int *sf, double *scv, double *lsv, double *ysv) -> unsigned {
+            constexpr int NC = decltype(NCc)::value;
+            const int c0 = lane + 64 * U * it;
+            unsigned okm = 0;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                ok[u] = (c0 + 64 * u < C) && k[u] < cnt_s[sf[u]];
-                const int gp = sf[u] * rmax + s * beam + (ok[u] ? k[u] : 0);
-                ev[u] = st.edge[(size_t)n[u] * beam + k[u]];
-                scv[u] = (MODE == 2) ? 0.0 : st.score[gp];
-                lsv[u] = (MODE == 1) ? 0.0 : st.lse[gp];
-                ysv[u] = (MODE == 2) ? st.ysum[gp] : 0.0;
+            for (int j = 0; j < NC; ++j) {
+                // straight-line code (no short circuit around the LDS read, no skipped store): a candidate past the end is the last
+                // one over again, reads what that one reads and stores the same predecessor row to the same place
+                const bool live = k[j] < cnt_s[sf[j]], ok = live & (c0 + 64 * j < C);
+                const int gp = sf[j] * rmax + s * beam + (live ? k[j] : 0);
+                scv[j] = (MODE == 2) ? 0.0 : beam_ld(st.score, (unsigned)gp * 8u);
+                lsv[j] = (MODE == 1) ? 0.0 : beam_ld(st.lse, (unsigned)gp * 8u);
+                ysv[j] = (MODE == 2) ? beam_ld(st.ysum, (unsigned)gp * 8u) : 0.0;
                 // (the predecessor row is written here, not beside the key: it need not stay in a register while the loads are in flight)
-                if (c0 + 64 * u < C) gp_of[c0 + 64 * u] = ok[u] ? gp : -1;
+                gp_of[min(c0 + 64 * j, C - 1)] = live ? gp : -1;
+                okm |= (ok ? 1u : 0u) << j;
+                // what mode 2's finish still needs of the start frame: where the predecessor's term is in LDS
+                sf[j] = (MODE == 2) ? sf[j] * beam + k[j] : -1;
             }
+            return okm;
+        };
+        auto finish = [&](int it, auto NCc, auto REG0, unsigned okm, const int *sel, const float *ev, const double *scv,
+                          const double *lsv, const double *ysv) {
+            constexpr int NC = decltype(NCc)::value;
+            constexpr int reg0 = decltype(REG0)::value;    // first register slot of the candidates, or -1: keys[] in LDS
+            const int c0 = lane + 64 * U * it;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int c = c0 + 64 * u;
-                if (c >= C) break;
-                double sc = INF;
-                if (ok[u]) {
-                    const double e = (double)ev[u];
-                    if (MODE == 0) sc = scv[u] + (((fused && sf[u] == frame - 1) ? lse_new[k[u]] : lsv[u]) - e);
-                    else if (MODE == 1) sc = scv[u] - e;
-                    else sc = (Sarr[sf[u] * beam + k[u]] + lsv[u]) - (ysv[u] + e);
-                    ++nvalid;
+            for (int j = 0; j < NC; ++j) {
+                const int c = c0 + 64 * j;
+                const bool ok = (okm >> j) & 1u;           // (clear past the end)
+                const double e = (double)ev[j];
+                double t;
+                if (MODE == 0) {
+                    // the row's position in the previous cell comes back from the predecessor row level2 stored (-1: none), not from
+                    // a register kept across the loads: eight of them are what the kernel is short of
+                    const int kp = gp_of[min(c, C - 1)] - gprev;
+                    const bool from_fold = fused && (unsigned)kp < (unsigned)beam;
+                    double ln = lse_new[from_fold ? kp : 0];
+                    asm volatile("" : "+v"(ln));           // (read whatever kp: left alone the read moves under a branch per candidate)
+                    t = scv[j] + ((from_fold ? ln : lsv[j]) - e);
+                } else if (MODE == 1) {
+                    t = scv[j] - e;
+                } else {
+                    t = (Sarr[sel[j]] + lsv[j]) - (ysv[j] + e);
                 }
-                if constexpr (reg0 >= 0) kreg[reg0 + u] = sc; else keys[c] = sc;
+                const double sc = ok ? t : INF;
+                nvalid += ok ? 1 : 0;
+                if constexpr (reg0 >= 0) kreg[reg0 + j] = sc; else if (c < C) keys[c] = sc;
                 if (sc < bv) { bv = sc; bi = c; }          // ascending c: ties keep the lower index
             }
         };
-        group(0, std::integral_constant<int, 0>{});
-        if (C > 64 * U) group(1, std::integral_constant<int, U>{});
-        for (int it = 2; 64 * U * it < C; ++it) group(it, std::integral_constant<int, -1>{});
+        // NCc candidates of a lane from group `it` on: a round trip per level
+        auto take = [&](int it, auto NCc, auto REG0) {
+            constexpr int NC = decltype(NCc)::value;
+            int k[NC], sf[NC];
+            float ev[NC];
+            double scv[NC], lsv[NC], ysv[NC];
+            level1(it, NCc, k, sf, ev);
+            const unsigned okm = level2(it, NCc, k, sf, scv, lsv, ysv);
+            finish(it, NCc, REG0, okm, sf, ev, scv, lsv, ysv);
+        };
+        using I0 = std::integral_constant<int, 0>;
+        using IU = std::integral_constant<int, U>;
+        using IR = std::integral_constant<int, NREG>;
+        using IL = std::integral_constant<int, -1>;
+        if constexpr (MODE == 0) {
+            // the decode's form: eight candidates of a lane at once, so both register groups in two round trips and the headline
+            // cells (500-520 candidates) in four where group after group it was six.  (The third group's level 1 beside the first
+            // two's does not fit: with those twelve registers held across level 2 the compiler spills 56 bytes a lane.)
+            take(0, IR{}, I0{});
+            for (int it = 2; 64 * U * it < C; ++it) take(it, IU{}, IL{});
+        } else {
+            take(0, IU{}, I0{});
+            if (C > 64 * U) take(1, IU{}, IU{});
+            for (int it = 2; 64 * U * it < C; ++it) take(it, IU{}, IL{});
+        }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) nvalid += __shfl_xor(nvalid, off);
         K = min(beam, nvalid);
@@ -544,37 +650,8 @@ __global__ __launch_bounds__(64) void beam_step_chunked_kernel(jlm_lattice lat, 
         const int fprev = (frame - 1) * B + s;
         for (int f = lane; f < frame; f += 64) cnt_s[f] = st.cnt[f * B + s];
         const int kprev = st.cnt[fprev];
-        if (fused && kprev > 0) {
-            const int base = st.live_base[fprev];
-            const float2 *part = reinterpret_cast<const float2 *>(st.lse_part);
-            const int sub = lane & 7;
-            for (int r0 = 0; r0 < kprev; r0 += 8) {
-                const int r = r0 + (lane >> 3);
-                float m = JLM_NEG_BIG;
-                double sm = 0.0;
-                if (r < kprev)
-                    for (int p = sub; p < st.n_parts; p += 8) {
-                        const float2 v = part[(size_t)p * st.ld_part + base + r];
-                        const float mm = fmaxf(m, v.x);
-                        sm = sm * (double)expf(m - mm) + (double)v.y * (double)expf(v.x - mm);
-                        m = mm;
-                    }
-#pragma unroll
-                for (int off = 4; off >= 1; off >>= 1) {
-                    const float m2 = __shfl_xor(m, off);
-                    const double s2 = __shfl_xor(sm, off);
-                    const float mm = fmaxf(m, m2);
-                    sm = sm * (double)expf(m - mm) + s2 * (double)expf(m2 - mm);
-                    m = mm;
-                }
-                if (sub == 0 && r < kprev) {
-                    double l = (double)m + log(sm);
-                    if (!(fabs(l) < 1.0e300)) { if (st.flags) atomicOr(st.flags, 1); l = 1.0e30; }
-                    lse_new[r] = l;
-                    st.lse[(size_t)(frame - 1) * rmax + s * beam + r] = l;
-                }
-            }
-        }
+        if (fused && kprev > 0)
+            beam_fold_parts(st, lane, kprev, st.live_base[fprev], lse_new, st.lse + ((size_t)(frame - 1) * rmax + s * beam));
         const int C = (ne - nb) * beam;
         if (MODE == 2) {
             for (int f = 0; f < frame; ++f) {
@@ -815,6 +892,8 @@ extern "C" int jlm_beam_step(const jlm_lattice *lat_host, const jlm_beam_state *
         return 0;
     }
     const size_t lds = plan.lds;
+    // beam_ld: a predecessor row's byte offset (8 bytes a row) must fit 32 bits
+    if ((size_t)lat.n_frames * lat.n_sent * lat.beam > ((size_t)1 << 29)) return -1;
     const void *fn = mode == 0 ? (const void *)beam_step_kernel<0>
                    : mode == 1 ? (const void *)beam_step_kernel<1> : (const void *)beam_step_kernel<2>;
     static JlmLdsGrant grant[3];

@@ -39,6 +39,7 @@ extern "C" int jlm_prof_read_wg_gemm(unsigned long long *out) {
 #define JLM_WG_T(i) (void)0
 #endif
 #include <stdlib.h>
+#include <type_traits>
 
 #define BK 32
 
@@ -608,9 +609,16 @@ __global__ __launch_bounds__(Cfg::NTHREADS) void gemm_split_kernel(ARows A, BRow
     JLM_WG_T(3);
 }
 
-// NST-stage form (NST = 3 is what is instantiated) for grids that do not fill the chip (the T projection: 240 workgroups, one per CU, so the
-// extra stage costs no residency).  Per k-step:  wait(step kt landed) ; barrier ; request step kt + 2 ; MFMAs(kt):
-// a DMA piece has two k-steps to arrive and the wait is s_waitcnt vmcnt(pieces of one stage), not vmcnt(0).
+// Ring form for grids that do not fill the chip (the T projection: 240 workgroups, one per CU and one wave per SIMD, so nothing but the
+// wave's own instruction order hides a latency, and the extra stages cost no residency).  NST = 4 stages; the fragments live in two
+// register sets.  K-step kt:
+//     wait(step kt + 1 landed: only step kt + 2's pieces may be out) ; barrier ; first MFMAs of kt (their fragments were read a step
+//     ago) ; read the fragments of kt + 1 into the other set ; request step kt + 3 ; remaining MFMAs of kt
+// so no MFMA waits for an LDS read issued in its own step, and the DMA pieces (~60 issue cycles each beside MFMAs) go out behind
+// matrix work instead of in front of the reads.  Step kt + 3 refills the stage of step kt - 1, whose reads every wave had back before
+// it issued the MFMAs of kt - 1, i.e. before this step's barrier.  The waits are counted from the issue order (vmcnt(pieces of one
+// stage)), never vmcnt(0) while a later step is in flight.  Each accumulator sees the MFMAs of gemm_split_kernel in its order -- k
+// ascending, lo.hi, hi.lo, hi.hi per 16-k step -- so the result is that kernel's bit for bit.
 template <class Cfg, class ARows, class BRows, class Epi, int NST>
 __global__ __launch_bounds__(Cfg::NTHREADS) void gemm_split3_kernel(ARows A, BRows B, int K, Epi epi, TileMap tmap) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -676,40 +684,67 @@ __global__ __launch_bounds__(Cfg::NTHREADS) void gemm_split3_kernel(ARows A, BRo
 #pragma unroll
         for (int p = 0; p < 2; ++p) goff[st][p] = li * 32 + (((4 * st + 2 * h + p) ^ ((li >> 1) & 7)) * 4);
     JLM_WG_T(1);
+    static_assert(NST == 4, "the loop below refills the stage of step kt - 1 with step kt + 3");
 #pragma unroll
     for (int q = 0; q < NST - 1; ++q)
         if (q < nk) issue(q * BK, q);
-    int stg = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        // steps kt+1 .. kt+NST-2 may still be in flight (fewer at the end: wait for everything then)
-        if (kt + NST - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((NST - 2) * PER) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (kt + NST - 1 < nk) issue((kt + NST - 1) * BK, stg == 0 ? NST - 1 : stg - 1);
+    f16x8 a[2][2][MT][2], b[2][2][NT][2];     // [register set][16-k step][block][plane]
+    auto read = [&](auto SET, int stg) {
+        constexpr int set = decltype(SET)::value;
         const float *as = As + (stg * BM + wm * MT * 32) * 32;
         const float *bs = Bs + (stg * BN + wn * NT * 32) * 32;
-        f16x8 a[2][MT][2], b[2][NT][2];
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) a[st][mt][p] = *reinterpret_cast<const f16x8 *>(as + mt * 1024 + goff[st][p]);
+                for (int mt = 0; mt < MT; ++mt) a[set][st][mt][p] = *reinterpret_cast<const f16x8 *>(as + mt * 1024 + goff[st][p]);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) b[st][nt][p] = *reinterpret_cast<const f16x8 *>(bs + nt * 1024 + goff[st][p]);
+                for (int nt = 0; nt < NT; ++nt) b[set][st][nt][p] = *reinterpret_cast<const f16x8 *>(bs + nt * 1024 + goff[st][p]);
             }
+    };
+    auto mfmas = [&](auto SET, int st) {
+        constexpr int set = decltype(SET)::value;
+#pragma unroll
+        for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[set][st][mt][pr == 0 ? 1 : 0], b[set][st][nt][pr == 1 ? 1 : 0],
+                                                                         acc[mt][nt], 0, 0, 0);
+    };
+    auto step = [&](int kt, auto CUR, auto NXT) {
+        if (kt + 1 < nk) {
+            if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PER) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+        // The compiler treats an LDS-DMA request as a possible LDS access of unknown order: the first use of an LDS read behind one
+        // gets lgkmcnt(0), whatever was counted.  So the step's first MFMAs come first -- their wait finds only the reads of a step ago
+        // -- and the reads of kt + 1 and the requests of kt + 3 follow them: at the next use of a read (the next step's first MFMA)
+        // three MFMAs and the requests' issue have passed.
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-            for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[st][mt][pr == 0 ? 1 : 0], b[st][nt][pr == 1 ? 1 : 0],
-                                                                             acc[mt][nt], 0, 0, 0);
-        stg = stg == NST - 1 ? 0 : stg + 1;
+        mfmas(CUR, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        // (the reads also behind the last step, where what they fetch is stale and never used: under a condition the compiler would
+        //  have to guard the MFMAs of both register sets)
+        read(NXT, (kt + 1) & (NST - 1));
+        if (kt + 3 < nk) issue((kt + 3) * BK, (kt + 3) & (NST - 1));
+        __builtin_amdgcn_sched_barrier(0);
+        mfmas(CUR, 1);
+    };
+    // step 0 landed: the pieces of steps 1 and 2, where there are such steps, may still be out
+    if (nk >= 3) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(2 * PER) : "memory");
+    else if (nk == 2) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(PER) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    using S0 = std::integral_constant<int, 0>;
+    using S1 = std::integral_constant<int, 1>;
+    if (nk > 0) read(S0{}, 0);
+    for (int kt = 0; kt + 1 < nk; kt += 2) {
+        step(kt, S0{}, S1{});
+        step(kt + 1, S1{}, S0{});
     }
+    if (nk & 1) step(nk - 1, S0{}, S1{});
     JLM_WG_T(2);
     __syncthreads();                          // the epilogues reuse the staging memory
     epi.template run<Cfg>(acc, m0, n0, wm, wn, lane, M, N, smem, pre);
@@ -793,7 +828,7 @@ extern "C" int jlm_gemm_nt(const float *Ap, int lda, const int *a_rows, const fl
 extern "C" int jlm_gemm_nt_split_form(int M, int N) {
     const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128);
     const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
-    static int stages = -1;                    // 3 stages: 17.4 -> 13.8 us on the T projection; 4 and 6 are no better
+    static int stages = -1;                    // 3 (default): the ring kernel (gemm_split3_kernel); any other value: the two-stage kernel
     if (stages < 0) { const char *e = getenv("JLM_T_STAGES"); stages = e ? atoi(e) : 3; }
     // XCD map 1: the column tiles of one row tile run on the same XCD, so a gathered A row crosses the fabric into ONE L2
     // instead of up to tiles_n of them (T projection: 36.6 MB fetched per launch for 9.4 MB of operands with the linear map).
@@ -817,7 +852,7 @@ extern "C" int jlm_gemm_nt_split(const void *Ap, int lda, const int *a_rows, con
     epi.C = C; epi.c_map = c_rows; epi.ldc = ldc; epi.bias = bias; epi.scale = descale;
     const int form = jlm_gemm_nt_split_form(M, N);
     if (form == JLM_T_SPLIT3_LINEAR || form == JLM_T_SPLIT3_XCD)
-        return launch_gemm_split3<Cfg64, PlainRows, PlainRows, EpiStore, 3>(A, B, K, epi, form == JLM_T_SPLIT3_XCD ? 1 : 0, (hipStream_t)stream);
+        return launch_gemm_split3<Cfg64, PlainRows, PlainRows, EpiStore, 4>(A, B, K, epi, form == JLM_T_SPLIT3_XCD ? 1 : 0, (hipStream_t)stream);
     if (form == JLM_T_CFG64) return launch_gemm_split<Cfg64>(A, B, K, epi, 0, (hipStream_t)stream);
     return launch_gemm_split<Cfg128>(A, B, K, epi, 0, (hipStream_t)stream);
 }
