@@ -966,6 +966,67 @@ typedef struct {
 int jlm_rank_frames(const jlm_decode_model *model_host, const jlm_rank_plan *plan_host, void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
+ * The continuous cache of teacher-forced scoring (LSTM_Model.score_cached / score_streams_cached, jlm_amd/cache.py; Grave, Joulin,
+ * Usunier, "Improving neural language models with a continuous cache", ICLR 2017).  Additive to ABI 12.
+ *
+ * Take one row, a sequence or a stream.  Position j is the step that consumes word[j]; it leaves the hidden state h_j and is scored
+ * on w_j = target[j].  Positions are numbered over the whole life of a stream, across calls.  The cache before position q holds the
+ * pairs (h_i, w_i) for max(q - N, first) <= i < q, first = the row's oldest existing position; n_q is their count.
+ *   s_i       = theta * (h_q . h_i)                       h in real units (split rows: (hi + lo) / h_scale)
+ *   lpc_q     = log sum_{i : w_i = w_q} exp(s_i) - log sum_i exp(s_i)       (-inf when no i matches, and when n_q = 0: unused there)
+ *   p_q       = (1 - lambda) exp(-nll_q) + lambda exp(lpc_q)   when n_q > 0;   exp(-nll_q) when n_q = 0
+ *   nll_mix_q = -log p_q                                   (float64, on the host, via logaddexp: jlm_amd/cache.py)
+ * nll_q is what score_fold_kernel writes (self_norm models: -y).  Word ids are only ever compared, never used as an index.
+ * Ranges: N >= 1, theta >= 0, 0 <= lambda < 1.
+ *
+ * jlm_cache_rows (csrc/jlm_cache.hip, cache_rows_kernel): lpc of n_query consecutive positions pos0 .. pos0 + n_query - 1 of n_rows
+ * rows, for n_theta values of theta, from two rings:
+ *   hist  [cap][n_rows][H]   state rows in the model's state-row format, 4 bytes a value either way: split != 0 the split rows the
+ *                            LSTM step writes ([8 hi][8 lo] f16 of h * h_scale), else plain f32 (h_scale is not read); 16-byte aligned
+ *   words [cap][n_rows]      int32: w_i
+ * The slot of logical position j is j mod cap; the queries' own states and words are in the rings (cap >= N + n_query, so that no
+ * query's slot is an entry of another's window).  first [n_rows] device: row r's oldest existing position (>= 0); len [n_rows]
+ * device: the number of queries of row r, the positions pos0 .. pos0 + len[r] - 1 (rows are sorted longest first, so a row's queries are
+ * a prefix of the steps); thetas [n_theta] HOST floats, 1 <= n_theta <= JLM_CACHE_MAX_THETAS.
+ *   lpc [n_theta][n_query][n_rows] f32; entries (q, r) with q >= len[r] are left untouched.
+ *   flags (one device int, may be NULL): |= 1 when the product h_q . h_i of an entry inside a query's window is not finite.  A slot
+ *   outside every window is never read.
+ * Arithmetic: the products h_q . h_i come off the matrix pipe -- split rows: hi.hi + hi.lo + lo.hi in three v_mfma_f32_32x32x16_f16
+ * per 16 k with f32 accumulation over the stored halves, 1 / h_scale^2 folded into theta; f32 rows: v_mfma_f32_32x32x2_f32, an f32 fmaf
+ * chain over k -- s = f32(theta' * dot); the two sums are f32 online sums under one running maximum, expf / logf the f32 library
+ * functions, lpc = logf(M) - logf(Z).  The values of theta are independent of one another: lpc[t] is the same bits whatever else
+ * thetas holds.  The order of the sums depends on pos0 and the window, so the same window reached by another cut of a stream may
+ * differ within the rounding bound (tests/test_gpu_cache_rows.py derives it).
+ * Returns -1 before any launch for cap < N + n_query, N < 1, H <= 0 or H % 32 != 0 (what jlm_lstm_step / jlm_lstm_step_xg accept),
+ * hist not 16-byte or another pointer not 4-byte aligned or NULL, n_theta out of range, a theta that is negative or not finite,
+ * pos0 < 0 or pos0 + n_query + cap >= 2^31, n_rows > 65535, split != 0 with h_scale <= 0; 0 with nothing launched for n_rows == 0
+ * or n_query == 0; else 0 or a hipError_t. */
+#define JLM_CACHE_MAX_THETAS 16
+int jlm_cache_rows(const void *hist, const int *words, int cap, int n_rows, int H, int split, float h_scale, int pos0, int n_query,
+                   const int *first, const int *len, int N, const float *thetas_host, int n_theta, float *lpc, int *flags, void *stream);
+
+/* What a cached scoring call has beside its jlm_score_plan (whose layout is unchanged): the rings of jlm_cache_rows over the plan's
+ * n_rows rows, step t of the plan being position pos0 + t. */
+typedef struct {
+    void *hist; int *words; int cap;    /* the rings; the entries carried into the call are in their slots already */
+    int pos0;                           /* the position of step 0 */
+    const int *first;                   /* [n_rows] device */
+    const int *len;                     /* [n_rows] device: the steps row r is live */
+    int N;
+    const float *thetas; int n_theta;   /* host */
+    float *lpc;                         /* [n_theta][n_steps][n_rows] device */
+    int *flags;                         /* one device int or NULL: jlm_cache_rows' bit */
+} jlm_cache_plan;
+
+/* jlm_score_frames' loop -- the same launches in the same order, so nll_seq / nll_tok are the same bits -- with two additions: after
+ * step t the live rows of the state set the step wrote are copied into hist[slot(pos0 + t)] (an asynchronous device-to-device copy on
+ * `stream`, in the raw state-row format: one small launch) and the step's targets into words at the same slot; after the last step jlm_cache_rows runs
+ * once over the n_steps query positions.  No host synchronisation.  Every refusal of jlm_cache_rows is returned before the first
+ * launch.  events as jlm_score_frames'.  Returns as jlm_score_frames does. */
+int jlm_score_cache_frames(const jlm_decode_model *model_host, const jlm_score_plan *plan_host, const jlm_cache_plan *cache_host,
+                           void *stream, void *const *events);
+
+/* ------------------------------------------------------------------------
  * Left context of a decode (LSTM_Model.prime, Decoder.decode(context=), jlm_amd/context.py).  Sentence s with the committed words
  * ctx_s has the history hist = [<eos>] + ctx_s; its decode is the reference's with the root hypothesis consuming hist[-1] from the
  * state reached by consuming hist[:-1] from the zero state.

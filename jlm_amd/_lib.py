@@ -91,6 +91,12 @@ class RankPlan(Structure):
                 ("flags", c_void_p)]
 
 
+class CachePlan(Structure):
+    """jlm_cache_plan (include/jlm_hip.h)."""
+    _fields_ = [("hist", c_void_p), ("words", c_void_p), ("cap", c_int), ("pos0", c_int), ("first", c_void_p), ("len", c_void_p),
+                ("N", c_int), ("thetas", POINTER(c_float)), ("n_theta", c_int), ("lpc", c_void_p), ("flags", c_void_p)]
+
+
 class PrimePlan(Structure):
     """jlm_prime_plan (include/jlm_hip.h)."""
     _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("rows", c_void_p), ("prev", c_void_p),
@@ -169,6 +175,8 @@ _SIGS = {
     "jlm_complete_frames_masked": ([POINTER(DecodeModel), POINTER(CompletePlan), P, c_int, c_int, P, P, P], c_int),
     "jlm_rank_rows": ([P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P, P, P], c_int),
     "jlm_rank_frames": ([POINTER(DecodeModel), POINTER(RankPlan), P, P], c_int),
+    "jlm_cache_rows": ([P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P, c_int, POINTER(c_float), c_int, P, P, P], c_int),
+    "jlm_score_cache_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), POINTER(CachePlan), P, P], c_int),
     "jlm_prime_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P], c_int),
     "jlm_seed_context": ([P, P, c_int, P, P, c_int, P, c_int, c_int, c_longlong, P, P, P, P, P], c_int),
     "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,

@@ -501,7 +501,10 @@ extern "C" int jlm_seed_context(const void *src_h, const float *src_c, int H, co
 
 // Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),
 // T, the full-vocabulary normaliser as the frame loop launches it for kind 0, and the fold into -log p of the target word.
-extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
+// after_step(t, bound, h_out): called behind step t's last stamp with the state set the step wrote (jlm_score_cache_frames' copies;
+// jlm_score_frames: nothing).
+template <class AfterStep>
+static int score_loop(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events, AfterStep after_step) {
     const int R = p->n_rows, S = p->n_steps;
     if (R < 0 || S < 0 || !p->rows || !p->prev0 || !p->word || !p->target || !p->n_live || !p->nll_seq) return -1;
     if (R == 0 || S == 0) return 0;
@@ -532,8 +535,38 @@ extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan 
             JLM_TRY(jlm_score_fold(m->segs, m->n_segs, m->b2, s.T, m->ldt, p->part, R, n_parts, m->self_norm, target, ndev, bound,
                                    p->nll_seq, p->nll_tok ? p->nll_tok + (size_t)t * R : nullptr, p->flags, stream));
         JLM_TRY(stamp(t, 4));
+        JLM_TRY(after_step(t, bound, s.h_out));
     }
     return 0;
+}
+
+extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
+    return score_loop(m, p, stream, events, [](int, int, const void *) { return 0; });
+}
+
+// the refusals of jlm_cache_rows on their own (csrc/jlm_cache.hip)
+int jlm_cache_refuse(const void *hist, const int *words, int cap, int n_rows, int H, int split, float h_scale, int pos0, int n_query,
+                     const int *first, const int *len, int N, const float *thetas, int n_theta, const float *lpc);
+// the copy behind a step: rows 0 .. bound - 1 of the written state set and the step's targets into their ring slot (csrc/jlm_cache.hip)
+int jlm_cache_store(const void *h_rows, const int *target, int bound, int H, void *hist_slot, int *words_slot, void *stream);
+
+// Cached scoring (include/jlm_hip.h jlm_score_cache_frames): score_loop with the written state rows and the targets of every step
+// copied into the rings, and cache_rows_kernel once behind the last step.
+extern "C" int jlm_score_cache_frames(const jlm_decode_model *m, const jlm_score_plan *p, const jlm_cache_plan *cp, void *stream,
+                                      void *const *events) {
+    if (!cp) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    const int split = m->split_lstm ? 1 : 0;
+    JLM_TRY(jlm_cache_refuse(cp->hist, cp->words, cp->cap, R, m->H, split, m->h_scale, cp->pos0, S, cp->first, cp->len, cp->N, cp->thetas,
+                             cp->n_theta, cp->lpc));
+    const size_t row_bytes = (size_t)m->H * 4;
+    JLM_TRY(score_loop(m, p, stream, events, [&](int t, int bound, const void *h_out) -> int {
+        const size_t slot = (size_t)((cp->pos0 + t) % cp->cap);
+        return jlm_cache_store(h_out, p->target + (size_t)t * R, bound, m->H, (char *)cp->hist + slot * R * row_bytes, cp->words + slot * R, stream);
+    }));
+    if (R <= 0 || S <= 0) return 0;
+    return jlm_cache_rows(cp->hist, cp->words, cp->cap, R, m->H, split, m->h_scale, cp->pos0, S, cp->first, cp->len, cp->N, cp->thetas,
+                          cp->n_theta, cp->lpc, cp->flags, stream);
 }
 
 // Teacher-forced ranking (include/jlm_hip.h jlm_rank_frames): jlm_score_frames' loop over the live rows with the materialised logits

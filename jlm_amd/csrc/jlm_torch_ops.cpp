@@ -624,36 +624,83 @@ void tail_predict(const c10::intrusive_ptr<JlmModel> &model, const c10::intrusiv
 // flags one int32 (optional).  Every id must lie in [0, V): the caller checks (jlm_amd/score.py) -- the kernels index with them.
 // -> timed: [n_steps, 4] milliseconds per step (LSTM step, T projection, normaliser, fold) after waiting for the last step; else an
 // empty tensor and nothing waits.
+// (the checked jlm_score_plan of score_frames and score_cache_frames; live_host keeps the plan's host counts alive)
+struct ScorePlanArgs {
+    jlm_score_plan p{};
+    std::vector<int> live_host;
+    ScorePlanArgs(const char *op, const jlm_decode_model &m, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                  const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
+                  const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, const std::vector<int64_t> &n_live_host,
+                  const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t R, int64_t S)
+        : live_host(n_live_host.begin(), n_live_host.end()) {
+        auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+        auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+        check_row_sets(op, m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
+        TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
+                        is(n_live, at::kInt, S),
+                    "jlm.", op, ": int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
+        TORCH_CHECK(is(nll_seq, at::kDouble, R) && (!has(nll_tok) || is(*nll_tok, at::kDouble, S * R)) && (!has(flags) || is(*flags, at::kInt, 1)),
+                    "jlm.", op, ": float64 nll_seq [n_rows] / nll_tok [n_steps][n_rows], int32 flags");
+        TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.", op, ": T [n_rows, ldt] float32");
+        TORCH_CHECK(!has(part) || (is(*part, at::kFloat, max_parts * R * 2) && max_parts >= 1), "jlm.", op, ": part [max_parts][n_rows][2]");
+        TORCH_CHECK(!has(Tm) || (ld_tm > 0 && Tm->numel() >= ((R + 31) / 32 * 32) * ld_tm), "jlm.", op, ": Tm (whole 32-row blocks of ld_tm)");
+        p.n_rows = (int)R; p.n_steps = (int)S;
+        p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+        p.T = optr<float>(T, "T");
+        p.Tm = optr<void>(Tm, "Tm"); p.ld_tm = p.Tm ? (int)ld_tm : 0;
+        p.part = optr<float>(part, "part"); p.max_parts = p.part ? (int)max_parts : 0;
+        p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
+        p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
+        p.n_live_host = live_host.data();
+        p.nll_seq = ptr<double>(nll_seq, "nll_seq"); p.nll_tok = optr<double>(nll_tok, "nll_tok"); p.flags = optr<int>(flags, "flags");
+    }
+};
+
 Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
                     const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
                     const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host,
                     const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, S = n_steps;
+    const ScorePlanArgs sp("score_frames", m, h0, c0, h1, c1, T, Tm, ld_tm, part, max_parts, rows, prev0, word, target, n_live, n_live_host,
+                           nll_seq, nll_tok, flags, R, S);
+    return launch_frames("jlm_score_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_score_frames(&m, &sp.p, st, ev); });
+}
+
+// score_frames with the continuous cache (jlm_score_cache_frames, include/jlm_hip.h): its arguments, then the rings hist
+// [cap][n_rows][H] (4-byte values, the model's state-row format) and words [cap][n_rows] int32 with the carried entries in their slots,
+// pos0, first / len [n_rows] int32 on the device, N, thetas (host), lpc [n_theta][n_steps][n_rows] float32, cache_flags one int32.
+// -> as score_frames (the timed brackets are the scoring steps'; the cache pass runs behind the last).
+Tensor score_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                          const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
+                          const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host,
+                          const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed,
+                          const Tensor &hist, const Tensor &words, int64_t cap, int64_t pos0, const Tensor &first, const Tensor &len, int64_t N,
+                          std::vector<double> thetas, const Tensor &lpc, const OptTensor &cache_flags) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
     auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    check_row_sets("score_frames", m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
-    TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
-                    is(n_live, at::kInt, S),
-                "jlm.score_frames: int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
-    TORCH_CHECK(is(nll_seq, at::kDouble, R) && (!has(nll_tok) || is(*nll_tok, at::kDouble, S * R)) && (!has(flags) || is(*flags, at::kInt, 1)),
-                "jlm.score_frames: float64 nll_seq [n_rows] / nll_tok [n_steps][n_rows], int32 flags");
-    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.score_frames: T [n_rows, ldt] float32");
-    TORCH_CHECK(!has(part) || (is(*part, at::kFloat, max_parts * R * 2) && max_parts >= 1), "jlm.score_frames: part [max_parts][n_rows][2]");
-    TORCH_CHECK(!has(Tm) || (ld_tm > 0 && Tm->numel() >= ((R + 31) / 32 * 32) * ld_tm), "jlm.score_frames: Tm (whole 32-row blocks of ld_tm)");
-    jlm_score_plan p{};
-    p.n_rows = (int)R; p.n_steps = (int)S;
-    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
-    p.T = optr<float>(T, "T");
-    p.Tm = optr<void>(Tm, "Tm"); p.ld_tm = p.Tm ? (int)ld_tm : 0;
-    p.part = optr<float>(part, "part"); p.max_parts = p.part ? (int)max_parts : 0;
-    p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
-    p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
-    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
-    p.n_live_host = live_host.data();
-    p.nll_seq = ptr<double>(nll_seq, "nll_seq"); p.nll_tok = optr<double>(nll_tok, "nll_tok"); p.flags = optr<int>(flags, "flags");
-    return launch_frames("jlm_score_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
-                         [&](hipStream_t st, void *const *ev) { return jlm_score_frames(&m, &p, st, ev); });
+    const ScorePlanArgs sp("score_cache_frames", m, h0, c0, h1, c1, T, Tm, ld_tm, part, max_parts, rows, prev0, word, target, n_live,
+                           n_live_host, nll_seq, nll_tok, flags, R, S);
+    const int64_t n_theta = (int64_t)thetas.size();
+    TORCH_CHECK(n_theta >= 1 && n_theta <= JLM_CACHE_MAX_THETAS, "jlm.score_cache_frames: 1 .. ", JLM_CACHE_MAX_THETAS, " values of theta");
+    TORCH_CHECK(N >= 1 && cap >= N + S && cap <= INT32_MAX && pos0 >= 0 && pos0 + S + cap < INT32_MAX,
+                "jlm.score_cache_frames: N >= 1, cap >= N + n_steps, 0 <= pos0, pos0 + n_steps + cap < 2^31");
+    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
+                "jlm.score_cache_frames: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
+    TORCH_CHECK(is(first, at::kInt, R) && is(len, at::kInt, R) && is(lpc, at::kFloat, n_theta * S * R) &&
+                    (!has(cache_flags) || is(*cache_flags, at::kInt, 1)),
+                "jlm.score_cache_frames: int32 first / len [n_rows], float32 lpc [n_theta][n_steps][n_rows], int32 cache_flags");
+    std::vector<float> th(thetas.begin(), thetas.end());
+    jlm_cache_plan cp{};
+    cp.hist = ptr<void>(hist, "hist"); cp.words = ptr<int>(words, "words"); cp.cap = (int)cap; cp.pos0 = (int)pos0;
+    cp.first = ptr<const int>(first, "first"); cp.len = ptr<const int>(len, "len"); cp.N = (int)N;
+    cp.thetas = th.data(); cp.n_theta = (int)n_theta;
+    cp.lpc = ptr<float>(lpc, "lpc"); cp.flags = optr<int>(cache_flags, "cache_flags");
+    return launch_frames("jlm_score_cache_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_score_cache_frames(&m, &sp.p, &cp, st, ev); });
 }
 
 // The level table of jlm_rank_rows as tensors, checked: ids [n_ids], lv_off [n_cols + 1], lv_lo / lv_hi of one length, all int32 on the
@@ -1179,6 +1226,12 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
           "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed) -> Tensor",
           score_frames);
+    m.def("score_cache_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
+          "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed, "
+          "Tensor(k!) hist, Tensor(l!) words, int cap, int pos0, Tensor first, Tensor len, int N, float[] thetas, Tensor(m!) lpc, "
+          "Tensor(n!)? cache_flags) -> Tensor",
+          score_cache_frames);
     m.def("rank_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, Tensor target, Tensor? ids, Tensor? lv_off, Tensor? lv_lo, "
           "Tensor? lv_hi, int n_levels, Tensor(a!) rank, Tensor(b!)? flags) -> ()",
           rank_rows);

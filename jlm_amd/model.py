@@ -959,6 +959,24 @@ class LSTM_Model():
         _seq, tok, h2, c2 = self._scorer().run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
         return np.ascontiguousarray(tok.T), h2, c2
 
+    def score_streams_cached(self, inputs, targets, cache, h=None, c=None, state=None):
+        """score_streams with a continuous cache (jlm_amd/cache.py): ``cache`` a :class:`jlm_amd.cache.CacheSpec`
+        (N entries, one theta or up to 16 for tuning, lam), ``state`` the :class:`jlm_amd.cache.CacheState` an earlier call of the
+        stream returned (None: an empty cache, the stream starts here).  -> :class:`jlm_amd.cache.CachedScores`: ``nll_lm`` [B, n]
+        (score_streams' result, bit for bit), ``logp_cache`` [n_theta, B, n], ``n_entries`` [B, n], ``.nll(lam, theta_index)`` the
+        mixture in float64, and ``h``, ``c``, ``state`` to carry.  Cut a stream any way into calls: the cache of a position is the same
+        entries.  ValueError before anything runs for a bad argument or a state of another model or row count; JlmHipError when a
+        hidden state is not finite."""
+        from .cache import score_streams_cached
+        return score_streams_cached(self._scorer(), inputs, targets, cache, h, c, state)
+
+    def score_cached(self, sequences, start, cache, max_rows=None):
+        """score() with a continuous cache: -> one float64 array per sequence of the per-word mixed -log p at ``cache.lam`` and the
+        first theta of ``cache``.  Every sequence starts with an empty cache; the row plan is score()'s, with the cache's rings --
+        (N + n) H 4 bytes a row -- counted into the rows of a call."""
+        from .cache import score_cached
+        return score_cached(self._scorer(), sequences, start, cache, max_rows)
+
     def _ranker(self):
         from .rank import Ranker
         return self._driver(Ranker)

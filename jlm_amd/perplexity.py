@@ -17,6 +17,11 @@ after every line; a character model (config char_rnn) reads the characters of th
                    LSTM_Model.rank / rank_streams (jlm_amd/rank.py): top-k accuracy (--top), mean reciprocal rank, keystroke
                    savings of a candidate list of --list words, and the position of the word among its homophones.  A character
                    model reports the first two only.  Without --ranks nothing of this runs.
+  --cache N        stream mode: also score with a continuous cache of the last N (hidden state, next word) pairs of every stream
+                   (jlm_amd/cache.py) at --theta and --lam, in ONE pass -- LSTM_Model.score_streams_cached returns the plain -log p
+                   as well -- and print the cached perplexity after the plain one.  --tune-cache FILE sweeps --thetas and --lams on
+                   FILE, the dev set, prints the grid's best pair and reports the test perplexity at that pair.  Without --cache the
+                   output is what it was.
 """
 import argparse
 import os
@@ -74,6 +79,38 @@ def stream_perplexity(model, stream, batch_size, num_steps):
     return float(np.exp(total / n_tok)), total, n_tok
 
 
+def stream_cached_scores(model, stream, batch_size, num_steps, spec):
+    """-> the :class:`jlm_amd.cache.CachedScores` of every corpus_iterator chunk, state and cache carried, as stream_perplexity"""
+    from .score import stream_layout
+    x, y = stream_layout(stream, batch_size, num_steps)
+    h = c = state = None
+    out = []
+    for i in range(x.shape[1] // num_steps):
+        cols = slice(i * num_steps, (i + 1) * num_steps)
+        res = model.score_streams_cached(x[:, cols], y[:, cols], spec, h, c, state)
+        h, c, state = res.h, res.c, res.state
+        out.append(res)
+    return out
+
+
+def cached_perplexity(parts, lam, theta_index=0):
+    """-> (plain perplexity, cached perplexity, number of tokens) of a list of CachedScores; the plain one is stream_perplexity's sum"""
+    total = mixed = 0.0
+    n_tok = 0
+    for p in parts:
+        total += float(p.nll_lm.sum())
+        mixed += float(p.nll(lam, theta_index).sum())
+        n_tok += p.nll_lm.size
+    return float(np.exp(total / n_tok)), float(np.exp(mixed / n_tok)), n_tok
+
+
+def _floats(text, what, ap):
+    try:
+        return [float(x) for x in text.split(",") if x.strip()]
+    except ValueError:
+        ap.error("%s takes comma-separated numbers" % what)
+
+
 def sentence_ranks(model, sents, eos, readings, max_prefix):
     """-> (ranks [tokens, columns], the targets [tokens]) of every line on its own, as sentence_perplexity scores them"""
     ranks = model.rank(sents, eos, readings=readings, max_prefix=max_prefix)
@@ -124,7 +161,28 @@ def main(argv=None):
     ap.add_argument("--top", default="1,5,10", help="--ranks: the k of top-k accuracy, comma-separated")
     ap.add_argument("--list", type=int, default=5, dest="list_size", help="--ranks: words in the candidate list of the keystroke figure")
     ap.add_argument("--max_prefix", type=int, default=8, help="--ranks: typed kana up to which a word is looked for in the list")
+    ap.add_argument("--cache", type=int, default=0, metavar="N", help="stream mode: also report the perplexity with a continuous cache of N entries")
+    ap.add_argument("--theta", type=float, default=0.3, help="--cache: the flatness of the cache distribution")
+    ap.add_argument("--lam", type=float, default=0.1, help="--cache: the weight of the cache in the mixture")
+    ap.add_argument("--tune-cache", default=None, metavar="FILE", dest="tune_cache",
+                    help="--cache: sweep --thetas x --lams on FILE (the dev set) and report the test perplexity at the best pair")
+    ap.add_argument("--thetas", default=",".join("%.1f" % (0.1 * i) for i in range(11)), help="--tune-cache: the thetas of the grid")
+    ap.add_argument("--lams", default=",".join("%.2f" % (0.05 * i) for i in range(20)), help="--tune-cache: the lams of the grid")
     args = ap.parse_args(argv)
+    spec = tune_spec = None
+    if args.cache or args.tune_cache:
+        from .cache import CacheSpec, check_lam
+        if args.mode != "stream" or args.cache < 1:
+            ap.error("--cache N (N >= 1) and --tune-cache work in stream mode")
+        try:
+            spec = CacheSpec(args.cache, args.theta, args.lam)
+            if args.tune_cache:
+                tune_lams = [check_lam(x) for x in _floats(args.lams, "--lams", ap)]
+                if not tune_lams:
+                    ap.error("--lams is empty")
+                tune_spec = CacheSpec(args.cache, _floats(args.thetas, "--thetas", ap))
+        except ValueError as e:
+            ap.error(str(e))
     tops = [int(k) for k in args.top.split(",") if k.strip()]
     if args.ranks and (not tops or min(tops) < 1 or args.list_size < 1):
         ap.error("--top and --list take integers >= 1")
@@ -139,10 +197,26 @@ def main(argv=None):
     else:
         bs = args.batch_size or int(config.get("batch_size", 64))
         stream = [i for s in sents for i in s]
-        pp, _total, n_tok = stream_perplexity(model, stream, bs, args.num_steps)
+        if spec is None:
+            pp, _total, n_tok = stream_perplexity(model, stream, bs, args.num_steps)
+        else:
+            if tune_spec is not None:
+                from .cache import tune
+                dev_sents, _n = encode_lines(read_lines(args.tune_cache), vocab)
+                dev_parts = stream_cached_scores(model, [i for s in dev_sents for i in s], bs, args.num_steps, tune_spec)
+                best_theta, best_lam = tune(dev_parts, tune_lams)
+                dev_pp = cached_perplexity(dev_parts, best_lam, tune_spec.thetas.index(best_theta))
+                spec = CacheSpec(args.cache, best_theta, best_lam)
+                t0 = time.time()
+            pp, cached_pp, n_tok = cached_perplexity(stream_cached_scores(model, stream, bs, args.num_steps, spec), spec.lam)
     dt = time.time() - t0
     print("tokens: {}  <unk>: {}  tokens/s: {:.0f}".format(n_tok, n_unk, n_tok / dt if dt > 0 else float("inf")))
     print("Test perplexity: {}".format(pp))
+    if tune_spec is not None:
+        print("Cache tuned on {}: theta {} lam {}  (dev perplexity {} -> {} over {} x {} pairs)".format(
+            args.tune_cache, spec.theta, spec.lam, dev_pp[0], dev_pp[1], len(tune_spec.thetas), len(tune_lams)))
+    if spec is not None:
+        print("Test perplexity with cache (N {} theta {} lam {}): {}".format(spec.size, spec.theta, spec.lam, cached_pp))
     if args.ranks:
         readings = not isinstance(vocab, CharVocab)
         if args.mode == "sentence":

@@ -77,14 +77,21 @@ class Scorer:
         self.torch = dev_model.torch
         self.last_step_ms = None          # [n_steps, 4] of the last timed call: LSTM step, T projection, normaliser, fold
 
-    def row_bytes(self, n_steps, per_token=True):
+    def row_bytes(self, n_steps, per_token=True, cache_size=0, n_theta=1):
+        """bytes of a call's buffers per row; cache_size = N > 0: with the rings of a cached call, (N + n) state rows and words, and
+        its lpc (jlm_amd/cache.py)"""
         m = self.m
         n_parts = 0 if m.self_norm else max(m.n_vocab_tiles, 1)
-        return (4 * m.H + m.ldt + (m.ld_tm or 0)) * 4 + n_parts * 8 + 16 + n_steps * (8 + (8 if per_token else 0))
+        plain = (4 * m.H + m.ldt + (m.ld_tm or 0)) * 4 + n_parts * 8 + 16 + n_steps * (8 + (8 if per_token else 0))
+        if not cache_size:
+            return plain
+        return plain + (cache_size + n_steps) * (m.H * 4 + 4) + 4 * n_theta * n_steps + 8
 
-    def run(self, word, target, n_live, h=None, c=None, per_token=True, timed=False):
+    def run(self, word, target, n_live, h=None, c=None, per_token=True, timed=False, rings=None):
         """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
         the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
+        rings: a :class:`jlm_amd.cache.Rings` made for this call's (R, n_steps) -- the op is then ``score_cache_frames``, the same
+        launches with the cache pass behind them, and the rings hold the call's states, words and lpc afterwards.
         -> (nll_seq [R] f64, nll_tok [n_steps, R] f64 or None, h, c) -- numpy results, the state after the last step on the device."""
         torch, m = self.torch, self.m
         word = np.ascontiguousarray(word, dtype=np.int32)
@@ -116,8 +123,12 @@ class Scorer:
             nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
             nll_seq = torch.zeros(R, device=dev, dtype=f64)
             nll_tok = torch.zeros((S, R), device=dev, dtype=f64) if per_token else None
-            ms = _ops.backend().score_frames(m.decode_model(), *rs.state(), Tm, int(m.ld_tm or 0), part, n_parts, rs.rows, prev0, wd, tg,
-                                             nl, n_live, nll_seq, nll_tok, rs.flags, R, S, bool(timed))
+            args = (m.decode_model(), *rs.state(), Tm, int(m.ld_tm or 0), part, n_parts, rs.rows, prev0, wd, tg, nl, n_live, nll_seq, nll_tok,
+                    rs.flags, R, S, bool(timed))
+            if rings is None:
+                ms = _ops.backend().score_frames(*args)
+            else:
+                ms = _ops.backend().score_cache_frames(*args, *rings.op_args(R, S))
             if timed:
                 self.last_step_ms = ms.numpy()
             rs.check_flags("score_fold_kernel flagged a target outside the model's segments (flags %d)",
