@@ -96,7 +96,8 @@ class Ranker:
         """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
         the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
         levels: a :class:`Levels`, None = level A only.  -> (rank [n_steps, R, n_levels + 1] int32 in the device's column order, -1
-        where a row is not live, h, c) -- the state after the last step stays on the device."""
+        where a row is not live, h, c) -- the state after the last step stays on the device; as in Scorer.run, only the rows live
+        at the last step are defined in it."""
         torch, m = self.torch, self.m
         word = np.ascontiguousarray(word, dtype=np.int32)
         target = np.ascontiguousarray(target, dtype=np.int32)

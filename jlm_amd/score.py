@@ -92,7 +92,10 @@ class Scorer:
         the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
         rings: a :class:`jlm_amd.cache.Rings` made for this call's (R, n_steps) -- the op is then ``score_cache_frames``, the same
         launches with the cache pass behind them, and the rings hold the call's states, words and lpc afterwards.
-        -> (nll_seq [R] f64, nll_tok [n_steps, R] f64 or None, h, c) -- numpy results, the state after the last step on the device."""
+        -> (nll_seq [R] f64, nll_tok [n_steps, R] f64 or None, h, c) -- numpy results, the state after the last step on the device.
+        The returned h, c are the row set the LAST step wrote: they hold the final state of the rows live at that step.  A row that
+        stopped being live earlier is UNDEFINED there (its final state is in the other set when its length and n_steps differ in
+        parity, and its slot here is unwritten or one step old): ragged callers do not carry a state."""
         torch, m = self.torch, self.m
         word = np.ascontiguousarray(word, dtype=np.int32)
         target = np.ascontiguousarray(target, dtype=np.int32)
