@@ -1027,6 +1027,113 @@ int jlm_score_cache_frames(const jlm_decode_model *model_host, const jlm_score_p
                            void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
+ * The continuous cache on the decode side: the cache distribution over EVERY word of the window, as a patch of a row's materialised
+ * logits (csrc/jlm_cache_mix.hip, jlm_amd/cache.py cache_distribution / mixed_logits).  Additive to ABI 12.
+ *
+ * Positions, rings, window and s_i are those of jlm_cache_rows above: the window of position q is max(q - N, first) <= i < q with n_q
+ * entries, s_i = theta * (h_q . h_i) with h in real units.  For every word w
+ *   c_q(w)  = sum_{i in window, w_i = w} exp(s_i) / sum_{i in window} exp(s_i)                     (0 when no i matches)
+ *   p_q(w)  = (1 - lambda) p_lm(w) + lambda c_q(w)   when n_q > 0 and lambda > 0;   p_lm(w) otherwise
+ *   p_lm(w) = exp(y[w] - L),  L = lse(y) over the row; self-normalised models: L = 0 (as score_fold_kernel defines nll there)
+ * With rho = lambda / (1 - lambda), ordering by p_q is ordering by
+ *   y'[w]   = logaddexp(y[w], L + log rho + log c_q(w))  for the words of the window;   y'[w] = y[w], the same bits, for every other
+ * and lse(y') = L - log(1 - lambda): jlm_topk_rows' nll over the patched row is -log p_q(w) on ordinary models; on self-normalised
+ * models the host adds -log1p(-lambda).  One theta and one lambda a call.  Rank and top-k order stay jlm_rank_rows' / jlm_topk_rows'.
+ *
+ * jlm_cache_query (cache_query_kernel): one query per row -- row r < min(*n_dev, n_rows_max) (n_dev NULL: n_rows_max) of q_rows
+ * [.. n_rows_max][H], the state rows a step just wrote, in the rings' state-row format -- against that row's window at position
+ * `pos` in hist [cap][n_rows][H] (slot = position mod cap; cap >= N, n_rows_max <= n_rows; first [n_rows] device).  Writes
+ *   s[r * ld_s + j] = f32(theta' * dot),  j < n_q: window entry j, OLDEST first (position max(pos - N, first[r], 0) + j)
+ * and nothing else: entries j >= n_q, rows that are not live and the rows of an empty window are left as they are.  ld_s >= N.
+ * Arithmetic: split rows are decoded as f32(hi) + f32(lo) with 1 / h_scale^2 folded into theta; four lanes a key, each an f32 fmaf
+ * chain in k order over the 8-value units u = lane, lane + 4, ... of the row, folded (a0 + a1) + (a2 + a3).  The bits of s[r][j] are
+ * a function of the pair (h_q, h_i), H and theta alone: not of pos, cap, wrap-around, n_rows or where the key falls in the launch.
+ * flags (one device int, may be NULL): |= 1 when an s inside a window is not finite.
+ * Returns -1 before any launch for N < 1 or N > JLM_CACHE_MIX_MAX_N, cap < N, ld_s < N, n_rows_max outside [0, min(n_rows, 65535)],
+ * H <= 0 or H % 32 != 0, theta negative or not finite, split != 0 with h_scale <= 0, pos < 0 or pos + cap >= 2^31, hist / q_rows NULL
+ * or not 16-byte aligned, first / s NULL, or any of first / s / n_dev / flags not 4-byte aligned; 0 with nothing launched for
+ * n_rows_max == 0; else 0 or a hipError_t. */
+#define JLM_CACHE_MIX_MAX_N 4096
+int jlm_cache_query(const void *hist, int cap, int n_rows, int H, int split, float h_scale, const void *q_rows, int n_rows_max,
+                    const int *n_dev, int pos, const int *first, int N, float theta, float *s, int ld_s, int *flags, void *stream);
+
+/* jlm_cache_mix_rows (cache_mix_rows_kernel, one workgroup of 256 threads per live row, 12 N bytes of LDS): rewrites, in place, row
+ * r < min(*n_dev, n_rows_max) of the f32 logits y[r * ld_y + 0 .. n_cols) (jlm_topk_rows' conditions on y) into y' of the definition
+ * above, from the row's scores s[r * ld_s + 0 .. n_q) (jlm_cache_query's) and the window's words in words [cap][n_rows] at `pos`.
+ * Arithmetic: max, e_j = expf(s_j - max) and Z = sum e_j in a fixed tree over j; c(w) = the f32 sum of e_j over the entries with
+ * w_j = w in ascending j, formed at the FIRST occurrence of w in the window (one writer per word, no atomics); L as jlm_topk_rows
+ * forms its lse (f32 expf, f64 sums, its order), rounded to f32, 0 on self_norm models;
+ *   y'[w] = logaddexp_f32(y[w], (L + logf(rho)) + (logf(c) - logf(Z)))      y[w] = -inf: the cache term itself
+ * y' is a function of the window's contents in order (s_j, w_j), the row and lambda alone: the same bits for any cut of a stream, any
+ * pos / cap / wrap-around and whatever else the launch carries.  Every word outside the window keeps its bits.
+ * lpc_ent (may be NULL) [.. n_rows_max][ld_s]: logf(c(w_j)) - logf(Z) at j when entry j is the first occurrence of its word, -inf
+ * at a repeat; written for the rows that are patched, j < n_q.
+ * flags (one device int, may be NULL): |= 1 a row whose window holds an s that is not finite, |= 2 a row whose L is not finite (a
+ * NaN or +inf logit, or none above -inf): such a row is left exactly as it is.  |= 4 a window word outside [0, n_cols): the entry
+ * counts in Z, patches nothing, and nothing is indexed by it; the row's other words are patched.  A NaN y[w] stays NaN.
+ * lambda == 0 launches nothing; an empty window leaves the row's bits.
+ * Returns -1 before any launch for lambda outside [0, 1), the conditions of jlm_cache_query on N, cap, ld_s, n_rows_max, pos, first,
+ * n_dev and flags, jlm_topk_rows' on y / ld_y / n_cols, s or words NULL, or s / words / lpc_ent not 4-byte aligned; else 0 or a
+ * hipError_t. */
+int jlm_cache_mix_rows(float *y, int ld_y, int n_cols, int self_norm, const float *s, int ld_s, const int *words, int cap, int n_rows,
+                       int n_rows_max, const int *n_dev, int pos, const int *first, int N, float lam, float *lpc_ent, int *flags,
+                       void *stream);
+
+/* What a cached ranking call has beside its jlm_rank_plan (whose layout is unchanged): the rings of jlm_cache_rows over the plan's
+ * n_rows rows, step t of the plan being position pos0 + t; cap >= N (the slot a step writes left every later window N steps ago). */
+typedef struct {
+    void *hist; int *words; int cap;    /* the rings; the entries carried into the call are in their slots already */
+    int pos0;                           /* the position of step 0 */
+    const int *first;                   /* [n_rows] device */
+    int N;
+    float theta, lam;
+    float *s; int ld_s;                 /* [n_rows][ld_s] device scratch: the scores of one step, ld_s >= N */
+    int top_k;                          /* 0: no lists */
+    int *top_ids; double *top_nll;      /* [n_steps][n_rows][top_k] device: jlm_topk_rows over the patched rows of every step */
+    int *flags;                         /* one device int or NULL: the bits of jlm_cache_query / jlm_cache_mix_rows */
+} jlm_cache_mix_plan;
+
+/* jlm_rank_frames' loop -- the same launches in the same order -- with, per step, between the logit GEMMs and the ranking,
+ * jlm_cache_query on the state set the step wrote at position pos0 + t and jlm_cache_mix_rows on the logits, so that rank_rows_kernel
+ * ranks target[t] under the mixed distribution; behind the ranking, with top_k > 0, jlm_topk_rows over the n_live_host[t] live rows
+ * into top_ids / top_nll (n_live_host is required then; its flags go to the rank plan's), and jlm_cache_store of the written state
+ * rows and the step's targets into slot (pos0 + t) mod cap: the rings hold what jlm_score_cache_frames would have put there.
+ * No host synchronisation.  Every refusal of the two launchers (at the call's last position), top_k outside 0 .. min(JLM_TOPK_MAX,
+ * V), and an n_live_host[t] outside [0, n_rows] is returned before the first launch.  events (may be NULL):
+ * JLM_RANK_CACHE_EVENTS_PER_STEP * n_steps hipEvent_t, [0] .. [3] as jlm_rank_frames', [4] after the query, [5] after the patch,
+ * [6] after the ranking, the lists and the ring write.  Returns as jlm_rank_frames does. */
+#define JLM_RANK_CACHE_EVENTS_PER_STEP 7
+int jlm_rank_cache_frames(const jlm_decode_model *model_host, const jlm_rank_plan *plan_host, const jlm_cache_mix_plan *cache_host,
+                          void *stream, void *const *events);
+
+/* One step of prediction under the cache, for a caller who holds the carried state of n_rows streams and their rings. */
+typedef struct {
+    int n_rows;
+    const void *h;                      /* [n_rows, H] the carried state rows, in the model's state-row format */
+    float *T;                           /* [n_rows, ldt] f32 scratch (an untied f32 model: unused, T is h) */
+    float *logits; int ld_logits;       /* [n_rows, ld_logits] f32 scratch, ld_logits >= V rounded up to 4 */
+    const int *rows;                    /* [n_rows] device: 0, 1, ..., n_rows - 1 */
+    const void *hist; const int *words; int cap;    /* the rings [cap][n_rows][..] */
+    int pos;                            /* the position of the streams' next step */
+    const int *first;                   /* [n_rows] device */
+    int N;
+    float theta, lam;
+    float *s; int ld_s;                 /* [n_rows][ld_s] device scratch */
+    int k;                              /* 1 .. min(JLM_TOPK_MAX, V) */
+    const unsigned *mask; int ld_mask, n_sets; const int *row_set;    /* jlm_topk_rows_masked's; row_set NULL: jlm_topk_rows */
+    int *ids; double *nll;              /* [n_rows][k] device */
+    int *flags;                         /* one device int or NULL: the selection's */
+    int *cache_flags;                   /* one device int or NULL: the bits of jlm_cache_query / jlm_cache_mix_rows */
+} jlm_predict_cache_plan;
+
+/* Enqueues the T projection of h, the logit GEMMs, jlm_cache_query at pos, jlm_cache_mix_rows and jlm_topk_rows (row_set: _masked):
+ * ids / nll are the k best words of every row under the mixed distribution (self_norm models: the host adds -log1p(-lambda) where
+ * the window is not empty).  No LSTM step, no ring write, no host synchronisation; every refusal before the first launch.  Returns
+ * -2 for an untied split-row model -- its vocabulary GEMMs read the f32 copy of the state that only the LSTM step writes -- and
+ * otherwise as the launchers do. */
+int jlm_predict_cache_rows(const jlm_decode_model *model_host, const jlm_predict_cache_plan *plan_host, void *stream);
+
+/* ------------------------------------------------------------------------
  * Left context of a decode (LSTM_Model.prime, Decoder.decode(context=), jlm_amd/context.py).  Sentence s with the committed words
  * ctx_s has the history hist = [<eos>] + ctx_s; its decode is the reference's with the root hypothesis consuming hist[-1] from the
  * state reached by consuming hist[:-1] from the zero state.

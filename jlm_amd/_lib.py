@@ -97,6 +97,22 @@ class CachePlan(Structure):
                 ("N", c_int), ("thetas", POINTER(c_float)), ("n_theta", c_int), ("lpc", c_void_p), ("flags", c_void_p)]
 
 
+class CacheMixPlan(Structure):
+    """jlm_cache_mix_plan (include/jlm_hip.h)."""
+    _fields_ = [("hist", c_void_p), ("words", c_void_p), ("cap", c_int), ("pos0", c_int), ("first", c_void_p), ("N", c_int),
+                ("theta", c_float), ("lam", c_float), ("s", c_void_p), ("ld_s", c_int), ("top_k", c_int), ("top_ids", c_void_p),
+                ("top_nll", c_void_p), ("flags", c_void_p)]
+
+
+class PredictCachePlan(Structure):
+    """jlm_predict_cache_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_rows", c_int), ("h", c_void_p), ("T", c_void_p), ("logits", c_void_p), ("ld_logits", c_int), ("rows", c_void_p),
+                ("hist", c_void_p), ("words", c_void_p), ("cap", c_int), ("pos", c_int), ("first", c_void_p), ("N", c_int),
+                ("theta", c_float), ("lam", c_float), ("s", c_void_p), ("ld_s", c_int), ("k", c_int), ("mask", c_void_p),
+                ("ld_mask", c_int), ("n_sets", c_int), ("row_set", c_void_p), ("ids", c_void_p), ("nll", c_void_p), ("flags", c_void_p),
+                ("cache_flags", c_void_p)]
+
+
 class PrimePlan(Structure):
     """jlm_prime_plan (include/jlm_hip.h)."""
     _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("rows", c_void_p), ("prev", c_void_p),
@@ -177,6 +193,10 @@ _SIGS = {
     "jlm_rank_frames": ([POINTER(DecodeModel), POINTER(RankPlan), P, P], c_int),
     "jlm_cache_rows": ([P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P, c_int, POINTER(c_float), c_int, P, P, P], c_int),
     "jlm_score_cache_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), POINTER(CachePlan), P, P], c_int),
+    "jlm_cache_query": ([P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_int, P, c_int, c_float, P, c_int, P, P], c_int),
+    "jlm_cache_mix_rows": ([P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, c_int, c_float, P, P, P], c_int),
+    "jlm_rank_cache_frames": ([POINTER(DecodeModel), POINTER(RankPlan), POINTER(CacheMixPlan), P, P], c_int),
+    "jlm_predict_cache_rows": ([POINTER(DecodeModel), POINTER(PredictCachePlan), P], c_int),
     "jlm_prime_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P], c_int),
     "jlm_seed_context": ([P, P, c_int, P, P, c_int, P, c_int, c_int, c_longlong, P, P, P, P, P], c_int),
     "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,

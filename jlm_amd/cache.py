@@ -18,6 +18,16 @@ lpc does not depend on lam, so lam is swept on the host from one device pass (:f
 
 ``LSTM_Model.score_cached`` / ``score_streams_cached`` (jlm_amd/model.py) are the public entry points, ``python -m jlm_amd.perplexity
 --cache`` the command-line front end.
+
+Ranking and prediction need the cache's mass on EVERY word of the window, not the target's alone:
+
+    c_q(w) = sum_{i in window, w_i = w} exp(s_i) / sum_{i in window} exp(s_i)
+    p_q(w) = (1 - lam) p_lm(w) + lam c_q(w)  when n_q > 0 and lam > 0;  p_lm(w) otherwise;  p_lm(w) = exp(y[w] - L), L = lse(y) (self_norm: 0)
+    y'[w]  = logaddexp(y[w], L + log(lam / (1 - lam)) + log c_q(w))  on the words of the window,  y[w] elsewhere
+
+-- ordering by y' is ordering by p_q, and lse(y') = L - log(1 - lam).  :func:`cache_distribution` and :func:`mixed_logits` state it
+in float64; on the device ``torch.ops.jlm.rank_cache_frames`` patches every step's logits (csrc/jlm_cache_mix.hip) before
+``rank_rows_kernel`` / ``topk_rows_kernel`` read them: ``LSTM_Model.rank_streams_cached`` / ``rank_cached`` / ``predict_next_cached``.
 """
 import numpy as np
 
@@ -102,6 +112,52 @@ def mix_nll(nll_lm, lpc, n_entries, lam):
     with np.errstate(invalid="ignore"):
         mixed = -np.logaddexp(np.log1p(-lam) - nll, np.log(lam) + np.asarray(lpc, dtype=np.float64))
     return np.where(np.asarray(n_entries) > 0, mixed, nll)
+
+
+def cache_distribution(h, words, size, theta, V, carried=0):
+    """The cache distribution over EVERY word, for ONE row, in float64 (include/jlm_hip.h jlm_cache_query / jlm_cache_mix_rows,
+    DESIGN.md section 20).  ``h`` [n, H], ``words`` [n], ``carried`` as :func:`cache_log_probs` takes them; one ``theta``.
+    -> (c [n - carried, V] float64: c_q(w) = sum_{i in window, w_i = w} exp(s_i) / sum_{i in window} exp(s_i), a row of zeros where the
+    window is empty; n_entries [n - carried]).  log c_q(w_q) is lpc_q of :func:`cache_log_probs`."""
+    h = np.asarray(h, dtype=np.float64)
+    w = np.asarray(words, dtype=np.int64)
+    n = len(w)
+    if n and (w.min() < 0 or w.max() >= V):
+        raise ValueError("a cached word is outside [0, %d)" % V)
+    c = np.zeros((n - carried, V))
+    cnt = np.zeros(n - carried, dtype=np.int64)
+    for q in range(carried, n):
+        lo = max(q - size, 0)
+        cnt[q - carried] = q - lo
+        if q == lo:
+            continue
+        s = float(theta) * (h[lo:q] @ h[q])
+        e = np.exp(s - s.max())
+        np.add.at(c[q - carried], w[lo:q], e)
+        c[q - carried] /= e.sum()
+    return c, cnt
+
+
+def mixed_logits(y, c, lam, self_norm=False):
+    """y' of the definition, float64: rows ``y`` [..., V] of logits and ``c`` [..., V] of :func:`cache_distribution` ->
+    logaddexp(y, L + log(lam / (1 - lam)) + log c) where c > 0 and y where c = 0, L = lse(y) over the row (``self_norm``: 0).  Ordering
+    a row by y' is ordering it by p = (1 - lam) p_lm + lam c, and lse(y') = L - log(1 - lam).  lam = 0 and a row whose c is all zero (an
+    empty window) return y's bits."""
+    lam = check_lam(lam)
+    y = np.asarray(y, dtype=np.float64)
+    c = np.asarray(c, dtype=np.float64)
+    if y.shape != c.shape:
+        raise ValueError("y and c must have the same shape (got %s, %s)" % (y.shape, c.shape))
+    if lam == 0.0:
+        return y.copy()
+    if self_norm:
+        L = np.zeros(y.shape[:-1] + (1,))
+    else:
+        top = y.max(axis=-1, keepdims=True)
+        L = top + np.log(np.exp(y - top).sum(axis=-1, keepdims=True))
+    with np.errstate(divide="ignore", invalid="ignore"):          # (log 0 = -inf where c = 0: those entries are y's)
+        term = L + (np.log(lam) - np.log1p(-lam)) + np.log(c)
+        return np.where(c > 0, np.logaddexp(y, term), y)
 
 
 # ---------------------------------------------------------------------------------------------------------------- device side
@@ -249,6 +305,240 @@ def score_cached(scorer, sequences, start, cache, max_rows=None):
             L = int(ch["lens"][r])
             out[i] = mix_nll(tok[:L, r], lpc[0, :L, r], n_entries[:L], spec.lam)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- ranking and prediction
+MIX_MAX_SIZE = 4096                 # JLM_CACHE_MIX_MAX_N
+
+
+def _check_mix_spec(cache):
+    """a CacheSpec the mixing loop takes: one theta (a rank depends on lam and theta both) and size <= 4096"""
+    spec = _check_spec(cache)
+    if len(spec.thetas) != 1:
+        raise ValueError("ranking and prediction under the cache take one theta a call (got %d)" % len(spec.thetas))
+    if spec.size > MIX_MAX_SIZE:
+        raise ValueError("ranking and prediction under the cache take a cache of at most %d entries (got %d)" % (MIX_MAX_SIZE, spec.size))
+    return spec
+
+
+def _check_state(m, state, B):
+    if state is not None:
+        if not isinstance(state, CacheState) or state.m is not m:
+            raise ValueError("this cache state belongs to another model")
+        if state.n_rows != B:
+            raise ValueError("this cache state holds %d streams, the call has %d" % (state.n_rows, B))
+
+
+def _flag_error(fl):
+    if fl & 1:
+        return _lib.JlmHipError("cache_query_kernel flagged a product h_q . h_i that is not finite: a hidden state is NaN or inf")
+    if fl & 2:
+        return _lib.JlmHipError("cache_mix_rows_kernel flagged a row whose log-normaliser is not finite")
+    return _lib.JlmHipError("cache_mix_rows_kernel flagged a cached word outside the vocabulary (flags %d)" % fl)
+
+
+class MixRings:
+    """The rings of one cached ranking call of R rows and S steps (jlm_cache_mix_plan): :class:`Rings`' layout -- cap = N + S slots,
+    the carried entries at the local positions 0 .. carried - 1, ``first`` 0 -- with the scratch ``s`` [R, N] of one step's scores in
+    lpc's place, and ``top`` > 0 the lists top_ids / top_nll [S, R, top] of every step."""
+
+    def __init__(self, m, spec, R, S, state=None, top=0):
+        torch, dev = m.torch, m.device
+        self.m, self.spec, self.R, self.S, self.top = m, spec, R, S, int(top)
+        N = spec.size
+        self.carried = min(state.count, N) if state is not None else 0
+        self.cap = N + S
+        with m._ctx():
+            # (no uninitialised memory here: the carried entries and zeros behind them in one pass -- every slot is written before
+            #  it is read, DESIGN.md section 19, and the fill is the S + N - carried slots the copy of the carried entries leaves)
+            rest = self.cap - self.carried
+            self.hist = torch.zeros((rest, R, m.H), device=dev, dtype=torch.float32)
+            self.words = torch.zeros((rest, R), device=dev, dtype=torch.int32)
+            if self.carried:
+                self.hist = torch.cat([state.hist[state.count - self.carried:].view(torch.float32), self.hist])
+                self.words = torch.cat([state.words[state.count - self.carried:], self.words])
+            self.first = torch.zeros(R, device=dev, dtype=torch.int32)
+            self.s = torch.zeros((R, N), device=dev, dtype=torch.float32)
+            self.top_ids = torch.full((S, R, self.top), -1, device=dev, dtype=torch.int32) if self.top else None
+            self.top_nll = torch.full((S, R, self.top), float("nan"), device=dev, dtype=torch.float64) if self.top else None
+            self.flags = torch.zeros(1, device=dev, dtype=torch.int32)
+
+    @staticmethod
+    def row_bytes(H, N, S, top):
+        return (N + S) * (4 * H + 4) + 4 * N + 12 * S * top
+
+    def op_args(self, R, S):
+        if (R, S) != (self.R, self.S):
+            raise ValueError("these rings were made for %d rows and %d steps (got %d, %d)" % (self.R, self.S, R, S))
+        return (self.hist, self.words, self.cap, self.carried, self.first, self.spec.size, self.spec.theta, self.spec.lam, self.s,
+                self.spec.size, self.top, self.top_ids, self.top_nll, self.flags)
+
+    def check(self):
+        fl = int(self.flags.cpu()[0])
+        if fl:
+            raise _flag_error(fl)
+
+    def n_entries(self):
+        """[S]: the entries of a live row's window at each step"""
+        return np.minimum(self.carried + np.arange(self.S, dtype=np.int64), self.spec.size)
+
+    def lists(self, self_norm):
+        """(top_ids [S, R, top] int64, top_logp [S, R, top] float64 = log p_q under the mixture) -- after the op"""
+        ids = self.top_ids.cpu().numpy().astype(np.int64)
+        logp = -self.top_nll.cpu().numpy()
+        if self_norm and self.spec.lam > 0:                # y' orders as p_q does; exp(y') sums to 1 / (1 - lam) where the cache has entries
+            logp = logp + np.where(self.n_entries() > 0, np.log1p(-float(np.float32(self.spec.lam))), 0.0)[:, None, None]
+        return ids, logp
+
+    def state_after(self, pos):
+        end = self.carried + self.S
+        cnt = min(end, self.spec.size)
+        return CacheState(self.m, self.hist[end - cnt:end], self.words[end - cnt:end], pos)
+
+
+class CachedRanks:
+    """What a cached ranking call of streams returns.  ``ranks`` [B, n, columns] int32: rank_streams' array under the mixed
+    distribution; ``top_ids`` [B, n, top] int64 / ``top_logp`` [B, n, top] float64 (log p_q, most probable first) when ``top`` > 0,
+    else None; ``n_entries`` [B, n]; ``h``, ``c``, ``state``: what the next call of the stream carries (interchangeable with
+    score_streams_cached's)."""
+
+    def __init__(self, ranks, top_ids, top_logp, n_entries, h, c, state):
+        self.ranks, self.top_ids, self.top_logp, self.n_entries = ranks, top_ids, top_logp, n_entries
+        self.h, self.c, self.state = h, c, state
+
+
+def _check_top(top, V):
+    if not is_int(top) or not 0 <= top <= min(64, V):
+        raise ValueError("top must be an integer in [0, %d] (got %r)" % (min(64, V), top))
+    return int(top)
+
+
+def rank_streams_cached(ranker, inputs, targets, cache, h=None, c=None, state=None, levels=None, top=0):
+    """LSTM_Model.rank_streams_cached: see there."""
+    from .rank import _columns
+    m = ranker.m
+    spec = _check_mix_spec(cache)
+    top = _check_top(top, m.V)
+    x = np.asarray(inputs)
+    y = np.asarray(targets)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
+    if (h is None) != (c is None):
+        raise ValueError("carry both h and c, or neither")
+    B, n = x.shape
+    _check_state(m, state, B)
+    check_ids(x, m.V, "rank")
+    check_ids(y, m.V, "rank")
+    if h is not None and (tuple(h.shape) != (B, m.H) or tuple(c.shape) != (B, m.H)):
+        raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (B, m.H, tuple(h.shape), tuple(c.shape)))
+    L = levels.n_levels if levels is not None else 0
+    if B == 0 or n == 0:
+        return CachedRanks(np.full((B, n, L + 1), -1, dtype=np.int32), np.zeros((B, n, top), dtype=np.int64) if top else None,
+                           np.zeros((B, n, top)) if top else None, np.zeros((B, n), dtype=np.int64), h, c, state)
+    rings = MixRings(m, spec, B, n, state, top)
+    rk, h2, c2 = ranker.run(x.T, y.T, [B] * n, h=h, c=c, levels=levels, rings=rings)
+    flat = _columns(levels, rk.reshape(n * B, L + 1), np.ascontiguousarray(y.T).reshape(-1))
+    ranks = np.ascontiguousarray(flat.reshape(n, B, L + 1).transpose(1, 0, 2))
+    ids = logp = None
+    if top:
+        ids, logp = rings.lists(m.self_norm)
+        ids, logp = np.ascontiguousarray(ids.transpose(1, 0, 2)), np.ascontiguousarray(logp.transpose(1, 0, 2))
+    pos = (state.pos if state is not None else 0) + n
+    return CachedRanks(ranks, ids, logp, np.ascontiguousarray(np.broadcast_to(rings.n_entries()[None, :], (B, n))), h2, c2,
+                       rings.state_after(pos))
+
+
+def rank_cached(ranker, sequences, start, cache, levels=None, max_rows=None):
+    """LSTM_Model.rank_cached: see there."""
+    from .generate import GENERATE_BUDGET_BYTES
+    from .rank import _columns
+    m = ranker.m
+    spec = _check_mix_spec(cache)
+    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
+    for s in seqs:
+        check_ids(s, m.V, "rank")
+    check_ids([start], m.V, "rank (start)")
+    L = levels.n_levels if levels is not None else 0
+    lens = [len(s) for s in seqs]
+    longest = max(lens) if lens else 0
+    if max_rows is None:
+        max_rows = clamp_rows(MAX_ROWS, GENERATE_BUDGET_BYTES, ranker.row_bytes(longest, L, spec.size), m.H)
+    out = [np.full((k, L + 1), -1, dtype=np.int32) for k in lens]
+    for ch in plan_rows(lens, max_rows):
+        idx = ch["idx"]
+        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
+        rings = MixRings(m, spec, len(idx), ch["n_steps"])
+        rk, _h, _c = ranker.run(word, target, ch["n_live"], levels=levels, rings=rings)
+        for r, i in enumerate(idx):
+            k = int(ch["lens"][r])
+            out[i] = _columns(levels, rk[:k, r, :], target[:k, r])
+    return out
+
+
+def predict_next_cached(ranker, h, state, cache, n=10, allowed=None):
+    """LSTM_Model.predict_next_cached: see there."""
+    from .complete import check_allowed
+    from .readings import ReadingIndex
+    from .rowsets import RowSets, t_is_state
+    from . import ops as _ops
+    m = ranker.m
+    torch = m.torch
+    spec = _check_mix_spec(cache)
+    if m.mode == "untied" and m.split_lstm:
+        raise ValueError("predict_next_cached has no form for an untied split-row model: the f32 copy of the state its vocabulary "
+                         "GEMMs read exists only inside the LSTM step")
+    if h is None or len(tuple(h.shape)) != 2 or int(h.shape[1]) != m.H:
+        raise ValueError("h must be the carried state [B, %d] a stream call returned" % m.H)
+    B = int(h.shape[0])
+    _check_state(m, state, B)
+    if not is_int(n) or not 1 <= n <= min(64, m.V):
+        raise ValueError("n must be an integer in [1, %d] (got %r)" % (min(64, m.V), n))
+    sets = check_allowed(allowed, B, m.V, "predict_next_cached (allowed)")
+    out = [(np.zeros(0, dtype=np.int64), np.zeros(0))] * B
+    if B == 0 or (sets is not None and all(s is not None and not len(s) for s in sets)):
+        return out
+    # the window is the state's last min(count, N) entries: a ring of exactly those, read in place
+    cnt = min(state.count, spec.size) if state is not None else 0
+    dev, i32 = m.device, torch.int32
+    with m._ctx():
+        rs = RowSets(m, B, logits=True)
+        if cnt:
+            hist = state.hist[state.count - cnt:].view(torch.float32).contiguous()
+            words = state.words[state.count - cnt:].contiguous()
+        else:
+            hist = torch.zeros((1, B, m.H), device=dev, dtype=torch.float32)
+            words = torch.zeros((1, B), device=dev, dtype=i32)
+        N = max(cnt, 1)
+        first = torch.zeros(B, device=dev, dtype=i32)
+        s = torch.zeros((B, N), device=dev, dtype=torch.float32)
+        ids = torch.full((B, n), -1, device=dev, dtype=i32)
+        nll = torch.full((B, n), float("nan"), device=dev, dtype=torch.float64)
+        cflags = torch.zeros(1, device=dev, dtype=i32)
+        mask_args = (None, 0, 0, [])
+        if sets is not None:
+            restricted = [r for r in range(B) if sets[r] is not None and len(sets[r])]      # (an empty set: no result, below)
+            mask, index = ReadingIndex.mask([sets[r] for r in restricted], m.V)
+            row_set = [-1] * B
+            for r, k in zip(restricted, index):
+                row_set[r] = int(k)
+            mask_args = (torch.from_numpy(mask.view(np.int32)).to(dev), mask.shape[1], mask.shape[0], row_set)
+        hq = h.view(torch.float32).contiguous()
+        _ops.backend().predict_cache_rows(m.decode_model(), hq, None if t_is_state(m) else rs.T, rs.logits, rs.ld_logits, rs.rows, hist, words,
+                                          N, cnt, first, N, spec.theta, spec.lam, s, N, int(n), *mask_args, ids, nll, rs.flags, cflags, B)
+        rs.check_flags("topk_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)")
+        fl = int(cflags.cpu()[0])
+        if fl:
+            raise _flag_error(fl)
+        ids_h, logp = ids.cpu().numpy().astype(np.int64), -nll.cpu().numpy()
+    if m.self_norm and spec.lam > 0 and cnt:
+        logp = logp + np.log1p(-float(np.float32(spec.lam)))
+    res = []
+    for r in range(B):
+        keep = ids_h[r] >= 0                               # a set smaller than n pads its list with (-1, +inf)
+        if sets is not None and sets[r] is not None and not len(sets[r]):
+            keep[:] = False
+        res.append((ids_h[r][keep], logp[r][keep]))
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------- tuning (numpy)

@@ -571,7 +571,12 @@ extern "C" int jlm_score_cache_frames(const jlm_decode_model *m, const jlm_score
 
 // Teacher-forced ranking (include/jlm_hip.h jlm_rank_frames): jlm_score_frames' loop over the live rows with the materialised logits
 // of a drawing frame of jlm_generate_frames in the normaliser's place, and rank_rows_kernel (csrc/jlm_rank.hip) on the step's targets.
-extern "C" int jlm_rank_frames(const jlm_decode_model *m, const jlm_rank_plan *p, void *stream, void *const *events) {
+// before_rank(t, bound, h_out, ndev, stamp): between the logit GEMMs' stamp and the ranking, with the state set the step wrote;
+// after_rank(t, bound, h_out): behind the ranking, ahead of the step's last stamp, per_step - 1.  jlm_rank_frames: nothing in either;
+// jlm_rank_cache_frames: the cache's query and patch (stamps 4 and 5), and the top-k list and the ring write.
+template <class BeforeRank, class AfterRank>
+static int rank_loop(const jlm_decode_model *m, const jlm_rank_plan *p, void *stream, void *const *events, int per_step,
+                     BeforeRank before_rank, AfterRank after_rank) {
     const int R = p->n_rows, S = p->n_steps;
     if (R < 0 || S < 0 || !p->rows || !p->prev0 || !p->word || !p->target || !p->n_live || !p->logits || !p->rank) return -1;
     if (p->n_levels < 0 || p->n_levels > JLM_RANK_MAX_LEVELS) return -1;
@@ -579,7 +584,7 @@ extern "C" int jlm_rank_frames(const jlm_decode_model *m, const jlm_rank_plan *p
     JLM_TRY(rows_refuse(m, p->T));
     const int V = m->segs[m->n_segs - 1].v_end;
     if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
-    const Stamps stamp{events, JLM_RANK_EVENTS_PER_STEP, stream};
+    const Stamps stamp{events, per_step, stream};
     const size_t ld_rank = (size_t)p->n_levels + 1;
     for (int t = 0; t < S; ++t) {
         const int bound = p->n_live_host ? p->n_live_host[t] : R;
@@ -595,12 +600,102 @@ extern "C" int jlm_rank_frames(const jlm_decode_model *m, const jlm_rank_plan *p
         JLM_TRY(stamp(t, 2));
         if (bound > 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, bound, stream));
         JLM_TRY(stamp(t, 3));
+        JLM_TRY(before_rank(t, bound, s.h_out, ndev, stamp));
         if (bound > 0)
             JLM_TRY(jlm_rank_rows(p->logits, p->ld_logits, V, bound, ndev, target, p->ids, p->n_ids, p->lv_off, p->lv_lo, p->lv_hi, p->n_levels,
                                   p->rank + (size_t)t * R * ld_rank, p->flags, stream));
-        JLM_TRY(stamp(t, 4));
+        JLM_TRY(after_rank(t, bound, s.h_out));
+        JLM_TRY(stamp(t, per_step - 1));
     }
     return 0;
+}
+
+extern "C" int jlm_rank_frames(const jlm_decode_model *m, const jlm_rank_plan *p, void *stream, void *const *events) {
+    return rank_loop(m, p, stream, events, JLM_RANK_EVENTS_PER_STEP, [](int, int, const void *, const int *, const Stamps &) { return 0; },
+                     [](int, int, const void *) { return 0; });
+}
+
+// the refusals of jlm_cache_query / jlm_cache_mix_rows on their own (csrc/jlm_cache_mix.hip)
+int jlm_cache_query_refuse(const void *hist, int cap, int n_rows, int H, int split, float h_scale, const void *q_rows, int n_rows_max,
+                           const int *n_dev, int pos, const int *first, int N, float theta, const float *s, int ld_s, const int *flags);
+int jlm_cache_mix_refuse(const float *y, int ld_y, int n_cols, const float *s, int ld_s, const int *words, int cap, int n_rows,
+                         int n_rows_max, const int *n_dev, int pos, const int *first, int N, float lam, const float *lpc_ent,
+                         const int *flags);
+
+// Ranking under the continuous cache (include/jlm_hip.h jlm_rank_cache_frames): rank_loop with the logits of every step patched into
+// the mixed distribution before they are ranked -- cache_query_kernel on the state set the step wrote, cache_mix_rows_kernel -- an
+// optional top-k list of the patched rows, and jlm_score_cache_frames' ring write behind the step.
+extern "C" int jlm_rank_cache_frames(const jlm_decode_model *m, const jlm_rank_plan *p, const jlm_cache_mix_plan *cp, void *stream,
+                                     void *const *events) {
+    if (!cp || !p || m->n_segs < 1) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    if (R < 0 || S < 0 || cp->pos0 < 0 || (long long)cp->pos0 + S > 0x7fffffffll) return -1;
+    const int split = m->split_lstm ? 1 : 0;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    const int pos_last = cp->pos0 + (S > 0 ? S - 1 : 0);
+    JLM_TRY(jlm_cache_query_refuse(cp->hist, cp->cap, R, m->H, split, m->h_scale, p->h[0], R, p->n_live, pos_last, cp->first, cp->N, cp->theta,
+                                   cp->s, cp->ld_s, cp->flags));
+    JLM_TRY(jlm_cache_mix_refuse(p->logits, p->ld_logits, V, cp->s, cp->ld_s, cp->words, cp->cap, R, R, p->n_live, pos_last, cp->first, cp->N,
+                                 cp->lam, nullptr, cp->flags));
+    if (cp->top_k < 0 || cp->top_k > JLM_TOPK_MAX || cp->top_k > V) return -1;
+    if (cp->top_k > 0 && (!cp->top_ids || !cp->top_nll || !p->n_live_host)) return -1;
+    if (p->n_live_host)
+        for (int t = 0; t < S; ++t)
+            if (p->n_live_host[t] < 0 || p->n_live_host[t] > R) return -1;
+    const size_t row_bytes = (size_t)m->H * 4;
+    return rank_loop(
+        m, p, stream, events, JLM_RANK_CACHE_EVENTS_PER_STEP,
+        [&](int t, int bound, const void *h_out, const int *ndev, const Stamps &stamp) -> int {
+            const int pos = cp->pos0 + t;
+            if (bound > 0)
+                JLM_TRY(jlm_cache_query(cp->hist, cp->cap, R, m->H, split, m->h_scale, h_out, bound, ndev, pos, cp->first, cp->N, cp->theta,
+                                        cp->s, cp->ld_s, cp->flags, stream));
+            JLM_TRY(stamp(t, 4));
+            if (bound > 0)
+                JLM_TRY(jlm_cache_mix_rows(p->logits, p->ld_logits, V, m->self_norm, cp->s, cp->ld_s, cp->words, cp->cap, R, bound, ndev, pos,
+                                           cp->first, cp->N, cp->lam, nullptr, cp->flags, stream));
+            return stamp(t, 5);
+        },
+        [&](int t, int bound, const void *h_out) -> int {
+            if (cp->top_k > 0 && p->n_live_host[t] > 0)
+                JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, p->n_live_host[t], cp->top_k, m->self_norm,
+                                      cp->top_ids + (size_t)t * R * cp->top_k, cp->top_nll + (size_t)t * R * cp->top_k, cp->top_k, p->flags,
+                                      stream));
+            const size_t slot = (size_t)((cp->pos0 + t) % cp->cap);
+            return jlm_cache_store(h_out, p->target + (size_t)t * R, bound, m->H, (char *)cp->hist + slot * R * row_bytes,
+                                   cp->words + slot * R, stream);
+        });
+}
+
+// One step of prediction under the cache, for a caller who holds the carried state of its streams (include/jlm_hip.h
+// jlm_predict_cache_rows): the T projection of h, the logits, the cache's query and patch at `pos`, and the (masked) top-k selection.
+// No LSTM step and no ring write.
+extern "C" int jlm_predict_cache_rows(const jlm_decode_model *m, const jlm_predict_cache_plan *p, void *stream) {
+    if (!p || m->n_segs < 1) return -1;
+    const int R = p->n_rows;
+    if (R < 0 || !p->rows || !p->logits || !p->ids || !p->nll) return -1;
+    if (m->untied && m->split_lstm) return -2;                     // its vocabulary GEMMs read the f32 copy only the LSTM step writes
+    const int split = m->split_lstm ? 1 : 0;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    JLM_TRY(jlm_cache_query_refuse(p->hist, p->cap, R, m->H, split, m->h_scale, p->h, R, nullptr, p->pos, p->first, p->N, p->theta, p->s,
+                                   p->ld_s, p->cache_flags));
+    JLM_TRY(jlm_cache_mix_refuse(p->logits, p->ld_logits, V, p->s, p->ld_s, p->words, p->cap, R, R, nullptr, p->pos, p->first, p->N, p->lam,
+                                 nullptr, p->cache_flags));
+    if (p->k < 1 || p->k > JLM_TOPK_MAX || p->k > V) return -1;
+    if (p->row_set && (p->n_sets < 0 || (p->n_sets > 0 && (!p->mask || p->ld_mask < (V + 31) / 32)))) return -1;
+    if (R == 0) return 0;
+    JLM_TRY(rows_refuse(m, p->T));
+    float *T = t_is_state(m) ? (float *)const_cast<void *>(p->h) : p->T;
+    JLM_TRY(rows_t_projection(m, const_cast<void *>(p->h), p->rows, T, R, nullptr, stream));
+    JLM_TRY(rows_logits(m, T, p->logits, p->ld_logits, R, stream));
+    JLM_TRY(jlm_cache_query(p->hist, p->cap, R, m->H, split, m->h_scale, p->h, R, nullptr, p->pos, p->first, p->N, p->theta, p->s, p->ld_s,
+                            p->cache_flags, stream));
+    JLM_TRY(jlm_cache_mix_rows(p->logits, p->ld_logits, V, m->self_norm, p->s, p->ld_s, p->words, p->cap, R, R, nullptr, p->pos, p->first,
+                               p->N, p->lam, nullptr, p->cache_flags, stream));
+    if (p->row_set)
+        return jlm_topk_rows_masked(p->logits, p->ld_logits, V, R, p->k, m->self_norm, p->mask, p->ld_mask, p->n_sets, p->row_set, p->ids,
+                                    p->nll, p->k, p->flags, stream);
+    return jlm_topk_rows(p->logits, p->ld_logits, V, R, p->k, m->self_norm, p->ids, p->nll, p->k, p->flags, stream);
 }
 
 // Ancestral sampling (include/jlm_hip.h jlm_generate_frames): the prompt frames step the LSTM of their live prefix only; every drawing

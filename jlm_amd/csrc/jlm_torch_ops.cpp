@@ -32,6 +32,9 @@
 //                             the rank of a given word in every row of materialised logits, at every level of its list (jlm_rank_rows)
 //   torch.ops.jlm.rank_frames(Model, state row sets, logits, ..., word, target, n_live, level table, rank, ...)
 //                             teacher-forced ranking of many sequences: ONE op (jlm_rank_frames; LSTM_Model.rank / rank_streams)
+//   torch.ops.jlm.rank_cache_frames / predict_cache_rows
+//                             the same under the continuous cache, and its one-step prediction form (jlm_rank_cache_frames,
+//                             jlm_predict_cache_rows; LSTM_Model.rank_streams_cached / rank_cached / predict_next_cached)
 //   torch.ops.jlm.prime_frames(Model, state row sets, rows, prev, word, n_live, ...)
 //                             the state after a left context: LSTM steps only, ONE op (jlm_prime_frames; LSTM_Model.prime)
 //   torch.ops.jlm.seed_context(Plan, src_h, src_c, last, has, idx)
@@ -749,6 +752,42 @@ void rank_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, cons
 // sets, rows / prev0 / word / target / n_live, generate_frames' logits [n_rows, ld_logits], rank_rows' level table; rank int32
 // [n_steps][n_rows][n_levels + 1].  Every id must lie in [0, V): the caller checks (jlm_amd/rank.py).  -> timed: [n_steps, 4]
 // milliseconds per step (LSTM step, T projection, logit GEMMs, ranking) after waiting for the last step; else an empty tensor.
+// (the checked jlm_rank_plan of rank_frames and rank_cache_frames; live_host keeps the plan's host counts alive)
+struct RankPlanArgs {
+    jlm_rank_plan p{};
+    std::vector<int> live_host;
+    int64_t V = 0;
+    RankPlanArgs(const char *op, const jlm_decode_model &m, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                 const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0, const Tensor &word,
+                 const Tensor &target, const Tensor &n_live, const std::vector<int64_t> &n_live_host, const OptTensor &ids,
+                 const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels, const Tensor &rank,
+                 const OptTensor &flags, int64_t R, int64_t S)
+        : live_host(n_live_host.begin(), n_live_host.end()) {
+        auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+        auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+        check_row_sets(op, m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
+        TORCH_CHECK(m.n_segs >= 1, "jlm.", op, ": a model without segments");
+        V = m.segs[m.n_segs - 1].v_end;
+        const RankLevels lv(op, ids, lv_off, lv_lo, lv_hi, V, n_levels);
+        TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
+                        is(n_live, at::kInt, S),
+                    "jlm.", op, ": int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
+        TORCH_CHECK(is(rank, at::kInt, S * R * (n_levels + 1)) && (!has(flags) || is(*flags, at::kInt, 1)),
+                    "jlm.", op, ": int32 rank [n_steps][n_rows][n_levels + 1], int32 flags");
+        TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.", op, ": T [n_rows, ldt] float32");
+        TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.", op, ": logits [n_rows, ld_logits] float32");
+        p.n_rows = (int)R; p.n_steps = (int)S;
+        p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+        p.T = optr<float>(T, "T");
+        p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits;
+        p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
+        p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
+        p.n_live_host = live_host.data();
+        p.ids = lv.ids; p.n_ids = lv.n_ids; p.lv_off = lv.off; p.lv_lo = lv.lo; p.lv_hi = lv.hi; p.n_levels = (int)n_levels;
+        p.rank = ptr<int>(rank, "rank"); p.flags = optr<int>(flags, "flags");
+    }
+};
+
 Tensor rank_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
                    const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0, const Tensor &word,
                    const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host, const OptTensor &ids, const OptTensor &lv_off,
@@ -756,32 +795,49 @@ Tensor rank_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, 
                    int64_t n_steps, bool timed) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, S = n_steps;
+    const RankPlanArgs rp("rank_frames", m, h0, c0, h1, c1, T, logits, ld_logits, rows, prev0, word, target, n_live, n_live_host, ids, lv_off,
+                          lv_lo, lv_hi, n_levels, rank, flags, R, S);
+    return launch_frames("jlm_rank_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_rank_frames(&m, &rp.p, st, ev); });
+}
+
+// rank_frames under the continuous cache (jlm_rank_cache_frames, include/jlm_hip.h): its arguments, then the rings hist
+// [cap][n_rows][H] (4-byte values, the model's state-row format) and words [cap][n_rows] int32 with the carried entries in their slots,
+// pos0, first [n_rows] int32 on the device, N, theta, lam, the scratch s [n_rows][ld_s] float32, top_k with top_ids int32 / top_nll
+// float64 [n_steps][n_rows][top_k] (top_k = 0: none), cache_flags one int32.  -> timed: [n_steps, 6] milliseconds per step (LSTM step,
+// T projection, logit GEMMs, cache query, cache patch, ranking with the lists and the ring write); else an empty tensor.
+Tensor rank_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                         const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0,
+                         const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host, const OptTensor &ids,
+                         const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels, const Tensor &rank,
+                         const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed, const Tensor &hist, const Tensor &words,
+                         int64_t cap, int64_t pos0, const Tensor &first, int64_t N, double theta, double lam, const Tensor &s, int64_t ld_s,
+                         int64_t top_k, const OptTensor &top_ids, const OptTensor &top_nll, const OptTensor &cache_flags) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
     auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
     auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    check_row_sets("rank_frames", m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
-    TORCH_CHECK(m.n_segs >= 1, "jlm.rank_frames: a model without segments");
-    const int64_t V = m.segs[m.n_segs - 1].v_end;
-    const RankLevels lv("rank_frames", ids, lv_off, lv_lo, lv_hi, V, n_levels);
-    TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
-                    is(n_live, at::kInt, S),
-                "jlm.rank_frames: int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
-    TORCH_CHECK(is(rank, at::kInt, S * R * (n_levels + 1)) && (!has(flags) || is(*flags, at::kInt, 1)),
-                "jlm.rank_frames: int32 rank [n_steps][n_rows][n_levels + 1], int32 flags");
-    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.rank_frames: T [n_rows, ldt] float32");
-    TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.rank_frames: logits [n_rows, ld_logits] float32");
-    jlm_rank_plan p{};
-    p.n_rows = (int)R; p.n_steps = (int)S;
-    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
-    p.T = optr<float>(T, "T");
-    p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits;
-    p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
-    p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
-    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
-    p.n_live_host = live_host.data();
-    p.ids = lv.ids; p.n_ids = lv.n_ids; p.lv_off = lv.off; p.lv_lo = lv.lo; p.lv_hi = lv.hi; p.n_levels = (int)n_levels;
-    p.rank = ptr<int>(rank, "rank"); p.flags = optr<int>(flags, "flags");
-    return launch_frames("jlm_rank_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_EVENTS_PER_STEP,
-                         [&](hipStream_t st, void *const *ev) { return jlm_rank_frames(&m, &p, st, ev); });
+    const RankPlanArgs rp("rank_cache_frames", m, h0, c0, h1, c1, T, logits, ld_logits, rows, prev0, word, target, n_live, n_live_host, ids,
+                          lv_off, lv_lo, lv_hi, n_levels, rank, flags, R, S);
+    TORCH_CHECK(N >= 1 && N <= JLM_CACHE_MIX_MAX_N && cap >= N && cap <= INT32_MAX && pos0 >= 0 && pos0 + S + cap < INT32_MAX && ld_s >= N &&
+                    ld_s <= INT32_MAX,
+                "jlm.rank_cache_frames: 1 <= N <= ", JLM_CACHE_MIX_MAX_N, ", cap >= N, ld_s >= N, 0 <= pos0, pos0 + n_steps + cap < 2^31");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam >= 0.0 && lam < 1.0, "jlm.rank_cache_frames: theta finite and >= 0, lam in [0, 1)");
+    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
+                "jlm.rank_cache_frames: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
+    TORCH_CHECK(is(first, at::kInt, R) && is(s, at::kFloat, R * ld_s) && (!has(cache_flags) || is(*cache_flags, at::kInt, 1)),
+                "jlm.rank_cache_frames: int32 first [n_rows], float32 s [n_rows][ld_s], int32 cache_flags");
+    TORCH_CHECK(top_k >= 0 && top_k <= JLM_TOPK_MAX && top_k <= rp.V &&
+                    (top_k == 0 || (has(top_ids) && has(top_nll) && is(*top_ids, at::kInt, S * R * top_k) && is(*top_nll, at::kDouble, S * R * top_k))),
+                "jlm.rank_cache_frames: top_k in 0 .. min(", JLM_TOPK_MAX, ", V) with int32 top_ids / float64 top_nll [n_steps][n_rows][top_k]");
+    jlm_cache_mix_plan cp{};
+    cp.hist = ptr<void>(hist, "hist"); cp.words = ptr<int>(words, "words"); cp.cap = (int)cap; cp.pos0 = (int)pos0;
+    cp.first = ptr<const int>(first, "first"); cp.N = (int)N; cp.theta = (float)theta; cp.lam = (float)lam;
+    cp.s = ptr<float>(s, "s"); cp.ld_s = (int)ld_s; cp.top_k = (int)top_k;
+    cp.top_ids = top_k > 0 ? ptr<int>(*top_ids, "top_ids") : nullptr; cp.top_nll = top_k > 0 ? ptr<double>(*top_nll, "top_nll") : nullptr;
+    cp.flags = optr<int>(cache_flags, "cache_flags");
+    return launch_frames("jlm_rank_cache_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_CACHE_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_rank_cache_frames(&m, &rp.p, &cp, st, ev); });
 }
 
 // one draw per row of f32 logits y [n_rows, ld] (jlm_sample_rows, include/jlm_hip.h).  seed: the uint64 seed's bits as int64.
@@ -931,6 +987,58 @@ void topk_rows_masked(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_row
                                    ptr<const int>(sets, "row_set"), ptr<int>(ids, "ids"), ptr<double>(nll, "nll"), (int)ld_out,
                                    optr<int>(flags, "flags"), stream_of(y)),
               "jlm_topk_rows_masked");
+}
+
+// One step of prediction under the continuous cache (jlm_predict_cache_rows, include/jlm_hip.h): h [n_rows, H] the carried state rows
+// in the model's state-row format, the scratch T / logits / s, rows [n_rows] int32, the rings and their scalars as rank_cache_frames
+// takes them with pos the streams' next position, k, and -- mask given -- the word sets of topk_rows_masked with one set index per
+// row.  ids int32 / nll float64 [n_rows, k].  On the current stream; nothing waits.
+void predict_cache_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h, const OptTensor &T, const Tensor &logits,
+                        int64_t ld_logits, const Tensor &rows, const Tensor &hist, const Tensor &words, int64_t cap, int64_t pos,
+                        const Tensor &first, int64_t N, double theta, double lam, const Tensor &s, int64_t ld_s, int64_t k,
+                        const OptTensor &mask, int64_t ld_mask, int64_t n_sets, std::vector<int64_t> row_set, const Tensor &ids,
+                        const Tensor &nll, const OptTensor &flags, const OptTensor &cache_flags, int64_t n_rows) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows;
+    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
+    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
+    TORCH_CHECK(m.n_segs >= 1, "jlm.predict_cache_rows: a model without segments");
+    TORCH_CHECK(!(m.untied && m.split_lstm), "jlm.predict_cache_rows: an untied split-row model keeps the f32 copy of its state, which its "
+                                             "vocabulary GEMMs read, only inside the LSTM step: there is no one-step form for it");
+    const int64_t V = m.segs[m.n_segs - 1].v_end;
+    TORCH_CHECK(R >= 0 && R <= 65535 && h.defined() && h.element_size() == 4 && h.numel() >= R * m.H && is(rows, at::kInt, R),
+                "jlm.predict_cache_rows: h [n_rows, H] of 4-byte values, int32 rows [n_rows], n_rows <= 65535");
+    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.predict_cache_rows: T [n_rows, ldt] float32");
+    TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.predict_cache_rows: logits [n_rows, ld_logits] float32");
+    TORCH_CHECK(N >= 1 && N <= JLM_CACHE_MIX_MAX_N && cap >= N && cap <= INT32_MAX && pos >= 0 && pos + cap < INT32_MAX && ld_s >= N &&
+                    ld_s <= INT32_MAX,
+                "jlm.predict_cache_rows: 1 <= N <= ", JLM_CACHE_MIX_MAX_N, ", cap >= N, ld_s >= N, 0 <= pos, pos + cap < 2^31");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam >= 0.0 && lam < 1.0, "jlm.predict_cache_rows: theta finite and >= 0, lam in [0, 1)");
+    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
+                "jlm.predict_cache_rows: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
+    TORCH_CHECK(is(first, at::kInt, R) && is(s, at::kFloat, R * ld_s) && (!has(cache_flags) || is(*cache_flags, at::kInt, 1)) &&
+                    (!has(flags) || is(*flags, at::kInt, 1)),
+                "jlm.predict_cache_rows: int32 first [n_rows], float32 s [n_rows][ld_s], int32 flags / cache_flags");
+    TORCH_CHECK(k >= 1 && k <= JLM_TOPK_MAX && k <= V && is(ids, at::kInt, R * k) && is(nll, at::kDouble, R * k),
+                "jlm.predict_cache_rows: k in 1 .. min(", JLM_TOPK_MAX, ", V), int32 ids / float64 nll [n_rows, k]");
+    const c10::hip::HIPGuard device_guard(logits.device().index());
+    on_gpu(logits, "logits");
+    Tensor sets;
+    if (has(mask)) sets = check_word_sets("predict_cache_rows", *mask, ld_mask, n_sets, V, row_set, R, logits);
+    jlm_predict_cache_plan p{};
+    p.n_rows = (int)R; p.h = ptr<const void>(h, "h"); p.T = optr<float>(T, "T");
+    p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits; p.rows = ptr<const int>(rows, "rows");
+    p.hist = ptr<const void>(hist, "hist"); p.words = ptr<const int>(words, "words"); p.cap = (int)cap; p.pos = (int)pos;
+    p.first = ptr<const int>(first, "first"); p.N = (int)N; p.theta = (float)theta; p.lam = (float)lam;
+    p.s = ptr<float>(s, "s"); p.ld_s = (int)ld_s; p.k = (int)k;
+    if (has(mask)) {
+        p.mask = n_sets > 0 ? ptr<const unsigned>(*mask, "mask") : nullptr; p.ld_mask = (int)ld_mask; p.n_sets = (int)n_sets;
+        p.row_set = ptr<const int>(sets, "row_set");
+    }
+    p.ids = ptr<int>(ids, "ids"); p.nll = ptr<double>(nll, "nll"); p.flags = optr<int>(flags, "flags");
+    p.cache_flags = optr<int>(cache_flags, "cache_flags");
+    const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
+    jlm_check(jlm_predict_cache_rows(&m, &p, stream_of(logits)), "jlm_predict_cache_rows");
 }
 
 // one beam selection per prompt over per-row top-`beam` lists (jlm_beam_merge, include/jlm_hip.h): cand_ids int32 / cand_nll float64
@@ -1240,6 +1348,17 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor? ids, Tensor? lv_off, Tensor? lv_lo, Tensor? lv_hi, int n_levels, Tensor(g!) rank, Tensor(h!)? flags, int n_rows, "
           "int n_steps, bool timed) -> Tensor",
           rank_frames);
+    m.def("rank_cache_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, int[] n_live_host, "
+          "Tensor? ids, Tensor? lv_off, Tensor? lv_lo, Tensor? lv_hi, int n_levels, Tensor(g!) rank, Tensor(h!)? flags, int n_rows, "
+          "int n_steps, bool timed, Tensor(i!) hist, Tensor(j!) words, int cap, int pos0, Tensor first, int N, float theta, float lam, "
+          "Tensor(k!) s, int ld_s, int top_k, Tensor(l!)? top_ids, Tensor(m!)? top_nll, Tensor(n!)? cache_flags) -> Tensor",
+          rank_cache_frames);
+    m.def("predict_cache_rows(__torch__.torch.classes.jlm.Model model, Tensor h, Tensor(a!)? T, Tensor(b!) logits, int ld_logits, Tensor rows, "
+          "Tensor hist, Tensor words, int cap, int pos, Tensor first, int N, float theta, float lam, Tensor(c!) s, int ld_s, int k, "
+          "Tensor? mask, int ld_mask, int n_sets, int[] row_set, Tensor(d!) ids, Tensor(e!) nll, Tensor(f!)? flags, Tensor(g!)? cache_flags, "
+          "int n_rows) -> ()",
+          predict_cache_rows);
     m.def("sample_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, float temperature, int seed, int step, Tensor? row_id, "
           "Tensor? forced, Tensor(a!)? done, int stop_id, bool self_norm, Tensor(b!) word, Tensor(c!) ids, Tensor(d!) nll, Tensor(e!)? flags) -> ()",
           sample_rows);

@@ -1010,6 +1010,36 @@ class LSTM_Model():
         from .rank import rank_streams
         return rank_streams(self._ranker(), inputs, targets, h, c, self._rank_levels(readings, max_prefix))
 
+    def rank_streams_cached(self, inputs, targets, cache, h=None, c=None, state=None, readings=True, max_prefix=8, top=0):
+        """rank_streams under the continuous cache (jlm_amd/cache.py): every step's full-vocabulary logits are
+        patched on the device into the mixed distribution p = (1 - lam) p_lm + lam c, c the cache's distribution over the words of the
+        last ``cache.size`` positions, before the target is ranked.  ``cache``: a :class:`jlm_amd.cache.CacheSpec` with ONE theta and
+        size <= 4096; ``state``: the :class:`jlm_amd.cache.CacheState` an earlier call of the stream returned -- this method's or
+        score_streams_cached's, they are interchangeable -- None: an empty cache.  -> :class:`jlm_amd.cache.CachedRanks`: ``ranks``
+        [B, n, max_prefix + 3] in rank()'s columns, ``top_ids`` / ``top_logp`` [B, n, top] (the ``top`` <= 64 most probable words of
+        every step and their log p under the mixture; None for top = 0), ``n_entries``, and ``h``, ``c``, ``state`` to carry.  lam = 0
+        and the first step of a fresh stream give rank_streams' ranks; a stream cut any way into calls gives the same ranks and
+        lists.  ValueError before anything runs for a bad argument, more than one theta, size > 4096, or a state of another model or
+        row count."""
+        from .cache import rank_streams_cached
+        return rank_streams_cached(self._ranker(), inputs, targets, cache, h, c, state, self._rank_levels(readings, max_prefix), top)
+
+    def rank_cached(self, sequences, start, cache, readings=True, max_prefix=8, max_rows=None):
+        """rank() under the continuous cache: every sequence starts from an empty cache; rank()'s row plan with the rings counted into
+        the rows of a call.  -> per sequence an int32 [len, max_prefix + 3] array, rank()'s columns."""
+        from .cache import rank_cached
+        return rank_cached(self._ranker(), sequences, start, cache, self._rank_levels(readings, max_prefix), max_rows)
+
+    def predict_next_cached(self, h, state, cache, n=10, allowed=None):
+        """The ``n`` most probable next words of B streams under the continuous cache, from what a stream call left: ``h`` the carried
+        state [B, H] (device tensor, as rank_streams_cached / score_streams_cached return it), ``state`` their CacheState (None: an
+        empty cache, the model's own list).  One T projection, the logits, the cache's query and patch, and the selection: no LSTM
+        step, and the state is not changed.  -> per row (ids int64, logp float64 = log p under the mixture), most probable first.
+        ``allowed``: predict_top's.  ValueError for an untied split-row model, whose vocabulary GEMMs read a copy of the state that
+        exists only inside the LSTM step."""
+        from .cache import predict_next_cached
+        return predict_next_cached(self._ranker(), h, state, cache, n, allowed)
+
     def generate(self, prompts=None, n_words=100, temperature=1.0, seed=0, stop_id=None, max_rows=None, top_k=None, top_p=None):
         """Ancestral sampling on the device (jlm_amd/generate.py): the reference's sampling loop (model.py:213-245, one predict() and
         one sample() per word) for many rows at once.  ``prompts``: R word-id lists of length >= 1 (None: one row starting at <eos>, the

@@ -21,7 +21,8 @@ after every line; a character model (config char_rnn) reads the characters of th
                    (jlm_amd/cache.py) at --theta and --lam, in ONE pass -- LSTM_Model.score_streams_cached returns the plain -log p
                    as well -- and print the cached perplexity after the plain one.  --tune-cache FILE sweeps --thetas and --lams on
                    FILE, the dev set, prints the grid's best pair and reports the test perplexity at that pair.  Without --cache the
-                   output is what it was.
+                   output is what it was.  With --ranks as well (N <= 4096), a second --ranks line "with cache" over the same tokens,
+                   at the theta and lam the cached perplexity is reported at (LSTM_Model.rank_streams_cached).
 """
 import argparse
 import os
@@ -118,15 +119,20 @@ def sentence_ranks(model, sents, eos, readings, max_prefix):
     return (np.concatenate(ranks) if ranks else np.zeros((0, width), dtype=np.int32)), np.array([t for s in sents for t in s], dtype=np.int64)
 
 
-def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix):
-    """-> (ranks [tokens, columns], the targets [tokens]) over the corpus_iterator chunks, state carried, as stream_perplexity"""
+def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix, spec=None):
+    """-> (ranks [tokens, columns], the targets [tokens]) over the corpus_iterator chunks, state carried, as stream_perplexity;
+    ``spec``: a CacheSpec -- the ranks under the continuous cache (LSTM_Model.rank_streams_cached), the cache carried too"""
     from .score import stream_layout
     x, y = stream_layout(stream, batch_size, num_steps)
-    h = c = None
+    h = c = state = None
     out = []
     for i in range(x.shape[1] // num_steps):
         cols = slice(i * num_steps, (i + 1) * num_steps)
-        r, h, c = model.rank_streams(x[:, cols], y[:, cols], h, c, readings=readings, max_prefix=max_prefix)
+        if spec is None:
+            r, h, c = model.rank_streams(x[:, cols], y[:, cols], h, c, readings=readings, max_prefix=max_prefix)
+        else:
+            res = model.rank_streams_cached(x[:, cols], y[:, cols], spec, h, c, state, readings=readings, max_prefix=max_prefix)
+            r, h, c, state = res.ranks, res.h, res.c, res.state
         out.append(r)
     ranks = np.concatenate(out, axis=1)
     return ranks.reshape(-1, ranks.shape[-1]), y.reshape(-1).astype(np.int64)
@@ -186,6 +192,8 @@ def main(argv=None):
     tops = [int(k) for k in args.top.split(",") if k.strip()]
     if args.ranks and (not tops or min(tops) < 1 or args.list_size < 1):
         ap.error("--top and --list take integers >= 1")
+    if args.ranks and spec is not None and spec.size > 4096:
+        ap.error("--ranks with --cache takes a cache of at most 4096 entries")
     config, vocab = load_vocab(args)
     from .model import LSTM_Model
     path = args.file or os.path.join(_config.data_path, "test.txt")
@@ -224,6 +232,10 @@ def main(argv=None):
         else:
             ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix)
         print(ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
+        if spec is not None:
+            ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix, spec)
+            print("with cache (N {} theta {} lam {}): ".format(spec.size, spec.theta, spec.lam) +
+                  ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
     return pp
 
 

@@ -88,14 +88,22 @@ class Ranker:
                 self._levels[key] = Levels(self.m, index, int(max_prefix))
         return self._levels[key]
 
-    def row_bytes(self, n_steps, n_levels):
+    def row_bytes(self, n_steps, n_levels, cache_size=0, top=0):
+        """the bytes a row of a call takes; ``cache_size`` > 0: with the rings and the score scratch of a cached call"""
         m = self.m
-        return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + n_steps * (8 + 4 * (n_levels + 1)) + 32
+        base = (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + n_steps * (8 + 4 * (n_levels + 1)) + 32
+        if cache_size:
+            from .cache import MixRings
+            base += MixRings.row_bytes(m.H, cache_size, n_steps, top)
+        return base
 
-    def run(self, word, target, n_live, h=None, c=None, levels=None, timed=False):
+    def run(self, word, target, n_live, h=None, c=None, levels=None, timed=False, rings=None):
         """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
         the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
-        levels: a :class:`Levels`, None = level A only.  -> (rank [n_steps, R, n_levels + 1] int32 in the device's column order, -1
+        levels: a :class:`Levels`, None = level A only.  rings: a :class:`jlm_amd.cache.MixRings` made for this call's (R, n_steps) --
+        the op is then ``rank_cache_frames``: every step's logits are patched into the mixed distribution of the continuous cache
+        before they are ranked, the rings' ``top`` best words of every step go to the rings' lists, and last_step_ms has six columns
+        (the cache's query and patch between the logit GEMMs and the ranking).  -> (rank [n_steps, R, n_levels + 1] int32 in the device's column order, -1
         where a row is not live, h, c) -- the state after the last step stays on the device; as in Scorer.run, only the rows live
         at the last step are defined in it."""
         torch, m = self.torch, self.m
@@ -122,10 +130,16 @@ class Ranker:
             nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
             rank = torch.full((S, R, L + 1), -1, device=dev, dtype=i32)
             table = levels.args() if levels is not None else (None, None, None, None, 0)
-            ms = _ops.backend().rank_frames(m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, prev0, wd, tg, nl, n_live,
-                                            *table, rank, rs.flags, R, S, bool(timed))
+            args = (m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, prev0, wd, tg, nl, n_live, *table, rank, rs.flags, R, S,
+                    bool(timed))
+            if rings is None:
+                ms = _ops.backend().rank_frames(*args)
+            else:
+                ms = _ops.backend().rank_cache_frames(*args, *rings.op_args(R, S))
             if timed:
                 self.last_step_ms = ms.numpy()
+            if rings is not None:
+                rings.check()
             rs.check_flags("rank_rows_kernel flagged a target outside the vocabulary (flags %d)",
                            "the logit of a target word is NaN: its rank is undefined")
             out = rank.cpu().numpy()
