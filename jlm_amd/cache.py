@@ -17,7 +17,8 @@ the written state rows copied into a ring after every step, and ``cache_rows_ker
 lpc does not depend on lam, so lam is swept on the host from one device pass (:func:`tune`).
 
 ``LSTM_Model.score_cached`` / ``score_streams_cached`` (jlm_amd/model.py) are the public entry points, ``python -m jlm_amd.perplexity
---cache`` the command-line front end.
+--cache`` the command-line front end.  :class:`Ring` is the ring of a cached call; :class:`Rings` (scoring) and :class:`MixRings`
+(ranking) add their ops' own buffers.
 
 Ranking and prediction need the cache's mass on EVERY word of the window, not the target's alone:
 
@@ -32,8 +33,12 @@ in float64; on the device ``torch.ops.jlm.rank_cache_frames`` patches every step
 import numpy as np
 
 from . import _lib
-from .rowsets import check_ids, clamp_rows, is_int
-from .score import MAX_ROWS, SCORE_BUDGET_BYTES, plan_rows, sentence_arrays
+from . import ops as _ops
+from .complete import check_allowed
+from .generate import GENERATE_BUDGET_BYTES
+from .readings import ReadingIndex
+from .rowsets import RowSets, check_streams, is_int, t_is_state
+from .score import MAX_ROWS, SCORE_BUDGET_BYTES, sentence_loop
 
 MAX_THETAS = 16                     # JLM_CACHE_MAX_THETAS
 MAX_SIZE = 1 << 24
@@ -190,42 +195,32 @@ class CacheState:
         return np.ascontiguousarray(h), np.ascontiguousarray(self.words.detach().cpu().numpy().T.astype(np.int64)), self.positions
 
 
-class Rings:
-    """The rings of one cached call of R rows and S steps (jlm_cache_plan): cap = N + S slots, the carried entries at the local
-    positions 0 .. carried - 1 and the call's steps at carried .. carried + S - 1 -- a call numbers positions from its oldest carried
-    entry, so ``first`` is 0 and no slot wraps; :class:`CacheState` keeps the stream's own numbering.  ``lens`` [R]: the steps each
-    row is live."""
+class Ring:
+    """The ring of one cached call of R rows and S steps: cap = N + S slots of (h, word), the carried entries at the local positions
+    0 .. carried - 1 and the call's steps at carried .. carried + S - 1 -- a call numbers positions from its oldest carried entry, so
+    ``first`` is 0 and no slot wraps; :class:`CacheState` keeps the stream's own numbering.  A subclass gives the slots' memory with
+    the carried entries at its front (``_slots``) and adds its op's own buffers; it constructs inside the model's context."""
 
-    def __init__(self, m, spec, R, S, lens, state=None):
+    def __init__(self, m, spec, R, S, state=None):
         torch, dev = m.torch, m.device
         self.m, self.spec, self.R, self.S = m, spec, R, S
-        N = spec.size
-        self.carried = min(state.count, N) if state is not None else 0
-        self.cap = N + S
-        with m._ctx():
-            self.hist = torch.empty((self.cap, R, m.H), device=dev, dtype=torch.float32)
-            self.words = torch.empty((self.cap, R), device=dev, dtype=torch.int32)
-            if self.carried:
-                self.hist[:self.carried].copy_(state.hist[state.count - self.carried:].view(torch.float32))
-                self.words[:self.carried].copy_(state.words[state.count - self.carried:])
-            self.first = torch.zeros(R, device=dev, dtype=torch.int32)
-            self.len = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
-            self.lpc = torch.full((len(spec.thetas), S, R), float("-inf"), device=dev, dtype=torch.float32)
-            self.flags = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.carried = min(state.count, spec.size) if state is not None else 0
+        self.cap = spec.size + S
+        k = self.carried
+        self.hist = self._slots((self.cap, R, m.H), torch.float32, state.hist[state.count - k:].view(torch.float32) if k else None)
+        self.words = self._slots((self.cap, R), torch.int32, state.words[state.count - k:] if k else None)
+        self.first = torch.zeros(R, device=dev, dtype=torch.int32)
+        self.flags = torch.zeros(1, device=dev, dtype=torch.int32)
 
-    def op_args(self, R, S):
+    def ring_args(self, R, S):
+        """the ops' argument run hist, words, cap, pos, first"""
         if (R, S) != (self.R, self.S):
             raise ValueError("these rings were made for %d rows and %d steps (got %d, %d)" % (self.R, self.S, R, S))
-        return (self.hist, self.words, self.cap, self.carried, self.first, self.len, self.spec.size, list(self.spec.thetas), self.lpc,
-                self.flags)
+        return self.hist, self.words, self.cap, self.carried, self.first
 
-    def results(self):
-        """(lpc [n_theta, S, R] float64, host; n_entries [S] of a row live at that step) -- after the op; JlmHipError when the kernel
-        flagged a product that is not finite"""
-        if int(self.flags.cpu()[0]) & 1:
-            raise _lib.JlmHipError("cache_rows_kernel flagged a product h_q . h_i that is not finite: a hidden state is NaN or inf")
-        n_entries = np.minimum(self.carried + np.arange(self.S, dtype=np.int64), self.spec.size)
-        return self.lpc.cpu().numpy().astype(np.float64), n_entries
+    def n_entries(self):
+        """[S]: the entries of a live row's window at each step"""
+        return np.minimum(self.carried + np.arange(self.S, dtype=np.int64), self.spec.size)
 
     def state_after(self, pos):
         """the CacheState after the call's S steps (every row live to the end), the stream's next position being ``pos``"""
@@ -233,6 +228,34 @@ class Rings:
         cnt = min(end, self.spec.size)
         # (views: the rings are not written after the call, and a copy of N state rows a call costs as much as the cache pass)
         return CacheState(self.m, self.hist[end - cnt:end], self.words[end - cnt:end], pos)
+
+
+class Rings(Ring):
+    """The rings of one cached scoring call (jlm_cache_plan): :class:`Ring` in uninitialised memory -- every slot is written before it
+    is read -- with ``lens`` [R], the steps each row is live, and lpc [n_theta, S, R]."""
+
+    def __init__(self, m, spec, R, S, lens, state=None):
+        torch, dev = m.torch, m.device
+        with m._ctx():
+            super().__init__(m, spec, R, S, state)
+            self.len = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+            self.lpc = torch.full((len(spec.thetas), S, R), float("-inf"), device=dev, dtype=torch.float32)
+
+    def _slots(self, shape, dtype, front):
+        t = self.m.torch.empty(shape, device=self.m.device, dtype=dtype)
+        if front is not None:
+            t[:len(front)].copy_(front)
+        return t
+
+    def op_args(self, R, S):
+        return (*self.ring_args(R, S), self.len, self.spec.size, list(self.spec.thetas), self.lpc, self.flags)
+
+    def results(self):
+        """(lpc [n_theta, S, R] float64, host; n_entries [S] of a row live at that step) -- after the op; JlmHipError when the kernel
+        flagged a product that is not finite"""
+        if int(self.flags.cpu()[0]) & 1:
+            raise _lib.JlmHipError("cache_rows_kernel flagged a product h_q . h_i that is not finite: a hidden state is NaN or inf")
+        return self.lpc.cpu().numpy().astype(np.float64), self.n_entries()
 
 
 class CachedScores:
@@ -255,22 +278,8 @@ def score_streams_cached(scorer, inputs, targets, cache, h=None, c=None, state=N
     """LSTM_Model.score_streams_cached: see there."""
     m = scorer.m
     spec = _check_spec(cache)
-    x = np.asarray(inputs)
-    y = np.asarray(targets)
-    if x.ndim != 2 or x.shape != y.shape:
-        raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
-    if (h is None) != (c is None):
-        raise ValueError("carry both h and c, or neither")
-    B, n = x.shape
-    if state is not None:
-        if not isinstance(state, CacheState) or state.m is not m:
-            raise ValueError("this cache state belongs to another model")
-        if state.n_rows != B:
-            raise ValueError("this cache state holds %d streams, the call has %d" % (state.n_rows, B))
-    check_ids(x, m.V, "score")
-    check_ids(y, m.V, "score")
-    if h is not None and (tuple(h.shape) != (B, m.H) or tuple(c.shape) != (B, m.H)):
-        raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (B, m.H, tuple(h.shape), tuple(c.shape)))
+    x, y, B, n = check_streams(m, inputs, targets, h, c, "score")
+    _check_state(m, state, B)
     n_theta = len(spec.thetas)
     if B == 0 or n == 0:
         return CachedScores(np.zeros((B, n)), np.full((n_theta, B, n), -np.inf), np.zeros((B, n), dtype=np.int64), spec.thetas, h, c, state)
@@ -286,25 +295,14 @@ def score_cached(scorer, sequences, start, cache, max_rows=None):
     """LSTM_Model.score_cached: see there."""
     m = scorer.m
     spec = _check_spec(cache)
-    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
-    for s in seqs:
-        check_ids(s, m.V, "score")
-    check_ids([start], m.V, "score (start)")
-    lens = [len(s) for s in seqs]
-    longest = max(lens) if lens else 0
-    if max_rows is None:
-        max_rows = clamp_rows(MAX_ROWS, SCORE_BUDGET_BYTES, scorer.row_bytes(longest, True, spec.size, len(spec.thetas)), m.H)
-    out = [np.zeros(L, dtype=np.float64) for L in lens]
-    for ch in plan_rows(lens, max_rows):
-        idx = ch["idx"]
-        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
-        rings = Rings(m, spec, len(idx), ch["n_steps"], ch["lens"])
-        _seq, tok, _h, _c = scorer.run(word, target, ch["n_live"], per_token=True, rings=rings)
+
+    def run(ch, word, target, lens):
+        rings = Rings(m, spec, len(lens), ch["n_steps"], lens)
+        tok = scorer.run(word, target, ch["n_live"], per_token=True, rings=rings)[1]
         lpc, n_entries = rings.results()
-        for r, i in enumerate(idx):
-            L = int(ch["lens"][r])
-            out[i] = mix_nll(tok[:L, r], lpc[0, :L, r], n_entries[:L], spec.lam)
-    return out
+        return [mix_nll(tok[:n, r], lpc[0, :n, r], n_entries[:n], spec.lam) for r, n in enumerate(lens)]
+    return sentence_loop(m, sequences, start, "score", max_rows, (MAX_ROWS, SCORE_BUDGET_BYTES),
+                         lambda n: scorer.row_bytes(n, True, spec.size, len(spec.thetas)), lambda n: np.zeros(n, dtype=np.float64), run)
 
 
 # ---------------------------------------------------------------------------------------------------------------- ranking and prediction
@@ -337,50 +335,38 @@ def _flag_error(fl):
     return _lib.JlmHipError("cache_mix_rows_kernel flagged a cached word outside the vocabulary (flags %d)" % fl)
 
 
-class MixRings:
-    """The rings of one cached ranking call of R rows and S steps (jlm_cache_mix_plan): :class:`Rings`' layout -- cap = N + S slots,
-    the carried entries at the local positions 0 .. carried - 1, ``first`` 0 -- with the scratch ``s`` [R, N] of one step's scores in
-    lpc's place, and ``top`` > 0 the lists top_ids / top_nll [S, R, top] of every step."""
+class MixRings(Ring):
+    """The rings of one cached ranking call (jlm_cache_mix_plan): :class:`Ring` in zeroed memory, with the scratch ``s`` [R, N] of one
+    step's scores in lpc's place, and ``top`` > 0 the lists top_ids / top_nll [S, R, top] of every step."""
 
     def __init__(self, m, spec, R, S, state=None, top=0):
         torch, dev = m.torch, m.device
-        self.m, self.spec, self.R, self.S, self.top = m, spec, R, S, int(top)
-        N = spec.size
-        self.carried = min(state.count, N) if state is not None else 0
-        self.cap = N + S
+        self.top = int(top)
         with m._ctx():
-            # (no uninitialised memory here: the carried entries and zeros behind them in one pass -- every slot is written before
-            #  it is read, DESIGN.md section 19, and the fill is the S + N - carried slots the copy of the carried entries leaves)
-            rest = self.cap - self.carried
-            self.hist = torch.zeros((rest, R, m.H), device=dev, dtype=torch.float32)
-            self.words = torch.zeros((rest, R), device=dev, dtype=torch.int32)
-            if self.carried:
-                self.hist = torch.cat([state.hist[state.count - self.carried:].view(torch.float32), self.hist])
-                self.words = torch.cat([state.words[state.count - self.carried:], self.words])
-            self.first = torch.zeros(R, device=dev, dtype=torch.int32)
-            self.s = torch.zeros((R, N), device=dev, dtype=torch.float32)
+            super().__init__(m, spec, R, S, state)
+            self.s = torch.zeros((R, spec.size), device=dev, dtype=torch.float32)
             self.top_ids = torch.full((S, R, self.top), -1, device=dev, dtype=torch.int32) if self.top else None
             self.top_nll = torch.full((S, R, self.top), float("nan"), device=dev, dtype=torch.float64) if self.top else None
-            self.flags = torch.zeros(1, device=dev, dtype=torch.int32)
+
+    def _slots(self, shape, dtype, front):
+        # (no uninitialised memory here: the carried entries and zeros behind them in one pass -- every slot is written before it is
+        #  read, DESIGN.md section 19, and the fill is the slots the copy of the carried entries leaves)
+        k = len(front) if front is not None else 0
+        rest = self.m.torch.zeros((shape[0] - k,) + shape[1:], device=self.m.device, dtype=dtype)
+        return rest if front is None else self.m.torch.cat([front, rest])
 
     @staticmethod
     def row_bytes(H, N, S, top):
         return (N + S) * (4 * H + 4) + 4 * N + 12 * S * top
 
     def op_args(self, R, S):
-        if (R, S) != (self.R, self.S):
-            raise ValueError("these rings were made for %d rows and %d steps (got %d, %d)" % (self.R, self.S, R, S))
-        return (self.hist, self.words, self.cap, self.carried, self.first, self.spec.size, self.spec.theta, self.spec.lam, self.s,
-                self.spec.size, self.top, self.top_ids, self.top_nll, self.flags)
+        return (*self.ring_args(R, S), self.spec.size, self.spec.theta, self.spec.lam, self.s, self.spec.size, self.top, self.top_ids,
+                self.top_nll, self.flags)
 
     def check(self):
         fl = int(self.flags.cpu()[0])
         if fl:
             raise _flag_error(fl)
-
-    def n_entries(self):
-        """[S]: the entries of a live row's window at each step"""
-        return np.minimum(self.carried + np.arange(self.S, dtype=np.int64), self.spec.size)
 
     def lists(self, self_norm):
         """(top_ids [S, R, top] int64, top_logp [S, R, top] float64 = log p_q under the mixture) -- after the op"""
@@ -389,11 +375,6 @@ class MixRings:
         if self_norm and self.spec.lam > 0:                # y' orders as p_q does; exp(y') sums to 1 / (1 - lam) where the cache has entries
             logp = logp + np.where(self.n_entries() > 0, np.log1p(-float(np.float32(self.spec.lam))), 0.0)[:, None, None]
         return ids, logp
-
-    def state_after(self, pos):
-        end = self.carried + self.S
-        cnt = min(end, self.spec.size)
-        return CacheState(self.m, self.hist[end - cnt:end], self.words[end - cnt:end], pos)
 
 
 class CachedRanks:
@@ -415,30 +396,17 @@ def _check_top(top, V):
 
 def rank_streams_cached(ranker, inputs, targets, cache, h=None, c=None, state=None, levels=None, top=0):
     """LSTM_Model.rank_streams_cached: see there."""
-    from .rank import _columns
     m = ranker.m
     spec = _check_mix_spec(cache)
     top = _check_top(top, m.V)
-    x = np.asarray(inputs)
-    y = np.asarray(targets)
-    if x.ndim != 2 or x.shape != y.shape:
-        raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
-    if (h is None) != (c is None):
-        raise ValueError("carry both h and c, or neither")
-    B, n = x.shape
+    x, y, B, n = check_streams(m, inputs, targets, h, c, "rank")
     _check_state(m, state, B)
-    check_ids(x, m.V, "rank")
-    check_ids(y, m.V, "rank")
-    if h is not None and (tuple(h.shape) != (B, m.H) or tuple(c.shape) != (B, m.H)):
-        raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (B, m.H, tuple(h.shape), tuple(c.shape)))
     L = levels.n_levels if levels is not None else 0
     if B == 0 or n == 0:
         return CachedRanks(np.full((B, n, L + 1), -1, dtype=np.int32), np.zeros((B, n, top), dtype=np.int64) if top else None,
                            np.zeros((B, n, top)) if top else None, np.zeros((B, n), dtype=np.int64), h, c, state)
     rings = MixRings(m, spec, B, n, state, top)
-    rk, h2, c2 = ranker.run(x.T, y.T, [B] * n, h=h, c=c, levels=levels, rings=rings)
-    flat = _columns(levels, rk.reshape(n * B, L + 1), np.ascontiguousarray(y.T).reshape(-1))
-    ranks = np.ascontiguousarray(flat.reshape(n, B, L + 1).transpose(1, 0, 2))
+    ranks, h2, c2 = ranker.streams(x, y, h, c, levels, rings)
     ids = logp = None
     if top:
         ids, logp = rings.lists(m.self_norm)
@@ -450,37 +418,11 @@ def rank_streams_cached(ranker, inputs, targets, cache, h=None, c=None, state=No
 
 def rank_cached(ranker, sequences, start, cache, levels=None, max_rows=None):
     """LSTM_Model.rank_cached: see there."""
-    from .generate import GENERATE_BUDGET_BYTES
-    from .rank import _columns
-    m = ranker.m
-    spec = _check_mix_spec(cache)
-    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
-    for s in seqs:
-        check_ids(s, m.V, "rank")
-    check_ids([start], m.V, "rank (start)")
-    L = levels.n_levels if levels is not None else 0
-    lens = [len(s) for s in seqs]
-    longest = max(lens) if lens else 0
-    if max_rows is None:
-        max_rows = clamp_rows(MAX_ROWS, GENERATE_BUDGET_BYTES, ranker.row_bytes(longest, L, spec.size), m.H)
-    out = [np.full((k, L + 1), -1, dtype=np.int32) for k in lens]
-    for ch in plan_rows(lens, max_rows):
-        idx = ch["idx"]
-        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
-        rings = MixRings(m, spec, len(idx), ch["n_steps"])
-        rk, _h, _c = ranker.run(word, target, ch["n_live"], levels=levels, rings=rings)
-        for r, i in enumerate(idx):
-            k = int(ch["lens"][r])
-            out[i] = _columns(levels, rk[:k, r, :], target[:k, r])
-    return out
+    return ranker.sentences(sequences, start, levels, max_rows, (MAX_ROWS, GENERATE_BUDGET_BYTES), _check_mix_spec(cache))
 
 
 def predict_next_cached(ranker, h, state, cache, n=10, allowed=None):
     """LSTM_Model.predict_next_cached: see there."""
-    from .complete import check_allowed
-    from .readings import ReadingIndex
-    from .rowsets import RowSets, t_is_state
-    from . import ops as _ops
     m = ranker.m
     torch = m.torch
     spec = _check_mix_spec(cache)

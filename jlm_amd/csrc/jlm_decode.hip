@@ -402,6 +402,8 @@ static bool t_is_state(const jlm_decode_model *m) { return m->untied && !m->spli
 
 // -2: a split-row model without wt8 / xgate8 (DeviceModel builds them together); -1: no T rows where T is not the state
 static int rows_refuse(const jlm_decode_model *m, const float *T) { return m->split_lstm && !m->wt8 ? -2 : !T && !t_is_state(m) ? -1 : 0; }
+// -1: a row of logits that is no multiple of 4 floats or shorter than V rounded up to one
+static int logits_refuse(int ld_logits, int V) { return ld_logits % 4 != 0 || ld_logits < ((V + 3) & ~3) ? -1 : 0; }
 
 // event i of frame f, per_frame events a frame (none when the call is untimed: events NULL)
 struct Stamps {
@@ -450,15 +452,8 @@ extern "C" int jlm_prime_frames(const jlm_decode_model *m, const jlm_prime_plan 
         const int bound = p->n_live_host[f];
         if (bound < 0 || bound > R) return -1;
         if (bound == 0) continue;
-        void *h_in = p->h[f & 1], *h_out = p->h[(f + 1) & 1];
-        float *c_in = p->c[f & 1], *c_out = p->c[(f + 1) & 1];
-        const int *prev = p->prev + (size_t)f * R, *word = p->word + (size_t)f * R, *ndev = p->n_live + f;
-        if (m->split_lstm)
-            JLM_TRY(jlm_lstm_step_xg(h_in, c_in, m->H, h_out, c_out, p->rows, prev, word, m->wt8, m->xgate8, m->H, m->gate_descale,
-                                     m->h_scale, nullptr, bound, ndev, stream));
-        else
-            JLM_TRY(jlm_lstm_step((const float *)h_in, c_in, m->H, (float *)h_out, c_out, p->rows, prev, word, m->emb, m->ld_emb, m->wt,
-                                  m->gate_bias, m->kpad, m->H, m->E, bound, ndev, stream));
+        JLM_TRY(rows_lstm_step(m, p->h[f & 1], p->c[f & 1], p->h[(f + 1) & 1], p->c[(f + 1) & 1], p->rows, p->prev + (size_t)f * R,
+                               p->word + (size_t)f * R, nullptr, bound, p->n_live + f, stream));
     }
     return 0;
 }
@@ -499,6 +494,29 @@ extern "C" int jlm_seed_context(const void *src_h, const float *src_c, int H, co
     return (int)hipGetLastError();
 }
 
+// The steps of a teacher-forced loop (score_loop, rank_loop) over a plan's live rows, a prefix of its row sets.  Step t: its bound (-1
+// for one outside 0 .. n_rows, before anything is recorded), stamp 0, the LSTM step, stamp 1, the T projection, stamp 2; then
+// tail(t, bound, ndev, target, s) with the step's live count on the device, its targets and its state sets.
+template <class Plan, class Tail>
+static int forced_steps(const jlm_decode_model *m, const Plan *p, const Stamps &stamp, void *stream, Tail tail) {
+    const int R = p->n_rows;
+    for (int t = 0; t < p->n_steps; ++t) {
+        const int bound = p->n_live_host ? p->n_live_host[t] : R;
+        if (bound < 0 || bound > R) return -1;
+        const int *ndev = p->n_live + t;
+        const PingPong s(m, p->h, p->c, p->T, t);         // (word[] and prev[] are indexed by the row: g = rows[r] = r)
+        JLM_TRY(stamp(t, 0));
+        if (bound > 0)
+            JLM_TRY(rows_lstm_step(m, s.h_in, s.c_in, s.h_out, s.c_out, p->rows, t == 0 ? p->prev0 : p->rows, p->word + (size_t)t * R, p->T,
+                                   bound, ndev, stream));
+        JLM_TRY(stamp(t, 1));
+        if (bound > 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, bound, ndev, stream));
+        JLM_TRY(stamp(t, 2));
+        JLM_TRY(tail(t, bound, ndev, p->target + (size_t)t * R, s));
+    }
+    return 0;
+}
+
 // Teacher-forced scoring (include/jlm_hip.h jlm_score_frames): per step the LSTM step of the live rows (a prefix of the row sets),
 // T, the full-vocabulary normaliser as the frame loop launches it for kind 0, and the fold into -log p of the target word.
 // after_step(t, bound, h_out): called behind step t's last stamp with the state set the step wrote (jlm_score_cache_frames' copies;
@@ -511,18 +529,7 @@ static int score_loop(const jlm_decode_model *m, const jlm_score_plan *p, void *
     JLM_TRY(rows_refuse(m, p->T));
     if (!m->self_norm && (!p->part || p->max_parts < 1)) return -1;
     const Stamps stamp{events, JLM_SCORE_EVENTS_PER_STEP, stream};
-    for (int t = 0; t < S; ++t) {
-        const int bound = p->n_live_host ? p->n_live_host[t] : R;
-        if (bound < 0 || bound > R) return -1;
-        const int *ndev = p->n_live + t;
-        const int *word = p->word + (size_t)t * R, *target = p->target + (size_t)t * R;
-        const PingPong s(m, p->h, p->c, p->T, t);         // (word[] and prev[] are indexed by the row: g = rows[r] = r)
-        const int *prev = t == 0 ? p->prev0 : p->rows;
-        JLM_TRY(stamp(t, 0));
-        if (bound > 0) JLM_TRY(rows_lstm_step(m, s.h_in, s.c_in, s.h_out, s.c_out, p->rows, prev, word, p->T, bound, ndev, stream));
-        JLM_TRY(stamp(t, 1));
-        if (bound > 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, bound, ndev, stream));
-        JLM_TRY(stamp(t, 2));
+    return forced_steps(m, p, stamp, stream, [&](int t, int bound, const int *ndev, const int *target, const PingPong &s) -> int {
         int n_parts = 0;
         if (bound > 0 && !m->self_norm) {
             FullLse fl;
@@ -535,9 +542,8 @@ static int score_loop(const jlm_decode_model *m, const jlm_score_plan *p, void *
             JLM_TRY(jlm_score_fold(m->segs, m->n_segs, m->b2, s.T, m->ldt, p->part, R, n_parts, m->self_norm, target, ndev, bound,
                                    p->nll_seq, p->nll_tok ? p->nll_tok + (size_t)t * R : nullptr, p->flags, stream));
         JLM_TRY(stamp(t, 4));
-        JLM_TRY(after_step(t, bound, s.h_out));
-    }
-    return 0;
+        return after_step(t, bound, s.h_out);
+    });
 }
 
 extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan *p, void *stream, void *const *events) {
@@ -549,6 +555,12 @@ int jlm_cache_refuse(const void *hist, const int *words, int cap, int n_rows, in
                      const int *first, const int *len, int N, const float *thetas, int n_theta, const float *lpc);
 // the copy behind a step: rows 0 .. bound - 1 of the written state set and the step's targets into their ring slot (csrc/jlm_cache.hip)
 int jlm_cache_store(const void *h_rows, const int *target, int bound, int H, void *hist_slot, int *words_slot, void *stream);
+// ... of step t of a cached loop over R rows, into slot (pos0 + t) % cap of the plan's rings
+template <class CachePlan>
+static int ring_store(const CachePlan *cp, int t, const void *h_out, const int *target, int bound, int R, int H, void *stream) {
+    const size_t slot = (size_t)((cp->pos0 + t) % cp->cap);
+    return jlm_cache_store(h_out, target + (size_t)t * R, bound, H, (char *)cp->hist + slot * R * H * 4, cp->words + slot * R, stream);
+}
 
 // Cached scoring (include/jlm_hip.h jlm_score_cache_frames): score_loop with the written state rows and the targets of every step
 // copied into the rings, and cache_rows_kernel once behind the last step.
@@ -559,11 +571,8 @@ extern "C" int jlm_score_cache_frames(const jlm_decode_model *m, const jlm_score
     const int split = m->split_lstm ? 1 : 0;
     JLM_TRY(jlm_cache_refuse(cp->hist, cp->words, cp->cap, R, m->H, split, m->h_scale, cp->pos0, S, cp->first, cp->len, cp->N, cp->thetas,
                              cp->n_theta, cp->lpc));
-    const size_t row_bytes = (size_t)m->H * 4;
-    JLM_TRY(score_loop(m, p, stream, events, [&](int t, int bound, const void *h_out) -> int {
-        const size_t slot = (size_t)((cp->pos0 + t) % cp->cap);
-        return jlm_cache_store(h_out, p->target + (size_t)t * R, bound, m->H, (char *)cp->hist + slot * R * row_bytes, cp->words + slot * R, stream);
-    }));
+    JLM_TRY(score_loop(m, p, stream, events,
+                       [&](int t, int bound, const void *h_out) { return ring_store(cp, t, h_out, p->target, bound, R, m->H, stream); }));
     if (R <= 0 || S <= 0) return 0;
     return jlm_cache_rows(cp->hist, cp->words, cp->cap, R, m->H, split, m->h_scale, cp->pos0, S, cp->first, cp->len, cp->N, cp->thetas,
                           cp->n_theta, cp->lpc, cp->flags, stream);
@@ -583,21 +592,10 @@ static int rank_loop(const jlm_decode_model *m, const jlm_rank_plan *p, void *st
     if (R == 0 || S == 0) return 0;
     JLM_TRY(rows_refuse(m, p->T));
     const int V = m->segs[m->n_segs - 1].v_end;
-    if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
+    JLM_TRY(logits_refuse(p->ld_logits, V));
     const Stamps stamp{events, per_step, stream};
     const size_t ld_rank = (size_t)p->n_levels + 1;
-    for (int t = 0; t < S; ++t) {
-        const int bound = p->n_live_host ? p->n_live_host[t] : R;
-        if (bound < 0 || bound > R) return -1;
-        const int *ndev = p->n_live + t;
-        const int *word = p->word + (size_t)t * R, *target = p->target + (size_t)t * R;
-        const PingPong s(m, p->h, p->c, p->T, t);
-        const int *prev = t == 0 ? p->prev0 : p->rows;
-        JLM_TRY(stamp(t, 0));
-        if (bound > 0) JLM_TRY(rows_lstm_step(m, s.h_in, s.c_in, s.h_out, s.c_out, p->rows, prev, word, p->T, bound, ndev, stream));
-        JLM_TRY(stamp(t, 1));
-        if (bound > 0) JLM_TRY(rows_t_projection(m, s.h_out, p->rows, s.T, bound, ndev, stream));
-        JLM_TRY(stamp(t, 2));
+    return forced_steps(m, p, stamp, stream, [&](int t, int bound, const int *ndev, const int *target, const PingPong &s) -> int {
         if (bound > 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, bound, stream));
         JLM_TRY(stamp(t, 3));
         JLM_TRY(before_rank(t, bound, s.h_out, ndev, stamp));
@@ -605,9 +603,8 @@ static int rank_loop(const jlm_decode_model *m, const jlm_rank_plan *p, void *st
             JLM_TRY(jlm_rank_rows(p->logits, p->ld_logits, V, bound, ndev, target, p->ids, p->n_ids, p->lv_off, p->lv_lo, p->lv_hi, p->n_levels,
                                   p->rank + (size_t)t * R * ld_rank, p->flags, stream));
         JLM_TRY(after_rank(t, bound, s.h_out));
-        JLM_TRY(stamp(t, per_step - 1));
-    }
-    return 0;
+        return stamp(t, per_step - 1);
+    });
 }
 
 extern "C" int jlm_rank_frames(const jlm_decode_model *m, const jlm_rank_plan *p, void *stream, void *const *events) {
@@ -642,7 +639,6 @@ extern "C" int jlm_rank_cache_frames(const jlm_decode_model *m, const jlm_rank_p
     if (p->n_live_host)
         for (int t = 0; t < S; ++t)
             if (p->n_live_host[t] < 0 || p->n_live_host[t] > R) return -1;
-    const size_t row_bytes = (size_t)m->H * 4;
     return rank_loop(
         m, p, stream, events, JLM_RANK_CACHE_EVENTS_PER_STEP,
         [&](int t, int bound, const void *h_out, const int *ndev, const Stamps &stamp) -> int {
@@ -661,9 +657,7 @@ extern "C" int jlm_rank_cache_frames(const jlm_decode_model *m, const jlm_rank_p
                 JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, p->n_live_host[t], cp->top_k, m->self_norm,
                                       cp->top_ids + (size_t)t * R * cp->top_k, cp->top_nll + (size_t)t * R * cp->top_k, cp->top_k, p->flags,
                                       stream));
-            const size_t slot = (size_t)((cp->pos0 + t) % cp->cap);
-            return jlm_cache_store(h_out, p->target + (size_t)t * R, bound, m->H, (char *)cp->hist + slot * R * row_bytes,
-                                   cp->words + slot * R, stream);
+            return ring_store(cp, t, h_out, p->target, bound, R, m->H, stream);
         });
 }
 
@@ -712,7 +706,7 @@ static int generate_frames(const jlm_decode_model *m, const jlm_generate_plan *p
     if (R == 0 || N == 0) return 0;
     JLM_TRY(rows_refuse(m, p->T));
     const int V = m->segs[m->n_segs - 1].v_end;
-    if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
+    JLM_TRY(logits_refuse(p->ld_logits, V));
     if (p->n_live_host[P - 1] != R) return -1;                  // every row is live at the last prompt frame (right-aligned prompts)
     const Stamps stamp{events, JLM_GENERATE_EVENTS_PER_FRAME, stream};
     const int F = P + N - 1;
@@ -760,7 +754,7 @@ static int complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p
     const int V = m->segs[m->n_segs - 1].v_end;
     if (B > V || (long long)NP * B > 0x7fffffff) return -1;
     const int R = NP * B;
-    if (p->ld_logits % 4 != 0 || p->ld_logits < ((V + 3) & ~3)) return -1;
+    JLM_TRY(logits_refuse(p->ld_logits, V));
     if (p->n_live_host[P - 1] != NP) return -1;                 // every prompt is live at the last prompt frame (right-aligned)
     const Stamps stamp{events, JLM_COMPLETE_EVENTS_PER_FRAME, stream};
     const int F = P + N - 1;

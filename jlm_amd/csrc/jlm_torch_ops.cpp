@@ -98,6 +98,11 @@ template <class T = void> T *optr(const OptTensor &t, const char *name) {
     return ptr<T>(*t, name);
 }
 
+// what the ops' argument checks ask of a tensor: of type `ty` with n elements or more; an optional one: given; given and so, or not given
+bool is(const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; }
+bool has(const OptTensor &t) { return t.has_value() && t->defined(); }
+bool opt_ok(const OptTensor &t, at::ScalarType ty, int64_t n) { return !has(t) || is(*t, ty, n); }
+
 // the current torch stream of the device the tensor lives on (ops never switch devices themselves: the caller's
 // torch.cuda.device context / set_device is what the HIP runtime launches on)
 hipStream_t stream_of(const Tensor &t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
@@ -554,7 +559,6 @@ void prime_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, c
                   int64_t n_rows, int64_t n_steps) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, S = n_steps;
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     check_row_sets("prime_frames", m, R, h0, c0, h1, c1, n_live_host, S, "frame", R);
     TORCH_CHECK(is(rows, at::kInt, R) && is(prev, at::kInt, S * R) && is(word, at::kInt, S * R) && is(n_live, at::kInt, S),
                 "jlm.prime_frames: int32 rows [n_rows], prev / word [n_steps][n_rows], n_live [n_steps]");
@@ -578,7 +582,6 @@ void seed_context(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &src_h, 
     JlmPlan &pl = *plan;
     TORCH_CHECK(pl.ctx_H > 0 && pl.p.ctx_prev && pl.p.ctx_word, "jlm.seed_context: the plan was made without ctx_prev / ctx_word");
     const int64_t H = pl.ctx_H, n_src = last.numel();
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(src_h.defined() && src_h.element_size() == 4 && src_h.numel() >= n_src * H && is(src_c, at::kFloat, n_src * H) &&
                     is(last, at::kInt, n_src) && is(has, at::kInt, n_src) && is(idx, at::kInt, pl.lat.n_sent),
                 "jlm.seed_context: src_h / src_c [n_src, H] of 4-byte values, int32 last / has [n_src], idx [n_sent]");
@@ -601,7 +604,6 @@ void tail_predict(const c10::intrusive_ptr<JlmModel> &model, const c10::intrusiv
     JlmPlan &pl = *plan;
     const jlm_decode_model &m = model->m;
     const int64_t B = pl.lat.n_sent, R = B * n_out;
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(pl.p.kind != 2 && pl.lat.n_frames >= 1, "jlm.tail_predict: the plan must have run a static decode");
     TORCH_CHECK(n_out >= 1 && n_out <= 64 && stride >= 1 && chunk >= 0 && chunk <= (1 << 20), "jlm.tail_predict: n_out is 1 .. 64, stride >= 1, chunk >= 0");
     TORCH_CHECK(is(ids, at::kInt, 1) && is(sp_off, at::kInt, B + 1) && sp_frame.defined() && is(sp_lo, at::kInt, sp_frame.numel()) &&
@@ -627,34 +629,42 @@ void tail_predict(const c10::intrusive_ptr<JlmModel> &model, const c10::intrusiv
 // flags one int32 (optional).  Every id must lie in [0, V): the caller checks (jlm_amd/score.py) -- the kernels index with them.
 // -> timed: [n_steps, 4] milliseconds per step (LSTM step, T projection, normaliser, fold) after waiting for the last step; else an
 // empty tensor and nothing waits.
-// (the checked jlm_score_plan of score_frames and score_cache_frames; live_host keeps the plan's host counts alive)
-struct ScorePlanArgs {
-    jlm_score_plan p{};
+// (the checked "forced rows" of a teacher-forced plan, jlm_score_plan or jlm_rank_plan: the state row sets, T, rows / prev0, word / target
+//  and n_live; live_host keeps the plan's host counts alive)
+template <class Plan> struct ForcedPlanArgs {
+    Plan p{};
     std::vector<int> live_host;
-    ScorePlanArgs(const char *op, const jlm_decode_model &m, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
-                  const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
-                  const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, const std::vector<int64_t> &n_live_host,
-                  const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t R, int64_t S)
+    ForcedPlanArgs(const char *op, const jlm_decode_model &m, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                   const OptTensor &T, const Tensor &rows, const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live,
+                   const std::vector<int64_t> &n_live_host, int64_t R, int64_t S)
         : live_host(n_live_host.begin(), n_live_host.end()) {
-        auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-        auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
         check_row_sets(op, m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
         TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
                         is(n_live, at::kInt, S),
                     "jlm.", op, ": int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
-        TORCH_CHECK(is(nll_seq, at::kDouble, R) && (!has(nll_tok) || is(*nll_tok, at::kDouble, S * R)) && (!has(flags) || is(*flags, at::kInt, 1)),
-                    "jlm.", op, ": float64 nll_seq [n_rows] / nll_tok [n_steps][n_rows], int32 flags");
         TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.", op, ": T [n_rows, ldt] float32");
-        TORCH_CHECK(!has(part) || (is(*part, at::kFloat, max_parts * R * 2) && max_parts >= 1), "jlm.", op, ": part [max_parts][n_rows][2]");
-        TORCH_CHECK(!has(Tm) || (ld_tm > 0 && Tm->numel() >= ((R + 31) / 32 * 32) * ld_tm), "jlm.", op, ": Tm (whole 32-row blocks of ld_tm)");
         p.n_rows = (int)R; p.n_steps = (int)S;
         p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
         p.T = optr<float>(T, "T");
-        p.Tm = optr<void>(Tm, "Tm"); p.ld_tm = p.Tm ? (int)ld_tm : 0;
-        p.part = optr<float>(part, "part"); p.max_parts = p.part ? (int)max_parts : 0;
         p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
         p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
         p.n_live_host = live_host.data();
+    }
+};
+
+// (the checked jlm_score_plan of score_frames and score_cache_frames)
+struct ScorePlanArgs : ForcedPlanArgs<jlm_score_plan> {
+    ScorePlanArgs(const char *op, const jlm_decode_model &m, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                  const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
+                  const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, const std::vector<int64_t> &n_live_host,
+                  const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t R, int64_t S)
+        : ForcedPlanArgs(op, m, h0, c0, h1, c1, T, rows, prev0, word, target, n_live, n_live_host, R, S) {
+        TORCH_CHECK(is(nll_seq, at::kDouble, R) && opt_ok(nll_tok, at::kDouble, S * R) && opt_ok(flags, at::kInt, 1),
+                    "jlm.", op, ": float64 nll_seq [n_rows] / nll_tok [n_steps][n_rows], int32 flags");
+        TORCH_CHECK(!has(part) || (is(*part, at::kFloat, max_parts * R * 2) && max_parts >= 1), "jlm.", op, ": part [max_parts][n_rows][2]");
+        TORCH_CHECK(!has(Tm) || (ld_tm > 0 && Tm->numel() >= ((R + 31) / 32 * 32) * ld_tm), "jlm.", op, ": Tm (whole 32-row blocks of ld_tm)");
+        p.Tm = optr<void>(Tm, "Tm"); p.ld_tm = p.Tm ? (int)ld_tm : 0;
+        p.part = optr<float>(part, "part"); p.max_parts = p.part ? (int)max_parts : 0;
         p.nll_seq = ptr<double>(nll_seq, "nll_seq"); p.nll_tok = optr<double>(nll_tok, "nll_tok"); p.flags = optr<int>(flags, "flags");
     }
 };
@@ -671,6 +681,28 @@ Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0,
                          [&](hipStream_t st, void *const *ev) { return jlm_score_frames(&m, &sp.p, st, ev); });
 }
 
+// The ring of a cache op, checked, into its plan (jlm_cache_plan, jlm_cache_mix_plan, jlm_predict_cache_plan): hist, words, cap and N; the
+// caller has checked its own bounds on cap and its position.
+template <class Plan>
+void ring_into(const char *op, Plan &cp, int64_t H, int64_t R, const Tensor &hist, const Tensor &words, int64_t cap, int64_t N) {
+    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * H && is(words, at::kInt, cap * R),
+                "jlm.", op, ": hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
+    cp.hist = ptr<void>(hist, "hist"); cp.words = ptr<int>(words, "words"); cp.cap = (int)cap; cp.N = (int)N;
+}
+
+// ... of a mixing op (rank_cache_frames, predict_cache_rows), with their bounds -- `steps` positions behind `pos`, which the message
+// calls `pos_text` -- and theta, lam, ld_s
+template <class Plan>
+void mix_ring_into(const char *op, Plan &cp, int64_t H, int64_t R, const Tensor &hist, const Tensor &words, int64_t cap, int64_t pos,
+                   int64_t steps, const char *pos_text, int64_t N, double theta, double lam, int64_t ld_s) {
+    TORCH_CHECK(N >= 1 && N <= JLM_CACHE_MIX_MAX_N && cap >= N && cap <= INT32_MAX && pos >= 0 && pos + steps + cap < INT32_MAX && ld_s >= N &&
+                    ld_s <= INT32_MAX,
+                "jlm.", op, ": 1 <= N <= ", JLM_CACHE_MIX_MAX_N, ", cap >= N, ld_s >= N, ", pos_text, " + cap < 2^31");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam >= 0.0 && lam < 1.0, "jlm.", op, ": theta finite and >= 0, lam in [0, 1)");
+    ring_into(op, cp, H, R, hist, words, cap, N);
+    cp.theta = (float)theta; cp.lam = (float)lam; cp.ld_s = (int)ld_s;
+}
+
 // score_frames with the continuous cache (jlm_score_cache_frames, include/jlm_hip.h): its arguments, then the rings hist
 // [cap][n_rows][H] (4-byte values, the model's state-row format) and words [cap][n_rows] int32 with the carried entries in their slots,
 // pos0, first / len [n_rows] int32 on the device, N, thetas (host), lpc [n_theta][n_steps][n_rows] float32, cache_flags one int32.
@@ -683,23 +715,18 @@ Tensor score_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tenso
                           std::vector<double> thetas, const Tensor &lpc, const OptTensor &cache_flags) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, S = n_steps;
-    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     const ScorePlanArgs sp("score_cache_frames", m, h0, c0, h1, c1, T, Tm, ld_tm, part, max_parts, rows, prev0, word, target, n_live,
                            n_live_host, nll_seq, nll_tok, flags, R, S);
     const int64_t n_theta = (int64_t)thetas.size();
     TORCH_CHECK(n_theta >= 1 && n_theta <= JLM_CACHE_MAX_THETAS, "jlm.score_cache_frames: 1 .. ", JLM_CACHE_MAX_THETAS, " values of theta");
     TORCH_CHECK(N >= 1 && cap >= N + S && cap <= INT32_MAX && pos0 >= 0 && pos0 + S + cap < INT32_MAX,
                 "jlm.score_cache_frames: N >= 1, cap >= N + n_steps, 0 <= pos0, pos0 + n_steps + cap < 2^31");
-    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
-                "jlm.score_cache_frames: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
-    TORCH_CHECK(is(first, at::kInt, R) && is(len, at::kInt, R) && is(lpc, at::kFloat, n_theta * S * R) &&
-                    (!has(cache_flags) || is(*cache_flags, at::kInt, 1)),
+    jlm_cache_plan cp{};
+    ring_into("score_cache_frames", cp, m.H, R, hist, words, cap, N);
+    TORCH_CHECK(is(first, at::kInt, R) && is(len, at::kInt, R) && is(lpc, at::kFloat, n_theta * S * R) && opt_ok(cache_flags, at::kInt, 1),
                 "jlm.score_cache_frames: int32 first / len [n_rows], float32 lpc [n_theta][n_steps][n_rows], int32 cache_flags");
     std::vector<float> th(thetas.begin(), thetas.end());
-    jlm_cache_plan cp{};
-    cp.hist = ptr<void>(hist, "hist"); cp.words = ptr<int>(words, "words"); cp.cap = (int)cap; cp.pos0 = (int)pos0;
-    cp.first = ptr<const int>(first, "first"); cp.len = ptr<const int>(len, "len"); cp.N = (int)N;
+    cp.pos0 = (int)pos0; cp.first = ptr<const int>(first, "first"); cp.len = ptr<const int>(len, "len");
     cp.thetas = th.data(); cp.n_theta = (int)n_theta;
     cp.lpc = ptr<float>(lpc, "lpc"); cp.flags = optr<int>(cache_flags, "cache_flags");
     return launch_frames("jlm_score_cache_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
@@ -713,7 +740,6 @@ struct RankLevels {
     int n_ids = 0;
     RankLevels(const char *op, const OptTensor &ids_t, const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_cols,
                int64_t n_levels) {
-        auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
         auto is_int = [&](const OptTensor &t, int64_t n) { return has(t) && t->scalar_type() == at::kInt && t->numel() >= n; };
         TORCH_CHECK(n_levels >= 0 && n_levels <= JLM_RANK_MAX_LEVELS, "jlm.", op, ": n_levels in 0 .. ", JLM_RANK_MAX_LEVELS);
         if (!has(lv_off)) return;
@@ -734,8 +760,6 @@ struct RankLevels {
 void rank_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, const Tensor &target,
                const OptTensor &ids, const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels,
                const Tensor &rank, const OptTensor &flags) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    auto opt_ok = [&](const OptTensor &t, at::ScalarType ty, int64_t n) { return !t.has_value() || !t->defined() || is(*t, ty, n); };
     TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && ld >= 0 && is(y, at::kFloat, n_rows * ld), "jlm.rank_rows: y [n_rows, ld] float32");
     const RankLevels lv("rank_rows", ids, lv_off, lv_lo, lv_hi, n_cols, n_levels);
     TORCH_CHECK(is(target, at::kInt, n_rows) && is(rank, at::kInt, n_rows * (n_levels + 1)) && opt_ok(n_dev, at::kInt, 1) &&
@@ -752,37 +776,22 @@ void rank_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, cons
 // sets, rows / prev0 / word / target / n_live, generate_frames' logits [n_rows, ld_logits], rank_rows' level table; rank int32
 // [n_steps][n_rows][n_levels + 1].  Every id must lie in [0, V): the caller checks (jlm_amd/rank.py).  -> timed: [n_steps, 4]
 // milliseconds per step (LSTM step, T projection, logit GEMMs, ranking) after waiting for the last step; else an empty tensor.
-// (the checked jlm_rank_plan of rank_frames and rank_cache_frames; live_host keeps the plan's host counts alive)
-struct RankPlanArgs {
-    jlm_rank_plan p{};
-    std::vector<int> live_host;
+// (the checked jlm_rank_plan of rank_frames and rank_cache_frames)
+struct RankPlanArgs : ForcedPlanArgs<jlm_rank_plan> {
     int64_t V = 0;
     RankPlanArgs(const char *op, const jlm_decode_model &m, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
                  const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0, const Tensor &word,
                  const Tensor &target, const Tensor &n_live, const std::vector<int64_t> &n_live_host, const OptTensor &ids,
                  const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels, const Tensor &rank,
                  const OptTensor &flags, int64_t R, int64_t S)
-        : live_host(n_live_host.begin(), n_live_host.end()) {
-        auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-        auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-        check_row_sets(op, m, R, h0, c0, h1, c1, n_live_host, S, "step", R);
+        : ForcedPlanArgs(op, m, h0, c0, h1, c1, T, rows, prev0, word, target, n_live, n_live_host, R, S) {
         TORCH_CHECK(m.n_segs >= 1, "jlm.", op, ": a model without segments");
         V = m.segs[m.n_segs - 1].v_end;
         const RankLevels lv(op, ids, lv_off, lv_lo, lv_hi, V, n_levels);
-        TORCH_CHECK(is(rows, at::kInt, R) && is(prev0, at::kInt, R) && is(word, at::kInt, S * R) && is(target, at::kInt, S * R) &&
-                        is(n_live, at::kInt, S),
-                    "jlm.", op, ": int32 rows / prev0 [n_rows], word / target [n_steps][n_rows], n_live [n_steps]");
-        TORCH_CHECK(is(rank, at::kInt, S * R * (n_levels + 1)) && (!has(flags) || is(*flags, at::kInt, 1)),
+        TORCH_CHECK(is(rank, at::kInt, S * R * (n_levels + 1)) && opt_ok(flags, at::kInt, 1),
                     "jlm.", op, ": int32 rank [n_steps][n_rows][n_levels + 1], int32 flags");
-        TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.", op, ": T [n_rows, ldt] float32");
         TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.", op, ": logits [n_rows, ld_logits] float32");
-        p.n_rows = (int)R; p.n_steps = (int)S;
-        p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
-        p.T = optr<float>(T, "T");
         p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits;
-        p.rows = ptr<const int>(rows, "rows"); p.prev0 = ptr<const int>(prev0, "prev0");
-        p.word = ptr<const int>(word, "word"); p.target = ptr<const int>(target, "target"); p.n_live = ptr<const int>(n_live, "n_live");
-        p.n_live_host = live_host.data();
         p.ids = lv.ids; p.n_ids = lv.n_ids; p.lv_off = lv.off; p.lv_lo = lv.lo; p.lv_hi = lv.hi; p.n_levels = (int)n_levels;
         p.rank = ptr<int>(rank, "rank"); p.flags = optr<int>(flags, "flags");
     }
@@ -815,25 +824,16 @@ Tensor rank_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor
                          int64_t top_k, const OptTensor &top_ids, const OptTensor &top_nll, const OptTensor &cache_flags) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, S = n_steps;
-    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     const RankPlanArgs rp("rank_cache_frames", m, h0, c0, h1, c1, T, logits, ld_logits, rows, prev0, word, target, n_live, n_live_host, ids,
                           lv_off, lv_lo, lv_hi, n_levels, rank, flags, R, S);
-    TORCH_CHECK(N >= 1 && N <= JLM_CACHE_MIX_MAX_N && cap >= N && cap <= INT32_MAX && pos0 >= 0 && pos0 + S + cap < INT32_MAX && ld_s >= N &&
-                    ld_s <= INT32_MAX,
-                "jlm.rank_cache_frames: 1 <= N <= ", JLM_CACHE_MIX_MAX_N, ", cap >= N, ld_s >= N, 0 <= pos0, pos0 + n_steps + cap < 2^31");
-    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam >= 0.0 && lam < 1.0, "jlm.rank_cache_frames: theta finite and >= 0, lam in [0, 1)");
-    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
-                "jlm.rank_cache_frames: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
-    TORCH_CHECK(is(first, at::kInt, R) && is(s, at::kFloat, R * ld_s) && (!has(cache_flags) || is(*cache_flags, at::kInt, 1)),
+    jlm_cache_mix_plan cp{};
+    mix_ring_into("rank_cache_frames", cp, m.H, R, hist, words, cap, pos0, S, "0 <= pos0, pos0 + n_steps", N, theta, lam, ld_s);
+    TORCH_CHECK(is(first, at::kInt, R) && is(s, at::kFloat, R * ld_s) && opt_ok(cache_flags, at::kInt, 1),
                 "jlm.rank_cache_frames: int32 first [n_rows], float32 s [n_rows][ld_s], int32 cache_flags");
     TORCH_CHECK(top_k >= 0 && top_k <= JLM_TOPK_MAX && top_k <= rp.V &&
                     (top_k == 0 || (has(top_ids) && has(top_nll) && is(*top_ids, at::kInt, S * R * top_k) && is(*top_nll, at::kDouble, S * R * top_k))),
                 "jlm.rank_cache_frames: top_k in 0 .. min(", JLM_TOPK_MAX, ", V) with int32 top_ids / float64 top_nll [n_steps][n_rows][top_k]");
-    jlm_cache_mix_plan cp{};
-    cp.hist = ptr<void>(hist, "hist"); cp.words = ptr<int>(words, "words"); cp.cap = (int)cap; cp.pos0 = (int)pos0;
-    cp.first = ptr<const int>(first, "first"); cp.N = (int)N; cp.theta = (float)theta; cp.lam = (float)lam;
-    cp.s = ptr<float>(s, "s"); cp.ld_s = (int)ld_s; cp.top_k = (int)top_k;
+    cp.pos0 = (int)pos0; cp.first = ptr<const int>(first, "first"); cp.s = ptr<float>(s, "s"); cp.top_k = (int)top_k;
     cp.top_ids = top_k > 0 ? ptr<int>(*top_ids, "top_ids") : nullptr; cp.top_nll = top_k > 0 ? ptr<double>(*top_nll, "top_nll") : nullptr;
     cp.flags = optr<int>(cache_flags, "cache_flags");
     return launch_frames("jlm_rank_cache_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_CACHE_EVENTS_PER_STEP,
@@ -844,8 +844,6 @@ Tensor rank_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor
 void sample_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, double temperature, int64_t seed,
                  int64_t step, const OptTensor &row_id, const OptTensor &forced, const OptTensor &done, int64_t stop_id, bool self_norm,
                  const Tensor &word, const Tensor &ids, const Tensor &nll, const OptTensor &flags) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    auto opt_ok = [&](const OptTensor &t, at::ScalarType ty, int64_t n) { return !t.has_value() || !t->defined() || is(*t, ty, n); };
     TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.sample_rows: y [n_rows, ld] float32");
     TORCH_CHECK(is(word, at::kInt, n_rows) && is(ids, at::kInt, n_rows) && is(nll, at::kDouble, n_rows) && opt_ok(n_dev, at::kInt, 1) &&
                     opt_ok(row_id, at::kInt, n_rows) && opt_ok(forced, at::kInt, n_rows) && opt_ok(done, at::kInt, n_rows) &&
@@ -865,8 +863,6 @@ void sample_rows_trunc(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_ro
                        int64_t seed, int64_t step, const OptTensor &row_id, const OptTensor &forced, const OptTensor &done,
                        int64_t stop_id, bool self_norm, int64_t top_k, double top_p, const Tensor &word, const Tensor &ids,
                        const Tensor &nll, const OptTensor &flags) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
-    auto opt_ok = [&](const OptTensor &t, at::ScalarType ty, int64_t n) { return !t.has_value() || !t->defined() || is(*t, ty, n); };
     TORCH_CHECK(top_p > 0.0, "jlm.sample_rows_trunc: top_p in (0, 1] (>= 1: off)");
     TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.sample_rows_trunc: y [n_rows, ld] float32");
     TORCH_CHECK(is(word, at::kInt, n_rows) && is(ids, at::kInt, n_rows) && is(nll, at::kDouble, n_rows) && opt_ok(n_dev, at::kInt, 1) &&
@@ -898,8 +894,6 @@ Tensor generate_frames_trunc(const c10::intrusive_ptr<JlmModel> &model, const Te
                              int64_t n_words, bool timed, int64_t top_k, double top_p) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows, P = n_prompt, N = n_words;
-    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(P >= 1 && N >= 0, "jlm.generate_frames: n_prompt >= 1 and n_words >= 0");
     TORCH_CHECK(top_p > 0.0, "jlm.generate_frames_trunc: top_p in (0, 1] (>= 1: off)");
     top_k = std::min<int64_t>(std::max<int64_t>(top_k, 0), INT32_MAX);
@@ -943,7 +937,6 @@ Tensor generate_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
 // float64 [n_rows, ld_out].
 void topk_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, int64_t k, bool self_norm, const Tensor &ids, const Tensor &nll,
                int64_t ld_out, const OptTensor &flags) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.topk_rows: y [n_rows, ld] float32");
     TORCH_CHECK(is(ids, at::kInt, n_rows * ld_out) && is(nll, at::kDouble, n_rows * ld_out) &&
                     (!flags.has_value() || !flags->defined() || is(*flags, at::kInt, 1)),
@@ -974,7 +967,6 @@ Tensor check_word_sets(const char *op, const Tensor &mask, int64_t ld_mask, int6
 void topk_rows_masked(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, int64_t k, bool self_norm, const Tensor &mask,
                       int64_t ld_mask, int64_t n_sets, std::vector<int64_t> row_set, const Tensor &ids, const Tensor &nll, int64_t ld_out,
                       const OptTensor &flags) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(n_rows >= 0 && n_cols >= 1 && is(y, at::kFloat, n_rows * ld), "jlm.topk_rows_masked: y [n_rows, ld] float32");
     TORCH_CHECK(is(ids, at::kInt, n_rows * ld_out) && is(nll, at::kDouble, n_rows * ld_out) &&
                     (!flags.has_value() || !flags->defined() || is(*flags, at::kInt, 1)),
@@ -1000,8 +992,6 @@ void predict_cache_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor 
                         const Tensor &nll, const OptTensor &flags, const OptTensor &cache_flags, int64_t n_rows) {
     const jlm_decode_model &m = model->m;
     const int64_t R = n_rows;
-    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(m.n_segs >= 1, "jlm.predict_cache_rows: a model without segments");
     TORCH_CHECK(!(m.untied && m.split_lstm), "jlm.predict_cache_rows: an untied split-row model keeps the f32 copy of its state, which its "
                                              "vocabulary GEMMs read, only inside the LSTM step: there is no one-step form for it");
@@ -1010,14 +1000,9 @@ void predict_cache_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor 
                 "jlm.predict_cache_rows: h [n_rows, H] of 4-byte values, int32 rows [n_rows], n_rows <= 65535");
     TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.predict_cache_rows: T [n_rows, ldt] float32");
     TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.predict_cache_rows: logits [n_rows, ld_logits] float32");
-    TORCH_CHECK(N >= 1 && N <= JLM_CACHE_MIX_MAX_N && cap >= N && cap <= INT32_MAX && pos >= 0 && pos + cap < INT32_MAX && ld_s >= N &&
-                    ld_s <= INT32_MAX,
-                "jlm.predict_cache_rows: 1 <= N <= ", JLM_CACHE_MIX_MAX_N, ", cap >= N, ld_s >= N, 0 <= pos, pos + cap < 2^31");
-    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam >= 0.0 && lam < 1.0, "jlm.predict_cache_rows: theta finite and >= 0, lam in [0, 1)");
-    TORCH_CHECK(hist.defined() && hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
-                "jlm.predict_cache_rows: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
-    TORCH_CHECK(is(first, at::kInt, R) && is(s, at::kFloat, R * ld_s) && (!has(cache_flags) || is(*cache_flags, at::kInt, 1)) &&
-                    (!has(flags) || is(*flags, at::kInt, 1)),
+    jlm_predict_cache_plan p{};
+    mix_ring_into("predict_cache_rows", p, m.H, R, hist, words, cap, pos, 0, "0 <= pos, pos", N, theta, lam, ld_s);
+    TORCH_CHECK(is(first, at::kInt, R) && is(s, at::kFloat, R * ld_s) && opt_ok(cache_flags, at::kInt, 1) && opt_ok(flags, at::kInt, 1),
                 "jlm.predict_cache_rows: int32 first [n_rows], float32 s [n_rows][ld_s], int32 flags / cache_flags");
     TORCH_CHECK(k >= 1 && k <= JLM_TOPK_MAX && k <= V && is(ids, at::kInt, R * k) && is(nll, at::kDouble, R * k),
                 "jlm.predict_cache_rows: k in 1 .. min(", JLM_TOPK_MAX, ", V), int32 ids / float64 nll [n_rows, k]");
@@ -1025,12 +1010,9 @@ void predict_cache_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor 
     on_gpu(logits, "logits");
     Tensor sets;
     if (has(mask)) sets = check_word_sets("predict_cache_rows", *mask, ld_mask, n_sets, V, row_set, R, logits);
-    jlm_predict_cache_plan p{};
     p.n_rows = (int)R; p.h = ptr<const void>(h, "h"); p.T = optr<float>(T, "T");
     p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits; p.rows = ptr<const int>(rows, "rows");
-    p.hist = ptr<const void>(hist, "hist"); p.words = ptr<const int>(words, "words"); p.cap = (int)cap; p.pos = (int)pos;
-    p.first = ptr<const int>(first, "first"); p.N = (int)N; p.theta = (float)theta; p.lam = (float)lam;
-    p.s = ptr<float>(s, "s"); p.ld_s = (int)ld_s; p.k = (int)k;
+    p.pos = (int)pos; p.first = ptr<const int>(first, "first"); p.s = ptr<float>(s, "s"); p.k = (int)k;
     if (has(mask)) {
         p.mask = n_sets > 0 ? ptr<const unsigned>(*mask, "mask") : nullptr; p.ld_mask = (int)ld_mask; p.n_sets = (int)n_sets;
         p.row_set = ptr<const int>(sets, "row_set");
@@ -1046,7 +1028,6 @@ void predict_cache_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor 
 void beam_merge(const Tensor &cand_ids, const Tensor &cand_nll, int64_t beam, int64_t n_prompts, bool first, int64_t stop_id,
                 const Tensor &word, const Tensor &prev, const Tensor &score, const Tensor &finished, const Tensor &bp_parent,
                 const Tensor &bp_word, const Tensor &bp_nll) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     const int64_t R = n_prompts * beam;
     TORCH_CHECK(beam >= 1 && n_prompts >= 0 && is(cand_ids, at::kInt, R * beam) && is(cand_nll, at::kDouble, R * beam),
                 "jlm.beam_merge: cand_ids int32 / cand_nll float64 [n_prompts * beam, beam]");
@@ -1076,8 +1057,6 @@ Tensor complete_frames_masked(const c10::intrusive_ptr<JlmModel> &model, const T
                        int64_t ld_mask, int64_t n_sets, std::vector<int64_t> prompt_set) {
     const jlm_decode_model &m = model->m;
     const int64_t NP = n_prompts, B = beam, P = n_prompt, N = n_words, R = n_prompts * beam;
-    auto has = [](const OptTensor &t) { return t.has_value() && t->defined(); };
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     TORCH_CHECK(NP >= 0 && B >= 1 && P >= 1 && N >= 0, "jlm.complete_frames: n_prompts >= 0, beam >= 1, n_prompt >= 1 and n_words >= 0");
     check_row_sets("complete_frames", m, R, h0, c0, h1, c1, n_live_host, P, "prompt frame", NP);
     TORCH_CHECK(is(rows, at::kInt, R) && is(prev, at::kInt, P * NP) && is(prompt, at::kInt, P * NP) && is(n_live, at::kInt, P),
@@ -1137,7 +1116,6 @@ Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
 // 0, then (timed) milliseconds of range, histogram, seeding, Lloyd passes, final assignment.
 Tensor kmeans1d(const Tensor &x, int64_t bit, int64_t seed, int64_t max_iter, double tol, const Tensor &code, const Tensor &codebook,
                 const Tensor &scratch, int64_t grid, bool timed) {
-    auto is = [](const Tensor &t, at::ScalarType ty, int64_t n) { return t.defined() && t.scalar_type() == ty && t.numel() >= n; };
     const int64_t n = x.defined() ? x.numel() : 0;
     TORCH_CHECK(n >= 1 && n <= JLM_KMEANS_MAX_N && is(x, at::kFloat, n), "jlm.kmeans1d: x float32, 1 .. 2^27 values");
     TORCH_CHECK(bit >= 1 && bit <= 8 && max_iter >= 1 && max_iter <= INT32_MAX && seed >= 0 && grid >= 0 && grid <= (1 << 20),

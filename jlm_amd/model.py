@@ -947,17 +947,8 @@ class LSTM_Model():
         ids, row b consuming inputs[b, t] and scored on targets[b, t] at step t, the LSTM state carried from (h, c) -- device tensors
         [B, H] returned by an earlier call, None = zero state.  -> (nll [B, n] float64, h, c): the per-token -log p and the state after
         the last step (device tensors, in the state-row format of the model; pass them back as they are)."""
-        x = np.asarray(inputs)
-        y = np.asarray(targets)
-        if x.ndim != 2 or x.shape != y.shape:
-            raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
-        B, n = x.shape
-        if (h is None) != (c is None):
-            raise ValueError("carry both h and c, or neither")
-        if B == 0 or n == 0:
-            return np.zeros((B, n), dtype=np.float64), h, c
-        _seq, tok, h2, c2 = self._scorer().run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
-        return np.ascontiguousarray(tok.T), h2, c2
+        from .score import score_streams
+        return score_streams(self._scorer(), inputs, targets, h, c)
 
     def score_streams_cached(self, inputs, targets, cache, h=None, c=None, state=None):
         """score_streams with a continuous cache (jlm_amd/cache.py): ``cache`` a :class:`jlm_amd.cache.CacheSpec`

@@ -29,9 +29,10 @@ import numpy as np
 
 from . import ops as _ops
 from . import rowsets
+from .cache import MixRings
 from .generate import GENERATE_BUDGET_BYTES, MAX_ROWS
-from .rowsets import RowSets, check_ids
-from .score import plan_rows, sentence_arrays
+from .rowsets import RowSets, check_streams, forced_rows
+from .score import sentence_loop
 
 MAX_PREFIX_LIMIT = 30               # prefix levels 0 .. 30 and level X: the 32 level columns of jlm_rank_rows
 
@@ -93,7 +94,6 @@ class Ranker:
         m = self.m
         base = (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + n_steps * (8 + 4 * (n_levels + 1)) + 32
         if cache_size:
-            from .cache import MixRings
             base += MixRings.row_bytes(m.H, cache_size, n_steps, top)
         return base
 
@@ -107,31 +107,13 @@ class Ranker:
         where a row is not live, h, c) -- the state after the last step stays on the device; as in Scorer.run, only the rows live
         at the last step are defined in it."""
         torch, m = self.torch, self.m
-        word = np.ascontiguousarray(word, dtype=np.int32)
-        target = np.ascontiguousarray(target, dtype=np.int32)
-        S, R = target.shape
-        check_ids(word, m.V, "rank")
-        check_ids(target, m.V, "rank")
-        n_live = [int(x) for x in n_live]
-        dev, i32 = m.device, torch.int32
         L = levels.n_levels if levels is not None else 0
         with m._ctx():
-            rs = RowSets(m, R, logits=True)
-            if h is None:
-                prev0 = torch.full((R,), -1, device=dev, dtype=i32)
-            else:
-                if tuple(h.shape) != (R, m.H) or tuple(c.shape) != (R, m.H):
-                    raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (R, m.H, tuple(h.shape), tuple(c.shape)))
-                rs.h[0].copy_(h)
-                rs.c[0].copy_(c)
-                prev0 = rs.rows
-            wd = torch.from_numpy(word).to(dev)
-            tg = torch.from_numpy(target).to(dev)
-            nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
-            rank = torch.full((S, R, L + 1), -1, device=dev, dtype=i32)
+            rs = RowSets(m, np.shape(target)[1], logits=True)
+            S, R, forced = forced_rows(m, rs, word, target, n_live, h, c, "rank")
+            rank = torch.full((S, R, L + 1), -1, device=m.device, dtype=torch.int32)
             table = levels.args() if levels is not None else (None, None, None, None, 0)
-            args = (m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, prev0, wd, tg, nl, n_live, *table, rank, rs.flags, R, S,
-                    bool(timed))
+            args = (m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, *forced, *table, rank, rs.flags, R, S, bool(timed))
             if rings is None:
                 ms = _ops.backend().rank_frames(*args)
             else:
@@ -143,7 +125,25 @@ class Ranker:
             rs.check_flags("rank_rows_kernel flagged a target outside the vocabulary (flags %d)",
                            "the logit of a target word is NaN: its rank is undefined")
             out = rank.cpu().numpy()
-        return out, rs.h[S % 2], rs.c[S % 2]
+        return (out,) + rs.after(S)
+
+    def sentences(self, sequences, start, levels, max_rows, limit, spec=None):
+        """rank_sequences, and with ``spec`` (a checked CacheSpec) jlm_amd.cache.rank_cached: every chunk with rings of its own"""
+        L = levels.n_levels if levels is not None else 0
+
+        def run(ch, word, target, lens):
+            rings = MixRings(self.m, spec, len(lens), ch["n_steps"]) if spec else None
+            rk = self.run(word, target, ch["n_live"], levels=levels, rings=rings)[0]
+            return [_columns(levels, rk[:n, r, :], target[:n, r]) for r, n in enumerate(lens)]
+        return sentence_loop(self.m, sequences, start, "rank", max_rows, limit, lambda n: self.row_bytes(n, L, spec.size if spec else 0),
+                             lambda n: np.full((n, L + 1), -1, dtype=np.int32), run)
+
+    def streams(self, x, y, h, c, levels, rings=None):
+        """a stream call of the checked x, y [B, n] -> (ranks [B, n, columns] in the public columns, h, c)"""
+        B, n = x.shape
+        rk, h2, c2 = self.run(x.T, y.T, [B] * n, h=h, c=c, levels=levels, rings=rings)
+        flat = _columns(levels, rk.reshape(n * B, -1), np.ascontiguousarray(y.T).reshape(-1))
+        return np.ascontiguousarray(flat.reshape(n, B, -1).transpose(1, 0, 2)), h2, c2
 
 
 def _columns(levels, dev_rank, target):
@@ -152,44 +152,16 @@ def _columns(levels, dev_rank, target):
 
 def rank_sequences(ranker, sequences, start, levels=None, max_rows=None):
     """LSTM_Model.rank: see there."""
-    V = ranker.m.V
-    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
-    for s in seqs:
-        check_ids(s, V, "rank")
-    check_ids([start], V, "rank (start)")
-    L = levels.n_levels if levels is not None else 0
-    lens = [len(s) for s in seqs]
-    longest = max(lens) if lens else 0
-    if max_rows is None:
-        max_rows = rowsets.clamp_rows(MAX_ROWS, GENERATE_BUDGET_BYTES, ranker.row_bytes(longest, L), ranker.m.H)
-    out = [np.full((n, L + 1), -1, dtype=np.int32) for n in lens]
-    for ch in plan_rows(lens, max_rows):
-        idx = ch["idx"]
-        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
-        rk, _h, _c = ranker.run(word, target, ch["n_live"], levels=levels)
-        for r, i in enumerate(idx):
-            n = int(ch["lens"][r])
-            out[i] = _columns(levels, rk[:n, r, :], target[:n, r])
-    return out
+    return ranker.sentences(sequences, start, levels, max_rows, (MAX_ROWS, GENERATE_BUDGET_BYTES))
 
 
 def rank_streams(ranker, inputs, targets, h=None, c=None, levels=None):
     """LSTM_Model.rank_streams: see there."""
-    x = np.asarray(inputs)
-    y = np.asarray(targets)
-    if x.ndim != 2 or x.shape != y.shape:
-        raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
-    if (h is None) != (c is None):
-        raise ValueError("carry both h and c, or neither")
-    B, n = x.shape
-    L = levels.n_levels if levels is not None else 0
-    check_ids(x, ranker.m.V, "rank")
-    check_ids(y, ranker.m.V, "rank")
+    x, y, B, n = check_streams(ranker.m, inputs, targets, h, c)
     if B == 0 or n == 0:
+        L = levels.n_levels if levels is not None else 0
         return np.full((B, n, L + 1), -1, dtype=np.int32), h, c
-    rk, h2, c2 = ranker.run(x.T, y.T, [B] * n, h=h, c=c, levels=levels)
-    flat = _columns(levels, rk.reshape(n * B, L + 1), np.ascontiguousarray(y.T).reshape(-1))
-    return np.ascontiguousarray(flat.reshape(n, B, L + 1).transpose(1, 0, 2)), h2, c2
+    return ranker.streams(x, y, h, c, levels)
 
 
 # ---------------------------------------------------------------------------------------------------------------- metrics (numpy)

@@ -1,9 +1,12 @@
-"""What the row-set drivers share: :class:`jlm_amd.score.Scorer`, :class:`jlm_amd.generate.Generator` and
-:class:`jlm_amd.complete.Completer`.
+"""What the row-set drivers share: :class:`jlm_amd.score.Scorer`, :class:`jlm_amd.rank.Ranker`, :class:`jlm_amd.generate.Generator`,
+:class:`jlm_amd.complete.Completer` and :class:`jlm_amd.context.Primer`.
 
 Each of them is ONE device op over "row sets": two ping-pong sets of LSTM state rows, stepped frame by frame inside the op
 (csrc/jlm_decode.hip).  Here: the id and prompt checks made before any launch, the plan of right-aligned prompts that generate and
-complete share, the per-call row budget, and the buffers every call allocates.
+complete share, the per-call row budget, the buffers every call allocates, and what the teacher-forced calls -- score, rank and their
+cached forms -- share besides: the argument check of the stream entry points (:func:`check_streams`) and the setup of a call
+(:func:`forced_rows`).  The sentence-mode loop of those calls is :func:`jlm_amd.score.sentence_loop`, their ring
+:class:`jlm_amd.cache.Ring`.
 """
 import numpy as np
 
@@ -111,6 +114,10 @@ class RowSets:
         """the ops' state arguments: h0, c0, h1, c1, T"""
         return self.h[0], self.c[0], self.h[1], self.c[1], self.T
 
+    def after(self, S):
+        """(h, c) as a call of S steps leaves them: the row set its last step wrote"""
+        return self.h[S % 2], self.c[S % 2]
+
     def check_flags(self, message, bit0=None):
         """The flag word read back.  JlmHipError(``bit0``) when bit 0 is set and ``bit0`` is given, else JlmHipError(``message`` %
         flags) when any bit is."""
@@ -119,3 +126,48 @@ class RowSets:
             raise _lib.JlmHipError(bit0)
         if fl:
             raise _lib.JlmHipError(message % fl)
+
+
+def check_streams(m, inputs, targets, h, c, what=None):
+    """The arguments of a stream entry point: ValueError unless inputs / targets are [B, n] arrays of one shape and (h, c) are both None
+    or both [B, H].  ``what`` ("score" / "rank"): the ids are checked here, under that label, by a caller that allocates before its
+    call's setup (:func:`forced_rows`) checks them.  -> x, y, B, n"""
+    x = np.asarray(inputs)
+    y = np.asarray(targets)
+    if x.ndim != 2 or x.shape != y.shape:
+        raise ValueError("inputs and targets must be [B, n] arrays of the same shape (got %s, %s)" % (x.shape, y.shape))
+    if (h is None) != (c is None):
+        raise ValueError("carry both h and c, or neither")
+    B, n = x.shape
+    if what:
+        check_ids(x, m.V, what)
+        check_ids(y, m.V, what)
+    check_carried(m, h, c, B)
+    return x, y, B, n
+
+
+def check_carried(m, h, c, R):
+    if h is not None and (tuple(h.shape) != (R, m.H) or tuple(c.shape) != (R, m.H)):
+        raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (R, m.H, tuple(h.shape), tuple(c.shape)))
+
+
+def forced_rows(m, rs, word, target, n_live, h, c, what):
+    """The setup of a teacher-forced call, inside the model's context, on the call's :class:`RowSets` ``rs``: word / target [S, R]
+    (host) checked and uploaded with n_live, and the carried (h, c) copied into row set 0 (None: the zero state, prev0 = -1).
+    -> (S, R, the ops' argument run rows, prev0, word, target, n_live, its host copy)"""
+    torch = m.torch
+    word = np.ascontiguousarray(word, dtype=np.int32)
+    target = np.ascontiguousarray(target, dtype=np.int32)
+    S, R = target.shape
+    check_ids(word, m.V, what)
+    check_ids(target, m.V, what)
+    n_live = [int(x) for x in n_live]
+    if h is None:
+        prev0 = torch.full((R,), -1, device=m.device, dtype=torch.int32)
+    else:
+        check_carried(m, h, c, R)
+        rs.h[0].copy_(h)
+        rs.c[0].copy_(c)
+        prev0 = rs.rows
+    up = lambda a: torch.from_numpy(a).to(m.device)
+    return S, R, (rs.rows, prev0, up(word), up(target), up(np.asarray(n_live, dtype=np.int32)), n_live)

@@ -7,13 +7,14 @@ projection, the full-vocabulary normaliser the decoders use, and ``score_fold_ke
 normaliser's slices and takes the target word's logit.  Nothing comes back to the host between steps.
 
 Host logic of this module (row plan, stream layout, id checks) is plain numpy; :class:`Scorer` owns the device buffers of a call.
-``LSTM_Model.score`` / ``score_streams`` (jlm_amd/model.py) are the public entry points, ``python -m jlm_amd.perplexity`` the
-command-line front end.
+``LSTM_Model.score`` / ``score_streams`` (jlm_amd/model.py) are the public entry points, over :func:`score_sequences` and
+:func:`score_streams` here; ``python -m jlm_amd.perplexity`` is the command-line front end.  :func:`sentence_loop` is the sentence mode
+of every teacher-forced call: score and rank (jlm_amd/rank.py) and their cached forms (jlm_amd/cache.py).
 """
 import numpy as np
 
 from . import ops as _ops
-from .rowsets import RowSets, check_ids, clamp_rows
+from .rowsets import RowSets, check_ids, check_streams, clamp_rows, forced_rows
 
 # rows per call: the gate GEMM is most efficient at large row counts (37-40 % of the MFMA peak at 20 480 rows, 28 % at 2 560:
 # BENCH_r06); a call's buffers are bounded by SCORE_BUDGET_BYTES besides
@@ -97,23 +98,10 @@ class Scorer:
         stopped being live earlier is UNDEFINED there (its final state is in the other set when its length and n_steps differ in
         parity, and its slot here is unwritten or one step old): ragged callers do not carry a state."""
         torch, m = self.torch, self.m
-        word = np.ascontiguousarray(word, dtype=np.int32)
-        target = np.ascontiguousarray(target, dtype=np.int32)
-        S, R = target.shape
-        check_ids(word, m.V, "score")
-        check_ids(target, m.V, "score")
-        n_live = [int(x) for x in n_live]
-        dev, i32, f64 = m.device, torch.int32, torch.float64
+        dev, f64 = m.device, torch.float64
         with m._ctx():
+            R = np.shape(target)[1]
             rs = RowSets(m, R)
-            if h is None:
-                prev0 = torch.full((R,), -1, device=dev, dtype=i32)
-            else:
-                if tuple(h.shape) != (R, m.H) or tuple(c.shape) != (R, m.H):
-                    raise ValueError("the carried state must be [%d, %d] (got %s, %s)" % (R, m.H, tuple(h.shape), tuple(c.shape)))
-                rs.h[0].copy_(h)
-                rs.c[0].copy_(c)
-                prev0 = rs.rows
             part, n_parts = None, 0
             if not m.self_norm:
                 n_parts = max(m.n_vocab_tiles, 1)
@@ -121,13 +109,10 @@ class Scorer:
             Tm = None
             if part is not None and getattr(m, "ld_tm", 0):
                 Tm = torch.zeros(((R + 31) // 32 * 32, m.ld_tm), device=dev, dtype=torch.float32)     # whole 32-row blocks (jlm_hip.h)
-            wd = torch.from_numpy(word).to(dev)
-            tg = torch.from_numpy(target).to(dev)
-            nl = torch.as_tensor(np.asarray(n_live, dtype=np.int32)).to(dev)
+            S, R, forced = forced_rows(m, rs, word, target, n_live, h, c, "score")
             nll_seq = torch.zeros(R, device=dev, dtype=f64)
             nll_tok = torch.zeros((S, R), device=dev, dtype=f64) if per_token else None
-            args = (m.decode_model(), *rs.state(), Tm, int(m.ld_tm or 0), part, n_parts, rs.rows, prev0, wd, tg, nl, n_live, nll_seq, nll_tok,
-                    rs.flags, R, S, bool(timed))
+            args = (m.decode_model(), *rs.state(), Tm, int(m.ld_tm or 0), part, n_parts, *forced, nll_seq, nll_tok, rs.flags, R, S, bool(timed))
             if rings is None:
                 ms = _ops.backend().score_frames(*args)
             else:
@@ -139,28 +124,44 @@ class Scorer:
                            "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
             seq = nll_seq.cpu().numpy()
             tok = nll_tok.cpu().numpy() if per_token else None
-        return seq, tok, rs.h[S % 2], rs.c[S % 2]
+        return (seq, tok) + rs.after(S)
+
+
+def sentence_loop(m, sequences, start, what, max_rows, limit, row_bytes, empty, run):
+    """The sentence mode of score, rank and their cached forms (``what``: "score" / "rank", the label of the id errors).  The
+    sequences and ``start`` are checked, sorted and cut into chunks of at most ``max_rows`` rows -- None: ``limit`` = (rows, bytes) a
+    call, with ``row_bytes(longest)`` bytes a row -- and each chunk runs as ``run(chunk, word, target, lens)`` (:func:`plan_rows`,
+    :func:`sentence_arrays`; lens: the rows' lengths as a list), which returns the result of every row of the chunk.  -> per sequence,
+    in input order, its row's result; ``empty(n)`` for a sequence that took no row."""
+    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
+    for s in seqs:
+        check_ids(s, m.V, what)
+    check_ids([start], m.V, what + " (start)")
+    lens = [len(s) for s in seqs]
+    if max_rows is None:
+        max_rows = clamp_rows(*limit, row_bytes(max(lens, default=0)), m.H)
+    out = [empty(n) for n in lens]
+    for ch in plan_rows(lens, max_rows):
+        word, target = sentence_arrays([seqs[i] for i in ch["idx"]], start, ch["n_steps"])
+        for i, res in zip(ch["idx"], run(ch, word, target, ch["lens"].tolist())):
+            out[i] = res
+    return out
 
 
 def score_sequences(scorer, sequences, start, per_token=True, max_rows=None):
     """LSTM_Model.score: see there."""
-    V = scorer.m.V
-    seqs = [np.asarray(s, dtype=np.int64).ravel() for s in sequences]
-    for s in seqs:
-        check_ids(s, V, "score")
-    check_ids([start], V, "score (start)")
-    lens = [len(s) for s in seqs]
-    longest = max(lens) if lens else 0
-    if max_rows is None:
-        max_rows = clamp_rows(MAX_ROWS, SCORE_BUDGET_BYTES, scorer.row_bytes(longest, per_token), scorer.m.H)
-    out = [np.zeros(L, dtype=np.float64) for L in lens] if per_token else np.zeros(len(seqs), dtype=np.float64)
-    for ch in plan_rows(lens, max_rows):
-        idx = ch["idx"]
-        word, target = sentence_arrays([seqs[i] for i in idx], start, ch["n_steps"])
+    def run(ch, word, target, lens):
         seq, tok, _h, _c = scorer.run(word, target, ch["n_live"], per_token=per_token)
-        for r, i in enumerate(idx):
-            if per_token:
-                out[i] = tok[:ch["lens"][r], r].copy()
-            else:
-                out[i] = seq[r]
-    return out
+        return [tok[:n, r].copy() for r, n in enumerate(lens)] if per_token else seq
+    out = sentence_loop(scorer.m, sequences, start, "score", max_rows, (MAX_ROWS, SCORE_BUDGET_BYTES), lambda n: scorer.row_bytes(n, per_token),
+                        (lambda n: np.zeros(n, dtype=np.float64)) if per_token else (lambda n: 0.0), run)
+    return out if per_token else np.asarray(out, dtype=np.float64)
+
+
+def score_streams(scorer, inputs, targets, h=None, c=None):
+    """LSTM_Model.score_streams: see there."""
+    x, y, B, n = check_streams(scorer.m, inputs, targets, h, c)
+    if B == 0 or n == 0:
+        return np.zeros((B, n), dtype=np.float64), h, c
+    _seq, tok, h2, c2 = scorer.run(x.T, y.T, [B] * n, h=h, c=c, per_token=True)
+    return np.ascontiguousarray(tok.T), h2, c2
