@@ -642,6 +642,7 @@ typedef struct {
     const int *mixed_head_split;
 } jlm_decode_model;
 
+struct jlm_decode_cache;
 typedef struct {
     int kind;                       /* 0 static, full vocabulary; 1 static, selected vocabulary; 2 incremental */
     int max_cands;
@@ -676,6 +677,9 @@ typedef struct {
      * -1) and consumes ctx_word[g].  bp of frame 0 stays -1: jlm_backtrace stops at the root as before.  h / c then hold n_sent
      * more rows behind the pool. */
     const int *ctx_prev, *ctx_word;
+    /* The continuous cache inside the frame loop (additive, ABI 12; NULL: the loop is what it was, launch for launch).  Kind 0 only:
+     * see jlm_decode_cache below. */
+    const struct jlm_decode_cache *cache;
 } jlm_decode_plan;
 
 /* Returns 0 or a hipError_t.  st_host->lse_part / n_parts are managed by the call.  A full-vocabulary
@@ -1166,6 +1170,68 @@ int jlm_prime_frames(const jlm_decode_model *model_host, const jlm_prime_plan *p
  * < 2^31 (the LSTM step's addressing).  Returns 0, -1 for bad arguments, or a hipError_t. */
 int jlm_seed_context(const void *src_h, const float *src_c, int H, const int *last, const int *has, int n_src, const int *idx,
                      int n_sent, int beam, long long G, void *dst_h, float *dst_c, int *ctx_prev, int *ctx_word, void *stream);
+
+/* ------------------------------------------------------------------------
+ * The continuous cache inside a decode (Decoder.decode(context=, cache=); ABI 12, additive).  Sections 18 / 20's
+ * definition with a window that is FIXED for the whole decode: sentence s with hist = [<eos>] + ctx_s has the window of the last
+ * n_s = min(len(ctx_s), N) pairs (h_j, hist[j + 1]), h_j the state after consuming hist[j] from the zero state -- the state that
+ * predicted hist[j + 1]; a decode's own hypotheses add nothing.  For hypothesis row r of sentence s in frame f, with the state h_r the
+ * frame's LSTM step wrote, and every lattice word w that starts in cell (f, s):
+ *     s_i    = theta (h_r . h_i)                         i in the window of s, h in real units
+ *     c_r(w) = sum_{i : w_i = w} exp(s_i) / sum_i exp(s_i)
+ *     p_r(w) = (1 - lam) p_lm(w | r) + lam c_r(w)        if n_s > 0;  p_lm(w | r) if n_s = 0
+ *     edge cost = -log p_r(w),   p_lm = exp(y - L), L the row's full-vocabulary log-normaliser (self-normalised models: 0).
+ * Word ids are only compared (an out-of-vocabulary lattice word is id 0 and mixes like any other).  One theta and one lam a call,
+ * N <= JLM_CACHE_MIX_MAX_N.  The beam step computes score + (lse - edge) in f64, so the feature is a rewrite of the edge buffer:
+ *     edge' = L + log(1 - lam) + logaddexp(y - L, log rho + log M - log Z)   for a word with a match (rho = lam / (1 - lam)),
+ *     edge' = y + log(1 - lam)                                              for a word without,
+ * formed in f64 from the f32 sums M = sum_{i : w_i = w} e_i and Z = sum_i e_i, e_i = expf(s_i - max s), and rounded once to the f32
+ * the buffer holds.  Rows of a sentence with n_s = 0 keep their bits.
+ *
+ * The window of cache row r (rows of a CachedContext, jlm_amd/context.py): hist [cap][n_src][H] in the model's state-row format,
+ * words [cap][n_src], count [n_src] <= cap; its entries are the slots cap - count[r] .. cap - 1, oldest first.  Slots below that
+ * are never read.  idx [n_sent]: the cache row of every sentence of the batch (outside [0, n_src): no window). */
+typedef struct jlm_decode_cache {
+    const void *hist; const int *words, *count; int cap, n_src;
+    const int *idx;                 /* [n_sent] device */
+    int N; float theta, lam;
+    float *s; int ld_s;             /* scratch [n_sent * beam][ld_s], ld_s >= min(cap, N); contents arbitrary */
+} jlm_decode_cache;
+
+/* cache_cell_query_kernel: s[(j * beam + k) * ld_s + i] = theta (h[g0[j] + k] . key_i) for every sentence j < n_sent with
+ * frame < sent_len[j], slot k < min(cnt[j], beam) and entry i < n_j = min(count[idx[j]], cap, N) of its window (oldest first).
+ * Grid (chunk of 64 keys, sentence): the cell's query rows are staged in LDS eight at a time and every key of the chunk is dotted
+ * against each; per (query, key) the partition, the f32 fmaf chain, the reduction and the decode of split rows are jlm_cache_query's,
+ * so the bits are its bits for the same two rows and theta, whatever the cell, the chunk, cnt or the launch.  g0, cnt [n_sent]: the
+ * frame's entries (jlm_decode_plan.g0 + cell, jlm_beam_state.cnt + cell).  A product that is not finite ORs 8 into *flags.
+ * Returns 0, -1 for bad arguments (H % 32, H > 2048 -- the staged rows take 32 H bytes of LDS --, N outside [1, JLM_CACHE_MIX_MAX_N], cap < 1, ld_s < min(cap, N), theta, h_scale, a null
+ * or misaligned pointer, n_sent > 65535) before any launch, or a hipError_t. */
+int jlm_cache_cell_query(const void *h, int H, int split, float h_scale, const int *g0, const int *cnt, const int *sent_len, int frame,
+                         int n_sent, int beam, const void *hist, const int *count, int cap, int n_src, const int *idx, int N,
+                         float theta, float *s, int ld_s, int *flags, void *stream);
+
+/* cache_cell_patch_kernel: one workgroup per sentence j of the frame (skipped when frame >= sent_len[j] or cnt[j] = 0).
+ * part != NULL (ordinary models): the (max, sum exp) slices part[p * ld_part + live_base[j] + k], p < n_parts, of the cell's rows
+ * are first folded into lse[j * beam + k] (f64) with jlm_beam_step's fused fold -- its order, arithmetic and sanitising: a value
+ * that is not finite ORs 1 into *flags and becomes 1e30 -- whether the sentence has a window or not, so that the next jlm_beam_step
+ * runs in its unfused form; part == NULL (self-normalised models): L = 0, lse is not touched.  Then, for a sentence with n_j > 0:
+ * per slot the maximum, e_i = expf(s_i - max) (written back over s) and Z in a fixed tree; per position of the cell's word list
+ * wl[wl_off[l] .. wl_off[l + 1]), l = wl_base + wl_idx[j] (jlm_edge_logits' lists, found as it finds them) and slot k, M in ascending
+ * i and edge[wl_out * beam + k] <- edge' as defined above.  One writer per address, no atomics.  A slot with a score that is not
+ * finite keeps its edge logits (8 is ORed into *flags).  lse, g-indexed arrays: the frame's first entry.
+ * Returns 0, -1 for bad arguments (lam outside (0, 1), N, cap, ld_s, beam outside [1, JLM_MAX_BEAM], part without live_base / lse /
+ * n_parts >= 1, a null pointer) before any launch, -3, or a hipError_t. */
+int jlm_cache_cell_patch(float *s, int ld_s, const int *words, const int *count, int cap, int n_src, const int *idx, int N, float lam,
+                         const int *cnt, const int *sent_len, int frame, int n_sent, int beam, const int *wl, const int *wl_off,
+                         const int *wl_idx, int wl_base, const int *wl_out, float *edge, const float *part, int ld_part, int n_parts,
+                         const int *live_base, double *lse, int *flags, void *stream);
+
+/* jlm_prime_frames that keeps its states: behind the step of frame f >= n_steps - cap, the live prefix of the state set the step
+ * wrote and target[f][0 .. n_live_host[f]) are copied into slot f - (n_steps - cap) of hist [cap][n_rows][H] / words [cap][n_rows]
+ * (jlm_cache_store; earlier frames are not stored).  Priming is right-aligned: a row's entries end at slot cap - 1.  Rows past the
+ * live prefix of a slot are not written.  1 <= cap; target [n_steps][n_rows] device.  jlm_prime_frames' launches otherwise. */
+int jlm_prime_cache_frames(const jlm_decode_model *model_host, const jlm_prime_plan *plan_host, const int *target, void *hist, int *words,
+                           int cap, void *stream);
 
 /* ------------------------------------------------------------------------
  * Prediction of an unfinished last word behind a static decode (Decoder.decode_predict; ABI 12, additive).

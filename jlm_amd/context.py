@@ -11,6 +11,11 @@ rows sorted longest first, right-aligned step arrays, live counts -- the plan of
 :class:`Primer`, the row-set driver beside Scorer, Generator and Completer: ONE op (``torch.ops.jlm.prime_frames``, csrc/jlm_decode.hip
 ``jlm_prime_frames``) that launches the LSTM step of every frame and nothing else.  ``DecodeEngine.submit(context=)`` gathers the rows
 of a batch behind its plan's state pool (``torch.ops.jlm.seed_context``, ``seed_context_kernel``) in front of the frame loop.
+
+The continuous cache inside a decode: ``prime(cache=CacheSpec)`` keeps the last N (state, next word) pairs of
+every history too (``torch.ops.jlm.prime_cache_frames``) and returns a :class:`CachedContext`; the frame loop then mixes the cache
+over that fixed window into every edge cost (csrc/jlm_cache_edge.hip), and the host-side searches do the same in float64
+(:meth:`DecodeContext.host_mixer`).
 """
 import numpy as np
 
@@ -54,6 +59,39 @@ class ContextState:
             h = raw.astype(np.float32)
         keep = self.has_host.astype(bool)[:, None]
         return np.where(keep, h, np.float32(0)), np.where(keep, c, np.float32(0))
+
+
+class CachedContext(ContextState):
+    """A :class:`ContextState` that also holds every row's window for a decode under the continuous cache: the
+    last ``count[r]`` = min(len(ctx_r), N) pairs (h_j, hist[j + 1]) of hist = [<eos>] + ctx_r, h_j the state after hist[j].  ``hist``
+    [cap, n, H] in the model's state-row format, ``words`` [cap, n] int32, ``count`` [n] int32 (``count_host``: its host copy): row r's
+    entries are the slots cap - count[r] .. cap - 1, oldest first; the slots below hold nothing that is read.  ``spec``: the CacheSpec
+    it was primed for (one theta).  Immutable and reusable like its base."""
+
+    def __init__(self, m, h, c, last, has, last_host, has_host, hist, words, count, count_host, spec):
+        super().__init__(m, h, c, last, has, last_host, has_host)
+        self.hist, self.words, self.count, self.spec = hist, words, count, spec
+        self.count_host = np.asarray(count_host, dtype=np.int32)
+        self.cap = int(words.shape[0])
+
+    def cache_numpy(self):
+        """(h [n, cap, H] float32 with split rows decoded, words [n, cap] int64, count [n]) on the host; row r's window is
+        h[r, cap - count[r]:], words[r, cap - count[r]:]"""
+        from .cache import decode_rows
+        h = decode_rows(self.m, self.hist.view(self.m.torch.float32)).transpose(1, 0, 2)
+        return np.ascontiguousarray(h), np.ascontiguousarray(self.words.detach().cpu().numpy().T.astype(np.int64)), self.count_host.copy()
+
+
+def check_decode_cache(cache):
+    """the ``cache=`` of a decode: a CacheSpec of ONE theta and N <= 4096 (JLM_CACHE_MIX_MAX_N); ValueError otherwise"""
+    from .cache import CacheSpec, MIX_MAX_SIZE
+    if not isinstance(cache, CacheSpec):
+        raise ValueError("cache must be a CacheSpec (got %r)" % (cache,))
+    if len(cache.thetas) != 1:
+        raise ValueError("a decode under the cache takes one theta (got %d)" % len(cache.thetas))
+    if cache.size > MIX_MAX_SIZE:
+        raise ValueError("a decode under the cache keeps at most %d entries a sentence (got %d)" % (MIX_MAX_SIZE, cache.size))
+    return cache
 
 
 def normalize_contexts(contexts, V, w2i=None, unk=0):
@@ -105,7 +143,8 @@ def plan_priming(contexts, max_rows, eos=EOS_ID):
     """The calls of one ``prime``: rows sorted by step count, longest first (stable), at most ``max_rows`` a call
     (rowsets.plan_prompts).  -> list of dict(idx = the caller's context of each row, n_steps = the longest row's steps, n_live
     [n_steps], word / prev [n_steps, R] int32 right-aligned (rowsets.prompt_arrays; prev -1 at a row's first frame), last [R] =
-    hist[-1], has [R] = 1 where the row steps at all).  A call whose rows never step has n_steps = 0."""
+    hist[-1], has [R] = 1 where the row steps at all, target [n_steps, R] = the word each step predicts: hist[j + 1] at the step that
+    consumes hist[j], lens [R] = the steps of each row).  A call whose rows never step has n_steps = 0."""
     steps, last = [], []
     for ctx in contexts:
         w, l = step_words(ctx, eos)
@@ -115,7 +154,9 @@ def plan_priming(contexts, max_rows, eos=EOS_ID):
     for ch in rowsets.plan_prompts([len(w) for w in steps], max_rows):
         idx = ch["idx"]
         word, prev = rowsets.prompt_arrays([steps[i] for i in idx], ch["n_prompt"])
-        chunks.append(dict(idx=idx, n_steps=ch["n_prompt"], n_live=ch["n_live"], word=word, prev=prev,
+        # (what each step is scored on under the cache: the next word of the row, hist[-1] at its last step -- hist[1:], right-aligned)
+        target, _ = rowsets.prompt_arrays([np.append(steps[i][1:], last[i])[:len(steps[i])] for i in idx], ch["n_prompt"])
+        chunks.append(dict(idx=idx, n_steps=ch["n_prompt"], n_live=ch["n_live"], word=word, prev=prev, target=target, lens=ch["lens"],
                            last=np.asarray([last[i] for i in idx], dtype=np.int32), has=(ch["lens"] > 0).astype(np.int32)))
     return chunks
 
@@ -130,42 +171,70 @@ class Primer:
     def row_bytes(self, n_steps):
         return (4 * self.m.H + self.m.ldt) * 4 + n_steps * 8 + 16
 
-    def run(self, chunk):
-        """One call over a chunk of :func:`plan_priming`.  -> (h, c) [R, H] device tensors: the set the last frame wrote"""
+    def run(self, chunk, cap=0):
+        """One call over a chunk of :func:`plan_priming`.  -> (h, c) [R, H] device tensors: the set the last frame wrote.  ``cap`` >= 1:
+        the states and targets of the last min(cap, n_steps) frames are kept too (``torch.ops.jlm.prime_cache_frames``): -> (h, c, hist
+        [k, R, H], words [k, R]), zeroed memory of which frame f's live rows are written."""
         torch, m = self.torch, self.m
         R, S = len(chunk["idx"]), int(chunk["n_steps"])
         rs = rowsets.RowSets(m, R)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(m.device)
+        if cap:
+            k = max(min(int(cap), S), 1)
+            hist = torch.zeros((k, R, m.H), device=m.device, dtype=torch.float32)
+            words = torch.zeros((k, R), device=m.device, dtype=torch.int32)
+            if S > 0:
+                _ops.backend().prime_cache_frames(m.decode_model(), rs.h[0], rs.c[0], rs.h[1], rs.c[1], rs.rows, up(chunk["prev"]),
+                                                  up(chunk["word"]), up(chunk["n_live"]), [int(x) for x in chunk["n_live"]], R, S,
+                                                  up(chunk["target"]), hist, words, k)
+            return rs.h[S % 2], rs.c[S % 2], hist, words
         if S > 0:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(m.device)
             _ops.backend().prime_frames(m.decode_model(), rs.h[0], rs.c[0], rs.h[1], rs.c[1], rs.rows, up(chunk["prev"]), up(chunk["word"]),
                                         up(chunk["n_live"]), [int(x) for x in chunk["n_live"]], R, S)
         return rs.h[S % 2], rs.c[S % 2]
 
 
-def prime(primer, contexts, max_rows=None, w2i=None, unk=0, checked=False):
-    """LSTM_Model.prime: see there.  checked: ``contexts`` is what normalize_contexts returned."""
+def prime(primer, contexts, max_rows=None, w2i=None, unk=0, checked=False, cache=None):
+    """LSTM_Model.prime: see there.  checked: ``contexts`` is what normalize_contexts returned.  cache: a CacheSpec -> a
+    :class:`CachedContext` (cap = min(N, the longest context), at least 1)."""
     m = primer.m
     torch = primer.torch
+    if cache is not None:
+        check_decode_cache(cache)
     ctxs = contexts if checked else normalize_contexts(contexts, m.V, w2i, unk)
     n = len(ctxs)
+    longest = max([len(c) for c in ctxs] + [0])
+    cap = max(min(cache.size, longest), 1) if cache is not None else 0
     if max_rows is None:
-        longest = max([len(c) for c in ctxs] + [0])
-        max_rows = rowsets.clamp_rows(MAX_ROWS, PRIME_BUDGET_BYTES, primer.row_bytes(longest), m.H)
+        max_rows = rowsets.clamp_rows(MAX_ROWS, PRIME_BUDGET_BYTES, primer.row_bytes(longest) + cap * (m.H + 1) * 4, m.H)
     last, has = np.full(n, EOS_ID, dtype=np.int32), np.zeros(n, dtype=np.int32)
     with m._ctx():
         h = torch.zeros((n, m.H), device=m.device, dtype=torch.float32)
         c = torch.zeros((n, m.H), device=m.device, dtype=torch.float32)
+        if cap:
+            hist = torch.zeros((cap, n, m.H), device=m.device, dtype=torch.float32)
+            words = torch.zeros((cap, n), device=m.device, dtype=torch.int32)
         for ch in plan_priming(ctxs, max_rows):
             idx = ch["idx"]
             last[idx], has[idx] = ch["last"], ch["has"]
             if ch["n_steps"] == 0:
                 continue
-            hc, cc = primer.run(ch)
             k = int(ch["has"].sum())          # the rows that stepped are a prefix (longest first); the others stay zero
             at = torch.from_numpy(np.ascontiguousarray(idx[:k], dtype=np.int64)).to(m.device)
+            if cap:
+                hc, cc, hh, ww = primer.run(ch, cap)
+                kk = int(ww.shape[0])         # the call's slots are the last kk of the window: priming is right-aligned
+                hist[cap - kk:].index_copy_(1, at, hh[:, :k])
+                words[cap - kk:].index_copy_(1, at, ww[:, :k])
+            else:
+                hc, cc = primer.run(ch)
             h.index_copy_(0, at, hc[:k])
             c.index_copy_(0, at, cc[:k])
-        return ContextState(m, h, c, torch.from_numpy(last.copy()).to(m.device), torch.from_numpy(has.copy()).to(m.device), last, has)
+        dev = lambda a: torch.from_numpy(a.copy()).to(m.device)
+        if not cap:
+            return ContextState(m, h, c, dev(last), dev(has), last, has)
+        count = np.minimum([len(x) for x in ctxs], cap).astype(np.int32)
+        return CachedContext(m, h, c, dev(last), dev(has), last, has, hist, words, dev(count), count, cache)
 
 
 class DecodeContext:
@@ -173,7 +242,36 @@ class DecodeContext:
 
     def __init__(self, state, rows):
         self.state, self.rows = state, [int(r) for r in rows]
-        self._host = None
+        self._host = self._window = None
+
+    @property
+    def cached(self):
+        """the decode runs under the continuous cache: a CachedContext with lam > 0 (lam = 0 is the decode without)"""
+        return isinstance(self.state, CachedContext) and self.state.spec.lam > 0.0
+
+    def host_mixer(self, i):
+        """None, or for input i of a cached decode the host form of the mixture (the float64 definition, jlm_amd/cache.py):
+        mix(pred [rows, V], h [rows, H]) -> (1 - lam) pred + lam c(h) over the input's window; an empty window returns pred"""
+        if not self.cached:
+            return None
+        if self._window is None:
+            self._window = self.state.cache_numpy()
+        hh, ww, cnt = self._window
+        r, spec = self.rows[i], self.state.spec
+        n = int(cnt[r])
+        keys, words = hh[r, hh.shape[1] - n:].astype(np.float64), ww[r, ww.shape[1] - n:]
+
+        def mix(pred, h):
+            pred = np.asarray(pred, dtype=np.float64)
+            if n == 0:
+                return pred
+            s = spec.theta * (np.asarray(h, dtype=np.float64) @ keys.T)
+            e = np.exp(s - s.max(axis=1, keepdims=True))
+            c = np.zeros_like(pred)
+            for q in range(pred.shape[0]):
+                np.add.at(c[q], words, e[q] / e[q].sum())
+            return (1.0 - spec.lam) * pred + spec.lam * c
+        return mix
 
     def sub(self, keep):
         return DecodeContext(self.state, [self.rows[i] for i in keep])
@@ -187,10 +285,17 @@ class DecodeContext:
         return h[r:r + 1].astype(np.float64), c[r:r + 1].astype(np.float64), int(self.state.last_host[r])
 
 
-def resolve(model, context, n, w2i, single=False):
+def resolve(model, context, n, w2i, single=False, cache=None):
     """The ``context=`` argument of ``decode`` (single) / ``decode_batch`` -> None (every history is ``<eos>`` alone: today's decode)
-    or a :class:`DecodeContext` over ``n`` inputs.  Lists are primed here (``model``: the LSTM_Model).  ValueError for a length
-    mismatch, a bad id, or a state of another model."""
+    or a :class:`DecodeContext` over ``n`` inputs.  Lists are primed here (``model``: the LSTM_Model), with ``cache`` (a CacheSpec,
+    lam > 0) into a :class:`CachedContext`.  ValueError for a length mismatch, a bad id, a state of another model, or ``cache=``
+    beside a state that was primed already."""
+    if cache is not None:
+        check_decode_cache(cache)
+        if isinstance(context, (DecodeContext, ContextState)):
+            raise ValueError("cache=: the context is primed already; prime it with LSTM_Model.prime(contexts, cache=...)")
+        if cache.lam == 0.0:
+            cache = None                  # p = p_lm: the decode without a cache, the same launches
     if context is None or isinstance(context, DecodeContext):
         return context
     if isinstance(context, ContextState):
@@ -210,7 +315,7 @@ def resolve(model, context, n, w2i, single=False):
         ctxs = normalize_contexts(context, model.dev.V, w2i, unk)
         if not any(len(c) for c in ctxs):
             return None
-        state = prime(model._primer(), ctxs, checked=True)
+        state = prime(model._primer(), ctxs, checked=True, cache=cache)
     if state.is_empty():
         return None
     return DecodeContext(state, range(n))

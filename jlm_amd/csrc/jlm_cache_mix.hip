@@ -17,6 +17,7 @@
 // (its layout, f32 expf, f64 sums, its order), read before any word is patched.  y[w] <- logaddexp(y[w], L + log rho + log c - log Z).
 #include <math.h>
 #include "jlm_common.h"
+#include "jlm_cache_unit.h"
 
 namespace {
 
@@ -39,22 +40,7 @@ struct QueryArgs {
     float theta;                       // split rows: theta / h_scale^2
 };
 
-union Rec {
-    uint4 u;
-    f16x8 h;
-    float f[4];
-};
-
-// the eight values of one 32-byte unit: split rows f32(hi) + f32(lo) (the scale stays in, theta carries 1 / h_scale^2), else the f32s
-template <bool SPLIT>
-__device__ __forceinline__ void cq_unit(const uint4 *row, int u, float v[8]) {
-    Rec a, b;
-    a.u = row[2 * u];
-    b.u = row[2 * u + 1];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = SPLIT ? (float)a.h[i] + (float)b.h[i] : (i < 4 ? a.f[i] : b.f[i - 4]);
-}
-
+// (Rec and cq_unit, the decode of one 32-byte unit of a state row: csrc/jlm_cache_unit.h, shared with cache_cell_query_kernel)
 template <bool SPLIT>
 __global__ void __launch_bounds__(4 * CQ_KEYS) cache_query_kernel(const QueryArgs a) {
     const int r = blockIdx.y;

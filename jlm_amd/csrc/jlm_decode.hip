@@ -41,6 +41,15 @@ thread_local EventPool g_events;
 
 }  // namespace
 
+// the refusals of jlm_cache_cell_query / jlm_cache_cell_patch on their own (csrc/jlm_cache_edge.hip)
+int jlm_cache_cell_query_refuse(const void *h, int H, int split, float h_scale, const int *g0, const int *cnt, const int *sent_len, int frame,
+                                int n_sent, int beam, const void *hist, const int *count, int cap, int n_src, const int *idx, int N,
+                                float theta, const float *s, int ld_s, const int *flags);
+int jlm_cache_cell_patch_refuse(const float *s, int ld_s, const int *words, const int *count, int cap, int n_src, const int *idx, int N,
+                                float lam, const int *cnt, const int *sent_len, int frame, int n_sent, int beam, const int *wl,
+                                const int *wl_off, const int *wl_idx, int wl_base, const int *wl_out, const float *edge, const float *part,
+                                int ld_part, int n_parts, const int *live_base, const double *lse, const int *flags);
+
 // ABI 11: the model's mixed segments are mx6 rows (FP6 cross-term planes, csrc/jlm_mx6_body.h) when their s8 is 0 -- the hypothesis
 // rows are then packed by jlm_pack_t_mixed6; a model mixes the two formats in no launch (jlm_vocab_lse_mixed: -2)
 static inline bool jlm_model_mx6(const jlm_decode_model *m) {
@@ -167,6 +176,21 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
     };
     hipEvent_t join = nullptr;
     int pending_parts = 0;
+    // The continuous cache (jlm_decode_plan.cache, kind 0): behind the normaliser and the edge logits of every frame, the cache scores
+    // of the frame's hypotheses (jlm_cache_cell_query) and the rewrite of the edge logits leaving it (jlm_cache_cell_patch), which also
+    // folds the frame's normaliser slices -- the next beam step then runs unfused.  The edge logits stay on the main stream.  Every
+    // refusal comes here, before the first launch.
+    const jlm_decode_cache *cc = p->cache;
+    const int split = m->split_lstm ? 1 : 0;
+    if (cc) {
+        if (!full || !st.live_base || (!m->self_norm && (!p->part || p->max_parts < 1))) return -1;
+        JLM_TRY(jlm_cache_cell_query_refuse(p->h, m->H, split, m->h_scale, p->g0, st.cnt, lat->sent_len, 0, B, beam, cc->hist, cc->count,
+                                            cc->cap, cc->n_src, cc->idx, cc->N, cc->theta, cc->s, cc->ld_s, st.flags));
+        JLM_TRY(jlm_cache_cell_patch_refuse(cc->s, cc->ld_s, cc->words, cc->count, cc->cap, cc->n_src, cc->idx, cc->N, cc->lam, st.cnt,
+                                            lat->sent_len, 0, B, beam, p->sg_word, p->sg_off, p->sidx, 0, p->sg_node, p->edge,
+                                            m->self_norm ? nullptr : p->part, rmax, 1, st.live_base, st.lse, st.flags));
+        side_s = nullptr;
+    }
 
     // word-list normaliser: the kernel jlm_wordlist_lse_form names (split rows for lists of 128 .. 4064 words)
     auto wl_lse = [&](const int *g0, const int *cidx, const int *words, const int *off, const int *idx, int base, int merge,
@@ -300,6 +324,15 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                                      p->lse_cu_share_pct, &pending_parts, stream));
         }
         JLM_TRY(stamp(f, 5));
+        if (cc) {
+            JLM_TRY(jlm_cache_cell_query(p->h, m->H, split, m->h_scale, p->g0 + cell, st.cnt + cell, lat->sent_len, f, B, beam, cc->hist,
+                                         cc->count, cc->cap, cc->n_src, cc->idx, cc->N, cc->theta, cc->s, cc->ld_s, st.flags, stream));
+            JLM_TRY(jlm_cache_cell_patch(cc->s, cc->ld_s, cc->words, cc->count, cc->cap, cc->n_src, cc->idx, cc->N, cc->lam, st.cnt + cell,
+                                         lat->sent_len, f, B, beam, p->sg_word, p->sg_off, p->sidx, cell, p->sg_node, p->edge,
+                                         pending_parts ? p->part : nullptr, rmax, pending_parts, st.live_base + cell,
+                                         st.lse + (size_t)f * rmax, st.flags, stream));
+            pending_parts = 0;             // folded: the next beam step reads lse
+        }
     }
     if (join) JLM_HIP(hipStreamWaitEvent(main_s, join, 0));
     return jlm_backtrace(lat, &st, p->out_nodes, p->out_len, p->out_score, p->stride, stream);
@@ -441,8 +474,10 @@ static int frame_lstm_step(const jlm_decode_model *m, const Plan *p, const PingP
 }
 
 // The priming loop (include/jlm_hip.h jlm_prime_frames): the LSTM step of the live prefix of right-aligned word rows, frame by frame,
-// and nothing else -- the state a decode with a left context starts from.
-extern "C" int jlm_prime_frames(const jlm_decode_model *m, const jlm_prime_plan *p, void *stream) {
+// and nothing else -- the state a decode with a left context starts from.  after_step(f, bound, h_out): called behind the step of
+// frame f with the state set it wrote (jlm_prime_cache_frames' copies; jlm_prime_frames: nothing).
+template <class AfterStep>
+static int prime_loop(const jlm_decode_model *m, const jlm_prime_plan *p, void *stream, AfterStep after_step) {
     const int R = p->n_rows, S = p->n_steps;
     if (R < 0 || S < 0) return -1;
     if (R == 0 || S == 0) return 0;
@@ -454,8 +489,31 @@ extern "C" int jlm_prime_frames(const jlm_decode_model *m, const jlm_prime_plan 
         if (bound == 0) continue;
         JLM_TRY(rows_lstm_step(m, p->h[f & 1], p->c[f & 1], p->h[(f + 1) & 1], p->c[(f + 1) & 1], p->rows, p->prev + (size_t)f * R,
                                p->word + (size_t)f * R, nullptr, bound, p->n_live + f, stream));
+        JLM_TRY(after_step(f, bound, p->h[(f + 1) & 1]));
     }
     return 0;
+}
+
+extern "C" int jlm_prime_frames(const jlm_decode_model *m, const jlm_prime_plan *p, void *stream) {
+    return prime_loop(m, p, stream, [](int, int, const void *) { return 0; });
+}
+
+// the copy behind a step: rows 0 .. bound - 1 of the written state set and the step's targets into their ring slot (csrc/jlm_cache.hip)
+int jlm_cache_store(const void *h_rows, const int *target, int bound, int H, void *hist_slot, int *words_slot, void *stream);
+
+// Priming that keeps its states (include/jlm_hip.h jlm_prime_cache_frames): prime_loop with the state rows and the targets of the last
+// `cap` frames copied into hist / words -- the window of a decode under the continuous cache.
+extern "C" int jlm_prime_cache_frames(const jlm_decode_model *m, const jlm_prime_plan *p, const int *target, void *hist, int *words, int cap,
+                                      void *stream) {
+    if (!p || cap < 1) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    if (R > 0 && S > 0 && (!target || !hist || !words || ((uintptr_t)hist & 15) != 0)) return -1;
+    return prime_loop(m, p, stream, [&](int f, int bound, const void *h_out) -> int {
+        const int slot = f - (S - cap);
+        if (slot < 0) return 0;
+        return jlm_cache_store(h_out, target + (size_t)f * R, bound, m->H, (char *)hist + (size_t)slot * R * m->H * 4,
+                               words + (size_t)slot * R, stream);
+    });
 }
 
 // seed_context_kernel (include/jlm_hip.h jlm_seed_context): workgroup s gathers the primed state of sentence s behind the plan's pool,

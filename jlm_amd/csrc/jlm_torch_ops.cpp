@@ -39,6 +39,10 @@
 //                             the state after a left context: LSTM steps only, ONE op (jlm_prime_frames; LSTM_Model.prime)
 //   torch.ops.jlm.seed_context(Plan, src_h, src_c, last, has, idx)
 //                             primed states gathered behind a plan's pool for frame 0 (jlm_seed_context; Decoder.decode(context=))
+//   torch.ops.jlm.prime_cache_frames(Model, state row sets, ..., target, hist, words, cap)
+//                             prime_frames that keeps the last cap frames' states and targets (jlm_prime_cache_frames; prime(cache=))
+//   torch.ops.jlm.seed_cache(Plan, hist, words, count, idx, s, cap, N, theta, lam)
+//                             the window of the plan's next frame loop: no launch (jlm_decode_plan.cache; Decoder.decode(cache=))
 //   torch.ops.jlm.tail_predict(Model, Plan, ids, sp_off, sp_frame, sp_lo, sp_hi, n_out, chunk, out_score, out_row, out_word, out_nodes,
 //                              out_len, stride)
 //                             predictions of an unfinished last word behind a plan's decode (jlm_tail_predict; Decoder.decode_predict)
@@ -228,6 +232,8 @@ struct JlmPlan : torch::CustomClassHolder {
     int timed_frames = 0;                   // frames of the last timed decode (0: the last decode was not timed)
     int device = -1;
     int ctx_H = 0;                          // a plan with a left context: the state rows' width (0: no such plan)
+    jlm_decode_cache cache{};               // the next frame loop's window (seed_cache; p.cache points here or is NULL)
+    std::vector<Tensor> cache_keep;         // ... and its tensors, kept until the next seed_cache
 
     JlmPlan(TDict t, IDict i) : tensors(std::move(t)) {
         const Tensor *ints = find(tensors, "ints");
@@ -330,6 +336,7 @@ int64_t decode_frames(const c10::intrusive_ptr<JlmModel> &model, const c10::intr
     // (Rounds 2-4 could replay the launch sequence as a captured hipGraph, JLM_GRAPH=1: correct and slower -- 3.52-3.58 vs 2.58-2.71 ms
     //  per 256-sentence chunk, hipGraphLaunch of the 130-node two-branch graph cost more than the launches -- removed in round 5.)
     const int rc = jlm_decode_frames(&model->m, &pl.p, &pl.lat, &pl.st, main.stream(), side_s, ev);
+    pl.p.cache = nullptr;                   // (seed_cache: the window of ONE frame loop)
     if (rc == -2) return -2;
     jlm_check(rc, "jlm_decode_frames");
     return 0;
@@ -592,6 +599,62 @@ void seed_context(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &src_h, 
                                pl.p.c, const_cast<int *>(pl.p.ctx_prev), const_cast<int *>(pl.p.ctx_word),
                                c10::hip::getCurrentHIPStream(pl.device).stream()),
               "jlm_seed_context");
+}
+
+// prime_frames that keeps its states (jlm_prime_cache_frames): target [n_steps][n_rows] int32, and the window's hist [cap][n_rows][H]
+// (4-byte values) / words [cap][n_rows] int32, which take the last `cap` frames' live rows and targets.
+void prime_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                        const Tensor &rows, const Tensor &prev, const Tensor &word, const Tensor &n_live, std::vector<int64_t> n_live_host,
+                        int64_t n_rows, int64_t n_steps, const Tensor &target, const Tensor &hist, const Tensor &words, int64_t cap) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    check_row_sets("prime_cache_frames", m, R, h0, c0, h1, c1, n_live_host, S, "frame", R);
+    TORCH_CHECK(is(rows, at::kInt, R) && is(prev, at::kInt, S * R) && is(word, at::kInt, S * R) && is(n_live, at::kInt, S) &&
+                    is(target, at::kInt, S * R),
+                "jlm.prime_cache_frames: int32 rows [n_rows], prev / word / target [n_steps][n_rows], n_live [n_steps]");
+    TORCH_CHECK(cap >= 1 && cap <= 0x7fffffff / std::max<int64_t>(R, 1) && hist.defined() && hist.is_cuda() && hist.is_contiguous() &&
+                    hist.element_size() == 4 && hist.numel() >= cap * R * m.H && is(words, at::kInt, cap * R),
+                "jlm.prime_cache_frames: hist [cap][n_rows][H] of 4-byte values, int32 words [cap][n_rows]");
+    TORCH_CHECK(R * (int64_t)std::max(m.H / 4, 1) < 0x7ffffff0ll, "jlm.prime_cache_frames: rows x H / 4 must stay below 2^31");
+    jlm_prime_plan p{};
+    p.n_rows = (int)R; p.n_steps = (int)S;
+    p.h[0] = ptr<void>(h0, "h0"); p.h[1] = ptr<void>(h1, "h1"); p.c[0] = ptr<float>(c0, "c0"); p.c[1] = ptr<float>(c1, "c1");
+    p.rows = ptr<const int>(rows, "rows"); p.prev = ptr<const int>(prev, "prev"); p.word = ptr<const int>(word, "word");
+    p.n_live = ptr<const int>(n_live, "n_live");
+    std::vector<int> live_host(n_live_host.begin(), n_live_host.end());
+    p.n_live_host = live_host.data();
+    (void)launch_frames("jlm_prime_cache_frames", h0.device().index(), false, 0, 1, [&](hipStream_t st, void *const *) {
+        return jlm_prime_cache_frames(&m, &p, ptr<const int>(target, "target"), hist.data_ptr(), ptr<int>(words, "words"), (int)cap, st);
+    });
+}
+
+// The window of a batch's sentences for the plan's NEXT frame loop (jlm_decode_plan.cache): no launch, the plan keeps the tensors.
+// hist [cap][n_src][H] (4-byte values), words [cap][n_src], count [n_src], idx [n_sent] int32 on the device, the scratch s
+// [n_sent * beam][ld_s] float32.  The frame loop that follows takes the struct and clears it: a later batch starts without a cache.
+void seed_cache(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &hist, const Tensor &words, const Tensor &count, const Tensor &idx,
+                const Tensor &s, int64_t cap, int64_t N, double theta, double lam) {
+    JlmPlan &pl = *plan;
+    const int64_t n_src = count.numel(), rmax = (int64_t)pl.lat.n_sent * pl.lat.beam;
+    TORCH_CHECK(pl.ctx_H > 0, "jlm.seed_cache: the plan was made without a left context");
+    TORCH_CHECK(cap >= 1 && N >= 1 && N <= JLM_CACHE_MIX_MAX_N && n_src >= 1 && n_src <= 0x7fffffff / cap, "jlm.seed_cache: cap, N or the row count");
+    const int64_t ld_s = rmax > 0 ? s.numel() / rmax : 0;
+    TORCH_CHECK(hist.defined() && hist.is_cuda() && hist.is_contiguous() && hist.element_size() == 4 && hist.numel() >= cap * n_src * pl.ctx_H &&
+                    is(words, at::kInt, cap * n_src) && is(count, at::kInt, n_src) && is(idx, at::kInt, pl.lat.n_sent) &&
+                    is(s, at::kFloat, rmax * std::min(cap, N)) && ld_s >= std::min(cap, N),
+                "jlm.seed_cache: hist [cap][n_src][H], int32 words [cap][n_src], count [n_src], idx [n_sent], float32 s [n_sent * beam][>= min(cap, N)]");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam > 0.0 && lam < 1.0, "jlm.seed_cache: theta >= 0, 0 < lam < 1");
+    pl.cache_keep = {hist, words, count, idx, s};
+    pl.cache.hist = hist.data_ptr(); pl.cache.words = ptr<const int>(words, "words"); pl.cache.count = ptr<const int>(count, "count");
+    pl.cache.cap = (int)cap; pl.cache.n_src = (int)n_src; pl.cache.idx = ptr<const int>(idx, "idx");
+    pl.cache.N = (int)N; pl.cache.theta = (float)theta; pl.cache.lam = (float)lam;
+    pl.cache.s = ptr<float>(s, "s"); pl.cache.ld_s = (int)ld_s;
+    pl.p.cache = &pl.cache;
+}
+
+// seed_cache undone: a batch that failed between seed_cache and its frame loop leaves no window behind on the plan
+void clear_cache(const c10::intrusive_ptr<JlmPlan> &plan) {
+    plan->p.cache = nullptr;
+    plan->cache_keep.clear();
 }
 
 // The predictions of an unfinished last word behind a plan's static decode (jlm_tail_predict): one launch on the current stream, which
@@ -1400,6 +1463,12 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor prev, Tensor word, Tensor n_live, int[] n_live_host, int n_rows, int n_steps) -> ()", prime_frames);
     m.def("seed_context(__torch__.torch.classes.jlm.Plan plan, Tensor src_h, Tensor src_c, Tensor last, Tensor has, Tensor idx) -> ()",
           seed_context);
+    m.def("prime_cache_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor rows, "
+          "Tensor prev, Tensor word, Tensor n_live, int[] n_live_host, int n_rows, int n_steps, Tensor target, Tensor(e!) hist, "
+          "Tensor(f!) words, int cap) -> ()", prime_cache_frames);
+    m.def("seed_cache(__torch__.torch.classes.jlm.Plan plan, Tensor hist, Tensor words, Tensor count, Tensor idx, Tensor(a!) s, int cap, int N, "
+          "float theta, float lam) -> ()", seed_cache);
+    m.def("clear_cache(__torch__.torch.classes.jlm.Plan plan) -> ()", clear_cache);
     m.def("tail_predict(__torch__.torch.classes.jlm.Model model, __torch__.torch.classes.jlm.Plan plan, Tensor ids, Tensor sp_off, "
           "Tensor sp_frame, Tensor sp_lo, Tensor sp_hi, int n_out, int chunk, Tensor(a!) out_score, Tensor(b!) out_row, Tensor(c!) out_word, "
           "Tensor(d!) out_nodes, Tensor(e!) out_len, int stride) -> ()", tail_predict);

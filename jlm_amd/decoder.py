@@ -194,25 +194,46 @@ class Decoder():
                 self.perf_log_lstm.append(t_lstm)
                 self.perf_log_softmax.append(t_soft)
 
-    def _context(self, context, n, single=False):
-        """the ``context=`` argument of decode / decode_batch as None or a jlm_amd.context.DecodeContext over the call's n inputs"""
+    def _context(self, context, n, single=False, cache=None):
+        """the ``context=`` argument of decode / decode_batch as None or a jlm_amd.context.DecodeContext over the call's n inputs;
+        ``cache``: the call's CacheSpec (word lists are primed with it)"""
+        from . import context as _context
+        if cache is not None:
+            _context.check_decode_cache(cache)
         if context is None:
             return None
-        from . import context as _context
-        return _context.resolve(self.model, context, n, self.w2i, single=single)
+        return _context.resolve(self.model, context, n, self.w2i, single=single, cache=cache)
+
+    def _refuse_cache(self, ctx, what, cache=None):
+        """ValueError where a decode under the continuous cache is asked of an entry point or an argument that has none: ``ctx`` a
+        resolved context, or ``cache`` the call's CacheSpec -- checked BEFORE the context is resolved, which primes word lists on the
+        device"""
+        from .context import CachedContext, DecodeContext, check_decode_cache
+        state = ctx.state if isinstance(ctx, DecodeContext) else ctx
+        if (cache is not None and check_decode_cache(cache).lam > 0.0) or (isinstance(state, CachedContext) and state.spec.lam > 0.0):
+            raise ValueError("%s takes no continuous cache (DESIGN.md section 21: the static full-vocabulary Decoder.decode only)" % what)
 
     def decode_batch(self, inputs, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-                     random_sampling=False, context=None):
-        """``context`` (keyword): the words committed in front of every input -- a list with one entry per input (None, empty, or a
+                     random_sampling=False, context=None, cache=None):
+        """``cache`` (keyword): a :class:`jlm_amd.cache.CacheSpec` (one theta, N <= 4096) beside ``context`` word lists, or a
+        :class:`jlm_amd.context.CachedContext` as ``context`` (``self.model.prime(contexts, cache=...)``): the continuous cache over
+        every input's own context -- its last N (state, next word) pairs -- is mixed into every edge cost, p = (1 - lam) p_lm + lam c
+        (DESIGN.md section 21); an input without context words is decoded as without a cache, and so is lam = 0.  ValueError with
+        ``vocab_select`` or ``compat_quirks``, before anything runs.
+        ``context`` (keyword): the words committed in front of every input -- a list with one entry per input (None, empty, or a
         sequence of word ids / lexicon strings; a string outside the vocabulary reads as <unk>), or a ContextState of one row per input
         (``self.model.prime``), which any number of calls may reuse.  Input i is decoded as the continuation of
         [<eos>] + context[i] (jlm_amd/context.py); scores are -log p(path | that history).  None, or nothing but empty entries: the
         reference's decode."""
         inputs = list(inputs)
-        ctx = self._context(context, len(inputs))
+        if vocab_select:                     # (before the context is resolved: nothing is primed for a call that is refused)
+            self._refuse_cache(context, "vocab_select", cache)
+        if self.compat_quirks:
+            self._refuse_cache(context, "compat_quirks", cache)
+        ctx = self._context(context, len(inputs), cache=cache)
         if beam_width is None:       # the reference's unpruned search, sentence at a time on the host
             return [self._decode_unpruned(x, topN, vocab_select, samples, top_sampling, random_sampling,
-                                          context=ctx.host_row(i) if ctx is not None else None) for i, x in enumerate(inputs)]
+                                          context=self._host_context(ctx, i)) for i, x in enumerate(inputs)]
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
             raise ValueError("beam_width must be 1..%d on the GPU path (or None: the unpruned host-side search)" % self.MAX_BEAM)
         if not inputs:
@@ -276,12 +297,20 @@ class Decoder():
             lv_last = self.lattice_vocab
             for i in sorted(heavy):
                 out[i] = self._decode_unpruned(inputs[i], topN, vocab_select, samples, top_sampling, random_sampling,
-                                               beam_width=beam_width, context=ctx.host_row(i) if ctx is not None else None)
+                                               beam_width=beam_width, context=self._host_context(ctx, i))
             if (len(inputs) - 1) not in heavy:
                 self.lattice_vocab = lv_last      # (the reference leaves the LAST sentence's list behind)
             return out
         self.perf_sen += len(inputs)
         return out
+
+    @staticmethod
+    def _host_context(ctx, i):
+        """what _decode_unpruned takes of input i's left context: None, (h, c, word), or under the cache (h, c, word, mix)"""
+        if ctx is None:
+            return None
+        mix = ctx.host_mixer(i)
+        return ctx.host_row(i) + ((mix,) if mix is not None else ())
 
     def _cand_limit(self, lat, beam_width):
         """candidates of one lattice cell the device beam step accepts for this batch shape"""
@@ -386,7 +415,8 @@ class Decoder():
         host: every candidate survives, each frame is one ``predict_with_context`` call over all of its paths (the GPU
         kernels behind LSTM_Model's numpy API), the result is the final frame in generation order, unsorted.  Also the
         engine of :meth:`_decode_stale_vocab` (a beam and a fixed vocabulary list).  ``context``: None, or (h [1, H], c [1, H], word)
-        -- the primed state read back and the last word of the history: what the root consumes, and from where."""
+        -- the primed state read back and the last word of the history: what the root consumes, and from where; a fourth element
+        mix(pred, h) under the continuous cache: every frame's probabilities become the mixture (context.DecodeContext.host_mixer)."""
         import math
         import numpy as np
         if len(input) == 0:
@@ -427,6 +457,8 @@ class Decoder():
                 cur["pred"], cur["h"], cur["c"] = [], [], []
                 continue
             (pred, _y, _t1, _t2), h2, c2 = self.model.predict_with_context([p[2] for p in cur["paths"]], hid, cel, vocab)
+            if context is not None and len(context) > 3:
+                pred = context[3](pred, h2)
             cur["pred"], cur["h"], cur["c"] = pred, h2, c2
         out = [(score, [w for w in nodes if w != "<eos>"]) for score, nodes, _lw in frames[len(input)]["paths"]]
         self.perf_sen += 1
@@ -475,10 +507,14 @@ class Decoder():
             yield item
 
     def decode(self, input, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-               random_sampling=False, context=None):
+               random_sampling=False, context=None, cache=None):
         """``context`` (keyword): the words committed in front of ``input`` -- one sequence of word ids / lexicon strings, or a
-        ContextState of one row (see decode_batch)."""
-        ctx = self._context(context, 1, single=True)
+        ContextState of one row (see decode_batch); ``cache``: decode_batch's."""
+        if vocab_select:
+            self._refuse_cache(context, "vocab_select", cache)
+        if self.compat_quirks or self.dynamic:
+            self._refuse_cache(context, "compat_quirks" if self.compat_quirks else type(self).__name__, cache)
+        ctx = self._context(context, 1, single=True, cache=cache)
         out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling, context=ctx)[0]
         if len(input):
             # the reference's shape: dict frame -> [Node] (decoder.py:79-135), what _build_lattice returns
@@ -495,7 +531,7 @@ class Decoder():
         """the tail starts of one input: [(s, lo, hi)] for every s in [0, len) at which vocabulary words properly extend text[s:]"""
         return index.tail_spans(text if isinstance(text, str) else "".join(text))
 
-    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None):
+    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None, cache=None):
         """Conversion while the user types: every input is kana whose LAST word may be unfinished.  -> per input a pair
         (conversions, predictions).  ``conversions`` is ``decode_batch(inputs, topN, beam_width, context=context)``'s list, the very
         launches and bits.  ``predictions`` is [(score, [word, ...])], at most ``topN`` (1 .. 64), ascending: the best paths that cover
@@ -511,6 +547,8 @@ class Decoder():
             raise TypeError("%s has no decode_predict: the last word is predicted from rows normalised over the full word vocabulary "
                             "(the static Decoder)" % type(self).__name__)
         inputs = list(inputs)
+        if cache is not None:
+            raise ValueError("decode_predict takes no continuous cache (DESIGN.md section 21: Decoder.decode only)")
         if beam_width is None:
             raise ValueError("decode_predict needs a beam (beam_width=None is the unpruned host-side search)")
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
@@ -555,6 +593,7 @@ class Decoder():
                              "beam %d (decode_batch would search them on the host); convert them with decode" %
                              (", ".join("%d (%r)" % (i, inputs[i]) for i in sorted(e.sentences)), beam_width))
         ctx = self._context(context.context, 1, single=True) if isinstance(context, _Single) else self._context(context, len(inputs))
+        self._refuse_cache(ctx, "decode_predict")
         if getattr(self, "_predict_ids", None) is None:
             import torch
             self._predict_ids = torch.from_numpy(np.ascontiguousarray(index.ids, dtype=np.int32)).to(self.model.dev.device)
@@ -578,11 +617,11 @@ class Decoder():
         self.perf_sen += len(full)
         return out
 
-    def decode_predict(self, input, topN=10, beam_width=10, context=None):
+    def decode_predict(self, input, topN=10, beam_width=10, context=None, cache=None):
         """:meth:`decode_predict_batch` of one input -> (conversions, predictions); ``context`` as :meth:`decode` takes it."""
         if self.dynamic or self.char_model:
             raise TypeError("%s has no decode_predict (see Decoder.decode_predict_batch)" % type(self).__name__)
-        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context))[0]
+        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context), cache=cache)[0]
         if len(input):
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
                                     for f, nodes in enumerate(self.last_lattice.backward_lookup(0))}

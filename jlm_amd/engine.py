@@ -148,6 +148,7 @@ class _Plan:
         self.busy = False
         # left context: the root rows' prev / word (seed_context_kernel writes entries s * beam), the batch's rows of the primed state
         self.ctx_prev = self.ctx_word = self.ctx_idx = self.ctx_idx_host = self.ctx_state = None
+        self.cache_bufs = None               # decodes under the continuous cache: their score scratch (_CacheBufs), made on first use
         if ctx:
             self.ctx_prev, self.ctx_word = torch.full((rmax,), -1, device=dev, dtype=i32), torch.zeros(rmax, device=dev, dtype=i32)
             self.ctx_idx, self.ctx_idx_host = torch.zeros(B, device=dev, dtype=i32), pin(torch.zeros(B, dtype=i32))
@@ -187,6 +188,19 @@ class _Plan:
 
     def fits(self, need):
         return all(self.caps[k] >= v for k, v in need.items())
+
+
+class _CacheBufs:
+    """The score scratch of a plan's decodes under the continuous cache: s [rmax, ld_s] float32 (jlm_decode_cache.s), kept on the plan
+    and reused while it is wide enough.  Zeroed memory; the kernels write every entry they read."""
+
+    def __init__(self, eng, rmax, ld_s):
+        self.ld_s = int(ld_s)
+        self.s = eng.torch.zeros((rmax, self.ld_s), device=eng.device, dtype=eng.torch.float32)
+
+    @staticmethod
+    def fit(have, eng, rmax, n):
+        return have if have is not None and have.ld_s >= n else _CacheBufs(eng, rmax, _round_up(max(n, 1), 64))
 
 
 class DecodeEngine:
@@ -289,7 +303,9 @@ class DecodeEngine:
         timing="inflight": the same events recorded on the batch's own stream of the PIPELINED submit -- a kernel's time
         then includes what it loses to the other batches in flight (bench.py: `frac_in_pipeline`).
         context: None, or (ContextState, the state's row of every sentence of ``lat``): the sentences' primed states are gathered behind
-        the plan's pool by one launch in front of the frame loop, on the batch's stream (jlm_amd/context.py).
+        the plan's pool by one launch in front of the frame loop, on the batch's stream (jlm_amd/context.py).  A CachedContext with
+        lam > 0 also hands the frame loop every sentence's window (``torch.ops.jlm.seed_cache``: no launch): the continuous cache is
+        mixed into every edge cost (static full-vocabulary decodes only, ValueError otherwise).
         predict: None, or ((sp_off [n_sent + 1], sp_frame, sp_lo, sp_hi), ids, words, n_out): the batch's spans in CSR (sentence s: the
         frames its unfinished tail may start at and the range of ``ids`` -- the device copy of ReadingIndex.ids -- of the words whose
         reading properly extends the tail from there), ``words`` the id -> string list; one more launch behind the frame loop
@@ -339,6 +355,9 @@ class DecodeEngine:
             rows = np.asarray(rows, dtype=np.int32).reshape(-1)
             if state.m is not self.m or rows.shape[0] != lat.n_sent or (rows.size and (rows.min() < 0 or rows.max() >= state.n)):
                 raise ValueError("context: one row of a ContextState of this model per sentence of the batch")
+        cached = context is not None and getattr(context[0], "spec", None) is not None and context[0].spec.lam > 0.0
+        if cached and (dynamic or vocab is not None or predict is not None):
+            raise ValueError("the continuous cache runs inside the static full-vocabulary decode only")
         if predict is not None:
             if dynamic or vocab is not None:
                 raise ValueError("predict: the last word is predicted behind a static full-vocabulary decode only")
@@ -365,10 +384,17 @@ class DecodeEngine:
                 p.ctx_idx_host.numpy()[:] = rows
                 p.ctx_idx.copy_(p.ctx_idx_host, non_blocking=True)
                 ops.backend().seed_context(p.obj, state.h, state.c, state.last, state.has, p.ctx_idx)
+                if cached:
+                    # the window of every sentence for this frame loop (jlm_decode_plan.cache): no launch, the op keeps the tensors
+                    p.cache_bufs = bufs = _CacheBufs.fit(p.cache_bufs, self, p.rmax, min(state.cap, state.spec.size))
+                    ops.backend().seed_cache(p.obj, state.hist, state.words, state.count, p.ctx_idx, bufs.s, int(state.cap),
+                                             int(state.spec.size), float(state.spec.theta), float(state.spec.lam))
             done = self._enqueue(p, lat, vocab, dyn_lists, dynamic, perm, max_words, topN, timing)
             if predict is not None:
                 done = self._enqueue_predict(p, sp, predict[1], n_pred)
         except BaseException:
+            if cached:
+                ops.backend().clear_cache(p.obj)      # (the window was for this batch's frame loop, which may not have run)
             # nothing may keep the plan: launches already enqueued finish first, then its buffers are free again
             if self.device.type == "cuda":
                 try:
@@ -507,6 +533,8 @@ class DecodeEngine:
             # (ABI 11) the beam step met a log-normaliser that is not finite: a row's sum of 2^y overflowed (or vanished) in the fixed-reference
             # normaliser -- an overflowed row's hypotheses would score -inf and be pruned, leaving a plausible but wrong n-best
             p.busy = False
+            if int(p.h_len[-1]) & 8:
+                raise _lib.JlmHipError("the cache flagged a product h . h_i that is not finite: a hidden state is NaN or inf")
             raise _lib.JlmHipError("a log-normaliser is not finite: this model's logits left the range the fixed-reference normaliser covers "
                                    "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
         if getattr(self.m, "lse_fixed_ref", 0):

@@ -52,6 +52,11 @@ def build_parser():
     parser.add_argument("--batch", type=int, default=1, help="sentences decoded per batch on the GPU")
     parser.add_argument("--context_words", "-cw", type=int, default=0,
                         help="gold words of every sentence given to the decoder as left context (the rest is converted)")
+    parser.add_argument("--cache", type=int, default=0,
+                        help="with --context_words: decode the set a second time under a continuous cache of N entries over every "
+                             "sentence's context (Decoder.decode(cache=)) and log both summaries")
+    parser.add_argument("--theta", type=float, default=0.3, help="--cache: the cache's theta")
+    parser.add_argument("--lam", type=float, default=0.1, help="--cache: the cache's lambda")
     parser.add_argument("--cut_last", type=int, default=0,
                         help="drop the last N kana of every reading and count how often the full target is among the predictions of "
                              "the unfinished last word (Decoder.decode_predict)")
@@ -83,6 +88,13 @@ class Evaluator:
         self.cut_last = max(0, int(getattr(args, "cut_last", 0) or 0))
         if self.cut_last and (args.use_ngram or self.config['char_rnn'] or args.dynamic_decoding or args.vocab_select):
             raise ValueError("--cut_last: the last word is predicted by the static decoder over the full vocabulary")
+        self.cache = None                # --cache N: the CacheSpec of the second pass
+        if int(getattr(args, "cache", 0) or 0):
+            if not self.context_words or args.dynamic_decoding or args.vocab_select or self.cut_last:
+                raise ValueError("--cache needs --context_words and the static decoder over the full vocabulary")
+            from .cache import CacheSpec
+            from .context import check_decode_cache
+            self.cache = check_decode_cache(CacheSpec(int(args.cache), theta=float(args.theta), lam=float(args.lam)))
         self.contexts = None             # with --context_words: every loaded sentence's context tokens (load_eval_set)
         self.decoder = self._make_decoder()
         if hasattr(self.decoder, "perf_timing"):
@@ -111,12 +123,16 @@ class Evaluator:
             name = name[:-len(".txt")] + "_ctx_{}.txt".format(self.context_words)
         if self.cut_last:
             name = name[:-len(".txt")] + "_cut_{}.txt".format(self.cut_last)
+        if self.cache is not None:
+            name = name[:-len(".txt")] + "_cache_{}.txt".format(self.cache.size)
         return name
 
-    def _decode_all(self, inputs):
+    def _decode_all(self, inputs, cache=None):
         a = self.args
         kw = dict(beam_width=a.beam_size, vocab_select=a.vocab_select, samples=a.samples,
                   top_sampling=a.top_sampling, random_sampling=a.random_sampling)
+        if cache is not None:
+            kw["cache"] = cache
         step = max(1, a.batch)
         ctx = self.contexts if self.context_words else None
         if step == 1:                 # sentence at a time, as the reference does
@@ -204,6 +220,25 @@ class Evaluator:
                 print("--- %s seconds per step for vocab fix.---" % fix(d.perf_log_fix_vocab))
                 print("--- %s seconds per step for lattice path fix.---" % fix(d.perf_log_fix_lattice_path_prob))
             print("--- %s seconds ---" % (time.time() - t_start))
+            if self.cache is not None:
+                # the same set once more under the cache: its verdicts and its summary line behind the first pass's
+                hits = {"best hit": 0, "nbest hit": 0, "no hit": 0}
+                t_start = time.time()
+                log.write('\n')
+                for x, y, nb in zip(inputs, targets, self._decode_all(inputs, cache=self.cache)):
+                    sentences = [''.join(_surface(w) for w in words) for _score, words in nb]
+                    verdict = "best hit" if y == sentences[0] else ("nbest hit" if y in sentences else "no hit")
+                    hits[verdict] += 1
+                    log.write(verdict + '\n')
+                    log.write('{}\t{}\n'.format(y, x))
+                    log.writelines(s + '\n' for s in sentences)
+                summary = 'cache {} theta {} lam {} best_hit {} nbest_hit{} no_hit {} eval_size {}'.format(
+                    self.cache.size, self.cache.theta, self.cache.lam, hits["best hit"], hits["nbest hit"],
+                    a.eval_size - hits["best hit"] - hits["nbest hit"], a.eval_size)
+                log.write(summary)
+                log.write("--- %s seconds ---" % (time.time() - t_start))
+                print(summary)
+                print("--- %s seconds ---" % (time.time() - t_start))
         return best, nbest_hits
 
     def load_eval_set(self):

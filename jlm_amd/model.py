@@ -922,15 +922,18 @@ class LSTM_Model():
         from .context import Primer
         return self._driver(Primer)
 
-    def prime(self, contexts, max_rows=None):
+    def prime(self, contexts, max_rows=None, cache=None):
         """The LSTM state after a left context, for many contexts at once, on the device (jlm_amd/context.py).  ``contexts``: word-id
         lists, empty ones allowed; context s stands for the history [<eos>] + contexts[s].  -> a :class:`jlm_amd.context.ContextState`
         of one row per context: the state after every word of the history but the last, and that last word -- what
         ``Decoder.decode_batch(..., context=state)`` starts frame 0 from.  The state is immutable and may be reused by any number of
         decodes.  One op per ``max_rows`` rows (default: from the buffers' size): the LSTM step of every frame and nothing else.
-        ValueError for an id outside [0, V) before anything runs."""
+        ValueError for an id outside [0, V) before anything runs.
+        ``cache``: a :class:`jlm_amd.cache.CacheSpec` (one theta, N <= 4096) -> a :class:`jlm_amd.context.CachedContext`, which also
+        keeps the last N (state, next word) pairs of every history: ``Decoder.decode_batch(..., context=state)`` then mixes the
+        continuous cache over that window into every edge cost."""
         from .context import prime
-        return prime(self._primer(), contexts, max_rows)
+        return prime(self._primer(), contexts, max_rows, cache=cache)
 
     def score(self, sequences, start, per_token=True, max_rows=None):
         """evaluate() for many sequences at once, on the device (jlm_amd/score.py).  ``sequences``: word-id lists of any length

@@ -17,7 +17,11 @@ def shard_indices(lengths, rank, world):
 
 
 def decode_sharded(decoder, sentences, rank, world, **decode_kwargs):
-    """-> (indices, results) for this rank's shard."""
+    """-> (indices, results) for this rank's shard.  ValueError for a decode under the continuous cache (``cache=``, a CachedContext):
+    a primed context holds one row per sentence of the whole call, not of a shard."""
+    from .context import CachedContext
+    if decode_kwargs.get("cache") is not None or isinstance(decode_kwargs.get("context"), CachedContext):
+        raise ValueError("decode_sharded takes no continuous cache: prime and decode every rank's own sentences")
     idx = shard_indices([len(s) for s in sentences], rank, world)
     if not idx:
         return idx, []
