@@ -17,6 +17,8 @@ every history too (``torch.ops.jlm.prime_cache_frames``) and returns a :class:`C
 over that fixed window into every edge cost (csrc/jlm_cache_edge.hip), and the host-side searches do the same in float64
 (:meth:`DecodeContext.host_mixer`).
 """
+from collections import namedtuple
+
 import numpy as np
 
 from . import ops as _ops
@@ -237,6 +239,11 @@ def prime(primer, contexts, max_rows=None, w2i=None, unk=0, checked=False, cache
         return CachedContext(m, h, c, dev(last), dev(has), last, has, hist, words, dev(count), count, cache)
 
 
+# What a host-side search takes of one input's left context: the primed state read back (h, c [1, H]: from where the root steps), the
+# last word of the history (what the root consumes) and, under the continuous cache, mix(pred, h) (DecodeContext.host_mixer), else None
+HostContext = namedtuple("HostContext", "h c word mix")
+
+
 class DecodeContext:
     """What the decoders pass down: a :class:`ContextState` and, per input of the call, its row."""
 
@@ -276,13 +283,17 @@ class DecodeContext:
     def sub(self, keep):
         return DecodeContext(self.state, [self.rows[i] for i in keep])
 
-    def host_row(self, i):
-        """(h [1, H], c [1, H] float64, last) of input i, for the host-side searches"""
+    def for_chunk(self, idx):
+        """what ``DecodeEngine.submit(context=)`` takes for the chunk of the call's inputs ``idx``"""
+        return self.state, [self.rows[j] for j in idx]
+
+    def host(self, i):
+        """input i's left context for the host-side searches: HostContext(h [1, H], c [1, H] float64, the last word, mix)"""
         if self._host is None:
             self._host = self.state.numpy()
         r = self.rows[i]
         h, c = self._host
-        return h[r:r + 1].astype(np.float64), c[r:r + 1].astype(np.float64), int(self.state.last_host[r])
+        return HostContext(h[r:r + 1].astype(np.float64), c[r:r + 1].astype(np.float64), int(self.state.last_host[r]), self.host_mixer(i))
 
 
 def resolve(model, context, n, w2i, single=False, cache=None):

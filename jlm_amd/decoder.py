@@ -36,7 +36,7 @@ Deliberate differences (DESIGN.md "Reference quirks"):
 import gc
 import os
 import pickle
-from collections import deque
+from collections import deque, namedtuple
 
 from . import config as _config
 from .data import Vocab
@@ -66,6 +66,11 @@ class _CellTooLarge(Exception):
     def __init__(self, sentences):
         Exception.__init__(self, sentences)
         self.sentences = list(sentences)
+
+
+# a chunk of a call between its preparation and its launch: the call's input indices, their lattice, and what the decode's own ``extra``
+# made of the two (word lists, spans; None without one)
+_Chunk = namedtuple("_Chunk", "idx lat extra")
 
 
 class Decoder():
@@ -194,21 +199,26 @@ class Decoder():
                 self.perf_log_lstm.append(t_lstm)
                 self.perf_log_softmax.append(t_soft)
 
-    def _context(self, context, n, single=False, cache=None):
-        """the ``context=`` argument of decode / decode_batch as None or a jlm_amd.context.DecodeContext over the call's n inputs;
-        ``cache``: the call's CacheSpec (word lists are primed with it)"""
+    def _context(self, context, n, cache=None):
+        """the ``context=`` argument of a batch method (a one-input call's as _Single) as None or a jlm_amd.context.DecodeContext over
+        the call's n inputs; ``cache``: the call's CacheSpec (word lists are primed with it)"""
         from . import context as _context
         if cache is not None:
             _context.check_decode_cache(cache)
+        single = isinstance(context, _Single)
+        if single:
+            context = context.context
         if context is None:
             return None
         return _context.resolve(self.model, context, n, self.w2i, single=single, cache=cache)
 
     def _refuse_cache(self, ctx, what, cache=None):
-        """ValueError where a decode under the continuous cache is asked of an entry point or an argument that has none: ``ctx`` a
-        resolved context, or ``cache`` the call's CacheSpec -- checked BEFORE the context is resolved, which primes word lists on the
+        """ValueError where a decode under the continuous cache is asked of an entry point or an argument that has none: ``ctx`` the
+        call's ``context=`` as given, ``cache`` its CacheSpec -- checked BEFORE the context is resolved, which primes word lists on the
         device"""
         from .context import CachedContext, DecodeContext, check_decode_cache
+        if isinstance(ctx, _Single):
+            ctx = ctx.context
         state = ctx.state if isinstance(ctx, DecodeContext) else ctx
         if (cache is not None and check_decode_cache(cache).lam > 0.0) or (isinstance(state, CachedContext) and state.spec.lam > 0.0):
             raise ValueError("%s takes no continuous cache (DESIGN.md section 21: the static full-vocabulary Decoder.decode only)" % what)
@@ -231,9 +241,9 @@ class Decoder():
         if self.compat_quirks:
             self._refuse_cache(context, "compat_quirks", cache)
         ctx = self._context(context, len(inputs), cache=cache)
+        sel = (vocab_select, samples, top_sampling, random_sampling)
         if beam_width is None:       # the reference's unpruned search, sentence at a time on the host
-            return [self._decode_unpruned(x, topN, vocab_select, samples, top_sampling, random_sampling,
-                                          context=self._host_context(ctx, i)) for i, x in enumerate(inputs)]
+            return [self._search_on_host(x, self._host_context(ctx, i), topN, None, *sel) for i, x in enumerate(inputs)]
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
             raise ValueError("beam_width must be 1..%d on the GPU path (or None: the unpruned host-side search)" % self.MAX_BEAM)
         if not inputs:
@@ -245,72 +255,91 @@ class Decoder():
                 raise ValueError("compat_quirks: the stale-vocabulary path of the reference takes no left context")
             return [self._decode_stale_vocab(x, topN, beam_width) for x in inputs]
         if not all(inputs):        # (an empty string / list is falsy)
-            # the reference's loop over an empty input leaves the <eos> path alone: [(0.0, [])] (decoder.py:220-241)
-            keep = [i for i, x in enumerate(inputs) if len(x)]
-            sub = self.decode_batch([inputs[i] for i in keep], topN, beam_width, vocab_select, samples, top_sampling,
-                                    random_sampling, context=ctx.sub(keep) if ctx is not None else None) if keep else []
-            out = [[(0.0, [])] for _ in inputs]
-            for i, r in zip(keep, sub):
-                out[i] = r
-            return out
+            return self._decode_subset(inputs, [i for i, x in enumerate(inputs) if len(x)], ctx, topN, beam_width, *sel)
         chunks = self._chunks(inputs, beam_width, reorder=not (samples and random_sampling))
+        workers = 1 if (samples and random_sampling) else self.prefetch_workers
+        extra, engine_kw, left = None, lambda _none: dict(vocab=None), None
+        if vocab_select:
+            # a chunk's word lists beside its lattice: (words, off) the engine's CSR over its sentences, lists[k] sentence k's own
+            extra = lambda idx, lat: lat.static_vocab(samples, top_sampling, random_sampling, len(self.w2i))
+            engine_kw = lambda vocab: dict(vocab=vocab[:2])
 
+            def left(vocab, k):      # the reference leaves the LAST sentence's list behind
+                self.lattice_vocab = vocab[2][k]
+        try:
+            out = self._launch_chunks(self._prepare_chunks(inputs, chunks, beam_width, workers, extra), chunks, len(inputs), ctx, topN,
+                                      beam_width, "static", engine_kw, left)
+        except _CellTooLarge as e:
+            return self._heavy_on_host(e.sentences, inputs, ctx, topN, beam_width, *sel)
+        self.perf_sen += len(inputs)
+        return out
+
+    def _decode_subset(self, inputs, keep, ctx, *args):
+        """decode_batch(*args) of the inputs ``keep`` alone, their context rows with them -> the whole call's result list: theirs in place,
+        [(0.0, [])] everywhere else -- an empty input's: the reference's loop leaves the <eos> path alone (decoder.py:220-241)"""
+        sub = self.decode_batch([inputs[i] for i in keep], *args, context=ctx.sub(keep) if ctx is not None else None) if keep else []
+        out = [[(0.0, [])] for _ in inputs]
+        for i, r in zip(keep, sub):
+            out[i] = r
+        return out
+
+    def _heavy_on_host(self, heavy, inputs, ctx, *args):
+        """The rest of a decode_batch(*args) call that met _CellTooLarge: the sentences named take the host-side search with the beam
+        (_search_on_host), everything else goes through the device again -> the call's result list."""
+        heavy = set(heavy)
+        out = self._decode_subset(inputs, [i for i in range(len(inputs)) if i not in heavy], ctx, *args)
+        lv_last = self.lattice_vocab
+        for i in sorted(heavy):
+            out[i] = self._search_on_host(inputs[i], self._host_context(ctx, i), *args)
+        if (len(inputs) - 1) not in heavy:
+            self.lattice_vocab = lv_last      # (the reference leaves the LAST sentence's list behind)
+        return out
+
+    # The chunk pipeline under decode_batch, decode_predict_batch and DynamicDecoder.decode_batch: _prepare_chunks is its host side,
+    # _launch_chunks its device side (decode_predict_batch drains the first before it starts the second).  What the three differ in comes
+    # as values: ``extra(idx, lat)``, what a chunk needs beside its lattice (word lists, spans), ``engine_kw(that)``, the engine's
+    # keywords made of it, and ``left(that, k)``, called when the chunk that holds the call's last input -- at position k -- is submitted.
+    def _prepare_chunks(self, texts, chunks, beam_width, workers, extra=None):
+        """Every chunk's _Chunk, in order and up to ``workers`` + 1 ahead of the consumer (_prefetched): the lattice (native, releases the
+        GIL), the check of its cells (_CellTooLarge) and ``extra``'s addition (None: none)."""
         def prepare(idx):
-            """host side of one chunk: lattice (native, releases the GIL) and, for vocab_select, its word lists"""
-            lat = BatchLattice(self._builder, [inputs[j] for j in idx], beam_width, pool=self._engine.staging_pool)
+            lat = BatchLattice(self._builder, [texts[j] for j in idx], beam_width, pool=self._engine.staging_pool)
             self._check_cells(lat, idx, beam_width)
-            if not vocab_select:
-                return idx, lat, None, None
-            words, off, lists = lat.static_vocab(samples, top_sampling, random_sampling, len(self.w2i))
-            return idx, lat, (words, off), lists
+            return _Chunk(idx, lat, extra(idx, lat) if extra is not None else None)
+        return self._prefetched(prepare, chunks, workers)
 
-        out = [None] * len(inputs)
+    def _launch_chunks(self, prepared, chunks, n, ctx, topN, beam_width, kind, engine_kw, left=None):
+        """The prepared chunks of a call of n inputs through the device pipeline (_run_pipeline): each is submitted with its rows of
+        ``ctx``, collected in order and scattered -> the call's result list."""
+        out = [None] * n
+
+        def submit(ch):
+            self.last_lattice = ch.lat
+            if left is not None and (n - 1) in ch.idx:
+                left(ch.extra, ch.idx.index(n - 1))
+            return ch.idx, self._engine.submit(ch.lat, kind, topN=topN, timing=self.perf_timing,
+                                               context=ctx.for_chunk(ch.idx) if ctx is not None else None, **engine_kw(ch.extra))
 
         def finish(idx, ticket):
             for j, r in zip(idx, self._engine.collect(ticket)):
                 out[j] = r
-            if ticket[1] is not self.last_lattice:        # (the lattice the caller may still look at keeps its arrays)
-                ticket[1].release()
+            if ticket.lat is not self.last_lattice:        # (the lattice the caller may still look at keeps its arrays)
+                ticket.lat.release()
             self._log_perf()
 
-        def submit(item):
-            idx, lat, vocab, lists = item
-            self.last_lattice = lat
-            if vocab_select and (len(inputs) - 1) in idx:
-                self.lattice_vocab = lists[idx.index(len(inputs) - 1)]      # the reference leaves the LAST sentence's list behind
-            return idx, self._engine.submit(lat, "static", vocab=vocab, topN=topN, timing=self.perf_timing,
-                                            context=(ctx.state, [ctx.rows[j] for j in idx]) if ctx is not None else None)
-
-        workers = 1 if (samples and random_sampling) else self.prefetch_workers
-        try:
-            self._run_pipeline(self._prefetched(prepare, chunks, workers), len(chunks), submit, finish,
-                               depth=self.depth_for(max(len(c) for c in chunks), beam_width))
-        except _CellTooLarge as e:
-            # the sentences named take the host-side beam search, everything else goes through the device again
-            heavy = set(e.sentences)
-            rest = [i for i in range(len(inputs)) if i not in heavy]
-            sub = self.decode_batch([inputs[i] for i in rest], topN, beam_width, vocab_select, samples, top_sampling,
-                                    random_sampling, context=ctx.sub(rest) if ctx is not None else None) if rest else []
-            out = [None] * len(inputs)
-            for i, r in zip(rest, sub):
-                out[i] = r
-            lv_last = self.lattice_vocab
-            for i in sorted(heavy):
-                out[i] = self._decode_unpruned(inputs[i], topN, vocab_select, samples, top_sampling, random_sampling,
-                                               beam_width=beam_width, context=self._host_context(ctx, i))
-            if (len(inputs) - 1) not in heavy:
-                self.lattice_vocab = lv_last      # (the reference leaves the LAST sentence's list behind)
-            return out
-        self.perf_sen += len(inputs)
+        self._run_pipeline(prepared, len(chunks), submit, finish, depth=self.depth_for(max(len(c) for c in chunks), beam_width))
         return out
 
     @staticmethod
     def _host_context(ctx, i):
-        """what _decode_unpruned takes of input i's left context: None, (h, c, word), or under the cache (h, c, word, mix)"""
-        if ctx is None:
-            return None
-        mix = ctx.host_mixer(i)
-        return ctx.host_row(i) + ((mix,) if mix is not None else ())
+        """what a host-side search takes of input i's left context: None or a jlm_amd.context.HostContext"""
+        return ctx.host(i) if ctx is not None else None
+
+    def _search_on_host(self, input, context, topN, beam_width, vocab_select, samples, top_sampling, random_sampling):
+        """one input searched on the host over LSTM_Model's numpy API: every input of a call with beam_width=None, and with the beam a
+        sentence whose lattice cells the device beam step cannot hold"""
+        return self._decode_unpruned(input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=beam_width,
+                                     context=context)
 
     def _cand_limit(self, lat, beam_width):
         """candidates of one lattice cell the device beam step accepts for this batch shape"""
@@ -368,8 +397,9 @@ class Decoder():
                 finish(*inflight.popleft())
         except BaseException:
             while inflight:                      # chunks already on the device: wait for them, their plans are released
+                _idx, ticket = inflight.popleft()
                 try:
-                    self._engine.collect(inflight.popleft()[1])
+                    self._engine.collect(ticket)
                 except Exception:
                     pass
             raise
@@ -414,9 +444,9 @@ class Decoder():
         """Decoder.decode of the reference with ``beam_width=None`` (decoder.py:220-241), statement for statement on the
         host: every candidate survives, each frame is one ``predict_with_context`` call over all of its paths (the GPU
         kernels behind LSTM_Model's numpy API), the result is the final frame in generation order, unsorted.  Also the
-        engine of :meth:`_decode_stale_vocab` (a beam and a fixed vocabulary list).  ``context``: None, or (h [1, H], c [1, H], word)
-        -- the primed state read back and the last word of the history: what the root consumes, and from where; a fourth element
-        mix(pred, h) under the continuous cache: every frame's probabilities become the mixture (context.DecodeContext.host_mixer)."""
+        engine of :meth:`_decode_stale_vocab` (a beam and a fixed vocabulary list).  ``context``: None, or a context.HostContext: h, c
+        [1, H] -- the primed state read back -- and word, the last of the history: what the root consumes, and from where; mix(pred, h)
+        under the continuous cache: every frame's probabilities become the mixture (context.DecodeContext.host_mixer)."""
         import math
         import numpy as np
         if len(input) == 0:
@@ -429,7 +459,7 @@ class Decoder():
         col = (lambda w: vocab.index(w)) if vocab is not None else (lambda w: w)       # ValueError for a word outside the list
         H = self.model.hidden_size
         # a path: (score, nodes tuple, word id of its last node); per frame also its state rows and probability rows
-        frames = {0: dict(paths=[(0.0, (), ends[0][0][2] if context is None else int(context[2]))])}
+        frames = {0: dict(paths=[(0.0, (), ends[0][0][2] if context is None else int(context.word))])}
         for i in range(len(input) + 1):
             if i > 0:
                 paths = []
@@ -449,7 +479,7 @@ class Decoder():
             if i == len(input):
                 break                                        # (the reference steps the last frame too and drops the result)
             if i == 0:
-                hid, cel = (np.zeros((1, H)), np.zeros((1, H))) if context is None else (np.asarray(context[0]), np.asarray(context[1]))
+                hid, cel = (np.zeros((1, H)), np.zeros((1, H))) if context is None else (np.asarray(context.h), np.asarray(context.c))
             else:
                 hid = np.stack([frames[f]["h"][k] for f, k in cur["src"]])
                 cel = np.stack([frames[f]["c"][k] for f, k in cur["src"]])
@@ -457,8 +487,8 @@ class Decoder():
                 cur["pred"], cur["h"], cur["c"] = [], [], []
                 continue
             (pred, _y, _t1, _t2), h2, c2 = self.model.predict_with_context([p[2] for p in cur["paths"]], hid, cel, vocab)
-            if context is not None and len(context) > 3:
-                pred = context[3](pred, h2)
+            if context is not None and context.mix is not None:
+                pred = context.mix(pred, h2)
             cur["pred"], cur["h"], cur["c"] = pred, h2, c2
         out = [(score, [w for w in nodes if w != "<eos>"]) for score, nodes, _lw in frames[len(input)]["paths"]]
         self.perf_sen += 1
@@ -510,12 +540,8 @@ class Decoder():
                random_sampling=False, context=None, cache=None):
         """``context`` (keyword): the words committed in front of ``input`` -- one sequence of word ids / lexicon strings, or a
         ContextState of one row (see decode_batch); ``cache``: decode_batch's."""
-        if vocab_select:
-            self._refuse_cache(context, "vocab_select", cache)
-        if self.compat_quirks or self.dynamic:
-            self._refuse_cache(context, "compat_quirks" if self.compat_quirks else type(self).__name__, cache)
-        ctx = self._context(context, 1, single=True, cache=cache)
-        out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling, context=ctx)[0]
+        out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling,
+                                context=_Single(context), cache=cache)[0]
         if len(input):
             # the reference's shape: dict frame -> [Node] (decoder.py:79-135), what _build_lattice returns
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
@@ -549,6 +575,7 @@ class Decoder():
         inputs = list(inputs)
         if cache is not None:
             raise ValueError("decode_predict takes no continuous cache (DESIGN.md section 21: Decoder.decode only)")
+        self._refuse_cache(context, "decode_predict")
         if beam_width is None:
             raise ValueError("decode_predict needs a beam (beam_width=None is the unpruned host-side search)")
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
@@ -572,48 +599,33 @@ class Decoder():
         for a in range(0, len(empty), self.max_batch):
             chunks.append(empty[a:a + self.max_batch])
 
-        def prepare(idx):
-            lat = BatchLattice(self._builder, [texts[j] for j in idx], beam_width, pool=self._engine.staging_pool)
-            self._check_cells(lat, idx, beam_width)
+        def spans(idx, _lat):
+            """the chunk's tail spans in CSR, as the engine takes them: (off [len(idx) + 1], frame, lo, hi)"""
             spans = [self._tail_spans(inputs[j], index) if len(inputs[j]) else [(0,) + tuple(index.ranges(""))[1:]] for j in idx]
             off = np.zeros(len(idx) + 1, dtype=np.int32)
             np.cumsum([len(s) for s in spans], out=off[1:])
             flat = np.array([t for s in spans for t in s], dtype=np.int32).reshape(-1, 3)
-            return idx, lat, (off, flat[:, 0].copy(), flat[:, 1].copy(), flat[:, 2].copy())
+            return off, flat[:, 0].copy(), flat[:, 1].copy(), flat[:, 2].copy()
 
         # every lattice before the first launch (the priming of the contexts included): a refusal leaves nothing enqueued
         prepared = []
         try:
-            for item in self._prefetched(prepare, chunks, self.prefetch_workers):
-                prepared.append(item)
+            for chunk in self._prepare_chunks(texts, chunks, beam_width, self.prefetch_workers, spans):
+                prepared.append(chunk)
         except _CellTooLarge as e:
-            for _idx, lat, _sp in prepared:
-                lat.release()
+            for chunk in prepared:
+                chunk.lat.release()
             raise ValueError("decode_predict: input(s) %s have a lattice cell with more candidates than the device beam step holds at "
                              "beam %d (decode_batch would search them on the host); convert them with decode" %
                              (", ".join("%d (%r)" % (i, inputs[i]) for i in sorted(e.sentences)), beam_width))
-        ctx = self._context(context.context, 1, single=True) if isinstance(context, _Single) else self._context(context, len(inputs))
-        self._refuse_cache(ctx, "decode_predict")
+        ctx = self._context(context, len(inputs))
         if getattr(self, "_predict_ids", None) is None:
             import torch
             self._predict_ids = torch.from_numpy(np.ascontiguousarray(index.ids, dtype=np.int32)).to(self.model.dev.device)
-        out = [None] * len(inputs)
-
-        def finish(idx, ticket):
-            for j, r in zip(idx, self._engine.collect(ticket)):
-                out[j] = r if len(inputs[j]) else ([(0.0, [])], r[1])
-            if ticket[1] is not self.last_lattice:
-                ticket[1].release()
-            self._log_perf()
-
-        def submit(item):
-            idx, lat, sp = item
-            self.last_lattice = lat
-            return idx, self._engine.submit(lat, "static", topN=topN, timing=self.perf_timing,
-                                            context=(ctx.state, [ctx.rows[j] for j in idx]) if ctx is not None else None,
-                                            predict=(sp, self._predict_ids, self.i2w, topN))
-
-        self._run_pipeline(iter(prepared), len(chunks), submit, finish, depth=self.depth_for(max(len(c) for c in chunks), beam_width))
+        out = self._launch_chunks(iter(prepared), chunks, len(inputs), ctx, topN, beam_width, "static",
+                                  lambda sp: dict(predict=(sp, self._predict_ids, self.i2w, topN)))
+        for j in empty:
+            out[j] = ([(0.0, [])], out[j][1])
         self.perf_sen += len(full)
         return out
 

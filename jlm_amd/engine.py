@@ -31,12 +31,16 @@ jlm_decode_frames, csrc/jlm_decode.hip): no host work between the frames, none o
 """
 import os
 import threading
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
 from . import ops
 
+# what DecodeEngine.submit returns for collect: the batch's plan (its buffers until collected) and lattice, topN and timing as submitted, the
+# event behind its last launch (None without a GPU), and the id -> string list of a predicting batch (submit(predict=)), else None
+Ticket = namedtuple("Ticket", "plan lat topN timing done words")
 
 _READOUT = [False]
 
@@ -355,7 +359,7 @@ class DecodeEngine:
             rows = np.asarray(rows, dtype=np.int32).reshape(-1)
             if state.m is not self.m or rows.shape[0] != lat.n_sent or (rows.size and (rows.min() < 0 or rows.max() >= state.n)):
                 raise ValueError("context: one row of a ContextState of this model per sentence of the batch")
-        cached = context is not None and getattr(context[0], "spec", None) is not None and context[0].spec.lam > 0.0
+        cached = context is not None and getattr(state, "spec", None) is not None and state.spec.lam > 0.0
         if cached and (dynamic or vocab is not None or predict is not None):
             raise ValueError("the continuous cache runs inside the static full-vocabulary decode only")
         if predict is not None:
@@ -403,9 +407,7 @@ class DecodeEngine:
                     pass
             p.busy = False
             raise
-        if predict is not None:
-            return (p, lat, topN, timing, done, predict[2])
-        return (p, lat, topN, timing, done)
+        return Ticket(p, lat, topN, timing, done, predict[2] if predict is not None else None)
 
     PREDICT_CHUNK = 0        # jlm_tail_predict's `chunk` (0: the launcher's default; tests move the chunk boundary)
 
@@ -515,7 +517,7 @@ class DecodeEngine:
 
     def collect(self, ticket):
         """Wait for a submitted batch and build its n-best lists."""
-        p, lat, topN, timing, done = ticket[:5]
+        p, lat, timing, done = ticket.plan, ticket.lat, ticket.timing, ticket.done
         with self._ctx():
             if done is not None:
                 done.synchronize()
@@ -545,9 +547,9 @@ class DecodeEngine:
                 p.busy = False
                 raise _lib.JlmHipError("a path score is not finite: this model's logits left the range the fixed-reference normaliser covers "
                                        "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
-        out = self._read_out(lat, p.h_nodes.numpy(), p.h_len.numpy()[:-1], p.h_score.numpy(), topN)
-        if len(ticket) > 5:
-            out = list(zip(out, self._read_predictions(lat, p, ticket[5])))
+        out = self._read_out(lat, p.h_nodes.numpy(), p.h_len.numpy()[:-1], p.h_score.numpy(), ticket.topN)
+        if ticket.words is not None:
+            out = list(zip(out, self._read_predictions(lat, p, ticket.words)))
         p.busy = False
         return out
 

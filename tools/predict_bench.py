@@ -106,10 +106,10 @@ def main(argv=None):
         torch.cuda.synchronize()
         e0, e1 = ev(), ev()
         e0.record()
-        ticket = eng._submit(lat, "static", None, None, topN, False, None, (sp, dec._predict_ids, dec.i2w, topN))
+        ticket = eng._submit(lat, "static", None, None, topN, False, predict=(sp, dec._predict_ids, dec.i2w, topN))
         e1.record()
         e1.synchronize()
-        p = ticket[0]
+        p = ticket.plan
         o = p.pr_off
         t0, t1 = ev(), ev()
         t0.record()
