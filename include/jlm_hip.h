@@ -1316,6 +1316,20 @@ int jlm_train_colsum(const float *a, int ld, int n_rows, int n_cols, float *out,
  * norm_weight, 0 without self-normalisation) ce_out[0] = +inf and flag[0] = 1 */
 int jlm_train_ce(const float *run_m, const float *run_s, const float *tgt_logit, int n_rows, float nw, double *ce_out, int *flag,
                  void *stream);
+/* ---- distillation (jlm_amd/distill.py).  Additive: ABI 12.  ys: a student's logits of words [v0, v0 + n_cols),
+ * yt: a frozen teacher's logits of the same words, each with its own leading dimension.  run [6, n_rows]: three running (max, sum exp)
+ * pairs, rows 0, 1 of ys (L_s), rows 2, 3 of ys inv_tau (A_s), rows 4, 5 of yt inv_tau (A_t); inv_tau = 1 / temperature > 0.
+ * Pass 1: the window's pairs merged into run (first: run is overwritten, not read), each logit read once, in granules of 64 words from
+ * the window's first as jlm_train_lse_update walks them: at inv_tau == 1 rows 0, 1 are that entry's bits and rows 2, 3 equal them. */
+int jlm_distill_lse_update(const float *ys, int ld_s, const float *yt, int ld_t, int n_cols, int n_rows, float inv_tau, float *run,
+                           int first, void *stream);
+/* Pass 2: ys -> dy = s (c_hard (p - onehot) + nw2 L_s p + c_soft (p^tau - q)) in place, p = exp(ys - L_s), p^tau = exp(ys inv_tau - A_s),
+ * q = exp(yt inv_tau - A_t); c_hard = 1 - alpha, c_soft = alpha tau.  tgt_logit as in jlm_train_dy.  kl_row[row] (first: = 0, else +=) the
+ * window's sum of q (log q - log p^tau), a q of 0 adding 0: one wave per row, granule sums by butterfly, taken in order. */
+int jlm_distill_dy(float *ys, int ld_s, const float *yt, int ld_t, int n_cols, int v0, int n_rows, const float *run, const int *target,
+                   float *tgt_logit, float *kl_row, float s, float nw2, float c_hard, float c_soft, float inv_tau, int first, void *stream);
+/* kl_out[0] (float64) = mean of kl_row; a value that is not finite gives +inf and flag[0] = 1 */
+int jlm_distill_kl(const float *kl_row, int n_rows, double *kl_out, int *flag, void *stream);
 /* demb[w - v_lo, e] += sum over the rows r that read word w of mask (.) dx[r, col0 + e], rows in index order, for the words in
  * [v_lo, v_hi) and e < n_cols: the target is that range of words and columns of the [V, width] gradient.  dx [n, ld_dx], the mask that of
  * the [n, width] array; ids_sorted int32 [n] ascending, perm int64 [n] the row of each (a stable sort) */

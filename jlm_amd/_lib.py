@@ -222,6 +222,9 @@ _SIGS = {
     "jlm_train_dy": ([P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P], c_int),
     "jlm_train_colsum": ([P, c_int, c_int, c_int, P, c_int, P], c_int),
     "jlm_train_ce": ([P, P, P, c_int, c_float, P, P, P], c_int),
+    "jlm_distill_lse_update": ([P, c_int, P, c_int, c_int, c_int, c_float, P, c_int, P], c_int),
+    "jlm_distill_dy": ([P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, P], c_int),
+    "jlm_distill_kl": ([P, c_int, P, P, P], c_int),
     "jlm_train_scatter_rows": ([P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, c_int, c_int, c_uint64, c_uint, c_float, P], c_int),
     "jlm_train_adam": ([P, P, P, P, c_longlong, c_float, P, P], c_int),
     "jlm_train_expand_codes": ([P, c_int, P, P, c_longlong, P], c_int),

@@ -1294,6 +1294,39 @@ void train_ce(const Tensor &run_m, const Tensor &run_s, const Tensor &tgt_logit,
               "jlm_train_ce");
 }
 
+void train_distill_lse_update(const Tensor &ys, int64_t ld_s, const Tensor &yt, int64_t ld_t, int64_t n_cols, int64_t n_rows, double inv_tau,
+                              const Tensor &run, bool first) {
+    TORCH_CHECK(n_cols >= 1 && n_rows >= 1 && ld_s >= n_cols && ld_s <= INT32_MAX && ld_t >= n_cols && ld_t <= INT32_MAX && n_rows <= INT32_MAX &&
+                inv_tau > 0.0 && std::isfinite(inv_tau), "jlm.train_distill_lse_update: bad shape");
+    const c10::hip::HIPGuard device_guard(ys.device().index());
+    jlm_check(jlm_distill_lse_update(vptr<const float>(ys, at::kFloat, span(n_rows, ld_s, n_cols), "ys"), (int)ld_s,
+                                     vptr<const float>(yt, at::kFloat, span(n_rows, ld_t, n_cols), "yt"), (int)ld_t, (int)n_cols, (int)n_rows,
+                                     (float)inv_tau, vptr<float>(run, at::kFloat, 6 * n_rows, "run"), first ? 1 : 0, stream_of(ys)),
+              "jlm_distill_lse_update");
+}
+
+void train_distill_dy(const Tensor &ys, int64_t ld_s, const Tensor &yt, int64_t ld_t, int64_t n_cols, int64_t v0, int64_t n_rows, const Tensor &run,
+                      const Tensor &target, const Tensor &tgt_logit, const Tensor &kl_row, double s, double nw2, double c_hard, double c_soft,
+                      double inv_tau, bool first) {
+    TORCH_CHECK(n_cols >= 1 && n_rows >= 1 && ld_s >= n_cols && ld_s <= INT32_MAX && ld_t >= n_cols && ld_t <= INT32_MAX && n_rows <= INT32_MAX &&
+                v0 >= 0 && v0 + n_cols <= INT32_MAX && inv_tau > 0.0 && std::isfinite(inv_tau), "jlm.train_distill_dy: bad shape");
+    const c10::hip::HIPGuard device_guard(ys.device().index());
+    jlm_check(jlm_distill_dy(vptr<float>(ys, at::kFloat, span(n_rows, ld_s, n_cols), "ys"), (int)ld_s,
+                             vptr<const float>(yt, at::kFloat, span(n_rows, ld_t, n_cols), "yt"), (int)ld_t, (int)n_cols, (int)v0, (int)n_rows,
+                             vptr<const float>(run, at::kFloat, 6 * n_rows, "run"), vptr<const int>(target, at::kInt, n_rows, "target"),
+                             vptr<float>(tgt_logit, at::kFloat, n_rows, "tgt_logit"), vptr<float>(kl_row, at::kFloat, n_rows, "kl_row"), (float)s,
+                             (float)nw2, (float)c_hard, (float)c_soft, (float)inv_tau, first ? 1 : 0, stream_of(ys)),
+              "jlm_distill_dy");
+}
+
+void train_distill_kl(const Tensor &kl_row, int64_t n_rows, const Tensor &kl_out, const Tensor &flag) {
+    TORCH_CHECK(n_rows >= 1 && n_rows <= INT32_MAX, "jlm.train_distill_kl: bad shape");
+    const c10::hip::HIPGuard device_guard(kl_row.device().index());
+    jlm_check(jlm_distill_kl(vptr<const float>(kl_row, at::kFloat, n_rows, "kl_row"), (int)n_rows, vptr<double>(kl_out, at::kDouble, 1, "kl_out"),
+                             vptr<int>(flag, at::kInt, 1, "flag"), stream_of(kl_row)),
+              "jlm_distill_kl");
+}
+
 void train_scatter_rows(const Tensor &dx, int64_t ld_dx, int64_t col0, int64_t n_cols, int64_t width, const Tensor &ids_sorted, const Tensor &perm,
                         int64_t n, const Tensor &demb, int64_t ld, int64_t v_lo, int64_t v_hi, int64_t key, int64_t thr, double scale) {
     TORCH_CHECK(n >= 1 && n <= INT32_MAX && n_cols >= 1 && col0 >= 0 && col0 + n_cols <= width && ld_dx >= width && ld_dx <= INT32_MAX &&
@@ -1453,6 +1486,12 @@ TORCH_LIBRARY(jlm, m) {
           "float s, float nw2) -> ()", train_dy);
     m.def("train_colsum(Tensor a, int ld, int n_rows, int n_cols, Tensor(a!) out, bool accumulate) -> ()", train_colsum);
     m.def("train_ce(Tensor run_m, Tensor run_s, Tensor tgt_logit, int n_rows, float nw, Tensor(a!) ce_out, Tensor(b!) flag) -> ()", train_ce);
+    m.def("train_distill_lse_update(Tensor ys, int ld_s, Tensor yt, int ld_t, int n_cols, int n_rows, float inv_tau, Tensor(a!) run, "
+          "bool first) -> ()", train_distill_lse_update);
+    m.def("train_distill_dy(Tensor(a!) ys, int ld_s, Tensor yt, int ld_t, int n_cols, int v0, int n_rows, Tensor run, Tensor target, "
+          "Tensor(b!) tgt_logit, Tensor(c!) kl_row, float s, float nw2, float c_hard, float c_soft, float inv_tau, bool first) -> ()",
+          train_distill_dy);
+    m.def("train_distill_kl(Tensor kl_row, int n_rows, Tensor(a!) kl_out, Tensor(b!) flag) -> ()", train_distill_kl);
     m.def("train_scatter_rows(Tensor dx, int ld_dx, int col0, int n_cols, int width, Tensor ids_sorted, Tensor perm, int n, Tensor(a!) demb, "
           "int ld, int v_lo, int v_hi, int key, int thr, float scale) -> ()", train_scatter_rows);
     m.def("train_adam(Tensor(a!) w, Tensor g, Tensor(b!) m, Tensor(c!) v, int n, float lr_t, Tensor? flag) -> ()", train_adam);

@@ -12,6 +12,9 @@
 // dy_kernel             logits of a chunk -> dy = s (p (1 + 2 nw lse) - onehot) in place; the target's logit is met on the way.
 // colsum_kernel         out[c] (+)= sum over rows in row order (db2 of a chunk, the gate biases).
 // ce_kernel             one workgroup: ce = mean(lse - y[target]) in f64 -> the pass's loss slot; a non-finite loss raises the flag word.
+// distill_lse_update_kernel, distill_dy_kernel, distill_kl_kernel
+//                       the same two passes over a student's and a frozen teacher's logits: three running
+//                       normalisers, dy with the soft term, and the Kullback-Leibler row sums, one writer and a fixed order.
 // scatter_rows_kernel   dEmb[w] += sum of mask (.) dx over the rows that read word w: the ids sorted, one wave per distinct word, index order.
 // adam_kernel           TensorFlow's Adam over the flat parameter buffer, 16-byte accesses; a raised flag word stops every update.
 // expand_codes_kernel   w = book[gid]: the weights of a compressed model from its codebooks (fine-tuning).
@@ -310,6 +313,147 @@ extern "C" int jlm_train_ce(const float *run_m, const float *run_s, const float 
                             void *stream) {
     if (!run_m || !run_s || !tgt_logit || !ce_out || !flag || n_rows < 1) return -1;
     hipLaunchKernelGGL(ce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, run_m, run_s, tgt_logit, n_rows, nw, ce_out, flag);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- the distillation loss
+// A student's logits y_s and a frozen teacher's y_t over the same words (jlm_amd/distill.py).  run [6, n_rows]
+// holds three running (max, sum exp) pairs: rows 0, 1 of y_s (L_s), rows 2, 3 of y_s / tau (A_s), rows 4, 5 of y_t / tau (A_t).
+//
+// Pass 1 walks the window as lse_update_kernel does, each logit read once: granules of 64 words from the window's first, one value per
+// lane, xor butterflies, merged in order.  Windows that start on multiples of 64 words leave the same bits however the words are cut,
+// and at inv_tau == 1.0f (y * 1.0f is y) the L_s pair is lse_update_kernel's and the A_s pair is the L_s pair, bit for bit.
+__global__ __launch_bounds__(256) void distill_lse_update_kernel(const float *__restrict__ ys, long long ld_s, const float *__restrict__ yt,
+                                                                 long long ld_t, int n_cols, int n_rows, float inv_tau,
+                                                                 float *__restrict__ run, int first) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n_rows) return;
+    const float *sr = ys + (long long)row * ld_s, *tr = yt + (long long)row * ld_t;
+    float M[3] = {JLM_NEG_BIG, JLM_NEG_BIG, JLM_NEG_BIG}, S[3] = {0.0f, 0.0f, 0.0f};
+    if (!first) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            M[k] = run[(long long)(2 * k) * n_rows + row];
+            S[k] = run[(long long)(2 * k + 1) * n_rows + row];
+        }
+    }
+    for (int c0 = 0; c0 < n_cols; c0 += 64) {
+        const int c = c0 + lane;
+        const bool in = c < n_cols;
+        float v[3] = {JLM_NEG_BIG, JLM_NEG_BIG, JLM_NEG_BIG};
+        if (in) {
+            v[0] = sr[c];
+            v[1] = v[0] * inv_tau;
+            v[2] = tr[c] * inv_tau;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float m = wave_max(v[k]);
+            const float s = wave_sum(in ? expf(v[k] - m) : 0.0f);
+            lse_merge(M[k], S[k], m, s);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            run[(long long)(2 * k) * n_rows + row] = M[k];
+            run[(long long)(2 * k + 1) * n_rows + row] = S[k];
+        }
+    }
+}
+
+extern "C" int jlm_distill_lse_update(const float *ys, int ld_s, const float *yt, int ld_t, int n_cols, int n_rows, float inv_tau, float *run,
+                                      int first, void *stream) {
+    if (!ys || !yt || !run || n_cols < 1 || n_rows < 1 || ld_s < n_cols || ld_t < n_cols || !(inv_tau > 0.0f) || !isfinite(inv_tau))
+        return -1;
+    hipLaunchKernelGGL(distill_lse_update_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ys,
+                       (long long)ld_s, yt, (long long)ld_t, n_cols, n_rows, inv_tau, run, first);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// Pass 2, one wave per row over the window's granules in order.  With p = exp(y_s - L_s), p^tau = exp(y_s / tau - A_s) and
+// q = exp(y_t / tau - A_t):  dy = s (c_hard (p - onehot) + nw2 L_s p + c_soft (p^tau - q)) in place over y_s, with c_hard = 1 - alpha and
+// c_soft = alpha tau from the host; the target's logit is met on the way.  The row's Kullback-Leibler terms q (log q - log p^tau), in
+// log space (q == 0 adds 0; a q that is not a number stays one), are added by butterfly per granule and the granule sums taken in order
+// into kl_row[row], which this wave alone writes and which starts at 0 when `first` is set: kl_row does not depend on the cut either.
+__global__ __launch_bounds__(256) void distill_dy_kernel(float *__restrict__ ys, long long ld_s, const float *__restrict__ yt, long long ld_t,
+                                                         int n_cols, int v0, int n_rows, const float *__restrict__ run,
+                                                         const int *__restrict__ target, float *__restrict__ tgt_logit,
+                                                         float *__restrict__ kl_row, float s, float nw2, float c_hard, float c_soft,
+                                                         float inv_tau, int first) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n_rows) return;
+    float *sr = ys + (long long)row * ld_s;
+    const float *tr = yt + (long long)row * ld_t;
+    const float Ls = run[row] + logf(run[(long long)n_rows + row]);
+    const float As = run[2ll * n_rows + row] + logf(run[3ll * n_rows + row]);
+    const float At = run[4ll * n_rows + row] + logf(run[5ll * n_rows + row]);
+    const int tg = target[row] - v0;
+    float kl = first ? 0.0f : kl_row[row];
+    for (int c0 = 0; c0 < n_cols; c0 += 64) {
+        const int c = c0 + lane;
+        float term = 0.0f;
+        if (c < n_cols) {
+            const float vs = sr[c], vt = tr[c];
+            const bool hit = c == tg;
+            if (hit) tgt_logit[row] = vs;
+            const float ls = vs * inv_tau - As, lt = vt * inv_tau - At;
+            const float p = expf(vs - Ls), pt = expf(ls), q = expf(lt);
+            term = q == 0.0f ? 0.0f : q * (lt - ls);
+            sr[c] = s * (c_hard * (p - (hit ? 1.0f : 0.0f)) + (p * nw2) * Ls + c_soft * (pt - q));
+        }
+        kl += wave_sum(term);
+    }
+    if (lane == 0) kl_row[row] = kl;
+}
+
+extern "C" int jlm_distill_dy(float *ys, int ld_s, const float *yt, int ld_t, int n_cols, int v0, int n_rows, const float *run,
+                              const int *target, float *tgt_logit, float *kl_row, float s, float nw2, float c_hard, float c_soft,
+                              float inv_tau, int first, void *stream) {
+    if (!ys || !yt || !run || !target || !tgt_logit || !kl_row || n_cols < 1 || n_rows < 1 || ld_s < n_cols || ld_t < n_cols || v0 < 0 ||
+        !(inv_tau > 0.0f) || !isfinite(inv_tau))
+        return -1;
+    hipLaunchKernelGGL(distill_dy_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ys, (long long)ld_s, yt,
+                       (long long)ld_t, n_cols, v0, n_rows, run, target, tgt_logit, kl_row, s, nw2, c_hard, c_soft, inv_tau, first);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// One workgroup, in ce_kernel's shape: kl_out[0] = the mean of kl_row in f64.  A value that is not finite gives +inf and raises the flag
+// word that stops Adam.
+__global__ __launch_bounds__(256) void distill_kl_kernel(const float *__restrict__ kl_row, int n_rows, double *__restrict__ kl_out,
+                                                         int *__restrict__ flag) {
+    __shared__ double part[256];
+    double s = 0.0;
+    int bad = 0;
+    for (int r = threadIdx.x; r < n_rows; r += 256) {
+        const float k = kl_row[r];
+        s += (double)k;
+        bad |= !isfinite(k);
+    }
+    bad = __syncthreads_or(bad);
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double kl = part[0] / (double)n_rows;
+        if (bad || !isfinite(kl) || !isfinite((float)kl)) {
+            kl_out[0] = (double)INFINITY;
+            flag[0] = 1;
+        } else {
+            kl_out[0] = kl;
+        }
+    }
+}
+
+extern "C" int jlm_distill_kl(const float *kl_row, int n_rows, double *kl_out, int *flag, void *stream) {
+    if (!kl_row || !kl_out || !flag || n_rows < 1) return -1;
+    hipLaunchKernelGGL(distill_kl_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kl_row, n_rows, kl_out, flag);
     JLM_LAUNCH_CHECK();
     return 0;
 }

@@ -364,10 +364,7 @@ class ReferenceStepper(_StepperBase):
         if not train:
             return
         # ---- backward
-        dY = np.exp(Y - lse[:, None])
-        if self.norm_weight:
-            dY *= (1.0 + 2.0 * self.norm_weight * lse)[:, None]
-        dY[np.arange(N), tgt] -= 1.0
+        dY = self._dy(Y, lse, ids, tgt)
         dY /= N
         g = {"b2": dY.sum(axis=0)}
         demb = dY.T @ P
@@ -396,6 +393,16 @@ class ReferenceStepper(_StepperBase):
         self._g = g
         self._update(g)
 
+    def _dy(self, Y, lse, ids, tgt):
+        """N times the gradient of a training step's loss in its logits Y [N, V] (a subclass trains on another loss:
+        jlm_amd/distill.py)"""
+        N = Y.shape[0]
+        dY = np.exp(Y - lse[:, None])
+        if self.norm_weight:
+            dY *= (1.0 + 2.0 * self.norm_weight * lse)[:, None]
+        dY[np.arange(N), tgt] -= 1.0
+        return dY
+
     def _update(self, g):
         """the tail of a training step: Adam over every tensor (a subclass updates something else: jlm_amd/finetune.py)"""
         w = self.w
@@ -411,6 +418,29 @@ class ReferenceStepper(_StepperBase):
 # ------------------------------------------------------------------------------------------------- the device
 def _signed64(z):
     return z - (1 << 64) if z >= 1 << 63 else z
+
+
+def vocabulary_segments(d):
+    """model_dims' dict -> the vocabulary as the device meets it: list of (start, end, width k, block key, how its projected rows
+    Q [N, k] come about: direct | cols | factored, first column of P, VT key or None)"""
+    V, E, segs = d["V"], d["E"], []
+    if d["kind"] == "tied":
+        segs.append((0, V, E, ("LM", None), "direct", 0, None))
+    c0 = 0
+    for i, (size, s, e) in enumerate(d["segs"]):
+        if d["kind"] == "dsoftmax":
+            segs.append((s, e, size, ("LM", i), "cols", c0, None))
+            c0 += size
+        elif i == 0:
+            segs.append((s, e, size, ("LM0", None), "direct", 0, None))
+        else:
+            segs.append((s, e, size, ("LM%d" % i, None), "factored", 0, ("VT%d" % i, None)))
+    return segs
+
+
+def window_pieces(segs, v0, v1):
+    """the words [v0, v1) cut where a segment ends: [(segment, piece start, piece length)]"""
+    return [(si, max(v0, sg[0]), min(v1, sg[1]) - max(v0, sg[0])) for si, sg in enumerate(segs) if sg[0] < v1 and sg[1] > v0]
 
 
 class DeviceStepper(_StepperBase):
@@ -449,18 +479,9 @@ class DeviceStepper(_StepperBase):
             #   direct    Q = P                      (tied LM; LM0 of a V_table model)
             #   cols      Q = P[:, c0:c0 + k]        (a D_softmax block)
             #   factored  Q = P VT^T                 (V_table segments i > 0: the cost stays V_i k, as in inference)
-            self.segs, self.Q, self.dQ, self.D = [], {}, {}, {}
-            if d["kind"] == "tied":
-                self.segs.append((0, V, E, ("LM", None), "direct", 0, None))
-            c0 = 0
-            for i, (size, s, e) in enumerate(d["segs"]):
-                if d["kind"] == "dsoftmax":
-                    self.segs.append((s, e, size, ("LM", i), "cols", c0, None))
-                    c0 += size
-                elif i == 0:
-                    self.segs.append((s, e, size, ("LM0", None), "direct", 0, None))
-                else:
-                    self.segs.append((s, e, size, ("LM%d" % i, None), "factored", 0, ("VT%d" % i, None)))
+            self.segs, self.Q, self.dQ, self.D = vocabulary_segments(d), {}, {}, {}
+            for i, (s, e, size, _blk, kind, _c0, _vt) in enumerate(self.segs):
+                if kind == "factored":
                     self.Q[i], self.dQ[i], self.D[i] = z(N, size), z(N, size), z(e - s, E)
             self.X, self.dX, self.P, self.dP = z(N, E), z(N, E), z(N, E), z(N, E)
             self.Z, self.dZ = z(N, 4 * H), z(N, 4 * H)
@@ -583,8 +604,7 @@ class DeviceStepper(_StepperBase):
         out = []
         for v0 in range(0, self.d["V"], self.Vc):
             v1 = min(self.d["V"], v0 + self.Vc)
-            pieces = [(si, max(v0, sg[0]), min(v1, sg[1]) - max(v0, sg[0])) for si, sg in enumerate(self.segs) if sg[0] < v1 and sg[1] > v0]
-            out.append((v0, v1 - v0, pieces))
+            out.append((v0, v1 - v0, window_pieces(self.segs, v0, v1)))
         return out
 
     def _logits(self, v0, pieces):
@@ -596,10 +616,44 @@ class DeviceStepper(_StepperBase):
             self.ops.train_gemm(Q, ldq, 1, self.p[blk][a - s:a - s + n], 1, k, self.Y[:, a - v0:], self.Vc, N, n, k, False,
                                 self.p[("b2", None)][a:a + n])
 
+    def _vocabulary_loss(self, train, ids_d, tgt_d):
+        """From P and the factored Q to the step's ce slot and, with ``train``, db2, dBlock, dVT and dP: the chunked vocabulary loss,
+        inside the step's device context (a subclass trains on another loss: jlm_amd/distill.py)"""
+        O, N, Vc = self.ops, self.B * self.T, self.Vc
+        windows = self._windows()
+        s, nw2 = 1.0 / N, 2.0 * self.norm_weight
+        for wi, (v0, n, pieces) in enumerate(windows):
+            self._logits(v0, pieces)
+            O.train_lse_update(self.Y, Vc, n, N, self.run_m, self.run_s, wi == 0)
+            if not train:            # the target's logit is read on the way (the dy written here is never used)
+                O.train_dy(self.Y, Vc, n, v0, N, self.run_m, self.run_s, tgt_d, self.tgt, s, nw2)
+        if train:
+            # ---- second pass: dy of a window in place, and the products it feeds, segment by segment
+            for v0, n, pieces in windows:
+                if len(windows) > 1:
+                    self._logits(v0, pieces)
+                O.train_dy(self.Y, Vc, n, v0, N, self.run_m, self.run_s, tgt_d, self.tgt, s, nw2)
+                self._dy_products(v0, n, pieces)
+        O.train_ce(self.run_m, self.run_s, self.tgt, N, self.norm_weight, self.ce[self.n_ce:], self.flag)
+
+    def _dy_products(self, v0, n, pieces):
+        """what the dy of a window (in Y) feeds: db2 of its words, then per piece dBlock, dQ and, where a factored segment ends, dVT, dP"""
+        O, p, g, N, E, Vc = self.ops, self.p, self.g, self.B * self.T, self.d["E"], self.Vc
+        O.train_colsum(self.Y, Vc, N, n, g[("b2", None)][v0:v0 + n], False)
+        for si, a, m in pieces:
+            s0, e0, k, blk, kind, _c0, vt = self.segs[si]
+            Q, ldq, dQ = self._q(si)
+            dy = self.Y[:, a - v0:]
+            O.train_gemm(dy, 1, Vc, Q, ldq, 1, g[blk][a - s0:a - s0 + m], k, m, k, N, False, None)      # dBlock = dy^T Q (TN)
+            O.train_gemm(dy, Vc, 1, p[blk][a - s0:a - s0 + m], k, 1, dQ, ldq, N, k, m, a > s0, None)    # dQ (+)= dy Block (NN)
+            if kind == "factored" and a + m == e0:
+                O.train_gemm(dQ, 1, k, self.P, E, 1, g[vt], E, k, E, N, False, None)                   # dVT_i = dQ_i^T P (TN)
+                O.train_gemm(dQ, k, 1, p[vt], E, 1, self.dP, E, N, E, k, True, None)                   # dP += dQ_i VT_i (NN)
+
     def step_async(self, x, y, train=True):
         torch, O, d, B, T = self.torch, self.ops, self.d, self.B, self.T
         ids, tgt = self._check_batch(x, y)
-        V, H, E, N, Vc = d["V"], d["H"], d["E"], B * T, self.Vc
+        V, H, E, N = d["V"], d["H"], d["E"], B * T
         keep = self.keep if train else 1.0
         thr, scale = keep_threshold(keep), 1.0 / keep
         key_in, key_out = _signed64(mask_key(self.seed, self.t, SITE_INPUT)), _signed64(mask_key(self.seed, self.t, SITE_OUTPUT))
@@ -625,30 +679,7 @@ class DeviceStepper(_StepperBase):
             for si, sg in enumerate(self.segs):
                 if sg[4] == "factored":                                                                            # Q_i = P VT_i^T (NT)
                     O.train_gemm(self.P, E, 1, p[sg[6]], 1, E, self.Q[si], sg[2], N, sg[2], E, False, None)
-            windows = self._windows()
-            s, nw2 = 1.0 / N, 2.0 * self.norm_weight
-            for wi, (v0, n, pieces) in enumerate(windows):
-                self._logits(v0, pieces)
-                O.train_lse_update(self.Y, Vc, n, N, self.run_m, self.run_s, wi == 0)
-                if not train:            # the target's logit is read on the way (the dy written here is never used)
-                    O.train_dy(self.Y, Vc, n, v0, N, self.run_m, self.run_s, tgt_d, self.tgt, s, nw2)
-            if train:
-                # ---- the vocabulary loss, second pass: dy of a window in place, and the products it feeds, segment by segment
-                for v0, n, pieces in windows:
-                    if len(windows) > 1:
-                        self._logits(v0, pieces)
-                    O.train_dy(self.Y, Vc, n, v0, N, self.run_m, self.run_s, tgt_d, self.tgt, s, nw2)
-                    O.train_colsum(self.Y, Vc, N, n, g[("b2", None)][v0:v0 + n], False)
-                    for si, a, m in pieces:
-                        s0, e0, k, blk, kind, _c0, vt = self.segs[si]
-                        Q, ldq, dQ = self._q(si)
-                        dy = self.Y[:, a - v0:]
-                        O.train_gemm(dy, 1, Vc, Q, ldq, 1, g[blk][a - s0:a - s0 + m], k, m, k, N, False, None)      # dBlock = dy^T Q (TN)
-                        O.train_gemm(dy, Vc, 1, p[blk][a - s0:a - s0 + m], k, 1, dQ, ldq, N, k, m, a > s0, None)    # dQ (+)= dy Block (NN)
-                        if kind == "factored" and a + m == e0:
-                            O.train_gemm(dQ, 1, k, self.P, E, 1, g[vt], E, k, E, N, False, None)                   # dVT_i = dQ_i^T P (TN)
-                            O.train_gemm(dQ, k, 1, p[vt], E, 1, self.dP, E, N, E, k, True, None)                   # dP += dQ_i VT_i (NN)
-            O.train_ce(self.run_m, self.run_s, self.tgt, N, self.norm_weight, self.ce[self.n_ce:], self.flag)
+            self._vocabulary_loss(train, ids_d, tgt_d)
             self.n_ce += 1
             self._mark("vocabulary")
             if train:

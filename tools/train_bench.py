@@ -17,8 +17,13 @@
                 step, IN THE SAME RUN: mid-tied and mid-vtable at B = 128, the codes of every tensor from kmeans_compress at BIT bits;
                 the same warm-up, timed steps and regions for both steppers, and the fine-tuning step's phases by HIP events
                 (codebook_grad, adam, expand take the place of the plain step's adam)
+  --distill TEACHER_FIXTURE
+                instead of all that: the distilling step (jlm_amd.distill.DistillDeviceStepper, alpha 0.5, temperature 2) beside the
+                plain step of the same student, IN THE SAME RUN: student mid-tied at H = 256, teacher TEACHER_FIXTURE (mid-tied or
+                mid-vtable) at H = 512, B = 128; step ms and phases of both (the phase ``teacher_forward`` ends where the teacher's P
+                and Q stand; it begins after the student's LSTM, so the student's own P is inside it)
 
-    python tools/train_bench.py [--quick] [--profile N] [--finetune BIT ...]
+    python tools/train_bench.py [--quick] [--profile N] [--finetune BIT ...] [--distill TEACHER_FIXTURE]
 """
 import argparse
 import json
@@ -36,10 +41,10 @@ F32_MATRIX_PEAK = 157e12
 T_STEPS = 20
 
 
-def _model(name):
+def _model(name, hidden=512):
     from jlm_amd import synth, train as T
     mode = name.split("-")[1]
-    cfg = synth.make_config(50000, 512, 256, mode, synth.README_SEGS, True)
+    cfg = synth.make_config(50000, hidden, 256, mode, synth.README_SEGS, True)
     return cfg, T.init_weights(cfg, None, 101)
 
 
@@ -104,17 +109,44 @@ def finetune_leg(bits, n_timed, n_warm, kw):
     return out
 
 
+def distill_leg(teacher_name, n_timed, n_warm, kw, alpha=0.5, temperature=2.0):
+    import torch
+    from jlm_amd import distill as D, train as T
+    cfg, w = _model("mid-tied", 256)
+    tcfg, tw = _model(teacher_name)
+    batches = _batches(50000, 128, n_timed)
+    out = {"bench": "distill", "device": torch.cuda.get_device_name(0), "num_steps": T_STEPS, "batch_size": 128, "timed_steps": n_timed,
+           "warmup": n_warm, "chunk_bytes": T.TRAIN_CHUNK_BYTES, "student": "mid-tied H=256", "teacher": "%s H=512" % teacher_name,
+           "alpha": alpha, "temperature": temperature}
+    for leg in ("plain", "distill"):
+        if leg == "plain":
+            st = T.DeviceStepper(cfg, w, 128, T_STEPS, **kw)
+        else:
+            st = D.DistillDeviceStepper(cfg, w, tcfg, tw, 128, T_STEPS, alpha=alpha, temperature=temperature, **kw)
+        secs, ph = _timed(st, batches, n_warm, torch)
+        out[leg] = {"step_ms": round(secs[1] / n_timed * 1e3, 3), "regions_s": [round(s, 4) for s in secs], "phase_ms": ph,
+                    "words_per_window": st.Vc, "vocab_windows": -(-st.d["V"] // st.Vc)}
+        del st
+        torch.cuda.empty_cache()
+    out["ratio"] = round(out["distill"]["step_ms"] / out["plain"]["step_ms"], 4)
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--quick", action="store_true", help="10 timed steps per region, B = 128 only")
     ap.add_argument("--profile", type=int, default=0, metavar="N")
     ap.add_argument("--finetune", type=int, nargs="+", default=None, metavar="BIT")
+    ap.add_argument("--distill", default=None, metavar="TEACHER_FIXTURE", choices=("mid-tied", "mid-vtable"))
     args = ap.parse_args(argv)
     import torch
     from jlm_amd import train as T
     kw = dict(lr=1e-3, dropout=0.9, norm_weight=0.1, seed=1)
     if args.finetune:
         return finetune_leg(args.finetune, *((10, 3) if args.quick else (50, 10)), kw)
+    if args.distill:
+        return distill_leg(args.distill, *((10, 3) if args.quick else (50, 10)), kw)
     if args.profile:
         cfg, w = _model("mid-vtable")
         st = T.DeviceStepper(cfg, w, 128, T_STEPS, **kw)
