@@ -1339,6 +1339,27 @@ int jlm_train_scatter_rows(const float *dx, int ld_dx, int col0, int n_cols, int
  * lr sqrt(1 - beta2^t) / (1 - beta1^t) from the host.  flag (may be NULL): nothing is updated once flag[0] != 0 */
 int jlm_train_adam(float *w, const float *g, float *m, float *v, long long n, float lr_t, const int *flag, void *stream);
 
+/* ---- dynamic evaluation (jlm_amd/dyneval.py).  Additive: ABI 12. */
+/* jlm_train_gemm split over the contraction: split s of S = ceil(K / kc) (kc a multiple of 16) runs the same fmaf chain over
+ * [s kc, min(K, (s + 1) kc)) and writes its tile to part[s][M][N]; a second launch forms part[0] + part[1] + ... in that order, adds the
+ * bias, then C when accumulating, and writes C.  One writer per element, no atomics: the result depends on the operands and kc alone,
+ * and with S = 1 it is jlm_train_gemm's bits.  part: part_elems float32 of scratch, -1 when part_elems < S M N. */
+int jlm_train_gemm_splitk(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, float *C, int ldc,
+                          int M, int N, int K, int accumulate, const float *bias, int kc, float *part, long long part_elems,
+                          void *stream);
+#define JLM_DYNEVAL_MAX_BLOCKS 4096
+/* ms[i] = fmaf(g[i], g[i], ms[i]) over n values, n a multiple of 4, pointers 16-byte aligned.  flag as in jlm_train_adam. */
+int jlm_dyneval_sqacc(float *ms, const float *g, long long n, const int *flag, void *stream);
+/* rms[i] = sqrtf(ms[i] inv_chunks), and mean_out[0] (float64) = the sum of those f32 values / n_real in a fixed order: per block a partial
+ * sum into partial (float64 [JLM_DYNEVAL_MAX_BLOCKS]), then one workgroup adds the partials in index order.  n_real <= n: the number of
+ * parameters among the n words (the padding words hold 0). */
+int jlm_dyneval_rms(const float *ms, long long n, float inv_chunks, float *rms, long long n_real, double *partial, double *mean_out,
+                    void *stream);
+/* w = (float)((w - step) + min(lam_scale r, 1) (w0 - w)) evaluated in float64: r = rms[i] and step = lr g / (r + eps), or with rms NULL
+ * r = 1 and step = lr g.  One rounding to f32 per element.  n a multiple of 4, pointers 16-byte aligned; flag as in jlm_train_adam. */
+int jlm_dyneval_update(float *w, const float *g, const float *w0, const float *rms, long long n, double lr, double lam_scale, double eps,
+                       const int *flag, void *stream);
+
 /* ---- fine-tuning the codebooks of a k-means compressed model (jlm_amd/finetune.py).  Additive: ABI 12.
  * A compressed model's weights are w[i] = book[gid[i]] over the flat parameter buffer: book holds every tensor's codebook, tensor t at
  * t K (K = 2^bit); gid[i] = t K + code for a coded element, -1 for the padding between tensors.  The codes never change. */

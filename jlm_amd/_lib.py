@@ -227,6 +227,11 @@ _SIGS = {
     "jlm_distill_kl": ([P, c_int, P, P, P], c_int),
     "jlm_train_scatter_rows": ([P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, c_int, c_int, c_uint64, c_uint, c_float, P], c_int),
     "jlm_train_adam": ([P, P, P, P, c_longlong, c_float, P, P], c_int),
+    "jlm_train_gemm_splitk": ([P, c_longlong, c_longlong, P, c_longlong, c_longlong, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P,
+                               c_longlong, P], c_int),
+    "jlm_dyneval_sqacc": ([P, P, c_longlong, P, P], c_int),
+    "jlm_dyneval_rms": ([P, c_longlong, c_float, P, c_longlong, P, P, P], c_int),
+    "jlm_dyneval_update": ([P, P, P, P, c_longlong, c_double, c_double, c_double, P, P], c_int),
     "jlm_train_expand_codes": ([P, c_int, P, P, c_longlong, P], c_int),
     "jlm_train_codebook_grad": ([P, c_longlong, P, c_longlong, P, c_int, c_int, P, P, P], c_int),
 }

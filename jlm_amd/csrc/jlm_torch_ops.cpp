@@ -51,7 +51,9 @@
 //   torch.ops.jlm.train_*       the kernels of a training step, one op per launcher (jlm_train.hip; jlm_amd/train.py DeviceStepper)
 //   torch.ops.jlm.train_expand_codes / train_codebook_grad
 //                               fine-tuning the codebooks of a compressed model (jlm_amd/finetune.py CodebookDeviceStepper)
-//   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows      LSTM_Model.predict / project (numpy-facing API)
+//   torch.ops.jlm.train_gemm_splitk / dyneval_sqacc / dyneval_rms / dyneval_update
+//                               dynamic evaluation (jlm_amd/dyneval.py DynEvalDeviceStepper)
+//   torch.ops.jlm.lstm_step / gemm_nt / softmax_rows     LSTM_Model.predict / project (numpy-facing API)
 //   torch.ops.jlm.pack_split_f16 / pack_split_f16_col / dequant_u8     weight preparation at load
 //
 // Built by __graft_entry__.build():  g++ -shared ... -> jlm_amd/_torch_ops.so, loaded with torch.ops.load_library.
@@ -1350,6 +1352,55 @@ void train_adam(const Tensor &w, const Tensor &g, const Tensor &m, const Tensor 
               "jlm_train_adam");
 }
 
+// ---- dynamic evaluation (jlm_amd/dyneval.py)
+void train_gemm_splitk(const Tensor &A, int64_t sam, int64_t sak, const Tensor &B, int64_t sbk, int64_t sbn, const Tensor &C, int64_t ldc,
+                       int64_t M, int64_t N, int64_t K, bool accumulate, const OptTensor &bias, int64_t kc, const Tensor &part) {
+    TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX && ldc >= N && ldc <= INT32_MAX && sam >= 1 &&
+                sak >= 1 && sbk >= 1 && sbn >= 1 && kc >= 16 && kc % 16 == 0 && kc <= INT32_MAX, "jlm.train_gemm_splitk: bad shape");
+    TORCH_CHECK(part.defined() && part.is_contiguous() && part.numel() >= (K + kc - 1) / kc * M * N,
+                "jlm.train_gemm_splitk: `part` holds fewer than ceil(K / kc) M N values");
+    const c10::hip::HIPGuard device_guard(C.device().index());
+    const bool has_bias = bias.has_value() && bias->defined();
+    jlm_check(jlm_train_gemm_splitk(vptr<const float>(A, at::kFloat, (M - 1) * sam + (K - 1) * sak + 1, "A"), sam, sak,
+                                    vptr<const float>(B, at::kFloat, (K - 1) * sbk + (N - 1) * sbn + 1, "B"), sbk, sbn,
+                                    vptr<float>(C, at::kFloat, span(M, ldc, N), "C"), (int)ldc, (int)M, (int)N, (int)K, accumulate ? 1 : 0,
+                                    has_bias ? vptr<const float>(*bias, at::kFloat, N, "bias") : nullptr, (int)kc,
+                                    vptr<float>(part, at::kFloat, part.numel(), "part"), (long long)part.numel(), stream_of(C)),
+              "jlm_train_gemm_splitk");
+}
+
+void dyneval_sqacc(const Tensor &ms, const Tensor &g, int64_t n, const OptTensor &flag) {
+    TORCH_CHECK(n >= 4 && n % 4 == 0, "jlm.dyneval_sqacc: n must be a positive multiple of 4");
+    const c10::hip::HIPGuard device_guard(ms.device().index());
+    const bool has_flag = flag.has_value() && flag->defined();
+    jlm_check(jlm_dyneval_sqacc(vptr<float>(ms, at::kFloat, n, "ms"), vptr<const float>(g, at::kFloat, n, "g"), (long long)n,
+                                has_flag ? vptr<const int>(*flag, at::kInt, 1, "flag") : nullptr, stream_of(ms)),
+              "jlm_dyneval_sqacc");
+}
+
+void dyneval_rms(const Tensor &ms, int64_t n, double inv_chunks, const Tensor &rms, int64_t n_real, const Tensor &partial,
+                 const Tensor &mean_out) {
+    TORCH_CHECK(n >= 4 && n % 4 == 0 && n_real >= 1 && n_real <= n && inv_chunks > 0.0 && std::isfinite(inv_chunks),
+                "jlm.dyneval_rms: n must be a positive multiple of 4, 1 <= n_real <= n, inv_chunks > 0");
+    const c10::hip::HIPGuard device_guard(ms.device().index());
+    jlm_check(jlm_dyneval_rms(vptr<const float>(ms, at::kFloat, n, "ms"), (long long)n, (float)inv_chunks, vptr<float>(rms, at::kFloat, n, "rms"),
+                              (long long)n_real, vptr<double>(partial, at::kDouble, JLM_DYNEVAL_MAX_BLOCKS, "partial"),
+                              vptr<double>(mean_out, at::kDouble, 1, "mean_out"), stream_of(ms)),
+              "jlm_dyneval_rms");
+}
+
+void dyneval_update(const Tensor &w, const Tensor &g, const Tensor &w0, const OptTensor &rms, int64_t n, double lr, double lam_scale, double eps,
+                    const OptTensor &flag) {
+    TORCH_CHECK(n >= 4 && n % 4 == 0, "jlm.dyneval_update: n must be a positive multiple of 4");
+    const c10::hip::HIPGuard device_guard(w.device().index());
+    const bool has_rms = rms.has_value() && rms->defined(), has_flag = flag.has_value() && flag->defined();
+    jlm_check(jlm_dyneval_update(vptr<float>(w, at::kFloat, n, "w"), vptr<const float>(g, at::kFloat, n, "g"),
+                                 vptr<const float>(w0, at::kFloat, n, "w0"), has_rms ? vptr<const float>(*rms, at::kFloat, n, "rms") : nullptr,
+                                 (long long)n, lr, lam_scale, eps,
+                                 has_flag ? vptr<const int>(*flag, at::kInt, 1, "flag") : nullptr, stream_of(w)),
+              "jlm_dyneval_update");
+}
+
 // ---- fine-tuning the codebooks of a compressed model (jlm_amd/finetune.py)
 void train_expand_codes(const Tensor &book, const Tensor &gid, const Tensor &w, int64_t n) {
     TORCH_CHECK(n >= 4 && n % 4 == 0, "jlm.train_expand_codes: n must be a positive multiple of 4");
@@ -1495,6 +1546,12 @@ TORCH_LIBRARY(jlm, m) {
     m.def("train_scatter_rows(Tensor dx, int ld_dx, int col0, int n_cols, int width, Tensor ids_sorted, Tensor perm, int n, Tensor(a!) demb, "
           "int ld, int v_lo, int v_hi, int key, int thr, float scale) -> ()", train_scatter_rows);
     m.def("train_adam(Tensor(a!) w, Tensor g, Tensor(b!) m, Tensor(c!) v, int n, float lr_t, Tensor? flag) -> ()", train_adam);
+    m.def("train_gemm_splitk(Tensor A, int sam, int sak, Tensor B, int sbk, int sbn, Tensor(a!) C, int ldc, int M, int N, int K, bool accumulate, "
+          "Tensor? bias, int kc, Tensor(b!) part) -> ()", train_gemm_splitk);
+    m.def("dyneval_sqacc(Tensor(a!) ms, Tensor g, int n, Tensor? flag) -> ()", dyneval_sqacc);
+    m.def("dyneval_rms(Tensor ms, int n, float inv_chunks, Tensor(a!) rms, int n_real, Tensor(b!) partial, Tensor(c!) mean_out) -> ()", dyneval_rms);
+    m.def("dyneval_update(Tensor(a!) w, Tensor g, Tensor w0, Tensor? rms, int n, float lr, float lam_scale, float eps, Tensor? flag) -> ()",
+          dyneval_update);
     m.def("train_expand_codes(Tensor book, Tensor gid, Tensor(a!) w, int n) -> ()", train_expand_codes);
     m.def("train_codebook_grad(Tensor g, Tensor order, Tensor chunks, int n_chunks, int n_groups, Tensor(a!) partial, Tensor(b!) gbook) -> ()",
           train_codebook_grad);

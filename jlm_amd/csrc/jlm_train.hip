@@ -5,6 +5,8 @@
 // train_gemm_kernel     C (+)= A B (+ bias) over operands given by element strides: the NT form (both K-contiguous), the row-contracting
 //                       TN form (dW = X^T dZ, dEmb = dY^T P) and the NN form (dP += dY Emb).  64 x 64 tile, 4 x 4 per lane, an exact f32
 //                       fmaf chain in k order per output element; the k tile sits in LDS once and is read along either axis.
+// train_gemm_splitk_kernel, train_gemm_combine_kernel
+//                       the same product split over the contraction, the splits' tiles added in order by a second launch (section 23).
 // embed_rows_kernel     x = mask (.) Emb[id]: the step's input rows.
 // cell_fwd_kernel       z -> i, f, o, g (kept, in place), c, h, and the dropped output r = mask (.) h.
 // cell_bwd_kernel       dh = mask (.) dr + dh_next, dc -> dz [B, 4H], dc_prev.
@@ -17,6 +19,9 @@
 //                       normalisers, dy with the soft term, and the Kullback-Leibler row sums, one writer and a fixed order.
 // scatter_rows_kernel   dEmb[w] += sum of mask (.) dx over the rows that read word w: the ids sorted, one wave per distinct word, index order.
 // adam_kernel           TensorFlow's Adam over the flat parameter buffer, 16-byte accesses; a raised flag word stops every update.
+// dyneval_sqacc_kernel, dyneval_rms_kernel, dyneval_mean_kernel, dyneval_update_kernel
+//                       dynamic evaluation: ms += g^2, rms = sqrt(ms / chunks) with its f64 mean in a fixed order, and
+//                       the decay-to-prior update over the flat parameter buffer.
 // expand_codes_kernel   w = book[gid]: the weights of a compressed model from its codebooks (fine-tuning).
 // codebook_partial_kernel, codebook_combine_kernel
 //                       the codebook gradient: per code the sum of its elements' weight gradients, in f64, a fixed order, one writer.
@@ -105,6 +110,103 @@ extern "C" int jlm_train_gemm(const float *A, long long sam, long long sak, cons
     if (gy > 65535 || gx > 2147483647ll) return -1;
     hipLaunchKernelGGL(train_gemm_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, A, sam, sak, B, sbk, sbn, C,
                        (long long)ldc, M, N, K, accumulate, bias, sak == 1 ? 1 : 0, sbn == 1 ? 1 : 0);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same product split over the contraction: at B T of a few rows C has a handful of tiles under a K as long as
+// the vocabulary.  Split s = blockIdx.z runs the fmaf chain over [s kc, min(K, (s + 1) kc)) and writes its tile to part[s][M][N];
+// train_gemm_combine_kernel then forms v = part[0] + part[1] + ... in that order, adds the bias, then *c when accumulating -- the
+// epilogue order above.  One writer per element and no atomics: the bits depend on the operands and kc alone, and one split gives
+// train_gemm_kernel's.
+// train_gemm_kernel's tile loop over the k tiles of [k_lo, k_hi) (k_lo a multiple of TG_BK): the same loads, the same fmaf chain per output
+// element in k order.  (A copy, not a shared function: the trainer's kernel stays the code it was.)
+__device__ __forceinline__ void tg_accumulate(const float *__restrict__ A, long long sam, long long sak, const float *__restrict__ B,
+                                              long long sbk, long long sbn, int M, int N, int k_lo, int k_hi, int a_kfast, int b_nfast,
+                                              float (&acc)[4][4]) {
+    __shared__ __attribute__((aligned(16))) float As[TG_BK][TG_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[TG_BK][TG_LD];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int m0 = blockIdx.y * TG_BM, n0 = blockIdx.x * TG_BN;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
+    for (int k0 = k_lo; k0 < k_hi; k0 += TG_BK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + i * 256;
+            int mm, kk;
+            if (a_kfast) { kk = idx & 15; mm = idx >> 4; } else { mm = idx & 63; kk = idx >> 6; }
+            const int gm = m0 + mm, gk = k0 + kk;
+            As[kk][mm] = (gm < M && gk < k_hi) ? A[(long long)gm * sam + (long long)gk * sak] : 0.0f;
+            int nn;
+            if (b_nfast) { nn = idx & 63; kk = idx >> 6; } else { kk = idx & 15; nn = idx >> 4; }
+            const int gn = n0 + nn, gk2 = k0 + kk;
+            Bs[kk][nn] = (gn < N && gk2 < k_hi) ? B[(long long)gk2 * sbk + (long long)gn * sbn] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < TG_BK; ++kk) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(&As[kk][ty * 4]);
+            const f32x4 b = *reinterpret_cast<const f32x4 *>(&Bs[kk][tx * 4]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void train_gemm_splitk_kernel(const float *__restrict__ A, long long sam, long long sak,
+                                                                const float *__restrict__ B, long long sbk, long long sbn,
+                                                                float *__restrict__ part, int M, int N, int K, int kc, int a_kfast,
+                                                                int b_nfast) {
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int m0 = blockIdx.y * TG_BM, n0 = blockIdx.x * TG_BN;
+    const long long k_lo = (long long)blockIdx.z * kc;
+    const int k_hi = (int)(k_lo + kc < K ? k_lo + kc : K);
+    float acc[4][4];
+    tg_accumulate(A, sam, sak, B, sbk, sbn, M, N, (int)k_lo, k_hi, a_kfast, b_nfast, acc);
+    float *out = part + (long long)blockIdx.z * M * N;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int gm = m0 + ty * 4 + i;
+        if (gm >= M) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int gn = n0 + tx * 4 + j;
+            if (gn < N) out[(long long)gm * N + gn] = acc[i][j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void train_gemm_combine_kernel(const float *__restrict__ part, int n_split, float *C, long long ldc, int M,
+                                                                 int N, int accumulate, const float *__restrict__ bias) {
+    const long long mn = (long long)M * N, e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= mn) return;
+    const int gm = (int)(e / N), gn = (int)(e % N);
+    float v = part[e];
+    for (int s = 1; s < n_split; ++s) v += part[s * mn + e];
+    if (bias) v += bias[gn];
+    float *c = C + (long long)gm * ldc + gn;
+    if (accumulate) v += *c;
+    *c = v;
+}
+
+extern "C" int jlm_train_gemm_splitk(const float *A, long long sam, long long sak, const float *B, long long sbk, long long sbn, float *C,
+                                     int ldc, int M, int N, int K, int accumulate, const float *bias, int kc, float *part,
+                                     long long part_elems, void *stream) {
+    if (!A || !B || !C || !part || M < 1 || N < 1 || K < 1 || ldc < N || sam < 1 || sak < 1 || sbk < 1 || sbn < 1) return -1;
+    if (kc < TG_BK || kc % TG_BK) return -1;
+    const long long gy = (M + TG_BM - 1) / TG_BM, gx = (N + TG_BN - 1) / TG_BN, gz = ((long long)K + kc - 1) / kc, mn = (long long)M * N;
+    if (gy > 65535 || gz > 65535 || gx > 2147483647ll || part_elems < gz * mn || (mn + 255) / 256 > 2147483647ll) return -1;
+    hipLaunchKernelGGL(train_gemm_splitk_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(256), 0, (hipStream_t)stream, A, sam,
+                       sak, B, sbk, sbn, part, M, N, K, kc, sak == 1 ? 1 : 0, sbn == 1 ? 1 : 0);
+    JLM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(train_gemm_combine_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, (hipStream_t)stream, part, (int)gz, C,
+                       (long long)ldc, M, N, accumulate, bias);
     JLM_LAUNCH_CHECK();
     return 0;
 }
@@ -527,6 +629,113 @@ extern "C" int jlm_train_adam(float *w, const float *g, float *m, float *v, long
     long long grid = (n4 + 255) / 256;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, n4, lr_t, flag);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------- dynamic evaluation
+// (jlm_amd/dyneval.py).  All three walk the flat parameter buffer as adam_kernel does: 16-byte accesses, grid-stride.
+__global__ __launch_bounds__(256) void dyneval_sqacc_kernel(float *__restrict__ ms, const float *__restrict__ g, long long n4,
+                                                            const int *__restrict__ flag) {
+    if (flag && flag[0]) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        f32x4 mm = reinterpret_cast<f32x4 *>(ms)[i];
+        const f32x4 gg = reinterpret_cast<const f32x4 *>(g)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mm[k] = fmaf(gg[k], gg[k], mm[k]);
+        reinterpret_cast<f32x4 *>(ms)[i] = mm;
+    }
+}
+
+static long long flat_grid(long long n4) {
+    const long long grid = (n4 + 255) / 256;
+    return grid > JLM_DYNEVAL_MAX_BLOCKS ? JLM_DYNEVAL_MAX_BLOCKS : grid;
+}
+
+extern "C" int jlm_dyneval_sqacc(float *ms, const float *g, long long n, const int *flag, void *stream) {
+    if (!ms || !g || n < 4 || (n & 3) || ((uintptr_t)ms | (uintptr_t)g) & 15) return -1;
+    hipLaunchKernelGGL(dyneval_sqacc_kernel, dim3((unsigned)flat_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, ms, g, n / 4, flag);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// rms = sqrtf(ms inv_chunks), and the f64 sum of those f32 values in a fixed order: a lane adds its elements in the order it meets
+// them, the block's 256 lane sums meet in an LDS tree (stride 128, 64, ..., 1), lane 0 writes partial[block].
+__global__ __launch_bounds__(256) void dyneval_rms_kernel(const float *__restrict__ ms, long long n4, float inv_chunks,
+                                                          float *__restrict__ rms, double *__restrict__ partial) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const f32x4 mm = reinterpret_cast<const f32x4 *>(ms)[i];
+        f32x4 rr;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            rr[k] = sqrtf(mm[k] * inv_chunks);
+            s += (double)rr[k];
+        }
+        reinterpret_cast<f32x4 *>(rms)[i] = rr;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// one workgroup: the blocks' sums in index order -> the mean over the n_real parameters (the padding words hold 0 and add nothing)
+__global__ __launch_bounds__(64) void dyneval_mean_kernel(const double *__restrict__ partial, int n_partial, long long n_real,
+                                                          double *__restrict__ mean_out) {
+    if (threadIdx.x) return;
+    double s = 0.0;
+    for (int b = 0; b < n_partial; ++b) s += partial[b];
+    mean_out[0] = s / (double)n_real;
+}
+
+extern "C" int jlm_dyneval_rms(const float *ms, long long n, float inv_chunks, float *rms, long long n_real, double *partial,
+                               double *mean_out, void *stream) {
+    if (!ms || !rms || !partial || !mean_out || n < 4 || (n & 3) || n_real < 1 || n_real > n || !(inv_chunks > 0.0f) ||
+        ((uintptr_t)ms | (uintptr_t)rms) & 15)
+        return -1;
+    const long long grid = flat_grid(n / 4);
+    hipLaunchKernelGGL(dyneval_rms_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, ms, n / 4, inv_chunks, rms, partial);
+    JLM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dyneval_mean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, (int)grid, n_real, mean_out);
+    JLM_LAUNCH_CHECK();
+    return 0;
+}
+
+// The decay-to-prior update.  Per element the float64 stepper's expression is evaluated in f64, in its order, and rounded to f32 once:
+//   r = rms ? rms[i] : 1;  step = lr g, with rms step = lr g / (r + eps);  c = min(lam_scale r, 1)
+//   w = (float)(((double)w - step) + c ((double)w0 - (double)w))
+// lam_scale is lambda under the sgd rule and lambda / mean(RMS) under the rms rule.  A padding word (w = g = w0 = rms = 0) stays 0.
+// The pass moves 16 or 20 bytes per element, so the f64 arithmetic (one division under the rms rule) hides behind the memory traffic.
+__global__ __launch_bounds__(256) void dyneval_update_kernel(float *__restrict__ w, const float *__restrict__ g, const float *__restrict__ w0,
+                                                             const float *__restrict__ rms, long long n4, double lr, double lam_scale,
+                                                             double eps, const int *__restrict__ flag) {
+    if (flag && flag[0]) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        f32x4 ww = reinterpret_cast<f32x4 *>(w)[i];
+        const f32x4 gg = reinterpret_cast<const f32x4 *>(g)[i], w00 = reinterpret_cast<const f32x4 *>(w0)[i];
+        f32x4 rr = {1.0f, 1.0f, 1.0f, 1.0f};
+        if (rms) rr = reinterpret_cast<const f32x4 *>(rms)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double wk = (double)ww[k], r = (double)rr[k];
+            double step = lr * (double)gg[k];
+            if (rms) step = step / (r + eps);
+            ww[k] = (float)((wk - step) + fmin(lam_scale * r, 1.0) * ((double)w00[k] - wk));
+        }
+        reinterpret_cast<f32x4 *>(w)[i] = ww;
+    }
+}
+
+extern "C" int jlm_dyneval_update(float *w, const float *g, const float *w0, const float *rms, long long n, double lr, double lam_scale,
+                                  double eps, const int *flag, void *stream) {
+    if (!w || !g || !w0 || n < 4 || (n & 3) || ((uintptr_t)w | (uintptr_t)g | (uintptr_t)w0 | (uintptr_t)rms) & 15) return -1;
+    hipLaunchKernelGGL(dyneval_update_kernel, dim3((unsigned)flat_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, w, g, w0, rms, n / 4, lr,
+                       lam_scale, eps, flag);
     JLM_LAUNCH_CHECK();
     return 0;
 }

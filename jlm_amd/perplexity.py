@@ -23,6 +23,11 @@ after every line; a character model (config char_rnn) reads the characters of th
                    FILE, the dev set, prints the grid's best pair and reports the test perplexity at that pair.  Without --cache the
                    output is what it was.  With --ranks as well (N <= 4096), a second --ranks line "with cache" over the same tokens,
                    at the theta and lam the cached perplexity is reported at (LSTM_Model.rank_streams_cached).
+  --dynamic        stream mode: after the static line, the dynamically evaluated perplexity (jlm_amd/dyneval.py): the stream read in
+                   chunks of -b (default 1) x --de-steps tokens, each scored and then learnt from by --de-rule at --de-lr and --de-lam.
+                   Rule rms takes its gradient statistics over --de-stat-chunks chunks of data/train.txt.  --tune-dynamic FILE sweeps
+                   --de-lrs x --de-lams on FILE, the dev set, and reports the test perplexity at the best pair.  Not with --cache,
+                   --ranks or --mode sentence.  Without --dynamic the output is what it was.
 """
 import argparse
 import os
@@ -155,7 +160,9 @@ def ranks_line(ranks, targets, index, tops, list_size):
     return "  ".join(parts)
 
 
-def main(argv=None):
+def main(argv=None, de_stepper=None):
+    """``de_stepper``: the ``stepper`` of ``jlm_amd.dyneval.dynamic_perplexity`` for the --dynamic figures (tests: "reference", the
+    float64 stepper, which also gives the static line, from a pass at zero rates, so that nothing needs the device)"""
     ap = argparse.ArgumentParser(description="Test perplexity of a dumped model on the device (reference train/train.py:101-102)")
     _config.add_model_args(ap)
     ap.add_argument("--file", default=None, help="text to score, one sentence per line (default: <root>/data/test.txt)")
@@ -174,7 +181,43 @@ def main(argv=None):
                     help="--cache: sweep --thetas x --lams on FILE (the dev set) and report the test perplexity at the best pair")
     ap.add_argument("--thetas", default=",".join("%.1f" % (0.1 * i) for i in range(11)), help="--tune-cache: the thetas of the grid")
     ap.add_argument("--lams", default=",".join("%.2f" % (0.05 * i) for i in range(20)), help="--tune-cache: the lams of the grid")
+    ap.add_argument("--dynamic", action="store_true",
+                    help="stream mode: also report the dynamically evaluated perplexity -- one gradient step per chunk (jlm_amd/dyneval.py)")
+    ap.add_argument("--de-rule", choices=("sgd", "rms"), default="sgd", dest="de_rule", help="--dynamic: the update rule")
+    ap.add_argument("--de-lr", type=float, default=0.005, dest="de_lr", help="--dynamic: the learning rate")
+    ap.add_argument("--de-lam", type=float, default=0.02, dest="de_lam", help="--dynamic: the decay towards the loaded weights, in [0, 1)")
+    ap.add_argument("--de-eps", type=float, default=1e-3, dest="de_eps", help="--dynamic, rule rms: what is added to RMS")
+    ap.add_argument("--de-steps", type=int, default=5, dest="de_steps", help="--dynamic: tokens per chunk, i.e. per update")
+    ap.add_argument("--de-stat-chunks", type=int, default=500, dest="de_stat_chunks",
+                    help="--dynamic, rule rms: chunks of data/train.txt the gradient statistics are taken over")
+    ap.add_argument("--tune-dynamic", default=None, metavar="FILE", dest="tune_dynamic",
+                    help="--dynamic: sweep --de-lrs x --de-lams on FILE (the dev set) and report the test perplexity at the best pair")
+    ap.add_argument("--de-lrs", default="0.001,0.002,0.005,0.01,0.02", dest="de_lrs", help="--tune-dynamic: the learning rates of the grid")
+    ap.add_argument("--de-lams", default="0,0.01,0.02,0.05", dest="de_lams", help="--tune-dynamic: the decays of the grid")
     args = ap.parse_args(argv)
+    if args.tune_dynamic and not args.dynamic:
+        ap.error("--tune-dynamic goes with --dynamic")
+    de_spec = de_grid = None
+    if args.dynamic:
+        from . import dyneval as _de
+        if args.mode != "stream" or args.cache or args.tune_cache or args.ranks:
+            ap.error("--dynamic works in stream mode, without --cache and --ranks")
+        if args.comp:
+            ap.error("--dynamic runs on the uncompressed weights")
+        try:
+            de_spec = _de.DynEvalSpec(args.de_lr, args.de_lam, args.de_rule, args.de_eps, args.batch_size or 1, args.de_steps)
+            _de.check_spec(de_spec, stats={} if args.de_rule == "rms" else None)
+            if args.de_rule == "rms" and args.de_stat_chunks < 1:
+                ap.error("--de-stat-chunks takes an integer >= 1")
+            if args.tune_dynamic:
+                de_grid = (_floats(args.de_lrs, "--de-lrs", ap), _floats(args.de_lams, "--de-lams", ap))
+                if not de_grid[0] or not de_grid[1]:
+                    ap.error("--de-lrs or --de-lams is empty")
+                for lr in de_grid[0]:
+                    for lam in de_grid[1]:
+                        _de.check_spec(de_spec.replace(lr=lr, lam=lam), stats={} if args.de_rule == "rms" else None)
+        except ValueError as e:
+            ap.error(str(e))
     spec = tune_spec = None
     if args.cache or args.tune_cache:
         from .cache import CacheSpec, check_lam
@@ -198,14 +241,17 @@ def main(argv=None):
     from .model import LSTM_Model
     path = args.file or os.path.join(_config.data_path, "test.txt")
     sents, n_unk = encode_lines(read_lines(path, args.es), vocab)
-    model = LSTM_Model(experiment_id=args.experiment_id, comp=args.comp)
+    model = None if de_stepper == "reference" else LSTM_Model(experiment_id=args.experiment_id, comp=args.comp)
     t0 = time.time()
     if args.mode == "sentence":
         pp, _total, n_tok = sentence_perplexity(model, sents, vocab.t2i["<eos>"])
     else:
-        bs = args.batch_size or int(config.get("batch_size", 64))
+        bs = args.batch_size or (1 if args.dynamic else int(config.get("batch_size", 64)))
         stream = [i for s in sents for i in s]
-        if spec is None:
+        if model is None:
+            pp, _total, n_tok = _de.dynamic_perplexity(args.experiment_id, stream, _de.DynEvalSpec(0.0, batch_size=bs, num_steps=args.num_steps),
+                                                       stepper=de_stepper)
+        elif spec is None:
             pp, _total, n_tok = stream_perplexity(model, stream, bs, args.num_steps)
         else:
             if tune_spec is not None:
@@ -225,6 +271,24 @@ def main(argv=None):
             args.tune_cache, spec.theta, spec.lam, dev_pp[0], dev_pp[1], len(tune_spec.thetas), len(tune_lams)))
     if spec is not None:
         print("Test perplexity with cache (N {} theta {} lam {}): {}".format(spec.size, spec.theta, spec.lam, cached_pp))
+    if de_spec is not None:
+        stats = None
+        if de_spec.rule == "rms":
+            train_sents, _n = encode_lines(read_lines(os.path.join(_config.data_path, "train.txt")), vocab)
+            stats = _de.experiment_stats(args.experiment_id, [i for s in train_sents for i in s], args.de_stat_chunks, bs, args.de_steps,
+                                         stepper=de_stepper)
+        if de_grid is not None:
+            dev_sents, _n = encode_lines(read_lines(args.tune_dynamic), vocab)
+            grid, (best_lr, best_lam) = _de.tune(args.experiment_id, [i for s in dev_sents for i in s], de_grid[0], de_grid[1], de_spec.rule,
+                                                 de_spec.eps, bs, args.de_steps, stats=stats, stepper=de_stepper)
+            de_spec = de_spec.replace(lr=best_lr, lam=best_lam)
+            print("Dynamic evaluation tuned on {}: lr {} lam {}  (dev perplexity {} over {} x {} pairs)".format(
+                args.tune_dynamic, best_lr, best_lam, float(grid.min()), grid.shape[0], grid.shape[1]))
+        t0 = time.time()
+        de_pp, _total, de_tok = _de.dynamic_perplexity(args.experiment_id, stream, de_spec, stats=stats, stepper=de_stepper)
+        dt = time.time() - t0
+        print("Test perplexity with dynamic evaluation (rule {} lr {} lam {} chunks of {} x {}; {} tokens, {:.0f} tokens/s): {}".format(
+            de_spec.rule, de_spec.lr, de_spec.lam, bs, args.de_steps, de_tok, de_tok / dt if dt > 0 else float("inf"), de_pp))
     if args.ranks:
         readings = not isinstance(vocab, CharVocab)
         if args.mode == "sentence":

@@ -573,6 +573,10 @@ class DeviceStepper(_StepperBase):
         self.ops.train_adam(self.W, self.G, self.M, self.Vv, self.n_flat, adam_lr_t(self.lr, self.t), self.flag)
         self._mark("adam")
 
+    def _gemm(self, *args):
+        """every contraction of a step (a subclass routes some of them to another launch form: jlm_amd/dyneval.py)"""
+        self.ops.train_gemm(*args)
+
     # ---- the embedding's forms
     def _assemble_embedding(self):
         d, O, E = self.d, self.ops, self.d["E"]
@@ -581,7 +585,7 @@ class DeviceStepper(_StepperBase):
                 if i == 0:
                     self.emb[s:e].copy_(self.p[("LM0", None)])
                 else:
-                    O.train_gemm(self.p[("LM%d" % i, None)], size, 1, self.p[("VT%d" % i, None)], E, 1, self.emb[s:e], E, e - s, E, size, False,
+                    self._gemm(self.p[("LM%d" % i, None)], size, 1, self.p[("VT%d" % i, None)], E, 1, self.emb[s:e], E, e - s, E, size, False,
                                  None)
         elif d["kind"] == "dsoftmax":
             c0 = 0
@@ -613,7 +617,7 @@ class DeviceStepper(_StepperBase):
         for si, a, n in pieces:
             s, _e, k, blk, _kind, _c0, _vt = self.segs[si]
             Q, ldq, _dq = self._q(si)
-            self.ops.train_gemm(Q, ldq, 1, self.p[blk][a - s:a - s + n], 1, k, self.Y[:, a - v0:], self.Vc, N, n, k, False,
+            self._gemm(Q, ldq, 1, self.p[blk][a - s:a - s + n], 1, k, self.Y[:, a - v0:], self.Vc, N, n, k, False,
                                 self.p[("b2", None)][a:a + n])
 
     def _vocabulary_loss(self, train, ids_d, tgt_d):
@@ -644,11 +648,11 @@ class DeviceStepper(_StepperBase):
             s0, e0, k, blk, kind, _c0, vt = self.segs[si]
             Q, ldq, dQ = self._q(si)
             dy = self.Y[:, a - v0:]
-            O.train_gemm(dy, 1, Vc, Q, ldq, 1, g[blk][a - s0:a - s0 + m], k, m, k, N, False, None)      # dBlock = dy^T Q (TN)
-            O.train_gemm(dy, Vc, 1, p[blk][a - s0:a - s0 + m], k, 1, dQ, ldq, N, k, m, a > s0, None)    # dQ (+)= dy Block (NN)
+            self._gemm(dy, 1, Vc, Q, ldq, 1, g[blk][a - s0:a - s0 + m], k, m, k, N, False, None)      # dBlock = dy^T Q (TN)
+            self._gemm(dy, Vc, 1, p[blk][a - s0:a - s0 + m], k, 1, dQ, ldq, N, k, m, a > s0, None)    # dQ (+)= dy Block (NN)
             if kind == "factored" and a + m == e0:
-                O.train_gemm(dQ, 1, k, self.P, E, 1, g[vt], E, k, E, N, False, None)                   # dVT_i = dQ_i^T P (TN)
-                O.train_gemm(dQ, k, 1, p[vt], E, 1, self.dP, E, N, E, k, True, None)                   # dP += dQ_i VT_i (NN)
+                self._gemm(dQ, 1, k, self.P, E, 1, g[vt], E, k, E, N, False, None)                   # dVT_i = dQ_i^T P (TN)
+                self._gemm(dQ, k, 1, p[vt], E, 1, self.dP, E, N, E, k, True, None)                   # dP += dQ_i VT_i (NN)
 
     def step_async(self, x, y, train=True):
         torch, O, d, B, T = self.torch, self.ops, self.d, self.B, self.T
@@ -668,23 +672,23 @@ class DeviceStepper(_StepperBase):
             self._mark("start")
             self._assemble_embedding()
             O.train_embed_rows(self.emb, E, V, ids_d, N, E, self.X, key_in, thr, scale)
-            O.train_gemm(self.X, E, 1, IM, 4 * H, 1, self.Z, 4 * H, N, 4 * H, E, False, p[("b", None)])
+            self._gemm(self.X, E, 1, IM, 4 * H, 1, self.Z, 4 * H, N, 4 * H, E, False, p[("b", None)])
             self._mark("inputs")
             for t in range(T):
                 rows, nxt = slice(t * B, (t + 1) * B), slice((t + 1) * B, (t + 2) * B)
-                O.train_gemm(self.Hs[rows], H, 1, HM, 4 * H, 1, self.Z[rows], 4 * H, B, 4 * H, H, True, None)
+                self._gemm(self.Hs[rows], H, 1, HM, 4 * H, 1, self.Z[rows], 4 * H, B, 4 * H, H, True, None)
                 O.train_cell_fwd(self.Z[rows], self.Cs[rows], self.Cs[nxt], self.Hs[nxt], self.R[rows], B, H, t * B, key_out, thr, scale)
             self._mark("lstm_forward")
-            O.train_gemm(self.R, H, 1, p[("PM", None)], E, 1, self.P, E, N, E, H, False, None)
+            self._gemm(self.R, H, 1, p[("PM", None)], E, 1, self.P, E, N, E, H, False, None)
             for si, sg in enumerate(self.segs):
                 if sg[4] == "factored":                                                                            # Q_i = P VT_i^T (NT)
-                    O.train_gemm(self.P, E, 1, p[sg[6]], 1, E, self.Q[si], sg[2], N, sg[2], E, False, None)
+                    self._gemm(self.P, E, 1, p[sg[6]], 1, E, self.Q[si], sg[2], N, sg[2], E, False, None)
             self._vocabulary_loss(train, ids_d, tgt_d)
             self.n_ce += 1
             self._mark("vocabulary")
             if train:
-                O.train_gemm(self.R, 1, H, self.dP, E, 1, g[("PM", None)], E, H, E, N, False, None)                # dPM = R^T dP (TN)
-                O.train_gemm(self.dP, E, 1, p[("PM", None)], 1, E, self.dR, H, N, H, E, False, None)              # dr = dP PM^T (NT)
+                self._gemm(self.R, 1, H, self.dP, E, 1, g[("PM", None)], E, H, E, N, False, None)                # dPM = R^T dP (TN)
+                self._gemm(self.dP, E, 1, p[("PM", None)], 1, E, self.dR, H, N, H, E, False, None)              # dr = dP PM^T (NT)
                 self.dc.zero_()
                 self._mark("projection_backward")
                 for t in range(T - 1, -1, -1):
@@ -692,12 +696,12 @@ class DeviceStepper(_StepperBase):
                     O.train_cell_bwd(self.Z[rows], self.Cs[nxt], self.Cs[rows], self.dR[rows], self.dh if t < T - 1 else None, self.dc,
                                      self.dZ[rows], B, H, t * B, key_out, thr, scale)
                     if t:
-                        O.train_gemm(self.dZ[rows], 4 * H, 1, HM, 1, 4 * H, self.dh, H, B, H, 4 * H, False, None)  # dh_prev = dz HM^T (NT)
+                        self._gemm(self.dZ[rows], 4 * H, 1, HM, 1, 4 * H, self.dh, H, B, H, 4 * H, False, None)  # dh_prev = dz HM^T (NT)
                 self._mark("lstm_backward")
-                O.train_gemm(self.Hs, 1, H, self.dZ, 4 * H, 1, g[("HM", None)], 4 * H, H, 4 * H, N, False, None)   # dHM = h_prev^T dz (TN)
-                O.train_gemm(self.X, 1, E, self.dZ, 4 * H, 1, g[("IM", None)], 4 * H, E, 4 * H, N, False, None)    # dIM = x^T dz (TN)
+                self._gemm(self.Hs, 1, H, self.dZ, 4 * H, 1, g[("HM", None)], 4 * H, H, 4 * H, N, False, None)   # dHM = h_prev^T dz (TN)
+                self._gemm(self.X, 1, E, self.dZ, 4 * H, 1, g[("IM", None)], 4 * H, E, 4 * H, N, False, None)    # dIM = x^T dz (TN)
                 O.train_colsum(self.dZ, 4 * H, N, 4 * H, g[("b", None)], False)
-                O.train_gemm(self.dZ, 4 * H, 1, IM, 1, 4 * H, self.dX, E, N, E, 4 * H, False, None)               # dx = dz IM^T (NT)
+                self._gemm(self.dZ, 4 * H, 1, IM, 1, 4 * H, self.dX, E, N, E, 4 * H, False, None)               # dx = dz IM^T (NT)
                 ids_sorted, perm = torch.sort(ids_d, stable=True)
                 for si, (s0, e0, k, blk, kind, c0, vt) in enumerate(self.segs):
                     if kind != "factored":           # dBlock[w] += the rows that read word w (their columns of this block)
@@ -706,8 +710,8 @@ class DeviceStepper(_StepperBase):
                         D = self.D[si]
                         D.zero_()
                         O.train_scatter_rows(self.dX, E, 0, E, E, ids_sorted, perm, N, D, E, s0, e0, key_in, thr, scale)
-                        O.train_gemm(D, E, 1, p[vt], 1, E, g[blk], k, e0 - s0, k, E, True, None)
-                        O.train_gemm(p[blk], 1, k, D, E, 1, g[vt], E, k, E, e0 - s0, True, None)
+                        self._gemm(D, E, 1, p[vt], 1, E, g[blk], k, e0 - s0, k, E, True, None)
+                        self._gemm(p[blk], 1, k, D, E, 1, g[vt], E, k, E, e0 - s0, True, None)
                 self._mark("weight_gradients")
                 self._update()
             self.Hs[:B].copy_(self.Hs[T * B:])
