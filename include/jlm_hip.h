@@ -643,6 +643,7 @@ typedef struct {
 } jlm_decode_model;
 
 struct jlm_decode_cache;
+struct jlm_decode_ngram;
 typedef struct {
     int kind;                       /* 0 static, full vocabulary; 1 static, selected vocabulary; 2 incremental */
     int max_cands;
@@ -680,6 +681,9 @@ typedef struct {
     /* The continuous cache inside the frame loop (additive, ABI 12; NULL: the loop is what it was, launch for launch).  Kind 0 only:
      * see jlm_decode_cache below. */
     const struct jlm_decode_cache *cache;
+    /* A back-off n-gram model mixed into every edge cost (additive, ABI 12; NULL: the loop is what it was, launch for launch).  Kind 0
+     * only, and not together with `cache` (-1): see jlm_decode_ngram below. */
+    const struct jlm_decode_ngram *ngram;
 } jlm_decode_plan;
 
 /* Returns 0 or a hipError_t.  st_host->lse_part / n_parts are managed by the call.  A full-vocabulary
@@ -1225,6 +1229,54 @@ int jlm_cache_cell_patch(float *s, int ld_s, const int *words, const int *count,
                          const int *cnt, const int *sent_len, int frame, int n_sent, int beam, const int *wl, const int *wl_off,
                          const int *wl_idx, int wl_base, const int *wl_out, float *edge, const float *part, int ld_part, int n_parts,
                          const int *live_base, double *lse, int *flags, void *stream);
+
+/* ------------------------------------------------------------------------
+ * A back-off word n-gram model mixed into a decode (Decoder.decode(ngram=); ABI 12, additive).
+ *
+ * Table: tuples of 1 .. order word ids, order 1, 2 or 3, -> (lp, bow): lp the natural log of the conditional probability of the
+ * tuple's last word, bow the natural log of the back-off weight of the tuple as a context (0 where the file gives none); both the
+ * float32 nearest to ln 10 x the file's number, everything after that float64.  Word ids <= 2^21 - 2, lp <= 0, both finite: the
+ * host refuses anything else when it builds the table (jlm_amd/ngram.py), so the kernel has no flag for it.
+ * For a history h = (.., u, v) and a word w, with k = min(order - 1, len(h)) history words in use:
+ *     q(w | h_k) = lp(h_k, w)                                 if (h_k, w) is in the table
+ *                = -inf                                       else if k = 0   (a word without a unigram: p_ng = 0)
+ *                = bow(h_k) [0 if absent] + q(w | h_{k-1})    else            (h_{k-1} drops the oldest word)
+ * -- ARPA back-off with the weights applied.  The history of a hypothesis is [<eos>] + context + the path's words so far: a decode
+ * without context starts from (<eos>) alone, its first word is predicted from the bigram (<eos>, w), never from a padded trigram.
+ * For hypothesis row r with full-vocabulary log-normaliser L (self-normalised models: 0) and every lattice word w leaving its cell,
+ * with logit y:
+ *     p_r(w) = (1 - lam) exp(y - L) + lam exp(q(w | hist_r)),     0 < lam < 1, one lam a call
+ *     edge'  = L + log(1 - lam) + logaddexp(y - L, log(lam / (1 - lam)) + q)      q finite
+ *     edge'  = y + log(1 - lam)                                                  q = -inf
+ * formed in f64 and rounded once to the f32 the buffer holds.  Word ids are only compared; the raw-kana fallback is id 0 and mixes
+ * like any other word.
+ *
+ * The table on the device: keys [2^log2cap] 64-bit, vals [2^log2cap][2] float32 (lp, bow).  key = (w + 1) | (v + 1) << 21 |
+ * (u + 1) << 42 with the predicted word lowest and absent positions 0 -- key 0 is an empty slot; home slot
+ * (key * 0x9E3779B97F4A7C15) >> (64 - log2cap), linear probing; max_probe the longest displacement in use.  A probe stops on the
+ * key, on 0, or after max_probe + 1 slots.  root_hist [n_sent][2]: the last two words of [<eos>] + context of every sentence of the
+ * batch, -1 for "no word". */
+typedef struct jlm_decode_ngram {
+    const void *keys; const float *vals; int log2cap, max_probe, order; float lam;
+    const int *root_hist;           /* [n_sent][2] device */
+} jlm_decode_ngram;
+
+/* ngram_cell_patch_kernel (csrc/jlm_ngram_edge.hip): one workgroup per sentence j of the frame (skipped when frame >= sent_len[j] or
+ * cnt[j] = 0).  part != NULL: the cell's normaliser slices are first folded into lse[j * beam + k] exactly as jlm_cache_cell_patch
+ * folds them (jlm_beam_step's fused fold: order, arithmetic, sanitising -- flag bit 1, the value 1e30), so that the next
+ * jlm_beam_step runs unfused; part == NULL: L = 0, lse is not touched.  Slot k < min(cnt[j], beam) is row g = g0[j] + k of the
+ * pools bp / word / score (jlm_beam_state's, whole): its newest word is word[g], the one before word[bp[g]]; where the walk reaches
+ * a root (bp = -1) the words come from root_hist[j] -- a root row's own word is never read.  Per position of the cell's word list
+ * wl[wl_off[l] .. wl_off[l + 1]), l = wl_base + wl_idx[j] (jlm_edge_logits' lists) and slot k: edge[wl_out * beam + k] <- edge'.
+ * One writer per address.  A slot whose score[g] is not finite (score may be NULL: not looked at) keeps its edge logits and ORs 8
+ * into *flags.  lse: the frame's first entry.
+ * Returns 0, -1 before any launch (order outside 1 .. 3, log2cap outside 6 .. 31, max_probe >= 2^log2cap, lam outside (0, 1), beam
+ * outside [1, JLM_MAX_BEAM], a null or misaligned pointer, part without live_base / lse / n_parts >= 1), or a hipError_t. */
+int jlm_ngram_cell_patch(const void *keys, const float *vals, int log2cap, int max_probe, int order, float lam, const int *g0,
+                         const int *cnt, const int *sent_len, int frame, int n_sent, int beam, const int *bp, const int *word,
+                         const double *score, const int *root_hist, const int *wl, const int *wl_off, const int *wl_idx, int wl_base,
+                         const int *wl_out, float *edge, const float *part, int ld_part, int n_parts, const int *live_base, double *lse,
+                         int *flags, void *stream);
 
 /* jlm_prime_frames that keeps its states: behind the step of frame f >= n_steps - cap, the live prefix of the state set the step
  * wrote and target[f][0 .. n_live_host[f]) are copied into slot f - (n_steps - cap) of hist [cap][n_rows][H] / words [cap][n_rows]

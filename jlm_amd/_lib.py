@@ -60,7 +60,7 @@ class DecodePlan(Structure):
                 ("run_max", c_void_p), ("run_sum", c_void_p), ("part", c_void_p), ("max_parts", c_int), ("lse_cu_share_pct", c_int),
                 ("out_nodes", c_void_p), ("out_len", c_void_p), ("out_score", c_void_p), ("stride", c_int),
                 ("di_wwords", c_void_p), ("sg_wword", c_void_p), ("Tm", c_void_p), ("ld_tm", c_int),
-                ("ctx_prev", c_void_p), ("ctx_word", c_void_p), ("cache", c_void_p)]
+                ("ctx_prev", c_void_p), ("ctx_word", c_void_p), ("cache", c_void_p), ("ngram", c_void_p)]
 
 
 
@@ -202,6 +202,8 @@ _SIGS = {
     "jlm_cache_cell_query": ([P, c_int, c_int, c_float, P, P, P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, c_float, P, c_int, P, P],
                              c_int),
     "jlm_cache_cell_patch": ([P, c_int, P, P, c_int, c_int, P, c_int, c_float, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int,
+                              P, P, P, P], c_int),
+    "jlm_ngram_cell_patch": ([P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, P, P, P, c_int, c_int,
                               P, P, P, P], c_int),
     "jlm_prime_cache_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P, P, P, c_int, P], c_int),
     "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,

@@ -34,13 +34,18 @@ class ContextState:
     """The primed state of n histories on the device of a :class:`jlm_amd.model.DeviceModel`; nothing in it is written after it is
     made.  ``h``, ``c`` [n, H]: the state after ``hist[:-1]``, h in the model's state-row format (split rows or f32: 4 bytes a value
     either way); ``last`` [n] int32: ``hist[-1]``, the word the root consumes; ``has`` [n] int32: 0 where the history is ``<eos>``
-    alone -- the row never stepped and the root starts from the zero state.  ``last_host`` / ``has_host``: their host copies."""
+    alone -- the row never stepped and the root starts from the zero state.  ``last_host`` / ``has_host``: their host copies.
+    ``tail_host`` [n, 2] int32 (keyword, optional): the last two words of every history, -1 for "no word" -- what a decode under an
+    n-gram mixture starts from (``prime`` records it); a state built without it counts as (-1, last_host)."""
 
-    def __init__(self, m, h, c, last, has, last_host, has_host):
+    def __init__(self, m, h, c, last, has, last_host, has_host, *, tail_host=None):
         self.m, self.h, self.c, self.last, self.has = m, h, c, last, has
         self.last_host = np.asarray(last_host, dtype=np.int32)
         self.has_host = np.asarray(has_host, dtype=np.int32)
         self.n = int(self.last_host.shape[0])
+        if tail_host is None:
+            tail_host = np.stack([np.full(self.n, -1, dtype=np.int32), self.last_host], axis=1)
+        self.tail_host = np.asarray(tail_host, dtype=np.int32).reshape(self.n, 2)
 
     def __len__(self):
         return self.n
@@ -70,8 +75,8 @@ class CachedContext(ContextState):
     entries are the slots cap - count[r] .. cap - 1, oldest first; the slots below hold nothing that is read.  ``spec``: the CacheSpec
     it was primed for (one theta).  Immutable and reusable like its base."""
 
-    def __init__(self, m, h, c, last, has, last_host, has_host, hist, words, count, count_host, spec):
-        super().__init__(m, h, c, last, has, last_host, has_host)
+    def __init__(self, m, h, c, last, has, last_host, has_host, hist, words, count, count_host, spec, *, tail_host=None):
+        super().__init__(m, h, c, last, has, last_host, has_host, tail_host=tail_host)
         self.hist, self.words, self.count, self.spec = hist, words, count, spec
         self.count_host = np.asarray(count_host, dtype=np.int32)
         self.cap = int(words.shape[0])
@@ -233,10 +238,13 @@ def prime(primer, contexts, max_rows=None, w2i=None, unk=0, checked=False, cache
             h.index_copy_(0, at, hc[:k])
             c.index_copy_(0, at, cc[:k])
         dev = lambda a: torch.from_numpy(a.copy()).to(m.device)
+        # the last two words of [<eos>] + ctx, -1 where the history is <eos> alone
+        tail = np.array([[(int(x[-2]) if len(x) >= 2 else EOS_ID) if len(x) else -1, int(x[-1]) if len(x) else EOS_ID] for x in ctxs],
+                        dtype=np.int32).reshape(n, 2)
         if not cap:
-            return ContextState(m, h, c, dev(last), dev(has), last, has)
+            return ContextState(m, h, c, dev(last), dev(has), last, has, tail_host=tail)
         count = np.minimum([len(x) for x in ctxs], cap).astype(np.int32)
-        return CachedContext(m, h, c, dev(last), dev(has), last, has, hist, words, dev(count), count, cache)
+        return CachedContext(m, h, c, dev(last), dev(has), last, has, hist, words, dev(count), count, cache, tail_host=tail)
 
 
 # What a host-side search takes of one input's left context: the primed state read back (h, c [1, H]: from where the root steps), the
@@ -279,6 +287,10 @@ class DecodeContext:
                 np.add.at(c[q], words, e[q] / e[q].sum())
             return (1.0 - spec.lam) * pred + spec.lam * c
         return mix
+
+    def tail(self, i):
+        """the last words (at most two) of input i's history [<eos>] + context"""
+        return [int(x) for x in self.state.tail_host[self.rows[i]] if x >= 0]
 
     def sub(self, keep):
         return DecodeContext(self.state, [self.rows[i] for i in keep])

@@ -49,6 +49,12 @@ int jlm_cache_cell_patch_refuse(const float *s, int ld_s, const int *words, cons
                                 float lam, const int *cnt, const int *sent_len, int frame, int n_sent, int beam, const int *wl,
                                 const int *wl_off, const int *wl_idx, int wl_base, const int *wl_out, const float *edge, const float *part,
                                 int ld_part, int n_parts, const int *live_base, const double *lse, const int *flags);
+// the refusals of jlm_ngram_cell_patch on their own (csrc/jlm_ngram_edge.hip)
+int jlm_ngram_cell_patch_refuse(const void *keys, const float *vals, int log2cap, int max_probe, int order, float lam, const int *g0,
+                                const int *cnt, const int *sent_len, int frame, int n_sent, int beam, const int *bp, const int *word,
+                                const double *score, const int *root_hist, const int *wl, const int *wl_off, const int *wl_idx, int wl_base,
+                                const int *wl_out, const float *edge, const float *part, int ld_part, int n_parts, const int *live_base,
+                                const double *lse, const int *flags);
 
 // ABI 11: the model's mixed segments are mx6 rows (FP6 cross-term planes, csrc/jlm_mx6_body.h) when their s8 is 0 -- the hypothesis
 // rows are then packed by jlm_pack_t_mixed6; a model mixes the two formats in no launch (jlm_vocab_lse_mixed: -2)
@@ -191,6 +197,17 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                                             m->self_norm ? nullptr : p->part, rmax, 1, st.live_base, st.lse, st.flags));
         side_s = nullptr;
     }
+    // A back-off n-gram model (jlm_decode_plan.ngram, kind 0): behind the normaliser and the edge logits of every frame, the rewrite of
+    // the edge logits leaving it (jlm_ngram_cell_patch), which folds the frame's normaliser slices as the cache's patch does.  Not beside
+    // the cache: a three-way mixture is not defined.  Every refusal comes here, before the first launch.
+    const jlm_decode_ngram *ng = p->ngram;
+    if (ng) {
+        if (cc || !full || !st.live_base || (!m->self_norm && (!p->part || p->max_parts < 1))) return -1;
+        JLM_TRY(jlm_ngram_cell_patch_refuse(ng->keys, ng->vals, ng->log2cap, ng->max_probe, ng->order, ng->lam, p->g0, st.cnt, lat->sent_len,
+                                            0, B, beam, st.bp, st.word, st.score, ng->root_hist, p->sg_word, p->sg_off, p->sidx, 0,
+                                            p->sg_node, p->edge, m->self_norm ? nullptr : p->part, rmax, 1, st.live_base, st.lse, st.flags));
+        side_s = nullptr;
+    }
 
     // word-list normaliser: the kernel jlm_wordlist_lse_form names (split rows for lists of 128 .. 4064 words)
     auto wl_lse = [&](const int *g0, const int *cidx, const int *words, const int *off, const int *idx, int base, int merge,
@@ -331,6 +348,13 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                                          lat->sent_len, f, B, beam, p->sg_word, p->sg_off, p->sidx, cell, p->sg_node, p->edge,
                                          pending_parts ? p->part : nullptr, rmax, pending_parts, st.live_base + cell,
                                          st.lse + (size_t)f * rmax, st.flags, stream));
+            pending_parts = 0;             // folded: the next beam step reads lse
+        }
+        if (ng) {
+            JLM_TRY(jlm_ngram_cell_patch(ng->keys, ng->vals, ng->log2cap, ng->max_probe, ng->order, ng->lam, p->g0 + cell, st.cnt + cell,
+                                         lat->sent_len, f, B, beam, st.bp, st.word, st.score, ng->root_hist, p->sg_word, p->sg_off, p->sidx,
+                                         cell, p->sg_node, p->edge, pending_parts ? p->part : nullptr, rmax, pending_parts,
+                                         st.live_base + cell, st.lse + (size_t)f * rmax, st.flags, stream));
             pending_parts = 0;             // folded: the next beam step reads lse
         }
     }

@@ -43,6 +43,8 @@
 //                             prime_frames that keeps the last cap frames' states and targets (jlm_prime_cache_frames; prime(cache=))
 //   torch.ops.jlm.seed_cache(Plan, hist, words, count, idx, s, cap, N, theta, lam)
 //                             the window of the plan's next frame loop: no launch (jlm_decode_plan.cache; Decoder.decode(cache=))
+//   torch.ops.jlm.seed_ngram(Plan, keys, vals, root_hist, log2cap, max_probe, order, lam) / clear_ngram(Plan)
+//                             the n-gram table of the plan's next frame loop: no launch (jlm_decode_plan.ngram; Decoder.decode(ngram=))
 //   torch.ops.jlm.tail_predict(Model, Plan, ids, sp_off, sp_frame, sp_lo, sp_hi, n_out, chunk, out_score, out_row, out_word, out_nodes,
 //                              out_len, stride)
 //                             predictions of an unfinished last word behind a plan's decode (jlm_tail_predict; Decoder.decode_predict)
@@ -236,6 +238,8 @@ struct JlmPlan : torch::CustomClassHolder {
     int ctx_H = 0;                          // a plan with a left context: the state rows' width (0: no such plan)
     jlm_decode_cache cache{};               // the next frame loop's window (seed_cache; p.cache points here or is NULL)
     std::vector<Tensor> cache_keep;         // ... and its tensors, kept until the next seed_cache
+    jlm_decode_ngram ngram{};               // the next frame loop's n-gram table (seed_ngram; p.ngram points here or is NULL)
+    std::vector<Tensor> ngram_keep;         // ... and its tensors, kept until the next seed_ngram
 
     JlmPlan(TDict t, IDict i) : tensors(std::move(t)) {
         const Tensor *ints = find(tensors, "ints");
@@ -339,6 +343,7 @@ int64_t decode_frames(const c10::intrusive_ptr<JlmModel> &model, const c10::intr
     //  per 256-sentence chunk, hipGraphLaunch of the 130-node two-branch graph cost more than the launches -- removed in round 5.)
     const int rc = jlm_decode_frames(&model->m, &pl.p, &pl.lat, &pl.st, main.stream(), side_s, ev);
     pl.p.cache = nullptr;                   // (seed_cache: the window of ONE frame loop)
+    pl.p.ngram = nullptr;                   // (seed_ngram: the table of ONE frame loop)
     if (rc == -2) return -2;
     jlm_check(rc, "jlm_decode_frames");
     return 0;
@@ -657,6 +662,34 @@ void seed_cache(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &hist, con
 void clear_cache(const c10::intrusive_ptr<JlmPlan> &plan) {
     plan->p.cache = nullptr;
     plan->cache_keep.clear();
+}
+
+// The n-gram table of the plan's NEXT frame loop (jlm_decode_plan.ngram): no launch, the plan keeps the tensors.  keys [2^log2cap] int64
+// (the table's 64-bit keys, bit for bit), vals [2^log2cap][2] float32, root_hist [n_sent][2] int32 on the device.  The frame loop that
+// follows takes the struct and clears it: a later batch starts without a table.
+void seed_ngram(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &keys, const Tensor &vals, const Tensor &root_hist, int64_t log2cap,
+                int64_t max_probe, int64_t order, double lam) {
+    JlmPlan &pl = *plan;
+    TORCH_CHECK(log2cap >= 6 && log2cap <= 31 && max_probe >= 0 && max_probe < ((int64_t)1 << log2cap) && order >= 1 && order <= 3,
+                "jlm.seed_ngram: log2cap 6 .. 31, 0 <= max_probe < 2^log2cap, order 1 .. 3");
+    const int64_t cap = (int64_t)1 << log2cap;
+    TORCH_CHECK(is(keys, at::kLong, cap) && keys.numel() == cap && is(vals, at::kFloat, 2 * cap) && vals.numel() == 2 * cap &&
+                    is(root_hist, at::kInt, 2 * (int64_t)pl.lat.n_sent) && keys.is_cuda() && vals.is_cuda() && root_hist.is_cuda() &&
+                    keys.is_contiguous() && vals.is_contiguous() && root_hist.is_contiguous() &&
+                    keys.device().index() == pl.device && vals.device().index() == pl.device && root_hist.device().index() == pl.device,
+                "jlm.seed_ngram: int64 keys [2^log2cap], float32 vals [2^log2cap][2], int32 root_hist [n_sent][2] on the plan's device");
+    TORCH_CHECK(lam > 0.0 && lam < 1.0 && (float)lam > 0.0f && (float)lam < 1.0f, "jlm.seed_ngram: 0 < lam < 1");
+    pl.ngram_keep = {keys, vals, root_hist};
+    pl.ngram.keys = keys.data_ptr(); pl.ngram.vals = ptr<const float>(vals, "vals");
+    pl.ngram.log2cap = (int)log2cap; pl.ngram.max_probe = (int)max_probe; pl.ngram.order = (int)order; pl.ngram.lam = (float)lam;
+    pl.ngram.root_hist = ptr<const int>(root_hist, "root_hist");
+    pl.p.ngram = &pl.ngram;
+}
+
+// seed_ngram undone: a batch that failed between seed_ngram and its frame loop leaves no table behind on the plan
+void clear_ngram(const c10::intrusive_ptr<JlmPlan> &plan) {
+    plan->p.ngram = nullptr;
+    plan->ngram_keep.clear();
 }
 
 // The predictions of an unfinished last word behind a plan's static decode (jlm_tail_predict): one launch on the current stream, which
@@ -1565,6 +1598,9 @@ TORCH_LIBRARY(jlm, m) {
     m.def("seed_cache(__torch__.torch.classes.jlm.Plan plan, Tensor hist, Tensor words, Tensor count, Tensor idx, Tensor(a!) s, int cap, int N, "
           "float theta, float lam) -> ()", seed_cache);
     m.def("clear_cache(__torch__.torch.classes.jlm.Plan plan) -> ()", clear_cache);
+    m.def("seed_ngram(__torch__.torch.classes.jlm.Plan plan, Tensor keys, Tensor vals, Tensor root_hist, int log2cap, int max_probe, int order, "
+          "float lam) -> ()", seed_ngram);
+    m.def("clear_ngram(__torch__.torch.classes.jlm.Plan plan) -> ()", clear_ngram);
     m.def("tail_predict(__torch__.torch.classes.jlm.Model model, __torch__.torch.classes.jlm.Plan plan, Tensor ids, Tensor sp_off, "
           "Tensor sp_frame, Tensor sp_lo, Tensor sp_hi, int n_out, int chunk, Tensor(a!) out_score, Tensor(b!) out_row, Tensor(c!) out_word, "
           "Tensor(d!) out_nodes, Tensor(e!) out_len, int stride) -> ()", tail_predict);

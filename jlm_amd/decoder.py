@@ -223,9 +223,30 @@ class Decoder():
         if (cache is not None and check_decode_cache(cache).lam > 0.0) or (isinstance(state, CachedContext) and state.spec.lam > 0.0):
             raise ValueError("%s takes no continuous cache (DESIGN.md section 21: the static full-vocabulary Decoder.decode only)" % what)
 
+    def _check_ngram(self, ngram, context, cache, vocab_select):
+        """the ``ngram=`` of a decode, checked BEFORE the context is resolved (which primes word lists on the device): an NGramMix whose
+        ids lie below the model's V, without ``cache=`` / a CachedContext, ``vocab_select`` or ``compat_quirks``; ValueError otherwise"""
+        from .context import CachedContext, DecodeContext
+        from .ngram import check_mix
+        check_mix(ngram, len(self.w2i))
+        if isinstance(context, _Single):
+            context = context.context
+        state = context.state if isinstance(context, DecodeContext) else context
+        if cache is not None or isinstance(state, CachedContext):
+            raise ValueError("ngram= and the continuous cache in one decode: a three-way mixture is not defined (DESIGN.md section 24)")
+        if vocab_select:
+            raise ValueError("vocab_select takes no n-gram mixture (DESIGN.md section 24: the static full-vocabulary Decoder.decode only)")
+        if self.compat_quirks:
+            raise ValueError("compat_quirks takes no n-gram mixture (DESIGN.md section 24)")
+        return ngram
+
     def decode_batch(self, inputs, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-                     random_sampling=False, context=None, cache=None):
-        """``cache`` (keyword): a :class:`jlm_amd.cache.CacheSpec` (one theta, N <= 4096) beside ``context`` word lists, or a
+                     random_sampling=False, context=None, cache=None, ngram=None):
+        """``ngram`` (keyword): a :class:`jlm_amd.ngram.NGramMix` -- a back-off word n-gram model is mixed into every edge cost,
+        p = (1 - lam) p_lm + lam p_ng(w | the last words of [<eos>] + context + the path so far), with or without
+        ``context``.  ValueError with ``cache=`` / a CachedContext, ``vocab_select`` or ``compat_quirks``, for anything that is not an
+        NGramMix and for a table with a word id outside the model's vocabulary, before anything runs.
+        ``cache`` (keyword): a :class:`jlm_amd.cache.CacheSpec` (one theta, N <= 4096) beside ``context`` word lists, or a
         :class:`jlm_amd.context.CachedContext` as ``context`` (``self.model.prime(contexts, cache=...)``): the continuous cache over
         every input's own context -- its last N (state, next word) pairs -- is mixed into every edge cost, p = (1 - lam) p_lm + lam c
         (DESIGN.md section 21); an input without context words is decoded as without a cache, and so is lam = 0.  ValueError with
@@ -236,6 +257,8 @@ class Decoder():
         [<eos>] + context[i] (jlm_amd/context.py); scores are -log p(path | that history).  None, or nothing but empty entries: the
         reference's decode."""
         inputs = list(inputs)
+        if ngram is not None:
+            self._check_ngram(ngram, context, cache, vocab_select)
         if vocab_select:                     # (before the context is resolved: nothing is primed for a call that is refused)
             self._refuse_cache(context, "vocab_select", cache)
         if self.compat_quirks:
@@ -243,7 +266,8 @@ class Decoder():
         ctx = self._context(context, len(inputs), cache=cache)
         sel = (vocab_select, samples, top_sampling, random_sampling)
         if beam_width is None:       # the reference's unpruned search, sentence at a time on the host
-            return [self._search_on_host(x, self._host_context(ctx, i), topN, None, *sel) for i, x in enumerate(inputs)]
+            return [self._search_on_host(x, self._host_context(ctx, i), topN, None, *sel, **self._host_ngram(ngram, ctx, i))
+                    for i, x in enumerate(inputs)]
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
             raise ValueError("beam_width must be 1..%d on the GPU path (or None: the unpruned host-side search)" % self.MAX_BEAM)
         if not inputs:
@@ -255,10 +279,11 @@ class Decoder():
                 raise ValueError("compat_quirks: the stale-vocabulary path of the reference takes no left context")
             return [self._decode_stale_vocab(x, topN, beam_width) for x in inputs]
         if not all(inputs):        # (an empty string / list is falsy)
-            return self._decode_subset(inputs, [i for i, x in enumerate(inputs) if len(x)], ctx, topN, beam_width, *sel)
+            return self._decode_subset(inputs, [i for i, x in enumerate(inputs) if len(x)], ctx, topN, beam_width, *sel,
+                                       **(dict(ngram=ngram) if ngram is not None else {}))
         chunks = self._chunks(inputs, beam_width, reorder=not (samples and random_sampling))
         workers = 1 if (samples and random_sampling) else self.prefetch_workers
-        extra, engine_kw, left = None, lambda _none: dict(vocab=None), None
+        extra, engine_kw, left = None, lambda _none: dict(vocab=None, **(dict(ngram=ngram) if ngram is not None else {})), None
         if vocab_select:
             # a chunk's word lists beside its lattice: (words, off) the engine's CSR over its sentences, lists[k] sentence k's own
             extra = lambda idx, lat: lat.static_vocab(samples, top_sampling, random_sampling, len(self.w2i))
@@ -270,27 +295,28 @@ class Decoder():
             out = self._launch_chunks(self._prepare_chunks(inputs, chunks, beam_width, workers, extra), chunks, len(inputs), ctx, topN,
                                       beam_width, "static", engine_kw, left)
         except _CellTooLarge as e:
-            return self._heavy_on_host(e.sentences, inputs, ctx, topN, beam_width, *sel)
+            return self._heavy_on_host(e.sentences, inputs, ctx, topN, beam_width, *sel, **(dict(ngram=ngram) if ngram is not None else {}))
         self.perf_sen += len(inputs)
         return out
 
-    def _decode_subset(self, inputs, keep, ctx, *args):
+    def _decode_subset(self, inputs, keep, ctx, *args, ngram=None):
         """decode_batch(*args) of the inputs ``keep`` alone, their context rows with them -> the whole call's result list: theirs in place,
         [(0.0, [])] everywhere else -- an empty input's: the reference's loop leaves the <eos> path alone (decoder.py:220-241)"""
-        sub = self.decode_batch([inputs[i] for i in keep], *args, context=ctx.sub(keep) if ctx is not None else None) if keep else []
+        sub = self.decode_batch([inputs[i] for i in keep], *args, context=ctx.sub(keep) if ctx is not None else None,
+                                **(dict(ngram=ngram) if ngram is not None else {})) if keep else []
         out = [[(0.0, [])] for _ in inputs]
         for i, r in zip(keep, sub):
             out[i] = r
         return out
 
-    def _heavy_on_host(self, heavy, inputs, ctx, *args):
+    def _heavy_on_host(self, heavy, inputs, ctx, *args, ngram=None):
         """The rest of a decode_batch(*args) call that met _CellTooLarge: the sentences named take the host-side search with the beam
         (_search_on_host), everything else goes through the device again -> the call's result list."""
         heavy = set(heavy)
-        out = self._decode_subset(inputs, [i for i in range(len(inputs)) if i not in heavy], ctx, *args)
+        out = self._decode_subset(inputs, [i for i in range(len(inputs)) if i not in heavy], ctx, *args, **(dict(ngram=ngram) if ngram is not None else {}))
         lv_last = self.lattice_vocab
         for i in sorted(heavy):
-            out[i] = self._search_on_host(inputs[i], self._host_context(ctx, i), *args)
+            out[i] = self._search_on_host(inputs[i], self._host_context(ctx, i), *args, **self._host_ngram(ngram, ctx, i))
         if (len(inputs) - 1) not in heavy:
             self.lattice_vocab = lv_last      # (the reference leaves the LAST sentence's list behind)
         return out
@@ -335,11 +361,20 @@ class Decoder():
         """what a host-side search takes of input i's left context: None or a jlm_amd.context.HostContext"""
         return ctx.host(i) if ctx is not None else None
 
-    def _search_on_host(self, input, context, topN, beam_width, vocab_select, samples, top_sampling, random_sampling):
+    @staticmethod
+    def _host_ngram(ngram, ctx, i):
+        """the keywords a host-side search takes of the call's ``ngram=`` for input i: none, or ngram = (the NGramMix, the last words of
+        the input's history [<eos>] + context)"""
+        if ngram is None:
+            return {}
+        from .generate import EOS_ID
+        return dict(ngram=(ngram, ctx.tail(i) if ctx is not None else [EOS_ID]))
+
+    def _search_on_host(self, input, context, topN, beam_width, vocab_select, samples, top_sampling, random_sampling, ngram=None):
         """one input searched on the host over LSTM_Model's numpy API: every input of a call with beam_width=None, and with the beam a
         sentence whose lattice cells the device beam step cannot hold"""
         return self._decode_unpruned(input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=beam_width,
-                                     context=context)
+                                     context=context, ngram=ngram)
 
     def _cand_limit(self, lat, beam_width):
         """candidates of one lattice cell the device beam step accepts for this batch shape"""
@@ -440,13 +475,15 @@ class Decoder():
         return chunks
 
     def _decode_unpruned(self, input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=None, vocab=None,
-                         context=None):
+                         context=None, ngram=None):
         """Decoder.decode of the reference with ``beam_width=None`` (decoder.py:220-241), statement for statement on the
         host: every candidate survives, each frame is one ``predict_with_context`` call over all of its paths (the GPU
         kernels behind LSTM_Model's numpy API), the result is the final frame in generation order, unsorted.  Also the
         engine of :meth:`_decode_stale_vocab` (a beam and a fixed vocabulary list).  ``context``: None, or a context.HostContext: h, c
         [1, H] -- the primed state read back -- and word, the last of the history: what the root consumes, and from where; mix(pred, h)
-        under the continuous cache: every frame's probabilities become the mixture (context.DecodeContext.host_mixer)."""
+        under the continuous cache: every frame's probabilities become the mixture (context.DecodeContext.host_mixer).  ``ngram``: None,
+        or (an NGramMix, the last words of the history): every path keeps its last two words and its probabilities become the n-gram
+        mixture by the float64 definition (jlm_amd/ngram.py)."""
         import math
         import numpy as np
         if len(input) == 0:
@@ -460,6 +497,10 @@ class Decoder():
         H = self.model.hidden_size
         # a path: (score, nodes tuple, word id of its last node); per frame also its state rows and probability rows
         frames = {0: dict(paths=[(0.0, (), ends[0][0][2] if context is None else int(context.word))])}
+        if ngram is not None:
+            assert vocab is None
+            frames[0]["hist"] = [tuple(ngram[1])[-2:]]
+            q_of = {}                                        # history -> exp q(. | history) over the vocabulary
         for i in range(len(input) + 1):
             if i > 0:
                 paths = []
@@ -475,6 +516,8 @@ class Decoder():
                     raise ValueError("beam_width=None: frame %d holds %d hypotheses (max_unpruned_paths = %d)" % (
                         i, len(paths), self.max_unpruned_paths))
                 frames[i] = dict(paths=[(p[0], p[1], p[2]) for p in paths], src=[(p[3], p[4]) for p in paths])
+                if ngram is not None:
+                    frames[i]["hist"] = [(frames[p[3]]["hist"][p[4]] + (int(p[2]),))[-2:] for p in paths]
             cur = frames[i]
             if i == len(input):
                 break                                        # (the reference steps the last frame too and drops the result)
@@ -489,6 +532,12 @@ class Decoder():
             (pred, _y, _t1, _t2), h2, c2 = self.model.predict_with_context([p[2] for p in cur["paths"]], hid, cel, vocab)
             if context is not None and context.mix is not None:
                 pred = context.mix(pred, h2)
+            if ngram is not None:
+                pred = np.array(pred, dtype=np.float64)
+                for k, hk in enumerate(cur["hist"]):
+                    if hk not in q_of:
+                        q_of[hk] = np.exp(ngram[0].table.logq_all(hk, pred.shape[1]))
+                    pred[k] = (1.0 - ngram[0].lam) * pred[k] + ngram[0].lam * q_of[hk]
             cur["pred"], cur["h"], cur["c"] = pred, h2, c2
         out = [(score, [w for w in nodes if w != "<eos>"]) for score, nodes, _lw in frames[len(input)]["paths"]]
         self.perf_sen += 1
@@ -537,11 +586,11 @@ class Decoder():
             yield item
 
     def decode(self, input, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-               random_sampling=False, context=None, cache=None):
+               random_sampling=False, context=None, cache=None, ngram=None):
         """``context`` (keyword): the words committed in front of ``input`` -- one sequence of word ids / lexicon strings, or a
-        ContextState of one row (see decode_batch); ``cache``: decode_batch's."""
+        ContextState of one row (see decode_batch); ``cache``, ``ngram``: decode_batch's."""
         out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling,
-                                context=_Single(context), cache=cache)[0]
+                                context=_Single(context), cache=cache, **(dict(ngram=ngram) if ngram is not None else {}))[0]
         if len(input):
             # the reference's shape: dict frame -> [Node] (decoder.py:79-135), what _build_lattice returns
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
@@ -557,7 +606,7 @@ class Decoder():
         """the tail starts of one input: [(s, lo, hi)] for every s in [0, len) at which vocabulary words properly extend text[s:]"""
         return index.tail_spans(text if isinstance(text, str) else "".join(text))
 
-    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None, cache=None):
+    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None, cache=None, ngram=None):
         """Conversion while the user types: every input is kana whose LAST word may be unfinished.  -> per input a pair
         (conversions, predictions).  ``conversions`` is ``decode_batch(inputs, topN, beam_width, context=context)``'s list, the very
         launches and bits.  ``predictions`` is [(score, [word, ...])], at most ``topN`` (1 .. 64), ascending: the best paths that cover
@@ -573,6 +622,8 @@ class Decoder():
             raise TypeError("%s has no decode_predict: the last word is predicted from rows normalised over the full word vocabulary "
                             "(the static Decoder)" % type(self).__name__)
         inputs = list(inputs)
+        if ngram is not None:
+            raise ValueError("decode_predict takes no n-gram mixture (DESIGN.md section 24: Decoder.decode only)")
         if cache is not None:
             raise ValueError("decode_predict takes no continuous cache (DESIGN.md section 21: Decoder.decode only)")
         self._refuse_cache(context, "decode_predict")
@@ -629,11 +680,11 @@ class Decoder():
         self.perf_sen += len(full)
         return out
 
-    def decode_predict(self, input, topN=10, beam_width=10, context=None, cache=None):
+    def decode_predict(self, input, topN=10, beam_width=10, context=None, cache=None, ngram=None):
         """:meth:`decode_predict_batch` of one input -> (conversions, predictions); ``context`` as :meth:`decode` takes it."""
         if self.dynamic or self.char_model:
             raise TypeError("%s has no decode_predict (see Decoder.decode_predict_batch)" % type(self).__name__)
-        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context), cache=cache)[0]
+        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context), cache=cache, ngram=ngram)[0]
         if len(input):
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
                                     for f, nodes in enumerate(self.last_lattice.backward_lookup(0))}

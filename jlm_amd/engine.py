@@ -153,6 +153,7 @@ class _Plan:
         # left context: the root rows' prev / word (seed_context_kernel writes entries s * beam), the batch's rows of the primed state
         self.ctx_prev = self.ctx_word = self.ctx_idx = self.ctx_idx_host = self.ctx_state = None
         self.cache_bufs = None               # decodes under the continuous cache: their score scratch (_CacheBufs), made on first use
+        self.ngram_bufs = None               # decodes under an n-gram mixture: the batch's root histories (_NgramBufs), made on first use
         if ctx:
             self.ctx_prev, self.ctx_word = torch.full((rmax,), -1, device=dev, dtype=i32), torch.zeros(rmax, device=dev, dtype=i32)
             self.ctx_idx, self.ctx_idx_host = torch.zeros(B, device=dev, dtype=i32), pin(torch.zeros(B, dtype=i32))
@@ -205,6 +206,18 @@ class _CacheBufs:
     @staticmethod
     def fit(have, eng, rmax, n):
         return have if have is not None and have.ld_s >= n else _CacheBufs(eng, rmax, _round_up(max(n, 1), 64))
+
+
+class _NgramBufs:
+    """What a plan's decodes under an n-gram mixture keep beside the table: root_hist [n_sent, 2] int32 on the device
+    (jlm_decode_ngram.root_hist) and its page-locked staging copy, written per batch."""
+
+    def __init__(self, eng, n_sent):
+        torch = eng.torch
+        self.root_hist = torch.zeros((n_sent, 2), device=eng.device, dtype=torch.int32)
+        self.host = torch.zeros((n_sent, 2), dtype=torch.int32)
+        if eng.device.type == "cuda":
+            self.host = self.host.pin_memory()
 
 
 class DecodeEngine:
@@ -299,7 +312,18 @@ class DecodeEngine:
         return p
 
     # ----------------------------------------------------------------- decode
-    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None, predict=None):
+    def ngram_tensors(self, table):
+        """the device tensors of an NGramTable's hash table -- (keys int64 [2^log2cap], vals float32 [2^log2cap, 2], its
+        device_arrays()) --, made once per table and device and reused by every batch"""
+        key = (self.device.type, self.device.index)
+        if key not in table._dev:
+            arr = table.device_arrays()
+            torch = self.torch
+            with self._ctx():
+                table._dev[key] = (torch.from_numpy(arr["keys"].view(np.int64)).to(self.device), torch.from_numpy(arr["vals"]).to(self.device), arr)
+        return table._dev[key]
+
+    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None, predict=None, ngram=None):
         """Enqueue one batch (upload, the frame-loop op, asynchronous read-back) and return a
         ticket for :meth:`collect`.  Nothing here waits for the GPU.  Successive calls use
         alternating streams (see __init__); every ticket owns its plan's buffers until collected.
@@ -314,11 +338,14 @@ class DecodeEngine:
         frames its unfinished tail may start at and the range of ``ids`` -- the device copy of ReadingIndex.ids -- of the words whose
         reading properly extends the tail from there), ``words`` the id -> string list; one more launch behind the frame loop
         (jlm_tail_predict) selects the n_out best (hypothesis, extension word) pairs per sentence, and :meth:`collect` returns
-        (conversions, predictions) pairs (static full-vocabulary decodes only)."""
+        (conversions, predictions) pairs (static full-vocabulary decodes only).
+        ngram: None, or a jlm_amd.ngram.NGramMix: the back-off n-gram model is mixed into every edge cost (``torch.ops.jlm.seed_ngram``:
+        no launch; one more launch per frame, csrc/jlm_ngram_edge.hip).  Static full-vocabulary decodes only and
+        not under the continuous cache: ValueError otherwise."""
         torch = self.torch
         with self._submit_lock, self._ctx():          # (the plan list and the stream rotation are shared by every submitting thread)
             if self.device.type != "cuda" or self.n_streams < 2 or (timing and timing != "inflight"):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict, ngram)
             if len(self._streams) != self.n_streams:
                 # the launch streams are shared by every engine on the device: each also gets a side stream inside the op, and
                 # streams beyond the GPU's hardware queues (GPU_MAX_HW_QUEUES, jlm_amd/__init__.py) serialise one another --
@@ -333,9 +360,9 @@ class DecodeEngine:
             if not cur.query():                                  # after whatever the caller queued (weight uploads, ...);
                 strm.wait_stream(cur)                            # nothing pending there in the steady state: no event, no wait
             with torch.cuda.stream(strm):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict, ngram)
 
-    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None, predict=None):
+    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None, predict=None, ngram=None):
         torch = self.torch
         dynamic = kind == "dynamic"
         vmode = "dynamic" if dynamic else ("select" if vocab is not None else "full")
@@ -362,6 +389,13 @@ class DecodeEngine:
         cached = context is not None and getattr(state, "spec", None) is not None and state.spec.lam > 0.0
         if cached and (dynamic or vocab is not None or predict is not None):
             raise ValueError("the continuous cache runs inside the static full-vocabulary decode only")
+        if ngram is not None:
+            from .ngram import check_mix
+            check_mix(ngram, self.m.V)
+            if dynamic or vocab is not None or predict is not None:
+                raise ValueError("an n-gram mixture runs inside the static full-vocabulary decode only")
+            if cached:
+                raise ValueError("an n-gram mixture and the continuous cache in one decode: a three-way mixture is not defined")
         if predict is not None:
             if dynamic or vocab is not None:
                 raise ValueError("predict: the last word is predicted behind a static full-vocabulary decode only")
@@ -393,12 +427,26 @@ class DecodeEngine:
                     p.cache_bufs = bufs = _CacheBufs.fit(p.cache_bufs, self, p.rmax, min(state.cap, state.spec.size))
                     ops.backend().seed_cache(p.obj, state.hist, state.words, state.count, p.ctx_idx, bufs.s, int(state.cap),
                                              int(state.spec.size), float(state.spec.theta), float(state.spec.lam))
+            if ngram is not None:
+                # the table and every sentence's root history for this frame loop (jlm_decode_plan.ngram): one small upload, no launch
+                from .generate import EOS_ID
+                if p.ngram_bufs is None:
+                    p.ngram_bufs = _NgramBufs(self, p.B)
+                nb, root = p.ngram_bufs, p.ngram_bufs.host.numpy()
+                root[:] = 0
+                root[:lat.n_sent] = (-1, EOS_ID) if context is None else state.tail_host[rows]
+                nb.root_hist.copy_(nb.host, non_blocking=True)
+                keys, vals, arr = self.ngram_tensors(ngram.table)
+                ops.backend().seed_ngram(p.obj, keys, vals, nb.root_hist, int(arr["log2cap"]), int(arr["max_probe"]), int(ngram.table.order),
+                                         float(ngram.lam))
             done = self._enqueue(p, lat, vocab, dyn_lists, dynamic, perm, max_words, topN, timing)
             if predict is not None:
                 done = self._enqueue_predict(p, sp, predict[1], n_pred)
         except BaseException:
             if cached:
                 ops.backend().clear_cache(p.obj)      # (the window was for this batch's frame loop, which may not have run)
+            if ngram is not None:
+                ops.backend().clear_ngram(p.obj)
             # nothing may keep the plan: launches already enqueued finish first, then its buffers are free again
             if self.device.type == "cuda":
                 try:
@@ -536,7 +584,8 @@ class DecodeEngine:
             # normaliser -- an overflowed row's hypotheses would score -inf and be pruned, leaving a plausible but wrong n-best
             p.busy = False
             if int(p.h_len[-1]) & 8:
-                raise _lib.JlmHipError("the cache flagged a product h . h_i that is not finite: a hidden state is NaN or inf")
+                raise _lib.JlmHipError("the cache flagged a product h . h_i that is not finite: a hidden state is NaN or inf (or, under an "
+                                       "n-gram mixture, a hypothesis's score is not finite)")
             raise _lib.JlmHipError("a log-normaliser is not finite: this model's logits left the range the fixed-reference normaliser covers "
                                    "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
         if getattr(self.m, "lse_fixed_ref", 0):

@@ -57,6 +57,10 @@ def build_parser():
                              "sentence's context (Decoder.decode(cache=)) and log both summaries")
     parser.add_argument("--theta", type=float, default=0.3, help="--cache: the cache's theta")
     parser.add_argument("--lam", type=float, default=0.1, help="--cache: the cache's lambda")
+    parser.add_argument("--ngram_mix", default=None,
+                        help="decode the set a second time with the back-off n-gram model of this file (SRILM text, python -m "
+                             "jlm_amd.ngram; read at --ngram_order) mixed into every edge cost (Decoder.decode(ngram=)) and log both summaries")
+    parser.add_argument("--ngram_lam", type=float, default=0.3, help="--ngram_mix: the n-gram model's weight lambda")
     parser.add_argument("--cut_last", type=int, default=0,
                         help="drop the last N kana of every reading and count how often the full target is among the predictions of "
                              "the unfinished last word (Decoder.decode_predict)")
@@ -95,6 +99,13 @@ class Evaluator:
             from .cache import CacheSpec
             from .context import check_decode_cache
             self.cache = check_decode_cache(CacheSpec(int(args.cache), theta=float(args.theta), lam=float(args.lam)))
+        self.ngram_mix = None            # --ngram_mix FILE: the NGramMix of the second pass
+        if getattr(args, "ngram_mix", None):
+            if args.use_ngram or self.config['char_rnn'] or args.dynamic_decoding or args.vocab_select or self.cut_last or self.cache is not None:
+                raise ValueError("--ngram_mix needs the static decoder over the full vocabulary, without --cache and --cut_last")
+            from .ngram import NGramMix, NGramTable, check_mix
+            path = args.ngram_mix if os.path.isabs(args.ngram_mix) or os.path.exists(args.ngram_mix) else os.path.join(_config.data_path, args.ngram_mix)
+            self.ngram_mix = check_mix(NGramMix(NGramTable.from_srilm(path, self.w2i, int(args.ngram_order)), float(args.ngram_lam)), len(self.w2i))
         self.contexts = None             # with --context_words: every loaded sentence's context tokens (load_eval_set)
         self.decoder = self._make_decoder()
         if hasattr(self.decoder, "perf_timing"):
@@ -125,14 +136,18 @@ class Evaluator:
             name = name[:-len(".txt")] + "_cut_{}.txt".format(self.cut_last)
         if self.cache is not None:
             name = name[:-len(".txt")] + "_cache_{}.txt".format(self.cache.size)
+        if getattr(self, "ngram_mix", None) is not None:
+            name = name[:-len(".txt")] + "_ngmix_{}.txt".format(self.ngram_mix.table.order)
         return name
 
-    def _decode_all(self, inputs, cache=None):
+    def _decode_all(self, inputs, cache=None, ngram=None):
         a = self.args
         kw = dict(beam_width=a.beam_size, vocab_select=a.vocab_select, samples=a.samples,
                   top_sampling=a.top_sampling, random_sampling=a.random_sampling)
         if cache is not None:
             kw["cache"] = cache
+        if ngram is not None:
+            kw["ngram"] = ngram
         step = max(1, a.batch)
         ctx = self.contexts if self.context_words else None
         if step == 1:                 # sentence at a time, as the reference does
@@ -220,21 +235,23 @@ class Evaluator:
                 print("--- %s seconds per step for vocab fix.---" % fix(d.perf_log_fix_vocab))
                 print("--- %s seconds per step for lattice path fix.---" % fix(d.perf_log_fix_lattice_path_prob))
             print("--- %s seconds ---" % (time.time() - t_start))
-            if self.cache is not None:
-                # the same set once more under the cache: its verdicts and its summary line behind the first pass's
+            mix = getattr(self, "ngram_mix", None)
+            if self.cache is not None or mix is not None:
+                # the same set once more under the cache (or the n-gram mixture): its verdicts and its summary line behind the first pass's
                 hits = {"best hit": 0, "nbest hit": 0, "no hit": 0}
                 t_start = time.time()
                 log.write('\n')
-                for x, y, nb in zip(inputs, targets, self._decode_all(inputs, cache=self.cache)):
+                for x, y, nb in zip(inputs, targets, self._decode_all(inputs, cache=self.cache, ngram=mix)):
                     sentences = [''.join(_surface(w) for w in words) for _score, words in nb]
                     verdict = "best hit" if y == sentences[0] else ("nbest hit" if y in sentences else "no hit")
                     hits[verdict] += 1
                     log.write(verdict + '\n')
                     log.write('{}\t{}\n'.format(y, x))
                     log.writelines(s + '\n' for s in sentences)
-                summary = 'cache {} theta {} lam {} best_hit {} nbest_hit{} no_hit {} eval_size {}'.format(
-                    self.cache.size, self.cache.theta, self.cache.lam, hits["best hit"], hits["nbest hit"],
-                    a.eval_size - hits["best hit"] - hits["nbest hit"], a.eval_size)
+                head = ('cache {} theta {} lam {}'.format(self.cache.size, self.cache.theta, self.cache.lam) if self.cache is not None
+                        else 'ngram_mix order {} lam {}'.format(mix.table.order, mix.lam))
+                summary = '{} best_hit {} nbest_hit{} no_hit {} eval_size {}'.format(
+                    head, hits["best hit"], hits["nbest hit"], a.eval_size - hits["best hit"] - hits["nbest hit"], a.eval_size)
                 log.write(summary)
                 log.write("--- %s seconds ---" % (time.time() - t_start))
                 print(summary)

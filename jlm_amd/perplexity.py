@@ -85,6 +85,29 @@ def stream_perplexity(model, stream, batch_size, num_steps):
     return float(np.exp(total / n_tok)), total, n_tok
 
 
+def stream_ngram_scores(model, stream, batch_size, num_steps, table):
+    """-> (nll, logq), float64 arrays over the tokens stream_perplexity scores: the model's -log p (score_streams) and the n-gram
+    model's q(token | the words before it in its row of the layout) from NGramTable.logq -- what the mixture's perplexity is made of,
+    on the host; no kernel beside score_streams' runs"""
+    from .score import stream_layout
+    x, y = stream_layout(stream, batch_size, num_steps)
+    h = c = None
+    T = (x.shape[1] // num_steps) * num_steps
+    nll = np.zeros((x.shape[0], T))
+    for i in range(T // num_steps):
+        cols = slice(i * num_steps, (i + 1) * num_steps)
+        part, h, c = model.score_streams(x[:, cols], y[:, cols], h, c)
+        nll[:, cols] = np.asarray(part, dtype=np.float64)
+    logq = np.array([[table.logq(x[r, max(0, t - 1):t + 1], y[r, t]) for t in range(T)] for r in range(x.shape[0])], dtype=np.float64)
+    return nll.reshape(-1), logq.reshape(-1)
+
+
+def ngram_mixture_perplexity(nll, logq, lam):
+    """exp(mean -log((1 - lam) p_lm + lam p_ng)) in float64 (jlm_amd.ngram.mixture_nll)"""
+    from .ngram import mixture_nll
+    return float(np.exp(mixture_nll(nll, logq, lam).mean()))
+
+
 def stream_cached_scores(model, stream, batch_size, num_steps, spec):
     """-> the :class:`jlm_amd.cache.CachedScores` of every corpus_iterator chunk, state and cache carried, as stream_perplexity"""
     from .score import stream_layout
@@ -194,7 +217,24 @@ def main(argv=None, de_stepper=None):
                     help="--dynamic: sweep --de-lrs x --de-lams on FILE (the dev set) and report the test perplexity at the best pair")
     ap.add_argument("--de-lrs", default="0.001,0.002,0.005,0.01,0.02", dest="de_lrs", help="--tune-dynamic: the learning rates of the grid")
     ap.add_argument("--de-lams", default="0,0.01,0.02,0.05", dest="de_lams", help="--tune-dynamic: the decays of the grid")
+    ap.add_argument("--ngram", default=None, metavar="FILE",
+                    help="stream mode: also report the perplexity of the mixture with the back-off n-gram model of FILE (SRILM text, "
+                         "python -m jlm_amd.ngram), formed on the host in float64 from score_streams' -log p: no new kernel runs")
+    ap.add_argument("--ngram-order", type=int, default=3, dest="ngram_order", help="--ngram: the order FILE is read at")
+    ap.add_argument("--ngram-lam", type=float, default=0.3, dest="ngram_lam", help="--ngram: the n-gram model's weight")
+    ap.add_argument("--tune-ngram", default=None, metavar="DEV", dest="tune_ngram", help="--ngram: pick lambda on this text file over --ngram-lams")
+    ap.add_argument("--ngram-lams", default=",".join("%.2f" % (0.05 * i) for i in range(1, 20)), dest="ngram_lams",
+                    help="--tune-ngram: the lambdas of the grid")
     args = ap.parse_args(argv)
+    if args.tune_ngram and not args.ngram:
+        ap.error("--tune-ngram goes with --ngram")
+    ngram_lams = None
+    if args.ngram:
+        if args.mode != "stream" or args.dynamic:
+            ap.error("--ngram works in stream mode, without --dynamic")
+        ngram_lams = _floats(args.ngram_lams, "--ngram-lams", ap) if args.tune_ngram else [args.ngram_lam]
+        if not ngram_lams or not all(0.0 < x < 1.0 for x in ngram_lams) or args.ngram_order not in (1, 2, 3):
+            ap.error("--ngram-lam / --ngram-lams lie in (0, 1), --ngram-order is 1, 2 or 3")
     if args.tune_dynamic and not args.dynamic:
         ap.error("--tune-dynamic goes with --dynamic")
     de_spec = de_grid = None
@@ -271,6 +311,21 @@ def main(argv=None, de_stepper=None):
             args.tune_cache, spec.theta, spec.lam, dev_pp[0], dev_pp[1], len(tune_spec.thetas), len(tune_lams)))
     if spec is not None:
         print("Test perplexity with cache (N {} theta {} lam {}): {}".format(spec.size, spec.theta, spec.lam, cached_pp))
+    if args.ngram:
+        from .ngram import NGramTable
+        ng_path = args.ngram if os.path.exists(args.ngram) else os.path.join(_config.data_path, args.ngram)
+        table = NGramTable.from_srilm(ng_path, vocab.t2i, args.ngram_order)
+        ng_lam = args.ngram_lam
+        if args.tune_ngram:
+            dev_sents, _n = encode_lines(read_lines(args.tune_ngram), vocab)
+            dev_nll, dev_q = stream_ngram_scores(model, [i for s in dev_sents for i in s], bs, args.num_steps, table)
+            grid = [ngram_mixture_perplexity(dev_nll, dev_q, x) for x in ngram_lams]
+            ng_lam = ngram_lams[int(np.argmin(grid))]
+            print("N-gram mixture tuned on {}: lam {}  (dev perplexity {} -> {} over {} values)".format(
+                args.tune_ngram, ng_lam, float(np.exp(dev_nll.mean())), min(grid), len(grid)))
+        ng_nll, ng_q = stream_ngram_scores(model, stream, bs, args.num_steps, table)
+        print("Test perplexity with n-gram mixture (order {} lam {}; host float64 over score_streams' -log p): {}".format(
+            table.order, ng_lam, ngram_mixture_perplexity(ng_nll, ng_q, ng_lam)))
     if de_spec is not None:
         stats = None
         if de_spec.rule == "rms":

@@ -18,7 +18,10 @@ def shard_indices(lengths, rank, world):
 
 def decode_sharded(decoder, sentences, rank, world, **decode_kwargs):
     """-> (indices, results) for this rank's shard.  ValueError for a decode under the continuous cache (``cache=``, a CachedContext):
-    a primed context holds one row per sentence of the whole call, not of a shard."""
+    a primed context holds one row per sentence of the whole call, not of a shard; and for ``ngram=`` (the
+    sharded decode is outside the n-gram mixture)."""
+    if decode_kwargs.get("ngram") is not None:
+        raise ValueError("decode_sharded takes no n-gram mixture (DESIGN.md section 24)")
     from .context import CachedContext
     if decode_kwargs.get("cache") is not None or isinstance(decode_kwargs.get("context"), CachedContext):
         raise ValueError("decode_sharded takes no continuous cache: prime and decode every rank's own sentences")
