@@ -1309,6 +1309,48 @@ int jlm_tail_predict(const jlm_segment *segs_host, int n_segs, const float *b2, 
                      int chunk, double *out_score, int *out_row, int *out_word, int *out_nodes, int *out_len, int stride, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Per-segment candidate lists behind a static decode (Decoder.decode_candidates; ABI 12, additive).
+ * Path `rank` of sentence s is the chain of pool rows g_K, bp[g_K], ..., g_0 (the root, bp = -1) from the final row
+ * g_K = sent_len[s] * rmax + s * beam + rank (rmax = n_sent * beam); segment k = 1 .. K is the word of g_k.  A row r < n_rows of the call
+ * (the rows of a jlm_score_plan) names a sentence, a depth d = k - 1 and a word a: "a in place of the word of segment k".  Its suffix
+ * steps j = #{t < n_steps : n_live[t] > r}: the caller sorts rows by j, longest first, as jlm_score_plan wants them.
+ * The decode whose pools these are must have completed, or run earlier on the same stream.
+ * alt_head_kernel (csrc/jlm_alt.hip), one launch, one workgroup of 256 threads per sentence, writes for every row of the sentence
+ *   nll_seq[r] = head + (score[g_K] - score[g_{k+j}]),   head = (score[g_d] + lse[g_d]) - (double)logit(T[g_d], a)   in f64
+ *                (mode 1, self-normalised: score[g_d] - logit), the logit bit-equal to jlm_edge_logits' for that (row, word);
+ *   prev0[r] = r;  and for j >= 1 rows r of p->h[0] / p->c[0] = the state rows (h, c)[g_d], byte for byte (H 4-byte values each).
+ * It replaces the caller's zeroing of nll_seq: jlm_score_frames then adds the j suffix terms.  Rows of the call that no sentence lists
+ * are not written.  flags (p->flags, one device int or NULL): |= 1 when an lse read is not finite, |= 2 when a row's word lies in no
+ * segment (its nll_seq is NaN), |= 4 when a walk leaves the pool -- a bp outside [-1, n_frames * rmax), a path of n_frames rows or more,
+ * sent_len outside [1, n_frames) -- or has fewer segments than a row's depth + 1 + j: such a row gets nll_seq = +inf and prev0 = -1 and
+ * nothing is copied for it.  LDS: 16 rows of T, n_frames path entries and n_steps counts, whatever the beam.  No atomics but the flag
+ * word's OR; one writer per address. */
+typedef struct {
+    int n_sent, beam, n_frames, rank;     /* of the decode whose pools these are; 0 <= rank < beam */
+    const void *h; const float *c;        /* the decode's state pools (jlm_decode_plan.h / .c) */
+    const float *T;                       /* its projection rows, [.., ldt] (jlm_decode_plan.T: untied models, as jlm_tail_predict) */
+    const double *score, *lse;            /* jlm_beam_state.score / .lse (lse may be NULL in mode 1) */
+    const int *bp;                        /* jlm_beam_state.bp */
+    const int *sent_len;                  /* jlm_lattice.sent_len [n_sent] */
+    const int *sent_off, *sent_rows;      /* [n_sent + 1], [n_rows] device: the rows of sentence s are sent_rows[sent_off[s] .. sent_off[s + 1]) */
+    const int *depth, *alt;               /* [n_rows] device: d = k - 1 and the word a of every row */
+    int *prev0;                           /* [n_rows] device, written; must be the score plan's prev0 */
+} jlm_alt_plan;
+
+/* -1 before any launch: a null or misaligned pointer (16 bytes: T, the state pools and row sets and the segments' blocks; 8: f64; 4:
+ * the rest), beam outside [1, JLM_MAX_BEAM], rank outside [0, beam), ldt % 4, H % 4, mode outside {0, 1}, a->prev0 != p->prev0, a pool of
+ * 2^31 rows or more, an LDS request that does not fit.  n_sent == 0 or n_rows == 0: 0, nothing launched.  -3 / a hipError_t as the
+ * launchers do.  jlm_alt_head_refuse: the same refusals on their own (0: the launch would be made), no GPU needed. */
+int jlm_alt_head_refuse(const jlm_segment *segs_host, int n_segs, const float *b2, int ldt, int H, int mode, const jlm_alt_plan *alt_host,
+                        const jlm_score_plan *plan_host);
+int jlm_alt_head(const jlm_segment *segs_host, int n_segs, const float *b2, int ldt, int H, int mode, const jlm_alt_plan *alt_host,
+                 const jlm_score_plan *plan_host, void *stream);
+/* jlm_alt_head, then jlm_score_frames' launches unchanged over plan_host's n_steps steps (none for n_steps == 0), no host
+ * synchronisation in between; every refusal of either comes before the first launch.  events as jlm_score_frames'. */
+int jlm_alt_frames(const jlm_decode_model *model_host, const jlm_alt_plan *alt_host, const jlm_score_plan *plan_host, void *stream,
+                   void *const *events);
+
+/* ------------------------------------------------------------------------
  * Scalar k-means compression of one weight tensor (jlm_amd/compress.py kmeans_compress; the reference's train/comp.py:20-48,
  * scikit-learn KMeans over the flattened weights).  Greedy k-means++ seeding, then Lloyd's iteration, all sums in integers so that
  * the result does not depend on the launch shape or on the order of any accumulation:

@@ -73,6 +73,13 @@ class ScorePlan(Structure):
                 ("nll_seq", c_void_p), ("nll_tok", c_void_p), ("flags", c_void_p)]
 
 
+class AltPlan(Structure):
+    """jlm_alt_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_sent", c_int), ("beam", c_int), ("n_frames", c_int), ("rank", c_int), ("h", c_void_p), ("c", c_void_p),
+                ("T", c_void_p), ("score", c_void_p), ("lse", c_void_p), ("bp", c_void_p), ("sent_len", c_void_p),
+                ("sent_off", c_void_p), ("sent_rows", c_void_p), ("depth", c_void_p), ("alt", c_void_p), ("prev0", c_void_p)]
+
+
 class GeneratePlan(Structure):
     """jlm_generate_plan (include/jlm_hip.h)."""
     _fields_ = [("n_rows", c_int), ("n_prompt", c_int), ("n_words", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("T", c_void_p),
@@ -208,6 +215,9 @@ _SIGS = {
     "jlm_prime_cache_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P, P, P, c_int, P], c_int),
     "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,
                           P, P, P, P, P, c_int, P], c_int),
+    "jlm_alt_head_refuse": ([POINTER(Segment), c_int, P, c_int, c_int, c_int, POINTER(AltPlan), POINTER(ScorePlan)], c_int),
+    "jlm_alt_head": ([POINTER(Segment), c_int, P, c_int, c_int, c_int, POINTER(AltPlan), POINTER(ScorePlan), P], c_int),
+    "jlm_alt_frames": ([POINTER(DecodeModel), POINTER(AltPlan), POINTER(ScorePlan), P, P], c_int),
     "jlm_vocab_lse_mixed_form": ([POINTER(Segment), POINTER(c_float), POINTER(c_float), c_int, c_int, c_int], c_int),
     "jlm_vocab_lse_split_form": ([], c_int),
     "jlm_gemm_nt_split_form": ([c_int, c_int], c_int),

@@ -283,7 +283,37 @@ def build_parser():
     ap.add_argument("--convert", default=None, metavar="KANA",
                     help="convert KANA whose last word may be unfinished (Decoder.decode_predict): prints the conversions and the "
                          "predictions of the last word; --prompt is the left context, -b the beam, --n-best the lists' length")
+    ap.add_argument("--candidates", default=None, metavar="KANA",
+                    help="convert KANA and list, for every segment of the best conversion, the words that could stand there, best first "
+                         "(Decoder.decode_candidates); --prompt is the left context, -b the beam")
+    ap.add_argument("--n-cand", type=int, default=10, help="with --candidates: words per segment (<= 64)")
+    ap.add_argument("--lookahead", type=int, default=None, metavar="J",
+                    help="with --candidates: words of the path re-scored behind a substitute (default: all of them)")
     return ap
+
+
+def candidates_main(args, vocab, prompts):
+    """--candidates: one (conversions, segments) pair per prompt, printed as the best conversion and one list per segment"""
+    from .decoder import Decoder
+    dec = Decoder(experiment_id=args.experiment_id, comp=args.comp)
+    t0 = time.time()
+    res = dec.decode_candidates_batch([args.candidates] * len(prompts), topN=1, beam_width=args.beam, n_cand=args.n_cand,
+                                      lookahead=args.lookahead, context=[list(p[1:]) for p in prompts])
+    dt = time.time() - t0
+    for b, (p, (conv, segs)) in enumerate(zip(prompts, res)):
+        if b:
+            print()
+        head = _gen.render(p[1:], vocab)
+        print("conversion%s:" % (" after " + head if head else ""))
+        print("%s\t%.4f" % (" ".join(w.split("/")[0] for w in conv[0][1]), conv[0][0]))
+        for start, length, cands in segs:
+            print("segment %d+%d %s:" % (start, length, args.candidates[start:start + length]))
+            for score, word in cands:
+                print("%s\t%.4f" % (word.split("/")[0], score))
+    n_out = sum(len(c) for _conv, segs in res for _s, _l, c in segs)
+    print("inputs: {}  segments: {}  candidates/s: {:.0f}".format(len(prompts), sum(len(sg) for _c, sg in res),
+                                                                  n_out / dt if dt > 0 else float("inf")), file=sys.stderr)
+    return res
 
 
 def convert_main(args, vocab, prompts):
@@ -330,6 +360,10 @@ def main(argv=None):
         n_unk += u
     if n_unk:
         print("prompts: %d word(s) outside the vocabulary read as <unk>" % n_unk, file=sys.stderr)
+    if args.candidates is not None:
+        if args.convert is not None or args.reading is not None or args.top is not None or isinstance(vocab, CharVocab):
+            ap.error("--candidates is a mode of its own (no --convert / --reading / --top), on a word model")
+        return candidates_main(args, vocab, prompts)
     if args.convert is not None:
         if args.reading is not None or args.top is not None or isinstance(vocab, CharVocab):
             ap.error("--convert is a mode of its own (no --reading / --top), on a word model")

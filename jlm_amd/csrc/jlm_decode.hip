@@ -632,6 +632,25 @@ extern "C" int jlm_score_frames(const jlm_decode_model *m, const jlm_score_plan 
     return score_loop(m, p, stream, events, [](int, int, const void *) { return 0; });
 }
 
+// Candidate lists behind a static decode (include/jlm_hip.h jlm_alt_frames): alt_head_kernel (csrc/jlm_alt.hip) seeds the accumulator,
+// the row sets and prev0 of the plan's rows from the decode's pools, then jlm_score_frames' launches add the suffix terms.  What
+// score_loop would refuse at its first step or later is refused here, before the head launch.
+extern "C" int jlm_alt_frames(const jlm_decode_model *m, const jlm_alt_plan *a, const jlm_score_plan *p, void *stream, void *const *events) {
+    if (!m || !a || !p) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    JLM_TRY(jlm_alt_head_refuse(m->segs, m->n_segs, m->b2, m->ldt, m->H, m->self_norm ? 1 : 0, a, p));
+    if (R > 0 && S > 0) {
+        if (!p->rows || !p->prev0 || !p->word || !p->target || !p->n_live || !p->nll_seq) return -1;
+        JLM_TRY(rows_refuse(m, p->T));
+        if (!m->self_norm && (!p->part || p->max_parts < 1)) return -1;
+        for (int t = 0; t < S; ++t)
+            if (p->n_live_host && (p->n_live_host[t] < 0 || p->n_live_host[t] > R)) return -1;
+    }
+    JLM_TRY(jlm_alt_head(m->segs, m->n_segs, m->b2, m->ldt, m->H, m->self_norm ? 1 : 0, a, p, stream));
+    if (R <= 0 || S <= 0) return 0;
+    return jlm_score_frames(m, p, stream, events);
+}
+
 // the refusals of jlm_cache_rows on their own (csrc/jlm_cache.hip)
 int jlm_cache_refuse(const void *hist, const int *words, int cap, int n_rows, int H, int split, float h_scale, int pos0, int n_query,
                      const int *first, const int *len, int N, const float *thetas, int n_theta, const float *lpc);

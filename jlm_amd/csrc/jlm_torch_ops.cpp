@@ -45,6 +45,8 @@
 //                             the window of the plan's next frame loop: no launch (jlm_decode_plan.cache; Decoder.decode(cache=))
 //   torch.ops.jlm.seed_ngram(Plan, keys, vals, root_hist, log2cap, max_probe, order, lam) / clear_ngram(Plan)
 //                             the n-gram table of the plan's next frame loop: no launch (jlm_decode_plan.ngram; Decoder.decode(ngram=))
+//   torch.ops.jlm.alt_frames(Model, Plan, rank, sent_off, sent_rows, depth, alt, score_frames' arguments)
+//                             per-segment candidate lists behind a plan's decode (jlm_alt_frames; Decoder.decode_candidates)
 //   torch.ops.jlm.tail_predict(Model, Plan, ids, sp_off, sp_frame, sp_lo, sp_hi, n_out, chunk, out_score, out_row, out_word, out_nodes,
 //                              out_len, stride)
 //                             predictions of an unfinished last word behind a plan's decode (jlm_tail_predict; Decoder.decode_predict)
@@ -779,6 +781,38 @@ Tensor score_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0,
                          [&](hipStream_t st, void *const *ev) { return jlm_score_frames(&m, &sp.p, st, ev); });
 }
 
+// The per-segment candidate lists behind a plan's static decode (jlm_alt_frames, include/jlm_hip.h): alt_head_kernel over the plan's
+// pools, then score_frames' launches over the same rows, on the current stream.  The plan's decode must have COMPLETED (the caller has
+// waited for its ticket's event: DecodeEngine.collect) and the plan must still be held; the stream need not be the decode's.
+// rank: the path; sent_off [n_sent + 1], sent_rows / depth / alt [n_rows] int32 on the device; the rest are score_frames' arguments
+// (prev0 and nll_seq are written by the head launch: the caller zeroes nothing).  -> as score_frames.
+Tensor alt_frames(const c10::intrusive_ptr<JlmModel> &model, const c10::intrusive_ptr<JlmPlan> &plan, int64_t rank, const Tensor &sent_off,
+                  const Tensor &sent_rows, const Tensor &depth, const Tensor &alt, const Tensor &h0, const Tensor &c0, const Tensor &h1,
+                  const Tensor &c1, const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts,
+                  const Tensor &rows, const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live,
+                  std::vector<int64_t> n_live_host, const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t n_rows,
+                  int64_t n_steps, bool timed) {
+    JlmPlan &pl = *plan;
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps, B = pl.lat.n_sent;
+    TORCH_CHECK(pl.p.kind == 0 && pl.lat.n_frames >= 1, "jlm.alt_frames: the plan must have run a static full-vocabulary decode");
+    TORCH_CHECK(rank >= 0 && rank < pl.lat.beam, "jlm.alt_frames: rank is 0 .. beam - 1");
+    TORCH_CHECK(is(sent_off, at::kInt, B + 1) && is(sent_rows, at::kInt, R) && is(depth, at::kInt, R) && is(alt, at::kInt, R),
+                "jlm.alt_frames: int32 sent_off [n_sent + 1], sent_rows / depth / alt [n_rows]");
+    TORCH_CHECK(h0.device().index() == pl.device, "jlm.alt_frames: the row sets live on the plan's device");
+    TORCH_CHECK(R * (int64_t)std::max(m.H / 4, 1) < 0x7ffffff0ll, "jlm.alt_frames: rows x H / 4 must stay below 2^31");
+    const ScorePlanArgs sp("alt_frames", m, h0, c0, h1, c1, T, Tm, ld_tm, part, max_parts, rows, prev0, word, target, n_live, n_live_host,
+                           nll_seq, nll_tok, flags, R, S);
+    jlm_alt_plan a{};
+    a.n_sent = pl.lat.n_sent; a.beam = pl.lat.beam; a.n_frames = pl.lat.n_frames; a.rank = (int)rank;
+    a.h = pl.p.h; a.c = pl.p.c; a.T = pl.p.T; a.score = pl.st.score; a.lse = pl.st.lse; a.bp = pl.st.bp; a.sent_len = pl.lat.sent_len;
+    a.sent_off = ptr<const int>(sent_off, "sent_off"); a.sent_rows = ptr<const int>(sent_rows, "sent_rows");
+    a.depth = ptr<const int>(depth, "depth"); a.alt = ptr<const int>(alt, "alt"); a.prev0 = ptr<int>(prev0, "prev0");
+    jlm_check(jlm_alt_head_refuse(m.segs, m.n_segs, m.b2, m.ldt, m.H, m.self_norm ? 1 : 0, &a, &sp.p), "jlm_alt_frames");
+    return launch_frames("jlm_alt_frames", pl.device, timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_alt_frames(&m, &a, &sp.p, st, ev); });
+}
+
 // The ring of a cache op, checked, into its plan (jlm_cache_plan, jlm_cache_mix_plan, jlm_predict_cache_plan): hist, words, cap and N; the
 // caller has checked its own bounds on cap and its position.
 template <class Plan>
@@ -1492,6 +1526,12 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
           "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed) -> Tensor",
           score_frames);
+    m.def("alt_frames(__torch__.torch.classes.jlm.Model model, __torch__.torch.classes.jlm.Plan plan, int rank, Tensor sent_off, "
+          "Tensor sent_rows, Tensor depth, Tensor alt, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor(k!) prev0, Tensor word, Tensor target, "
+          "Tensor n_live, int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, "
+          "bool timed) -> Tensor",
+          alt_frames);
     m.def("score_cache_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
           "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
           "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed, "

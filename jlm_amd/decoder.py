@@ -691,6 +691,114 @@ class Decoder():
         return out
 
 
+    # ------------------------------------------------------------------ per-segment candidate lists
+    MAX_CANDIDATES = 64
+
+    def decode_candidates_batch(self, inputs, topN=10, beam_width=10, n_cand=10, lookahead=None, rank=0, context=None):
+        """The window an input method shows: per input a pair (conversions, segments).  ``conversions`` is
+        ``decode_batch(inputs, topN, beam_width, context=context)``'s list, the very chunks, launches and bits.  ``segments`` cuts
+        path ``rank`` of it into its words: [(start, length, [(score, word), ...]), ...] in path order, where a segment's list holds the
+        lattice words with that start and length -- the path's own and the raw-kana fallback among them --, at most ``n_cand``
+        (1 .. 64), ascending by (score, lattice node order).  score = -log p of the path with the segment's word replaced: the
+        hypothesis's score in front of the segment - log p(word | it), then the next ``lookahead`` words of the path re-scored behind
+        the substitute under the full vocabulary (None: all of them), then the path's own terms for the rest; the path's own word
+        scores what the path scores, up to rounding.  An empty input gives ([(0.0, [])], []), an input with fewer than rank + 1
+        paths gives segments = [].  Per chunk one more op behind the collected decode (``torch.ops.jlm.alt_frames``); the plan stays
+        busy until its lists are read.
+        ValueError before any launch, every lattice built first: ``beam_width=None``, ``n_cand`` outside 1 .. 64, a negative
+        ``lookahead`` or ``rank``, ``rank >= topN``, compat_quirks with a stale vocabulary, a sentence with a lattice cell the device
+        beam step cannot hold, a CachedContext.  TypeError for the other decoders: their rows are not normalised over the full
+        vocabulary, or are not words."""
+        if self.dynamic or self.char_model:
+            raise TypeError("%s has no decode_candidates: a segment's alternatives are scored on rows normalised over the full word "
+                            "vocabulary (the static Decoder)" % type(self).__name__)
+        inputs = list(inputs)
+        self._refuse_cache(context, "decode_candidates")
+        from .context import CachedContext, DecodeContext
+        state = context.context if isinstance(context, _Single) else context
+        state = state.state if isinstance(state, DecodeContext) else state
+        if isinstance(state, CachedContext):
+            raise ValueError("decode_candidates takes no CachedContext (DESIGN.md section 25: the cache rewrites edge costs per hypothesis)")
+        if beam_width is None:
+            raise ValueError("decode_candidates needs a beam (beam_width=None is the unpruned host-side search)")
+        if not 1 <= int(beam_width) <= self.MAX_BEAM:
+            raise ValueError("beam_width must be 1..%d" % self.MAX_BEAM)
+        is_int = lambda x: not isinstance(x, bool) and int(x) == x
+        if not is_int(n_cand) or not 1 <= int(n_cand) <= self.MAX_CANDIDATES:
+            raise ValueError("n_cand must be an integer in 1..%d (got %r)" % (self.MAX_CANDIDATES, n_cand))
+        if lookahead is not None and (not is_int(lookahead) or int(lookahead) < 0):
+            raise ValueError("lookahead must be None or an integer >= 0 (got %r)" % (lookahead,))
+        if not is_int(topN) or not is_int(rank) or not 0 <= int(rank) < int(topN):
+            raise ValueError("rank must be an integer in 0..topN - 1 (got rank %r, topN %r)" % (rank, topN))
+        topN, beam_width, n_cand, rank = int(topN), int(beam_width), int(n_cand), int(rank)
+        lookahead = None if lookahead is None else int(lookahead)
+        if self.compat_quirks and self.lattice_vocab:
+            raise ValueError("compat_quirks: the stale-vocabulary path of the reference normalises over an old word list; candidates need "
+                             "the full vocabulary")
+        if not inputs:
+            return []
+        # the batches of decode_batch over the inputs that have kana: the same chunks, the same bits
+        full = [i for i, x in enumerate(inputs) if len(x)]
+        out = [([(0.0, [])], []) for _ in inputs]
+        if not full:
+            return out
+        chunks = [[full[j] for j in c] for c in self._chunks([inputs[i] for i in full], beam_width)]
+        # every lattice before the first launch (the priming of the contexts included): a refusal leaves nothing enqueued
+        prepared = []
+        try:
+            for chunk in self._prepare_chunks(inputs, chunks, beam_width, self.prefetch_workers):
+                prepared.append(chunk)
+        except _CellTooLarge as e:
+            for chunk in prepared:
+                chunk.lat.release()
+            raise ValueError("decode_candidates: input(s) %s have a lattice cell with more candidates than the device beam step holds at "
+                             "beam %d (decode_batch would search them on the host); convert them with decode" %
+                             (", ".join("%d (%r)" % (i, inputs[i]) for i in sorted(e.sentences)), beam_width))
+        ctx = self._context(context, len(inputs))
+        eng = self._engine
+
+        def submit(ch):
+            self.last_lattice = ch.lat
+            return ch.idx, eng.submit(ch.lat, "static", topN=topN, timing=self.perf_timing,
+                                      context=ctx.for_chunk(ch.idx) if ctx is not None else None, vocab=None)
+
+        def finish(idx, ticket):
+            conv = eng.collect(ticket, keep=True)            # phase 1; the plan's pools are read once more
+            try:
+                segs = eng.candidates(ticket, rank, lookahead, n_cand)
+            finally:
+                ticket.plan.busy = False
+            for j, c, sg in zip(idx, conv, segs):
+                out[j] = (c, sg)
+            if ticket.lat is not self.last_lattice:
+                ticket.lat.release()
+            self._log_perf()
+
+        # (phase 2 is not pipelined across chunks: a chunk is finished before the next is submitted)
+        eng.pipelined = len(chunks) > 1                      # (as decode_batch sets it for the call's chunks)
+        done = 0
+        try:
+            for ch in prepared:
+                done += 1
+                finish(*submit(ch))
+        finally:
+            eng.pipelined = False
+            for ch in prepared[done:]:                       # a failure: the chunks never submitted give their blocks back
+                ch.lat.release()
+        self.perf_sen += len(full)
+        return out
+
+    def decode_candidates(self, input, topN=10, beam_width=10, n_cand=10, lookahead=None, rank=0, context=None):
+        """:meth:`decode_candidates_batch` of one input -> (conversions, segments); ``context`` as :meth:`decode` takes it."""
+        if self.dynamic or self.char_model:
+            raise TypeError("%s has no decode_candidates (see Decoder.decode_candidates_batch)" % type(self).__name__)
+        out = self.decode_candidates_batch([input], topN, beam_width, n_cand, lookahead, rank, context=_Single(context))[0]
+        if len(input):
+            self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
+                                    for f, nodes in enumerate(self.last_lattice.backward_lookup(0))}
+        return out
+
+
 class _Single:
     """the ``context=`` of a one-input call on its way through the batch method: resolved there, after the argument checks"""
 

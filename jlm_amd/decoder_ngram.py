@@ -87,3 +87,9 @@ class NGramDecoder():
         raise TypeError("NGramDecoder has no decode_predict: the last word is predicted from the static Decoder's full-vocabulary rows")
 
     decode_predict_batch = decode_predict
+
+    def decode_candidates(self, *a, **kw):
+        """the static neural Decoder's: an n-gram model has no rows normalised over the full vocabulary to score a segment's alternatives on"""
+        raise TypeError("NGramDecoder has no decode_candidates: a segment's alternatives are scored on the static Decoder's full-vocabulary rows")
+
+    decode_candidates_batch = decode_candidates

@@ -563,8 +563,9 @@ class DecodeEngine:
         return done
 
 
-    def collect(self, ticket):
-        """Wait for a submitted batch and build its n-best lists."""
+    def collect(self, ticket, keep=False):
+        """Wait for a submitted batch and build its n-best lists.  keep=True: the plan stays busy -- its pools are read once more
+        (:meth:`candidates`) -- and the caller clears ``ticket.plan.busy``; a batch that fails here leaves no plan busy either way."""
         p, lat, timing, done = ticket.plan, ticket.lat, ticket.timing, ticket.done
         with self._ctx():
             if done is not None:
@@ -599,8 +600,63 @@ class DecodeEngine:
         out = self._read_out(lat, p.h_nodes.numpy(), p.h_len.numpy()[:-1], p.h_score.numpy(), ticket.topN)
         if ticket.words is not None:
             out = list(zip(out, self._read_predictions(lat, p, ticket.words)))
-        p.busy = False
+        if not keep:
+            p.busy = False
         return out
+
+    ALT_MAX_ROWS = None      # rows per jlm_alt_frames call (None: score.MAX_ROWS within score.SCORE_BUDGET_BYTES; tests force it down)
+
+    def candidates(self, ticket, rank=0, lookahead=None, n_cand=10):
+        """The per-segment candidate lists of path ``rank`` of a collected static full-vocabulary batch whose plan is still busy
+        (collect(keep=True)): -> per sentence [(start, length, [(score, word), ...])] (jlm_amd/candidates.py).
+        Per call of at most ALT_MAX_ROWS rows ONE op (``torch.ops.jlm.alt_frames``): the head launch over the plan's pools, then
+        score_frames' launches for the longest suffix, no host synchronisation inside, on the caller's current stream: collect() has waited
+        for the decode, so it need not be the decode's stream.  The row sets and id arrays are the call's own."""
+        from . import candidates as _cand
+        from . import score as _score
+        from .rowsets import RowSets, check_ids, clamp_rows
+        p, lat, m, torch = ticket.plan, ticket.lat, self.m, self.torch
+        if not p.busy or p.key[0] != "static" or p.key[1] != "full":
+            raise ValueError("candidates: a collected static full-vocabulary batch whose plan is still held (collect(keep=True))")
+        segments = _cand.segments_of(lat, p.h_nodes.numpy(), p.h_len.numpy()[:-1], int(rank))
+        longest = max((len(sg) for sg in segments), default=0)
+        max_rows = self.ALT_MAX_ROWS or clamp_rows(_score.MAX_ROWS, _score.SCORE_BUDGET_BYTES,
+                                                   _score.Scorer(m).row_bytes(max(longest - 1, 0), per_token=False), m.H)
+        index, calls = _cand.plan_rows(lat, segments, lookahead, int(max_rows))
+        totals = np.zeros(len(index), dtype=np.float64)
+        dev, f64, i32 = self.device, torch.float64, torch.int32
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        with self._ctx():
+            for call in calls:
+                R, S = len(call["idx"]), int(call["n_steps"])
+                check_ids(call["alt"], m.V, "candidates")
+                check_ids(call["target"], m.V, "candidates")
+                rs = RowSets(m, R)
+                part, n_parts, Tm = None, 0, None
+                if not m.self_norm:
+                    n_parts = max(m.n_vocab_tiles, 1)
+                    part = torch.zeros((n_parts, R, 2), device=dev, dtype=torch.float32)
+                    if getattr(m, "ld_tm", 0):
+                        Tm = torch.zeros(((R + 31) // 32 * 32, m.ld_tm), device=dev, dtype=torch.float32)     # whole 32-row blocks (jlm_hip.h)
+                # The head launch writes prev0 and the accumulator of every row a sentence lists -- all of them -- and the normaliser every
+                # slice it reads: none of the three needs a value.  They are filled all the same: every uninitialised allocation of the
+                # package is a site the poison modules must reach (DESIGN.md section 19), and a row the head launch skipped then reads as
+                # prev0 = -1 / total 0.0, which tests/test_gpu_alt_head.py pins on poisoned buffers.  (part: n_vocab_tiles x rows x 8 bytes a call.)
+                prev0 = torch.full((R,), -1, device=dev, dtype=i32)
+                nll_seq = torch.zeros(R, device=dev, dtype=f64)
+                n_live = [int(x) for x in call["n_live"]]
+                ops.backend().alt_frames(m.decode_model(), p.obj, int(rank), up(call["sent_off"]), up(call["sent_rows"]), up(call["depth"]),
+                                         up(call["alt"]), *rs.state(), Tm, int(m.ld_tm or 0), part, n_parts, rs.rows, prev0,
+                                         up(call["word"]), up(call["target"]), up(call["n_live"]), n_live, nll_seq, None, rs.flags, R, S,
+                                         False)
+                fl = int(rs.flags.cpu()[0])
+                if fl & 4:
+                    raise _lib.JlmHipError("candidates: a path's back-pointer chain left the plan's pools (flags %d)" % fl)
+                rs.check_flags("candidates: a word outside the model's segments (flags %d)",
+                               "a log-normaliser is not finite: this model's logits left the range the fixed-reference normaliser covers "
+                               "(DeviceModel.mixed_calib); set JLM_MX_FIXREF=0")
+                totals[call["idx"]] = nll_seq.cpu().numpy()
+        return _cand.lists_of(lat, segments, index, totals, int(n_cand))
 
     @staticmethod
     def _read_predictions(lat, p, words):

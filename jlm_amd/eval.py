@@ -64,6 +64,10 @@ def build_parser():
     parser.add_argument("--cut_last", type=int, default=0,
                         help="drop the last N kana of every reading and count how often the full target is among the predictions of "
                              "the unfinished last word (Decoder.decode_predict)")
+    # (no attribute without the flag: the namespace of a run that does not ask for it is what it was)
+    parser.add_argument("--candidates", type=int, default=argparse.SUPPRESS,
+                        help="for sentences whose best conversion has the gold segmentation but a wrong string: where the gold word "
+                             "stands in each wrong segment's list of N candidates (Decoder.decode_candidates)")
     return parser
 
 
@@ -106,7 +110,15 @@ class Evaluator:
             from .ngram import NGramMix, NGramTable, check_mix
             path = args.ngram_mix if os.path.isabs(args.ngram_mix) or os.path.exists(args.ngram_mix) else os.path.join(_config.data_path, args.ngram_mix)
             self.ngram_mix = check_mix(NGramMix(NGramTable.from_srilm(path, self.w2i, int(args.ngram_order)), float(args.ngram_lam)), len(self.w2i))
+        self.candidates = max(0, int(getattr(args, "candidates", 0) or 0))
+        if self.candidates and (args.use_ngram or self.config['char_rnn'] or args.dynamic_decoding or args.vocab_select or self.cut_last or
+                                self.cache is not None or self.ngram_mix is not None):
+            raise ValueError("--candidates: the segments' lists come from the static decoder over the full vocabulary, without --cut_last, "
+                             "--cache and --ngram_mix")
+        if self.candidates > 64:
+            raise ValueError("--candidates: at most 64 words per segment")
         self.contexts = None             # with --context_words: every loaded sentence's context tokens (load_eval_set)
+        self.gold = None                 # with --candidates: every loaded sentence's gold tokens (load_eval_set)
         self.decoder = self._make_decoder()
         if hasattr(self.decoder, "perf_timing"):
             self.decoder.perf_timing = True       # the log's per-step times (eval.py:104-121) need the per-frame events
@@ -138,6 +150,8 @@ class Evaluator:
             name = name[:-len(".txt")] + "_cache_{}.txt".format(self.cache.size)
         if getattr(self, "ngram_mix", None) is not None:
             name = name[:-len(".txt")] + "_ngmix_{}.txt".format(self.ngram_mix.table.order)
+        if getattr(self, "candidates", 0):
+            name = name[:-len(".txt")] + "_cand_{}.txt".format(self.candidates)
         return name
 
     def _decode_all(self, inputs, cache=None, ngram=None):
@@ -196,6 +210,53 @@ class Evaluator:
             print(summary)
             print("--- %s seconds ---" % (time.time() - t_start))
         return hits["best hit"], hits["nbest hit"], hits["no hit"]
+
+    def evaluate_candidates(self):
+        """--candidates N: the sentences whose 1-best has the gold segmentation but another string; for every wrong segment the position
+        of the gold word in the segment's list.  -> (such sentences, wrong segments, those with the gold word at position <= 1, <= 5,
+        <= N, sentences every wrong segment's top N can fix)"""
+        n, a = self.candidates, self.args
+        step = max(1, a.batch)
+        with open(self.log_name(), 'w', encoding='utf-8') as log:
+            inputs, targets = self.load_eval_set()
+            ctx = self.contexts if self.context_words else None
+            t_start = time.time()
+            res = []
+            for i in range(0, len(inputs), step):
+                res.extend(self.decoder.decode_candidates_batch(inputs[i:i + step], topN=1, beam_width=a.beam_size, n_cand=n,
+                                                                context=ctx[i:i + step] if ctx is not None else None))
+            sents = wrong = le1 = le5 = len_ = fixable = 0
+            for x, y, gold, (conv, segs) in zip(inputs, targets, self.gold, res):
+                best = conv[0][1] if conv else []
+                spans, start = [], 0
+                for t in gold:
+                    spans.append((start, len(_reading(t))))
+                    start += len(_reading(t))
+                if ''.join(_surface(w) for w in best) == y or [(s, l) for s, l, _c in segs] != spans:
+                    continue
+                sents += 1
+                log.write('{}\t{}\n'.format(y, x))
+                ok = True
+                for t, w, (s, l, cands) in zip(gold, best, segs):
+                    if _surface(w) == _surface(t):
+                        continue
+                    wrong += 1
+                    pos = next((k + 1 for k, (_sc, c) in enumerate(cands) if _surface(c) == _surface(t)), None)
+                    le1 += pos is not None and pos <= 1
+                    le5 += pos is not None and pos <= 5
+                    len_ += pos is not None
+                    ok = ok and pos is not None
+                    log.write('{}+{} {} -> {} position {}\n'.format(s, l, _surface(w), _surface(t), pos if pos is not None else '-'))
+                fixable += ok
+            share = lambda k, of: (float(k) / of) if of else 0.0
+            summary = ('candidates {} same_seg_wrong {} wrong_segments {} pos_le_1 {:.3f} pos_le_5 {:.3f} pos_le_{} {:.3f} fixable {:.3f} '
+                       'eval_size {}').format(n, sents, wrong, share(le1, wrong), share(le5, wrong), n, share(len_, wrong),
+                                              share(fixable, sents), len(inputs))
+            log.write(summary)
+            log.write("--- %s seconds ---" % (time.time() - t_start))
+            print(summary)
+            print("--- %s seconds ---" % (time.time() - t_start))
+        return sents, wrong, le1, le5, len_, fixable
 
     def _timing_lines(self):
         a, d = self.args, self.decoder
@@ -266,6 +327,7 @@ class Evaluator:
         want = self.args.eval_size
         xs, ys = [], []
         self.contexts = [] if self.context_words else None
+        self.gold = [] if getattr(self, "candidates", 0) else None
         with open(os.path.join(_config.data_path, 'test.txt'), 'r', encoding='utf-8') as f:
             lines = f.readlines()
         print('take {} for evaluation from all {} lines'.format(want, len(lines)))
@@ -276,6 +338,8 @@ class Evaluator:
             if self.context_words:
                 ctx, tokens = split_sentence(tokens, self.context_words)
                 self.contexts.append(ctx)
+            if self.gold is not None:
+                self.gold.append(list(tokens))
             xs.append(''.join(_reading(t) for t in tokens))
             ys.append(''.join(_surface(t) for t in tokens))
             if len(xs) >= want:
@@ -303,6 +367,8 @@ def main(argv=None):
         _config.set_root(args.root)
     os.makedirs('eval', exist_ok=True)
     ev = Evaluator(args)
+    if ev.candidates:
+        return ev.evaluate_candidates()
     return ev.evaluate_cut() if ev.cut_last else ev.evaluate()
 
 
