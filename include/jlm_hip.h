@@ -1278,6 +1278,93 @@ int jlm_ngram_cell_patch(const void *keys, const float *vals, int log2cap, int m
                          const int *wl_out, float *edge, const float *part, int ld_part, int n_parts, const int *live_base, double *lse,
                          int *flags, void *stream);
 
+/* ------------------------------------------------------------------------
+ * The n-gram model's distribution over EVERY word of a row, as a patch of the row's materialised logits (ABI 12,
+ * additive), so that rank_rows_kernel, topk_rows_kernel and topk_rows_masked_kernel run unchanged on the mixture.  q(w | h) is the
+ * definition above.  A row has f32 logits y[0 .. V), the history (u, v) = hist[r] (-1: no word; v = -1: no history at all) and
+ * L = lse(y) in topk_rows_kernel's arithmetic (self_norm: 0), read before any word is patched:
+ *     y'[w] = logaddexp(y[w], L + log(lam / (1 - lam)) + q(w | h))     q finite (y[w] = -inf: the finite n-gram term)
+ *     y'[w] = y[w], the same bits                                      q = -inf
+ * so that (1 - lam) exp(y' - L) is the mixture; the selection kernels report lse(y') - y', -log of the ROW-NORMALISED mixture (equal
+ * to the mixture for a table that sums to one), and -y' on self-normalised models, where the host adds -log1p(-lam).
+ *
+ * The table for this walk (jlm_amd/ngram.py NGramTable.successor_arrays): dense unigrams uni_lp [V] (-inf: none) and uni_bow [V];
+ * bigrams in CSR by context word, bi_off [V + 1] into bi_w / bi_lp [n_bi]; trigrams in CSR by context index, tri_off [n_ctx + 1] into
+ * tri_w / tri_lp [n_tri], and tri_bow [n_ctx] = bow(u v); the context index of (u, v) is found in an open-addressing map ctx_keys
+ * [2^log2cap] 64-bit / ctx_vals [2^log2cap], key (v + 1) | (u + 1) << 21, key 0 an empty slot, the hash and the probing of
+ * jlm_decode_ngram's table: a hit in the home slot is one round trip. */
+typedef struct jlm_ngram_rows {
+    const float *uni_lp, *uni_bow;
+    const int *bi_off, *bi_w; const float *bi_lp; int n_bi;
+    const int *tri_off, *tri_w; const float *tri_lp, *tri_bow; int n_tri, n_ctx;
+    const void *ctx_keys; const int *ctx_vals; int log2cap, max_probe;
+} jlm_ngram_rows;
+
+/* ngram_mix_rows_kernel (csrc/jlm_ngram_mix.hip): one workgroup of 256 threads per live row r < min(n_rows, *n_dev) (n_dev may be
+ * NULL), (V + 31) / 32 * 4 bytes of LDS for a bitmap of the patched words.  The trigram successors of (u, v) are patched with
+ * q = lp, then the bigram successors of v that no trigram covered with q = bow(u v) + lp, then every remaining word with a unigram
+ * with q = (bow(u v) + bow(v)) + lp, all in f32: t = (L + logf(rho)) + q, y' = max + log1pf(expf(min - max)).  order = 1 or v = -1:
+ * the last pass alone; order = 2 or u = -1: the last two.  The bitmap (integer OR in LDS) gives every logit one writer, which reads
+ * the original y[w]; no float atomics, plain vector loads and stores.  Every index read from a table array -- a range bound, a
+ * context index, a successor word -- is checked against n_bi / n_tri / n_ctx / V before it is used (a bad one is skipped), every
+ * probe loop ends after max_probe + 1 slots and every slot is masked into the map, whatever the table holds.  The bytes of y'[r] are
+ * a function of y[r][0 .. V), hist[r] and the table: not of n_rows, r, or what lies beyond V or beyond the live rows, where nothing
+ * is written.  *flags (may be NULL) |= 2: L of a row is not finite, |= 4: a history id outside [-1, V); the row is left as it is.
+ * Returns -1 before any launch for order outside 1 .. 3, lam outside (0, 1), V < 1 or V > JLM_NGRAM_MIX_MAX_V (the bitmap's LDS),
+ * ld_y % 4 != 0 or ld_y < V rounded up to 4, negative n_rows / n_bi / n_tri / n_ctx, log2cap outside 6 .. 31, max_probe outside
+ * [0, 2^log2cap), a null pointer, y not 16-byte, ctx_keys not 8-byte or another pointer not 4-byte aligned;
+ * 0 for n_rows = 0; a hipError_t of the launch.  jlm_ngram_mix_refuse: the refusals on their own. */
+#define JLM_NGRAM_MIX_MAX_V 393216      /* 48 KB of bitmap, beside under 100 bytes of static LDS: inside the 64 KB a workgroup
+                                         * may ask for without an attribute */
+int jlm_ngram_mix_refuse(const float *y, int ld_y, int n_cols, const jlm_ngram_rows *table, const int *hist, int n_rows, const int *n_dev,
+                         float lam, int order, const int *flags);
+int jlm_ngram_mix_rows(float *y, int ld_y, int n_cols, int self_norm, const jlm_ngram_rows *table, const int *hist, int n_rows,
+                       const int *n_dev, float lam, int order, int *flags, void *stream);
+
+/* ngram_hist_advance_kernel: hist_out[q] = (hist_in[prev_row[q]][1], word[q]) for q < n -- the histories of the rows a beam merge
+ * wrote, from those of the rows it chose them from; hist_in and hist_out are different buffers (double-buffered by the caller).  A
+ * prev_row outside [0, n_in): (-1, word[q]).  Returns -1 for negative n / n_in, a null or misaligned pointer or hist_in == hist_out. */
+int jlm_ngram_hist_advance(const int *hist_in, int n_in, const int *prev_row, const int *word, int n, int *hist_out, void *stream);
+
+/* What a ranking call under the n-gram mixture has beside its jlm_rank_plan (whose layout is unchanged). */
+typedef struct {
+    const jlm_ngram_rows *table; int order; float lam;
+    const int *hist;                    /* [n_steps][n_rows][2] device: (u, v) before target[t][r]; the loop is teacher-forced */
+    int top_k;                          /* 0: no lists */
+    int *top_ids; double *top_nll;      /* [n_steps][n_rows][top_k] device: jlm_topk_rows over the patched rows of every step */
+    int *flags;                         /* one device int or NULL: the bits of jlm_ngram_mix_rows */
+} jlm_ngram_mix_plan;
+
+/* jlm_rank_frames' loop -- the same launches in the same order -- with, per step, between the logit GEMMs and the ranking,
+ * jlm_ngram_mix_rows on the step's live rows with the histories hist[t], so that rank_rows_kernel ranks target[t] under the mixture;
+ * behind the ranking, with top_k > 0, jlm_topk_rows over the n_live_host[t] live rows into top_ids / top_nll (n_live_host is required
+ * then; its flags go to the rank plan's).  No host synchronisation.  Every refusal of jlm_ngram_mix_rows, top_k outside 0 ..
+ * min(JLM_TOPK_MAX, V) and an n_live_host[t] outside [0, n_rows] is returned before the first launch.  events (may be NULL):
+ * JLM_RANK_NGRAM_EVENTS_PER_STEP * n_steps hipEvent_t, [0] .. [3] as jlm_rank_frames', [4] after the patch, [5] after the ranking
+ * and the lists.  Returns as jlm_rank_frames does. */
+#define JLM_RANK_NGRAM_EVENTS_PER_STEP 6
+int jlm_rank_ngram_frames(const jlm_decode_model *model_host, const jlm_rank_plan *plan_host, const jlm_ngram_mix_plan *ngram_host,
+                          void *stream, void *const *events);
+
+/* What a completion under the n-gram mixture has beside its jlm_complete_plan (whose layout is unchanged): hist[0] and hist[1], two
+ * different 8-byte aligned device buffers [n_prompts * beam][2].  hist[0][p] = the last two words of prompt p (-1: no word), from the
+ * host; selecting frame k reads hist[k & 1] and, behind its merge, writes hist[(k + 1) & 1] (jlm_ngram_hist_advance over the rows the
+ * merge wrote; not behind the last).  hist[1] is not looked at when n_words = 1. */
+typedef struct {
+    const jlm_ngram_rows *table; int order; float lam;
+    int *hist[2];
+    int *flags;                         /* one device int or NULL: the bits of jlm_ngram_mix_rows */
+} jlm_complete_ngram_plan;
+
+/* jlm_complete_frames (prompt_set NULL; then mask NULL and n_sets 0) or jlm_complete_frames_masked (prompt_set given) -- the same
+ * launches in the same order -- with jlm_ngram_mix_rows on the n_sel rows of every selecting frame between the logit GEMMs and the
+ * selection, and the history advance behind every merge: a hypothesis is continued under the mixture of its own last two words.
+ * Every refusal before the first launch; no host synchronisation; events as jlm_complete_frames' (the patch is inside the selection's
+ * bracket, the advance inside the merge's). */
+int jlm_complete_frames_ngram(const jlm_decode_model *model_host, const jlm_complete_plan *plan_host,
+                              const jlm_complete_ngram_plan *ngram_host, const unsigned *mask, int ld_mask, int n_sets,
+                              const int *prompt_set, void *stream, void *const *events);
+
 /* jlm_prime_frames that keeps its states: behind the step of frame f >= n_steps - cap, the live prefix of the state set the step
  * wrote and target[f][0 .. n_live_host[f]) are copied into slot f - (n_steps - cap) of hist [cap][n_rows][H] / words [cap][n_rows]
  * (jlm_cache_store; earlier frames are not stored).  Priming is right-aligned: a row's entries end at slot cap - 1.  Rows past the

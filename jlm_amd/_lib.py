@@ -120,6 +120,24 @@ class PredictCachePlan(Structure):
                 ("cache_flags", c_void_p)]
 
 
+class NgramRows(Structure):
+    """jlm_ngram_rows (include/jlm_hip.h)."""
+    _fields_ = [("uni_lp", c_void_p), ("uni_bow", c_void_p), ("bi_off", c_void_p), ("bi_w", c_void_p), ("bi_lp", c_void_p), ("n_bi", c_int),
+                ("tri_off", c_void_p), ("tri_w", c_void_p), ("tri_lp", c_void_p), ("tri_bow", c_void_p), ("n_tri", c_int), ("n_ctx", c_int),
+                ("ctx_keys", c_void_p), ("ctx_vals", c_void_p), ("log2cap", c_int), ("max_probe", c_int)]
+
+
+class NgramMixPlan(Structure):
+    """jlm_ngram_mix_plan (include/jlm_hip.h)."""
+    _fields_ = [("table", POINTER(NgramRows)), ("order", c_int), ("lam", c_float), ("hist", c_void_p), ("top_k", c_int),
+                ("top_ids", c_void_p), ("top_nll", c_void_p), ("flags", c_void_p)]
+
+
+class CompleteNgramPlan(Structure):
+    """jlm_complete_ngram_plan (include/jlm_hip.h)."""
+    _fields_ = [("table", POINTER(NgramRows)), ("order", c_int), ("lam", c_float), ("hist", c_void_p * 2), ("flags", c_void_p)]
+
+
 class PrimePlan(Structure):
     """jlm_prime_plan (include/jlm_hip.h)."""
     _fields_ = [("n_rows", c_int), ("n_steps", c_int), ("h", c_void_p * 2), ("c", c_void_p * 2), ("rows", c_void_p), ("prev", c_void_p),
@@ -212,6 +230,11 @@ _SIGS = {
                               P, P, P, P], c_int),
     "jlm_ngram_cell_patch": ([P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, P, P, P, c_int, c_int,
                               P, P, P, P], c_int),
+    "jlm_ngram_mix_refuse": ([P, c_int, c_int, POINTER(NgramRows), P, c_int, P, c_float, c_int, P], c_int),
+    "jlm_ngram_mix_rows": ([P, c_int, c_int, c_int, POINTER(NgramRows), P, c_int, P, c_float, c_int, P, P], c_int),
+    "jlm_ngram_hist_advance": ([P, c_int, P, P, c_int, P, P], c_int),
+    "jlm_rank_ngram_frames": ([POINTER(DecodeModel), POINTER(RankPlan), POINTER(NgramMixPlan), P, P], c_int),
+    "jlm_complete_frames_ngram": ([POINTER(DecodeModel), POINTER(CompletePlan), POINTER(CompleteNgramPlan), P, c_int, c_int, P, P, P], c_int),
     "jlm_prime_cache_frames": ([POINTER(DecodeModel), POINTER(PrimePlan), P, P, P, c_int, P], c_int),
     "jlm_tail_predict": ([POINTER(Segment), c_int, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, c_int, c_int,
                           P, P, P, P, P, c_int, P], c_int),

@@ -338,6 +338,7 @@ def _flag_error(fl):
 class MixRings(Ring):
     """The rings of one cached ranking call (jlm_cache_mix_plan): :class:`Ring` in zeroed memory, with the scratch ``s`` [R, N] of one
     step's scores in lpc's place, and ``top`` > 0 the lists top_ids / top_nll [S, R, top] of every step."""
+    op = "rank_cache_frames"            # the op Ranker.run calls with op_args behind rank_frames' arguments
 
     def __init__(self, m, spec, R, S, state=None, top=0):
         torch, dev = m.torch, m.device

@@ -25,6 +25,11 @@ Word sets (``predict_top(allowed=)``, ``complete(first_allowed=)``; ``LSTM_Model
 over the whole vocabulary, so scores stay -log p under the full distribution, comparable with ``score()``.  A set smaller than the
 beam pads frame 0's list with (-1, +inf): such a candidate becomes a finished hypothesis of infinite score that is never expanded,
 and hypotheses whose total is not finite are dropped from the result.
+
+A back-off n-gram mixture (``ngram=`` of all four entry points, a :class:`jlm_amd.ngram.NGramMix`): every
+selecting frame's rows are patched into the logits of (1 - lam) p_lm + lam q(. | h) before the selection, masked or not
+(``torch.ops.jlm.complete_frames_ngram``, csrc/jlm_ngram_mix.hip), h the last two words of the prompt followed by the hypothesis's own,
+carried on the device behind every merge.  ``ngram=None`` calls exactly the op it called before.
 """
 import argparse
 import sys
@@ -183,14 +188,17 @@ class Completer:
         self.torch = dev_model.torch
         self.last_frame_ms = None         # [frames, 5] of the last timed call: LSTM step, T projection, logit GEMMs, selection, merge
 
-    def row_bytes(self, n_prompt, n_words, beam):
+    def row_bytes(self, n_prompt, n_words, beam, ngram=False):
+        """the bytes a row of a call takes; ``ngram``: with its two history entries (jlm_amd.ngram_mix.BeamHist)"""
         m = self.m
-        return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + beam * 12 + n_words * 16 + n_prompt * 8 + 48
+        return (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + beam * 12 + n_words * 16 + n_prompt * 8 + 48 + (16 if ngram else 0)
 
-    def run(self, prompts, n_words, beam, stop_id=None, timed=False, n_live=None, first_sets=None):
+    def run(self, prompts, n_words, beam, stop_id=None, timed=False, n_live=None, first_sets=None, ngram=None):
         """One call over prompts already sorted by length (longest first).  n_live: the chunk's live counts from plan_prompts (None:
         rowsets.live_counts of the prompts).  first_sets: None, or per prompt None or the word ids its first word is chosen among
-        (the masked op; None leaves the call exactly what it was).  -> (bp_parent, bp_word [n_words, R] int32, bp_nll [n_words, R]
+        (the masked op; None leaves the call exactly what it was).  ngram: None, or a checked :class:`jlm_amd.ngram.NGramMix` -- the
+        op is then ``complete_frames_ngram``, masked or not: every selecting frame's rows are patched into the mixture of the
+        hypothesis's own last two words before the selection (jlm_amd/ngram_mix.py).  -> (bp_parent, bp_word [n_words, R] int32, bp_nll [n_words, R]
         float64, score [R] float64), R = len(prompts) * beam, rank i of prompt p at row p * beam + i."""
         torch, m = self.torch, self.m
         if n_live is None:
@@ -214,25 +222,38 @@ class Completer:
             args = (m.decode_model(), *rs.state(), rs.logits, rs.ld_logits, rs.rows, up(prev), up(prompt), up(n_live),
                     [int(x) for x in n_live], cand_ids, cand_nll, word, prev_row, score, finished, -1 if stop_id is None else int(stop_id),
                     bp_parent, bp_word, bp_nll, rs.flags, NP, B, P, int(n_words), bool(timed))
-            if first_sets is None:
-                ms = _ops.backend().complete_frames(*args)
-            else:
+            mask_args = (None, 0, 0, [])
+            if first_sets is not None:
                 restricted = [p for p in range(NP) if first_sets[p] is not None]
                 mask, index = ReadingIndex.mask([first_sets[p] for p in restricted], m.V)
                 prompt_set = [-1] * NP
                 for p, s in zip(restricted, index):
                     prompt_set[p] = int(s)
-                ms = _ops.backend().complete_frames_masked(*args, torch.from_numpy(mask.view(np.int32)).to(dev), mask.shape[1],
-                                                           mask.shape[0], prompt_set)
+                mask_args = (torch.from_numpy(mask.view(np.int32)).to(dev), mask.shape[1], mask.shape[0], prompt_set)
+            if ngram is not None:
+                from .ngram_mix import BeamHist
+                bh = BeamHist(m, ngram, prompts, R)
+                ms = _ops.backend().complete_frames_ngram(*args, *mask_args, *bh.op_args())
+            elif first_sets is None:
+                ms = _ops.backend().complete_frames(*args)
+            else:
+                ms = _ops.backend().complete_frames_masked(*args, *mask_args)
             if timed:
                 self.last_frame_ms = ms.numpy()
+            if ngram is not None:
+                bh.check()
             rs.check_flags("topk_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)")
             return bp_parent.cpu().numpy(), bp_word.cpu().numpy(), bp_nll.cpu().numpy(), score.cpu().numpy()
 
 
-def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, first_allowed=None):
+def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, first_allowed=None, ngram=None):
     """LSTM_Model.complete: see there."""
     prompts, n_best = check_args(prompts, n_words, beam_width, n_best, stop_id, comp.m.V)
+    if ngram is not None:
+        from .ngram import check_mix_rows
+        check_mix_rows(ngram, comp.m.V)
+    # a self-normalised model under the mixture: the kernels score -y', and -log p of a word is -y' - log1p(-lam)
+    shift = -np.log1p(-float(np.float32(ngram.lam))) if ngram is not None and comp.m.self_norm else 0.0
     sets = check_allowed(first_allowed, len(prompts), comp.m.V, "complete (first_allowed)")
     out = [None] * len(prompts)
     if not prompts:
@@ -246,21 +267,23 @@ def complete(comp, prompts, n_words, beam_width=10, n_best=None, stop_id=None, m
             return out
     lens = [len(prompts[i]) for i in run]
     if max_rows is None:
-        max_rows = rowsets.clamp_rows(MAX_ROWS, COMPLETE_BUDGET_BYTES, comp.row_bytes(max(lens), n_words, beam_width), comp.m.H)
+        max_rows = rowsets.clamp_rows(MAX_ROWS, COMPLETE_BUDGET_BYTES, comp.row_bytes(max(lens), n_words, beam_width, ngram is not None), comp.m.H)
     for ch in plan_prompts(lens, beam_width, max_rows):
         idx = [run[j] for j in ch["idx"]]
         bp_parent, bp_word, bp_nll, score = comp.run([prompts[i] for i in idx], int(n_words), int(beam_width), stop_id, n_live=ch["n_live"],
-                                                     first_sets=None if sets is None else [sets[i] for i in idx])
+                                                     first_sets=None if sets is None else [sets[i] for i in idx], ngram=ngram)
         for j, i in enumerate(idx):
             out[i] = backtrace(bp_parent, bp_word, bp_nll, score, j, int(beam_width), n_best, stop_id)
+            if shift:
+                out[i] = [(ids, nll + shift, total + shift * len(ids)) for ids, nll, total in out[i]]     # (a carry adds no word)
             if sets is not None:                         # a set smaller than the beam: the padding's hypotheses have infinite totals
                 out[i] = [h for h in out[i] if np.isfinite(h[2])]
     return out
 
 
-def predict_top(comp, contexts, n=10, max_rows=None, allowed=None):
+def predict_top(comp, contexts, n=10, max_rows=None, allowed=None, ngram=None):
     """LSTM_Model.predict_top: see there.  Frame 0 of complete(contexts, 1, beam_width=n)."""
-    res = complete(comp, contexts, 1, beam_width=n, max_rows=max_rows, first_allowed=allowed)
+    res = complete(comp, contexts, 1, beam_width=n, max_rows=max_rows, first_allowed=allowed, ngram=ngram)
     return [(np.array([h[0][0] for h in r], dtype=np.int64), -np.array([h[1][0] for h in r], dtype=np.float64)) for r in res]
 
 
@@ -286,6 +309,11 @@ def build_parser():
     ap.add_argument("--candidates", default=None, metavar="KANA",
                     help="convert KANA and list, for every segment of the best conversion, the words that could stand there, best first "
                          "(Decoder.decode_candidates); --prompt is the left context, -b the beam")
+    ap.add_argument("--ngram", default=None, metavar="FILE",
+                    help="mix a back-off n-gram model (ARPA text, python -m jlm_amd.ngram) into every distribution the words are chosen "
+                         "from: with --top the next words, else every word of every completion; with --reading too")
+    ap.add_argument("--ngram-lam", type=float, default=None, dest="ngram_lam", help="--ngram: the n-gram model's weight, in (0, 1)")
+    ap.add_argument("--ngram-order", type=int, default=3, dest="ngram_order", help="--ngram: the order FILE is read at (1, 2 or 3)")
     ap.add_argument("--n-cand", type=int, default=10, help="with --candidates: words per segment (<= 64)")
     ap.add_argument("--lookahead", type=int, default=None, metavar="J",
                     help="with --candidates: words of the path re-scored behind a substitute (default: all of them)")
@@ -344,9 +372,17 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.exact and args.reading is None:
         ap.error("--exact needs --reading")
+    if args.ngram is not None and (args.ngram_lam is None or not 0.0 < args.ngram_lam < 1.0 or args.ngram_order not in (1, 2, 3)):
+        ap.error("--ngram needs --ngram-lam in (0, 1); --ngram-order is 1, 2 or 3")
+    if args.ngram is None and args.ngram_lam is not None:
+        ap.error("--ngram-lam goes with --ngram")
+    if args.ngram is not None and (args.convert is not None or args.candidates is not None):
+        ap.error("--ngram goes with --top and with completions, not with --convert / --candidates")
     _cfg, vocab = load_vocab(args)
     if args.reading is not None and isinstance(vocab, CharVocab):
         ap.error("--reading needs a word model: a character model's softmax is not over words")
+    if args.ngram is not None and isinstance(vocab, CharVocab):
+        ap.error("--ngram needs a word model: the table is over words")
     from .model import LSTM_Model
     if args.file:
         with open(args.file, encoding="utf-8") as f:
@@ -372,9 +408,15 @@ def main(argv=None):
     sep = "" if isinstance(vocab, CharVocab) else " "
     t0 = time.time()
     readings = None if args.reading is None else [args.reading] * len(prompts)
+    mix = None
+    if args.ngram is not None:
+        import os
+        from .ngram import NGramMix, NGramTable
+        path = args.ngram if os.path.exists(args.ngram) else os.path.join(_config.data_path, args.ngram)
+        mix = NGramMix(NGramTable.from_srilm(path, vocab.t2i, args.ngram_order), args.ngram_lam)
     if args.top is not None:
-        res = (model.predict_top(prompts, n=args.top) if readings is None else
-               model.predict_reading(prompts, readings, n=args.top, exact=args.exact))
+        res = (model.predict_top(prompts, n=args.top, ngram=mix) if readings is None else
+               model.predict_reading(prompts, readings, n=args.top, exact=args.exact, ngram=mix))
         dt = time.time() - t0
         for b, (p, (ids, logp)) in enumerate(zip(prompts, res)):
             if b:
@@ -384,7 +426,7 @@ def main(argv=None):
                 print("%s%s%s\t%.4f" % (head, sep if head else "", _gen.render([w], vocab), -lp))
         n_out = sum(len(r[0]) for r in res)
     else:
-        kw = dict(beam_width=args.beam, n_best=args.n_best, stop_id=EOS_ID if args.stop_at_eos else None)
+        kw = dict(beam_width=args.beam, n_best=args.n_best, stop_id=EOS_ID if args.stop_at_eos else None, ngram=mix)
         res = (model.complete(prompts, args.words, **kw) if readings is None else
                model.complete_reading(prompts, readings, args.words, exact=args.exact, **kw))
         dt = time.time() - t0

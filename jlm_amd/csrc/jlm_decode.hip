@@ -762,6 +762,39 @@ extern "C" int jlm_rank_cache_frames(const jlm_decode_model *m, const jlm_rank_p
         });
 }
 
+// Ranking under the n-gram mixture (include/jlm_hip.h jlm_rank_ngram_frames): rank_loop with ngram_mix_rows_kernel on every step's
+// logits before they are ranked, and an optional top-k list of the patched rows behind the ranking.  The loop is teacher-forced, so
+// the host knows every history and uploads them: nothing is carried on the device.
+extern "C" int jlm_rank_ngram_frames(const jlm_decode_model *m, const jlm_rank_plan *p, const jlm_ngram_mix_plan *np, void *stream,
+                                     void *const *events) {
+    if (!np || !p || !m || m->n_segs < 1) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    if (R < 0 || S < 0) return -1;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    JLM_TRY(jlm_ngram_mix_refuse(p->logits, p->ld_logits, V, np->table, np->hist, R, p->n_live, np->lam, np->order, np->flags));
+    if (np->top_k < 0 || np->top_k > JLM_TOPK_MAX || np->top_k > V) return -1;
+    if (np->top_k > 0 && (!np->top_ids || !np->top_nll || !p->n_live_host)) return -1;
+    // (with the logits checked by the patch's refusals above, that is every -1 of jlm_topk_rows: nothing is left to refuse in the loop)
+    if (p->n_live_host)
+        for (int t = 0; t < S; ++t)
+            if (p->n_live_host[t] < 0 || p->n_live_host[t] > R) return -1;
+    return rank_loop(
+        m, p, stream, events, JLM_RANK_NGRAM_EVENTS_PER_STEP,
+        [&](int t, int bound, const void *, const int *ndev, const Stamps &stamp) -> int {
+            if (bound > 0)
+                JLM_TRY(jlm_ngram_mix_rows(p->logits, p->ld_logits, V, m->self_norm, np->table, np->hist + (size_t)t * R * 2, bound, ndev,
+                                           np->lam, np->order, np->flags, stream));
+            return stamp(t, 4);
+        },
+        [&](int t, int, const void *) -> int {
+            if (np->top_k > 0 && p->n_live_host[t] > 0)
+                JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, p->n_live_host[t], np->top_k, m->self_norm,
+                                      np->top_ids + (size_t)t * R * np->top_k, np->top_nll + (size_t)t * R * np->top_k, np->top_k, p->flags,
+                                      stream));
+            return 0;
+        });
+}
+
 // One step of prediction under the cache, for a caller who holds the carried state of its streams (include/jlm_hip.h
 // jlm_predict_cache_rows): the T projection of h, the logits, the cache's query and patch at `pos`, and the (masked) top-k selection.
 // No LSTM step and no ring write.
@@ -843,8 +876,12 @@ extern "C" int jlm_generate_frames_trunc(const jlm_decode_model *m, const jlm_ge
 // distribution); every later frame steps all n_prompts * beam rows from the rows the previous merge chose, then the T projection, the
 // logit GEMMs, topk_rows_kernel and beam_merge_kernel, which writes the next frame's word / prev row and the back-pointers.
 // prompt_set (jlm_complete_frames_masked; NULL: none): selecting frame 0's rows, one per prompt, select within their word sets.
+// before_select(k, n_sel): between the logit GEMMs' stamp and selecting frame k's selection; after_merge(k, n_sel): behind its merge,
+// ahead of the frame's last stamp.  jlm_complete_frames and jlm_complete_frames_masked: nothing in either -- the same launches in the
+// same order --; jlm_complete_frames_ngram: the n-gram patch of the n_sel rows, and the histories of the rows the merge wrote.
+template <class BeforeSelect, class AfterMerge>
 static int complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p, const unsigned *mask, int ld_mask, int n_sets,
-                           const int *prompt_set, void *stream, void *const *events) {
+                           const int *prompt_set, void *stream, void *const *events, BeforeSelect before_select, AfterMerge after_merge) {
     const int NP = p->n_prompts, B = p->beam, P = p->n_prompt, N = p->n_words;
     if (NP < 0 || B < 1 || B > JLM_TOPK_MAX || P < 1 || N < 0 || !p->rows || !p->prev || !p->prompt || !p->n_live || !p->n_live_host ||
         !p->logits || !p->cand_ids || !p->cand_nll || !p->word || !p->prev_row || !p->score || !p->finished || !p->bp_parent ||
@@ -868,6 +905,7 @@ static int complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p
         JLM_TRY(stamp(f, 2));
         if (k >= 0) JLM_TRY(rows_logits(m, s.T, p->logits, p->ld_logits, n_sel, stream));
         JLM_TRY(stamp(f, 3));
+        if (k >= 0) JLM_TRY(before_select(k, n_sel));
         if (k == 0 && prompt_set)
             JLM_TRY(jlm_topk_rows_masked(p->logits, p->ld_logits, V, n_sel, B, m->self_norm, mask, ld_mask, n_sets, prompt_set, p->cand_ids,
                                          p->cand_nll, B, p->flags, stream));
@@ -877,17 +915,44 @@ static int complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p
         if (k >= 0)
             JLM_TRY(jlm_beam_merge(p->cand_ids, p->cand_nll, B, NP, k == 0, p->stop_id, p->word, p->prev_row, p->score, p->finished,
                                    p->bp_parent + (size_t)k * R, p->bp_word + (size_t)k * R, p->bp_nll + (size_t)k * R, stream));
+        if (k >= 0) JLM_TRY(after_merge(k, n_sel));
         JLM_TRY(stamp(f, 5));
     }
     return 0;
 }
 
 extern "C" int jlm_complete_frames(const jlm_decode_model *m, const jlm_complete_plan *p, void *stream, void *const *events) {
-    return complete_frames(m, p, nullptr, 0, 0, nullptr, stream, events);
+    return complete_frames(m, p, nullptr, 0, 0, nullptr, stream, events, [](int, int) { return 0; }, [](int, int) { return 0; });
 }
 
 extern "C" int jlm_complete_frames_masked(const jlm_decode_model *m, const jlm_complete_plan *p, const unsigned *mask, int ld_mask,
                                           int n_sets, const int *prompt_set, void *stream, void *const *events) {
     if (!prompt_set || n_sets < 0 || (n_sets > 0 && !mask)) return -1;
-    return complete_frames(m, p, mask, ld_mask, n_sets, prompt_set, stream, events);
+    return complete_frames(m, p, mask, ld_mask, n_sets, prompt_set, stream, events, [](int, int) { return 0; }, [](int, int) { return 0; });
+}
+
+// Completion under the n-gram mixture (include/jlm_hip.h jlm_complete_frames_ngram): complete_frames with the n_sel rows of every
+// selecting frame patched by ngram_mix_rows_kernel before the selection, plain or masked, and ngram_hist_advance_kernel behind every
+// merge but the last: hist[(k + 1) & 1] of the rows the merge wrote from hist[k & 1] of the rows it chose them from.
+extern "C" int jlm_complete_frames_ngram(const jlm_decode_model *m, const jlm_complete_plan *p, const jlm_complete_ngram_plan *np,
+                                         const unsigned *mask, int ld_mask, int n_sets, const int *prompt_set, void *stream,
+                                         void *const *events) {
+    if (!m || !p || !np || m->n_segs < 1) return -1;
+    if (prompt_set ? (n_sets < 0 || (n_sets > 0 && !mask)) : (mask != nullptr || n_sets != 0)) return -1;
+    const int NP = p->n_prompts, B = p->beam;
+    if (NP < 0 || B < 1 || (long long)NP * B > 0x7fffffff) return -1;
+    const int R = NP * B, V = m->segs[m->n_segs - 1].v_end;
+    JLM_TRY(jlm_ngram_mix_refuse(p->logits, p->ld_logits, V, np->table, np->hist[0], R, nullptr, np->lam, np->order, np->flags));
+    if (R > 0 && p->n_words > 1 && (!np->hist[1] || np->hist[1] == np->hist[0] || (((uintptr_t)np->hist[0] | (uintptr_t)np->hist[1]) & 7) != 0))
+        return -1;
+    return complete_frames(
+        m, p, mask, ld_mask, n_sets, prompt_set, stream, events,
+        [&](int k, int n_sel) -> int {
+            return jlm_ngram_mix_rows(p->logits, p->ld_logits, V, m->self_norm, np->table, np->hist[k & 1], n_sel, nullptr, np->lam, np->order,
+                                      np->flags, stream);
+        },
+        [&](int k, int n_sel) -> int {
+            if (k + 1 >= p->n_words) return 0;
+            return jlm_ngram_hist_advance(np->hist[k & 1], n_sel, p->prev_row, p->word, R, np->hist[(k + 1) & 1], stream);
+        });
 }

@@ -1180,13 +1180,14 @@ void beam_merge(const Tensor &cand_ids, const Tensor &cand_nll, int64_t beam, in
 // one int32.  Every id must lie in [0, V): the caller checks (jlm_amd/complete.py).  -> timed: [frames, 5] milliseconds per frame (LSTM
 // step, T projection, logit GEMMs, selection, merge) after waiting for the last frame; else an empty tensor and nothing waits.
 // complete_frames_masked (jlm_complete_frames_masked): the same with prompt p's first word restricted to set prompt_set[p] of `mask`.
-Tensor complete_frames_masked(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+// (ngram: the n-gram plan of complete_frames_ngram, or NULL -- then the entry points are complete_frames' / complete_frames_masked's)
+static Tensor complete_frames_any(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
                        const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
                        const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &cand_ids,
                        const Tensor &cand_nll, const Tensor &word, const Tensor &prev_row, const Tensor &score, const Tensor &finished,
                        int64_t stop_id, const Tensor &bp_parent, const Tensor &bp_word, const Tensor &bp_nll, const OptTensor &flags,
                        int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed, const OptTensor &mask,
-                       int64_t ld_mask, int64_t n_sets, std::vector<int64_t> prompt_set) {
+                       int64_t ld_mask, int64_t n_sets, std::vector<int64_t> prompt_set, const jlm_complete_ngram_plan *ngram) {
     const jlm_decode_model &m = model->m;
     const int64_t NP = n_prompts, B = beam, P = n_prompt, N = n_words, R = n_prompts * beam;
     TORCH_CHECK(NP >= 0 && B >= 1 && P >= 1 && N >= 0, "jlm.complete_frames: n_prompts >= 0, beam >= 1, n_prompt >= 1 and n_words >= 0");
@@ -1225,11 +1226,90 @@ Tensor complete_frames_masked(const c10::intrusive_ptr<JlmModel> &model, const T
     }
     const unsigned *mask_p = masked && n_sets > 0 ? ptr<const unsigned>(*mask, "mask") : nullptr;
     const int *sets_p = masked ? ptr<const int>(sets, "prompt_set") : nullptr;
+    if (ngram)
+        return launch_frames("jlm_complete_frames_ngram", h0.device().index(), timed, N > 0 && NP > 0 ? P + N - 1 : 0,
+                             JLM_COMPLETE_EVENTS_PER_FRAME, [&](hipStream_t st, void *const *ev) {
+                                 return jlm_complete_frames_ngram(&m, &p, ngram, mask_p, masked ? (int)ld_mask : 0, masked ? (int)n_sets : 0,
+                                                                  sets_p, st, ev);
+                             });
     return launch_frames(masked ? "jlm_complete_frames_masked" : "jlm_complete_frames", h0.device().index(), timed,
                          N > 0 && NP > 0 ? P + N - 1 : 0, JLM_COMPLETE_EVENTS_PER_FRAME, [&](hipStream_t st, void *const *ev) {
                              return masked ? jlm_complete_frames_masked(&m, &p, mask_p, (int)ld_mask, (int)n_sets, sets_p, st, ev)
                                            : jlm_complete_frames(&m, &p, st, ev);
                          });
+}
+
+Tensor complete_frames_masked(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
+                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &cand_ids,
+                       const Tensor &cand_nll, const Tensor &word, const Tensor &prev_row, const Tensor &score, const Tensor &finished,
+                       int64_t stop_id, const Tensor &bp_parent, const Tensor &bp_word, const Tensor &bp_nll, const OptTensor &flags,
+                       int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed, const OptTensor &mask,
+                       int64_t ld_mask, int64_t n_sets, std::vector<int64_t> prompt_set) {
+    return complete_frames_any(model, h0, c0, h1, c1, T, logits, ld_logits, rows, prev, prompt, n_live, std::move(n_live_host), cand_ids,
+                               cand_nll, word, prev_row, score, finished, stop_id, bp_parent, bp_word, bp_nll, flags, n_prompts, beam,
+                               n_prompt, n_words, timed, mask, ld_mask, n_sets, std::move(prompt_set), nullptr);
+}
+
+// The table of the n-gram row walk as tensors, checked, into a jlm_ngram_rows (include/jlm_hip.h; jlm_amd/ngram.py successor_tensors):
+// table = [uni_lp, uni_bow, bi_off, bi_w, bi_lp, tri_off, tri_w, tri_lp, tri_bow, ctx_keys (int64), ctx_vals], sizes = [n_bi, n_tri,
+// n_ctx, log2cap, max_probe]; an empty list is passed as a tensor of one element.
+struct NgramRowsArgs {
+    jlm_ngram_rows t{};
+    NgramRowsArgs(const char *op, const std::vector<Tensor> &table, const std::vector<int64_t> &sizes, int64_t V, int64_t order, double lam,
+                  const Tensor &like) {
+        TORCH_CHECK(table.size() == 11 && sizes.size() == 5, "jlm.", op, ": the n-gram table is 11 tensors and 5 sizes");
+        const int64_t n_bi = sizes[0], n_tri = sizes[1], n_ctx = sizes[2], log2cap = sizes[3], max_probe = sizes[4];
+        TORCH_CHECK(order >= 1 && order <= 3 && lam > 0.0 && lam < 1.0, "jlm.", op, ": n-gram order in 1 .. 3 and lam in (0, 1)");
+        TORCH_CHECK(V >= 1 && V <= JLM_NGRAM_MIX_MAX_V, "jlm.", op, ": the n-gram mixture over whole rows takes at most ", JLM_NGRAM_MIX_MAX_V,
+                    " words");
+        TORCH_CHECK(n_bi >= 0 && n_bi <= INT32_MAX && n_tri >= 0 && n_tri <= INT32_MAX && n_ctx >= 0 && n_ctx <= INT32_MAX && log2cap >= 6 &&
+                        log2cap <= 31 && max_probe >= 0 && max_probe < (int64_t(1) << log2cap),
+                    "jlm.", op, ": n-gram table sizes out of range");
+        for (const Tensor &x : table) TORCH_CHECK(x.defined() && x.device() == like.device(), "jlm.", op, ": the n-gram table lives on the call's device");
+        const int64_t one = 1, cap = int64_t(1) << log2cap;
+        TORCH_CHECK(is(table[0], at::kFloat, V) && is(table[1], at::kFloat, V) && is(table[2], at::kInt, V + 1) &&
+                        is(table[3], at::kInt, std::max(n_bi, one)) && is(table[4], at::kFloat, std::max(n_bi, one)) &&
+                        is(table[5], at::kInt, n_ctx + 1) && is(table[6], at::kInt, std::max(n_tri, one)) &&
+                        is(table[7], at::kFloat, std::max(n_tri, one)) && is(table[8], at::kFloat, std::max(n_ctx, one)) &&
+                        is(table[9], at::kLong, cap) && is(table[10], at::kInt, cap),
+                    "jlm.", op, ": float32 uni_lp / uni_bow [V], int32 bi_off [V + 1], bi_w / float32 bi_lp [n_bi], int32 tri_off [n_ctx + 1], "
+                    "tri_w / float32 tri_lp [n_tri], tri_bow [n_ctx], int64 ctx_keys / int32 ctx_vals [2^log2cap]");
+        t.uni_lp = ptr<const float>(table[0], "uni_lp"); t.uni_bow = ptr<const float>(table[1], "uni_bow");
+        t.bi_off = ptr<const int>(table[2], "bi_off"); t.bi_w = ptr<const int>(table[3], "bi_w"); t.bi_lp = ptr<const float>(table[4], "bi_lp");
+        t.n_bi = (int)n_bi;
+        t.tri_off = ptr<const int>(table[5], "tri_off"); t.tri_w = ptr<const int>(table[6], "tri_w");
+        t.tri_lp = ptr<const float>(table[7], "tri_lp"); t.tri_bow = ptr<const float>(table[8], "tri_bow");
+        t.n_tri = (int)n_tri; t.n_ctx = (int)n_ctx;
+        t.ctx_keys = ptr<const void>(table[9], "ctx_keys"); t.ctx_vals = ptr<const int>(table[10], "ctx_vals");
+        t.log2cap = (int)log2cap; t.max_probe = (int)max_probe;
+    }
+};
+
+// complete_frames / complete_frames_masked (mask None: the former) under the n-gram mixture (jlm_complete_frames_ngram, include/
+// jlm_hip.h): their arguments, then the table (NgramRowsArgs), order, lam, hist0 / hist1 int32 [n_prompts * beam][2] -- hist0's first
+// n_prompts rows the last two words of the prompts, -1 for no word --, ngram_flags one int32.
+Tensor complete_frames_ngram(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                       const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev,
+                       const Tensor &prompt, const Tensor &n_live, std::vector<int64_t> n_live_host, const Tensor &cand_ids,
+                       const Tensor &cand_nll, const Tensor &word, const Tensor &prev_row, const Tensor &score, const Tensor &finished,
+                       int64_t stop_id, const Tensor &bp_parent, const Tensor &bp_word, const Tensor &bp_nll, const OptTensor &flags,
+                       int64_t n_prompts, int64_t beam, int64_t n_prompt, int64_t n_words, bool timed, const OptTensor &mask,
+                       int64_t ld_mask, int64_t n_sets, std::vector<int64_t> prompt_set, std::vector<Tensor> table, std::vector<int64_t> sizes,
+                       int64_t order, double lam, const Tensor &hist0, const Tensor &hist1, const OptTensor &ngram_flags) {
+    const jlm_decode_model &m = model->m;
+    TORCH_CHECK(m.n_segs >= 1, "jlm.complete_frames_ngram: a model without segments");
+    const NgramRowsArgs tab("complete_frames_ngram", table, sizes, m.segs[m.n_segs - 1].v_end, order, lam, logits);
+    const int64_t R = n_prompts * beam;
+    TORCH_CHECK(n_prompts >= 0 && beam >= 1 && is(hist0, at::kInt, 2 * R) && is(hist1, at::kInt, 2 * R) && opt_ok(ngram_flags, at::kInt, 1) &&
+                    (R == 0 || hist0.data_ptr() != hist1.data_ptr()),
+                "jlm.complete_frames_ngram: two different int32 hist buffers [n_prompts * beam][2], int32 ngram_flags");
+    jlm_complete_ngram_plan np{};
+    np.table = &tab.t; np.order = (int)order; np.lam = (float)lam;
+    np.hist[0] = ptr<int>(hist0, "hist0"); np.hist[1] = ptr<int>(hist1, "hist1"); np.flags = optr<int>(ngram_flags, "ngram_flags");
+    return complete_frames_any(model, h0, c0, h1, c1, T, logits, ld_logits, rows, prev, prompt, n_live, std::move(n_live_host), cand_ids,
+                               cand_nll, word, prev_row, score, finished, stop_id, bp_parent, bp_word, bp_nll, flags, n_prompts, beam,
+                               n_prompt, n_words, timed, mask, ld_mask, n_sets, std::move(prompt_set), &np);
 }
 
 Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
@@ -1241,6 +1321,35 @@ Tensor complete_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &
     return complete_frames_masked(model, h0, c0, h1, c1, T, logits, ld_logits, rows, prev, prompt, n_live, std::move(n_live_host), cand_ids,
                                   cand_nll, word, prev_row, score, finished, stop_id, bp_parent, bp_word, bp_nll, flags, n_prompts, beam,
                                   n_prompt, n_words, timed, c10::nullopt, 0, 0, {});
+}
+
+// rank_frames under the n-gram mixture (jlm_rank_ngram_frames, include/jlm_hip.h): its arguments, then the table (NgramRowsArgs), order,
+// lam, hist int32 [n_steps][n_rows][2] on the device, top_k with top_ids int32 / top_nll float64 [n_steps][n_rows][top_k] (top_k = 0:
+// none), ngram_flags one int32.  -> timed: [n_steps, 5] milliseconds per step (LSTM step, T projection, logit GEMMs, n-gram patch,
+// ranking with the lists); else an empty tensor.
+Tensor rank_ngram_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                         const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0,
+                         const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host, const OptTensor &ids,
+                         const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels, const Tensor &rank,
+                         const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed, std::vector<Tensor> table,
+                         std::vector<int64_t> sizes, int64_t order, double lam, const Tensor &hist, int64_t top_k, const OptTensor &top_ids,
+                         const OptTensor &top_nll, const OptTensor &ngram_flags) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    const RankPlanArgs rp("rank_ngram_frames", m, h0, c0, h1, c1, T, logits, ld_logits, rows, prev0, word, target, n_live, n_live_host, ids,
+                          lv_off, lv_lo, lv_hi, n_levels, rank, flags, R, S);
+    const NgramRowsArgs tab("rank_ngram_frames", table, sizes, rp.V, order, lam, logits);
+    TORCH_CHECK(is(hist, at::kInt, S * R * 2) && opt_ok(ngram_flags, at::kInt, 1),
+                "jlm.rank_ngram_frames: int32 hist [n_steps][n_rows][2], int32 ngram_flags");
+    TORCH_CHECK(top_k >= 0 && top_k <= JLM_TOPK_MAX && top_k <= rp.V &&
+                    (top_k == 0 || (has(top_ids) && has(top_nll) && is(*top_ids, at::kInt, S * R * top_k) && is(*top_nll, at::kDouble, S * R * top_k))),
+                "jlm.rank_ngram_frames: top_k in 0 .. min(", JLM_TOPK_MAX, ", V) with int32 top_ids / float64 top_nll [n_steps][n_rows][top_k]");
+    jlm_ngram_mix_plan np{};
+    np.table = &tab.t; np.order = (int)order; np.lam = (float)lam; np.hist = ptr<const int>(hist, "hist"); np.top_k = (int)top_k;
+    np.top_ids = top_k > 0 ? ptr<int>(*top_ids, "top_ids") : nullptr; np.top_nll = top_k > 0 ? ptr<double>(*top_nll, "top_nll") : nullptr;
+    np.flags = optr<int>(ngram_flags, "ngram_flags");
+    return launch_frames("jlm_rank_ngram_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_NGRAM_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_rank_ngram_frames(&m, &rp.p, &np, st, ev); });
 }
 
 // scalar k-means compression of one tensor (jlm_kmeans1d, include/jlm_hip.h): x float32 [n], code uint8 [n], codebook float32 [2^bit],
@@ -1594,6 +1703,19 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(m!) bp_parent, Tensor(n!) bp_word, Tensor(o!) bp_nll, Tensor(p!)? flags, int n_prompts, int beam, int n_prompt, int n_words, "
           "bool timed, Tensor? mask, int ld_mask, int n_sets, int[] prompt_set) -> Tensor",
           complete_frames_masked);
+    m.def("complete_frames_ngram(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, "
+          "Tensor(e!)? T, Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev, Tensor prompt, Tensor n_live, int[] n_live_host, "
+          "Tensor(g!) cand_ids, Tensor(h!) cand_nll, Tensor(i!) word, Tensor(j!) prev_row, Tensor(k!) score, Tensor(l!) finished, int stop_id, "
+          "Tensor(m!) bp_parent, Tensor(n!) bp_word, Tensor(o!) bp_nll, Tensor(p!)? flags, int n_prompts, int beam, int n_prompt, int n_words, "
+          "bool timed, Tensor? mask, int ld_mask, int n_sets, int[] prompt_set, Tensor[] table, int[] sizes, int order, float lam, "
+          "Tensor(q!) hist0, Tensor(r!) hist1, Tensor(s!)? ngram_flags) -> Tensor",
+          complete_frames_ngram);
+    m.def("rank_ngram_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, int[] n_live_host, "
+          "Tensor? ids, Tensor? lv_off, Tensor? lv_lo, Tensor? lv_hi, int n_levels, Tensor(g!) rank, Tensor(h!)? flags, int n_rows, "
+          "int n_steps, bool timed, Tensor[] table, int[] sizes, int order, float lam, Tensor hist, int top_k, Tensor(i!)? top_ids, "
+          "Tensor(j!)? top_nll, Tensor(k!)? ngram_flags) -> Tensor",
+          rank_ngram_frames);
     m.def("kmeans1d(Tensor x, int bit, int seed, int max_iter, float tol, Tensor(a!) code, Tensor(b!) codebook, Tensor(c!) scratch, int grid, "
           "bool timed) -> Tensor",
           kmeans1d);

@@ -1024,6 +1024,26 @@ class LSTM_Model():
         from .cache import rank_cached
         return rank_cached(self._ranker(), sequences, start, cache, self._rank_levels(readings, max_prefix), max_rows)
 
+    def rank_streams_ngram(self, inputs, targets, ngram, h=None, c=None, tail=None, readings=True, max_prefix=8, top=0):
+        """rank_streams under a back-off n-gram mixture (jlm_amd/ngram_mix.py): every step's full-vocabulary
+        logits are patched on the device into the logits of p = (1 - lam) p_lm + lam q(. | the stream's last two words) before the
+        target is ranked.  ``ngram``: a :class:`jlm_amd.ngram.NGramMix`; ``tail``: int [B, 2], the last two words before
+        inputs[:, 0], -1 meaning none (None: the stream starts here).  -> :class:`jlm_amd.ngram_mix.NgramRanks`: ``ranks``
+        [B, n, max_prefix + 3] in rank()'s columns, ``top_ids`` / ``top_logp`` [B, n, top] (the ``top`` <= 64 most probable words of
+        every step and their log p under the mixture; None for top = 0), and ``h``, ``c``, ``tail`` to carry: a stream cut any way
+        into calls gives the same ranks and lists.  On ordinary models the lists' log p is that of the row-normalised mixture
+        p / ((1 - lam) + lam Z_h), Z_h = sum_w exp q(w | h): p itself for a table that sums to one, as jlm_amd.ngram.estimate's do,
+        and off by a constant per row -- no rank and no order changes -- for a file whose out-of-vocabulary n-grams were dropped.
+        ValueError before anything runs for a bad argument, a table with a word id >= V, or V > 393 216 (the kernel's bitmap)."""
+        from .ngram_mix import rank_streams_ngram
+        return rank_streams_ngram(self._ranker(), inputs, targets, ngram, h, c, tail, self._rank_levels(readings, max_prefix), top)
+
+    def rank_ngram(self, sequences, start, ngram, readings=True, max_prefix=8, max_rows=None):
+        """rank() under a back-off n-gram mixture: the history of s[t] is (start, s[0 .. t - 1]), its last two words in use; rank()'s
+        row plan.  -> per sequence an int32 [len, max_prefix + 3] array, rank()'s columns."""
+        from .ngram_mix import rank_ngram
+        return rank_ngram(self._ranker(), sequences, start, ngram, self._rank_levels(readings, max_prefix), max_rows)
+
     def predict_next_cached(self, h, state, cache, n=10, allowed=None):
         """The ``n`` most probable next words of B streams under the continuous cache, from what a stream call left: ``h`` the carried
         state [B, H] (device tensor, as rank_streams_cached / score_streams_cached return it), ``state`` their CacheState (None: an
@@ -1065,38 +1085,47 @@ class LSTM_Model():
         index = self.reading_index()
         return [index.lookup(r, exact=exact) for r in readings]
 
-    def predict_top(self, contexts, n=10, max_rows=None, allowed=None):
+    def predict_top(self, contexts, n=10, max_rows=None, allowed=None, ngram=None):
         """The ``n`` most probable next words after each context, on the device (jlm_amd/complete.py; the reference's
         find_top_N(predict(...), N), model.py:25-26, without the host-side softmax and argsort).  ``contexts``: word-id lists of length
         >= 1, each consumed from the zero state as generate() consumes a prompt.  -> per context (ids int64 [n], logp float64 [n]),
         most probable first, equal logits lower id first; logp = y - lse (self_norm: y).  1 <= n <= min(64, V).
         ``allowed``: None, or per context None or an array of word ids: that context's words are chosen among these only (the masked
         selection, csrc topk_rows_masked_kernel), and its result has min(n, size of the set) entries -- none, without reaching the
-        device, for an empty set.  logp stays y - lse over the WHOLE vocabulary: it is not renormalised over the set."""
+        device, for an empty set.  logp stays y - lse over the WHOLE vocabulary: it is not renormalised over the set.
+        ``ngram``: None, or a :class:`jlm_amd.ngram.NGramMix`: the words are ranked, and logp is taken, under the mixture
+        (1 - lam) p_lm + lam q(. | the context's last two words) -- rank_streams_ngram's distribution and its note on tables that do
+        not sum to one.  None calls exactly the op it called before."""
         from .complete import predict_top
-        return predict_top(self._completer(), contexts, n, max_rows, allowed)
+        return predict_top(self._completer(), contexts, n, max_rows, allowed, ngram)
 
-    def predict_reading(self, contexts, readings, n=10, exact=False, max_rows=None):
+    def predict_reading(self, contexts, readings, n=10, exact=False, max_rows=None, ngram=None):
         """predict_top among the words whose reading starts with (``exact``: equals) ``readings[i]``, one string per context, hiragana
-        or katakana -- what a predictive keyboard asks at every keystroke.  The sets come from reading_index()."""
-        return self.predict_top(contexts, n, max_rows, allowed=self._reading_sets(readings, len(contexts), exact))
+        or katakana -- what a predictive keyboard asks at every keystroke.  The sets come from reading_index().  ``ngram``:
+        predict_top's."""
+        return self.predict_top(contexts, n, max_rows, allowed=self._reading_sets(readings, len(contexts), exact), ngram=ngram)
 
-    def complete_reading(self, prompts, readings, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, exact=False):
+    def complete_reading(self, prompts, readings, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, exact=False, ngram=None):
         """complete() with the first generated word of prompt i chosen among the words whose reading starts with (``exact``: equals)
-        ``readings[i]``; the later words are free."""
+        ``readings[i]``; the later words are free.  ``ngram``: complete's."""
         return self.complete(prompts, n_words, beam_width, n_best, stop_id, max_rows,
-                             first_allowed=self._reading_sets(readings, len(prompts), exact))
+                             first_allowed=self._reading_sets(readings, len(prompts), exact), ngram=ngram)
 
-    def complete(self, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, first_allowed=None):
+    def complete(self, prompts, n_words, beam_width=10, n_best=None, stop_id=None, max_rows=None, first_allowed=None, ngram=None):
         """Deterministic beam search over the LM, separately for each prompt (jlm_amd/complete.py).  A hypothesis's score is its summed
         -log p (f64); each frame keeps the ``beam_width`` best by (score, parent's rank, word id); with ``stop_id`` a hypothesis ending
         in it is finished and carried unchanged.  -> per prompt ``n_best`` (default beam_width) tuples (ids int64, nll float64 per
         word, total), total ascending.  ValueError for a bad argument before anything runs; JlmHipError when the device flags a
         non-finite logit or log-normaliser.  ``first_allowed``: None, or per prompt None or an array of word ids the FIRST generated
         word is chosen among (later words are free).  A set smaller than the beam leaves fewer first words than ranks; hypotheses
-        whose total is not finite are dropped, so such a prompt may return fewer than ``n_best`` results, and an empty set gives []."""
+        whose total is not finite are dropped, so such a prompt may return fewer than ``n_best`` results, and an empty set gives [].
+        ``ngram``: None, or a :class:`jlm_amd.ngram.NGramMix`: every word of every hypothesis is chosen and scored under the mixture
+        (1 - lam) p_lm + lam q(. | h), h the last two words of the prompt followed by the hypothesis's own (the device carries them
+        behind every merge).  On a self-normalised model the beam compares -y' and -log1p(-lam) a word is added to the results, so
+        with ``stop_id`` a finished hypothesis is compared without the words it does not have.  None calls exactly the op it called
+        before."""
         from .complete import complete
-        return complete(self._completer(), prompts, n_words, beam_width, n_best, stop_id, max_rows, first_allowed)
+        return complete(self._completer(), prompts, n_words, beam_width, n_best, stop_id, max_rows, first_allowed, ngram)
 
 
 def show_prob(model, w2i, inputs):

@@ -73,16 +73,18 @@ class NGramTable:
         self.keys, self.lp, self.bow, self.order = keys[at], lp[at], bow[at], int(order)
         self._dev = {}                   # device -> (keys, vals) tensors (jlm_amd/engine.py), made once
         self._arrays = {}
+        self._succ = {}                  # V -> successor_arrays(V)
+        self._max_id = None
 
     def __len__(self):
         return int(self.keys.shape[0])
 
     @property
     def max_id(self):
-        """the largest word id of any n-gram (-1: an empty table)"""
-        if not len(self):
-            return -1
-        return int(max(((self.keys >> sh) & 0x1FFFFF).max() for sh in (0, 21, 42))) - 1
+        """the largest word id of any n-gram (-1: an empty table); found once -- every call under the mixture asks (check_mix)"""
+        if self._max_id is None:
+            self._max_id = int(max(((self.keys >> sh) & 0x1FFFFF).max() for sh in (0, 21, 42))) - 1 if len(self) else -1
+        return self._max_id
 
     def rounded(self):
         """the table the device holds: every value the float32 nearest to it (what ``from_srilm`` returns is rounded already)"""
@@ -180,6 +182,66 @@ class NGramTable:
         vals[at, 0], vals[at, 1] = self.lp.astype(np.float32), self.bow.astype(np.float32)
         out = dict(keys=keys, vals=vals, log2cap=log2cap, max_probe=int(max_probe))
         self._arrays[memo] = out
+        return out
+
+    # ---------------------------------------------------------------------------------------------- the row walk's arrays
+    def successor_arrays(self, V):
+        """The layout csrc/jlm_ngram_mix.hip walks to form q(. | history) over ALL V words of a row, float32
+        values, made once per V:
+
+        ``uni_lp`` [V] (-inf without a unigram), ``uni_bow`` [V] (0 where absent); the bigrams in CSR by context word, in the table's
+        ascending key order: ``bi_off`` int32 [V + 1], ``bi_w`` int32, ``bi_lp``, ``bi_bow`` (bow(v w), 0 where absent); the trigrams
+        in CSR by distinct context (u, v): ``tri_off`` int32 [n_ctx + 1], ``tri_w`` int32, ``tri_lp``, and ``tri_bow`` [n_ctx] =
+        bow(u v).  A context is every (u, v) that has a trigram successor or is a bigram with a back-off weight other than 0, so a
+        weight without successors is found as one with them.  ``ctx_keys`` uint64 / ``ctx_vals`` int32 [2^log2cap]: the map from
+        (v + 1) | (u + 1) << 21 to the context's index in :meth:`device_arrays`' scheme (the same hash, linear probing, insertion
+        in ascending key order, ``max_probe`` the longest displacement); an empty slot holds key 0.  The bytes are deterministic.
+        ValueError for a word id >= V."""
+        V = int(V)
+        if V in self._succ:
+            return self._succ[V]
+        if not 1 <= V <= MAX_ID + 1:
+            raise ValueError("V is 1 .. %d" % (MAX_ID + 1))
+        if self.max_id >= V:
+            raise ValueError("the n-gram table holds word id %d, the row walk was asked for %d words" % (self.max_id, V))
+        f32, M = np.float32, (1 << 21) - 1
+        n1, n2 = np.searchsorted(self.keys, [1 << 21, 1 << 42])
+        uni_lp, uni_bow = np.full(V, -np.inf, dtype=f32), np.zeros(V, dtype=f32)
+        w1 = self.keys[:n1] - 1
+        uni_lp[w1], uni_bow[w1] = self.lp[:n1].astype(f32), self.bow[:n1].astype(f32)
+        k2, k3 = self.keys[n1:n2], self.keys[n2:]
+        bi_off = np.zeros(V + 1, dtype=np.int64)
+        np.cumsum(np.bincount((k2 >> 21) - 1, minlength=V), out=bi_off[1:])
+        weighted = k2[self.bow[n1:n2] != 0.0]
+        ctx = np.union1d(k3 >> 21, weighted)                               # ascending, distinct
+        tri_off = np.zeros(ctx.size + 1, dtype=np.int64)
+        np.cumsum(np.bincount(np.searchsorted(ctx, k3 >> 21), minlength=ctx.size), out=tri_off[1:])
+        tri_bow = np.zeros(ctx.size, dtype=f32)
+        at = np.searchsorted(k2, ctx)
+        has = (at < k2.size) & (k2[np.minimum(at, max(k2.size - 1, 0))] == ctx) if k2.size else np.zeros(ctx.size, dtype=bool)
+        tri_bow[has] = self.bow[n1:n2][at[has]].astype(f32)
+        log2cap = 6
+        while (1 << log2cap) < 2 * ctx.size:
+            log2cap += 1
+        cap, mask = 1 << log2cap, (1 << log2cap) - 1
+        home = ((ctx.astype(np.uint64) * np.uint64(GOLDEN)) >> np.uint64(64 - log2cap)).astype(np.int64).tolist()
+        used, slot_of, max_probe = bytearray(cap), [0] * ctx.size, 0
+        for i, s in enumerate(home):
+            d = 0
+            while used[s]:
+                s = (s + 1) & mask
+                d += 1
+            used[s] = 1
+            slot_of[i] = s
+            max_probe = max(max_probe, d)
+        ctx_keys, ctx_vals = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.int32)
+        at = np.asarray(slot_of, dtype=np.int64)
+        ctx_keys[at], ctx_vals[at] = ctx.astype(np.uint64), np.arange(ctx.size, dtype=np.int32)
+        out = dict(V=V, uni_lp=uni_lp, uni_bow=uni_bow, bi_off=bi_off.astype(np.int32), bi_w=((k2 & M) - 1).astype(np.int32),
+                   bi_lp=self.lp[n1:n2].astype(f32), bi_bow=self.bow[n1:n2].astype(f32), tri_off=tri_off.astype(np.int32),
+                   tri_w=((k3 & M) - 1).astype(np.int32), tri_lp=self.lp[n2:].astype(f32), tri_bow=tri_bow, ctx_keys=ctx_keys,
+                   ctx_vals=ctx_vals, log2cap=log2cap, max_probe=int(max_probe), n_ctx=int(ctx.size))
+        self._succ[V] = out
         return out
 
     # ---------------------------------------------------------------------------------------------- the file
@@ -330,6 +392,64 @@ def mixture_nll(nll, logq, lam):
     """-log((1 - lam) exp(-nll) + lam exp(logq)) elementwise in float64 (the host form of the mixture's perplexity)"""
     nll, logq = np.asarray(nll, dtype=np.float64), np.asarray(logq, dtype=np.float64)
     return -np.logaddexp(math.log1p(-lam) - nll, math.log(lam) + logq)
+
+
+def mixed_logits(table, history, y, lam, self_norm=False):
+    """The logits of the mixture (1 - lam) p_lm + lam exp(q(. | history)) over a whole row, in float64: with
+    L = lse(y), or 0 on self-normalised models, and rho = lam / (1 - lam),
+
+        y'[w] = logaddexp(y[w], L + log rho + q(w | history))     where q is finite (y[w] = -inf gives the finite n-gram term)
+        y'[w] = y[w]                                              where q = -inf
+
+    so that (1 - lam) exp(y' - L) is the mixture.  ``history``: the word ids before the row's word, oldest first (``table.context``
+    takes the last order - 1 of them); ``table`` holds the float32 values the device holds (``NGramMix.table``).  On ordinary models
+    the selection kernels report lse(y') - y'[w]: -log of the ROW-NORMALISED mixture p_mix(w) / ((1 - lam) + lam Z_h), Z_h = sum_w
+    exp q(w | h).  That is p_mix itself for a table that sums to one, as ``estimate``'s do; for a file whose out-of-vocabulary
+    n-grams were dropped it differs by a constant per row.  On self-normalised models they report -y', and the host adds
+    -log1p(-lam)."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    lam = float(lam)
+    if not 0.0 < lam < 1.0:
+        raise ValueError("the weight of the n-gram model lies in (0, 1) (got %r)" % (lam,))
+    history = [int(x) for x in history]
+    gaps = [i for i, x in enumerate(history) if x < 0]
+    if gaps:                                                               # -1: no word there, and none before it
+        history = history[gaps[-1] + 1:]
+    q = table.logq_all(history, y.shape[0])
+    if self_norm:
+        L = 0.0
+    else:
+        m = y.max()
+        L = m + math.log(np.exp(y - m).sum())
+    out = y.copy()
+    at = np.isfinite(q)
+    out[at] = np.logaddexp(y[at], L + (math.log(lam) - math.log1p(-lam)) + q[at])
+    return out
+
+
+SUCCESSOR_TENSORS = ("uni_lp", "uni_bow", "bi_off", "bi_w", "bi_lp", "tri_off", "tri_w", "tri_lp", "tri_bow", "ctx_keys", "ctx_vals")
+MIX_MAX_V = 393216                       # JLM_NGRAM_MIX_MAX_V (include/jlm_hip.h): the patched-word bitmap of a row takes 48 KB of LDS
+
+
+def successor_tensors(table, V, device):
+    """-> (dict of the device tensors of ``table.successor_arrays(V)`` in the order of SUCCESSOR_TENSORS -- ctx_keys as int64 --, the
+    arrays), made once per (table, V, device) and kept beside ``DecodeEngine.ngram_tensors``' on the table"""
+    import torch
+    key = ("rows", int(V), device.type, device.index)
+    if key not in table._dev:
+        arr = table.successor_arrays(V)
+        # (an empty list is uploaded as one zero: the launcher refuses a null pointer, the lengths travel beside the tensors)
+        up = lambda a: torch.from_numpy((a.view(np.int64) if a.dtype == np.uint64 else a) if a.size else np.zeros(1, a.dtype)).to(device)
+        table._dev[key] = ({name: up(arr[name]) for name in SUCCESSOR_TENSORS}, arr)
+    return table._dev[key]
+
+
+def check_mix_rows(ngram, V):
+    """``check_mix`` for a call that patches whole rows: also ValueError for a vocabulary whose bitmap the kernel cannot hold"""
+    check_mix(ngram, V)
+    if int(V) > MIX_MAX_V:
+        raise ValueError("the n-gram mixture over whole rows takes at most %d words (the model has %d)" % (MIX_MAX_V, int(V)))
+    return ngram
 
 
 def stream_logq(table, ids, eos=1):

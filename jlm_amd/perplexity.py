@@ -22,7 +22,9 @@ after every line; a character model (config char_rnn) reads the characters of th
                    as well -- and print the cached perplexity after the plain one.  --tune-cache FILE sweeps --thetas and --lams on
                    FILE, the dev set, prints the grid's best pair and reports the test perplexity at that pair.  Without --cache the
                    output is what it was.  With --ranks as well (N <= 4096), a second --ranks line "with cache" over the same tokens,
-                   at the theta and lam the cached perplexity is reported at (LSTM_Model.rank_streams_cached).
+                   at the theta and lam the cached perplexity is reported at (LSTM_Model.rank_streams_cached).  With --ngram FILE
+                   as well, a --ranks line "with n-gram" at the lambda the mixture's perplexity is reported at (--ngram-lam, or
+                   --tune-ngram's pick): LSTM_Model.rank_streams_ngram patches every step's logits on the device.
   --dynamic        stream mode: after the static line, the dynamically evaluated perplexity (jlm_amd/dyneval.py): the stream read in
                    chunks of -b (default 1) x --de-steps tokens, each scored and then learnt from by --de-rule at --de-lr and --de-lam.
                    Rule rms takes its gradient statistics over --de-stat-chunks chunks of data/train.txt.  --tune-dynamic FILE sweeps
@@ -147,16 +149,21 @@ def sentence_ranks(model, sents, eos, readings, max_prefix):
     return (np.concatenate(ranks) if ranks else np.zeros((0, width), dtype=np.int32)), np.array([t for s in sents for t in s], dtype=np.int64)
 
 
-def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix, spec=None):
+def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix, spec=None, ngram=None):
     """-> (ranks [tokens, columns], the targets [tokens]) over the corpus_iterator chunks, state carried, as stream_perplexity;
-    ``spec``: a CacheSpec -- the ranks under the continuous cache (LSTM_Model.rank_streams_cached), the cache carried too"""
+    ``spec``: a CacheSpec -- the ranks under the continuous cache (LSTM_Model.rank_streams_cached), the cache carried too; ``ngram``:
+    an NGramMix -- the ranks under the n-gram mixture (LSTM_Model.rank_streams_ngram), the streams' last two words carried too; a row's
+    first token has the history of its one input word, exactly as stream_ngram_scores gives it to the mixture's perplexity"""
     from .score import stream_layout
     x, y = stream_layout(stream, batch_size, num_steps)
-    h = c = state = None
+    h = c = state = tail = None
     out = []
     for i in range(x.shape[1] // num_steps):
         cols = slice(i * num_steps, (i + 1) * num_steps)
-        if spec is None:
+        if ngram is not None:
+            res = model.rank_streams_ngram(x[:, cols], y[:, cols], ngram, h, c, tail, readings=readings, max_prefix=max_prefix)
+            r, h, c, tail = res.ranks, res.h, res.c, res.tail
+        elif spec is None:
             r, h, c = model.rank_streams(x[:, cols], y[:, cols], h, c, readings=readings, max_prefix=max_prefix)
         else:
             res = model.rank_streams_cached(x[:, cols], y[:, cols], spec, h, c, state, readings=readings, max_prefix=max_prefix)
@@ -354,6 +361,11 @@ def main(argv=None, de_stepper=None):
         if spec is not None:
             ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix, spec)
             print("with cache (N {} theta {} lam {}): ".format(spec.size, spec.theta, spec.lam) +
+                  ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
+        if args.ngram:
+            from .ngram import NGramMix
+            ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix, ngram=NGramMix(table, ng_lam))
+            print("with n-gram (order {} lam {}): ".format(table.order, ng_lam) +
                   ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
     return pp
 

@@ -89,12 +89,15 @@ class Ranker:
                 self._levels[key] = Levels(self.m, index, int(max_prefix))
         return self._levels[key]
 
-    def row_bytes(self, n_steps, n_levels, cache_size=0, top=0):
-        """the bytes a row of a call takes; ``cache_size`` > 0: with the rings and the score scratch of a cached call"""
+    def row_bytes(self, n_steps, n_levels, cache_size=0, top=0, ngram=False):
+        """the bytes a row of a call takes; ``cache_size`` > 0: with the rings and the score scratch of a cached call; ``ngram``: with
+        the histories [n_steps, 2] int32 (and ``top`` lists) of a call under the n-gram mixture"""
         m = self.m
         base = (rowsets.ld_logits(m.V) + 4 * m.H + m.ldt) * 4 + n_steps * (8 + 4 * (n_levels + 1)) + 32
         if cache_size:
             base += MixRings.row_bytes(m.H, cache_size, n_steps, top)
+        if ngram:
+            base += n_steps * (8 + 12 * top)
         return base
 
     def run(self, word, target, n_live, h=None, c=None, levels=None, timed=False, rings=None):
@@ -103,7 +106,8 @@ class Ranker:
         levels: a :class:`Levels`, None = level A only.  rings: a :class:`jlm_amd.cache.MixRings` made for this call's (R, n_steps) --
         the op is then ``rank_cache_frames``: every step's logits are patched into the mixed distribution of the continuous cache
         before they are ranked, the rings' ``top`` best words of every step go to the rings' lists, and last_step_ms has six columns
-        (the cache's query and patch between the logit GEMMs and the ranking).  -> (rank [n_steps, R, n_levels + 1] int32 in the device's column order, -1
+        (the cache's query and patch between the logit GEMMs and the ranking); a :class:`jlm_amd.ngram_mix.NgramPatch`: the op is
+        ``rank_ngram_frames``, the patch is the n-gram mixture's and last_step_ms has five columns.  -> (rank [n_steps, R, n_levels + 1] int32 in the device's column order, -1
         where a row is not live, h, c) -- the state after the last step stays on the device; as in Scorer.run, only the rows live
         at the last step are defined in it."""
         torch, m = self.torch, self.m
@@ -117,7 +121,7 @@ class Ranker:
             if rings is None:
                 ms = _ops.backend().rank_frames(*args)
             else:
-                ms = _ops.backend().rank_cache_frames(*args, *rings.op_args(R, S))
+                ms = getattr(_ops.backend(), rings.op)(*args, *rings.op_args(R, S))
             if timed:
                 self.last_step_ms = ms.numpy()
             if rings is not None:
@@ -127,15 +131,16 @@ class Ranker:
             out = rank.cpu().numpy()
         return (out,) + rs.after(S)
 
-    def sentences(self, sequences, start, levels, max_rows, limit, spec=None):
-        """rank_sequences, and with ``spec`` (a checked CacheSpec) jlm_amd.cache.rank_cached: every chunk with rings of its own"""
+    def sentences(self, sequences, start, levels, max_rows, limit, spec=None, patch=None):
+        """rank_sequences, and with ``spec`` (a checked CacheSpec) jlm_amd.cache.rank_cached: every chunk with rings of its own; with
+        ``patch`` (word [S, R] -> a jlm_amd.ngram_mix.NgramPatch) jlm_amd.ngram_mix.rank_ngram: every chunk with its histories"""
         L = levels.n_levels if levels is not None else 0
 
         def run(ch, word, target, lens):
-            rings = MixRings(self.m, spec, len(lens), ch["n_steps"]) if spec else None
+            rings = MixRings(self.m, spec, len(lens), ch["n_steps"]) if spec else patch(word) if patch else None
             rk = self.run(word, target, ch["n_live"], levels=levels, rings=rings)[0]
             return [_columns(levels, rk[:n, r, :], target[:n, r]) for r, n in enumerate(lens)]
-        return sentence_loop(self.m, sequences, start, "rank", max_rows, limit, lambda n: self.row_bytes(n, L, spec.size if spec else 0),
+        return sentence_loop(self.m, sequences, start, "rank", max_rows, limit, lambda n: self.row_bytes(n, L, spec.size if spec else 0, ngram=patch is not None),
                              lambda n: np.full((n, L + 1), -1, dtype=np.int32), run)
 
     def streams(self, x, y, h, c, levels, rings=None):
