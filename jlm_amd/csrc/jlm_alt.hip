@@ -5,9 +5,9 @@
 // log-normalisers, row g = frame * rmax + s * beam + k.  Path `rank` of sentence s is the chain g_K, bp[g_K], ... down to the root g_0
 // (bp = -1), walked here from the final row sent_len[s] * rmax + s * beam + rank: no pool row index comes from the host.  A row r of the
 // call names (sentence, depth d = k - 1, word a): word a put into segment k of that path.  For it the kernel
-//   1. forms logit(T[g_d], a) in wordlist_kernel's arithmetic (csrc/jlm_beam.hip) statement for statement -- 8 lanes per word, lane
-//      `sub` takes the 16-byte pieces sub + 8 c of the weight row in order as one fmaf chain, xor butterfly over 1, 2, 4, then + b2[a] --
-//      so it is bit-equal to what jlm_edge_logits gives for that (row, word), as tail_predict_kernel's (csrc/jlm_tail.hip);
+//   1. forms logit(T[g_d], a) with wl_lookup and wl_dot of csrc/jlm_wordlist_dot.h, the functions wordlist_kernel (csrc/jlm_beam.hip)
+//      and tail_predict_kernel (csrc/jlm_tail.hip) call, then + b2[a] -- so it is bit-equal to what jlm_edge_logits gives for that
+//      (row, word);
 //   2. seeds the accumulator jlm_score_frames adds the suffix terms to:  nll_seq[r] = head + (score[g_K] - score[g_{k+j}])  in f64,
 //      head = score[g_d] + lse[g_d] - logit (mode 1, self-normalised: score[g_d] - logit), j = the row's suffix steps = the number of
 //      steps t with n_live[t] > r;
@@ -15,6 +15,7 @@
 // The path's T rows are staged AH_ROWS depths at a time: LDS is AH_ROWS rows of T, the path (n_frames entries) and the live counts,
 // whatever the beam.  Plain vector loads and stores, one writer per address, no atomics but the flag word's OR.
 #include "jlm_common.h"
+#include "jlm_wordlist_dot.h"
 
 #define AH_THREADS 256
 #define AH_ROWS 16                                 // path rows staged per pass
@@ -117,47 +118,10 @@ __global__ __launch_bounds__(AH_THREADS) void alt_head_kernel(AltArgs a) {
             const bool broken = r >= 0 && (d < 0 || d >= K || d + 1 + j > K);       // fewer segments than the row's depth
             const bool valid = r >= 0 && !broken && d >= d0 && d < d0 + nr;
             const int w = valid ? a.alt[r] : -1;
-            int K4 = 0, toff = 0;
-            bool found = false;
-            const f32x4 *brow = nullptr;
-            if (valid) {
-                for (int si = 0; si < a.segs.n; ++si)
-                    if (w >= a.segs.s[si].v_start && w < a.segs.s[si].v_end) {
-                        K4 = a.segs.s[si].k >> 2;
-                        toff = a.segs.s[si].t_off;
-                        brow = reinterpret_cast<const f32x4 *>(a.segs.s[si].B + (size_t)(w - a.segs.s[si].v_start) * a.segs.s[si].ldb);
-                        found = true;
-                    }
-            }
-            const float *trow = sm + (size_t)(valid ? d - d0 : 0) * ldt + toff;
-            float acc = 0.0f;
-            f32x4 bv[8];
-#pragma unroll
-            for (int c8 = 0; c8 < 8; ++c8) {
-                const int kc = sub + 8 * c8;
-                bv[c8] = (kc < K4 && kc < 64) ? brow[kc] : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int c8 = 0; c8 < 8; ++c8) {
-                const int kc = sub + 8 * c8;
-                if (kc >= K4 || kc >= 64) continue;
-                const f32x4 tv = *reinterpret_cast<const f32x4 *>(trow + kc * 4);
-                acc = fmaf(bv[c8][0], tv[0], acc);
-                acc = fmaf(bv[c8][1], tv[1], acc);
-                acc = fmaf(bv[c8][2], tv[2], acc);
-                acc = fmaf(bv[c8][3], tv[3], acc);
-            }
-            for (int kc = sub + 64; kc < K4; kc += 8) {            // k > 256 (untied models)
-                const f32x4 bw = brow[kc];
-                const f32x4 tv = *reinterpret_cast<const f32x4 *>(trow + kc * 4);
-                acc = fmaf(bw[0], tv[0], acc);
-                acc = fmaf(bw[1], tv[1], acc);
-                acc = fmaf(bw[2], tv[2], acc);
-                acc = fmaf(bw[3], tv[3], acc);
-            }
-            acc += __shfl_xor(acc, 1);
-            acc += __shfl_xor(acc, 2);
-            acc += __shfl_xor(acc, 4);
+            const WlWord p = wl_lookup(a.segs, w, valid);
+            const bool found = p.brow != nullptr;
+            float acc[1];
+            wl_dot<1>(sm + (size_t)(valid ? d - d0 : 0) * ldt, ldt, p, sub, 0, 1, acc);
             if (broken && d0 == 0 && sub == 0) {
                 a.nll_seq[r] = INF;
                 a.prev0[r] = -1;
@@ -166,7 +130,7 @@ __global__ __launch_bounds__(AH_THREADS) void alt_head_kernel(AltArgs a) {
             if (!valid) continue;
             if (sub == 0) {
                 if (found) {
-                    const float y = acc + a.b2[w];
+                    const float y = acc[0] + a.b2[w];
                     const double head = base[d - d0] - (double)y;
                     a.nll_seq[r] = head + (psc[K] - psc[d + 1 + j]);
                 } else {                                           // a word in no segment: NaN, nothing of B or b2 is read

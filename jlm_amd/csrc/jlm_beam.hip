@@ -5,6 +5,8 @@
 // wavefront shuffles for the reductions, no MFMA.
 #include "jlm_common.h"
 #include "jlm_beam_fold.h"
+#include "jlm_wave.h"
+#include "jlm_wordlist_dot.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -53,61 +55,9 @@ __global__ __launch_bounds__(WL_THREADS) void wordlist_kernel(
             const int w = valid ? wl[w0 + wi] : -1;
             // wl_w (the *_perm entry points): the weight row is word wl_w[i]'s, the bias word wl[i]'s
             const int ww = (valid && wl_w) ? wl_w[w0 + wi] : w;
-            int K4 = 0, toff = 0;
-            const f32x4 *brow = nullptr;
-            if (valid) {
-                for (int si = 0; si < segs.n; ++si)
-                    if (ww >= segs.s[si].v_start && ww < segs.s[si].v_end) {
-                        K4 = segs.s[si].k >> 2;
-                        toff = segs.s[si].t_off;
-                        brow = reinterpret_cast<const f32x4 *>(segs.s[si].B + (size_t)(ww - segs.s[si].v_start) * segs.s[si].ldb);
-                    }
-            }
+            // the logit's arithmetic is csrc/jlm_wordlist_dot.h's (the one definition: the other word-addressed kernels call it too)
             float acc[WL_ROWS];
-#pragma unroll
-            for (int r = 0; r < WL_ROWS; ++r) acc[r] = 0.0f;
-            // the word's whole share of the weight row is requested before any of it is used (k <= 256: at
-            // most 8 x 16 B per lane): one memory round trip per word instead of one per 32 k-values
-            f32x4 bv[8];
-#pragma unroll
-            for (int c8 = 0; c8 < 8; ++c8) {
-                const int kc = sub + 8 * c8;
-                bv[c8] = (kc < K4 && kc < 64) ? brow[kc] : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int c8 = 0; c8 < 8; ++c8) {
-                const int kc = sub + 8 * c8;
-                if (kc >= K4 || kc >= 64) continue;
-#pragma unroll
-                for (int r = 0; r < WL_ROWS; ++r) {
-                    if (rc + r < nrows) {
-                        const f32x4 tv = *reinterpret_cast<const f32x4 *>(sm + (size_t)r * ldt + toff + kc * 4);
-                        acc[r] = fmaf(bv[c8][0], tv[0], acc[r]);
-                        acc[r] = fmaf(bv[c8][1], tv[1], acc[r]);
-                        acc[r] = fmaf(bv[c8][2], tv[2], acc[r]);
-                        acc[r] = fmaf(bv[c8][3], tv[3], acc[r]);
-                    }
-                }
-            }
-            for (int kc = sub + 64; kc < K4; kc += 8) {            // k > 256 (untied models): the tail, as before
-                const f32x4 bw = brow[kc];
-#pragma unroll
-                for (int r = 0; r < WL_ROWS; ++r) {
-                    if (rc + r < nrows) {
-                        const f32x4 tv = *reinterpret_cast<const f32x4 *>(sm + (size_t)r * ldt + toff + kc * 4);
-                        acc[r] = fmaf(bw[0], tv[0], acc[r]);
-                        acc[r] = fmaf(bw[1], tv[1], acc[r]);
-                        acc[r] = fmaf(bw[2], tv[2], acc[r]);
-                        acc[r] = fmaf(bw[3], tv[3], acc[r]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < WL_ROWS; ++r) {
-                acc[r] += __shfl_xor(acc[r], 1);
-                acc[r] += __shfl_xor(acc[r], 2);
-                acc[r] += __shfl_xor(acc[r], 4);
-            }
+            wl_dot<WL_ROWS>(sm, ldt, wl_lookup(segs, ww, valid), sub, rc, nrows, acc);
             if (valid && sub == 0) {
                 const float bw = b2[w];
 #pragma unroll
@@ -288,32 +238,7 @@ extern "C" int jlm_wordlist_lse_perm(const jlm_segment *segs_host, int n_segs, c
 // 8 lanes per row, slices strided over them, 3 xor-shuffle steps -- instead of in a
 // separate jlm_lse_combine launch; the rows' positions in the slices are
 // live_base[(frame - 1, sentence)] + slot, recorded when the rows were listed.
-// Wave-wide lexicographic minimum of (v, i), result in every lane.  DPP cross-lane moves (a few
-// cycles each) instead of __shfl_xor, which is ds_bpermute on this ISA: three dependent LDS-crossbar
-// round trips per step made one selection round 0.9 us (8.8 of the kernel's 19 us for beam = 10).
-// Mirror steps leave every lane of a 16-lane row with the row's minimum; row_bcast15 / 31 carry it to
-// the last row; lane 63 holds the wave's and is read back through SGPRs.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ void argmin_dpp_step(double &v, int &i) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int hi2 = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const int i2 = __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xf, false);
-    const double v2 = __hiloint2double(hi2, lo2);
-    if (v2 < v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
-__device__ __forceinline__ void wave_argmin(double &v, int &i) {
-    argmin_dpp_step<0xB1, 0xf>(v, i);      // quad_perm(1,0,3,2)
-    argmin_dpp_step<0x4E, 0xf>(v, i);      // quad_perm(2,3,0,1)
-    argmin_dpp_step<0x141, 0xf>(v, i);     // row_half_mirror
-    argmin_dpp_step<0x140, 0xf>(v, i);     // row_mirror
-    argmin_dpp_step<0x142, 0xa>(v, i);     // row_bcast15 into rows 1 and 3
-    argmin_dpp_step<0x143, 0xc>(v, i);     // row_bcast31 into rows 2 and 3
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    i = __builtin_amdgcn_readlane(i, 63);
-    v = __hiloint2double(hi, lo);
-}
+// The rounds' wave-wide lexicographic minimum of (v, i) is wave_argmin (csrc/jlm_wave.h, shared with tail_predict_kernel).
 
 // The fused fold of both beam-step kernels (beam_fold_parts): csrc/jlm_beam_fold.h, shared with cache_cell_patch_kernel.
 

@@ -108,11 +108,6 @@ struct CellPatchArgs {
     double log1m, log_rho;             // log(1 - lambda), log(lambda / (1 - lambda))
 };
 
-__device__ __forceinline__ double ce_logaddexp(double x, double y) {
-    const double hi = fmax(x, y), lo = fmin(x, y);
-    return hi + log1p(exp(lo - hi));                               // (lo = -inf: hi)
-}
-
 __global__ void __launch_bounds__(CE_THREADS) cache_cell_patch_kernel(const CellPatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) double ce_lds[];   // int [n_pad] words | [beam] L | float [beam] Z
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -209,7 +204,7 @@ __global__ void __launch_bounds__(CE_THREADS) cache_cell_patch_kernel(const Cell
                 const float Z = sh_z[k];
                 if (!(Z > 0.0f)) continue;
                 const double y = (double)e_out[k], L = sh_L[k];
-                const double v = n_match > 0 ? L + a.log1m + ce_logaddexp(y - L, (a.log_rho + log((double)M[q])) - log((double)Z))
+                const double v = n_match > 0 ? L + a.log1m + jlm_logaddexp(y - L, (a.log_rho + log((double)M[q])) - log((double)Z))
                                              : y + a.log1m;
                 e_out[k] = (float)v;
             }

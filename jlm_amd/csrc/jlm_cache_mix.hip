@@ -13,23 +13,23 @@
 // e_j); the maximum, e_j = expf(s_j - max) and Z are formed in a fixed tree over j (thread t owns j = t, t + 256, ... in ascending
 // order, an xor tree over the wave, the four waves in order); c(w) is summed over the entries with w_j = w in ascending j by the thread
 // that owns the FIRST occurrence of w, so a word has one writer and nothing is atomic -- every lane of a wave reads the same word of
-// the LDS array in the all-pairs loop (a broadcast: no bank conflict).  L is the row's log-normaliser in topk_rows_kernel's arithmetic
-// (its layout, f32 expf, f64 sums, its order), read before any word is patched.  y[w] <- logaddexp(y[w], L + log rho + log c - log Z).
+// the LDS array in the all-pairs loop (a broadcast: no bank conflict).  L is the row's log-normaliser by rl_row (csrc/jlm_row_lse.h),
+// the function topk_rows_kernel's is built from, read before any word is patched.  y[w] <- logaddexp(y[w], L + log rho + log c - log Z).
 #include <math.h>
 #include "jlm_common.h"
 #include "jlm_cache_unit.h"
+#include "jlm_row_lse.h"
 
 namespace {
 
 constexpr int CQ_KEYS = 64;            // keys per workgroup of cache_query_kernel: 256 threads, four lanes a key
 constexpr int CM_THREADS = 256;
 constexpr int CM_WAVES = CM_THREADS / 64;
-constexpr int CM_UNROLL = 4;           // topk_rows_kernel's TK_UNROLL: the groups of chunks its running maximum moves by
 constexpr int CM_JPT = JLM_CACHE_MIX_MAX_N / CM_THREADS;          // window entries a thread owns at most
 
 static_assert(CM_JPT * CM_THREADS == JLM_CACHE_MIX_MAX_N && CM_JPT == 16, "cm_pairs_patch is instantiated for 1, 2, 4, 8 and 16 entries");
 
-static_assert(CM_WAVES == 4, "the log-normaliser below is laid out as topk_rows_kernel's (TK_WAVES = 4)");
+static_assert(CM_WAVES == RL_WAVES, "rl_row (csrc/jlm_row_lse.h) is called by a workgroup of RL_WAVES waves");
 
 struct QueryArgs {
     const uint4 *hist, *q;
@@ -84,56 +84,6 @@ struct MixArgs {
     float log_rho;                     // log(lambda / (1 - lambda))
 };
 
-__device__ __forceinline__ double cm_rescale(double s, float m, float M) { return m > -INFINITY ? s * exp((double)m - (double)M) : s; }
-
-// the log-normaliser of one row as topk_rows_kernel forms it: 16-byte chunks, an iteration = 64 consecutive chunks, wave w owning the
-// iterations [w ipw, (w + 1) ipw); per lane a running maximum and an f64 sum of f32 expf, rescaled in f64 when a group of CM_UNROLL
-// chunks raises the maximum; an xor tree over the wave, the waves merged in order.  -> (M, S) on every thread: lse = M + log S.
-__device__ __forceinline__ void cm_row_lse(const f32x4 *__restrict__ row, int n_cols, float *s_m, double *s_s, float &M, double &S) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int n4 = (n_cols + 3) >> 2, n_it = (n4 + 63) >> 6;
-    const int ipw = (n_it + CM_WAVES - 1) / CM_WAVES;
-    const int it0 = wv * ipw, it1 = min(it0 + ipw, n_it);
-    float m = -INFINITY;
-    double s = 0.0;
-    for (int it = it0; it < it1; it += CM_UNROLL) {
-        f32x4 v[CM_UNROLL];
-#pragma unroll
-        for (int u = 0; u < CM_UNROLL; ++u) {
-            const int c = (it + u) * 64 + lane;
-            v[u] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if (it + u < it1 && c < n4) v[u] = row[c];
-        }
-        float cm = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < CM_UNROLL; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * ((it + u) * 64 + lane) + j < n_cols) cm = fmaxf(cm, v[u][j]);
-        if (cm > m) { s = cm_rescale(s, m, cm); m = cm; }
-        const float me = m > -INFINITY ? m : 0.0f;
-#pragma unroll
-        for (int u = 0; u < CM_UNROLL; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * ((it + u) * 64 + lane) + j < n_cols) s += (double)expf(v[u][j] - me);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float m2 = __shfl_xor(m, off);
-        const double s2 = __shfl_xor(s, off);
-        const float mm = fmaxf(m, m2);
-        s = cm_rescale(s, m, mm) + cm_rescale(s2, m2, mm);
-        m = mm;
-    }
-    if (lane == 0) { s_m[wv] = m; s_s[wv] = s; }
-    __syncthreads();                                               // (every read of the row is behind this barrier)
-    M = s_m[0];
-    for (int w = 1; w < CM_WAVES; ++w) M = fmaxf(M, s_m[w]);
-    S = 0.0;
-    for (int w = 0; w < CM_WAVES; ++w) S += cm_rescale(s_s[w], s_m[w], M);
-}
-
 // The all-pairs pass and the patch.  A thread owns the entries j = tid + 256 u, u < JPT, in registers; the window is walked ONCE, four
 // entries i a trip (two 16-byte LDS reads at one address a wave: broadcasts), and every owned j takes from entry i what is its: a
 // repeat mark when w_i = w_j and i < j, e_i into c when w_i = w_j and i >= j.  Each c is still the sum over its matches in ascending
@@ -174,10 +124,7 @@ __device__ __forceinline__ void cm_pairs_patch(const MixArgs &a, int r, int n_q,
         if (a.lpc_ent) a.lpc_ent[(size_t)r * a.ld_s + j] = lpc;
         if (repeat || w < 0 || w >= a.n_cols) continue;
         const float yw = yrow[w], t = base + lpc;
-        if (t > -INFINITY && yw == yw) {
-            const float m = fmaxf(yw, t), d = fminf(yw, t) - m;    // (yw = -inf: d = -inf, the result is t)
-            yrow[w] = m + log1pf(expf(d));
-        }
+        if (t > -INFINITY && yw == yw) yrow[w] = jlm_logaddexpf(yw, t);
     }
 }
 
@@ -236,7 +183,7 @@ __global__ void __launch_bounds__(CM_THREADS) cache_mix_rows_kernel(const MixArg
     if (!SELF_NORM) {
         float M;
         double S;
-        cm_row_lse(reinterpret_cast<const f32x4 *>(yrow), a.n_cols, l_m, l_s, M, S);
+        rl_row(reinterpret_cast<const f32x4 *>(yrow), a.n_cols, l_m, l_s, M, S);
         if (!(M > -INFINITY && M < INFINITY && S > 0.0 && S < INFINITY)) {                   // (block-uniform)
             if (tid == 0 && a.flags) atomicOr(a.flags, 2);
             return;

@@ -62,6 +62,20 @@ __device__ __forceinline__ void lse_merge(float &m, float &s, float m2, float s2
     m = mm;
 }
 
+// logaddexp: max + log1p(exp(min - max)); the smaller value at -inf gives the larger one.  Nothing is guarded here -- two -inf, a
+// +inf or a NaN give NaN -- and what a caller excludes is its own affair, kept at its call site: the n-gram row patch asks for a
+// term that is finite on both sides and a logit that is no NaN, the cache row patch only for a term above -inf and a logit that is
+// no NaN.  f64 for the decode's edge patches (csrc/jlm_cache_edge.hip, csrc/jlm_ngram_edge.hip), f32 for the row patches
+// (csrc/jlm_cache_mix.hip, csrc/jlm_ngram_mix.hip): one definition each, so that the cache's and the n-gram model's patches round alike
+__device__ __forceinline__ double jlm_logaddexp(double x, double y) {
+    const double hi = fmax(x, y), lo = fmin(x, y);
+    return hi + log1p(exp(lo - hi));
+}
+__device__ __forceinline__ float jlm_logaddexpf(float x, float y) {
+    const float m = fmaxf(x, y), d = fminf(x, y) - m;
+    return m + log1pf(expf(d));
+}
+
 // ---- split-f16 operands (include/jlm_hip.h "f16x3"): x * scale = hi + lo, both f16.
 // The scaled value and hi are pinned in registers before they are used twice: left to itself the
 // compiler folds the multiply into ONE of the two uses of the f32->f16 conversion (v_fma_mix*,

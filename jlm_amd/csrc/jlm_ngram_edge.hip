@@ -35,11 +35,6 @@ struct NgramPatchArgs {
     double log1m, log_rho;             // log(1 - lambda), log(lambda / (1 - lambda))
 };
 
-__device__ __forceinline__ double ng_logaddexp(double x, double y) {
-    const double hi = fmax(x, y), lo = fmin(x, y);
-    return hi + log1p(exp(lo - hi));
-}
-
 __device__ __forceinline__ bool ng_id_ok(int w) { return w >= 0 && w <= NG_MAX_ID; }
 
 // the key of (u, v, w), the predicted word lowest; an absent position (< 0) is 0
@@ -200,7 +195,7 @@ __global__ void __launch_bounds__(NG_THREADS) ngram_cell_patch_kernel(const Ngra
                 }
             }
             const double L = sh_L[k];
-            const double r = found ? L + a.log1m + ng_logaddexp(y - L, a.log_rho + q) : y + a.log1m;
+            const double r = found ? L + a.log1m + jlm_logaddexp(y - L, a.log_rho + q) : y + a.log1m;
             *e_out = (float)r;
         }
     }

@@ -7,8 +7,8 @@
 //
 // ngram_mix_rows_kernel -- one workgroup of 256 threads per live row.  Thread 0 resolves the row's contexts -- bow(v) and the bigram
 // range of v in one trip, the home slot of (u, v) in the context map in the same trip, the trigram range and bow(u v) in a second --
-// while the other threads clear the bitmap and all of them form L in topk_rows_kernel's arithmetic (its layout, f32 expf, f64 sums,
-// its order; restated as cache_mix_rows_kernel restates it), read before any word is patched.  Then three passes, a barrier between
+// while the other threads clear the bitmap and all of them form L by rl_row (csrc/jlm_row_lse.h: the function topk_rows_kernel's
+// log-normaliser is built from and cache_mix_rows_kernel calls too), read before any word is patched.  Then three passes, a barrier between
 // them: the trigram successors (q = lp), the bigram successors no trigram covered (q = bow(u v) + lp), every remaining word with a
 // unigram (q = (bow(u v) + bow(v)) + lp).  A bitmap of V bits in LDS, set by integer OR, says which words are done: the thread whose
 // OR set the bit is the word's one writer, and it reads the original y[w].  No float atomics; every index read from the table is
@@ -17,16 +17,16 @@
 // ngram_hist_advance_kernel -- the histories behind a beam merge: hist_out[q] = (hist_in[prev_row[q]][1], word[q]).
 #include <math.h>
 #include "jlm_common.h"
+#include "jlm_row_lse.h"
 
 namespace {
 
 constexpr int NM_THREADS = 256;
 constexpr int NM_WAVES = NM_THREADS / 64;
 constexpr int NM_DEPTH = 8;            // words a thread has in flight in the unigram pass
-constexpr int NM_UNROLL = 4;           // topk_rows_kernel's TK_UNROLL: the groups of chunks its running maximum moves by
 constexpr unsigned long long NM_GOLDEN = 0x9E3779B97F4A7C15ull;
 
-static_assert(NM_WAVES == 4, "the log-normaliser below is laid out as topk_rows_kernel's (TK_WAVES = 4)");
+static_assert(NM_WAVES == RL_WAVES, "rl_row (csrc/jlm_row_lse.h) is called by a workgroup of RL_WAVES waves");
 
 struct NmArgs {
     float *y;
@@ -36,57 +36,6 @@ struct NmArgs {
     int ld_y, V, n_rows, order;
     float log_rho;                     // log(lambda / (1 - lambda))
 };
-
-__device__ __forceinline__ double nm_rescale(double s, float m, float M) { return m > -INFINITY ? s * exp((double)m - (double)M) : s; }
-
-// the log-normaliser of one row as topk_rows_kernel forms it (cm_row_lse of csrc/jlm_cache_mix.hip, statement for statement): 16-byte
-// chunks, an iteration = 64 consecutive chunks, wave w owning the iterations [w ipw, (w + 1) ipw); per lane a running maximum and an
-// f64 sum of f32 expf, rescaled in f64 when a group of NM_UNROLL chunks raises the maximum; an xor tree over the wave, the waves
-// merged in order.  -> (M, S) on every thread: lse = M + log S.
-__device__ __forceinline__ void nm_row_lse(const f32x4 *__restrict__ row, int n_cols, float *s_m, double *s_s, float &M, double &S) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int n4 = (n_cols + 3) >> 2, n_it = (n4 + 63) >> 6;
-    const int ipw = (n_it + NM_WAVES - 1) / NM_WAVES;
-    const int it0 = wv * ipw, it1 = min(it0 + ipw, n_it);
-    float m = -INFINITY;
-    double s = 0.0;
-    for (int it = it0; it < it1; it += NM_UNROLL) {
-        f32x4 v[NM_UNROLL];
-#pragma unroll
-        for (int u = 0; u < NM_UNROLL; ++u) {
-            const int c = (it + u) * 64 + lane;
-            v[u] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if (it + u < it1 && c < n4) v[u] = row[c];
-        }
-        float cm = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < NM_UNROLL; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * ((it + u) * 64 + lane) + j < n_cols) cm = fmaxf(cm, v[u][j]);
-        if (cm > m) { s = nm_rescale(s, m, cm); m = cm; }
-        const float me = m > -INFINITY ? m : 0.0f;
-#pragma unroll
-        for (int u = 0; u < NM_UNROLL; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * ((it + u) * 64 + lane) + j < n_cols) s += (double)expf(v[u][j] - me);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float m2 = __shfl_xor(m, off);
-        const double s2 = __shfl_xor(s, off);
-        const float mm = fmaxf(m, m2);
-        s = nm_rescale(s, m, mm) + nm_rescale(s2, m2, mm);
-        m = mm;
-    }
-    if (lane == 0) { s_m[wv] = m; s_s[wv] = s; }
-    __syncthreads();                                               // (every read of the row is behind this barrier)
-    M = s_m[0];
-    for (int w = 1; w < NM_WAVES; ++w) M = fmaxf(M, s_m[w]);
-    S = 0.0;
-    for (int w = 0; w < NM_WAVES; ++w) S += nm_rescale(s_s[w], s_m[w], M);
-}
 
 // the context index of (u, v), or -1: the home slot's key and value are requested together, a probe stops on the key, on an empty
 // slot, or after max_probe + 1 slots; every slot index is masked into the map
@@ -109,8 +58,7 @@ __device__ __forceinline__ int nm_context(const jlm_ngram_rows &t, int u, int v)
 // logaddexp(yw, t) of a logit and the n-gram term t = base + q; false: the word keeps its bits (t or yw is not a number to mix)
 __device__ __forceinline__ bool nm_mix(float yw, float t, float &out) {
     if (!(t > -INFINITY && t < INFINITY && yw == yw)) return false;
-    const float m = fmaxf(yw, t), d = fminf(yw, t) - m;            // (yw = -inf: d = -inf, the result is t)
-    out = m + log1pf(expf(d));
+    out = jlm_logaddexpf(yw, t);
     return true;
 }
 
@@ -176,7 +124,7 @@ __global__ void __launch_bounds__(NM_THREADS) ngram_mix_rows_kernel(const NmArgs
     if (!SELF_NORM) {
         float M;
         double S;
-        nm_row_lse(reinterpret_cast<const f32x4 *>(yrow), a.V, l_m, l_s, M, S);
+        rl_row(reinterpret_cast<const f32x4 *>(yrow), a.V, l_m, l_s, M, S);
         if (!(M > -INFINITY && M < INFINITY && S > 0.0 && S < INFINITY)) {
             if (tid == 0 && a.flags) atomicOr(a.flags, 2);
             return;

@@ -6,12 +6,14 @@
 // A row is 8 lanes of a wave, 8 rows per wave, 32 per workgroup -- the beam step's fold layout (jlm_beam.hip, fused K6 tail):
 //   fold    lane `sub` takes the slices p = sub, sub + 8, ...; three xor-shuffle steps merge the 8 partial (max, sum) pairs.
 //           Same order and arithmetic as beam_step_kernel's fold, so a row's log-normaliser is the one the decode uses.
-//   logit   lane `sub` takes the 16-byte chunks k4 = sub, sub + 8, ... of the target's weight row and the row of T (all requested
-//           before the first is used), fmaf in k order, three xor-shuffle adds, + b2[w]: wordlist_kernel<0>'s f32 arithmetic
-//           (jlm_edge_logits).
+//   logit   the word-addressed logit of csrc/jlm_wordlist_dot.h (jlm_edge_logits): its wl_lookup and its wl_sum8 are called; the
+//           fmaf chain between them is wl_dot's order (lane `sub`, chunks k4 = sub, sub + 8, ..., elements 0 .. 3) written out here,
+//           because this kernel's T row is in global memory, not staged in LDS, and BOTH rows are requested whole before the first
+//           use -- one round trip for the row pair.  + b2[w].
 // Both equalities are held to the bit by tests/test_gpu_score_fold.py, which calls the kernel through jlm_score_fold.
 // Latency-bound and tiny next to the step's three matrix kernels: one slice read per lane and slice row, one weight row per row.
 #include "jlm_common.h"
+#include "jlm_wordlist_dot.h"
 
 #define SF_THREADS 256
 #define SF_ROWS (SF_THREADS / 8)
@@ -56,19 +58,14 @@ __global__ __launch_bounds__(SF_THREADS) void score_fold_kernel(
         }
     }
     const int w = live ? target[r] : -1;
-    int K4 = 0, toff = 0;
-    const f32x4 *brow = nullptr;
-    for (int si = 0; si < segs.n; ++si)
-        if (w >= segs.s[si].v_start && w < segs.s[si].v_end) {
-            K4 = segs.s[si].k >> 2;
-            toff = segs.s[si].t_off;
-            brow = reinterpret_cast<const f32x4 *>(segs.s[si].B + (size_t)(w - segs.s[si].v_start) * segs.s[si].ldb);
-        }
+    const WlWord wd = wl_lookup(segs, w, true);             // (a row that is not live asks for word -1, which no segment holds)
+    const int K4 = wd.K4, toff = wd.toff;
+    const f32x4 *brow = wd.brow;
     float acc = 0.0f;
     if (brow) {
         const f32x4 *trow = reinterpret_cast<const f32x4 *>(T + (size_t)r * ldt + toff);
         // the lane's whole share of both rows is requested before any of it is used (k <= 256: at most 8 x 16 B each, as
-        // wordlist_kernel does): one memory round trip per row instead of one per 32 k-values
+        // wl_dot does for the weight row): one memory round trip per row instead of one per 32 k-values
         f32x4 bv[8], tv[8];
 #pragma unroll
         for (int c8 = 0; c8 < 8; ++c8) {
@@ -85,7 +82,7 @@ __global__ __launch_bounds__(SF_THREADS) void score_fold_kernel(
             acc = fmaf(bv[c8][2], tv[c8][2], acc);
             acc = fmaf(bv[c8][3], tv[c8][3], acc);
         }
-        for (int kc = sub + 64; kc < K4; kc += 8) {             // k > 256 (untied models): the tail, as wordlist_kernel
+        for (int kc = sub + 64; kc < K4; kc += 8) {             // k > 256 (untied models): the tail, as wl_dot
             const f32x4 b = brow[kc], t = trow[kc];
             acc = fmaf(b[0], t[0], acc);
             acc = fmaf(b[1], t[1], acc);
@@ -93,9 +90,7 @@ __global__ __launch_bounds__(SF_THREADS) void score_fold_kernel(
             acc = fmaf(b[3], t[3], acc);
         }
     }
-    acc += __shfl_xor(acc, 1);
-    acc += __shfl_xor(acc, 2);
-    acc += __shfl_xor(acc, 4);
+    acc = wl_sum8(acc);
     if (!live || sub != 0) return;
     double nll;
     if (!brow) {                       // a target outside every segment (the host checks ids before the launch)

@@ -7,9 +7,9 @@
 // score is score[g] + lse[g] - logit(row g, word) in f64 (self-normalised models: score[g] - logit), and the n_out best by
 // (score, candidate index) are written with their parents' back-traces.  Candidate index = position in (span, word, slot) order.
 //
-// Logits: wordlist_kernel's arithmetic (csrc/jlm_beam.hip) statement for statement -- 8 lanes per word, lane `sub` takes the 16-byte
-// pieces sub + 8 c of the weight row in order as one fmaf chain, xor butterfly over 1, 2, 4, then + b2[w] -- so a candidate's logit is
-// bit-equal to what jlm_edge_logits gives for that (row, word).  The rows of a span's frame are staged TP_ROWS at a time, as there.
+// Logits: wl_lookup and wl_dot of csrc/jlm_wordlist_dot.h, the functions wordlist_kernel (csrc/jlm_beam.hip) calls, then + b2[w] -- so a
+// candidate's logit is bit-equal to what jlm_edge_logits gives for that (row, word).  The rows of a span's frame are staged TP_ROWS at
+// a time, as there.
 //
 // Selection: candidates are appended to an LDS buffer as they are formed (every position has one writer: no atomics); whenever `chunk`
 // of them are waiting they are selected together with the n_out winners carried so far, and the winners are carried on -- LDS is
@@ -17,6 +17,8 @@
 // minimum throughout and a candidate index is unique, so the result depends neither on `chunk` nor on the order of formation.
 // A NaN score never compares below anything: it never ranks.
 #include "jlm_common.h"
+#include "jlm_wave.h"
+#include "jlm_wordlist_dot.h"
 
 #define TP_THREADS 256
 #define TP_ROWS 16                                 // hypothesis rows per pass (WL_ROWS of wordlist_kernel)
@@ -41,29 +43,6 @@ struct TailArgs {
     int stride;
 };
 
-// wave-wide lexicographic minimum of (v, i), result in every lane: the beam step's DPP reduction (csrc/jlm_beam.hip wave_argmin)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ void tp_argmin_dpp_step(double &v, int &i) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int hi2 = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const int i2 = __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xf, false);
-    const double v2 = __hiloint2double(hi2, lo2);
-    if (v2 < v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
-__device__ __forceinline__ void tp_wave_argmin(double &v, int &i) {
-    tp_argmin_dpp_step<0xB1, 0xf>(v, i);      // quad_perm(1,0,3,2)
-    tp_argmin_dpp_step<0x4E, 0xf>(v, i);      // quad_perm(2,3,0,1)
-    tp_argmin_dpp_step<0x141, 0xf>(v, i);     // row_half_mirror
-    tp_argmin_dpp_step<0x140, 0xf>(v, i);     // row_mirror
-    tp_argmin_dpp_step<0x142, 0xa>(v, i);     // row_bcast15 into rows 1 and 3
-    tp_argmin_dpp_step<0x143, 0xc>(v, i);     // row_bcast31 into rows 2 and 3
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    i = __builtin_amdgcn_readlane(i, 63);
-    v = __hiloint2double(hi, lo);
-}
-
 // a span the kernel serves: its frame inside the plan, its words inside ids[], not empty
 __device__ __forceinline__ bool tp_span_ok(const TailArgs &a, int f, int lo, int hi) {
     return f >= 0 && f < a.n_frames && lo >= 0 && lo < hi && hi <= a.n_ids;
@@ -86,7 +65,7 @@ __device__ void tp_select(double *key, int *cix, int n, int n_out, double *win_v
     for (int r = 0; r < n_out; ++r) {
         double v = bv;
         int c = bc;
-        tp_wave_argmin(v, c);
+        wave_argmin(v, c);
         const int o = (r & 1) * (TP_THREADS / 64);
         if (lane == 0) { red_v[o + wave] = v; red_c[o + wave] = c; }
         __syncthreads();
@@ -159,59 +138,8 @@ __global__ __launch_bounds__(TP_THREADS) void tail_predict_kernel(TailArgs a) {
                 const int wi = wb + slot;
                 const bool valid = wi < nw;
                 const int w = valid ? a.ids[lo + wi] : -1;
-                int K4 = 0, toff = 0;
-                const f32x4 *brow = nullptr;
-                if (valid) {
-                    for (int si = 0; si < a.segs.n; ++si)
-                        if (w >= a.segs.s[si].v_start && w < a.segs.s[si].v_end) {
-                            K4 = a.segs.s[si].k >> 2;
-                            toff = a.segs.s[si].t_off;
-                            brow = reinterpret_cast<const f32x4 *>(a.segs.s[si].B + (size_t)(w - a.segs.s[si].v_start) * a.segs.s[si].ldb);
-                        }
-                }
                 float acc[TP_ROWS];
-#pragma unroll
-                for (int r = 0; r < TP_ROWS; ++r) acc[r] = 0.0f;
-                f32x4 bv[8];
-#pragma unroll
-                for (int c8 = 0; c8 < 8; ++c8) {
-                    const int kc = sub + 8 * c8;
-                    bv[c8] = (kc < K4 && kc < 64) ? brow[kc] : f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-#pragma unroll
-                for (int c8 = 0; c8 < 8; ++c8) {
-                    const int kc = sub + 8 * c8;
-                    if (kc >= K4 || kc >= 64) continue;
-#pragma unroll
-                    for (int r = 0; r < TP_ROWS; ++r) {
-                        if (r < nr) {
-                            const f32x4 tv = *reinterpret_cast<const f32x4 *>(sm + (size_t)r * ldt + toff + kc * 4);
-                            acc[r] = fmaf(bv[c8][0], tv[0], acc[r]);
-                            acc[r] = fmaf(bv[c8][1], tv[1], acc[r]);
-                            acc[r] = fmaf(bv[c8][2], tv[2], acc[r]);
-                            acc[r] = fmaf(bv[c8][3], tv[3], acc[r]);
-                        }
-                    }
-                }
-                for (int kc = sub + 64; kc < K4; kc += 8) {            // k > 256 (untied models)
-                    const f32x4 bw = brow[kc];
-#pragma unroll
-                    for (int r = 0; r < TP_ROWS; ++r) {
-                        if (r < nr) {
-                            const f32x4 tv = *reinterpret_cast<const f32x4 *>(sm + (size_t)r * ldt + toff + kc * 4);
-                            acc[r] = fmaf(bw[0], tv[0], acc[r]);
-                            acc[r] = fmaf(bw[1], tv[1], acc[r]);
-                            acc[r] = fmaf(bw[2], tv[2], acc[r]);
-                            acc[r] = fmaf(bw[3], tv[3], acc[r]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < TP_ROWS; ++r) {
-                    acc[r] += __shfl_xor(acc[r], 1);
-                    acc[r] += __shfl_xor(acc[r], 2);
-                    acc[r] += __shfl_xor(acc[r], 4);
-                }
+                wl_dot<TP_ROWS>(sm, ldt, wl_lookup(a.segs, w, valid), sub, 0, nr, acc);
                 // the block's candidates: words wb .. wb + nwb, rows rc .. rc + nr, word-major behind what is waiting
                 const int nwb = min(TP_THREADS / 8, nw - wb);
                 if (valid && sub == 0) {

@@ -5,9 +5,10 @@
 //
 // topk_rows_kernel -- one workgroup of TK_WAVES waves per row, the row read ONCE in sample_rows_kernel's layout (16-byte chunks, an
 // "iteration" = 64 consecutive chunks, wave w owns the contiguous iterations [w * ipw, (w + 1) * ipw): wave spans in word order).
-//   lse   per lane a running max m and an f64 sum of f32 expf(y - m) over the lane's words, rescaled by exp(m_old - m_new) in f64 when
-//         a group of TK_UNROLL chunks raises the max; xor-tree over the wave, waves merged in order.  A lane that has only seen -inf
-//         or NaN keeps m = -inf and sums expf(y - 0) (0, or NaN for a NaN: flagged).
+//   lse   csrc/jlm_row_lse.h, the definition the cache and n-gram mix kernels share: per lane a running max m and an f64 sum of f32
+//         expf(y - m), moved by groups of TK_UNROLL chunks (rl_group's statements, written out below on the chunks loaded for the
+//         lists), an xor-tree over the wave (rl_wave_merge), waves merged in order (rl_block_merge).  A NaN logit makes the sum NaN:
+//         flagged.
 //   top-k per wave a candidate list in LDS (TK_CAP entries).  Until it holds k entries every word is appended; after that only words
 //         ABOVE the k-th entry's logit: the span is read in ascending id order, so a later word equal to it has a higher id and
 //         ranks below it.  Appends are ballot-compacted; when the next iteration could overflow the list, the wave selects its
@@ -24,19 +25,16 @@
 // B rounds: each lane offers its best remaining candidate by (score, word id) -- the list order, but where f64 rounding makes
 // neighbours' scores equal the lower id first -- and the wave takes the offer with the smallest (score, lane).
 #include "jlm_common.h"
+#include "jlm_row_lse.h"
 
-#define TK_WAVES 4
+#define TK_WAVES RL_WAVES               // the row layout is csrc/jlm_row_lse.h's: its wave count and its group of chunks
 #define TK_THREADS (64 * TK_WAVES)
-#define TK_UNROLL 4
+#define TK_UNROLL RL_GROUP
 #define TK_CAP 512                      // per-wave candidate list; >= JLM_TOPK_MAX + 4 * 64 (one iteration's appends)
 #define TK_SLOTS (TK_CAP / 64)
 
 static_assert(TK_CAP >= JLM_TOPK_MAX + 4 * 64, "a compacted list plus one iteration's appends must fit");
 static_assert(TK_WAVES * JLM_TOPK_MAX <= TK_CAP, "wave 0's list takes every wave's top k");
-
-// a partial sum taken relative to max m, relative to M >= m.  m = -inf: nothing finite was summed, the sum is 0 (or NaN after a NaN
-// logit) and stays as it is -- exp(-inf - -inf) would turn an empty lane's or wave's 0 into NaN.
-__device__ __forceinline__ double tk_rescale(double s, float m, float M) { return m > -INFINITY ? s * exp((double)m - (double)M) : s; }
 
 __device__ __forceinline__ bool tk_better(float ya, int ia, float yb, int ib) { return ya > yb || (ya == yb && ia < ib); }
 
@@ -118,13 +116,18 @@ __device__ __forceinline__ void topk_row(const float *__restrict__ y, int ld, in
             }
         }
         if (!SELF_NORM) {
+            // rl_group's statements (csrc/jlm_row_lse.h), written out: called as a function, the compiler no longer shares the sixteen
+            // word-bound tests between this sum and the list code below: 30 instructions more, and the selection of
+            // tools/complete_bench.py 1.1 to 3.1 % slower than the parent at four of six shapes, outside the parent's own spread
+            // (profiles/shared_arith_bench_ab.txt, set 1 against set 2).  A COPY: a change to rl_group is made
+            // here too.  tests/row_lse_pin.py holds it to rl_row's L on the device, to float32 resolution.
             float cm = -INFINITY;
 #pragma unroll
             for (int u = 0; u < TK_UNROLL; ++u)
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     if (4 * ((it + u) * 64 + lane) + j < n_cols) cm = fmaxf(cm, v[u][j]);
-            if (cm > m) { s = tk_rescale(s, m, cm); m = cm; }
+            if (cm > m) { s = rl_rescale(s, m, cm); m = cm; }
             const float me = m > -INFINITY ? m : 0.0f;
 #pragma unroll
             for (int u = 0; u < TK_UNROLL; ++u)
@@ -173,14 +176,7 @@ __device__ __forceinline__ void topk_row(const float *__restrict__ y, int ld, in
     }
     if (cnt > 0) cnt = tk_select(sy, si, cnt, k, lane);
     if (!SELF_NORM) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const float m2 = __shfl_xor(m, off);
-            const double s2 = __shfl_xor(s, off);
-            const float M = fmaxf(m, m2);
-            s = tk_rescale(s, m, M) + tk_rescale(s2, m2, M);
-            m = M;
-        }
+        rl_wave_merge(m, s);
     } else {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
@@ -188,11 +184,9 @@ __device__ __forceinline__ void topk_row(const float *__restrict__ y, int ld, in
     if (lane == 0) { s_m[wv] = m; s_s[wv] = s; s_n[wv] = cnt; }
     __syncthreads();
     if (wv != 0) return;
-    float M = s_m[0];
-    for (int w = 1; w < TK_WAVES; ++w) M = fmaxf(M, s_m[w]);
-    double S = 0.0;
-    if (!SELF_NORM)
-        for (int w = 0; w < TK_WAVES; ++w) S += tk_rescale(s_s[w], s_m[w], M);
+    float M;
+    double S;
+    rl_block_merge(s_m, s_s, M, S);                      // (SELF_NORM: every s_s is 0 and S is not used)
     int total = s_n[0];
     for (int w = 1; w < TK_WAVES; ++w) {                 // the other waves' lists behind wave 0's
         if (lane < s_n[w]) { s_y[total + lane] = s_y[w * TK_CAP + lane]; s_i[total + lane] = s_i[w * TK_CAP + lane]; }

@@ -12,6 +12,7 @@ torch = pytest.importorskip("torch")
 from jlm_amd import _lib                                                                  # noqa: E402
 from jlm_amd.cache import mixed_logits                                                    # noqa: E402
 from tests.cache_mix_budget import U, lpc_bar, lse_bar, score_bar, y_bar                  # noqa: E402
+from tests.row_lse_pin import CASES as LSE_CASES, LAM as LSE_LAM, expected_bits, pin_row  # noqa: E402
 from tests.test_gpu_cache_rows import H_SCALE, NAN_BITS, Rings, encode                    # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -242,6 +243,26 @@ def test_a_cached_word_the_model_gives_no_mass(self_norm):
         assert (700 in cs.window(r)[2]) == bool(np.isfinite(y2[r, 700]))
         assert np.isneginf(y2[r, 1])
     assert np.isfinite(y2[0, 700])
+
+
+@pytest.mark.parametrize("V,where", LSE_CASES)
+def test_L_is_the_topk_kernels_log_normaliser_bit_for_bit(V, where):
+    """tests/row_lse_pin.py: one live row whose maximum 0.0f sits in the first or the last non-empty wave span, a window of exactly one
+    entry holding w* (e = 1, Z = 1, c = 1 whatever the score) and y[w*] = -inf -- y'[w*] has the bits of
+    float32(float32(nll) + log rho), nll jlm_topk_rows' own"""
+    y, p, ws = pin_row(V, where)
+    cs = Case(0, 32, 1, 1, V, (FULL,), equal(ws), 1, lam=LSE_LAM)
+    assert cs.window(0)[2].tolist() == [ws]
+    cs.y[0, :V] = y
+    rc_q, rc_m, _, y2, ent, flags = launch(cs)
+    assert rc_q == 0 and rc_m == 0 and flags == 0, (rc_q, rc_m, flags)
+    assert ent[0, 0] == 0.0                                                # log c - log Z of the one entry
+    got, want = int(y2[0, ws:ws + 1].view(np.uint32)[0]), expected_bits(V, where)
+    print("V %d, p = %d (%s span), w* = %d: y'[w*] bits %08x, float32(float32(nll) + log rho) bits %08x" % (V, p, where, ws, got, want))
+    assert got == want, (V, where, hex(got), hex(want))
+    keep = np.ones(cs.ld_y, dtype=bool)
+    keep[ws] = False
+    assert same_bits(y2[0][keep], cs.y[0][keep])
 
 
 def test_flags_leave_the_row_unpatched():

@@ -13,6 +13,7 @@ torch = pytest.importorskip("torch")
 from jlm_amd import _lib                                                                  # noqa: E402
 from jlm_amd.ngram import NGramTable, mixed_logits, pack, successor_tensors               # noqa: E402
 from tests.ngram_mix_budget import y_bar                                                  # noqa: E402
+from tests.row_lse_pin import CASES as LSE_CASES, LAM as LSE_LAM, expected_bits, pin_row  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -309,6 +310,25 @@ def test_refusals_launch_nothing():
     assert call() == 0
     torch.cuda.synchronize()
     assert not same_bits(yd.cpu().numpy(), y)
+
+
+@pytest.mark.parametrize("V,where", LSE_CASES)
+def test_L_is_the_topk_kernels_log_normaliser_bit_for_bit(V, where):
+    """tests/row_lse_pin.py: one live row whose maximum 0.0f sits in the first or the last non-empty wave span, no history, a table
+    whose unigram of w* is 0.0 and y[w*] = -inf -- y'[w*] has the bits of float32(float32(nll) + log rho), nll jlm_topk_rows' own"""
+    y, p, ws = pin_row(V, where)
+    lp = np.full(V, -1.0)
+    lp[ws] = 0.0
+    table = NGramTable(np.arange(1, V + 1, dtype=np.int64), lp, np.zeros(V), 1).rounded()
+    assert table.successor_arrays(V)["uni_lp"][ws] == 0.0
+    row = make_rows(V, 1, 0)
+    row[0, :V] = y
+    rc, y2, flags = launch(table, V, row, np.array([(-1, -1)], dtype=np.int32), LSE_LAM, 3)
+    assert rc == 0 and flags == 0, (rc, flags)
+    got, want = int(y2[0, ws:ws + 1].view(np.uint32)[0]), expected_bits(V, where)
+    print("V %d, p = %d (%s span), w* = %d: y'[w*] bits %08x, float32(float32(nll) + log rho) bits %08x" % (V, p, where, ws, got, want))
+    assert got == want, (V, where, hex(got), hex(want))
+    assert same_bits(y2[0, V:], row[0, V:])
 
 
 @pytest.mark.parametrize("V", [262144, 393216])
