@@ -27,6 +27,7 @@
 #ifndef JLM_HIP_H
 #define JLM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1033,6 +1034,71 @@ typedef struct {
  * launch.  events as jlm_score_frames'.  Returns as jlm_score_frames does. */
 int jlm_score_cache_frames(const jlm_decode_model *model_host, const jlm_score_plan *plan_host, const jlm_cache_plan *cache_host,
                            void *stream, void *const *events);
+
+/* ------------------------------------------------------------------------
+ * Scoring against a memory of hidden states (LSTM_Model.score_memory / score_streams_memory, jlm_amd/memory.py, DESIGN.md section 28;
+ * the unbounded cache of Grave, Cisse and Joulin, NIPS 2017 -- with exact search, the datastore of a kNN-LM).  Additive to ABI 12.
+ *
+ * A memory is N >= 1 entries (k_i, v_i): k_i a hidden state in the model's state-row format, v_i the id of the word that followed it.
+ * It is built once, stays on the device and is shared by every row of every call.  A query position q has the state h_q and is scored
+ * on w_q, exactly as a position of the cache above.  For every theta of the call
+ *   s_i       = theta * (h_q . k_i)                       h, k in real units (split rows: (hi + lo) / h_scale)
+ *   lpm_q     = log sum_{i : v_i = w_q} exp(s_i) - log sum_{i < N} exp(s_i)     (-inf when no i matches)
+ *   p_q       = (1 - lambda) exp(-nll_q) + lambda exp(lpm_q)
+ *   nll_mix_q = -log p_q                                   (float64, on the host: jlm_amd/cache.py mix_nll with n_entries = N)
+ * There is no causality and no window: every query sees every entry.  Word ids are only ever compared, never used as an index.
+ * Ranges: theta >= 0 and finite, 0 <= lambda < 1, 1 .. JLM_CACHE_MAX_THETAS values of theta a call, N <= JLM_MEMORY_MAX_KEYS.
+ *
+ * jlm_memory_rows (csrc/jlm_memory.hip: memory_rows_kernel, memory_fold_kernel):
+ *   keys      [N][H]                 state rows, 4 bytes a value either way (split != 0: [8 hi][8 lo] f16 of k * h_scale; else f32, and
+ *                                    h_scale is not read); 16-byte aligned.   key_words [N] int32
+ *   q_rows    [n_steps][n_rows][H]   the queries' state rows in the same format, q_words [n_steps][n_rows] int32: what the store hook of
+ *                                    jlm_score_cache_frames leaves in a ring with nothing carried.  Query (t, r) is live iff t < len[r]
+ *                                    (len [n_rows] device int32; NULL: every query is live); rows and words of queries that are not
+ *                                    live are never read.
+ *   lpm       [n_theta][n_steps][n_rows] f32; entries of queries that are not live are left untouched.
+ *   flags     (one device int, may be NULL): |= 1 when a product h_q . k_i of a live query is not finite.
+ * The key split.  The keys are cut into ceil(N / S) consecutive ranges of S = jlm_memory_keys_per_split(N) keys, a function of N ALONE:
+ *   S = max(JLM_MEMORY_MIN_SPLIT_KEYS, ceil(ceil(N / JLM_MEMORY_MAX_SPLITS) / 64) * 64)
+ * -- 512 keys, one pair of 32-key tiles per wave, grown so that there are never more than 128 splits.  The grid is (block of 32
+ * queries) x (split), query block fastest.  A workgroup folds its range under cache_rows_kernel's arithmetic and in its fixed order
+ * (wave w: tile pairs w, w + 8, ...; the two half-waves; the eight waves) and writes one partial (m, Z, M) per (theta, split, query) to
+ * the workspace, [n_theta][n_split][3][n_steps * n_rows] f32, jlm_memory_workspace_bytes(N, n_rows, n_steps, n_theta) bytes;
+ * memory_fold_kernel folds a query's splits in ascending order and writes logf(M) - logf(Z).  Every word of the workspace that is read
+ * was written by the same call.  Arithmetic of the products, scores and sums: jlm_cache_rows'.
+ * The bits of lpm for (query state row, query word, theta, memory) do not depend on how many queries or thetas the call carries, on
+ * which other queries are live, on where in the call the query stands, or on what the workspace held before.
+ * Returns -1 before any launch for N < 1 or N > JLM_MEMORY_MAX_KEYS, H <= 0 or H % 32 != 0, n_theta out of range or thetas NULL, a
+ * theta that is negative or not finite, split != 0 with h_scale <= 0, n_rows or n_steps < 0, n_rows > 65535,
+ * n_rows * n_steps >= 2^27, keys / q_rows not 16-byte or another pointer not 4-byte aligned, a NULL pointer other than len and flags,
+ * workspace_bytes below jlm_memory_workspace_bytes(...); 0 with nothing launched for n_rows == 0 or n_steps == 0 (after the checks on
+ * N, H, thetas and h_scale); else 0 or a hipError_t. */
+#define JLM_MEMORY_MAX_KEYS (1 << 24)
+#define JLM_MEMORY_MIN_SPLIT_KEYS 512
+#define JLM_MEMORY_MAX_SPLITS 128
+int jlm_memory_keys_per_split(int N);                       /* 0 for N outside [1, JLM_MEMORY_MAX_KEYS] */
+size_t jlm_memory_workspace_bytes(int N, int n_rows, int n_steps, int n_theta);
+int jlm_memory_rows(const void *keys, const int *key_words, int N, int H, int split, float h_scale, const void *q_rows,
+                    const int *q_words, int n_rows, int n_steps, const int *len, const float *thetas_host, int n_theta, float *lpm,
+                    void *workspace, size_t workspace_bytes, int *flags, void *stream);
+
+/* What a call scored against a memory has beside its jlm_score_plan (whose layout is unchanged): step t of the plan is query row t. */
+typedef struct {
+    const void *keys; const int *key_words; int N;    /* the memory; read only */
+    void *q_rows; int *q_words;         /* [n_steps][n_rows][H] / [n_steps][n_rows] device: written by the loop, uninitialised before */
+    const int *len;                     /* [n_rows] device: the steps row r is live; NULL: all */
+    const float *thetas; int n_theta;   /* host */
+    float *lpm;                         /* [n_theta][n_steps][n_rows] device */
+    void *workspace; size_t workspace_bytes;
+    int *flags;                         /* one device int or NULL: jlm_memory_rows' bit */
+} jlm_memory_plan;
+
+/* jlm_score_frames' loop -- the same launches in the same order, so nll_seq / nll_tok and the returned state are the same bits --
+ * with the store hook of jlm_score_cache_frames behind every step (the live rows of the written state set into q_rows[t], the step's
+ * targets into q_words[t]) and jlm_memory_rows once behind the last step.  No host synchronisation.  Every refusal of
+ * jlm_memory_rows is returned before the first launch.  events as jlm_score_frames'.  Returns as jlm_score_frames does. */
+int jlm_score_memory_frames(const jlm_decode_model *model_host, const jlm_score_plan *plan_host, const jlm_memory_plan *memory_host,
+                            void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
  * The continuous cache on the decode side: the cache distribution over EVERY word of the window, as a patch of a row's materialised

@@ -6,7 +6,7 @@ has not been built (``python -c 'import __graft_entry__ as g; g.build()'``) and
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_uint, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # JLM_HIP_LIB: developer override used by tools/ab_lib.sh to A/B two builds of the same ABI
@@ -102,6 +102,13 @@ class CachePlan(Structure):
     """jlm_cache_plan (include/jlm_hip.h)."""
     _fields_ = [("hist", c_void_p), ("words", c_void_p), ("cap", c_int), ("pos0", c_int), ("first", c_void_p), ("len", c_void_p),
                 ("N", c_int), ("thetas", POINTER(c_float)), ("n_theta", c_int), ("lpc", c_void_p), ("flags", c_void_p)]
+
+
+class MemoryPlan(Structure):
+    """jlm_memory_plan (include/jlm_hip.h)."""
+    _fields_ = [("keys", c_void_p), ("key_words", c_void_p), ("N", c_int), ("q_rows", c_void_p), ("q_words", c_void_p), ("len", c_void_p),
+                ("thetas", POINTER(c_float)), ("n_theta", c_int), ("lpm", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+                ("flags", c_void_p)]
 
 
 class CacheMixPlan(Structure):
@@ -218,6 +225,10 @@ _SIGS = {
     "jlm_rank_frames": ([POINTER(DecodeModel), POINTER(RankPlan), P, P], c_int),
     "jlm_cache_rows": ([P, P, c_int, c_int, c_int, c_int, c_float, c_int, c_int, P, P, c_int, POINTER(c_float), c_int, P, P, P], c_int),
     "jlm_score_cache_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), POINTER(CachePlan), P, P], c_int),
+    "jlm_memory_keys_per_split": ([c_int], c_int),
+    "jlm_memory_workspace_bytes": ([c_int, c_int, c_int, c_int], c_size_t),
+    "jlm_memory_rows": ([P, P, c_int, c_int, c_int, c_float, P, P, c_int, c_int, P, POINTER(c_float), c_int, P, P, c_size_t, P, P], c_int),
+    "jlm_score_memory_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), POINTER(MemoryPlan), P, P], c_int),
     "jlm_cache_query": ([P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_int, P, c_int, c_float, P, c_int, P, P], c_int),
     "jlm_cache_mix_rows": ([P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, c_int, c_float, P, P, P], c_int),
     "jlm_rank_cache_frames": ([POINTER(DecodeModel), POINTER(RankPlan), POINTER(CacheMixPlan), P, P], c_int),

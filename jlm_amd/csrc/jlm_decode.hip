@@ -679,6 +679,30 @@ extern "C" int jlm_score_cache_frames(const jlm_decode_model *m, const jlm_score
                           cp->n_theta, cp->lpc, cp->flags, stream);
 }
 
+// the refusals of jlm_memory_rows on their own (csrc/jlm_memory.hip)
+int jlm_memory_refuse(const void *keys, const int *key_words, int N, int H, int split, float h_scale, const void *q_rows, const int *q_words,
+                      int n_rows, int n_steps, const int *len, const float *thetas, int n_theta, const float *lpm, const void *workspace,
+                      size_t workspace_bytes, const int *flags);
+
+// Scoring against a memory (include/jlm_hip.h jlm_score_memory_frames): score_loop with jlm_score_cache_frames' store hook over a ring
+// of exactly n_steps slots with nothing carried -- the query rows -- and memory_rows_kernel once behind the last step.
+extern "C" int jlm_score_memory_frames(const jlm_decode_model *m, const jlm_score_plan *p, const jlm_memory_plan *mp, void *stream,
+                                       void *const *events) {
+    if (!m || !p || !mp) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    const int split = m->split_lstm ? 1 : 0;
+    JLM_TRY(jlm_memory_refuse(mp->keys, mp->key_words, mp->N, m->H, split, m->h_scale, mp->q_rows, mp->q_words, R, S, mp->len, mp->thetas,
+                              mp->n_theta, mp->lpm, mp->workspace, mp->workspace_bytes, mp->flags));
+    struct {
+        void *hist; int *words; int cap, pos0;
+    } ring{mp->q_rows, mp->q_words, S > 0 ? S : 1, 0};
+    JLM_TRY(score_loop(m, p, stream, events,
+                       [&](int t, int bound, const void *h_out) { return ring_store(&ring, t, h_out, p->target, bound, R, m->H, stream); }));
+    if (R <= 0 || S <= 0) return 0;
+    return jlm_memory_rows(mp->keys, mp->key_words, mp->N, m->H, split, m->h_scale, mp->q_rows, mp->q_words, R, S, mp->len, mp->thetas,
+                           mp->n_theta, mp->lpm, mp->workspace, mp->workspace_bytes, mp->flags, stream);
+}
+
 // Teacher-forced ranking (include/jlm_hip.h jlm_rank_frames): jlm_score_frames' loop over the live rows with the materialised logits
 // of a drawing frame of jlm_generate_frames in the normaliser's place, and rank_rows_kernel (csrc/jlm_rank.hip) on the step's targets.
 // before_rank(t, bound, h_out, ndev, stamp): between the logit GEMMs' stamp and the ranking, with the state set the step wrote;

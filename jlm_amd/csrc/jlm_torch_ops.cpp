@@ -865,6 +865,44 @@ Tensor score_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tenso
                          [&](hipStream_t st, void *const *ev) { return jlm_score_cache_frames(&m, &sp.p, &cp, st, ev); });
 }
 
+// score_frames against a memory of hidden states (jlm_score_memory_frames, include/jlm_hip.h): its arguments, then the memory keys
+// [N][H] (4-byte values, the model's state-row format) and key_words [N] int32, the query rows q_rows [n_steps][n_rows][H] / q_words
+// [n_steps][n_rows] the loop writes, len [n_rows] int32 on the device, thetas (host), lpm [n_theta][n_steps][n_rows] float32, the
+// workspace (float32, jlm_memory_workspace_bytes) and mem_flags, one int32.  -> as score_frames (the memory pass runs behind the last
+// step's bracket).
+Tensor score_memory_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                           const OptTensor &T, const OptTensor &Tm, int64_t ld_tm, const OptTensor &part, int64_t max_parts, const Tensor &rows,
+                           const Tensor &prev0, const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host,
+                           const Tensor &nll_seq, const OptTensor &nll_tok, const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed,
+                           const Tensor &keys, const Tensor &key_words, int64_t N, const Tensor &q_rows, const Tensor &q_words, const Tensor &len,
+                           std::vector<double> thetas, const Tensor &lpm, const Tensor &workspace, const OptTensor &mem_flags) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    const ScorePlanArgs sp("score_memory_frames", m, h0, c0, h1, c1, T, Tm, ld_tm, part, max_parts, rows, prev0, word, target, n_live,
+                           n_live_host, nll_seq, nll_tok, flags, R, S);
+    const int64_t n_theta = (int64_t)thetas.size();
+    TORCH_CHECK(n_theta >= 1 && n_theta <= JLM_CACHE_MAX_THETAS, "jlm.score_memory_frames: 1 .. ", JLM_CACHE_MAX_THETAS, " values of theta");
+    TORCH_CHECK(N >= 1 && N <= JLM_MEMORY_MAX_KEYS, "jlm.score_memory_frames: 1 <= N <= ", JLM_MEMORY_MAX_KEYS);
+    TORCH_CHECK(keys.defined() && keys.element_size() == 4 && keys.numel() >= N * (int64_t)m.H && is(key_words, at::kInt, N),
+                "jlm.score_memory_frames: keys [N][H] of 4-byte values, int32 key_words [N]");
+    TORCH_CHECK(q_rows.defined() && q_rows.element_size() == 4 && q_rows.numel() >= S * R * (int64_t)m.H && is(q_words, at::kInt, S * R),
+                "jlm.score_memory_frames: q_rows [n_steps][n_rows][H] of 4-byte values, int32 q_words [n_steps][n_rows]");
+    const size_t need = jlm_memory_workspace_bytes((int)N, (int)R, (int)S, (int)n_theta);
+    TORCH_CHECK(is(len, at::kInt, R) && is(lpm, at::kFloat, n_theta * S * R) && opt_ok(mem_flags, at::kInt, 1) &&
+                    is(workspace, at::kFloat, (int64_t)(need / 4)),
+                "jlm.score_memory_frames: int32 len [n_rows], float32 lpm [n_theta][n_steps][n_rows], a float32 workspace of "
+                "jlm_memory_workspace_bytes, int32 mem_flags");
+    std::vector<float> th(thetas.begin(), thetas.end());
+    jlm_memory_plan mp{};
+    mp.keys = ptr<const void>(keys, "keys"); mp.key_words = ptr<const int>(key_words, "key_words"); mp.N = (int)N;
+    mp.q_rows = ptr<void>(q_rows, "q_rows"); mp.q_words = ptr<int>(q_words, "q_words"); mp.len = ptr<const int>(len, "len");
+    mp.thetas = th.data(); mp.n_theta = (int)n_theta;
+    mp.lpm = ptr<float>(lpm, "lpm"); mp.workspace = ptr<void>(workspace, "workspace"); mp.workspace_bytes = (size_t)workspace.numel() * 4;
+    mp.flags = optr<int>(mem_flags, "mem_flags");
+    return launch_frames("jlm_score_memory_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_SCORE_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_score_memory_frames(&m, &sp.p, &mp, st, ev); });
+}
+
 // The level table of jlm_rank_rows as tensors, checked: ids [n_ids], lv_off [n_cols + 1], lv_lo / lv_hi of one length, all int32 on the
 // device; without lv_off the other three are not passed on.
 struct RankLevels {
@@ -1647,6 +1685,12 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor(k!) hist, Tensor(l!) words, int cap, int pos0, Tensor first, Tensor len, int N, float[] thetas, Tensor(m!) lpc, "
           "Tensor(n!)? cache_flags) -> Tensor",
           score_cache_frames);
+    m.def("score_memory_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!)? Tm, int ld_tm, Tensor(g!)? part, int max_parts, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, "
+          "int[] n_live_host, Tensor(h!) nll_seq, Tensor(i!)? nll_tok, Tensor(j!)? flags, int n_rows, int n_steps, bool timed, "
+          "Tensor keys, Tensor key_words, int N, Tensor(k!) q_rows, Tensor(l!) q_words, Tensor len, float[] thetas, Tensor(m!) lpm, "
+          "Tensor(n!) workspace, Tensor(o!)? mem_flags) -> Tensor",
+          score_memory_frames);
     m.def("rank_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, Tensor target, Tensor? ids, Tensor? lv_off, Tensor? lv_lo, "
           "Tensor? lv_hi, int n_levels, Tensor(a!) rank, Tensor(b!)? flags) -> ()",
           rank_rows);

@@ -971,6 +971,22 @@ class LSTM_Model():
         from .cache import score_cached
         return score_cached(self._scorer(), sequences, start, cache, max_rows)
 
+    def score_streams_memory(self, inputs, targets, memory, spec, h=None, c=None):
+        """score_streams against a memory of hidden states (jlm_amd/memory.py): ``memory`` a
+        :class:`jlm_amd.memory.Memory` of this model (``Memory.build`` / ``Memory.load``), ``spec`` a :class:`jlm_amd.memory.MemorySpec`
+        (one theta or up to 16 for tuning, lam).  -> :class:`jlm_amd.memory.MemoryScores`: ``nll_lm`` [B, n] (score_streams' result, bit
+        for bit), ``logp_memory`` [n_theta, B, n], ``.nll(lam, theta_index)`` the mixture in float64, and ``h``, ``c`` to carry.  Every
+        position sees every entry of the memory, so a stream may be cut into calls any way.  ValueError before anything runs for a
+        bad argument or a memory of another model; JlmHipError when a hidden state or a key is not finite."""
+        from .memory import score_streams_memory
+        return score_streams_memory(self._scorer(), inputs, targets, memory, spec, h, c)
+
+    def score_memory(self, sequences, start, memory, spec, max_rows=None):
+        """score() against a memory: -> one float64 array per sequence of the per-word mixed -log p at ``spec.lam`` and the first theta
+        of ``spec``.  The row plan is score()'s, with the query rows and the key split's workspace counted into the bytes of a row."""
+        from .memory import score_memory
+        return score_memory(self._scorer(), sequences, start, memory, spec, max_rows)
+
     def _ranker(self):
         from .rank import Ranker
         return self._driver(Ranker)

@@ -30,6 +30,11 @@ after every line; a character model (config char_rnn) reads the characters of th
                    Rule rms takes its gradient statistics over --de-stat-chunks chunks of data/train.txt.  --tune-dynamic FILE sweeps
                    --de-lrs x --de-lams on FILE, the dev set, and reports the test perplexity at the best pair.  Not with --cache,
                    --ranks or --mode sentence.  Without --dynamic the output is what it was.
+  --memory MEM     stream mode: also score against the memory of hidden states saved in MEM (python -m jlm_amd.memory; jlm_amd/memory.py,
+                   DESIGN.md section 28) at --mem-theta and --mem-lam, in ONE pass -- LSTM_Model.score_streams_memory returns the plain
+                   -log p as well -- and print the perplexity under the memory after the plain one.  --tune-memory DEV sweeps --thetas
+                   and --lams on DEV and reports the test perplexity at the grid's best pair.  Not with --cache, --dynamic or --ngram.
+                   Without --memory the output is what it was.
 """
 import argparse
 import os
@@ -135,6 +140,20 @@ def cached_perplexity(parts, lam, theta_index=0):
     return float(np.exp(total / n_tok)), float(np.exp(mixed / n_tok)), n_tok
 
 
+def stream_memory_scores(model, stream, batch_size, num_steps, memory, spec):
+    """-> the :class:`jlm_amd.memory.MemoryScores` of every corpus_iterator chunk, state carried, as stream_perplexity"""
+    from .score import stream_layout
+    x, y = stream_layout(stream, batch_size, num_steps)
+    h = c = None
+    out = []
+    for i in range(x.shape[1] // num_steps):
+        cols = slice(i * num_steps, (i + 1) * num_steps)
+        res = model.score_streams_memory(x[:, cols], y[:, cols], memory, spec, h, c)
+        h, c = res.h, res.c
+        out.append(res)
+    return out
+
+
 def _floats(text, what, ap):
     try:
         return [float(x) for x in text.split(",") if x.strip()]
@@ -232,7 +251,29 @@ def main(argv=None, de_stepper=None):
     ap.add_argument("--tune-ngram", default=None, metavar="DEV", dest="tune_ngram", help="--ngram: pick lambda on this text file over --ngram-lams")
     ap.add_argument("--ngram-lams", default=",".join("%.2f" % (0.05 * i) for i in range(1, 20)), dest="ngram_lams",
                     help="--tune-ngram: the lambdas of the grid")
+    ap.add_argument("--memory", default=None, metavar="MEM", help="stream mode: also report the perplexity under the memory saved in MEM")
+    ap.add_argument("--mem-theta", type=float, default=0.3, dest="mem_theta", help="--memory: the flatness of the memory's distribution")
+    ap.add_argument("--mem-lam", type=float, default=0.1, dest="mem_lam", help="--memory: the weight of the memory in the mixture")
+    ap.add_argument("--tune-memory", default=None, metavar="DEV", dest="tune_memory",
+                    help="--memory: sweep --thetas x --lams on DEV (the dev set) and report the test perplexity at the best pair")
     args = ap.parse_args(argv)
+    if args.tune_memory and not args.memory:
+        ap.error("--tune-memory goes with --memory")
+    mem_spec = mem_tune_spec = None
+    if args.memory:
+        from .cache import check_lam as _check_lam
+        from .memory import MemorySpec
+        if args.mode != "stream" or args.cache or args.tune_cache or args.dynamic or args.ngram:
+            ap.error("--memory works in stream mode, without --cache, --dynamic and --ngram")
+        try:
+            mem_spec = MemorySpec(args.mem_theta, args.mem_lam)
+            if args.tune_memory:
+                mem_tune_lams = [_check_lam(x) for x in _floats(args.lams, "--lams", ap)]
+                if not mem_tune_lams:
+                    ap.error("--lams is empty")
+                mem_tune_spec = MemorySpec(_floats(args.thetas, "--thetas", ap))
+        except ValueError as e:
+            ap.error(str(e))
     if args.tune_ngram and not args.ngram:
         ap.error("--tune-ngram goes with --ngram")
     ngram_lams = None
@@ -298,6 +339,20 @@ def main(argv=None, de_stepper=None):
         if model is None:
             pp, _total, n_tok = _de.dynamic_perplexity(args.experiment_id, stream, _de.DynEvalSpec(0.0, batch_size=bs, num_steps=args.num_steps),
                                                        stepper=de_stepper)
+        elif mem_spec is not None:
+            from .memory import Memory, MemorySpec, tune as mem_tune
+            try:
+                memory = Memory.load(model, args.memory)
+            except (ValueError, OSError) as e:
+                ap.error(str(e))
+            if mem_tune_spec is not None:
+                dev_sents, _n = encode_lines(read_lines(args.tune_memory), vocab)
+                dev_parts = stream_memory_scores(model, [i for s in dev_sents for i in s], bs, args.num_steps, memory, mem_tune_spec)
+                best_theta, best_lam = mem_tune(dev_parts, mem_tune_lams)
+                mem_dev_pp = cached_perplexity(dev_parts, best_lam, mem_tune_spec.thetas.index(best_theta))
+                mem_spec = MemorySpec(best_theta, best_lam)
+                t0 = time.time()
+            pp, mem_pp, n_tok = cached_perplexity(stream_memory_scores(model, stream, bs, args.num_steps, memory, mem_spec), mem_spec.lam)
         elif spec is None:
             pp, _total, n_tok = stream_perplexity(model, stream, bs, args.num_steps)
         else:
@@ -318,6 +373,11 @@ def main(argv=None, de_stepper=None):
             args.tune_cache, spec.theta, spec.lam, dev_pp[0], dev_pp[1], len(tune_spec.thetas), len(tune_lams)))
     if spec is not None:
         print("Test perplexity with cache (N {} theta {} lam {}): {}".format(spec.size, spec.theta, spec.lam, cached_pp))
+    if mem_tune_spec is not None:
+        print("Memory tuned on {}: theta {} lam {}  (dev perplexity {} -> {} over {} x {} pairs)".format(
+            args.tune_memory, mem_spec.theta, mem_spec.lam, mem_dev_pp[0], mem_dev_pp[1], len(mem_tune_spec.thetas), len(mem_tune_lams)))
+    if mem_spec is not None:
+        print("Test perplexity with memory (N {} theta {} lam {}): {}".format(memory.N, mem_spec.theta, mem_spec.lam, mem_pp))
     if args.ngram:
         from .ngram import NGramTable
         ng_path = args.ngram if os.path.exists(args.ngram) else os.path.join(_config.data_path, args.ngram)

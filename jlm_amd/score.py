@@ -92,7 +92,8 @@ class Scorer:
         """One call: word / target [n_steps, R] int32 (host), n_live [n_steps] (host; non-increasing, rows live as a prefix).  h, c:
         the state to continue ([R, H] device tensors in the model's state-row format, as returned here), None = the zero state.
         rings: a :class:`jlm_amd.cache.Rings` made for this call's (R, n_steps) -- the op is then ``score_cache_frames``, the same
-        launches with the cache pass behind them, and the rings hold the call's states, words and lpc afterwards.
+        launches with the cache pass behind them, and the rings hold the call's states, words and lpc afterwards -- or a
+        :class:`jlm_amd.memory.MemoryRings`, whose ``op`` names ``score_memory_frames``: the same launches with the memory pass behind.
         -> (nll_seq [R] f64, nll_tok [n_steps, R] f64 or None, h, c) -- numpy results, the state after the last step on the device.
         The returned h, c are the row set the LAST step wrote: they hold the final state of the rows live at that step.  A row that
         stopped being live earlier is UNDEFINED there (its final state is in the other set when its length and n_steps differ in
@@ -116,7 +117,7 @@ class Scorer:
             if rings is None:
                 ms = _ops.backend().score_frames(*args)
             else:
-                ms = _ops.backend().score_cache_frames(*args, *rings.op_args(R, S))
+                ms = getattr(_ops.backend(), getattr(rings, "op", "score_cache_frames"))(*args, *rings.op_args(R, S))
             if timed:
                 self.last_step_ms = ms.numpy()
             rs.check_flags("score_fold_kernel flagged a target outside the model's segments (flags %d)",
