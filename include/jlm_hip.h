@@ -1101,6 +1101,53 @@ int jlm_score_memory_frames(const jlm_decode_model *model_host, const jlm_score_
                             void *stream, void *const *events);
 
 /* ------------------------------------------------------------------------
+ * Exact top-K retrieval over a memory (Memory.search, jlm_amd/memory.py memory_neighbours / memory_distribution):
+ * the mass of a memory on EVERY word, carried by the K nearest entries of the query.  Additive to ABI 12.
+ *
+ * A memory (k_i, v_i), i < N, a query state h_q, theta >= 0, 1 <= K <= JLM_MEMORY_TOPK_MAX, n_q = min(K, N), s_i = theta * (h_q . k_i)
+ * as above.  T_K(q) is the n_q entries that come first in the total order "larger s_i first, smaller i first among equal s_i".  For
+ * every word w
+ *   c_q(w) = sum_{i in T_K, v_i = w} exp(s_i) / sum_{i in T_K} exp(s_i)
+ *   p_q(w) = (1 - lambda) p_lm(w) + lambda c_q(w)             lambda = 0: p_lm, the same bits
+ * With K >= N this is the distribution of the section above.  As a patch of a row's logits it is jlm_cache_mix_rows' definition below,
+ * word for word, with T_K in the place of the window: rho = lambda / (1 - lambda),
+ *   y'[w] = logaddexp(y[w], L + log rho + log c_q(w)) on the retrieved words, the same bits elsewhere.  One theta, lambda and K a call.
+ *
+ * jlm_memory_topk (csrc/jlm_memory_topk.hip: memory_topk_score_kernel, memory_topk_select_kernel):
+ *   keys, key_words, N, H, split, h_scale     the memory, as jlm_memory_rows takes it
+ *   q_rows    [n_rows_max][H]        one query per row -- row r < min(*n_dev, n_rows_max) is live (n_dev NULL: n_rows_max; a device
+ *                                    int) -- the state rows a step just wrote, in the memory's format; rows that are not live are
+ *                                    never read
+ * For each live row r, entry j < n_q is the j-th of T_K, best first:
+ *   s[r * ld_s + j]                  its score, f32 (ld_s >= K)
+ *   ret_words[j * n_rows + r]        v_i       ([K][n_rows] int32, n_rows >= n_rows_max)
+ *   ret_idx[j * n_rows + r]          i         (the same shape; may be NULL)
+ * Entries j >= n_q and rows that are not live are left exactly as they were.  jlm_cache_mix_rows runs on these arrays unchanged:
+ * ret_words is its words [cap][n_rows] with cap = N_window = K and pos = n_q, first a device array of zeros, s is its s.
+ * Products: memory_rows_kernel's instructions in its k order -- split rows: three v_mfma_f32_32x32x16_f16 per 16 k over the stored
+ * halves (hi.hi, hi.lo, lo.hi; 1 / h_scale^2 folded into theta), f32 rows: v_mfma_f32_32x32x2_f32 -- and s_i = f32(theta' * dot) + 0
+ * (a zero score is +0).  The bits of s_i are a function of (query row, key row, theta) alone.
+ * Selection: exact.  Scores are compared by their bits' order-preserving integer image above the complement of the index, so equal
+ * score bits resolve to the smaller index and no two entries compare equal.  The memory is walked in chunks of
+ * jlm_memory_topk_chunk_keys(N, n_rows_max, K, workspace_bytes) keys -- a multiple of 32, as many as the workspace holds, at most N
+ * rounded up -- and a chunk's winners are merged with the running list of the earlier chunks; the result does not depend on the
+ * chunk, on the row's position in the launch, on the other rows or how many are live, on what the workspace or the outputs held
+ * before, or on the order any LDS counter is served in (integer counts only; no float atomics).  The workspace is
+ * [n_rows_max][chunk] f32 scores and [n_rows_max][K] 8-byte list entries; jlm_memory_topk_workspace_bytes(N, n_rows_max, K) is the
+ * least it may be (a chunk of 32 keys); every word of it that is read was written by the same call.
+ * flags (one device int, may be NULL): |= 1 when a score of a live row is not finite.
+ * Returns -1 before any launch for jlm_memory_rows' conditions on N, H, theta, h_scale, alignment (the workspace: 16 bytes) and NULL
+ * pointers (n_dev, ret_idx and flags may be NULL), K outside [1, JLM_MEMORY_TOPK_MAX], ld_s < K, n_rows_max outside [0, n_rows],
+ * n_rows > 65535, workspace_bytes below jlm_memory_topk_workspace_bytes(...); 0 with nothing launched for n_rows_max == 0; else 0 or
+ * a hipError_t. */
+#define JLM_MEMORY_TOPK_MAX 1024
+size_t jlm_memory_topk_workspace_bytes(int N, int n_rows_max, int K);      /* 0 for arguments the launcher refuses */
+int jlm_memory_topk_chunk_keys(int N, int n_rows_max, int K, size_t workspace_bytes);      /* 0 where the launcher refuses */
+int jlm_memory_topk(const void *keys, const int *key_words, int N, int H, int split, float h_scale, const void *q_rows, int n_rows_max,
+                    const int *n_dev, float theta, int K, float *s, int ld_s, int *ret_words, int *ret_idx, int n_rows, void *workspace,
+                    size_t workspace_bytes, int *flags, void *stream);
+
+/* ------------------------------------------------------------------------
  * The continuous cache on the decode side: the cache distribution over EVERY word of the window, as a patch of a row's materialised
  * logits (csrc/jlm_cache_mix.hip, jlm_amd/cache.py cache_distribution / mixed_logits).  Additive to ABI 12.
  *
@@ -1206,6 +1253,58 @@ typedef struct {
  * -2 for an untied split-row model -- its vocabulary GEMMs read the f32 copy of the state that only the LSTM step writes -- and
  * otherwise as the launchers do. */
 int jlm_predict_cache_rows(const jlm_decode_model *model_host, const jlm_predict_cache_plan *plan_host, void *stream);
+
+/* What a ranking call under a memory has beside its jlm_rank_plan (whose layout is unchanged): the memory, one theta / lambda / K, and
+ * the retrieval's buffers over the plan's n_rows rows (jlm_memory_topk's, above). */
+typedef struct {
+    const void *keys; const int *key_words; int N;    /* the memory; read only */
+    float theta, lam; int K;
+    float *s; int ld_s;                 /* [n_rows][ld_s] device scratch: the scores of one step's neighbours, ld_s >= K */
+    int *ret_words;                     /* [K][n_rows] device scratch: their words */
+    int *ret_idx;                       /* [K][n_rows] device scratch, or with keep_idx != 0 [n_steps][K][n_rows]: every step's indices */
+    int keep_idx;
+    const int *first;                   /* [n_rows] device zeros: jlm_cache_mix_rows' `first` */
+    void *workspace; size_t workspace_bytes;
+    int top_k;                          /* 0: no lists */
+    int *top_ids; double *top_nll;      /* [n_steps][n_rows][top_k] device: jlm_topk_rows over the patched rows of every step */
+    int *flags;                         /* one device int or NULL: the bits of jlm_memory_topk / jlm_cache_mix_rows */
+} jlm_memory_mix_plan;
+
+/* jlm_rank_frames' loop -- the same launches in the same order -- with, per step, between the logit GEMMs and the ranking,
+ * jlm_memory_topk on the state set the step wrote and jlm_cache_mix_rows on the logits (words = ret_words, cap = N_window = K,
+ * pos = min(K, N)), so that rank_rows_kernel ranks target[t] under p_q of the section "Exact top-K retrieval" above; behind the
+ * ranking, with top_k > 0, jlm_topk_rows over the n_live_host[t] live rows (n_live_host is required then; its flags go to the rank
+ * plan's).  Nothing is written to the memory and no ring is kept.  No host synchronisation.  Every refusal of the two launchers,
+ * top_k outside 0 .. min(JLM_TOPK_MAX, V) and an n_live_host[t] outside [0, n_rows] is returned before the first launch.  events (may
+ * be NULL): JLM_RANK_MEMORY_EVENTS_PER_STEP * n_steps hipEvent_t, [0] .. [3] as jlm_rank_frames', [4] after the retrieval, [5] after
+ * the patch, [6] after the ranking and the lists.  Returns as jlm_rank_frames does. */
+#define JLM_RANK_MEMORY_EVENTS_PER_STEP 7
+int jlm_rank_memory_frames(const jlm_decode_model *model_host, const jlm_rank_plan *plan_host, const jlm_memory_mix_plan *memory_host,
+                           void *stream, void *const *events);
+
+/* One step of prediction under a memory, for a caller who holds the carried state of n_rows streams. */
+typedef struct {
+    int n_rows;
+    const void *h;                      /* [n_rows, H] the carried state rows, in the model's state-row format */
+    float *T;                           /* [n_rows, ldt] f32 scratch (an untied f32 model: unused, T is h) */
+    float *logits; int ld_logits;       /* [n_rows, ld_logits] f32 scratch, ld_logits >= V rounded up to 4 */
+    const int *rows;                    /* [n_rows] device: 0, 1, ..., n_rows - 1 */
+    const void *keys; const int *key_words; int N;
+    float theta, lam; int K;
+    float *s; int ld_s; int *ret_words; int *ret_idx;      /* jlm_memory_topk's outputs over n_rows rows; ret_idx may be NULL */
+    const int *first;                   /* [n_rows] device zeros */
+    void *workspace; size_t workspace_bytes;
+    int k;                              /* 1 .. min(JLM_TOPK_MAX, V) */
+    const unsigned *mask; int ld_mask, n_sets; const int *row_set;    /* jlm_topk_rows_masked's; row_set NULL: jlm_topk_rows */
+    int *ids; double *nll;              /* [n_rows][k] device */
+    int *flags;                         /* one device int or NULL: the selection's */
+    int *memory_flags;                  /* one device int or NULL: the bits of jlm_memory_topk / jlm_cache_mix_rows */
+} jlm_predict_memory_plan;
+
+/* jlm_predict_cache_rows with the retrieval in the query's place: the T projection of h, the logits, jlm_memory_topk, the patch and
+ * jlm_topk_rows (row_set: _masked).  No LSTM step, no host synchronisation; every refusal before the first launch.  Returns -2 for an
+ * untied split-row model, for jlm_predict_cache_rows' reason, and otherwise as the launchers do. */
+int jlm_predict_memory_rows(const jlm_decode_model *model_host, const jlm_predict_memory_plan *plan_host, void *stream);
 
 /* ------------------------------------------------------------------------
  * Left context of a decode (LSTM_Model.prime, Decoder.decode(context=), jlm_amd/context.py).  Sentence s with the committed words

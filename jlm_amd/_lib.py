@@ -127,6 +127,24 @@ class PredictCachePlan(Structure):
                 ("cache_flags", c_void_p)]
 
 
+class MemoryMixPlan(Structure):
+    """jlm_memory_mix_plan (include/jlm_hip.h)."""
+    _fields_ = [("keys", c_void_p), ("key_words", c_void_p), ("N", c_int), ("theta", c_float), ("lam", c_float), ("K", c_int),
+                ("s", c_void_p), ("ld_s", c_int), ("ret_words", c_void_p), ("ret_idx", c_void_p), ("keep_idx", c_int), ("first", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("top_k", c_int), ("top_ids", c_void_p), ("top_nll", c_void_p),
+                ("flags", c_void_p)]
+
+
+class PredictMemoryPlan(Structure):
+    """jlm_predict_memory_plan (include/jlm_hip.h)."""
+    _fields_ = [("n_rows", c_int), ("h", c_void_p), ("T", c_void_p), ("logits", c_void_p), ("ld_logits", c_int), ("rows", c_void_p),
+                ("keys", c_void_p), ("key_words", c_void_p), ("N", c_int), ("theta", c_float), ("lam", c_float), ("K", c_int),
+                ("s", c_void_p), ("ld_s", c_int), ("ret_words", c_void_p), ("ret_idx", c_void_p), ("first", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("k", c_int), ("mask", c_void_p), ("ld_mask", c_int),
+                ("n_sets", c_int), ("row_set", c_void_p), ("ids", c_void_p), ("nll", c_void_p), ("flags", c_void_p),
+                ("memory_flags", c_void_p)]
+
+
 class NgramRows(Structure):
     """jlm_ngram_rows (include/jlm_hip.h)."""
     _fields_ = [("uni_lp", c_void_p), ("uni_bow", c_void_p), ("bi_off", c_void_p), ("bi_w", c_void_p), ("bi_lp", c_void_p), ("n_bi", c_int),
@@ -229,6 +247,11 @@ _SIGS = {
     "jlm_memory_workspace_bytes": ([c_int, c_int, c_int, c_int], c_size_t),
     "jlm_memory_rows": ([P, P, c_int, c_int, c_int, c_float, P, P, c_int, c_int, P, POINTER(c_float), c_int, P, P, c_size_t, P, P], c_int),
     "jlm_score_memory_frames": ([POINTER(DecodeModel), POINTER(ScorePlan), POINTER(MemoryPlan), P, P], c_int),
+    "jlm_memory_topk_workspace_bytes": ([c_int, c_int, c_int], c_size_t),
+    "jlm_memory_topk_chunk_keys": ([c_int, c_int, c_int, c_size_t], c_int),
+    "jlm_memory_topk": ([P, P, c_int, c_int, c_int, c_float, P, c_int, P, c_float, c_int, P, c_int, P, P, c_int, P, c_size_t, P, P], c_int),
+    "jlm_rank_memory_frames": ([POINTER(DecodeModel), POINTER(RankPlan), POINTER(MemoryMixPlan), P, P], c_int),
+    "jlm_predict_memory_rows": ([POINTER(DecodeModel), POINTER(PredictMemoryPlan), P], c_int),
     "jlm_cache_query": ([P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_int, P, c_int, c_float, P, c_int, P, P], c_int),
     "jlm_cache_mix_rows": ([P, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, c_int, c_float, P, P, P], c_int),
     "jlm_rank_cache_frames": ([POINTER(DecodeModel), POINTER(RankPlan), POINTER(CacheMixPlan), P, P], c_int),

@@ -850,6 +850,85 @@ extern "C" int jlm_predict_cache_rows(const jlm_decode_model *m, const jlm_predi
     return jlm_topk_rows(p->logits, p->ld_logits, V, R, p->k, m->self_norm, p->ids, p->nll, p->k, p->flags, stream);
 }
 
+// the refusals of jlm_memory_topk on their own (csrc/jlm_memory_topk.hip)
+int jlm_memory_topk_refuse(const void *keys, const int *key_words, int N, int H, int split, float h_scale, const void *q_rows, int n_rows_max,
+                           const int *n_dev, float theta, int K, const float *s, int ld_s, const int *ret_words, const int *ret_idx, int n_rows,
+                           const void *workspace, size_t workspace_bytes, const int *flags);
+
+// Ranking under a memory (include/jlm_hip.h jlm_rank_memory_frames): rank_loop with the logits of every step patched into the mixed
+// distribution before they are ranked -- the retrieval on the state set the step wrote, then cache_mix_rows_kernel over the retrieved
+// entries as a window of min(K, N) positions in a ring of K slots -- and an optional top-k list of the patched rows.
+extern "C" int jlm_rank_memory_frames(const jlm_decode_model *m, const jlm_rank_plan *p, const jlm_memory_mix_plan *mp, void *stream,
+                                      void *const *events) {
+    if (!m || !p || !mp || m->n_segs < 1) return -1;
+    const int R = p->n_rows, S = p->n_steps;
+    if (R < 0 || S < 0) return -1;
+    const int split = m->split_lstm ? 1 : 0;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    JLM_TRY(jlm_memory_topk_refuse(mp->keys, mp->key_words, mp->N, m->H, split, m->h_scale, p->h[0], R, p->n_live, mp->theta, mp->K, mp->s,
+                                   mp->ld_s, mp->ret_words, mp->ret_idx, R, mp->workspace, mp->workspace_bytes, mp->flags));
+    const int n_q = mp->K < mp->N ? mp->K : mp->N;
+    JLM_TRY(jlm_cache_mix_refuse(p->logits, p->ld_logits, V, mp->s, mp->ld_s, mp->ret_words, mp->K, R, R, p->n_live, n_q, mp->first, mp->K,
+                                 mp->lam, nullptr, mp->flags));
+    if (mp->keep_idx && !mp->ret_idx) return -1;
+    if (mp->top_k < 0 || mp->top_k > JLM_TOPK_MAX || mp->top_k > V) return -1;
+    if (mp->top_k > 0 && (!mp->top_ids || !mp->top_nll || !p->n_live_host)) return -1;
+    if (p->n_live_host)
+        for (int t = 0; t < S; ++t)
+            if (p->n_live_host[t] < 0 || p->n_live_host[t] > R) return -1;
+    return rank_loop(
+        m, p, stream, events, JLM_RANK_MEMORY_EVENTS_PER_STEP,
+        [&](int t, int bound, const void *h_out, const int *ndev, const Stamps &stamp) -> int {
+            int *idx = mp->keep_idx ? mp->ret_idx + (size_t)t * mp->K * R : mp->ret_idx;
+            if (bound > 0)
+                JLM_TRY(jlm_memory_topk(mp->keys, mp->key_words, mp->N, m->H, split, m->h_scale, h_out, bound, ndev, mp->theta, mp->K, mp->s,
+                                        mp->ld_s, mp->ret_words, idx, R, mp->workspace, mp->workspace_bytes, mp->flags, stream));
+            JLM_TRY(stamp(t, 4));
+            if (bound > 0)
+                JLM_TRY(jlm_cache_mix_rows(p->logits, p->ld_logits, V, m->self_norm, mp->s, mp->ld_s, mp->ret_words, mp->K, R, bound, ndev, n_q,
+                                           mp->first, mp->K, mp->lam, nullptr, mp->flags, stream));
+            return stamp(t, 5);
+        },
+        [&](int t, int, const void *) -> int {
+            if (mp->top_k > 0 && p->n_live_host[t] > 0)
+                JLM_TRY(jlm_topk_rows(p->logits, p->ld_logits, V, p->n_live_host[t], mp->top_k, m->self_norm,
+                                      mp->top_ids + (size_t)t * R * mp->top_k, mp->top_nll + (size_t)t * R * mp->top_k, mp->top_k, p->flags,
+                                      stream));
+            return 0;
+        });
+}
+
+// One step of prediction under a memory (include/jlm_hip.h jlm_predict_memory_rows): jlm_predict_cache_rows with the retrieval in the
+// query's place.  No LSTM step.
+extern "C" int jlm_predict_memory_rows(const jlm_decode_model *m, const jlm_predict_memory_plan *p, void *stream) {
+    if (!m || !p || m->n_segs < 1) return -1;
+    const int R = p->n_rows;
+    if (R < 0 || !p->rows || !p->logits || !p->ids || !p->nll) return -1;
+    if (m->untied && m->split_lstm) return -2;                     // its vocabulary GEMMs read the f32 copy only the LSTM step writes
+    const int split = m->split_lstm ? 1 : 0;
+    const int V = m->segs[m->n_segs - 1].v_end;
+    JLM_TRY(jlm_memory_topk_refuse(p->keys, p->key_words, p->N, m->H, split, m->h_scale, p->h, R, nullptr, p->theta, p->K, p->s, p->ld_s,
+                                   p->ret_words, p->ret_idx, R, p->workspace, p->workspace_bytes, p->memory_flags));
+    const int n_q = p->K < p->N ? p->K : p->N;
+    JLM_TRY(jlm_cache_mix_refuse(p->logits, p->ld_logits, V, p->s, p->ld_s, p->ret_words, p->K, R, R, nullptr, n_q, p->first, p->K, p->lam,
+                                 nullptr, p->memory_flags));
+    if (p->k < 1 || p->k > JLM_TOPK_MAX || p->k > V) return -1;
+    if (p->row_set && (p->n_sets < 0 || (p->n_sets > 0 && (!p->mask || p->ld_mask < (V + 31) / 32)))) return -1;
+    if (R == 0) return 0;
+    JLM_TRY(rows_refuse(m, p->T));
+    float *T = t_is_state(m) ? (float *)const_cast<void *>(p->h) : p->T;
+    JLM_TRY(rows_t_projection(m, const_cast<void *>(p->h), p->rows, T, R, nullptr, stream));
+    JLM_TRY(rows_logits(m, T, p->logits, p->ld_logits, R, stream));
+    JLM_TRY(jlm_memory_topk(p->keys, p->key_words, p->N, m->H, split, m->h_scale, p->h, R, nullptr, p->theta, p->K, p->s, p->ld_s, p->ret_words,
+                            p->ret_idx, R, p->workspace, p->workspace_bytes, p->memory_flags, stream));
+    JLM_TRY(jlm_cache_mix_rows(p->logits, p->ld_logits, V, m->self_norm, p->s, p->ld_s, p->ret_words, p->K, R, R, nullptr, n_q, p->first, p->K,
+                               p->lam, nullptr, p->memory_flags, stream));
+    if (p->row_set)
+        return jlm_topk_rows_masked(p->logits, p->ld_logits, V, R, p->k, m->self_norm, p->mask, p->ld_mask, p->n_sets, p->row_set, p->ids,
+                                    p->nll, p->k, p->flags, stream);
+    return jlm_topk_rows(p->logits, p->ld_logits, V, R, p->k, m->self_norm, p->ids, p->nll, p->k, p->flags, stream);
+}
+
 // Ancestral sampling (include/jlm_hip.h jlm_generate_frames): the prompt frames step the LSTM of their live prefix only; every drawing
 // frame steps all rows, projects T, materialises the full-vocabulary logits (one jlm_gemm_nt per segment, columns v_start .. v_end of
 // plan.logits, + b2) and draws with sample_rows_kernel, which also writes the word the next frame consumes.  With top_k / top_p on

@@ -35,6 +35,11 @@
 //   torch.ops.jlm.rank_cache_frames / predict_cache_rows
 //                             the same under the continuous cache, and its one-step prediction form (jlm_rank_cache_frames,
 //                             jlm_predict_cache_rows; LSTM_Model.rank_streams_cached / rank_cached / predict_next_cached)
+//   torch.ops.jlm.memory_topk(keys, key_words, ..., q_rows, theta, K, s, ret_words, ret_idx, workspace, flags)
+//                             the K nearest entries of a memory for every query row (jlm_memory_topk; Memory.search)
+//   torch.ops.jlm.rank_memory_frames / predict_memory_rows
+//                             rank_frames under a memory's K nearest entries, and its one-step prediction form (jlm_rank_memory_frames,
+//                             jlm_predict_memory_rows; LSTM_Model.rank_streams_memory / rank_memory / predict_next_memory)
 //   torch.ops.jlm.prime_frames(Model, state row sets, rows, prev, word, n_live, ...)
 //                             the state after a left context: LSTM steps only, ONE op (jlm_prime_frames; LSTM_Model.prime)
 //   torch.ops.jlm.seed_context(Plan, src_h, src_c, last, has, idx)
@@ -1010,6 +1015,59 @@ Tensor rank_cache_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor
                          [&](hipStream_t st, void *const *ev) { return jlm_rank_cache_frames(&m, &rp.p, &cp, st, ev); });
 }
 
+// The memory and the retrieval's buffers of a mixing op (rank_memory_frames, predict_memory_rows), checked, into its plan
+// (jlm_memory_mix_plan, jlm_predict_memory_plan): `n_idx` sets of ret_idx [K][n_rows].
+template <class Plan>
+void memory_mix_into(const char *op, Plan &mp, int64_t H, int64_t R, const Tensor &keys, const Tensor &key_words, int64_t N, double theta,
+                     double lam, int64_t K, const Tensor &s, int64_t ld_s, const Tensor &ret_words, const OptTensor &ret_idx, int64_t n_idx,
+                     const Tensor &first, const Tensor &workspace, const OptTensor &mem_flags) {
+    TORCH_CHECK(N >= 1 && N <= JLM_MEMORY_MAX_KEYS && K >= 1 && K <= JLM_MEMORY_TOPK_MAX && ld_s >= K && ld_s <= INT32_MAX && R <= 65535,
+                "jlm.", op, ": 1 <= N <= ", JLM_MEMORY_MAX_KEYS, ", 1 <= K <= ", JLM_MEMORY_TOPK_MAX, ", ld_s >= K, n_rows <= 65535");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam >= 0.0 && lam < 1.0, "jlm.", op, ": theta finite and >= 0, lam in [0, 1)");
+    TORCH_CHECK(keys.defined() && keys.element_size() == 4 && keys.numel() >= N * H && is(key_words, at::kInt, N),
+                "jlm.", op, ": keys [N][H] of 4-byte values, int32 key_words [N]");
+    const size_t need = jlm_memory_topk_workspace_bytes((int)N, (int)R, (int)K);
+    TORCH_CHECK(is(s, at::kFloat, R * ld_s) && is(ret_words, at::kInt, K * R) && opt_ok(ret_idx, at::kInt, n_idx * K * R) && is(first, at::kInt, R) &&
+                    is(workspace, at::kFloat, (int64_t)(need / 4)) && opt_ok(mem_flags, at::kInt, 1),
+                "jlm.", op, ": float32 s [n_rows][ld_s], int32 ret_words / ret_idx [K][n_rows], int32 first [n_rows], a float32 workspace of "
+                "jlm_memory_topk_workspace_bytes, int32 mem_flags");
+    mp.keys = ptr<const void>(keys, "keys"); mp.key_words = ptr<const int>(key_words, "key_words"); mp.N = (int)N;
+    mp.theta = (float)theta; mp.lam = (float)lam; mp.K = (int)K;
+    mp.s = ptr<float>(s, "s"); mp.ld_s = (int)ld_s; mp.ret_words = ptr<int>(ret_words, "ret_words"); mp.ret_idx = optr<int>(ret_idx, "ret_idx");
+    mp.first = ptr<const int>(first, "first"); mp.workspace = ptr<void>(workspace, "workspace");
+    mp.workspace_bytes = (size_t)workspace.numel() * 4;
+}
+
+// rank_frames under a memory (jlm_rank_memory_frames, include/jlm_hip.h): its arguments, then the memory keys [N][H] / key_words [N],
+// theta, lam, K, the scratch s [n_rows][ld_s] float32 and ret_words [K][n_rows] int32, ret_idx int32 [K][n_rows] (keep_idx:
+// [n_steps][K][n_rows], every step's neighbours), first [n_rows] int32 zeros, the workspace, top_k with top_ids int32 / top_nll float64
+// [n_steps][n_rows][top_k] (top_k = 0: none), mem_flags one int32.  -> timed: [n_steps, 6] milliseconds per step (LSTM step, T
+// projection, logit GEMMs, retrieval, patch, ranking with the lists); else an empty tensor.
+Tensor rank_memory_frames(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h0, const Tensor &c0, const Tensor &h1, const Tensor &c1,
+                          const OptTensor &T, const Tensor &logits, int64_t ld_logits, const Tensor &rows, const Tensor &prev0,
+                          const Tensor &word, const Tensor &target, const Tensor &n_live, std::vector<int64_t> n_live_host, const OptTensor &ids,
+                          const OptTensor &lv_off, const OptTensor &lv_lo, const OptTensor &lv_hi, int64_t n_levels, const Tensor &rank,
+                          const OptTensor &flags, int64_t n_rows, int64_t n_steps, bool timed, const Tensor &keys, const Tensor &key_words,
+                          int64_t N, double theta, double lam, int64_t K, const Tensor &s, int64_t ld_s, const Tensor &ret_words,
+                          const Tensor &ret_idx, bool keep_idx, const Tensor &first, const Tensor &workspace, int64_t top_k,
+                          const OptTensor &top_ids, const OptTensor &top_nll, const OptTensor &mem_flags) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows, S = n_steps;
+    const RankPlanArgs rp("rank_memory_frames", m, h0, c0, h1, c1, T, logits, ld_logits, rows, prev0, word, target, n_live, n_live_host, ids,
+                          lv_off, lv_lo, lv_hi, n_levels, rank, flags, R, S);
+    jlm_memory_mix_plan mp{};
+    memory_mix_into("rank_memory_frames", mp, m.H, R, keys, key_words, N, theta, lam, K, s, ld_s, ret_words, ret_idx, keep_idx ? S : 1, first,
+                    workspace, mem_flags);
+    TORCH_CHECK(top_k >= 0 && top_k <= JLM_TOPK_MAX && top_k <= rp.V &&
+                    (top_k == 0 || (has(top_ids) && has(top_nll) && is(*top_ids, at::kInt, S * R * top_k) && is(*top_nll, at::kDouble, S * R * top_k))),
+                "jlm.rank_memory_frames: top_k in 0 .. min(", JLM_TOPK_MAX, ", V) with int32 top_ids / float64 top_nll [n_steps][n_rows][top_k]");
+    mp.keep_idx = keep_idx ? 1 : 0; mp.top_k = (int)top_k;
+    mp.top_ids = top_k > 0 ? ptr<int>(*top_ids, "top_ids") : nullptr; mp.top_nll = top_k > 0 ? ptr<double>(*top_nll, "top_nll") : nullptr;
+    mp.flags = optr<int>(mem_flags, "mem_flags");
+    return launch_frames("jlm_rank_memory_frames", h0.device().index(), timed, R > 0 ? S : 0, JLM_RANK_MEMORY_EVENTS_PER_STEP,
+                         [&](hipStream_t st, void *const *ev) { return jlm_rank_memory_frames(&m, &rp.p, &mp, st, ev); });
+}
+
 // one draw per row of f32 logits y [n_rows, ld] (jlm_sample_rows, include/jlm_hip.h).  seed: the uint64 seed's bits as int64.
 void sample_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, const OptTensor &n_dev, double temperature, int64_t seed,
                  int64_t step, const OptTensor &row_id, const OptTensor &forced, const OptTensor &done, int64_t stop_id, bool self_norm,
@@ -1117,6 +1175,32 @@ void topk_rows(const Tensor &y, int64_t ld, int64_t n_cols, int64_t n_rows, int6
               "jlm_topk_rows");
 }
 
+// the K nearest entries of a memory for every query row (jlm_memory_topk, include/jlm_hip.h): keys [N][H] of 4-byte values and int32
+// key_words [N]; q_rows [n_rows][H] in the same format, every row live; s float32 [n_rows, ld_s], ret_words / ret_idx int32
+// [K][n_rows]; the workspace float32 of at least jlm_memory_topk_workspace_bytes, flags one int32.
+void memory_topk(const Tensor &keys, const Tensor &key_words, int64_t N, int64_t H, bool split, double h_scale, const Tensor &q_rows,
+                 int64_t n_rows, double theta, int64_t K, const Tensor &s, int64_t ld_s, const Tensor &ret_words, const Tensor &ret_idx,
+                 const Tensor &workspace, const OptTensor &flags) {
+    TORCH_CHECK(N >= 1 && N <= JLM_MEMORY_MAX_KEYS && K >= 1 && K <= JLM_MEMORY_TOPK_MAX && ld_s >= K && ld_s <= INT32_MAX && H >= 1 &&
+                    H <= INT32_MAX && n_rows >= 0 && n_rows <= 65535,
+                "jlm.memory_topk: 1 <= N <= ", JLM_MEMORY_MAX_KEYS, ", 1 <= K <= ", JLM_MEMORY_TOPK_MAX, ", ld_s >= K, 0 <= n_rows <= 65535");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38, "jlm.memory_topk: theta finite and >= 0");
+    TORCH_CHECK(keys.defined() && keys.element_size() == 4 && keys.numel() >= N * H && is(key_words, at::kInt, N),
+                "jlm.memory_topk: keys [N][H] of 4-byte values, int32 key_words [N]");
+    TORCH_CHECK(q_rows.defined() && q_rows.element_size() == 4 && q_rows.numel() >= n_rows * H, "jlm.memory_topk: q_rows [n_rows][H] of 4-byte values");
+    const size_t need = jlm_memory_topk_workspace_bytes((int)N, (int)n_rows, (int)K);
+    TORCH_CHECK(is(s, at::kFloat, n_rows * ld_s) && is(ret_words, at::kInt, K * n_rows) && is(ret_idx, at::kInt, K * n_rows) &&
+                    is(workspace, at::kFloat, (int64_t)(need / 4)) && opt_ok(flags, at::kInt, 1),
+                "jlm.memory_topk: float32 s [n_rows, ld_s], int32 ret_words / ret_idx [K][n_rows], a float32 workspace of "
+                "jlm_memory_topk_workspace_bytes, int32 flags");
+    const c10::hip::HIPGuard device_guard(keys.device().index());
+    jlm_check(jlm_memory_topk(ptr<const void>(keys, "keys"), ptr<const int>(key_words, "key_words"), (int)N, (int)H, split ? 1 : 0, (float)h_scale,
+                              ptr<const void>(q_rows, "q_rows"), (int)n_rows, nullptr, (float)theta, (int)K, ptr<float>(s, "s"), (int)ld_s,
+                              ptr<int>(ret_words, "ret_words"), ptr<int>(ret_idx, "ret_idx"), (int)n_rows, ptr<void>(workspace, "workspace"),
+                              (size_t)workspace.numel() * 4, optr<int>(flags, "flags"), stream_of(keys)),
+              "jlm_memory_topk");
+}
+
 // A word-set mask and its per-row set indices, checked on the host and the indices put on the device (jlm_topk_rows_masked, include/
 // jlm_hip.h): mask int32 [n_sets, ld_mask] holding the 32-bit words' bits, row_set one index in [-1, n_sets) per row.
 Tensor check_word_sets(const char *op, const Tensor &mask, int64_t ld_mask, int64_t n_sets, int64_t n_cols, const std::vector<int64_t> &row_set,
@@ -1191,6 +1275,46 @@ void predict_cache_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor 
     p.cache_flags = optr<int>(cache_flags, "cache_flags");
     const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
     jlm_check(jlm_predict_cache_rows(&m, &p, stream_of(logits)), "jlm_predict_cache_rows");
+}
+
+// One step of prediction under a memory (jlm_predict_memory_rows, include/jlm_hip.h): predict_cache_rows with the memory and the
+// retrieval's buffers, as rank_memory_frames takes them, in the rings' place.  ids int32 / nll float64 [n_rows, k].
+void predict_memory_rows(const c10::intrusive_ptr<JlmModel> &model, const Tensor &h, const OptTensor &T, const Tensor &logits,
+                         int64_t ld_logits, const Tensor &rows, const Tensor &keys, const Tensor &key_words, int64_t N, double theta, double lam,
+                         int64_t K, const Tensor &s, int64_t ld_s, const Tensor &ret_words, const OptTensor &ret_idx, const Tensor &first,
+                         const Tensor &workspace, int64_t k, const OptTensor &mask, int64_t ld_mask, int64_t n_sets,
+                         std::vector<int64_t> row_set, const Tensor &ids, const Tensor &nll, const OptTensor &flags, const OptTensor &mem_flags,
+                         int64_t n_rows) {
+    const jlm_decode_model &m = model->m;
+    const int64_t R = n_rows;
+    TORCH_CHECK(m.n_segs >= 1, "jlm.predict_memory_rows: a model without segments");
+    TORCH_CHECK(!(m.untied && m.split_lstm), "jlm.predict_memory_rows: an untied split-row model keeps the f32 copy of its state, which its "
+                                             "vocabulary GEMMs read, only inside the LSTM step: there is no one-step form for it");
+    const int64_t V = m.segs[m.n_segs - 1].v_end;
+    TORCH_CHECK(R >= 0 && R <= 65535 && h.defined() && h.element_size() == 4 && h.numel() >= R * m.H && is(rows, at::kInt, R),
+                "jlm.predict_memory_rows: h [n_rows, H] of 4-byte values, int32 rows [n_rows], n_rows <= 65535");
+    TORCH_CHECK(!has(T) || is(*T, at::kFloat, R * m.ldt), "jlm.predict_memory_rows: T [n_rows, ldt] float32");
+    TORCH_CHECK(ld_logits >= 0 && is(logits, at::kFloat, R * ld_logits), "jlm.predict_memory_rows: logits [n_rows, ld_logits] float32");
+    jlm_predict_memory_plan p{};
+    memory_mix_into("predict_memory_rows", p, m.H, R, keys, key_words, N, theta, lam, K, s, ld_s, ret_words, ret_idx, 1, first, workspace,
+                    mem_flags);
+    TORCH_CHECK(opt_ok(flags, at::kInt, 1), "jlm.predict_memory_rows: int32 flags");
+    TORCH_CHECK(k >= 1 && k <= JLM_TOPK_MAX && k <= V && is(ids, at::kInt, R * k) && is(nll, at::kDouble, R * k),
+                "jlm.predict_memory_rows: k in 1 .. min(", JLM_TOPK_MAX, ", V), int32 ids / float64 nll [n_rows, k]");
+    const c10::hip::HIPGuard device_guard(logits.device().index());
+    on_gpu(logits, "logits");
+    Tensor sets;
+    if (has(mask)) sets = check_word_sets("predict_memory_rows", *mask, ld_mask, n_sets, V, row_set, R, logits);
+    p.n_rows = (int)R; p.h = ptr<const void>(h, "h"); p.T = optr<float>(T, "T");
+    p.logits = ptr<float>(logits, "logits"); p.ld_logits = (int)ld_logits; p.rows = ptr<const int>(rows, "rows"); p.k = (int)k;
+    if (has(mask)) {
+        p.mask = n_sets > 0 ? ptr<const unsigned>(*mask, "mask") : nullptr; p.ld_mask = (int)ld_mask; p.n_sets = (int)n_sets;
+        p.row_set = ptr<const int>(sets, "row_set");
+    }
+    p.ids = ptr<int>(ids, "ids"); p.nll = ptr<double>(nll, "nll"); p.flags = optr<int>(flags, "flags");
+    p.memory_flags = optr<int>(mem_flags, "mem_flags");
+    const std::lock_guard<std::mutex> lock(g_enqueue_mutex);
+    jlm_check(jlm_predict_memory_rows(&m, &p, stream_of(logits)), "jlm_predict_memory_rows");
 }
 
 // one beam selection per prompt over per-row top-`beam` lists (jlm_beam_merge, include/jlm_hip.h): cand_ids int32 / cand_nll float64
@@ -1710,6 +1834,18 @@ TORCH_LIBRARY(jlm, m) {
           "Tensor? mask, int ld_mask, int n_sets, int[] row_set, Tensor(d!) ids, Tensor(e!) nll, Tensor(f!)? flags, Tensor(g!)? cache_flags, "
           "int n_rows) -> ()",
           predict_cache_rows);
+    m.def("rank_memory_frames(__torch__.torch.classes.jlm.Model model, Tensor(a!) h0, Tensor(b!) c0, Tensor(c!) h1, Tensor(d!) c1, Tensor(e!)? T, "
+          "Tensor(f!) logits, int ld_logits, Tensor rows, Tensor prev0, Tensor word, Tensor target, Tensor n_live, int[] n_live_host, "
+          "Tensor? ids, Tensor? lv_off, Tensor? lv_lo, Tensor? lv_hi, int n_levels, Tensor(g!) rank, Tensor(h!)? flags, int n_rows, "
+          "int n_steps, bool timed, Tensor keys, Tensor key_words, int N, float theta, float lam, int K, Tensor(i!) s, int ld_s, "
+          "Tensor(j!) ret_words, Tensor(k!) ret_idx, bool keep_idx, Tensor first, Tensor(l!) workspace, int top_k, Tensor(m!)? top_ids, "
+          "Tensor(n!)? top_nll, Tensor(o!)? mem_flags) -> Tensor",
+          rank_memory_frames);
+    m.def("predict_memory_rows(__torch__.torch.classes.jlm.Model model, Tensor h, Tensor(a!)? T, Tensor(b!) logits, int ld_logits, Tensor rows, "
+          "Tensor keys, Tensor key_words, int N, float theta, float lam, int K, Tensor(c!) s, int ld_s, Tensor(d!) ret_words, "
+          "Tensor(e!)? ret_idx, Tensor first, Tensor(f!) workspace, int k, Tensor? mask, int ld_mask, int n_sets, int[] row_set, "
+          "Tensor(g!) ids, Tensor(h!) nll, Tensor(i!)? flags, Tensor(j!)? mem_flags, int n_rows) -> ()",
+          predict_memory_rows);
     m.def("sample_rows(Tensor y, int ld, int n_cols, int n_rows, Tensor? n_dev, float temperature, int seed, int step, Tensor? row_id, "
           "Tensor? forced, Tensor(a!)? done, int stop_id, bool self_norm, Tensor(b!) word, Tensor(c!) ids, Tensor(d!) nll, Tensor(e!)? flags) -> ()",
           sample_rows);
@@ -1730,6 +1866,9 @@ TORCH_LIBRARY(jlm, m) {
     m.def("topk_rows(Tensor y, int ld, int n_cols, int n_rows, int k, bool self_norm, Tensor(a!) ids, Tensor(b!) nll, int ld_out, "
           "Tensor(c!)? flags) -> ()",
           topk_rows);
+    m.def("memory_topk(Tensor keys, Tensor key_words, int N, int H, bool split, float h_scale, Tensor q_rows, int n_rows, float theta, int K, "
+          "Tensor(a!) s, int ld_s, Tensor(b!) ret_words, Tensor(c!) ret_idx, Tensor(d!) workspace, Tensor(e!)? flags) -> ()",
+          memory_topk);
     m.def("beam_merge(Tensor cand_ids, Tensor cand_nll, int beam, int n_prompts, bool first, int stop_id, Tensor(a!) word, Tensor(b!) prev, "
           "Tensor(c!) score, Tensor(d!) finished, Tensor(e!) bp_parent, Tensor(f!) bp_word, Tensor(g!) bp_nll) -> ()",
           beam_merge);

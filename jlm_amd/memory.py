@@ -23,13 +23,16 @@ import numpy as np
 
 from . import _lib
 from . import cache as _cache
+from . import ops as _ops
 from .cache import CacheSpec, decode_rows, mix_nll
-from .rowsets import check_streams, is_int
+from .rowsets import RowSets, check_streams, is_int, t_is_state
 from .score import MAX_ROWS, SCORE_BUDGET_BYTES, sentence_loop
 
 MAX_KEYS = 1 << 24                  # JLM_MEMORY_MAX_KEYS
 MIN_SPLIT_KEYS = 512                # JLM_MEMORY_MIN_SPLIT_KEYS
 MAX_SPLITS = 128                    # JLM_MEMORY_MAX_SPLITS
+TOPK_MAX = 1024                     # JLM_MEMORY_TOPK_MAX
+TOPK_SCORE_BYTES = 1 << 28          # the most a retrieval's chunk of scores takes: a smaller memory is one chunk, a larger one several
 
 
 def keys_per_split(N):
@@ -48,6 +51,34 @@ class MemorySpec:
     @property
     def theta(self):
         return self.thetas[0]
+
+
+class MemoryMix:
+    """What ranking and prediction under a memory are asked for: the ``memory``, ONE ``theta`` >= 0 (a rank
+    depends on theta and lam both), 0 <= ``lam`` < 1 and 1 <= ``k`` <= 1024, the number of nearest entries that vote.  ValueError for
+    anything else, here, before anything runs; a memory of another model is refused by the call that is given it."""
+
+    def __init__(self, memory, theta=0.3, lam=0.1, k=64):
+        if not isinstance(memory, Memory):
+            raise ValueError("memory must be a Memory (got %r)" % (memory,))
+        spec = CacheSpec(1, theta, lam)              # (the same checks, the same messages)
+        if len(spec.thetas) != 1:
+            raise ValueError("ranking and prediction under a memory take one theta a call (got %d)" % len(spec.thetas))
+        if not is_int(k) or not 1 <= k <= TOPK_MAX:
+            raise ValueError("k must be an integer in [1, %d] (got %r)" % (TOPK_MAX, k))
+        self.memory, self.theta, self.lam, self.k = memory, spec.thetas[0], spec.lam, int(k)
+
+    @property
+    def n_q(self):
+        """the entries that vote: min(k, N)"""
+        return min(self.k, self.memory.N)
+
+
+def _check_mix(m, mix):
+    if not isinstance(mix, MemoryMix):
+        raise ValueError("mix must be a MemoryMix (got %r)" % (mix,))
+    _check_memory(m, mix.memory)
+    return mix
 
 
 def _check_spec(spec):
@@ -78,6 +109,35 @@ def memory_log_probs(h_q, w_q, keys, key_words, thetas):
             e = np.exp(s - s.max())
             lpm[t, q] = np.log(e[same].sum()) - np.log(e.sum())
     return lpm
+
+
+def memory_neighbours(h_q, keys, theta, k):
+    """T_K of the definition (include/jlm_hip.h jlm_memory_topk) for ONE query, in float64.  ``h_q`` [H]: the
+    query state in real units, ``keys`` [N, H]: the memory, decoded; ``theta`` >= 0; 1 <= ``k`` <= 1024.  -> (idx [n_q] int64, s [n_q]
+    float64), n_q = min(k, N): the entries that come first in the order "larger s_i = theta (h_q . k_i) first, smaller i first among
+    equal s_i", in that order."""
+    h = np.asarray(h_q, dtype=np.float64)
+    kv = np.asarray(keys, dtype=np.float64)
+    if kv.ndim != 2 or len(kv) < 1 or h.shape != kv.shape[1:]:
+        raise ValueError("h_q [H], keys [N >= 1, H]")
+    if not is_int(k) or not 1 <= k <= TOPK_MAX:
+        raise ValueError("k must be an integer in [1, %d] (got %r)" % (TOPK_MAX, k))
+    s = float(theta) * (kv @ h) + 0.0                       # (+ 0: a zero score is +0, one tie)
+    idx = np.lexsort((np.arange(len(s)), -s))[:min(int(k), len(s))]       # the last key is the primary one
+    return idx.astype(np.int64), s[idx]
+
+
+def memory_distribution(h_q, keys, key_words, theta, k, V):
+    """c_q of the definition for ONE query, in float64: c [V], c(w) = sum_{i in T_K, v_i = w} exp(s_i) / sum_{i in T_K} exp(s_i).
+    With k >= N, log c(w_q) is lpm_q of :func:`memory_log_probs`."""
+    v = np.asarray(key_words, dtype=np.int64)
+    if v.ndim != 1 or len(v) != len(keys) or (len(v) and (v.min() < 0 or v.max() >= V)):
+        raise ValueError("key_words [N] inside [0, %d)" % V)
+    idx, s = memory_neighbours(h_q, keys, theta, k)
+    e = np.exp(s - s.max())
+    c = np.zeros(V)
+    np.add.at(c, v[idx], e)
+    return c / e.sum()
 
 
 # ---------------------------------------------------------------------------------------------------------------- the store
@@ -177,6 +237,27 @@ class Memory:
         """(keys [N, H] float32 with split rows decoded, words [N] int64)"""
         return decode_rows(self.m, self.keys), self.words.detach().cpu().numpy().astype(np.int64)
 
+    def search(self, h, k, theta=1.0):
+        """The retrieval on its own (jlm_memory_topk): ``h`` [R, H] state rows on the device in the model's state-row format -- what a
+        stream call returns, or rows of ``keys`` -- 1 <= ``k`` <= 1024, ``theta`` >= 0.  -> (idx [R, n_q] int64, scores [R, n_q]
+        float32, words [R, n_q] int64), n_q = min(k, N): each row's nearest entries, best first, in the order of
+        :func:`memory_neighbours`.  JlmHipError when a score is not finite."""
+        m = self.m
+        torch = m.torch
+        mix = MemoryMix(self, theta, 0.0, k)
+        if h is None or len(tuple(h.shape)) != 2 or int(h.shape[1]) != m.H or not 0 <= int(h.shape[0]) <= 65535:
+            raise ValueError("h must be state rows [R <= 65535, %d] on the device" % m.H)
+        R, n_q = int(h.shape[0]), mix.n_q
+        if R == 0:
+            return np.zeros((0, n_q), dtype=np.int64), np.zeros((0, n_q), dtype=np.float32), np.zeros((0, n_q), dtype=np.int64)
+        with m._ctx():
+            buf = RetrievalBuffers(m, mix, R)
+            _ops.backend().memory_topk(self.keys, self.words, self.N, m.H, self.split, self.h_scale, h.view(torch.float32).contiguous(), R,
+                                       mix.theta, mix.k, buf.s, mix.k, buf.ret_words, buf.ret_idx, buf.workspace, buf.flags)
+            buf.check()
+            return (np.ascontiguousarray(buf.ret_idx[:n_q].cpu().numpy().T.astype(np.int64)), buf.s[:, :n_q].cpu().numpy().copy(),
+                    np.ascontiguousarray(buf.ret_words[:n_q].cpu().numpy().T.astype(np.int64)))
+
 
 def _check_memory(m, memory):
     if not isinstance(memory, Memory) or memory.m is not m:
@@ -272,6 +353,176 @@ def score_memory(scorer, sequences, start, memory, spec, max_rows=None):
     return sentence_loop(m, sequences, start, "score", max_rows, (MAX_ROWS, SCORE_BUDGET_BYTES),
                          lambda n: scorer.row_bytes(n, True) + MemoryRings.row_bytes(m.H, memory.N, n, n_theta),
                          lambda n: np.zeros(n, dtype=np.float64), run)
+
+
+# ---------------------------------------------------------------------------------------------------------------- ranking and prediction
+def _flag_error(fl):
+    if fl & 1:
+        return _lib.JlmHipError("the retrieval flagged a score theta (h_q . k_i) that is not finite: a hidden state or a key is NaN or inf")
+    if fl & 2:
+        return _lib.JlmHipError("cache_mix_rows_kernel flagged a row whose log-normaliser is not finite")
+    return _lib.JlmHipError("cache_mix_rows_kernel flagged a word of the memory outside the vocabulary (flags %d)" % fl)
+
+
+class RetrievalBuffers:
+    """The buffers of a retrieval over R rows (jlm_memory_topk's): the scores s [R, K], ret_words / ret_idx [K, R] -- ``steps`` > 0:
+    ret_idx [steps, K, R], every step's neighbours kept --, ``first`` [R] zeros (the patch reads the retrieved entries as a window that
+    starts at position 0), the workspace and the flag word.  All zeroed, none uninitialised.  Constructed inside the model's context."""
+
+    def __init__(self, m, mix, R, steps=0):
+        torch, dev, K = m.torch, m.device, mix.k
+        self.m, self.mix, self.R = m, mix, R
+        self.s = torch.zeros((R, K), device=dev, dtype=torch.float32)
+        self.ret_words = torch.zeros((K, R), device=dev, dtype=torch.int32)
+        self.ret_idx = torch.full(((steps, K, R) if steps else (K, R)), -1, device=dev, dtype=torch.int32)
+        self.first = torch.zeros(R, device=dev, dtype=torch.int32)
+        self.workspace = torch.zeros(max(self.workspace_floats(mix.memory.N, R, K), 4), device=dev, dtype=torch.float32)
+        self.flags = torch.zeros(1, device=dev, dtype=torch.int32)
+
+    @staticmethod
+    def chunk_keys(N, R):
+        """keys per chunk of the retrieval: the whole memory when its scores fit TOPK_SCORE_BYTES, else as many tiles as do"""
+        whole = -(-N // 32) * 32
+        return max(32, min(whole, TOPK_SCORE_BYTES // (4 * max(R, 1)) // 32 * 32))
+
+    @classmethod
+    def workspace_floats(cls, N, R, K):
+        return R * (cls.chunk_keys(N, R) + 2 * K)
+
+    @staticmethod
+    def row_bytes(N, K, S, top, neighbours):
+        """bytes a row of a ranking call adds to rank's: scores, words, indices, its share of the workspace (a chunk of at most the
+        whole memory: the row plan has not fixed R yet) and the lists"""
+        return 4 * K * (2 + (S if neighbours else 1)) + 4 * min(-(-N // 32) * 32, 1 << 16) + 8 * K + 12 * S * top + 8
+
+    def check(self):
+        fl = int(self.flags.cpu()[0])
+        if fl:
+            raise _flag_error(fl)
+
+
+class MixBuffers(RetrievalBuffers):
+    """... of one ranking call of R rows and S steps (jlm_memory_mix_plan), as the plug Ranker.run takes: with ``top`` > 0 the lists
+    top_ids / top_nll [S, R, top] of every step, with ``neighbours`` every step's indices."""
+    op = "rank_memory_frames"           # the op Ranker.run calls with op_args behind rank_frames' arguments
+
+    def __init__(self, m, mix, R, S, top=0, neighbours=False):
+        torch, dev = m.torch, m.device
+        self.S, self.top, self.keep = S, int(top), bool(neighbours)
+        with m._ctx():
+            super().__init__(m, mix, R, S if neighbours else 0)
+            self.top_ids = torch.full((S, R, self.top), -1, device=dev, dtype=torch.int32) if self.top else None
+            self.top_nll = torch.full((S, R, self.top), float("nan"), device=dev, dtype=torch.float64) if self.top else None
+
+    def op_args(self, R, S):
+        if (R, S) != (self.R, self.S):
+            raise ValueError("these buffers were made for %d rows and %d steps (got %d, %d)" % (self.R, self.S, R, S))
+        mix, mem = self.mix, self.mix.memory
+        return (mem.keys, mem.words, mem.N, mix.theta, mix.lam, mix.k, self.s, mix.k, self.ret_words, self.ret_idx, self.keep, self.first,
+                self.workspace, self.top, self.top_ids, self.top_nll, self.flags)
+
+    def lists(self, self_norm):
+        """(top_ids [S, R, top] int64, top_logp [S, R, top] float64 = log p_q under the mixture) -- after the op"""
+        ids = self.top_ids.cpu().numpy().astype(np.int64)
+        logp = -self.top_nll.cpu().numpy()
+        if self_norm and self.mix.lam > 0:                 # y' orders as p_q does; exp(y') sums to 1 / (1 - lam): a memory is never empty
+            logp = logp + np.log1p(-float(np.float32(self.mix.lam)))
+        return ids, logp
+
+    def neighbour_indices(self):
+        """[S, R, n_q] int64 -- after the op"""
+        return np.ascontiguousarray(self.ret_idx[:, :self.mix.n_q].cpu().numpy().transpose(0, 2, 1).astype(np.int64))
+
+
+class MemoryRanks:
+    """What a ranking call of streams under a memory returns.  ``ranks`` [B, n, columns] int32: rank_streams' array under the mixed
+    distribution; ``top_ids`` [B, n, top] int64 / ``top_logp`` [B, n, top] float64 (log p_q, most probable first) when ``top`` > 0,
+    else None; ``neighbours`` [B, n, n_q] int64 indices into the memory, best first, or None; ``h``, ``c``: what the next call of the
+    stream carries."""
+
+    def __init__(self, ranks, top_ids, top_logp, neighbours, h, c):
+        self.ranks, self.top_ids, self.top_logp, self.neighbours, self.h, self.c = ranks, top_ids, top_logp, neighbours, h, c
+
+
+def rank_streams_memory(ranker, inputs, targets, mix, h=None, c=None, levels=None, top=0, neighbours=False):
+    """LSTM_Model.rank_streams_memory: see there."""
+    m = ranker.m
+    mix = _check_mix(m, mix)
+    top = _cache._check_top(top, m.V)
+    x, y, B, n = check_streams(m, inputs, targets, h, c, "rank")
+    L = levels.n_levels if levels is not None else 0
+    if B == 0 or n == 0:
+        return MemoryRanks(np.full((B, n, L + 1), -1, dtype=np.int32), np.zeros((B, n, top), dtype=np.int64) if top else None,
+                           np.zeros((B, n, top)) if top else None, np.zeros((B, n, mix.n_q), dtype=np.int64) if neighbours else None, h, c)
+    buf = MixBuffers(m, mix, B, n, top, neighbours)
+    ranks, h2, c2 = ranker.streams(x, y, h, c, levels, buf)
+    ids = logp = None
+    if top:
+        ids, logp = buf.lists(m.self_norm)
+        ids, logp = np.ascontiguousarray(ids.transpose(1, 0, 2)), np.ascontiguousarray(logp.transpose(1, 0, 2))
+    nb = np.ascontiguousarray(buf.neighbour_indices().transpose(1, 0, 2)) if neighbours else None
+    return MemoryRanks(ranks, ids, logp, nb, h2, c2)
+
+
+def rank_memory(ranker, sequences, start, mix, levels=None, max_rows=None):
+    """LSTM_Model.rank_memory: see there."""
+    from .generate import GENERATE_BUDGET_BYTES
+    m = ranker.m
+    mix = _check_mix(m, mix)
+    return ranker.sentences(sequences, start, levels, max_rows, (MAX_ROWS, GENERATE_BUDGET_BYTES),
+                            patch=lambda word: MixBuffers(m, mix, int(np.shape(word)[1]), int(np.shape(word)[0])),
+                            extra_bytes=lambda n: RetrievalBuffers.row_bytes(mix.memory.N, mix.k, n, 0, False))
+
+
+def predict_next_memory(ranker, h, mix, n=10, allowed=None):
+    """LSTM_Model.predict_next_memory: see there."""
+    from .complete import check_allowed
+    from .readings import ReadingIndex
+    m = ranker.m
+    torch = m.torch
+    mix = _check_mix(m, mix)
+    if m.mode == "untied" and m.split_lstm:
+        raise ValueError("predict_next_memory has no form for an untied split-row model: the f32 copy of the state its vocabulary "
+                         "GEMMs read exists only inside the LSTM step")
+    if h is None or len(tuple(h.shape)) != 2 or int(h.shape[1]) != m.H:
+        raise ValueError("h must be the carried state [B, %d] a stream call returned" % m.H)
+    B = int(h.shape[0])
+    if not is_int(n) or not 1 <= n <= min(64, m.V):
+        raise ValueError("n must be an integer in [1, %d] (got %r)" % (min(64, m.V), n))
+    sets = check_allowed(allowed, B, m.V, "predict_next_memory (allowed)")
+    out = [(np.zeros(0, dtype=np.int64), np.zeros(0))] * B
+    if B == 0 or (sets is not None and all(s is not None and not len(s) for s in sets)):
+        return out
+    dev, i32, mem = m.device, torch.int32, mix.memory
+    with m._ctx():
+        rs = RowSets(m, B, logits=True)
+        buf = RetrievalBuffers(m, mix, B)
+        ids = torch.full((B, n), -1, device=dev, dtype=i32)
+        nll = torch.full((B, n), float("nan"), device=dev, dtype=torch.float64)
+        mask_args = (None, 0, 0, [])
+        if sets is not None:
+            restricted = [r for r in range(B) if sets[r] is not None and len(sets[r])]      # (an empty set: no result, below)
+            mask, index = ReadingIndex.mask([sets[r] for r in restricted], m.V)
+            row_set = [-1] * B
+            for r, k in zip(restricted, index):
+                row_set[r] = int(k)
+            mask_args = (torch.from_numpy(mask.view(np.int32)).to(dev), mask.shape[1], mask.shape[0], row_set)
+        hq = h.view(torch.float32).contiguous()
+        _ops.backend().predict_memory_rows(m.decode_model(), hq, None if t_is_state(m) else rs.T, rs.logits, rs.ld_logits, rs.rows, mem.keys,
+                                           mem.words, mem.N, mix.theta, mix.lam, mix.k, buf.s, mix.k, buf.ret_words, buf.ret_idx, buf.first,
+                                           buf.workspace, int(n), *mask_args, ids, nll, rs.flags, buf.flags, B)
+        rs.check_flags("topk_rows_kernel flagged a logit or log-normaliser that is not finite (flags %d)")
+        buf.check()
+        ids_h, logp = ids.cpu().numpy().astype(np.int64), -nll.cpu().numpy()
+    if m.self_norm and mix.lam > 0:
+        logp = logp + np.log1p(-float(np.float32(mix.lam)))
+    res = []
+    for r in range(B):
+        keep = ids_h[r] >= 0                               # a set smaller than n pads its list with (-1, +inf)
+        if sets is not None and sets[r] is not None and not len(sets[r]):
+            keep[:] = False
+        res.append((ids_h[r][keep], logp[r][keep]))
+    return res
 
 
 # ---------------------------------------------------------------------------------------------------------------- tuning (numpy)

@@ -1060,6 +1060,33 @@ class LSTM_Model():
         from .ngram_mix import rank_ngram
         return rank_ngram(self._ranker(), sequences, start, ngram, self._rank_levels(readings, max_prefix), max_rows)
 
+    def rank_streams_memory(self, inputs, targets, mix, h=None, c=None, readings=True, max_prefix=8, top=0, neighbours=False):
+        """rank_streams under a memory of hidden states (jlm_amd/memory.py): at every step the ``mix.k`` entries
+        of the memory nearest to the step's state are retrieved on the device -- an exact search -- and the full-vocabulary logits are
+        patched into the mixed distribution p = (1 - lam) p_lm + lam c, c the softmax of the retrieved scores summed per word, before
+        the target is ranked.  ``mix``: a :class:`jlm_amd.memory.MemoryMix`.  -> :class:`jlm_amd.memory.MemoryRanks`: ``ranks``
+        [B, n, max_prefix + 3] in rank()'s columns, ``top_ids`` / ``top_logp`` [B, n, top] (the ``top`` <= 64 most probable words of
+        every step and their log p under the mixture; None for top = 0), ``neighbours`` [B, n, min(k, N)] (the retrieved entries'
+        indices into the memory, best first; None unless asked for), and ``h``, ``c`` to carry.  lam = 0 gives rank_streams' ranks; a
+        stream cut any way into calls gives the same ranks, lists and neighbours.  ValueError before anything runs for a bad argument
+        or a memory of another model."""
+        from .memory import rank_streams_memory
+        return rank_streams_memory(self._ranker(), inputs, targets, mix, h, c, self._rank_levels(readings, max_prefix), top, neighbours)
+
+    def rank_memory(self, sequences, start, mix, readings=True, max_prefix=8, max_rows=None):
+        """rank() under a memory: rank()'s row plan with the retrieval's buffers counted into the rows of a call.  -> per sequence an
+        int32 [len, max_prefix + 3] array, rank()'s columns."""
+        from .memory import rank_memory
+        return rank_memory(self._ranker(), sequences, start, mix, self._rank_levels(readings, max_prefix), max_rows)
+
+    def predict_next_memory(self, h, mix, n=10, allowed=None):
+        """The ``n`` most probable next words of B streams under a memory, from what a stream call left: ``h`` the carried state
+        [B, H] (device tensor).  One T projection, the logits, the retrieval, the patch and the selection: no LSTM step.  -> per row
+        (ids int64, logp float64 = log p under the mixture), most probable first.  ``allowed``: predict_top's.  ValueError for an
+        untied split-row model, whose vocabulary GEMMs read a copy of the state that exists only inside the LSTM step."""
+        from .memory import predict_next_memory
+        return predict_next_memory(self._ranker(), h, mix, n, allowed)
+
     def predict_next_cached(self, h, state, cache, n=10, allowed=None):
         """The ``n`` most probable next words of B streams under the continuous cache, from what a stream call left: ``h`` the carried
         state [B, H] (device tensor, as rank_streams_cached / score_streams_cached return it), ``state`` their CacheState (None: an

@@ -34,7 +34,9 @@ after every line; a character model (config char_rnn) reads the characters of th
                    DESIGN.md section 28) at --mem-theta and --mem-lam, in ONE pass -- LSTM_Model.score_streams_memory returns the plain
                    -log p as well -- and print the perplexity under the memory after the plain one.  --tune-memory DEV sweeps --thetas
                    and --lams on DEV and reports the test perplexity at the grid's best pair.  Not with --cache, --dynamic or --ngram.
-                   Without --memory the output is what it was.
+                   Without --memory the output is what it was.  With --ranks and --mem-k K as well, a second --ranks line "with memory"
+                   over the same tokens, from LSTM_Model.rank_streams_memory at the K nearest entries, the theta and the lam the
+                   memory's perplexity is reported at; without --mem-k nothing of this runs.
 """
 import argparse
 import os
@@ -168,11 +170,12 @@ def sentence_ranks(model, sents, eos, readings, max_prefix):
     return (np.concatenate(ranks) if ranks else np.zeros((0, width), dtype=np.int32)), np.array([t for s in sents for t in s], dtype=np.int64)
 
 
-def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix, spec=None, ngram=None):
+def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix, spec=None, ngram=None, memory=None):
     """-> (ranks [tokens, columns], the targets [tokens]) over the corpus_iterator chunks, state carried, as stream_perplexity;
     ``spec``: a CacheSpec -- the ranks under the continuous cache (LSTM_Model.rank_streams_cached), the cache carried too; ``ngram``:
     an NGramMix -- the ranks under the n-gram mixture (LSTM_Model.rank_streams_ngram), the streams' last two words carried too; a row's
-    first token has the history of its one input word, exactly as stream_ngram_scores gives it to the mixture's perplexity"""
+    first token has the history of its one input word, exactly as stream_ngram_scores gives it to the mixture's perplexity;
+    ``memory``: a MemoryMix -- the ranks under the memory's K nearest entries (LSTM_Model.rank_streams_memory)"""
     from .score import stream_layout
     x, y = stream_layout(stream, batch_size, num_steps)
     h = c = state = tail = None
@@ -182,6 +185,9 @@ def stream_ranks(model, stream, batch_size, num_steps, readings, max_prefix, spe
         if ngram is not None:
             res = model.rank_streams_ngram(x[:, cols], y[:, cols], ngram, h, c, tail, readings=readings, max_prefix=max_prefix)
             r, h, c, tail = res.ranks, res.h, res.c, res.tail
+        elif memory is not None:
+            res = model.rank_streams_memory(x[:, cols], y[:, cols], memory, h, c, readings=readings, max_prefix=max_prefix)
+            r, h, c = res.ranks, res.h, res.c
         elif spec is None:
             r, h, c = model.rank_streams(x[:, cols], y[:, cols], h, c, readings=readings, max_prefix=max_prefix)
         else:
@@ -256,7 +262,11 @@ def main(argv=None, de_stepper=None):
     ap.add_argument("--mem-lam", type=float, default=0.1, dest="mem_lam", help="--memory: the weight of the memory in the mixture")
     ap.add_argument("--tune-memory", default=None, metavar="DEV", dest="tune_memory",
                     help="--memory: sweep --thetas x --lams on DEV (the dev set) and report the test perplexity at the best pair")
+    ap.add_argument("--mem-k", type=int, default=None, dest="mem_k", metavar="K",
+                    help="--memory with --ranks: a second --ranks line under the memory's K nearest entries (1 .. 1024)")
     args = ap.parse_args(argv)
+    if args.mem_k is not None and not (args.memory and args.ranks and 1 <= args.mem_k <= 1024):
+        ap.error("--mem-k K (1 .. 1024) goes with --memory and --ranks")
     if args.tune_memory and not args.memory:
         ap.error("--tune-memory goes with --memory")
     mem_spec = mem_tune_spec = None
@@ -426,6 +436,12 @@ def main(argv=None, de_stepper=None):
             from .ngram import NGramMix
             ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix, ngram=NGramMix(table, ng_lam))
             print("with n-gram (order {} lam {}): ".format(table.order, ng_lam) +
+                  ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
+        if args.mem_k is not None:
+            from .memory import MemoryMix
+            mix = MemoryMix(memory, mem_spec.theta, mem_spec.lam, args.mem_k)
+            ranks, targets = stream_ranks(model, stream, bs, args.num_steps, readings, args.max_prefix, memory=mix)
+            print("with memory (N {} K {} theta {} lam {}): ".format(memory.N, mix.k, mix.theta, mix.lam) +
                   ranks_line(ranks, targets, model.reading_index() if readings else None, tops, args.list_size))
     return pp
 

@@ -131,16 +131,18 @@ class Ranker:
             out = rank.cpu().numpy()
         return (out,) + rs.after(S)
 
-    def sentences(self, sequences, start, levels, max_rows, limit, spec=None, patch=None):
+    def sentences(self, sequences, start, levels, max_rows, limit, spec=None, patch=None, extra_bytes=None):
         """rank_sequences, and with ``spec`` (a checked CacheSpec) jlm_amd.cache.rank_cached: every chunk with rings of its own; with
-        ``patch`` (word [S, R] -> a jlm_amd.ngram_mix.NgramPatch) jlm_amd.ngram_mix.rank_ngram: every chunk with its histories"""
+        ``patch`` (word [S, R] -> a jlm_amd.ngram_mix.NgramPatch) jlm_amd.ngram_mix.rank_ngram: every chunk with its histories;
+        ``extra_bytes`` (n_steps -> bytes): what the patch's own buffers add to a row of a call (jlm_amd.memory.rank_memory)"""
         L = levels.n_levels if levels is not None else 0
+        more = extra_bytes or (lambda n: 0)
 
         def run(ch, word, target, lens):
             rings = MixRings(self.m, spec, len(lens), ch["n_steps"]) if spec else patch(word) if patch else None
             rk = self.run(word, target, ch["n_live"], levels=levels, rings=rings)[0]
             return [_columns(levels, rk[:n, r, :], target[:n, r]) for r, n in enumerate(lens)]
-        return sentence_loop(self.m, sequences, start, "rank", max_rows, limit, lambda n: self.row_bytes(n, L, spec.size if spec else 0, ngram=patch is not None),
+        return sentence_loop(self.m, sequences, start, "rank", max_rows, limit, lambda n: self.row_bytes(n, L, spec.size if spec else 0, ngram=patch is not None and extra_bytes is None) + more(n),
                              lambda n: np.full((n, L + 1), -1, dtype=np.int32), run)
 
     def streams(self, x, y, h, c, levels, rings=None):
