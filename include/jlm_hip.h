@@ -645,6 +645,7 @@ typedef struct {
 
 struct jlm_decode_cache;
 struct jlm_decode_ngram;
+struct jlm_decode_memory;
 typedef struct {
     int kind;                       /* 0 static, full vocabulary; 1 static, selected vocabulary; 2 incremental */
     int max_cands;
@@ -685,6 +686,9 @@ typedef struct {
     /* A back-off n-gram model mixed into every edge cost (additive, ABI 12; NULL: the loop is what it was, launch for launch).  Kind 0
      * only, and not together with `cache` (-1): see jlm_decode_ngram below. */
     const struct jlm_decode_ngram *ngram;
+    /* A memory of (hidden state, next word) pairs mixed into every edge cost (additive, ABI 12; NULL: the loop is what it was, launch for
+     * launch).  Kind 0 only, and not together with `cache` or `ngram` (-1): see jlm_decode_memory below. */
+    const struct jlm_decode_memory *memory;
 } jlm_decode_plan;
 
 /* Returns 0 or a hipError_t.  st_host->lse_part / n_parts are managed by the call.  A full-vocabulary
@@ -1442,6 +1446,62 @@ int jlm_ngram_cell_patch(const void *keys, const float *vals, int log2cap, int m
                          const double *score, const int *root_hist, const int *wl, const int *wl_off, const int *wl_idx, int wl_base,
                          const int *wl_out, float *edge, const float *part, int ld_part, int n_parts, const int *live_base, double *lse,
                          int *flags, void *stream);
+
+/* ------------------------------------------------------------------------
+ * A memory of (hidden state, next word) pairs inside a decode (Decoder.decode(memory=); ABI 12, additive): the
+ * distribution of jlm_memory_topk's section above on the edges of the continuous cache's section.  A memory (k_i, v_i), i < N; one
+ * theta >= 0, one 0 < lam < 1 and one 1 <= K <= JLM_MEMORY_TOPK_MAX a call; n_q = min(K, N).  For hypothesis row r of sentence s in
+ * frame f, with the state h_r the frame's LSTM step wrote and T_K(r) the retrieval's set for the query h_r (its total order: larger
+ * s_i = theta (h_r . k_i) first, smaller i first among equal s_i), and every lattice word w that starts in cell (f, s):
+ *     c_r(w) = sum_{i in T_K(r), v_i = w} exp(s_i) / sum_{i in T_K(r)} exp(s_i)
+ *     p_r(w) = (1 - lam) p_lm(w | r) + lam c_r(w)
+ *     edge'  = L + log(1 - lam) + logaddexp(y - L, log rho + log M - log Z)   for a word with a match (rho = lam / (1 - lam)),
+ *     edge'  = y + log(1 - lam)                                              for a word without,
+ * formed in f64 from the f32 sums M = sum_{i : v_i = w} e_i and Z = sum_i e_i over the retrieved list, e_i = expf(s_i - max s), and
+ * rounded once to the f32 the buffer holds: cache_cell_patch_kernel's arithmetic, operation for operation -- lane-strided partial sums
+ * for Z, then the xor-shuffle tree; M in ascending list position; the same logaddexp.  L is the row's full-vocabulary log-normaliser
+ * (self-normalised models: 0).  Word ids are only compared.  A decode's own hypotheses add nothing to the memory.  The memory applies
+ * with or without a left context, and to every row: a memory is never empty.
+ *
+ * What the frame loop is handed: the memory as jlm_memory_topk takes it, and the buffers of one frame's retrieval over the
+ * n_rows = n_sent * beam rows of the batch -- q_rows [n_rows][H], the frame's live rows gathered (jlm_memory_gather_rows), then
+ * jlm_memory_topk's s / ret_words / workspace.  flags: the retrieval's own flag int (its bit 0, a score that is not finite, would
+ * collide with bit 0 of the batch's word); the patch flags in jlm_beam_state.flags as the cache's patch does.  Per frame, behind the
+ * normaliser: gather, jlm_memory_topk (n_dev = the frame's live count), patch. */
+typedef struct jlm_decode_memory {
+    const void *keys; const int *key_words; int N, K; float theta, lam;
+    void *q_rows;                   /* [n_sent * beam][H] in the model's state-row format, 16-byte aligned; contents arbitrary */
+    float *s; int ld_s;             /* [n_sent * beam][ld_s], ld_s >= K */
+    int *ret_words;                 /* [K][n_sent * beam] */
+    void *workspace; size_t workspace_bytes;       /* jlm_memory_topk's, for n_rows_max = n_sent * beam */
+    int *flags;                     /* one device int or NULL: jlm_memory_topk's bits */
+} jlm_decode_memory;
+
+/* memory_gather_rows_kernel: for i < min(*n_dev, n_rows_max) (n_dev NULL: n_rows_max), row rows[i] of the pool h [n_pool_rows][H]
+ * -> row i of out [n_rows_max][H]; a row is 4 H bytes in either state-row format and moves as 16-byte records.  Rows of out that are
+ * not live are not written; an index outside [0, n_pool_rows) copies nothing.
+ * Returns 0 (nothing launched for n_rows_max == 0), -1 before any launch (H <= 0 or H % 4, n_rows_max outside [0, 65535], a null
+ * pointer, h or out off 16 bytes), or a hipError_t. */
+int jlm_memory_gather_rows(const void *h, int H, long long n_pool_rows, const int *rows, const int *n_dev, int n_rows_max, void *out,
+                           void *stream);
+
+/* memory_cell_patch_kernel (csrc/jlm_memory_edge.hip): one workgroup per sentence j of the frame (skipped when frame >= sent_len[j]
+ * or cnt[j] = 0).  part != NULL: the cell's normaliser slices are first folded into lse[j * beam + k] exactly as jlm_cache_cell_patch
+ * folds them (jlm_beam_step's fused fold: order, arithmetic, sanitising -- flag bit 1, the value 1e30), so that the next jlm_beam_step
+ * runs unfused; part == NULL: L = 0, lse is not touched.  Slot k < min(cnt[j], beam) is compact row c = live_base[j] + k of the
+ * frame's live rows -- the indexing of the normaliser's slices --: its scores are s[c * ld_s + i], its words ret_words[i * n_rows + c],
+ * i < n_q = min(K, N), jlm_memory_topk's outputs; entries i >= n_q are never read.  Per position of the cell's word list
+ * wl[wl_off[l] .. wl_off[l + 1]), l = wl_base + wl_idx[j] (jlm_edge_logits' lists) and slot k: edge[wl_out * beam + k] <- edge' as
+ * defined above.  Every slot has its own words: no match structure is shared within a cell.  One writer per address, no float
+ * atomics; s and ret_words are only read.  A slot with a score that is not finite keeps its edge logits and ORs 8 into *flags.  lse:
+ * the frame's first entry.  LDS: 32 bytes an entry of the list (n_q rounded up to a multiple of 4: 32 KiB at K = 1 024), whatever the beam.
+ * Returns 0, -1 before any launch (lam outside (0, 1), N < 1, K outside [1, JLM_MEMORY_TOPK_MAX], ld_s < K, n_rows outside
+ * [1, 65535], beam outside [1, JLM_MAX_BEAM], n_sent > 65535, part without lse / n_parts >= 1, a null or misaligned pointer), or a
+ * hipError_t. */
+int jlm_memory_cell_patch(const float *s, int ld_s, const int *ret_words, int n_rows, int N, int K, float lam, const int *cnt,
+                          const int *sent_len, int frame, int n_sent, int beam, const int *wl, const int *wl_off, const int *wl_idx,
+                          int wl_base, const int *wl_out, float *edge, const float *part, int ld_part, int n_parts, const int *live_base,
+                          double *lse, int *flags, void *stream);
 
 /* ------------------------------------------------------------------------
  * The n-gram model's distribution over EVERY word of a row, as a patch of the row's materialised logits (ABI 12,

@@ -60,7 +60,14 @@ class DecodePlan(Structure):
                 ("run_max", c_void_p), ("run_sum", c_void_p), ("part", c_void_p), ("max_parts", c_int), ("lse_cu_share_pct", c_int),
                 ("out_nodes", c_void_p), ("out_len", c_void_p), ("out_score", c_void_p), ("stride", c_int),
                 ("di_wwords", c_void_p), ("sg_wword", c_void_p), ("Tm", c_void_p), ("ld_tm", c_int),
-                ("ctx_prev", c_void_p), ("ctx_word", c_void_p), ("cache", c_void_p), ("ngram", c_void_p)]
+                ("ctx_prev", c_void_p), ("ctx_word", c_void_p), ("cache", c_void_p), ("ngram", c_void_p), ("memory", c_void_p)]
+
+
+class DecodeMemory(Structure):
+    """jlm_decode_memory (include/jlm_hip.h)."""
+    _fields_ = [("keys", c_void_p), ("key_words", c_void_p), ("N", c_int), ("K", c_int), ("theta", c_float), ("lam", c_float),
+                ("q_rows", c_void_p), ("s", c_void_p), ("ld_s", c_int), ("ret_words", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("flags", c_void_p)]
 
 
 
@@ -264,6 +271,9 @@ _SIGS = {
                               P, P, P, P], c_int),
     "jlm_ngram_cell_patch": ([P, P, c_int, c_int, c_int, c_float, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, P, P, P, c_int, c_int,
                               P, P, P, P], c_int),
+    "jlm_memory_gather_rows": ([P, c_int, c_longlong, P, P, c_int, P, P], c_int),
+    "jlm_memory_cell_patch": ([P, c_int, P, c_int, c_int, c_int, c_float, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int,
+                               P, P, P, P], c_int),
     "jlm_ngram_mix_refuse": ([P, c_int, c_int, POINTER(NgramRows), P, c_int, P, c_float, c_int, P], c_int),
     "jlm_ngram_mix_rows": ([P, c_int, c_int, c_int, POINTER(NgramRows), P, c_int, P, c_float, c_int, P, P], c_int),
     "jlm_ngram_hist_advance": ([P, c_int, P, P, c_int, P, P], c_int),

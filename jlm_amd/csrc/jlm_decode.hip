@@ -55,6 +55,16 @@ int jlm_ngram_cell_patch_refuse(const void *keys, const float *vals, int log2cap
                                 const double *score, const int *root_hist, const int *wl, const int *wl_off, const int *wl_idx, int wl_base,
                                 const int *wl_out, const float *edge, const float *part, int ld_part, int n_parts, const int *live_base,
                                 const double *lse, const int *flags);
+// the refusals of jlm_memory_gather_rows / jlm_memory_cell_patch (csrc/jlm_memory_edge.hip) and jlm_memory_topk (csrc/jlm_memory_topk.hip)
+int jlm_memory_gather_rows_refuse(const void *h, int H, long long n_pool_rows, const int *rows, const int *n_dev, int n_rows_max,
+                                  const void *out);
+int jlm_memory_cell_patch_refuse(const float *s, int ld_s, const int *ret_words, int n_rows, int N, int K, float lam, const int *cnt,
+                                 const int *sent_len, int frame, int n_sent, int beam, const int *wl, const int *wl_off, const int *wl_idx,
+                                 int wl_base, const int *wl_out, const float *edge, const float *part, int ld_part, int n_parts,
+                                 const int *live_base, const double *lse, const int *flags);
+int jlm_memory_topk_refuse(const void *keys, const int *key_words, int N, int H, int split, float h_scale, const void *q_rows, int n_rows_max,
+                           const int *n_dev, float theta, int K, const float *s, int ld_s, const int *ret_words, const int *ret_idx, int n_rows,
+                           const void *workspace, size_t workspace_bytes, const int *flags);
 
 // ABI 11: the model's mixed segments are mx6 rows (FP6 cross-term planes, csrc/jlm_mx6_body.h) when their s8 is 0 -- the hypothesis
 // rows are then packed by jlm_pack_t_mixed6; a model mixes the two formats in no launch (jlm_vocab_lse_mixed: -2)
@@ -208,6 +218,24 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                                             p->sg_node, p->edge, m->self_norm ? nullptr : p->part, rmax, 1, st.live_base, st.lse, st.flags));
         side_s = nullptr;
     }
+    // A memory of (hidden state, next word) pairs (jlm_decode_plan.memory, kind 0): behind the normaliser and the edge logits of every
+    // frame, the frame's live rows gathered into contiguous query rows (jlm_memory_gather_rows), their K nearest entries
+    // (jlm_memory_topk) and the rewrite of the edge logits leaving the frame (jlm_memory_cell_patch), which folds the frame's normaliser
+    // slices as the cache's patch does.  Not beside the cache or the n-gram model: a three-way mixture is not defined.  Every refusal
+    // comes here, before the first launch.
+    const jlm_decode_memory *mem = p->memory;
+    const long long pool_rows = (long long)F * rmax;
+    if (mem) {
+        if (cc || ng || !full || !st.live_base || (!m->self_norm && (!p->part || p->max_parts < 1)) || rmax > 65535) return -1;
+        JLM_TRY(jlm_memory_gather_rows_refuse(p->h, m->H, pool_rows, st.live, st.n_live, rmax, mem->q_rows));
+        JLM_TRY(jlm_memory_topk_refuse(mem->keys, mem->key_words, mem->N, m->H, split, m->h_scale, mem->q_rows, rmax, st.n_live, mem->theta,
+                                       mem->K, mem->s, mem->ld_s, mem->ret_words, nullptr, rmax, mem->workspace, mem->workspace_bytes,
+                                       mem->flags));
+        JLM_TRY(jlm_memory_cell_patch_refuse(mem->s, mem->ld_s, mem->ret_words, rmax, mem->N, mem->K, mem->lam, st.cnt, lat->sent_len, 0, B,
+                                             beam, p->sg_word, p->sg_off, p->sidx, 0, p->sg_node, p->edge, m->self_norm ? nullptr : p->part,
+                                             rmax, 1, st.live_base, st.lse, st.flags));
+        side_s = nullptr;
+    }
 
     // word-list normaliser: the kernel jlm_wordlist_lse_form names (split rows for lists of 128 .. 4064 words)
     auto wl_lse = [&](const int *g0, const int *cidx, const int *words, const int *off, const int *idx, int base, int merge,
@@ -355,6 +383,17 @@ extern "C" int jlm_decode_frames(const jlm_decode_model *m, const jlm_decode_pla
                                          lat->sent_len, f, B, beam, st.bp, st.word, st.score, ng->root_hist, p->sg_word, p->sg_off, p->sidx,
                                          cell, p->sg_node, p->edge, pending_parts ? p->part : nullptr, rmax, pending_parts,
                                          st.live_base + cell, st.lse + (size_t)f * rmax, st.flags, stream));
+            pending_parts = 0;             // folded: the next beam step reads lse
+        }
+        if (mem) {
+            const int bound = f == 0 ? B : rmax;
+            JLM_TRY(jlm_memory_gather_rows(p->h, m->H, pool_rows, rows, ndev, bound, mem->q_rows, stream));
+            JLM_TRY(jlm_memory_topk(mem->keys, mem->key_words, mem->N, m->H, split, m->h_scale, mem->q_rows, bound, ndev, mem->theta, mem->K,
+                                    mem->s, mem->ld_s, mem->ret_words, nullptr, rmax, mem->workspace, mem->workspace_bytes, mem->flags,
+                                    stream));
+            JLM_TRY(jlm_memory_cell_patch(mem->s, mem->ld_s, mem->ret_words, rmax, mem->N, mem->K, mem->lam, st.cnt + cell, lat->sent_len, f, B,
+                                          beam, p->sg_word, p->sg_off, p->sidx, cell, p->sg_node, p->edge, pending_parts ? p->part : nullptr,
+                                          rmax, pending_parts, st.live_base + cell, st.lse + (size_t)f * rmax, st.flags, stream));
             pending_parts = 0;             // folded: the next beam step reads lse
         }
     }
@@ -849,11 +888,6 @@ extern "C" int jlm_predict_cache_rows(const jlm_decode_model *m, const jlm_predi
                                     p->nll, p->k, p->flags, stream);
     return jlm_topk_rows(p->logits, p->ld_logits, V, R, p->k, m->self_norm, p->ids, p->nll, p->k, p->flags, stream);
 }
-
-// the refusals of jlm_memory_topk on their own (csrc/jlm_memory_topk.hip)
-int jlm_memory_topk_refuse(const void *keys, const int *key_words, int N, int H, int split, float h_scale, const void *q_rows, int n_rows_max,
-                           const int *n_dev, float theta, int K, const float *s, int ld_s, const int *ret_words, const int *ret_idx, int n_rows,
-                           const void *workspace, size_t workspace_bytes, const int *flags);
 
 // Ranking under a memory (include/jlm_hip.h jlm_rank_memory_frames): rank_loop with the logits of every step patched into the mixed
 // distribution before they are ranked -- the retrieval on the state set the step wrote, then cache_mix_rows_kernel over the retrieved

@@ -50,6 +50,8 @@
 //                             the window of the plan's next frame loop: no launch (jlm_decode_plan.cache; Decoder.decode(cache=))
 //   torch.ops.jlm.seed_ngram(Plan, keys, vals, root_hist, log2cap, max_probe, order, lam) / clear_ngram(Plan)
 //                             the n-gram table of the plan's next frame loop: no launch (jlm_decode_plan.ngram; Decoder.decode(ngram=))
+//   torch.ops.jlm.seed_memory(Plan, keys, key_words, N, H, theta, lam, K, q_rows, s, ret_words, workspace, flags) / clear_memory(Plan)
+//                             the memory of the plan's next frame loop: no launch (jlm_decode_plan.memory; Decoder.decode(memory=))
 //   torch.ops.jlm.alt_frames(Model, Plan, rank, sent_off, sent_rows, depth, alt, score_frames' arguments)
 //                             per-segment candidate lists behind a plan's decode (jlm_alt_frames; Decoder.decode_candidates)
 //   torch.ops.jlm.tail_predict(Model, Plan, ids, sp_off, sp_frame, sp_lo, sp_hi, n_out, chunk, out_score, out_row, out_word, out_nodes,
@@ -247,6 +249,8 @@ struct JlmPlan : torch::CustomClassHolder {
     std::vector<Tensor> cache_keep;         // ... and its tensors, kept until the next seed_cache
     jlm_decode_ngram ngram{};               // the next frame loop's n-gram table (seed_ngram; p.ngram points here or is NULL)
     std::vector<Tensor> ngram_keep;         // ... and its tensors, kept until the next seed_ngram
+    jlm_decode_memory memory{};             // the next frame loop's memory (seed_memory; p.memory points here or is NULL)
+    std::vector<Tensor> memory_keep;        // ... and its tensors, kept until the next seed_memory
 
     JlmPlan(TDict t, IDict i) : tensors(std::move(t)) {
         const Tensor *ints = find(tensors, "ints");
@@ -351,6 +355,7 @@ int64_t decode_frames(const c10::intrusive_ptr<JlmModel> &model, const c10::intr
     const int rc = jlm_decode_frames(&model->m, &pl.p, &pl.lat, &pl.st, main.stream(), side_s, ev);
     pl.p.cache = nullptr;                   // (seed_cache: the window of ONE frame loop)
     pl.p.ngram = nullptr;                   // (seed_ngram: the table of ONE frame loop)
+    pl.p.memory = nullptr;                  // (seed_memory: the memory of ONE frame loop)
     if (rc == -2) return -2;
     jlm_check(rc, "jlm_decode_frames");
     return 0;
@@ -697,6 +702,44 @@ void seed_ngram(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &keys, con
 void clear_ngram(const c10::intrusive_ptr<JlmPlan> &plan) {
     plan->p.ngram = nullptr;
     plan->ngram_keep.clear();
+}
+
+// The memory of the plan's NEXT frame loop (jlm_decode_plan.memory): no launch, the plan keeps the tensors.  keys [N][H] (4-byte values,
+// the model's state-row format), key_words [N] int32; the buffers of one frame's retrieval over the plan's n_sent * beam rows: q_rows
+// [rows][H] float32, s [rows][ld_s >= K] float32, ret_words [K][rows] int32, the workspace (float32, jlm_memory_topk's) and one int32 of
+// flags.  The frame loop that follows takes the struct and clears it: a later batch starts without a memory.  Unlike seed_cache, any
+// plan will do: a left context is not needed.
+void seed_memory(const c10::intrusive_ptr<JlmPlan> &plan, const Tensor &keys, const Tensor &key_words, int64_t N, int64_t H, double theta,
+                 double lam, int64_t K, const Tensor &q_rows, const Tensor &s, const Tensor &ret_words, const Tensor &workspace,
+                 const Tensor &flags) {
+    JlmPlan &pl = *plan;
+    const int64_t rmax = (int64_t)pl.lat.n_sent * pl.lat.beam;
+    TORCH_CHECK(N >= 1 && N <= 0x7fffffff && H >= 4 && H % 4 == 0 && K >= 1 && K <= JLM_MEMORY_TOPK_MAX && rmax >= 1 && rmax <= 65535,
+                "jlm.seed_memory: N >= 1, H % 4 == 0, 1 <= K <= ", JLM_MEMORY_TOPK_MAX, ", at most 65535 rows a batch");
+    const int64_t ld_s = s.defined() ? s.numel() / rmax : 0;
+    auto on_dev = [&](const Tensor &t) { return t.defined() && t.is_cuda() && t.is_contiguous() && t.device().index() == pl.device; };
+    TORCH_CHECK(on_dev(keys) && keys.element_size() == 4 && keys.numel() >= N * H && on_dev(key_words) && is(key_words, at::kInt, N) &&
+                    on_dev(q_rows) && is(q_rows, at::kFloat, rmax * H) && on_dev(s) && is(s, at::kFloat, rmax * K) && ld_s >= K &&
+                    on_dev(ret_words) && is(ret_words, at::kInt, K * rmax) && on_dev(workspace) && is(workspace, at::kFloat, 1) &&
+                    on_dev(flags) && is(flags, at::kInt, 1),
+                "jlm.seed_memory: keys [N][H], int32 key_words [N], float32 q_rows [rows][H], s [rows][>= K], int32 ret_words [K][rows], "
+                "a float32 workspace and int32 flags [1] on the plan's device");
+    TORCH_CHECK(theta >= 0.0 && theta < 3.0e38 && lam > 0.0 && lam < 1.0 && (float)lam > 0.0f && (float)lam < 1.0f,
+                "jlm.seed_memory: theta >= 0, 0 < lam < 1");
+    pl.memory_keep = {keys, key_words, q_rows, s, ret_words, workspace, flags};
+    pl.memory.keys = keys.data_ptr(); pl.memory.key_words = ptr<const int>(key_words, "key_words");
+    pl.memory.N = (int)N; pl.memory.K = (int)K; pl.memory.theta = (float)theta; pl.memory.lam = (float)lam;
+    pl.memory.q_rows = q_rows.data_ptr(); pl.memory.s = ptr<float>(s, "s"); pl.memory.ld_s = (int)ld_s;
+    pl.memory.ret_words = ptr<int>(ret_words, "ret_words");
+    pl.memory.workspace = workspace.data_ptr(); pl.memory.workspace_bytes = (size_t)workspace.numel() * 4;
+    pl.memory.flags = ptr<int>(flags, "flags");
+    pl.p.memory = &pl.memory;
+}
+
+// seed_memory undone: a batch that failed between seed_memory and its frame loop leaves no memory behind on the plan
+void clear_memory(const c10::intrusive_ptr<JlmPlan> &plan) {
+    plan->p.memory = nullptr;
+    plan->memory_keep.clear();
 }
 
 // The predictions of an unfinished last word behind a plan's static decode (jlm_tail_predict): one launch on the current stream, which
@@ -1946,6 +1989,9 @@ TORCH_LIBRARY(jlm, m) {
     m.def("seed_ngram(__torch__.torch.classes.jlm.Plan plan, Tensor keys, Tensor vals, Tensor root_hist, int log2cap, int max_probe, int order, "
           "float lam) -> ()", seed_ngram);
     m.def("clear_ngram(__torch__.torch.classes.jlm.Plan plan) -> ()", clear_ngram);
+    m.def("seed_memory(__torch__.torch.classes.jlm.Plan plan, Tensor keys, Tensor key_words, int N, int H, float theta, float lam, int K, "
+          "Tensor(a!) q_rows, Tensor(b!) s, Tensor(c!) ret_words, Tensor(d!) workspace, Tensor(e!) flags) -> ()", seed_memory);
+    m.def("clear_memory(__torch__.torch.classes.jlm.Plan plan) -> ()", clear_memory);
     m.def("tail_predict(__torch__.torch.classes.jlm.Model model, __torch__.torch.classes.jlm.Plan plan, Tensor ids, Tensor sp_off, "
           "Tensor sp_frame, Tensor sp_lo, Tensor sp_hi, int n_out, int chunk, Tensor(a!) out_score, Tensor(b!) out_row, Tensor(c!) out_word, "
           "Tensor(d!) out_nodes, Tensor(e!) out_len, int stride) -> ()", tail_predict);

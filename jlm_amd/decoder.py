@@ -240,9 +240,32 @@ class Decoder():
             raise ValueError("compat_quirks takes no n-gram mixture (DESIGN.md section 24)")
         return ngram
 
+    def _check_memory(self, memory, context, cache, ngram, vocab_select):
+        """the ``memory=`` of a decode, checked BEFORE the context is resolved (which primes word lists on the device): a MemoryMix of
+        this model (its H and row format), without ``cache=`` / a CachedContext, ``ngram=``, ``vocab_select`` or ``compat_quirks``;
+        ValueError otherwise.  -> the MemoryMix, or None for lam = 0: the decode without a memory"""
+        from .context import CachedContext, DecodeContext
+        from .memory import _check_mix
+        _check_mix(self.model.dev, memory)
+        if isinstance(context, _Single):
+            context = context.context
+        state = context.state if isinstance(context, DecodeContext) else context
+        if cache is not None or isinstance(state, CachedContext) or ngram is not None:
+            raise ValueError("memory= beside the continuous cache or an n-gram mixture: a three-way mixture is not defined (DESIGN.md section 30)")
+        if vocab_select:
+            raise ValueError("vocab_select takes no memory (DESIGN.md section 30: the static full-vocabulary Decoder.decode only)")
+        if self.compat_quirks:
+            raise ValueError("compat_quirks takes no memory (DESIGN.md section 30)")
+        return memory if memory.lam > 0.0 else None
+
     def decode_batch(self, inputs, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-                     random_sampling=False, context=None, cache=None, ngram=None):
-        """``ngram`` (keyword): a :class:`jlm_amd.ngram.NGramMix` -- a back-off word n-gram model is mixed into every edge cost,
+                     random_sampling=False, context=None, cache=None, ngram=None, memory=None):
+        """``memory`` (keyword): a :class:`jlm_amd.memory.MemoryMix` of this model -- the mass of the k nearest entries of every
+        hypothesis's state in a memory of (hidden state, next word) pairs is mixed into every edge cost, p = (1 - lam) p_lm + lam c_r
+        (DESIGN.md section 30), with or without ``context``; lam = 0 is the decode without.  ValueError with ``cache=`` / a
+        CachedContext, ``ngram=``, ``vocab_select`` or ``compat_quirks``, for a memory of another model, and for a device batch of more
+        than 65 535 rows (``max_batch`` x beam), before anything runs.
+        ``ngram`` (keyword): a :class:`jlm_amd.ngram.NGramMix` -- a back-off word n-gram model is mixed into every edge cost,
         p = (1 - lam) p_lm + lam p_ng(w | the last words of [<eos>] + context + the path so far), with or without
         ``context``.  ValueError with ``cache=`` / a CachedContext, ``vocab_select`` or ``compat_quirks``, for anything that is not an
         NGramMix and for a table with a word id outside the model's vocabulary, before anything runs.
@@ -257,8 +280,17 @@ class Decoder():
         [<eos>] + context[i] (jlm_amd/context.py); scores are -log p(path | that history).  None, or nothing but empty entries: the
         reference's decode."""
         inputs = list(inputs)
+        if memory is not None:
+            memory = self._check_memory(memory, context, cache, ngram, vocab_select)
         if ngram is not None:
             self._check_ngram(ngram, context, cache, vocab_select)
+        mix_kw = dict(ngram=ngram) if ngram is not None else (dict(memory=memory) if memory is not None else {})
+        if memory is not None and beam_width is not None and 1 <= int(beam_width) <= self.MAX_BEAM:
+            # (the retrieval addresses a batch's rows through 16 bits; before the context is resolved, as every refusal)
+            n_sent = max((len(c) for c in self._chunks(inputs, int(beam_width))), default=0)
+            if n_sent * int(beam_width) > 65535:
+                raise ValueError("a decode under a memory takes at most 65535 rows a device batch (%d sentences x beam %d): lower "
+                                 "Decoder.max_batch" % (n_sent, int(beam_width)))
         if vocab_select:                     # (before the context is resolved: nothing is primed for a call that is refused)
             self._refuse_cache(context, "vocab_select", cache)
         if self.compat_quirks:
@@ -266,7 +298,8 @@ class Decoder():
         ctx = self._context(context, len(inputs), cache=cache)
         sel = (vocab_select, samples, top_sampling, random_sampling)
         if beam_width is None:       # the reference's unpruned search, sentence at a time on the host
-            return [self._search_on_host(x, self._host_context(ctx, i), topN, None, *sel, **self._host_ngram(ngram, ctx, i))
+            host_mem = self._host_memory(memory)              # (the memory is read back once a call)
+            return [self._search_on_host(x, self._host_context(ctx, i), topN, None, *sel, **self._host_ngram(ngram, ctx, i), **host_mem)
                     for i, x in enumerate(inputs)]
         if not 1 <= int(beam_width) <= self.MAX_BEAM:
             raise ValueError("beam_width must be 1..%d on the GPU path (or None: the unpruned host-side search)" % self.MAX_BEAM)
@@ -279,11 +312,10 @@ class Decoder():
                 raise ValueError("compat_quirks: the stale-vocabulary path of the reference takes no left context")
             return [self._decode_stale_vocab(x, topN, beam_width) for x in inputs]
         if not all(inputs):        # (an empty string / list is falsy)
-            return self._decode_subset(inputs, [i for i, x in enumerate(inputs) if len(x)], ctx, topN, beam_width, *sel,
-                                       **(dict(ngram=ngram) if ngram is not None else {}))
+            return self._decode_subset(inputs, [i for i, x in enumerate(inputs) if len(x)], ctx, topN, beam_width, *sel, **mix_kw)
         chunks = self._chunks(inputs, beam_width, reorder=not (samples and random_sampling))
         workers = 1 if (samples and random_sampling) else self.prefetch_workers
-        extra, engine_kw, left = None, lambda _none: dict(vocab=None, **(dict(ngram=ngram) if ngram is not None else {})), None
+        extra, engine_kw, left = None, lambda _none: dict(vocab=None, **mix_kw), None
         if vocab_select:
             # a chunk's word lists beside its lattice: (words, off) the engine's CSR over its sentences, lists[k] sentence k's own
             extra = lambda idx, lat: lat.static_vocab(samples, top_sampling, random_sampling, len(self.w2i))
@@ -295,28 +327,31 @@ class Decoder():
             out = self._launch_chunks(self._prepare_chunks(inputs, chunks, beam_width, workers, extra), chunks, len(inputs), ctx, topN,
                                       beam_width, "static", engine_kw, left)
         except _CellTooLarge as e:
-            return self._heavy_on_host(e.sentences, inputs, ctx, topN, beam_width, *sel, **(dict(ngram=ngram) if ngram is not None else {}))
+            return self._heavy_on_host(e.sentences, inputs, ctx, topN, beam_width, *sel, **mix_kw)
         self.perf_sen += len(inputs)
         return out
 
-    def _decode_subset(self, inputs, keep, ctx, *args, ngram=None):
+    def _decode_subset(self, inputs, keep, ctx, *args, ngram=None, memory=None):
         """decode_batch(*args) of the inputs ``keep`` alone, their context rows with them -> the whole call's result list: theirs in place,
         [(0.0, [])] everywhere else -- an empty input's: the reference's loop leaves the <eos> path alone (decoder.py:220-241)"""
         sub = self.decode_batch([inputs[i] for i in keep], *args, context=ctx.sub(keep) if ctx is not None else None,
-                                **(dict(ngram=ngram) if ngram is not None else {})) if keep else []
+                                **(dict(ngram=ngram) if ngram is not None else {}),
+                                **(dict(memory=memory) if memory is not None else {})) if keep else []
         out = [[(0.0, [])] for _ in inputs]
         for i, r in zip(keep, sub):
             out[i] = r
         return out
 
-    def _heavy_on_host(self, heavy, inputs, ctx, *args, ngram=None):
+    def _heavy_on_host(self, heavy, inputs, ctx, *args, ngram=None, memory=None):
         """The rest of a decode_batch(*args) call that met _CellTooLarge: the sentences named take the host-side search with the beam
         (_search_on_host), everything else goes through the device again -> the call's result list."""
         heavy = set(heavy)
-        out = self._decode_subset(inputs, [i for i in range(len(inputs)) if i not in heavy], ctx, *args, **(dict(ngram=ngram) if ngram is not None else {}))
+        out = self._decode_subset(inputs, [i for i in range(len(inputs)) if i not in heavy], ctx, *args,
+                                  **(dict(ngram=ngram) if ngram is not None else {}), **(dict(memory=memory) if memory is not None else {}))
         lv_last = self.lattice_vocab
+        host_mem = self._host_memory(memory)
         for i in sorted(heavy):
-            out[i] = self._search_on_host(inputs[i], self._host_context(ctx, i), *args, **self._host_ngram(ngram, ctx, i))
+            out[i] = self._search_on_host(inputs[i], self._host_context(ctx, i), *args, **self._host_ngram(ngram, ctx, i), **host_mem)
         if (len(inputs) - 1) not in heavy:
             self.lattice_vocab = lv_last      # (the reference leaves the LAST sentence's list behind)
         return out
@@ -370,11 +405,30 @@ class Decoder():
         from .generate import EOS_ID
         return dict(ngram=(ngram, ctx.tail(i) if ctx is not None else [EOS_ID]))
 
-    def _search_on_host(self, input, context, topN, beam_width, vocab_select, samples, top_sampling, random_sampling, ngram=None):
+    @staticmethod
+    def _host_memory(memory):
+        """the keywords a host-side search takes of the call's ``memory=``: none, or memory = mix(pred [rows, V], h [rows, H]) ->
+        (1 - lam) pred + lam c(h), the float64 definition over the memory read back once (memory.memory_distribution)"""
+        if memory is None:
+            return {}
+        import numpy as np
+        from .memory import memory_distribution
+        keys, words = memory.memory.numpy()
+        keys = keys.astype(np.float64)
+
+        def mix(pred, h):
+            pred = np.array(pred, dtype=np.float64)
+            for q in range(pred.shape[0]):
+                pred[q] = (1.0 - memory.lam) * pred[q] + memory.lam * memory_distribution(h[q], keys, words, memory.theta, memory.k, pred.shape[1])
+            return pred
+        return dict(memory=mix)
+
+    def _search_on_host(self, input, context, topN, beam_width, vocab_select, samples, top_sampling, random_sampling, ngram=None,
+                        memory=None):
         """one input searched on the host over LSTM_Model's numpy API: every input of a call with beam_width=None, and with the beam a
         sentence whose lattice cells the device beam step cannot hold"""
         return self._decode_unpruned(input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=beam_width,
-                                     context=context, ngram=ngram)
+                                     context=context, ngram=ngram, memory=memory)
 
     def _cand_limit(self, lat, beam_width):
         """candidates of one lattice cell the device beam step accepts for this batch shape"""
@@ -475,7 +529,7 @@ class Decoder():
         return chunks
 
     def _decode_unpruned(self, input, topN, vocab_select, samples, top_sampling, random_sampling, beam_width=None, vocab=None,
-                         context=None, ngram=None):
+                         context=None, ngram=None, memory=None):
         """Decoder.decode of the reference with ``beam_width=None`` (decoder.py:220-241), statement for statement on the
         host: every candidate survives, each frame is one ``predict_with_context`` call over all of its paths (the GPU
         kernels behind LSTM_Model's numpy API), the result is the final frame in generation order, unsorted.  Also the
@@ -483,7 +537,8 @@ class Decoder():
         [1, H] -- the primed state read back -- and word, the last of the history: what the root consumes, and from where; mix(pred, h)
         under the continuous cache: every frame's probabilities become the mixture (context.DecodeContext.host_mixer).  ``ngram``: None,
         or (an NGramMix, the last words of the history): every path keeps its last two words and its probabilities become the n-gram
-        mixture by the float64 definition (jlm_amd/ngram.py)."""
+        mixture by the float64 definition (jlm_amd/ngram.py).  ``memory``: None, or mix(pred, h) of a memory
+        (:meth:`_host_memory`): the same plug as the cache's, on every frame of every input."""
         import math
         import numpy as np
         if len(input) == 0:
@@ -532,6 +587,9 @@ class Decoder():
             (pred, _y, _t1, _t2), h2, c2 = self.model.predict_with_context([p[2] for p in cur["paths"]], hid, cel, vocab)
             if context is not None and context.mix is not None:
                 pred = context.mix(pred, h2)
+            if memory is not None:
+                assert vocab is None
+                pred = memory(pred, h2)
             if ngram is not None:
                 pred = np.array(pred, dtype=np.float64)
                 for k, hk in enumerate(cur["hist"]):
@@ -586,11 +644,12 @@ class Decoder():
             yield item
 
     def decode(self, input, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-               random_sampling=False, context=None, cache=None, ngram=None):
+               random_sampling=False, context=None, cache=None, ngram=None, memory=None):
         """``context`` (keyword): the words committed in front of ``input`` -- one sequence of word ids / lexicon strings, or a
-        ContextState of one row (see decode_batch); ``cache``, ``ngram``: decode_batch's."""
+        ContextState of one row (see decode_batch); ``cache``, ``ngram``, ``memory``: decode_batch's."""
         out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling,
-                                context=_Single(context), cache=cache, **(dict(ngram=ngram) if ngram is not None else {}))[0]
+                                context=_Single(context), cache=cache, **(dict(ngram=ngram) if ngram is not None else {}),
+                                **(dict(memory=memory) if memory is not None else {}))[0]
         if len(input):
             # the reference's shape: dict frame -> [Node] (decoder.py:79-135), what _build_lattice returns
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
@@ -606,7 +665,7 @@ class Decoder():
         """the tail starts of one input: [(s, lo, hi)] for every s in [0, len) at which vocabulary words properly extend text[s:]"""
         return index.tail_spans(text if isinstance(text, str) else "".join(text))
 
-    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None, cache=None, ngram=None):
+    def decode_predict_batch(self, inputs, topN=10, beam_width=10, context=None, cache=None, ngram=None, memory=None):
         """Conversion while the user types: every input is kana whose LAST word may be unfinished.  -> per input a pair
         (conversions, predictions).  ``conversions`` is ``decode_batch(inputs, topN, beam_width, context=context)``'s list, the very
         launches and bits.  ``predictions`` is [(score, [word, ...])], at most ``topN`` (1 .. 64), ascending: the best paths that cover
@@ -622,6 +681,8 @@ class Decoder():
             raise TypeError("%s has no decode_predict: the last word is predicted from rows normalised over the full word vocabulary "
                             "(the static Decoder)" % type(self).__name__)
         inputs = list(inputs)
+        if memory is not None:
+            raise ValueError("decode_predict takes no memory (DESIGN.md section 30: Decoder.decode only)")
         if ngram is not None:
             raise ValueError("decode_predict takes no n-gram mixture (DESIGN.md section 24: Decoder.decode only)")
         if cache is not None:
@@ -680,11 +741,11 @@ class Decoder():
         self.perf_sen += len(full)
         return out
 
-    def decode_predict(self, input, topN=10, beam_width=10, context=None, cache=None, ngram=None):
+    def decode_predict(self, input, topN=10, beam_width=10, context=None, cache=None, ngram=None, memory=None):
         """:meth:`decode_predict_batch` of one input -> (conversions, predictions); ``context`` as :meth:`decode` takes it."""
         if self.dynamic or self.char_model:
             raise TypeError("%s has no decode_predict (see Decoder.decode_predict_batch)" % type(self).__name__)
-        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context), cache=cache, ngram=ngram)[0]
+        out = self.decode_predict_batch([input], topN, beam_width, context=_Single(context), cache=cache, ngram=ngram, memory=memory)[0]
         if len(input):
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
                                     for f, nodes in enumerate(self.last_lattice.backward_lookup(0))}
@@ -694,7 +755,7 @@ class Decoder():
     # ------------------------------------------------------------------ per-segment candidate lists
     MAX_CANDIDATES = 64
 
-    def decode_candidates_batch(self, inputs, topN=10, beam_width=10, n_cand=10, lookahead=None, rank=0, context=None):
+    def decode_candidates_batch(self, inputs, topN=10, beam_width=10, n_cand=10, lookahead=None, rank=0, context=None, memory=None):
         """The window an input method shows: per input a pair (conversions, segments).  ``conversions`` is
         ``decode_batch(inputs, topN, beam_width, context=context)``'s list, the very chunks, launches and bits.  ``segments`` cuts
         path ``rank`` of it into its words: [(start, length, [(score, word), ...]), ...] in path order, where a segment's list holds the
@@ -713,6 +774,8 @@ class Decoder():
             raise TypeError("%s has no decode_candidates: a segment's alternatives are scored on rows normalised over the full word "
                             "vocabulary (the static Decoder)" % type(self).__name__)
         inputs = list(inputs)
+        if memory is not None:
+            raise ValueError("decode_candidates takes no memory (DESIGN.md section 30: Decoder.decode only)")
         self._refuse_cache(context, "decode_candidates")
         from .context import CachedContext, DecodeContext
         state = context.context if isinstance(context, _Single) else context
@@ -788,11 +851,11 @@ class Decoder():
         self.perf_sen += len(full)
         return out
 
-    def decode_candidates(self, input, topN=10, beam_width=10, n_cand=10, lookahead=None, rank=0, context=None):
+    def decode_candidates(self, input, topN=10, beam_width=10, n_cand=10, lookahead=None, rank=0, context=None, memory=None):
         """:meth:`decode_candidates_batch` of one input -> (conversions, segments); ``context`` as :meth:`decode` takes it."""
         if self.dynamic or self.char_model:
             raise TypeError("%s has no decode_candidates (see Decoder.decode_candidates_batch)" % type(self).__name__)
-        out = self.decode_candidates_batch([input], topN, beam_width, n_cand, lookahead, rank, context=_Single(context))[0]
+        out = self.decode_candidates_batch([input], topN, beam_width, n_cand, lookahead, rank, context=_Single(context), memory=memory)[0]
         if len(input):
             self.backward_lookup = {f: [Node(st, ln, w, word) for (st, ln, w, word) in nodes]
                                     for f, nodes in enumerate(self.last_lattice.backward_lookup(0))}

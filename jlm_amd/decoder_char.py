@@ -149,13 +149,16 @@ class CharRNNDecoder(Decoder):
 
     # ---------------------------------------------------------------- search
     def decode(self, input, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False, random_sampling=False, cache=None,
-               ngram=None):
-        out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling, cache=cache, ngram=ngram)[0]
+               ngram=None, memory=None):
+        out = self.decode_batch([input], topN, beam_width, vocab_select, samples, top_sampling, random_sampling, cache=cache, ngram=ngram,
+                                memory=memory)[0]
         self.backward_lookup = {f: [Node(s, l, w, word) for (s, l, w, word) in nodes] for f, nodes in enumerate(self._last_ends)}
         return out
 
     def decode_batch(self, inputs, topN=10, beam_width=10, vocab_select=False, samples=0, top_sampling=False,
-                     random_sampling=False, cache=None, ngram=None):
+                     random_sampling=False, cache=None, ngram=None, memory=None):
+        if memory is not None:
+            raise ValueError("the character decoder takes no memory: its softmax is not over words")
         if ngram is not None:
             raise ValueError("the character decoder takes no n-gram mixture: its softmax is not over words")
         if cache is not None:

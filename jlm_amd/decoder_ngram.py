@@ -47,7 +47,9 @@ class NGramDecoder():
         return frames
 
     def decode(self, input, topN=10, beam_width=10, use_oov=False, vocab_select=False, samples=0, top_sampling=False,
-               random_sampling=False, cache=None, ngram=None):
+               random_sampling=False, cache=None, ngram=None, memory=None):
+        if memory is not None:
+            raise ValueError("the n-gram decoder takes no memory: it has no hidden states to query one")
         if ngram is not None:
             raise ValueError("the n-gram decoder takes no n-gram mixture: it is the n-gram model alone")
         if cache is not None:

@@ -154,6 +154,8 @@ class _Plan:
         self.ctx_prev = self.ctx_word = self.ctx_idx = self.ctx_idx_host = self.ctx_state = None
         self.cache_bufs = None               # decodes under the continuous cache: their score scratch (_CacheBufs), made on first use
         self.ngram_bufs = None               # decodes under an n-gram mixture: the batch's root histories (_NgramBufs), made on first use
+        self.memory_bufs = None              # decodes under a memory: one frame's retrieval buffers (_MemoryBufs), made on first use
+        self.memory_live = False             # the batch in flight runs under a memory: collect reads the retrieval's flag word
         if ctx:
             self.ctx_prev, self.ctx_word = torch.full((rmax,), -1, device=dev, dtype=i32), torch.zeros(rmax, device=dev, dtype=i32)
             self.ctx_idx, self.ctx_idx_host = torch.zeros(B, device=dev, dtype=i32), pin(torch.zeros(B, dtype=i32))
@@ -218,6 +220,41 @@ class _NgramBufs:
         self.host = torch.zeros((n_sent, 2), dtype=torch.int32)
         if eng.device.type == "cuda":
             self.host = self.host.pin_memory()
+
+
+class _MemoryBufs:
+    """The buffers of one frame's retrieval for a plan's decodes under a memory (jlm_decode_memory): the gathered query rows q_rows
+    [rmax, H], the scores s [rmax, K], ret_words [K, rmax], jlm_memory_topk's workspace -- one chunk when the scores of the whole memory
+    fit memory.TOPK_SCORE_BYTES (RetrievalBuffers' rule) -- and the retrieval's own flag word with its page-locked copy.  Kept on the plan
+    and reused while (N, K) and the chunk stay; all zeroed, none uninitialised."""
+
+    def __init__(self, eng, rmax, N, K):
+        torch, dev = eng.torch, eng.device
+        self.key = (int(N), int(K), self.CHUNK_KEYS)
+        self.q_rows = torch.zeros((rmax, eng.m.H), device=dev, dtype=torch.float32)
+        self.s = torch.zeros((rmax, K), device=dev, dtype=torch.float32)
+        self.ret_words = torch.full((K, rmax), -1, device=dev, dtype=torch.int32)
+        self.workspace = torch.zeros(max(self.workspace_floats(N, rmax, K), 4), device=dev, dtype=torch.float32)
+        self.flags = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.h_flags = torch.zeros(1, dtype=torch.int32)
+        if dev.type == "cuda":
+            self.h_flags = self.h_flags.pin_memory()
+
+    CHUNK_KEYS = None        # keys per chunk of the retrieval (None: RetrievalBuffers' rule; tests cut the workspace to chunks of 32)
+
+    @classmethod
+    def workspace_floats(cls, N, rmax, K):
+        from .memory import RetrievalBuffers
+        chunk = RetrievalBuffers.chunk_keys(N, rmax) if cls.CHUNK_KEYS is None else int(cls.CHUNK_KEYS)
+        return rmax * (chunk + 2 * K)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.q_rows, self.s, self.ret_words, self.workspace, self.flags))
+
+    @staticmethod
+    def fit(have, eng, rmax, N, K):
+        return have if have is not None and have.key == (int(N), int(K), _MemoryBufs.CHUNK_KEYS) else _MemoryBufs(eng, rmax, N, K)
 
 
 class DecodeEngine:
@@ -323,7 +360,8 @@ class DecodeEngine:
                 table._dev[key] = (torch.from_numpy(arr["keys"].view(np.int64)).to(self.device), torch.from_numpy(arr["vals"]).to(self.device), arr)
         return table._dev[key]
 
-    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None, predict=None, ngram=None):
+    def submit(self, lat, kind="static", vocab=None, dyn_lists=None, topN=10, timing=False, context=None, predict=None, ngram=None,
+               memory=None):
         """Enqueue one batch (upload, the frame-loop op, asynchronous read-back) and return a
         ticket for :meth:`collect`.  Nothing here waits for the GPU.  Successive calls use
         alternating streams (see __init__); every ticket owns its plan's buffers until collected.
@@ -341,11 +379,15 @@ class DecodeEngine:
         (conversions, predictions) pairs (static full-vocabulary decodes only).
         ngram: None, or a jlm_amd.ngram.NGramMix: the back-off n-gram model is mixed into every edge cost (``torch.ops.jlm.seed_ngram``:
         no launch; one more launch per frame, csrc/jlm_ngram_edge.hip).  Static full-vocabulary decodes only and
-        not under the continuous cache: ValueError otherwise."""
+        not under the continuous cache: ValueError otherwise.
+        memory: None, or a jlm_amd.memory.MemoryMix of this model with lam > 0: the mass of every row's K nearest entries is mixed into
+        every edge cost (``torch.ops.jlm.seed_memory``: no launch; per frame a gather, jlm_memory_topk and a patch,
+        csrc/jlm_memory_edge.hip), with or without ``context``.  Static full-vocabulary decodes of at most 65 535
+        rows only, and not beside the continuous cache or an n-gram mixture: ValueError otherwise."""
         torch = self.torch
         with self._submit_lock, self._ctx():          # (the plan list and the stream rotation are shared by every submitting thread)
             if self.device.type != "cuda" or self.n_streams < 2 or (timing and timing != "inflight"):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict, ngram)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict, ngram, memory)
             if len(self._streams) != self.n_streams:
                 # the launch streams are shared by every engine on the device: each also gets a side stream inside the op, and
                 # streams beyond the GPU's hardware queues (GPU_MAX_HW_QUEUES, jlm_amd/__init__.py) serialise one another --
@@ -360,9 +402,9 @@ class DecodeEngine:
             if not cur.query():                                  # after whatever the caller queued (weight uploads, ...);
                 strm.wait_stream(cur)                            # nothing pending there in the steady state: no event, no wait
             with torch.cuda.stream(strm):
-                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict, ngram)
+                return self._submit(lat, kind, vocab, dyn_lists, topN, timing, context, predict, ngram, memory)
 
-    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None, predict=None, ngram=None):
+    def _submit(self, lat, kind, vocab, dyn_lists, topN, timing, context=None, predict=None, ngram=None, memory=None):
         torch = self.torch
         dynamic = kind == "dynamic"
         vmode = "dynamic" if dynamic else ("select" if vocab is not None else "full")
@@ -396,6 +438,17 @@ class DecodeEngine:
                 raise ValueError("an n-gram mixture runs inside the static full-vocabulary decode only")
             if cached:
                 raise ValueError("an n-gram mixture and the continuous cache in one decode: a three-way mixture is not defined")
+        if memory is not None:
+            from .memory import _check_mix
+            _check_mix(self.m, memory)
+            if not memory.lam > 0.0:
+                raise ValueError("memory: lam = 0 is the decode without a memory (pass memory=None)")
+            if dynamic or vocab is not None or predict is not None:
+                raise ValueError("a memory runs inside the static full-vocabulary decode only")
+            if cached or ngram is not None:
+                raise ValueError("a memory beside the continuous cache or an n-gram mixture: a three-way mixture is not defined")
+            if lat.n_sent * lat.beam > 65535:
+                raise ValueError("a decode under a memory takes at most 65535 rows a batch (n_sent x beam = %d x %d)" % (lat.n_sent, lat.beam))
         if predict is not None:
             if dynamic or vocab is not None:
                 raise ValueError("predict: the last word is predicted behind a static full-vocabulary decode only")
@@ -415,6 +468,7 @@ class DecodeEngine:
             need["spans"] = int(sp[1].shape[0])
         p = self._plan_for(kind, vmode, lat, need, size_class, perm, ctx=context is not None, n_pred=n_pred if predict is not None else 0)
         p.busy = True
+        p.memory_live = memory is not None
         try:
             if context is not None:
                 # the primed rows of this batch's sentences -> rows G + s of the plan's pool, prev / word of the root rows: one launch
@@ -439,7 +493,19 @@ class DecodeEngine:
                 keys, vals, arr = self.ngram_tensors(ngram.table)
                 ops.backend().seed_ngram(p.obj, keys, vals, nb.root_hist, int(arr["log2cap"]), int(arr["max_probe"]), int(ngram.table.order),
                                          float(ngram.lam))
+            if memory is not None:
+                # the memory and one frame's retrieval buffers for this frame loop (jlm_decode_plan.memory): no launch, no upload
+                mem = memory.memory
+                p.memory_bufs = mb = _MemoryBufs.fit(p.memory_bufs, self, p.rmax, mem.N, memory.k)
+                mb.flags.zero_()
+                ops.backend().seed_memory(p.obj, mem.keys, mem.words, int(mem.N), int(self.m.H), float(memory.theta), float(memory.lam),
+                                          int(memory.k), mb.q_rows, mb.s, mb.ret_words, mb.workspace, mb.flags)
             done = self._enqueue(p, lat, vocab, dyn_lists, dynamic, perm, max_words, topN, timing)
+            if memory is not None:
+                mb.h_flags.copy_(mb.flags, non_blocking=True)
+                if self.device.type == "cuda":
+                    done = torch.cuda.Event(blocking=self.blocking_sync)
+                    done.record()
             if predict is not None:
                 done = self._enqueue_predict(p, sp, predict[1], n_pred)
         except BaseException:
@@ -447,6 +513,8 @@ class DecodeEngine:
                 ops.backend().clear_cache(p.obj)      # (the window was for this batch's frame loop, which may not have run)
             if ngram is not None:
                 ops.backend().clear_ngram(p.obj)
+            if memory is not None:
+                ops.backend().clear_memory(p.obj)
             # nothing may keep the plan: launches already enqueued finish first, then its buffers are free again
             if self.device.type == "cuda":
                 try:
@@ -580,6 +648,10 @@ class DecodeEngine:
                     self.last_n_live = p.h_nlive.numpy()[:lat.n_frames].copy()
         self.last_state = p
         p.ctx_state = None
+        if p.memory_live and int(p.memory_bufs.h_flags[0]) != 0:
+            p.busy = False
+            from .memory import _flag_error
+            raise _flag_error(int(p.memory_bufs.h_flags[0]))
         if int(p.h_len[-1]) != 0:
             # (ABI 11) the beam step met a log-normaliser that is not finite: a row's sum of 2^y overflowed (or vanished) in the fixed-reference
             # normaliser -- an overflowed row's hypotheses would score -inf and be pruned, leaving a plausible but wrong n-best

@@ -68,6 +68,12 @@ def build_parser():
     parser.add_argument("--candidates", type=int, default=argparse.SUPPRESS,
                         help="for sentences whose best conversion has the gold segmentation but a wrong string: where the gold word "
                              "stands in each wrong segment's list of N candidates (Decoder.decode_candidates)")
+    parser.add_argument("--memory", default=argparse.SUPPRESS,
+                        help="decode the set a second time under the memory of hidden states saved in this .npz (python -m jlm_amd.memory; "
+                             "Decoder.decode(memory=)) and log both summaries")
+    parser.add_argument("--mem-theta", dest="mem_theta", type=float, default=argparse.SUPPRESS, help="--memory: theta (default 0.3)")
+    parser.add_argument("--mem-lam", dest="mem_lam", type=float, default=argparse.SUPPRESS, help="--memory: the memory's weight lambda (default 0.1)")
+    parser.add_argument("--mem-k", dest="mem_k", type=int, default=argparse.SUPPRESS, help="--memory: the nearest entries that vote (default 64)")
     return parser
 
 
@@ -117,11 +123,20 @@ class Evaluator:
                              "--cache and --ngram_mix")
         if self.candidates > 64:
             raise ValueError("--candidates: at most 64 words per segment")
+        self.memory_mix = None           # --memory MEM.npz: the MemoryMix of the second pass (loaded behind the decoder, below)
+        if getattr(args, "memory", None) and (args.use_ngram or self.config['char_rnn'] or args.dynamic_decoding or args.vocab_select or
+                                              self.cut_last or self.candidates or self.cache is not None or self.ngram_mix is not None):
+            raise ValueError("--memory needs the static decoder over the full vocabulary, without --cache, --ngram_mix, --cut_last and "
+                             "--candidates")
         self.contexts = None             # with --context_words: every loaded sentence's context tokens (load_eval_set)
         self.gold = None                 # with --candidates: every loaded sentence's gold tokens (load_eval_set)
         self.decoder = self._make_decoder()
         if hasattr(self.decoder, "perf_timing"):
             self.decoder.perf_timing = True       # the log's per-step times (eval.py:104-121) need the per-frame events
+        if getattr(args, "memory", None):
+            from .memory import Memory, MemoryMix
+            self.memory_mix = MemoryMix(Memory.load(self.decoder.model, args.memory), theta=float(getattr(args, "mem_theta", 0.3)),
+                                        lam=float(getattr(args, "mem_lam", 0.1)), k=int(getattr(args, "mem_k", 64)))
 
     def _make_decoder(self):
         a = self.args                 # selection order of eval.py:41-48
@@ -152,9 +167,11 @@ class Evaluator:
             name = name[:-len(".txt")] + "_ngmix_{}.txt".format(self.ngram_mix.table.order)
         if getattr(self, "candidates", 0):
             name = name[:-len(".txt")] + "_cand_{}.txt".format(self.candidates)
+        if getattr(self, "memory_mix", None) is not None:
+            name = name[:-len(".txt")] + "_memory.txt"
         return name
 
-    def _decode_all(self, inputs, cache=None, ngram=None):
+    def _decode_all(self, inputs, cache=None, ngram=None, memory=None):
         a = self.args
         kw = dict(beam_width=a.beam_size, vocab_select=a.vocab_select, samples=a.samples,
                   top_sampling=a.top_sampling, random_sampling=a.random_sampling)
@@ -162,6 +179,8 @@ class Evaluator:
             kw["cache"] = cache
         if ngram is not None:
             kw["ngram"] = ngram
+        if memory is not None:
+            kw["memory"] = memory
         step = max(1, a.batch)
         ctx = self.contexts if self.context_words else None
         if step == 1:                 # sentence at a time, as the reference does
@@ -296,13 +315,14 @@ class Evaluator:
                 print("--- %s seconds per step for vocab fix.---" % fix(d.perf_log_fix_vocab))
                 print("--- %s seconds per step for lattice path fix.---" % fix(d.perf_log_fix_lattice_path_prob))
             print("--- %s seconds ---" % (time.time() - t_start))
-            mix = getattr(self, "ngram_mix", None)
-            if self.cache is not None or mix is not None:
-                # the same set once more under the cache (or the n-gram mixture): its verdicts and its summary line behind the first pass's
+            mix, mem = getattr(self, "ngram_mix", None), getattr(self, "memory_mix", None)
+            if self.cache is not None or mix is not None or mem is not None:
+                # the same set once more under the cache (or the n-gram mixture, or the memory): its verdicts and its summary line behind
+                # the first pass's
                 hits = {"best hit": 0, "nbest hit": 0, "no hit": 0}
                 t_start = time.time()
                 log.write('\n')
-                for x, y, nb in zip(inputs, targets, self._decode_all(inputs, cache=self.cache, ngram=mix)):
+                for x, y, nb in zip(inputs, targets, self._decode_all(inputs, cache=self.cache, ngram=mix, memory=mem)):
                     sentences = [''.join(_surface(w) for w in words) for _score, words in nb]
                     verdict = "best hit" if y == sentences[0] else ("nbest hit" if y in sentences else "no hit")
                     hits[verdict] += 1
@@ -310,7 +330,8 @@ class Evaluator:
                     log.write('{}\t{}\n'.format(y, x))
                     log.writelines(s + '\n' for s in sentences)
                 head = ('cache {} theta {} lam {}'.format(self.cache.size, self.cache.theta, self.cache.lam) if self.cache is not None
-                        else 'ngram_mix order {} lam {}'.format(mix.table.order, mix.lam))
+                        else 'ngram_mix order {} lam {}'.format(mix.table.order, mix.lam) if mix is not None
+                        else 'memory {} theta {} lam {} k {}'.format(mem.memory.N, mem.theta, mem.lam, mem.k))
                 summary = '{} best_hit {} nbest_hit{} no_hit {} eval_size {}'.format(
                     head, hits["best hit"], hits["nbest hit"], a.eval_size - hits["best hit"] - hits["nbest hit"], a.eval_size)
                 log.write(summary)

@@ -19,7 +19,9 @@ def shard_indices(lengths, rank, world):
 def decode_sharded(decoder, sentences, rank, world, **decode_kwargs):
     """-> (indices, results) for this rank's shard.  ValueError for a decode under the continuous cache (``cache=``, a CachedContext):
     a primed context holds one row per sentence of the whole call, not of a shard; and for ``ngram=`` (the
-    sharded decode is outside the n-gram mixture)."""
+    sharded decode is outside the n-gram mixture) and for ``memory=``."""
+    if decode_kwargs.get("memory") is not None:
+        raise ValueError("decode_sharded takes no memory (DESIGN.md section 30)")
     if decode_kwargs.get("ngram") is not None:
         raise ValueError("decode_sharded takes no n-gram mixture (DESIGN.md section 24)")
     from .context import CachedContext
